@@ -9,11 +9,18 @@ collisions (weak scaling: UAVs are independent, no data-path collective).  For N
 sub-record: BASELINE configs[4], 1 000 000 UAVs with mutual collisions sharded over the N ranks, the collision exchange over RCCL.
 Rank 0 prints ONE JSON line.
 
-Timing: W warm-up steps, then regions of EXACTLY K steps, each bracketed by barrier + synchronize on both sides, repeated until 50 ms
-have been measured.  `ms_per_step` / `value` = the median region by the WALL clock (time.perf_counter() between the two brackets,
-MAX over ranks) — SURVEY §8d's definition; one region of the driver's K = 20 lasts 0.2 ms, a fifth of it host start-up and synchronize
-latency, and that is included.  The DEVICE time of the same regions (hipEvents on the swarm's streams: before the first launch, after
-the last launch of each stream) is in the line too (`device_ms_per_step`, `value_device_time`) and is what `roofline` is computed from.
+Timing: W warm-up steps, then ONE region of EXACTLY K timed steps, bracketed by barrier + synchronize on both sides.  `ms_per_step` /
+`value` = that region by the WALL clock (time.perf_counter() between the two brackets, MAX over ranks) / K — SURVEY §8d's definition;
+host start-up and synchronize latency of the region are included (at K = 20 a region lasts 0.2 ms, a fifth of it that latency; choose
+K from ms_per_step so that the region lasts long enough).  The DEVICE time of the same region (hipEvents on the swarm's streams: before
+the first launch, after the last launch of each stream) is in the line too (`device_ms_per_step`, `value_device_time`) and is what
+`roofline` is computed from.  The sub-records (extra workloads, config-5 leg) keep their own step counts and repeat regions until
+--min-measure-ms have been timed.
+
+--dump-outputs DIR: after the timed region, the state the headline path left (what Swarm.get_state hands a caller: x, v, v_prev, R,
+omega, motor_rpm; external_force too for a collision workload) of rank 0's UAVs is written as DIR/<name>.npy (float64).  Inputs are
+seeded and the step count is W + K, so two builds run with the same arguments can be compared array for array.  Above 64 MB in all a
+fixed, seeded sample of UAVs is written, and its indices as DIR/uav_index.npy.
 """
 import argparse
 import json
@@ -67,10 +74,11 @@ COLLISION_BYTES = {"list_tick_per_uav": 28, "list_tick_per_uav_with_partner": 15
 # What the fields of the line mean and how they are measured.  NOT printed in the line (the driver keeps the last 8 KB of stdout: the
 # line must hold every number, so the prose lives here, in DESIGN.md §6 and behind `python bench.py --explain`).
 NOTES = {
-    "timing": "regions of exactly K steps, each bracketed by barrier + synchronize on both sides, in two passes: by time.perf_counter() "
-              "(ms_per_step / value: wall clock, host start-up and synchronize latency of the region included, MAX over ranks, median over "
-              "`regions` regions) and with a hipEvent pair around the region's launches (device_ms_per_step / value_device_time: what the "
-              "roofline is computed from)",
+    "timing": "headline: W warm-up steps, then one region of exactly K steps, bracketed by barrier + synchronize on both sides, timed by "
+              "time.perf_counter() (ms_per_step / value: wall clock, host start-up and synchronize latency of the region included, MAX over "
+              "ranks) and by a hipEvent pair around the region's launches (device_ms_per_step / value_device_time: what the roofline is "
+              "computed from).  Sub-records: regions of their own step counts, repeated until --min-measure-ms, in two passes (wall clock "
+              "without events, device time with them), medians over `regions` regions",
     "roofline": "hipEvents around each timed region: one before the first launch, one per stream after its last launch (the later of the two "
                 "ends the region; joining the streams afterwards is bookkeeping): elapsed / steps, inter-launch gaps included, median over the "
                 "regions; with two concurrent half-swarm launches per step `achieved` is the bytes of both over that time.  `achieved` prices "
@@ -189,7 +197,9 @@ def parse():
     ap.add_argument("--substeps", type=int, default=1, help="makeStep rounds fused per launch (state kept in registers)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg (rank 0, N=1 only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--min-measure-ms", type=float, default=50.0, help="regions of --steps steps are repeated until this much was timed")
+    ap.add_argument("--min-measure-ms", type=float, default=50.0, help="sub-records and the config-5 leg: regions are repeated until this much was timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the headline path computed (rank 0's UAVs) as DIR/<name>.npy")
     ap.add_argument("--config5", choices=["auto", "on", "off"], default="auto",
                     help="the 1 000 000-UAV collision leg (BASELINE configs[4]); auto = at every N for the default workload (one rank: the same "
                          "path on a one-rank communicator — the figure the N-rank value is divided by)")
@@ -430,9 +440,27 @@ def mean_search_candidates(x, inv_cell):
     return float(total.mean() - 1.0)  # (minus the UAV itself)
 
 
-def step_leg(args, R, n, workload, steps, warmup, traffic=(None, "not requested"), min_ms=None, seed=3, airframe="x500", arith=None, substeps=None):
-    """One timed workload on this rank's GPU: `n` UAVs of one airframe, regions of exactly `steps` steps (ticks).  Returns (record, st,
-    cmd); the record is built on rank 0 only."""
+def dump_state(sw, n, coll, out_dir, limit_bytes=64 * 10 ** 6):
+    """What the timed path computed, as a caller of it receives it (Swarm.get_state, plus the collision forces), written as
+    out_dir/<name>.npy in float64; above limit_bytes a fixed, seeded sample of UAVs (indices in uav_index.npy)."""
+    st = sw.get_state(0, n)
+    if coll:
+        st["external_force"] = sw.get_external_force(0, n)
+    row_bytes = sum(a[0].nbytes for a in st.values())
+    if n * row_bytes > limit_bytes:
+        keep = np.sort(np.random.default_rng(0).choice(n, limit_bytes // (row_bytes + 8), replace=False))
+        st = {k: a[keep] for k, a in st.items()}
+        st["uav_index"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in st.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def step_leg(args, R, n, workload, steps, warmup, traffic=(None, "not requested"), min_ms=None, seed=3, airframe="x500", arith=None, substeps=None,
+             headline=False):
+    """One timed workload on this rank's GPU: `n` UAVs of one airframe.  The headline (headline=True): one region of exactly `steps`
+    steps (ticks), wall clock and device events together, then --dump-outputs; every other leg: regions of exactly `steps` steps
+    until min_ms were timed.  Returns (record, st, cmd); the record is built on rank 0 only."""
     import mrs_multirotor_simulator_amd as M
     from mrs_multirotor_simulator_amd import airframes
     torch = R.torch
@@ -464,13 +492,20 @@ def step_leg(args, R, n, workload, steps, warmup, traffic=(None, "not requested"
         run(steps)
         sync_local()
         return None, st, cmd
-    # two passes over regions of exactly `steps` steps: with the library's hipEvent pair around each region (device time: roofline), and
-    # without it (wall clock: `value` — the events, and the synchronisation that reads them, are measurement, not workload)
+    # the headline: ONE region of exactly `steps` steps (--steps is the number of timed steps), wall clock and the library's hipEvent pair
+    # together (one pair per region: its cost is two event records).  Every other leg: two passes over regions of exactly `steps` steps,
+    # with the hipEvent pair around each region (device time: roofline), and without it (wall clock: `value`)
     budget = args.min_measure_ms if min_ms is None else min_ms
     sw.set_profiling(1)  # one hipEvent pair around every step_n / tick_n call, on the swarm's stream
-    _, ev = timed_regions(R, run, sync_local, steps, warmup, budget / 2, after_region=sw.last_step_kernel_ms)
-    sw.set_profiling(0)
-    times, _ = timed_regions(R, run, sync_local, steps, 0, budget / 2)
+    if headline:  # exactly `steps` timed steps: one region, its wall clock and its events
+        times, ev = timed_regions(R, run, sync_local, steps, warmup, 0.0, after_region=sw.last_step_kernel_ms)
+        sw.set_profiling(0)
+        if args.dump_outputs and R.rank == 0:
+            dump_state(sw, n, coll, args.dump_outputs)
+    else:
+        _, ev = timed_regions(R, run, sync_local, steps, warmup, budget / 2, after_region=sw.last_step_kernel_ms)
+        sw.set_profiling(0)
+        times, _ = timed_regions(R, run, sync_local, steps, 0, budget / 2)
     x_end = sw.get_state(0, n)["x"] if coll else sw.get_state(0, 64)["x"]
     assert np.all(np.isfinite(x_end[:64]))
     kern_ms = float(np.median([e[0] for e in ev]))
@@ -876,7 +911,8 @@ def main():
     R = Ranks()
     if R.world != args.gpus:
         raise SystemExit(f"bench.py --gpus {args.gpus} but the launcher started {R.world} rank(s)")
-    out, st, cmd = step_leg(args, R, args.uavs, args.workload, args.steps, args.warmup, traffic=live.get((args.uavs, args.workload), no_traffic))
+    out, st, cmd = step_leg(args, R, args.uavs, args.workload, args.steps, args.warmup, traffic=live.get((args.uavs, args.workload), no_traffic),
+                            headline=True)
     if args.pmc_child:
         R.close()
         return

@@ -9,6 +9,11 @@
   include/mrs_multirotor_simulator/uav_system/controllers/pid.hpp (the one controller header that needs neither Eigen nor Boost),
   compiled unmodified into oracle/_ref/libref_pid.so and driven with seeded (error, dt) sequences; parameters, stimulus and the
   outputs of update() are stored.
+* reference_kdtree_scenarios.npz — OUTPUT OF THE REFERENCE'S OWN CODE: the same kd-tree on the point clouds of
+  tests/test_collisions_ref.py and the two collision scenarios of tests/test_parity_gpu.py; points and CSR neighbour lists in the
+  order the radius search returns them (helpers.reference_kdtree reads them).
+* pid_reference_vectors_4242.npz — OUTPUT OF THE REFERENCE'S OWN CODE: the PIDController above on a second stimulus set
+  (pid_sequences(seed=4242, n_seq=40, n_steps=120)).
 * oracle_trajectories.npz — regression vectors of the CPU oracle (NOT reference outputs: the reference's dynamics cannot be
   built here) for BASELINE config 1 and a 64-UAV mixed-mode swarm; they freeze the oracle so that a later
   edit of oracle/uav_oracle.c cannot silently move the parity target.
@@ -45,6 +50,23 @@ def nanoflann_sets():
             d2[off[i]:off[i + 1]] = d2[off[i]:off[i + 1]][o]
         out[f"{name}_points"], out[f"{name}_offsets"], out[f"{name}_indices"], out[f"{name}_d2"] = pts, off, idx, d2
     np.savez_compressed(os.path.join(HERE, "nanoflann_radius_sets.npz"), **out)
+
+
+def kdtree_scenarios():
+    assert O.ref_lib() is not None, "oracle/_ref must be built from the reference tree (oracle/Makefile)"
+    import re
+    import test_collisions_ref
+    import test_parity_gpu
+    scenarios = {"probe": np.stack(np.meshgrid(np.arange(5) * 1.2, np.arange(5) * 1.2, [0.0], indexing="ij"), -1).reshape(-1, 3)}
+    scenarios.update(test_collisions_ref.clouds())
+    scenarios["close pairs"] = test_parity_gpu.close_pairs_cloud()
+    scenarios["five UAV clusters"] = test_parity_gpu.five_uav_clusters()
+    out = {}
+    for name, pts in scenarios.items():
+        key = re.sub(r"[^0-9A-Za-z]+", "_", name)
+        off, idx, d2 = O.ref_radius_neighbours(pts, 3.0, 10)
+        out[f"{key}_points"], out[f"{key}_offsets"], out[f"{key}_indices"], out[f"{key}_d2"] = pts, off, idx, d2
+    np.savez_compressed(os.path.join(HERE, "reference_kdtree_scenarios.npz"), **out)
 
 
 def oracle_trajectories():
@@ -217,10 +239,31 @@ def pid_reference():
     print("pid_reference_vectors.npz:", out.shape, "outputs,", int(np.isnan(out).sum()), "NaN")
 
 
+def pid_reference_4242():
+    L = O.ref_pid_lib()
+    assert L is not None, "oracle/_ref/libref_pid.so must be built from the reference tree (oracle/Makefile)"
+    params, err, dt, event, new_sat = pid_sequences(seed=4242, n_seq=40, n_steps=120)
+    out = np.zeros_like(err)
+    for q in range(len(params)):
+        h = L.ref_pid_create()
+        L.ref_pid_set_params(h, *params[q])
+        for k in range(err.shape[1]):
+            if event[q, k] == 1:
+                L.ref_pid_reset(h)
+            elif event[q, k] == 2:
+                L.ref_pid_set_saturation(h, new_sat[q, k])
+            out[q, k] = L.ref_pid_update(h, err[q, k], dt[q, k])
+        L.ref_pid_destroy(h)
+    np.savez_compressed(os.path.join(HERE, "pid_reference_vectors_4242.npz"), params=params, err=err, dt=dt, event=event, new_sat=new_sat,
+                        out=out)
+
+
 if __name__ == "__main__":
     nanoflann_sets()
     oracle_trajectories()
     all_modes()
     pid_reference()
+    kdtree_scenarios()
+    pid_reference_4242()
     for f in sorted(os.listdir(HERE)):
         print(f, os.path.getsize(os.path.join(HERE, f)))

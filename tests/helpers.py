@@ -1,5 +1,8 @@
 """Shared scenario builders for the parity tests: the same calls are issued to the CPU oracle
 (oracle/oracle_swarm.py — test infrastructure) and to the product (mrs_multirotor_simulator_amd.Swarm)."""
+import os
+import re
+
 import numpy as np
 
 from mrs_multirotor_simulator_amd import airframes
@@ -20,6 +23,21 @@ def oracle_params(name, **kw):
     O.lib().orc_calculate_inertia(p)
     O.lib().orc_scale_allocation(p)
     return p
+
+
+def reference_kdtree(name, pos):
+    """The reference's own kd-tree (nanoflann, squared radius 3.0, leaf size 10) on the stored scenario `name`: (offsets, idx, d2)
+    in the order its radius search hands the neighbours out, from tests/golden/reference_kdtree_scenarios.npz
+    (tests/golden/make_golden.py:kdtree_scenarios).  The stored points must be `pos` bit for bit; where oracle/_ref is built, the
+    library itself must still return the stored lists."""
+    key = re.sub(r"[^0-9A-Za-z]+", "_", name)
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_kdtree_scenarios.npz"))
+    assert np.array_equal(g[f"{key}_points"], pos), f"{name}: the stored scenario no longer matches the test's points"
+    off, idx, d2 = g[f"{key}_offsets"], g[f"{key}_indices"], g[f"{key}_d2"]
+    if O.ref_lib() is not None:
+        lo, li, ld = O.ref_radius_neighbours(pos, 3.0, 10)
+        assert np.array_equal(lo, off) and np.array_equal(li, idx) and np.array_equal(ld, d2), f"{name}: live kd-tree != stored lists"
+    return off, idx, d2
 
 
 def to_product_params(M, p):

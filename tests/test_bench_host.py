@@ -96,3 +96,35 @@ def test_explain_prints_the_notes_without_a_gpu():
     import json
     notes = json.loads(r.stdout)
     assert r.returncode == 0 and {"timing", "roofline", "roofline_collision", "sub_records", "rehearsal"} <= set(notes)
+
+
+def test_dump_state_writes_float64_arrays_and_samples_above_the_limit(tmp_path):
+    """bench.py --dump-outputs: every array as <name>.npy in float64; above the byte limit a fixed, seeded sample of UAVs with its
+    indices (uav_index.npy), the same sample on every run"""
+    import numpy as np
+    import bench
+
+    class FakeSwarm:
+        def get_state(self, first, count):
+            i = np.arange(first, first + count, dtype=np.float64)
+            return {"x": np.stack([i, i + 0.5, i + 0.25], axis=1), "R": np.repeat(i, 9).reshape(count, 3, 3)}
+
+        def get_external_force(self, first, count):
+            return -self.get_state(first, count)["x"]
+
+    bench.dump_state(FakeSwarm(), 100, False, str(tmp_path / "all"))
+    got = {f.stem: np.load(f) for f in (tmp_path / "all").glob("*.npy")}
+    assert set(got) == {"x", "R"} and got["R"].shape == (100, 3, 3) and all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["x"][:, 0], np.arange(100))
+    limit = 100 * (3 + 9 + 3) * 8 // 4  # room for about a quarter of the UAVs
+    samples = []
+    for r in range(2):
+        bench.dump_state(FakeSwarm(), 100, True, str(tmp_path / f"part{r}"), limit_bytes=limit)
+        samples.append({f.stem: np.load(f) for f in (tmp_path / f"part{r}").glob("*.npy")})
+    s = samples[0]
+    assert set(s) == {"x", "R", "external_force", "uav_index"} and sum(a.nbytes for a in s.values()) <= limit
+    idx = s["uav_index"].astype(np.int64)
+    assert 0 < len(idx) < 100 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(s["x"][:, 0], idx) and np.array_equal(s["external_force"], -s["x"])
+    for k in s:
+        assert np.array_equal(s[k], samples[1][k])

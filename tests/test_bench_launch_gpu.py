@@ -210,3 +210,40 @@ def test_config4_bench_form_against_oracle(mrs, oracle, volume):
     print(f"config 4 bench form, {volume:g} m^3 per UAV: {ticks} ticks in one call = {fused} fused launches, {searches} searches ({ahead} queued ahead), "
           f"{stalls} stalls / {replayed} launches replayed; oracle sample {m} UAVs, {int(clean.sum())} provably closed, {touched} of them under a "
           f"collision force at the end, worst per-UAV error {err:.2e}")
+
+
+def test_bench_dump_outputs_is_the_state_after_warmup_plus_steps(mrs, tmp_path):
+    """`bench.py --dump-outputs DIR`: one region of exactly --steps timed steps, and the state the headline path left behind is
+    written as DIR/<name>.npy — the same arrays on every run with the same arguments, and the same bits as W + K steps of the
+    bench's own inputs stepped here directly."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    M = mrs
+    n, warmup, steps = 4096, 3, 7
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    runs = []
+    for r in range(2):
+        d = tmp_path / f"run{r}"
+        p = subprocess.run([sys.executable, bench.__file__, "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--uavs", str(n),
+                            "--traffic", "off", "--no-cpu-baseline", "--config5", "off", "--sub-records", "off", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600, env=env)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == steps and line["warmup"] == warmup and line["regions"] == 1 and line["ms_per_step"] > 0
+        runs.append({f.stem: np.load(f) for f in d.glob("*.npy")})
+    assert set(runs[0]) == {"x", "v", "v_prev", "R", "omega", "motor_rpm"}
+    for k, a in runs[0].items():
+        assert a.dtype == np.float64 and len(a) == n and np.array_equal(a, runs[1][k]), k
+    st, cmd = _bench_inputs(n, "actuator", seed=3)
+    g = M.Swarm(n, arith=M.ARITH_FAST)
+    g.construct(0, n, M.model_params("x500", ground_enabled=True))
+    g.set_state(0, n, st["x"], st["v"], st["R"], st["omega"], st["motor_rpm"])
+    g.set_input(0, n, M.ACTUATOR_CMD, cmd)
+    g.step_n(DT, warmup)
+    g.step_n(DT, steps)
+    here = g.get_state(0, n)
+    for k, a in here.items():
+        assert np.array_equal(runs[0][k], a), k

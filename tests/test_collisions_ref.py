@@ -1,5 +1,7 @@
-"""Pins the collision semantics of the oracle to the REFERENCE's own kd-tree: oracle/_ref/libref_nanoflann.so is the
-reference's include/nanoflann.hpp + KDTreeVectorOfVectorsAdaptor.h compiled unmodified (oracle/Makefile).  CPU only."""
+"""Pins the collision semantics of the oracle to the REFERENCE's own kd-tree: its neighbour lists on the clouds below are stored in
+tests/golden/reference_kdtree_scenarios.npz (output of oracle/_ref/libref_nanoflann.so, the reference's include/nanoflann.hpp +
+KDTreeVectorOfVectorsAdaptor.h compiled unmodified by oracle/Makefile; helpers.reference_kdtree also re-queries that library
+wherever it is built).  CPU only."""
 import numpy as np
 import pytest
 
@@ -8,8 +10,6 @@ import helpers
 
 @pytest.fixture(scope="module")
 def ref(oracle):
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (reference tree absent and no prebuilt library)")
     return oracle
 
 
@@ -30,7 +30,7 @@ def clouds():
 def test_reference_kdtree_probe(ref):
     """SURVEY §8c probe: 1.2 m grid, centre point has 9 neighbours within squared radius 3.0: d2 in {0, 1.44, 2.88}."""
     g = np.stack(np.meshgrid(np.arange(5) * 1.2, np.arange(5) * 1.2, [0.0], indexing="ij"), -1).reshape(-1, 3)
-    off, idx, d2 = ref.ref_radius_neighbours(g, 3.0, 10)
+    off, idx, d2 = helpers.reference_kdtree("probe", g)
     c = 12
     dd = np.sort(d2[off[c]:off[c + 1]])
     assert len(dd) == 9 and np.allclose(dd, [0] + [1.44] * 4 + [2.88] * 4, atol=1e-12)
@@ -40,7 +40,7 @@ def test_reference_kdtree_probe(ref):
 def test_neighbour_set_and_forces_match_reference_kdtree(ref, name, pos):
     O = ref
     n = len(pos)
-    off, idx, d2 = O.ref_radius_neighbours(pos, 3.0, 10)
+    off, idx, d2 = helpers.reference_kdtree(name, pos)
     # literal metric of nanoflann L2_Adaptor::evalMetric for 3 dims
     diff = pos[:, None, :] - pos[None, :, :]
     D2 = (0.0 + diff[..., 0] * diff[..., 0] + diff[..., 1] * diff[..., 1]) + diff[..., 2] * diff[..., 2]

@@ -266,20 +266,32 @@ def test_collisions_match_oracle(M, oracle, crash):
     assert np.array_equal(p.g.get_external_force(), fg)
 
 
-def test_collision_neighbour_set_vs_reference_kdtree(M, oracle):
-    """Pairs found by the GPU hash == pairs found by the reference's own nanoflann (oracle/_ref), via the force support."""
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref not built")
+def close_pairs_cloud():
     rng = np.random.default_rng(5)
     n = 5000
     pos = rng.uniform(0, 30, (n, 3))
     pos[:50] = pos[50:100] + rng.normal(0, 0.05, (50, 3))  # guaranteed close pairs
     pos[100] = pos[101]  # coincident pair: normalized(0) = 0 -> zero force, still a neighbour
+    return pos
+
+
+def five_uav_clusters():
+    rng = np.random.default_rng(15)
+    n_clusters, per = 300, 5
+    centres = rng.uniform(0, 120, (n_clusters, 3)) + [0, 0, 10]
+    return (centres[:, None, :] + rng.normal(0, 0.22, (n_clusters, per, 3))).reshape(n_clusters * per, 3)  # five UAVs within ~0.5 m
+
+
+def test_collision_neighbour_set_vs_reference_kdtree(M, oracle):
+    """Pairs found by the GPU hash == pairs found by the reference's own nanoflann (stored lists, helpers.reference_kdtree), via the
+    force support."""
+    pos = close_pairs_cloud()
+    n = len(pos)
     g = M.Swarm(n)
     g.construct(0, n, M.model_params("x500"), pos, np.zeros(n))
     g.handle_collisions(True, False, 100.0)
     f = g.get_external_force()
-    off, idx, d2 = oracle.ref_radius_neighbours(pos, 3.0, 10)
+    off, idx, d2 = helpers.reference_kdtree("close pairs", pos)
     crit = 2 * (0.25 + 0.15)
     expect = np.zeros((n, 3))
     for i in range(n):
@@ -299,15 +311,10 @@ def test_collision_neighbour_set_vs_reference_kdtree(M, oracle):
 def test_collisions_three_body_clusters_in_the_reference_traversal_order(M, oracle):
     """UAVs with THREE OR MORE partners: the reference adds the rebounce forces in the order its kd-tree hands the neighbours out
     (src/multirotor_simulator.cpp:330-353), this library in ascending partner index.  The two sums differ by rounding only: held
-    here against forces accumulated in the reference's OWN traversal order (oracle/_ref: the reference's nanoflann, unsorted
-    results), at a few ulps of the force scale.  Mixed airframes so that the masses in the force expression differ."""
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref not built")
-    rng = np.random.default_rng(15)
-    n_clusters, per = 300, 5
-    n = n_clusters * per
-    centres = rng.uniform(0, 120, (n_clusters, 3)) + [0, 0, 10]
-    pos = (centres[:, None, :] + rng.normal(0, 0.22, (n_clusters, per, 3))).reshape(n, 3)  # five UAVs within ~0.5 m of each other
+    here against forces accumulated in the reference's OWN traversal order (the reference's nanoflann, unsorted results, stored:
+    helpers.reference_kdtree), at a few ulps of the force scale.  Mixed airframes so that the masses in the force expression differ."""
+    pos = five_uav_clusters()
+    n = len(pos)
     kinds = ["x500", "f450", "t650"]
     p = Pair(M, n)
     params = {}
@@ -316,7 +323,7 @@ def test_collisions_three_body_clusters_in_the_reference_traversal_order(M, orac
         params[k] = p.construct(k, 1, a, pos=pos[k:k + 1], heading=np.zeros(1))
     p.both("handle_collisions", True, False, 100.0)
     fg, fo = p.g.get_external_force(), p.o.get_external_force()
-    off, idx, d2 = oracle.ref_radius_neighbours(pos, 3.0, 10)
+    off, idx, d2 = helpers.reference_kdtree("five UAV clusters", pos)
     expect = np.zeros((n, 3))
     multi = 0
     for i in range(n):

@@ -74,11 +74,20 @@ def test_vectors_exercise_every_branch(golden):
 
 
 def test_reference_library_still_produces_the_vectors_and_matches_fresh_sequences(oracle, golden):
-    L = oracle.ref_pid_lib()
-    if L is None:
-        pytest.skip("oracle/_ref/libref_pid.so not built (reference tree absent and no prebuilt library)")
+    """A second stimulus set (seed 4242, stored with the reference's outputs in tests/golden/pid_reference_vectors_4242.npz) is
+    reproduced bit for bit by the oracle; where oracle/_ref/libref_pid.so is built, the library itself must still produce both
+    stored sets."""
     sys.path.insert(0, os.path.join(HERE, "golden"))
     import make_golden
+    fresh = np.load(os.path.join(HERE, "golden", "pid_reference_vectors_4242.npz"))
+    params, err, dt, event, new_sat = make_golden.pid_sequences(seed=4242, n_seq=40, n_steps=120)
+    for k, v in zip(("params", "err", "dt", "event", "new_sat"), (params, err, dt, event, new_sat)):
+        assert np.array_equal(fresh[k], v, equal_nan=True), f"stored stimulus {k} != make_golden.pid_sequences(seed=4242)"
+    for q in range(len(params)):
+        assert_same_bits(oracle_run(oracle, params[q], err[q], dt[q], event[q], new_sat[q]), fresh["out"][q], f"fresh sequence {q}")
+    L = oracle.ref_pid_lib()
+    if L is None:
+        return
 
     def ref_run(params, err, dt, event, new_sat):
         h = L.ref_pid_create()
@@ -96,7 +105,5 @@ def test_reference_library_still_produces_the_vectors_and_matches_fresh_sequence
     g = golden
     for q in range(0, len(g["params"]), 7):
         assert_same_bits(ref_run(g["params"][q], g["err"][q], g["dt"][q], g["event"][q], g["new_sat"][q]), g["out"][q], f"golden {q}")
-    params, err, dt, event, new_sat = make_golden.pid_sequences(seed=4242, n_seq=40, n_steps=120)
     for q in range(len(params)):
-        assert_same_bits(oracle_run(oracle, params[q], err[q], dt[q], event[q], new_sat[q]),
-                         ref_run(params[q], err[q], dt[q], event[q], new_sat[q]), f"fresh sequence {q}")
+        assert_same_bits(ref_run(params[q], err[q], dt[q], event[q], new_sat[q]), fresh["out"][q], f"fresh sequence {q}")

@@ -16,7 +16,9 @@
 //   * publishers: every UAV's odometry / IMU / range after its step (src/uav_system_ros.cpp:278-282) and the pose array every
 //     tick (src/multirotor_simulator.cpp:215, 365-389) — here ONE packed download per tick, started behind the tick's launch and
 //     handed to the publisher callback while the NEXT tick runs (mrs_swarm_get_outputs_async): messages leave one tick late in
-//     wall time, stamped with the sim time of the tick they describe
+//     wall time, stamped with the sim time of the tick they describe.  A second callback (setPosePublisher) receives the pose array
+//     alone (mrs_uav_pose_t, 56 B per UAV against 136): its download is started behind the same launch and handed out with the same
+//     delay and stamp; a host that publishes poses only sets that one and downloads 0.41x the bytes
 // Time is kept in integer nanoseconds like ros::Time.  "now" for the watchdog is the last PUBLISHED clock value: the
 // reference's callbacks read ros::Time::now(), which under use_sim_time is the /clock message this very node sent last.
 //
@@ -70,13 +72,19 @@ template <class S, class = void>
 struct has_async_outputs : std::false_type {};
 template <class S>
 struct has_async_outputs<S, std::void_t<decltype(std::declval<S&>().outputsWait(std::declval<S&>().getOutputsAsync(0, 0)))>> : std::true_type {};
+// ... and the pipelined pose-array download
+template <class S, class = void>
+struct has_async_poses : std::false_type {};
+template <class S>
+struct has_async_poses<S, std::void_t<decltype(std::declval<S&>().poseArrayWait(std::declval<S&>().getPoseArrayAsync(0, 0)))>> : std::true_type {};
 }  // namespace detail
 
 template <class SwarmT>
 class BasicMultirotorSimulator {
 public:
   using ns_t = int64_t;
-  // publisher callback: (sim time of the tick the payload describes, packed payloads of all UAVs — mrs_uav_output_t[count] —, count)
+  // publisher callback: (sim time of the tick the payload describes, packed payloads of all UAVs — mrs_uav_output_t[count], or
+  // mrs_uav_pose_t[count] for the pose publisher —, count)
   using PublishFn = std::function<void(double, const void*, int)>;
 
   BasicMultirotorSimulator(SwarmT& swarm, int n_uavs, const SimulatorConfig& cfg, double sim_time_start = 0.0)
@@ -99,7 +107,9 @@ public:
 
   // ---- publishers (src/uav_system_ros.cpp:278-282, src/multirotor_simulator.cpp:215): fn gets every tick's payload, one tick late ----
   void setPublisher(PublishFn fn) { publish_ = std::move(fn); }
-  // hand out the payload of the last tick (end of a run, before a pause: nothing stays in flight)
+  // publishPoses (src/multirotor_simulator.cpp:215, 365-389): fn gets every tick's pose array, one tick late
+  void setPosePublisher(PublishFn fn) { publish_poses_ = std::move(fn); }
+  // hand out the payloads of the last tick (end of a run, before a pause: nothing stays in flight)
   void flushPublisher() {
     if constexpr (detail::has_async_outputs<SwarmT>::value) {
       if (pending_ticket_ >= 0 && publish_) {
@@ -109,6 +119,14 @@ public:
       }
       pending_ticket_ = -1;
     }
+    if constexpr (detail::has_async_poses<SwarmT>::value) {
+      if (pending_pose_ticket_ >= 0 && publish_poses_) {
+        int count = 0;
+        const void* v = swarm_.poseArrayWait(pending_pose_ticket_, &count);
+        publish_poses_(toSec(pending_time_), v, count);
+      }
+      pending_pose_ticket_ = -1;
+    }
   }
 
   // ---- timerMain (src/multirotor_simulator.cpp:198-230): one tick; true when a clock message is due ----
@@ -117,14 +135,17 @@ public:
     sim_time_ += toNs(step);
     checkInputTimeouts();                                                                  // UavSystemRos::makeStep, first half
     swarm_.makeStep(step);                                                                 // :211-213
-    if constexpr (detail::has_async_outputs<SwarmT>::value) {                              // :215 publishPoses (+ uav_system_ros.cpp:278-282)
-      if (publish_ && n_ > 0) {
-        const int ticket = swarm_.getOutputsAsync(0, n_);  // behind this tick's launch; the copy runs beside the next tick
-        const ns_t stamp = sim_time_;
-        flushPublisher();                                  // the PREVIOUS tick's payload: landed while this tick was being queued
-        pending_ticket_ = ticket;
-        pending_time_   = stamp;
-      }
+    if (n_ > 0 && (publish_ || publish_poses_)) {                                         // :215 publishPoses (+ uav_system_ros.cpp:278-282)
+      int ticket = -1, pose_ticket = -1;                   // behind this tick's launch; the copies run beside the next tick
+      if constexpr (detail::has_async_outputs<SwarmT>::value)
+        if (publish_) ticket = swarm_.getOutputsAsync(0, n_);
+      if constexpr (detail::has_async_poses<SwarmT>::value)
+        if (publish_poses_) pose_ticket = swarm_.getPoseArrayAsync(0, n_);
+      const ns_t stamp = sim_time_;
+      flushPublisher();                                    // the PREVIOUS tick's payloads: landed while this tick was being queued
+      pending_ticket_      = ticket;
+      pending_pose_ticket_ = pose_ticket;
+      pending_time_        = stamp;
     }
     swarm_.handleCollisions(cfg_.collisions_enabled, cfg_.collisions_crash, cfg_.collisions_rebounce);  // :217
     ticks_++;
@@ -235,8 +256,8 @@ private:
   ns_t              sim_time_ = 0, last_published_time_ = 0, last_sim_time_status_ = 0;
   double            actual_rtf_ = 1.0;  // multirotor_simulator.cpp:62
   int64_t           ticks_      = 0;
-  PublishFn         publish_;
-  int               pending_ticket_ = -1;
+  PublishFn         publish_, publish_poses_;
+  int               pending_ticket_ = -1, pending_pose_ticket_ = -1;
   ns_t              pending_time_   = 0;
 };
 

@@ -733,6 +733,30 @@ public:
     if (count) *count = c;
     return v;
   }
+  // the pose array alone (publishPoses, src/multirotor_simulator.cpp:365-389): position + orientation, 56 B per UAV — the calls
+  // above for mrs_uav_pose_t (mrs_swarm_get_poses*).  A view stays valid until the next getPoseArray* call; getOutputs* leaves it alone.
+  std::vector<mrs_uav_pose_t> getPoseArray(int first, int count) {
+    std::vector<mrs_uav_pose_t> out((size_t)count);
+    mrs_throw_on_error(mrs_swarm_get_poses(s_, first, count, out.data()));
+    return out;
+  }
+  const mrs_uav_pose_t* getPoseArrayView(int first, int count) {
+    const mrs_uav_pose_t* v = nullptr;
+    mrs_throw_on_error(mrs_swarm_get_poses_view(s_, first, count, &v));
+    return v;
+  }
+  int getPoseArrayAsync(int first, int count) {
+    int32_t ticket = -1;
+    mrs_throw_on_error(mrs_swarm_get_poses_async(s_, first, count, &ticket));
+    return ticket;
+  }
+  const mrs_uav_pose_t* poseArrayWait(int ticket, int* count = nullptr) {
+    const mrs_uav_pose_t* v = nullptr;
+    int32_t               c = 0;
+    mrs_throw_on_error(mrs_swarm_poses_wait(s_, ticket, &v, &c));
+    if (count) *count = c;
+    return v;
+  }
   // batched subscriber side: pinned rows to fill with setInput payloads (layout of mrs_swarm_set_input), then one commit
   double* inputStaging(int count, int stride) {
     double* rows = nullptr;

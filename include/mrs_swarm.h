@@ -90,6 +90,13 @@ typedef struct {
   double range;                  /* rangefinder: (z - ground_z)/cos(tilt) + 0.01, >40 -> 41, body_z.z <= 0 -> 41  :403-419 */
 } mrs_uav_output_t;
 
+/* one entry of MultirotorSimulator::publishPoses' geometry_msgs/PoseArray (src/multirotor_simulator.cpp:380-383): the position and
+ * orientation fields of mrs_uav_output_t alone, 56 B (7 doubles, no padding) against its 136 B, bit for bit the same values */
+typedef struct {
+  double position[3];            /* pose.position = getState().x                              :380-382 */
+  double orientation[4];         /* x, y, z, w of mrs_lib::AttitudeConverter(state.R)           :383 */
+} mrs_uav_pose_t;
+
 /* MultirotorModel::State (+ what UavSystemRos::makeStep reads right after it: IMU acceleration, crash flag) of one UAV, packed for
  * ONE device-to-host copy of a whole range — multirotor_model.hpp:90-98, src/uav_system_ros.cpp:270-282 */
 typedef struct {
@@ -245,6 +252,21 @@ int mrs_swarm_get_outputs_view(mrs_swarm_t* s, int32_t first, int32_t count, con
  * the state after the tick the caller packed behind. */
 int mrs_swarm_get_outputs_async(mrs_swarm_t* s, int32_t first, int32_t count, int32_t* ticket);
 int mrs_swarm_outputs_wait(mrs_swarm_t* s, int32_t ticket, const mrs_uav_output_t** view, int32_t* count);
+/* The pose array alone (MultirotorSimulator::publishPoses, src/multirotor_simulator.cpp:215,365-389): the same calls for 56-B
+ * mrs_uav_pose_t records, for a host that publishes poses only (0.41x the bytes of mrs_uav_output_t).  The two payloads keep their own
+ * staging: a _view stays valid until the next call of ITS kind (a mrs_swarm_get_outputs* call does not invalidate a pose view, nor the
+ * reverse).  _async / _wait: the contract of mrs_swarm_get_outputs_async / mrs_swarm_outputs_wait above, with these ticket rules:
+ *   - each kind has its own two blocks: at most two pose downloads and two wide ones are in flight, and a pose block stays valid until the
+ *     second mrs_swarm_get_poses_async after its ticket's (wide downloads in between do not count);
+ *   - tickets of both kinds come from one counter; a wait given a ticket of the other kind, or one whose block has been handed to a
+ *     newer download of its kind, fails with MRS_ERR_ARG;
+ *   - any number of downloads of either kind may follow one tick: a stall repeats every one of them whose block is still held. */
+int mrs_swarm_get_poses(mrs_swarm_t* s, int32_t first, int32_t count, mrs_uav_pose_t* out);
+int mrs_swarm_get_poses_view(mrs_swarm_t* s, int32_t first, int32_t count, const mrs_uav_pose_t** view);
+int mrs_swarm_get_poses_async(mrs_swarm_t* s, int32_t first, int32_t count, int32_t* ticket);
+int mrs_swarm_poses_wait(mrs_swarm_t* s, int32_t ticket, const mrs_uav_pose_t** view, int32_t* count);
+/* pipelined downloads of both kinds: packs issued by the _async calls, and packs issued again by a replay after a stall */
+int mrs_swarm_get_download_stats(mrs_swarm_t* s, int64_t* issued, int64_t* reissued);
 
 /* ---- multi-GPU collision exchange (one swarm shard per process/GPU) ---- */
 /* device pointer + byte size of this shard's packed {x,y,z,mass,arm_length,prop_radius} records (48 B/UAV), refreshed by

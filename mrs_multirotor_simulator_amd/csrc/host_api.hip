@@ -536,18 +536,21 @@ int mrs_swarm_destroy(mrs_swarm_t* s) {
   for (auto e : s->ev) (void)hipEventDestroy(e);
   mrs_collide_free(s->cwork);
   if (s->dRec) (void)hipFree(s->dRec);
-  if (s->dOut) (void)hipFree(s->dOut);
   if (s->dSt) (void)hipFree(s->dSt);
   if (s->hSt) (void)hipHostFree(s->hSt);
-  if (s->hOut) (void)hipHostFree(s->hOut);
+  for (auto& b : s->ostage) {
+    if (b.d) (void)hipFree(b.d);
+    if (b.h) (void)hipHostFree(b.h);
+  }
   for (hipStream_t st : {s->stream_io, s->stream_up})
     if (st) (void)hipStreamSynchronize(st);  // (a copy may still be in flight into / out of the pinned blocks freed below)
-  for (auto& o : s->oslot) {
-    if (o.d) (void)hipFree(o.d);
-    if (o.h) (void)hipHostFree(o.h);
-    if (o.packed) (void)hipEventDestroy(o.packed);
-    if (o.done) (void)hipEventDestroy(o.done);
-  }
+  for (auto& ring : s->oslot)
+    for (auto& o : ring) {
+      if (o.d) (void)hipFree(o.d);
+      if (o.h) (void)hipHostFree(o.h);
+      if (o.packed) (void)hipEventDestroy(o.packed);
+      if (o.done) (void)hipEventDestroy(o.done);
+    }
   for (auto& i : s->islot) {
     if (i.d) (void)hipFree(i.d);
     if (i.h) (void)hipHostFree(i.h);
@@ -1067,72 +1070,78 @@ int mrs_swarm_set_ground_z(mrs_swarm_t* s, int32_t first, int32_t count, double 
   return modify_params(s, first, count, [&](mrs_model_params_t& p) { p.ground_z = ground_z; });  // :1063-1073
 }
 
-static int fetch_outputs(mrs_swarm* s, int32_t first, int32_t count) {
+}  // extern "C"
+namespace mrs_host {
+static hipError_t launch_pack(mrs_swarm* s, int kind, int first, int count, void* dev_out, hipStream_t st) {
+  if (kind == PAYLOAD_POSE) return mrs_launch_pack_poses(s->view(), first, count, static_cast<mrs_uav_pose_t*>(dev_out), st);
+  return mrs_launch_pack_outputs(s->view(), first, count, static_cast<mrs_uav_output_t*>(dev_out), st);
+}
+
+// the synchronous download of one payload kind into that kind's pinned staging (ostage[kind].h)
+static int fetch_payload(mrs_swarm* s, int kind, int32_t first, int32_t count) {
   HIPCHK(hipSetDevice(s->device));
   int rc = upload_types(s, s->table_dt > 0 ? s->table_dt : 0.001);
   if (rc) return rc;
-  if (count > s->out_cap) {
+  mrs_swarm::OutStage& b     = s->ostage[kind];
+  const size_t         bytes = payload_bytes(kind) * (size_t)count;
+  if (count > b.cap) {
     HIPCHK(hipStreamSynchronize(s->stream));
-    if (s->dOut) HIPCHK(hipFree(s->dOut));
-    if (s->hOut) HIPCHK(hipHostFree(s->hOut));
-    HIPCHK(hipMalloc(&s->dOut, sizeof(mrs_uav_output_t) * (size_t)count));
-    HIPCHK(hipHostMalloc(&s->hOut, sizeof(mrs_uav_output_t) * (size_t)count, hipHostMallocDefault));
-    s->out_cap = count;
+    if (b.d) HIPCHK(hipFree(b.d));
+    if (b.h) HIPCHK(hipHostFree(b.h));
+    b.d = nullptr; b.h = nullptr; b.cap = 0;
+    HIPCHK(hipMalloc(&b.d, bytes));
+    HIPCHK(hipHostMalloc(&b.h, bytes, hipHostMallocDefault));
+    b.cap = count;
   }
-  HIPCHK(mrs_launch_pack_outputs(s->view(), first, count, s->dOut, s->stream));
-  HIPCHK(hipMemcpyAsync(s->hOut, s->dOut, sizeof(mrs_uav_output_t) * (size_t)count, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(launch_pack(s, kind, first, count, b.d, s->stream));
+  HIPCHK(hipMemcpyAsync(b.h, b.d, bytes, hipMemcpyDeviceToHost, s->stream));
   HIPCHK(hipStreamSynchronize(s->stream));
   return MRS_OK;
 }
 
-int mrs_swarm_get_outputs(mrs_swarm_t* s, int32_t first, int32_t count, mrs_uav_output_t* out) {
-  MRS_ENTER(s);
+static int get_payload(mrs_swarm* s, int kind, int32_t first, int32_t count, void* out) {
   int rc = check_range(s, first, count);
   if (rc) return rc;
   if (!out) return fail(MRS_ERR_ARG, "null out");
   if (count == 0) return MRS_OK;
-  if ((rc = fetch_outputs(s, first, count))) return rc;
-  memcpy(out, s->hOut, sizeof(mrs_uav_output_t) * (size_t)count);
+  if ((rc = fetch_payload(s, kind, first, count))) return rc;
+  memcpy(out, s->ostage[kind].h, payload_bytes(kind) * (size_t)count);
   return MRS_OK;
 }
 
-int mrs_swarm_get_outputs_view(mrs_swarm_t* s, int32_t first, int32_t count, const mrs_uav_output_t** view) {
-  MRS_ENTER(s);
+static int get_payload_view(mrs_swarm* s, int kind, int32_t first, int32_t count, const void** view) {
   int rc = check_range(s, first, count);
   if (rc) return rc;
   if (!view) return fail(MRS_ERR_ARG, "null view");
   *view = nullptr;
   if (count == 0) return MRS_OK;
-  if ((rc = fetch_outputs(s, first, count))) return rc;
-  *view = s->hOut;
+  if ((rc = fetch_payload(s, kind, first, count))) return rc;
+  *view = s->ostage[kind].h;
   return MRS_OK;
 }
 
-}  // extern "C"
-namespace mrs_host {
 static int ensure_io_stream(mrs_swarm* s) {
   if (s->stream_io) return MRS_OK;
   HIPCHK(hipStreamCreateWithFlags(&s->stream_io, hipStreamNonBlocking));
   HIPCHK(hipStreamCreateWithFlags(&s->stream_up, hipStreamNonBlocking));
   return MRS_OK;
 }
+
 // pack behind everything queued on the step stream, copy on the copy stream (also called by drain() when the launch the pack
 // followed is replayed after a stall)
-int issue_outputs(mrs_swarm* s, int slot) {
-  mrs_swarm::OutSlot& o = s->oslot[slot];
+int issue_download(mrs_swarm* s, mrs_swarm::OutSlot& o) {
   HIPCHK(hipStreamWaitEvent(s->stream, o.done, 0));  // the copy out of this buffer two tickets ago (a no-op when long complete)
-  HIPCHK(mrs_launch_pack_outputs(s->view(), o.first, o.count, o.d, s->stream));
+  HIPCHK(launch_pack(s, o.kind, o.first, o.count, o.d, s->stream));
   HIPCHK(hipEventRecord(o.packed, s->stream));
   HIPCHK(hipStreamWaitEvent(s->stream_io, o.packed, 0));
-  HIPCHK(hipMemcpyAsync(o.h, o.d, sizeof(mrs_uav_output_t) * (size_t)o.count, hipMemcpyDeviceToHost, s->stream_io));
+  HIPCHK(hipMemcpyAsync(o.h, o.d, payload_bytes(o.kind) * (size_t)o.count, hipMemcpyDeviceToHost, s->stream_io));
   HIPCHK(hipEventRecord(o.done, s->stream_io));
   return MRS_OK;
 }
-}  // namespace mrs_host
-extern "C" {
 
-int mrs_swarm_get_outputs_async(mrs_swarm_t* s, int32_t first, int32_t count, int32_t* ticket) {
-  MRS_LOCK(s);  // NOT settle(): launches of lazily evaluated collision ticks stay queued; a stall among them is put right at the wait
+// the caller holds the lock and has NOT settled: launches of lazily evaluated collision ticks stay queued; a stall among them is put
+// right at the wait
+static int download_async(mrs_swarm* s, int kind, int32_t first, int32_t count, int32_t* ticket) {
   int rc = check_range(s, first, count);
   if (rc) return rc;
   if (!ticket) return fail(MRS_ERR_ARG, "null ticket");
@@ -1140,8 +1149,8 @@ int mrs_swarm_get_outputs_async(mrs_swarm_t* s, int32_t first, int32_t count, in
   HIPCHK(hipSetDevice(s->device));
   if ((rc = upload_types(s, s->table_dt > 0 ? s->table_dt : 0.001))) return rc;
   if ((rc = ensure_io_stream(s))) return rc;
-  const int32_t        t = s->out_tickets;
-  mrs_swarm::OutSlot&  o = s->oslot[t & 1];
+  const int32_t       t = s->out_tickets;
+  mrs_swarm::OutSlot& o = s->oslot[kind][s->out_turn[kind] & 1];
   if (!o.packed) {
     HIPCHK(hipEventCreateWithFlags(&o.packed, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&o.done, hipEventDisableTiming));
@@ -1151,30 +1160,41 @@ int mrs_swarm_get_outputs_async(mrs_swarm_t* s, int32_t first, int32_t count, in
     if (o.d) HIPCHK(hipFree(o.d));
     if (o.h) HIPCHK(hipHostFree(o.h));
     o.d = nullptr; o.h = nullptr; o.cap = 0;
-    HIPCHK(hipMalloc(&o.d, sizeof(mrs_uav_output_t) * (size_t)count));
-    HIPCHK(hipHostMalloc(&o.h, sizeof(mrs_uav_output_t) * (size_t)count, hipHostMallocDefault));
+    HIPCHK(hipMalloc(&o.d, payload_bytes(kind) * (size_t)count));
+    HIPCHK(hipHostMalloc(&o.h, payload_bytes(kind) * (size_t)count, hipHostMallocDefault));
     o.cap = count;
   }
+  o.kind   = kind;
   o.ticket = t;
   o.first  = first;
   o.count  = count;
-  if ((rc = issue_outputs(s, t & 1))) return rc;
-  if (!s->log.empty()) s->log.back().out_ticket = t;  // the pack followed this launch: a replay of it repeats the pack
+  if ((rc = issue_download(s, o))) return rc;
+  s->n_packs_issued++;
+  if (!s->log.empty()) {  // the pack followed this launch: a replay of it repeats the pack, after those issued before it
+    mrs_swarm::TickRec& r = s->log.back();
+    int                 m = 0;
+    for (int j = 0; j < r.n_packs; j++)  // (those whose slot has been recycled are done with: at most three others are left)
+      if (held_slot(s, r.packs[j].kind, r.packs[j].ticket)) r.packs[m++] = r.packs[j];
+    r.packs[m++] = {kind, t};
+    r.n_packs    = m;
+  }
+  s->out_turn[kind]++;
   s->out_tickets++;
   *ticket = t;
   return MRS_OK;
 }
 
-int mrs_swarm_outputs_wait(mrs_swarm_t* s, int32_t ticket, const mrs_uav_output_t** view, int32_t* count) {
-  MRS_LOCK(s);
+static int download_wait(mrs_swarm* s, int kind, int32_t ticket, const void** view, int32_t* count) {
   if (!s || !view) return fail(MRS_ERR_ARG, "null argument");
   *view = nullptr;
   if (ticket < 0 || ticket >= s->out_tickets) return fail(MRS_ERR_ARG, "no such ticket");
-  mrs_swarm::OutSlot& o = s->oslot[ticket & 1];
-  if (o.ticket != ticket) return fail(MRS_ERR_ARG, "this ticket's block has been handed to a newer download (two downloads in flight at most)");
+  mrs_swarm::OutSlot* o = held_slot(s, kind, ticket);
+  if (!o)
+    return fail(MRS_ERR_ARG, "no block of this payload kind holds this ticket (a ticket of the other kind, or its block has been handed to a "
+                             "newer download: two downloads per kind in flight at most)");
   HIPCHK(hipSetDevice(s->device));
   for (;;) {
-    HIPCHK(hipEventSynchronize(o.done));  // that copy only: steps queued behind the pack keep running
+    HIPCHK(hipEventSynchronize(o->done));  // that copy only: steps queued behind the pack keep running
     // launches of lazily evaluated collision ticks may have turned into no-ops before the pack ran (a UAV left its skin: DESIGN §4 K1b);
     // drain() repeats the search, replays them — and re-issues every pack that followed a replayed launch
     const volatile unsigned* hw = mrs_collide_host_words(s->cwork);
@@ -1182,8 +1202,58 @@ int mrs_swarm_outputs_wait(mrs_swarm_t* s, int32_t ticket, const mrs_uav_output_
     int rc = drain(s);
     if (rc) return rc;
   }
-  *view = o.h;
-  if (count) *count = o.count;
+  *view = o->h;
+  if (count) *count = o->count;
+  return MRS_OK;
+}
+}  // namespace mrs_host
+extern "C" {
+
+int mrs_swarm_get_outputs(mrs_swarm_t* s, int32_t first, int32_t count, mrs_uav_output_t* out) {
+  MRS_ENTER(s);
+  return get_payload(s, PAYLOAD_WIDE, first, count, out);
+}
+
+int mrs_swarm_get_outputs_view(mrs_swarm_t* s, int32_t first, int32_t count, const mrs_uav_output_t** view) {
+  MRS_ENTER(s);
+  return get_payload_view(s, PAYLOAD_WIDE, first, count, reinterpret_cast<const void**>(view));
+}
+
+int mrs_swarm_get_outputs_async(mrs_swarm_t* s, int32_t first, int32_t count, int32_t* ticket) {
+  MRS_LOCK(s);  // NOT settle(): see download_async
+  return download_async(s, PAYLOAD_WIDE, first, count, ticket);
+}
+
+int mrs_swarm_outputs_wait(mrs_swarm_t* s, int32_t ticket, const mrs_uav_output_t** view, int32_t* count) {
+  MRS_LOCK(s);
+  return download_wait(s, PAYLOAD_WIDE, ticket, reinterpret_cast<const void**>(view), count);
+}
+
+int mrs_swarm_get_poses(mrs_swarm_t* s, int32_t first, int32_t count, mrs_uav_pose_t* out) {
+  MRS_ENTER(s);
+  return get_payload(s, PAYLOAD_POSE, first, count, out);
+}
+
+int mrs_swarm_get_poses_view(mrs_swarm_t* s, int32_t first, int32_t count, const mrs_uav_pose_t** view) {
+  MRS_ENTER(s);
+  return get_payload_view(s, PAYLOAD_POSE, first, count, reinterpret_cast<const void**>(view));
+}
+
+int mrs_swarm_get_poses_async(mrs_swarm_t* s, int32_t first, int32_t count, int32_t* ticket) {
+  MRS_LOCK(s);  // NOT settle(): see download_async
+  return download_async(s, PAYLOAD_POSE, first, count, ticket);
+}
+
+int mrs_swarm_poses_wait(mrs_swarm_t* s, int32_t ticket, const mrs_uav_pose_t** view, int32_t* count) {
+  MRS_LOCK(s);
+  return download_wait(s, PAYLOAD_POSE, ticket, reinterpret_cast<const void**>(view), count);
+}
+
+int mrs_swarm_get_download_stats(mrs_swarm_t* s, int64_t* issued, int64_t* reissued) {
+  MRS_LOCK(s);
+  if (!s) return fail(MRS_ERR_ARG, "null swarm");
+  if (issued) *issued = s->n_packs_issued;
+  if (reissued) *reissued = s->n_packs_reissued;
   return MRS_OK;
 }
 

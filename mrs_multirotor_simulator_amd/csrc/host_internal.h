@@ -101,6 +101,7 @@ extern "C" int        mrs_collide_fused_pin(const CollideWork* w);
 extern "C" hipError_t mrs_launch_timeout_input(SwarmDev sw, int first, int count, hipStream_t st);
 extern "C" hipError_t mrs_launch_unpack_rows(SwarmDev sw, const double* rows, int stride, int width, int base, int first, int count, hipStream_t st);
 extern "C" hipError_t mrs_launch_pack_outputs(SwarmDev sw, int first, int count, mrs_uav_output_t* dev_out, hipStream_t st);
+extern "C" hipError_t mrs_launch_pack_poses(SwarmDev sw, int first, int count, mrs_uav_pose_t* dev_out, hipStream_t st);
 extern "C" hipError_t mrs_launch_pack_states(SwarmDev sw, int first, int count, mrs_uav_state_t* dev_out, hipStream_t st);
 extern "C" hipError_t mrs_launch_peer_allgather(const MrsPeerWindows* pw, const void* send, void* recv, size_t bytes, int rank, int world, unsigned seq,
                                                 size_t slot_bytes, unsigned* tickets, unsigned ticket_total, unsigned* err_host, unsigned* bpp_out,
@@ -119,6 +120,10 @@ using mrs_host::fail;
     if (_e != hipSuccess) return fail(MRS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
 
+
+// kinds of publisher payload: the wide record (odometry / IMU / range / pose, mrs_uav_output_t) and the pose array (mrs_uav_pose_t)
+enum { PAYLOAD_WIDE = 0, PAYLOAD_POSE = 1, PAYLOAD_KINDS = 2 };
+inline size_t payload_bytes(int kind) { return kind == PAYLOAD_POSE ? sizeof(mrs_uav_pose_t) : sizeof(mrs_uav_output_t); }
 
 struct TypeKey {  // everything that distinguishes two UavSystem parameterisations
   mrs_model_params_t    mp;  // takeoff_patch_enabled normalised to 0 (it is per-UAV mutable state)
@@ -240,10 +245,14 @@ struct mrs_swarm {
   int64_t n_cascade = 0;              // UAVs whose mode needs the controller cascade
   bool   types_dirty = true;
   double table_dt    = -1.0;
-  // publisher payloads: device pack buffer + pinned host staging
-  mrs_uav_output_t* dOut = nullptr;
-  mrs_uav_output_t* hOut = nullptr;
-  int32_t           out_cap = 0;
+  // publisher payloads of the synchronous calls (mrs_swarm_get_outputs* / get_poses*): device pack buffer + pinned host staging per
+  // kind, so that a view of one kind survives a call of the other
+  struct OutStage {
+    void*   d = nullptr;
+    void*   h = nullptr;
+    int32_t cap = 0;
+  };
+  OutStage ostage[PAYLOAD_KINDS];
   mrs_uav_state_t*  dSt = nullptr;   // packed states (mrs_swarm_get_states): device buffer + pinned host staging
   mrs_uav_state_t*  hSt = nullptr;
   int32_t           st_cap = 0;
@@ -251,12 +260,17 @@ struct mrs_swarm {
   // the pack kernel runs on the step stream behind everything queued so far, the device-to-host copy on `stream_io`, so the download
   // of tick t overlaps step t + 1.  `packed` orders copy behind pack, `done` is what the host waits for (and what the next pack into
   // the same buffer waits for on the device).
+  // Each payload kind has a ring of two slots (a loop that starts both kinds every tick keeps two downloads of each in flight); the
+  // tickets of both kinds come from one counter.
   struct OutSlot {
-    mrs_uav_output_t *d = nullptr, *h = nullptr;
-    int32_t           cap = 0, ticket = -1, first = 0, count = 0;
-    hipEvent_t        packed = nullptr, done = nullptr;
+    int32_t    kind = PAYLOAD_WIDE;
+    void *     d = nullptr, *h = nullptr;
+    int32_t    cap = 0, ticket = -1, first = 0, count = 0;
+    hipEvent_t packed = nullptr, done = nullptr;
   };
-  OutSlot     oslot[2];
+  OutSlot     oslot[PAYLOAD_KINDS][2];
+  int32_t     out_turn[PAYLOAD_KINDS] = {};  // the slot of each kind the next _async call takes (alternating)
+  int64_t     n_packs_issued = 0, n_packs_reissued = 0;
   // copy streams: download (stream_io) and command upload (stream_up) — one per direction, PCIe is full duplex.  (The download cut
   // in two halves on two streams — two DMA engines — was measured and dropped: 0.40 against 0.38 ms per 13.6-MB tick.)
   hipStream_t stream_io = nullptr, stream_up = nullptr;
@@ -282,9 +296,18 @@ struct mrs_swarm {
   // leaves its skin during step T the launches after T turn into no-ops, and the host repeats the search and replays them.
   struct Collide { bool on = false; int enabled = 0, crash = 0; double rebounce = 0.0; };
   // one fused launch: the collision tick it evaluates first (searched: a search queued right before it has done that), then makeStep(dt)
-  // pin: which position buffer the launch read; out_ticket: a pipelined output download packed right behind this launch (re-issued
-  // when the launch is replayed after a stall: what it packed then was the state of an earlier tick)
-  struct TickRec { double dt; Collide eval; bool searched; int pin; int out_ticket = -1; };
+  // pin: which position buffer the launch read; packs: the pipelined downloads packed right behind this launch, in the order they were
+  // issued (re-issued when the launch is replayed after a stall: what they packed then was the state of an earlier tick).  At most
+  // two per kind can still hold their slot, so four entries are enough (the _async call drops those whose slot has been recycled).
+  struct PackRef { int32_t kind, ticket; };
+  struct TickRec {
+    double  dt;
+    Collide eval;
+    bool    searched;
+    int     pin = 0;
+    int     n_packs = 0;
+    PackRef packs[2 * PAYLOAD_KINDS] = {};
+  };
   Collide              pend;                        // requested after the most recent step, not evaluated yet
   // A fused launch consumes the force it evaluates from registers and does not write the F_ext columns (24 B per UAV and tick).
   // While f_lazy.on those columns are stale: the latched force is "collision tick f_lazy on the position records f_lazy_pin",
@@ -364,7 +387,7 @@ int drain(mrs_swarm* s);
 
 namespace mrs_host {
 // ---- host_api.hip ----
-int     issue_outputs(mrs_swarm* s, int slot);  // pack + copy of the pipelined download held by oslot[slot]
+int     issue_download(mrs_swarm* s, mrs_swarm::OutSlot& o);  // pack + copy of the pipelined download held by slot o
 void    track_mode(mrs_swarm* s, int first, int count, int mode);
 int     check_range(const mrs_swarm* s, int first, int count);
 int     intern_type(mrs_swarm* s, const TypeKey& k, int* out);
@@ -385,6 +408,12 @@ int  collide_now(mrs_swarm* s, const mrs_swarm::Collide& c, bool force);
 int  wait_for_progress(mrs_swarm* s, const volatile unsigned* hw, unsigned index, int lead);
 int  step_one(mrs_swarm* s, double dt);
 int  drain(mrs_swarm* s);
+// the slot of `kind` that still holds the download `ticket` (nullptr: a ticket of the other kind, or its slot has been recycled)
+inline mrs_swarm::OutSlot* held_slot(mrs_swarm* s, int kind, int32_t ticket) {
+  for (auto& o : s->oslot[kind])
+    if (o.ticket == ticket) return &o;
+  return nullptr;
+}
 inline unsigned min_nonzero(unsigned a, unsigned b) { return a == 0u ? b : (b == 0u ? a : (a < b ? a : b)); }
 // the stall / warning index the host knows of: each chain of a split tick keeps mirrors of its own (one writer per word)
 inline unsigned stall_word(const volatile unsigned* hw) { return min_nonzero(hw[CTL_STALL], hw[CTL_STALL2]); }

@@ -1,7 +1,8 @@
 // outputs.hip — per-UAV publisher payloads derived on the device and packed for ONE device-to-host copy.
 // Replaces the per-UAV host work of UavSystemRos::publishOdometry/IMU/Rangefinder (src/uav_system_ros.cpp:342-431)
 // and MultirotorSimulator::publishPoses (src/multirotor_simulator.cpp:365-389): state never leaves HBM column by column.
-// HBM-bound gather: reads 22 doubles + flags per UAV (coalesced SoA columns), writes one 136-B record.
+// HBM-bound gather: reads 22 doubles + flags per UAV (coalesced SoA columns), writes one 136-B record (the pose array alone: 12
+// doubles read, one 56-B record written).
 #include <hip/hip_runtime.h>
 
 #include "../../include/mrs_swarm.h"
@@ -83,6 +84,23 @@ __global__ void __launch_bounds__(256) k_pack_outputs(SwarmDev sw, int first, in
   if (range > 40.0) range = 41.0;
   o.range = range;
   out[k]  = o;
+}
+
+// MultirotorSimulator::publishPoses (src/multirotor_simulator.cpp:365-389) alone: position and orientation, 56 B per UAV instead of
+// the 136 B of the wide record.  Same loads, same quat_from_matrix: the fields equal those of k_pack_outputs bit for bit.
+__global__ void __launch_bounds__(256) k_pack_poses(SwarmDev sw, int first, int count, mrs_uav_pose_t* out) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  const int    i  = first + k;
+  const size_t np = (size_t)sw.npad;
+  double R[9];
+  mrs_uav_pose_t o;
+#pragma unroll
+  for (int c = 0; c < 3; c++) o.position[c] = sw.S[(F_X + c) * np + i];
+#pragma unroll
+  for (int c = 0; c < 9; c++) R[c] = sw.S[(F_R + c) * np + i];
+  quat_from_matrix(R, o.orientation);
+  out[k] = o;
 }
 
 // mrs_lib::AttitudeConverter(R).getHeading(): q = Eigen::Quaterniond(R); heading = atan2 of the first column of
@@ -213,5 +231,11 @@ extern "C" hipError_t mrs_launch_pack_states(SwarmDev sw, int first, int count, 
 extern "C" hipError_t mrs_launch_pack_outputs(SwarmDev sw, int first, int count, mrs_uav_output_t* dev_out, hipStream_t st) {
   if (count <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_pack_outputs, dim3((count + 255) / 256), dim3(256), 0, st, sw, first, count, dev_out);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t mrs_launch_pack_poses(SwarmDev sw, int first, int count, mrs_uav_pose_t* dev_out, hipStream_t st) {
+  if (count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_pack_poses, dim3((count + 255) / 256), dim3(256), 0, st, sw, first, count, dev_out);
   return hipGetLastError();
 }

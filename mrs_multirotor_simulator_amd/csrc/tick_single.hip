@@ -264,8 +264,14 @@ int drain(mrs_swarm* s) {
         s->region_launches++;
         if ((rc = launch_part(s, e.dt, 1, 0, (s->n + 63) / 64, 1, s->stream))) return rc;
       }
-      // a pipelined output download packed behind the no-op took the state of an earlier tick: once more, behind the real launch
-      if (e.out_ticket >= 0 && s->oslot[e.out_ticket & 1].ticket == e.out_ticket && (rc = issue_outputs(s, e.out_ticket & 1))) return rc;
+      // the pipelined downloads packed behind the no-op took the state of an earlier tick: once more, behind the real launch, every one
+      // whose slot still holds its ticket, in the order they were issued
+      for (int j = 0; j < e.n_packs; j++) {
+        mrs_swarm::OutSlot* o = held_slot(s, e.packs[j].kind, e.packs[j].ticket);
+        if (!o) continue;
+        if ((rc = issue_download(s, *o))) return rc;
+        s->n_packs_reissued++;
+      }
     }
     if (s->log.empty()) return MRS_OK;
   }

@@ -60,6 +60,14 @@ OUTPUT_DTYPE = np.dtype([("position", "f8", 3), ("orientation", "f8", 4), ("velo
                          ("angular_velocity", "f8", 3), ("linear_acceleration", "f8", 3), ("range", "f8")])
 
 
+class UavPose(C.Structure):
+    """mrs_uav_pose_t: one entry of MultirotorSimulator::publishPoses' pose array (position, orientation x y z w)."""
+    _fields_ = [("position", C.c_double * 3), ("orientation", C.c_double * 4)]
+
+
+POSE_DTYPE = np.dtype([("position", "f8", 3), ("orientation", "f8", 4)])
+
+
 class CommInfo(C.Structure):
     """mrs_comm_info_t"""
     _fields_ = [("world", C.c_int32), ("rank", C.c_int32), ("rccl_ranks", C.c_int32), ("exchange", C.c_int32), ("n_total", C.c_int64),
@@ -101,6 +109,7 @@ ABI_SYMBOLS = [
     "mrs_swarm_set_hold", "mrs_swarm_get_collision_stats", "mrs_swarm_get_outputs_view", "mrs_swarm_input_staging", "mrs_swarm_commit_input", "mrs_swarm_last_step_kernel_ms", "mrs_swarm_set_profiling",
     "mrs_swarm_debug_search_ms", "mrs_swarm_debug_neighbour_lists", "mrs_swarm_clone_resized", "mrs_swarm_copy_uavs", "mrs_swarm_step_range", "mrs_swarm_get_states",
     "mrs_swarm_get_outputs_async", "mrs_swarm_outputs_wait", "mrs_cell_order",
+    "mrs_swarm_get_poses", "mrs_swarm_get_poses_view", "mrs_swarm_get_poses_async", "mrs_swarm_poses_wait", "mrs_swarm_get_download_stats",
 ]
 
 STATE_DTYPE = np.dtype([("x", "f8", 3), ("v", "f8", 3), ("v_prev", "f8", 3), ("R", "f8", (3, 3)), ("omega", "f8", 3), ("motor_rpm", "f8", 8),
@@ -300,6 +309,11 @@ def load_library():
         "mrs_swarm_get_outputs_async": [vp, i32, i32, ip],
         "mrs_swarm_outputs_wait": [vp, i32, C.POINTER(vp), ip],
         "mrs_cell_order": [dp, C.c_int64, f64, C.POINTER(C.c_int64)],
+        "mrs_swarm_get_poses": [vp, i32, i32, vp],
+        "mrs_swarm_get_poses_view": [vp, i32, i32, C.POINTER(vp)],
+        "mrs_swarm_get_poses_async": [vp, i32, i32, ip],
+        "mrs_swarm_poses_wait": [vp, i32, C.POINTER(vp), ip],
+        "mrs_swarm_get_download_stats": [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     }
     for name, args in sig.items():
         if os.environ.get("MRS_SWARM_LIB") and not hasattr(L, name):
@@ -675,6 +689,46 @@ class Swarm:
         _check(_lib.mrs_swarm_outputs_wait(self._h, int(ticket), C.byref(ptr), C.byref(cnt)))
         buf = (C.c_char * (cnt.value * OUTPUT_DTYPE.itemsize)).from_address(ptr.value)
         return np.frombuffer(buf, dtype=OUTPUT_DTYPE, count=cnt.value)
+
+    def get_poses(self, first=0, count=None):
+        """the pose array alone (publishPoses): position + orientation as a POSE_DTYPE array, one 56-B record per UAV"""
+        count = self.n - first if count is None else count
+        out = np.zeros(count, dtype=POSE_DTYPE)
+        assert out.dtype.itemsize == C.sizeof(UavPose)
+        _check(_lib.mrs_swarm_get_poses(self._h, first, count, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def get_poses_view(self, first=0, count=None):
+        """get_poses without the final host copy: a VIEW of the pose staging buffer, valid until the next get_poses* call (get_outputs*
+        calls leave it alone)"""
+        count = self.n - first if count is None else count
+        ptr = C.c_void_p()
+        _check(_lib.mrs_swarm_get_poses_view(self._h, first, count, C.byref(ptr)))
+        if count == 0:
+            return np.zeros(0, dtype=POSE_DTYPE)
+        buf = (C.c_char * (count * POSE_DTYPE.itemsize)).from_address(ptr.value)
+        return np.frombuffer(buf, dtype=POSE_DTYPE, count=count)
+
+    def get_poses_async(self, first=0, count=None):
+        """pipelined pose download (the contract of get_outputs_async, two pose blocks of its own); returns a ticket for poses_wait"""
+        count = self.n - first if count is None else count
+        t = C.c_int32()
+        _check(_lib.mrs_swarm_get_poses_async(self._h, first, count, C.byref(t)))
+        return int(t.value)
+
+    def poses_wait(self, ticket):
+        """blocks until the pose download of `ticket` has landed; a VIEW of the pinned block, valid until the second get_poses_async
+        call after the ticket's"""
+        ptr, cnt = C.c_void_p(), C.c_int32()
+        _check(_lib.mrs_swarm_poses_wait(self._h, int(ticket), C.byref(ptr), C.byref(cnt)))
+        buf = (C.c_char * (cnt.value * POSE_DTYPE.itemsize)).from_address(ptr.value)
+        return np.frombuffer(buf, dtype=POSE_DTYPE, count=cnt.value)
+
+    def download_stats(self):
+        """(pipelined packs issued by get_outputs_async / get_poses_async, packs issued again by a replay after a stall)"""
+        a, b = C.c_int64(), C.c_int64()
+        _check(_lib.mrs_swarm_get_download_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def input_staging(self, count, stride):
         """pinned host rows (count x stride doubles) to be filled with setInput payloads and sent by commit_input"""

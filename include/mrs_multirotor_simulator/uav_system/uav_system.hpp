@@ -764,6 +764,23 @@ public:
     return rows;
   }
   void commitInput(int first, int count, int mode, int stride) { mrs_throw_on_error(mrs_swarm_commit_input(s_, first, count, mode, stride)); }
+  // ---- device-resident callers (mrs_swarm_*_device): rows in device memory of this swarm's device, fenced against `stream` (the
+  // caller's hipStream_t as void*; nullptr = the null stream).  dtype MRS_DTYPE_F64 / MRS_DTYPE_F32; row k belongs to UAV first + k.
+  void setInputDevice(int first, int count, int mode, const void* dev_rows, int dtype, int stride, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_set_input_device(s_, first, count, mode, dev_rows, dtype, stride, stream));
+  }
+  // the MRS_OBS_* groups of `groups`, concatenated in bit order (mrs_swarm_gather_width elements per row)
+  void gatherDevice(int first, int count, uint32_t groups, void* dev_rows, int dtype, int stride, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_gather_device(s_, first, count, groups, dev_rows, dtype, stride, stream));
+  }
+  void crashedDevice(int first, int count, uint8_t* dev_out, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_get_crashed_device(s_, first, count, dev_out, stream));
+  }
+  // UavSystem(params, pos[k], heading[k]) again for the UAVs whose mask byte is set; command, mode and airframe are kept
+  void resetDevice(int first, int count, const uint8_t* dev_mask, const void* dev_pos, const void* dev_heading, int dtype, bool takeoff_patch_enabled,
+                   void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_reset_device(s_, first, count, dev_mask, dev_pos, dev_heading, dtype, takeoff_patch_enabled ? 1 : 0, stream));
+  }
   // the tail of the UavSystemRos constructor (:223-232) for the whole swarm: zero actuators, two makeStep(0.01)
   void warmUp() {
     std::vector<double> zeros((size_t)size() * MRS_MAX_MOTORS, 0.0);

@@ -445,6 +445,65 @@ int mrs_swarm_debug_neighbour_lists(mrs_swarm_t* s, int32_t crash, double reboun
 int mrs_swarm_last_step_kernel_ms(mrs_swarm_t* s, double* avg_ms, int32_t* n_launches);
 int mrs_swarm_set_profiling(mrs_swarm_t* s, int32_t mode);
 
+/* ---- device-resident callers: commands, observations, resets and crash flags in caller-owned DEVICE memory ----
+ * For a controller, policy or reward that lives on the same GPU (a torch module): the calls below batch the host-pointer calls named
+ * next to them, but read and write device rows of the swarm's device, so nothing crosses PCIe.  Row k always belongs to UAV first + k;
+ * a row holds `stride` elements of `dtype` (FP64, or FP32: a round-to-nearest cast of the FP64 value on the way out, widened exactly
+ * on the way in).
+ *
+ * Stream order: `ext_stream` (a hipStream_t; 0 = the null stream, which is what torch's default stream reports) is always honoured.
+ * Each call records an event on ext_stream and makes the swarm's stream wait on it, queues its kernel on the swarm's stream, records a
+ * second event there and makes ext_stream wait on that.  So what the caller queued on ext_stream before the call is what the kernel
+ * reads, work queued on ext_stream after the call sees the result, and a caching allocator cannot hand an input buffer out again while
+ * the kernel still reads it.  The two events belong to the swarm and are reused.  A caller that wants no fence passes the swarm's own
+ * stream (mrs_swarm_stream).
+ *
+ * Host waits: with collisions off none of these calls waits for the device.  With collisions on (lazily evaluated collision ticks,
+ * mrs_swarm_tick_n) they wait exactly where their host counterparts do: set_input_device and gather_device enter like
+ * mrs_swarm_set_input (the launches queued so far must have run, so a launch that turned into a no-op is replayed before the kernel is
+ * queued; a pending collision tick stays pending), get_crashed_device and reset_device like every state call (the pending collision
+ * tick is evaluated first: crash mode sets flags there).
+ *
+ * Every argument is checked on the host before anything is launched: ranges (MRS_ERR_RANGE), mode, dtype, stride >= width, the
+ * actuator width against n_motors, non-null pointers, and that every pointer is device memory of the swarm's device (MRS_ERR_ARG).
+ * On a sharded swarm gather, commands and crash flags act on the local shard; reset_device returns MRS_ERR_ARG there. */
+enum { MRS_DTYPE_F64 = 0, MRS_DTYPE_F32 = 1 };
+/* observation groups of mrs_swarm_gather_device, concatenated in bit order */
+enum {
+  MRS_OBS_POS      = 1 << 0, /* 3: x                                        MultirotorModel::State::x  multirotor_model.hpp:92 */
+  MRS_OBS_VEL      = 1 << 1, /* 3: v, world frame                                                 ::v  :93 */
+  MRS_OBS_VEL_BODY = 1 << 2, /* 3: R^T v, as mrs_uav_output_t.velocity_body          src/uav_system_ros.cpp:356-360 */
+  MRS_OBS_ROT      = 1 << 3, /* 9: R, row-major                                                   ::R  :95 */
+  MRS_OBS_QUAT     = 1 << 4, /* 4: x, y, z, w, as mrs_uav_output_t.orientation       src/uav_system_ros.cpp:350 */
+  MRS_OBS_OMEGA    = 1 << 5, /* 3: omega                                                      ::omega  :96 */
+  MRS_OBS_IMU      = 1 << 6, /* 3: UavSystem::getImuAcceleration                               uav_system.hpp:424 */
+  MRS_OBS_RPM      = 1 << 7, /* 8: motor_rpm, 0 past n_motors (as mrs_uav_state_t)          ::motor_rpm  :97 */
+  MRS_OBS_ALL      = 0xFF    /* 36 */
+};
+/* the device a swarm lives on (the device its pointers must belong to) */
+int mrs_swarm_device(const mrs_swarm_t* s, int32_t* device_id);
+/* elements per row of mrs_swarm_gather_device for `groups` (0 -> 0; unknown bits -> MRS_ERR_ARG); host only, no GPU */
+int mrs_swarm_gather_width(uint32_t groups, int32_t* width);
+/* UavSystem::setInput(...) x11 (uav_system.hpp:175-248) for UAVs [first, first+count) from device rows: the payload layouts and widths
+ * of mrs_swarm_set_input (ACTUATOR: min(stride, MRS_MAX_MOTORS) motors), written to the command columns and the mode by one kernel */
+int mrs_swarm_set_input_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, const void* dev_rows, int32_t dtype, int32_t stride,
+                               void* ext_stream);
+/* UavSystem::getState / getImuAcceleration (uav_system.hpp:386,424) and the odometry / pose fields of mrs_uav_output_t for UAVs
+ * [first, first+count): the MRS_OBS_* groups of `groups` into row k, elements [0, width); elements [width, stride) are not touched */
+int mrs_swarm_gather_device(mrs_swarm_t* s, int32_t first, int32_t count, uint32_t groups, void* dev_rows, int32_t dtype, int32_t stride,
+                            void* ext_stream);
+/* UavSystem::hasCrashed (uav_system.hpp:286) of UAVs [first, first+count): dev_out[k] = 1 or 0 */
+int mrs_swarm_get_crashed_device(mrs_swarm_t* s, int32_t first, int32_t count, uint8_t* dev_out, void* ext_stream);
+/* UavSystem(params, spawn_pos, spawn_heading) again (uav_system.hpp:144-153, what mrs_swarm_construct writes) for each UAV first + k
+ * whose dev_mask[k] != 0, on the device: state, IMU, external force and PID columns zero, R = AngleAxis(-heading[k], z), x = pos[k]
+ * (count x 3), the initial height = pos[k].z, crash flag cleared, takeoff patch = takeoff_patch_enabled.  dev_heading may be NULL
+ * (heading 0).  pos and heading are read for masked rows only.  The one difference from mrs_swarm_construct: the command, the
+ * feed-forwards, the input mode, the airframe type and the hold flag are KEPT (the host's mirror of the modes cannot follow a device-side
+ * mask without a synchronisation; a loop writes the next command right after the reset anyway).  The next collision tick repeats the
+ * neighbour search, as after a host write of positions.  MRS_ERR_ARG on a sharded swarm. */
+int mrs_swarm_reset_device(mrs_swarm_t* s, int32_t first, int32_t count, const uint8_t* dev_mask, const void* dev_pos, const void* dev_heading,
+                           int32_t dtype, int32_t takeoff_patch_enabled, void* ext_stream);
+
 #ifdef __cplusplus
 }
 #endif

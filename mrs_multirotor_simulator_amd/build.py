@@ -17,6 +17,7 @@ UNITS = [
     ("step_kernel_fast.hip", "fast"),
     ("collide.hip", "off"),
     ("outputs.hip", "off"),
+    ("device_io.hip", "off"),  # off: its observation rows equal the publisher payloads of outputs.hip bit for bit
     # host side (no kernels): C ABI, single-GPU tick, sharded tick, the three transports
     ("host_api.hip", "off"),
     ("tick_single.hip", "off"),
@@ -25,7 +26,7 @@ UNITS = [
     ("transport_local.hip", "off"),
     ("transport_peer.hip", "off"),
 ]
-DEPS = ["step_device.inc", "collide_device.inc", "swarm_layout.h", "host_internal.h", "sharded_protocol.h", os.path.join("..", "..", "include", "mrs_swarm.h")]
+DEPS = ["step_device.inc", "collide_device.inc", "swarm_layout.h", "pose_math.h", "host_internal.h", "sharded_protocol.h", os.path.join("..", "..", "include", "mrs_swarm.h")]
 
 
 def _hipcc():

@@ -1,0 +1,335 @@
+// device_io.hip — per-UAV I/O between the SoA state and caller-owned DEVICE rows, for callers whose controller, policy or reward
+// lives on the same GPU (a torch module): commands in, observations out, masked resets, crash flags, with no host copy on the way.
+// One lane per UAV; the state side is the coalesced field-major columns of swarm_layout.h, the caller side one row of `stride`
+// elements per UAV (FP64 or FP32).  The host entry points at the end validate every argument before anything is launched and fence
+// the caller's stream against the swarm's (include/mrs_swarm.h, "device-resident callers").
+#include "host_internal.h"
+#include "pose_math.h"
+
+namespace {
+
+// widths of the observation groups, in bit order (MRS_OBS_POS first)
+constexpr int kObsWidth[8] = {3, 3, 3, 9, 4, 3, 3, MRS_MAX_MOTORS};
+
+// Eigen::AngleAxisd(angle, UnitZ).toRotationMatrix() (Eigen/src/Geometry/AngleAxis.h), row-major out: the host's angle_axis_z
+// (host_api.hip) with the device's sin / cos
+__device__ __forceinline__ void angle_axis_z_dev(double angle, double R[9]) {
+  const double ax[3] = {0, 0, 1};
+  const double s = sin(angle), c = cos(angle);
+  const double sa[3] = {s * ax[0], s * ax[1], s * ax[2]};
+  const double ca[3] = {(1.0 - c) * ax[0], (1.0 - c) * ax[1], (1.0 - c) * ax[2]};
+  double       tmp;
+  tmp  = ca[0] * ax[1];
+  R[1] = tmp - sa[2];
+  R[3] = tmp + sa[2];
+  tmp  = ca[0] * ax[2];
+  R[2] = tmp + sa[1];
+  R[6] = tmp - sa[1];
+  tmp  = ca[1] * ax[2];
+  R[5] = tmp - sa[0];
+  R[7] = tmp + sa[0];
+  R[0] = ca[0] * ax[0] + c;
+  R[4] = ca[1] * ax[1] + c;
+  R[8] = ca[2] * ax[2] + c;
+}
+
+// observation groups of UAVs [first, first + count) into rows of `stride` elements, concatenated in bit order.  FP32 rows hold the
+// round-to-nearest cast of the FP64 value.  Direct per-lane stores, as k_pack_poses (LDS staging measured no better there).
+template <typename T>
+__global__ void __launch_bounds__(256) k_gather_rows(SwarmDev sw, int first, int count, uint32_t groups, T* rows, int stride) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  const int    i  = first + k;
+  const size_t np = (size_t)sw.npad;
+#define LD(f) sw.S[(size_t)(f) * np + i]
+  double v[3], R[9];
+  if (groups & (MRS_OBS_VEL | MRS_OBS_VEL_BODY)) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) v[c] = LD(F_V + c);
+  }
+  if (groups & (MRS_OBS_VEL_BODY | MRS_OBS_ROT | MRS_OBS_QUAT)) {
+#pragma unroll
+    for (int c = 0; c < 9; c++) R[c] = LD(F_R + c);
+  }
+  T* o = rows + (size_t)k * (size_t)stride;
+  if (groups & MRS_OBS_POS) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) o[c] = (T)LD(F_X + c);
+    o += 3;
+  }
+  if (groups & MRS_OBS_VEL) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) o[c] = (T)v[c];
+    o += 3;
+  }
+  if (groups & MRS_OBS_VEL_BODY) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) o[c] = (T)body_velocity(R, v, c);
+    o += 3;
+  }
+  if (groups & MRS_OBS_ROT) {
+#pragma unroll
+    for (int c = 0; c < 9; c++) o[c] = (T)R[c];
+    o += 9;
+  }
+  if (groups & MRS_OBS_QUAT) {
+    double q[4];
+    quat_from_matrix(R, q);
+#pragma unroll
+    for (int c = 0; c < 4; c++) o[c] = (T)q[c];
+    o += 4;
+  }
+  if (groups & MRS_OBS_OMEGA) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) o[c] = (T)LD(F_W + c);
+    o += 3;
+  }
+  if (groups & MRS_OBS_IMU) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) o[c] = (T)LD(F_IMU + c);
+    o += 3;
+  }
+  if (groups & MRS_OBS_RPM) {  // 0 past n_motors, as k_pack_states
+    const int nm = sw.T[sw.F[i] >> FLAG_TYPE_SHIFT].n_motors;
+#pragma unroll
+    for (int m = 0; m < MRS_MAX_MOTORS; m++) o[m] = (T)(m < nm ? LD(F_RPM + m) : 0.0);
+  }
+#undef LD
+}
+
+// setInput payload rows (FP64 or FP32, device-resident) into the command columns F_CMD + j, and the mode bits of the flag word: what
+// mrs_swarm_set_input's column uploads + flag update do, in one launch (k_unpack_rows with another source)
+template <typename T>
+__global__ void __launch_bounds__(256) k_scatter_cmd(SwarmDev sw, const T* rows, int stride, int width, int first, int count, uint32_t mode_bits) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  const int    i  = first + k;
+  const size_t np = (size_t)sw.npad;
+  const T*     r  = rows + (size_t)k * (size_t)stride;
+  for (int j = 0; j < width; j++) sw.S[(size_t)(F_CMD + j) * np + i] = (double)r[j];
+  sw.F[i] = (sw.F[i] & ~FLAG_MODE_MASK) | mode_bits;
+}
+
+// mrs_swarm_construct(params of the UAV's own type, pos, heading) for the UAVs whose mask byte is set, without the host: state,
+// IMU, external force and PID columns zero, R = AngleAxis(-heading, z), x = pos, _initial_pos_ z = pos z; crashed and v_prev-split
+// cleared, takeoff patch as given.  Commands, feed-forwards, the mode / feed-forward / type bits and the hold flag are kept.
+template <typename T>
+__global__ void __launch_bounds__(256) k_reset_masked(SwarmDev sw, int first, int count, const uint8_t* mask, const T* pos, const T* heading,
+                                                      uint32_t takeoff) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count || !mask[k]) return;
+  const int    i  = first + k;
+  const size_t np = (size_t)sw.npad;
+#define ST(f) sw.S[(size_t)(f) * np + i]
+  double x[3], R[9];
+#pragma unroll
+  for (int c = 0; c < 3; c++) x[c] = (double)pos[(size_t)k * 3 + c];
+  angle_axis_z_dev(-(heading ? (double)heading[k] : 0.0), R);
+#pragma unroll
+  for (int c = 0; c < 3; c++) ST(F_X + c) = x[c];
+#pragma unroll
+  for (int f = F_V; f < F_R; f++) ST(f) = 0.0;  // v, v_prev
+#pragma unroll
+  for (int c = 0; c < 9; c++) ST(F_R + c) = R[c];
+#pragma unroll
+  for (int f = F_W; f < F_INITZ; f++) ST(f) = 0.0;  // omega, motor rpm, IMU, external force
+  ST(F_INITZ) = x[2];
+#pragma unroll
+  for (int f = F_PID; f < F_CMD; f++) ST(f) = 0.0;
+#undef ST
+  sw.F[i] = (sw.F[i] & ~(FLAG_CRASHED | FLAG_VPREV_SPLIT | FLAG_TAKEOFF)) | takeoff;
+}
+
+// UavSystem::hasCrashed of UAVs [first, first + count) as bytes
+__global__ void __launch_bounds__(256) k_crashed_u8(const uint32_t* F, int first, int count, uint8_t* out) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  out[k] = (F[first + k] & FLAG_CRASHED) ? 1 : 0;
+}
+
+inline dim3 grid_of(int count) { return dim3((unsigned)((count + 255) / 256)); }
+
+// ---- host side ----
+size_t dtype_bytes(int dtype) { return dtype == MRS_DTYPE_F32 ? sizeof(float) : sizeof(double); }
+
+int check_dtype(int dtype) {
+  if (dtype != MRS_DTYPE_F64 && dtype != MRS_DTYPE_F32) return fail(MRS_ERR_ARG, "dtype must be MRS_DTYPE_F64 or MRS_DTYPE_F32");
+  return MRS_OK;
+}
+
+// `p` must be device memory of the swarm's device holding at least `bytes` bytes from p on (the end is checked against the allocation
+// that holds p where the runtime can tell)
+int check_device_ptr(const mrs_swarm* s, const void* p, size_t bytes, const char* what) {
+  if (!p) return fail(MRS_ERR_ARG, std::string(what) + ": null pointer");
+  hipPointerAttribute_t a;
+  memset(&a, 0, sizeof a);
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();  // (not sticky: a later launch must not report it)
+    return fail(MRS_ERR_ARG, std::string(what) + ": not a pointer the HIP runtime knows (host memory?)");
+  }
+  if (a.type != hipMemoryTypeDevice) return fail(MRS_ERR_ARG, std::string(what) + ": not device memory");
+  if (a.device != s->device)
+    return fail(MRS_ERR_ARG, std::string(what) + ": memory of device " + std::to_string(a.device) + ", the swarm lives on device " + std::to_string(s->device));
+  hipDeviceptr_t base = nullptr;
+  size_t         size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) == hipSuccess) {
+    if ((const char*)p + bytes > (const char*)base + size) return fail(MRS_ERR_ARG, std::string(what) + ": the rows extend past the end of their allocation");
+  } else {
+    (void)hipGetLastError();
+  }
+  return MRS_OK;
+}
+
+// bytes spanned by `count` rows of `stride` elements of which the first `width` are used
+size_t rows_bytes(int count, int stride, int width, int dtype) {
+  return ((size_t)(count - 1) * (size_t)stride + (size_t)width) * dtype_bytes(dtype);
+}
+
+// the stream fence of every call: the swarm's stream waits for what the caller queued on `ext` so far ...
+int fence_in(mrs_swarm* s, hipStream_t ext) {
+  if (ext == s->stream) return MRS_OK;
+  if (!s->ev_dio_in) HIPCHK(hipEventCreateWithFlags(&s->ev_dio_in, hipEventDisableTiming));
+  if (!s->ev_dio_out) HIPCHK(hipEventCreateWithFlags(&s->ev_dio_out, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(s->ev_dio_in, ext));
+  HIPCHK(hipStreamWaitEvent(s->stream, s->ev_dio_in, 0));
+  return MRS_OK;
+}
+// ... and `ext` waits for the kernel of the call
+int fence_out(mrs_swarm* s, hipStream_t ext) {
+  if (ext == s->stream) return MRS_OK;
+  HIPCHK(hipEventRecord(s->ev_dio_out, s->stream));
+  HIPCHK(hipStreamWaitEvent(ext, s->ev_dio_out, 0));
+  return MRS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrs_swarm_device(const mrs_swarm_t* s, int32_t* device_id) {
+  MRS_LOCK(s);
+  if (!s || !device_id) return fail(MRS_ERR_ARG, "null argument");
+  *device_id = s->device;
+  return MRS_OK;
+}
+
+int mrs_swarm_gather_width(uint32_t groups, int32_t* width) {
+  if (!width) return fail(MRS_ERR_ARG, "null width");
+  if (groups & ~(uint32_t)MRS_OBS_ALL) return fail(MRS_ERR_ARG, "unknown observation group bits");
+  int w = 0;
+  for (int b = 0; b < 8; b++)
+    if (groups & (1u << b)) w += kObsWidth[b];
+  *width = w;
+  return MRS_OK;
+}
+
+int mrs_swarm_set_input_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, const void* dev_rows, int32_t dtype, int32_t stride,
+                               void* ext_stream) {
+  MRS_ENTER_COMMANDS(s);
+  int rc = check_range(s, first, count);
+  if (rc) return rc;
+  if (mode < MRS_INPUT_UNKNOWN || mode > MRS_POSITION_CMD) return fail(MRS_ERR_ARG, "bad input mode");
+  if ((rc = check_dtype(dtype))) return rc;
+  if (count == 0) return MRS_OK;
+  int width = 0;  // the payload widths of mrs_swarm_set_input
+  switch (mode) {
+    case MRS_INPUT_UNKNOWN: width = 0; break;
+    case MRS_ACTUATOR_CMD: width = stride < MRS_MAX_MOTORS ? stride : MRS_MAX_MOTORS; break;
+    case MRS_ATTITUDE_CMD: width = 10; break;
+    case MRS_TILT_HDG_RATE_CMD: width = 5; break;
+    default: width = 4; break;
+  }
+  if (width > 0) {
+    if (stride < width || width < 1) return fail(MRS_ERR_ARG, "stride too small for this mode");
+    if ((rc = check_device_ptr(s, dev_rows, rows_bytes(count, stride, width, dtype), "dev_rows"))) return rc;
+  }
+  if (mode == MRS_ACTUATOR_CMD && width < MRS_MAX_MOTORS) {
+    for (int k = 0; k < count; k++)
+      if (s->keys[s->uav_type[(size_t)first + k]].mp.n_motors > width) return fail(MRS_ERR_ARG, "actuator payload narrower than n_motors");
+  }
+  HIPCHK(hipSetDevice(s->device));
+  hipStream_t ext = (hipStream_t)ext_stream;
+  if ((rc = fence_in(s, ext))) return rc;
+  const uint32_t mode_bits = (uint32_t)mode << FLAG_MODE_SHIFT;
+  if (dtype == MRS_DTYPE_F32)
+    hipLaunchKernelGGL(k_scatter_cmd<float>, grid_of(count), dim3(256), 0, s->stream, s->view(), static_cast<const float*>(dev_rows), stride, width,
+                       first, count, mode_bits);
+  else
+    hipLaunchKernelGGL(k_scatter_cmd<double>, grid_of(count), dim3(256), 0, s->stream, s->view(), static_cast<const double*>(dev_rows), stride,
+                       width, first, count, mode_bits);
+  HIPCHK(hipGetLastError());
+  if ((rc = fence_out(s, ext))) return rc;
+  // host mirror of the modes (kernel variant): a loop that keeps its mode finds nothing to change
+  const uint8_t* m    = s->uav_mode.data() + first;
+  unsigned       diff = 0;
+  for (int k = 0; k < count; k++) diff |= (unsigned)(m[k] ^ (uint8_t)mode);
+  if (diff) track_mode(s, first, count, mode);
+  return MRS_OK;
+}
+
+int mrs_swarm_gather_device(mrs_swarm_t* s, int32_t first, int32_t count, uint32_t groups, void* dev_rows, int32_t dtype, int32_t stride,
+                            void* ext_stream) {
+  MRS_ENTER_COMMANDS(s);
+  int rc = check_range(s, first, count);
+  if (rc) return rc;
+  int32_t width = 0;
+  if ((rc = mrs_swarm_gather_width(groups, &width))) return rc;
+  if (width == 0) return fail(MRS_ERR_ARG, "no observation group selected");
+  if ((rc = check_dtype(dtype))) return rc;
+  if (stride < width) return fail(MRS_ERR_ARG, "stride smaller than the width of the selected groups");
+  if (count == 0) return MRS_OK;
+  if ((rc = check_device_ptr(s, dev_rows, rows_bytes(count, stride, width, dtype), "dev_rows"))) return rc;
+  HIPCHK(hipSetDevice(s->device));
+  if ((groups & MRS_OBS_RPM) && (rc = upload_types(s, s->table_dt > 0 ? s->table_dt : 0.001))) return rc;  // (n_motors of the type table)
+  hipStream_t ext = (hipStream_t)ext_stream;
+  if ((rc = fence_in(s, ext))) return rc;
+  if (dtype == MRS_DTYPE_F32)
+    hipLaunchKernelGGL(k_gather_rows<float>, grid_of(count), dim3(256), 0, s->stream, s->view(), first, count, groups, static_cast<float*>(dev_rows), stride);
+  else
+    hipLaunchKernelGGL(k_gather_rows<double>, grid_of(count), dim3(256), 0, s->stream, s->view(), first, count, groups, static_cast<double*>(dev_rows),
+                       stride);
+  HIPCHK(hipGetLastError());
+  return fence_out(s, ext);
+}
+
+int mrs_swarm_get_crashed_device(mrs_swarm_t* s, int32_t first, int32_t count, uint8_t* dev_out, void* ext_stream) {
+  MRS_ENTER(s);
+  int rc = check_range(s, first, count);
+  if (rc) return rc;
+  if (count == 0) return MRS_OK;
+  if ((rc = check_device_ptr(s, dev_out, (size_t)count, "dev_out"))) return rc;
+  HIPCHK(hipSetDevice(s->device));
+  hipStream_t ext = (hipStream_t)ext_stream;
+  if ((rc = fence_in(s, ext))) return rc;
+  hipLaunchKernelGGL(k_crashed_u8, grid_of(count), dim3(256), 0, s->stream, s->dF, first, count, dev_out);
+  HIPCHK(hipGetLastError());
+  return fence_out(s, ext);
+}
+
+int mrs_swarm_reset_device(mrs_swarm_t* s, int32_t first, int32_t count, const uint8_t* dev_mask, const void* dev_pos, const void* dev_heading,
+                           int32_t dtype, int32_t takeoff_patch_enabled, void* ext_stream) {
+  MRS_ENTER(s);
+  int rc = check_range(s, first, count);
+  if (rc) return rc;
+  if (s->comm_world > 0) return fail(MRS_ERR_ARG, "mrs_swarm_reset_device: not on a sharded swarm");
+  if ((rc = check_dtype(dtype))) return rc;
+  if (count == 0) return MRS_OK;
+  if ((rc = check_device_ptr(s, dev_mask, (size_t)count, "dev_mask"))) return rc;
+  if ((rc = check_device_ptr(s, dev_pos, rows_bytes(count, 3, 3, dtype), "dev_pos"))) return rc;
+  if (dev_heading && (rc = check_device_ptr(s, dev_heading, rows_bytes(count, 1, 1, dtype), "dev_heading"))) return rc;
+  HIPCHK(hipSetDevice(s->device));
+  hipStream_t ext = (hipStream_t)ext_stream;
+  if ((rc = fence_in(s, ext))) return rc;
+  const uint32_t takeoff = takeoff_patch_enabled ? FLAG_TAKEOFF : 0u;
+  if (dtype == MRS_DTYPE_F32)
+    hipLaunchKernelGGL(k_reset_masked<float>, grid_of(count), dim3(256), 0, s->stream, s->view(), first, count, dev_mask,
+                       static_cast<const float*>(dev_pos), static_cast<const float*>(dev_heading), takeoff);
+  else
+    hipLaunchKernelGGL(k_reset_masked<double>, grid_of(count), dim3(256), 0, s->stream, s->view(), first, count, dev_mask,
+                       static_cast<const double*>(dev_pos), static_cast<const double*>(dev_heading), takeoff);
+  HIPCHK(hipGetLastError());
+  s->nbr_dirty = true;  // positions changed under the neighbour lists (what put_column notes for a host write of F_X)
+  return fence_out(s, ext);
+}
+
+}  // extern "C"

@@ -580,6 +580,8 @@ int mrs_swarm_destroy(mrs_swarm_t* s) {
   if (s->stream_i) (void)hipStreamDestroy(s->stream_i);
   if (s->ev_join_b) (void)hipEventDestroy(s->ev_join_b);
   if (s->ev_copy) (void)hipEventDestroy(s->ev_copy);
+  if (s->ev_dio_in) (void)hipEventDestroy(s->ev_dio_in);
+  if (s->ev_dio_out) (void)hipEventDestroy(s->ev_dio_out);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
   return MRS_OK;

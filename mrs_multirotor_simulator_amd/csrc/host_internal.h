@@ -3,6 +3,7 @@
 //   host_api.hip          C ABI: parameters, lifetime, construction, commands, state access, publisher payloads, probes
 //   tick_single.hip       the hot path of one GPU: makeStep launches, lazily evaluated collision ticks (fused launches, stall + replay)
 //   tick_sharded.hip      the sharded tick: communicator bookkeeping, search path, serial and split segments of the export-set exchange
+//   device_io.hip         C ABI + kernels for device-resident callers: commands, observations, resets, crash flags in device rows
 //   transport_rccl.hip    RCCL bound at run time (dlopen)
 //   transport_local.hip   in-process loopback group, caller-supplied all-gather, measurement stand-in
 //   transport_peer.hip    peer-window exchange (direct writes into the peers' device memory)
@@ -284,6 +285,8 @@ struct mrs_swarm {
   };
   InSlot  islot[2];
   int     in_turn = 0;   // the block the last mrs_swarm_input_staging handed out
+  // device-resident callers (device_io.hip): the caller's stream -> swarm's stream fence and back, created at first use
+  hipEvent_t ev_dio_in = nullptr, ev_dio_out = nullptr;
   // collision scratch
   PosRecord*   dRec = nullptr;
   CollideWork* cwork = nullptr;

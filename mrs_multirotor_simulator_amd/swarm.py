@@ -110,7 +110,14 @@ ABI_SYMBOLS = [
     "mrs_swarm_debug_search_ms", "mrs_swarm_debug_neighbour_lists", "mrs_swarm_clone_resized", "mrs_swarm_copy_uavs", "mrs_swarm_step_range", "mrs_swarm_get_states",
     "mrs_swarm_get_outputs_async", "mrs_swarm_outputs_wait", "mrs_cell_order",
     "mrs_swarm_get_poses", "mrs_swarm_get_poses_view", "mrs_swarm_get_poses_async", "mrs_swarm_poses_wait", "mrs_swarm_get_download_stats",
+    "mrs_swarm_device", "mrs_swarm_gather_width", "mrs_swarm_set_input_device", "mrs_swarm_gather_device", "mrs_swarm_get_crashed_device",
+    "mrs_swarm_reset_device",
 ]
+
+# device-resident callers (mrs_swarm_*_device): row element types and the observation groups of mrs_swarm_gather_device, in bit order
+DTYPE_F64, DTYPE_F32 = 0, 1
+OBS_POS, OBS_VEL, OBS_VEL_BODY, OBS_ROT, OBS_QUAT, OBS_OMEGA, OBS_IMU, OBS_RPM = (1 << b for b in range(8))
+OBS_ALL = 0xFF
 
 STATE_DTYPE = np.dtype([("x", "f8", 3), ("v", "f8", 3), ("v_prev", "f8", 3), ("R", "f8", (3, 3)), ("omega", "f8", 3), ("motor_rpm", "f8", 8),
                         ("imu_acceleration", "f8", 3), ("crashed", "i4"), ("n_motors", "i4")])
@@ -314,6 +321,12 @@ def load_library():
         "mrs_swarm_get_poses_async": [vp, i32, i32, ip],
         "mrs_swarm_poses_wait": [vp, i32, C.POINTER(vp), ip],
         "mrs_swarm_get_download_stats": [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+        "mrs_swarm_device": [vp, ip],
+        "mrs_swarm_gather_width": [C.c_uint32, ip],
+        "mrs_swarm_set_input_device": [vp, i32, i32, i32, vp, i32, i32, vp],
+        "mrs_swarm_gather_device": [vp, i32, i32, C.c_uint32, vp, i32, i32, vp],
+        "mrs_swarm_get_crashed_device": [vp, i32, i32, vp, vp],
+        "mrs_swarm_reset_device": [vp, i32, i32, vp, vp, vp, i32, i32, vp],
     }
     for name, args in sig.items():
         if os.environ.get("MRS_SWARM_LIB") and not hasattr(L, name):
@@ -341,6 +354,13 @@ def _arr(a, shape=None):
         return None
     a = np.ascontiguousarray(a, dtype=np.float64)
     return a.reshape(shape) if shape is not None else a
+
+
+def gather_width(groups):
+    """elements per row of Swarm.gather_device for the OBS_* bits in `groups` (host only, no GPU)"""
+    w = C.c_int32()
+    _check(load_library().mrs_swarm_gather_width(C.c_uint32(int(groups)), C.byref(w)))
+    return int(w.value)
 
 
 def default_params():
@@ -740,6 +760,28 @@ class Swarm:
 
     def commit_input(self, first, count, mode, stride):
         _check(_lib.mrs_swarm_commit_input(self._h, int(first), int(count), int(mode), int(stride)))
+
+    # -- device-resident callers: raw bindings, pointers and streams as ints (mrs_multirotor_simulator_amd.tensors wraps them for torch) --
+    def device(self):
+        """the device the swarm lives on"""
+        d = C.c_int32()
+        _check(_lib.mrs_swarm_device(self._h, C.byref(d)))
+        return int(d.value)
+
+    def set_input_device(self, first, count, mode, dev_rows, dtype, stride, ext_stream):
+        _check(_lib.mrs_swarm_set_input_device(self._h, int(first), int(count), int(mode), dev_rows or None, int(dtype), int(stride),
+                                               ext_stream or None))
+
+    def gather_device(self, first, count, groups, dev_rows, dtype, stride, ext_stream):
+        _check(_lib.mrs_swarm_gather_device(self._h, int(first), int(count), C.c_uint32(int(groups)), dev_rows or None, int(dtype), int(stride),
+                                            ext_stream or None))
+
+    def get_crashed_device(self, first, count, dev_out, ext_stream):
+        _check(_lib.mrs_swarm_get_crashed_device(self._h, int(first), int(count), dev_out or None, ext_stream or None))
+
+    def reset_device(self, first, count, dev_mask, dev_pos, dev_heading, dtype, takeoff_patch_enabled, ext_stream):
+        _check(_lib.mrs_swarm_reset_device(self._h, int(first), int(count), dev_mask or None, dev_pos or None, dev_heading or None, int(dtype),
+                                           int(bool(takeoff_patch_enabled)), ext_stream or None))
 
     def get_diag(self):
         d = Diag()

@@ -1,0 +1,138 @@
+"""torch tensors in and out of a Swarm without the host: commands, observations, masked resets and crash flags for a controller,
+policy or reward that lives on the swarm's GPU (include/mrs_swarm.h, "device-resident callers").
+
+Every call passes torch's current stream of the swarm's device as the caller stream: the library fences its own stream against it, so
+tensors written on that stream before the call are what the kernel reads, and work queued after the call sees the result.  Tensors are
+checked (check_tensor) before any library call: CPU tensors, tensors of another device, rows whose last dimension is not contiguous and
+wrong dtypes or shapes are refused with a ValueError.  Row k of every tensor belongs to UAV first + k.
+
+Imports torch; the package itself does not.
+"""
+import torch
+
+from .swarm import (ACTUATOR_CMD, ATTITUDE_CMD, DTYPE_F32, DTYPE_F64, INPUT_UNKNOWN, MAX_MOTORS, OBS_ALL, OBS_IMU, OBS_OMEGA,  # noqa: F401
+                    OBS_POS, OBS_QUAT, OBS_ROT, OBS_RPM, OBS_VEL, OBS_VEL_BODY, TILT_HDG_RATE_CMD, gather_width)
+
+_DTYPES = {torch.float64: DTYPE_F64, torch.float32: DTYPE_F32}
+
+
+def check_tensor(t, rows, min_width, dtype, device_index):
+    """Refuse `t` unless it is a tensor on cuda:`device_index` of `dtype` with `rows` rows whose last dimension is contiguous.
+    min_width None: a vector of `rows` elements; else a [rows, >= min_width] matrix.  Returns the row stride in elements (the
+    distance between two rows; the columns past min_width are padding the library does not touch).  Needs no GPU."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"expected a torch.Tensor, got {type(t).__name__}")
+    if t.device.type != "cuda":
+        raise ValueError(f"tensor is on {t.device}: device-resident calls need a tensor on cuda:{device_index} (use the host calls of Swarm "
+                         "for CPU data)")
+    if t.device.index != device_index:
+        raise ValueError(f"tensor is on {t.device}, the swarm lives on cuda:{device_index}")
+    if t.dtype != dtype:
+        raise ValueError(f"tensor has dtype {t.dtype}, expected {dtype}")
+    if min_width is None:
+        if t.dim() != 1 or t.shape[0] != rows:
+            raise ValueError(f"expected a vector of {rows} elements, got shape {tuple(t.shape)}")
+        if rows > 1 and t.stride(0) != 1:
+            raise ValueError(f"vector is not contiguous (stride {t.stride(0)})")
+        return 1
+    if t.dim() != 2 or t.shape[0] != rows or t.shape[1] < min_width:
+        raise ValueError(f"expected a [{rows}, >= {min_width}] matrix, got shape {tuple(t.shape)}")
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        raise ValueError(f"rows are not contiguous: the stride of the last dimension is {t.stride(1)}, must be 1")
+    stride = t.stride(0) if rows > 1 else t.shape[1]
+    if stride < t.shape[1]:
+        raise ValueError(f"rows overlap: row stride {stride} < row width {t.shape[1]}")
+    return stride
+
+
+def _dtype_code(dtype):
+    if dtype not in _DTYPES:
+        raise ValueError(f"dtype must be torch.float32 or torch.float64, got {dtype}")
+    return _DTYPES[dtype]
+
+
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _count(swarm, first, count):
+    return swarm.n - first if count is None else int(count)
+
+
+def command_width(mode, n_cols):
+    """payload elements per row of a setInput mode (mrs_swarm_set_input; ACTUATOR: the row's own width, at most MAX_MOTORS)"""
+    if mode == INPUT_UNKNOWN:
+        return 0
+    if mode == ACTUATOR_CMD:
+        return min(n_cols, MAX_MOTORS)
+    if mode == ATTITUDE_CMD:
+        return 10
+    if mode == TILT_HDG_RATE_CMD:
+        return 5
+    return 4
+
+
+def gather(swarm, groups, first=0, count=None, dtype=torch.float32, out=None):
+    """The OBS_* groups of UAVs [first, first + count) as a [count, gather_width(groups)] tensor on the swarm's device (or into `out`, a
+    [count, >= width] tensor whose columns past the width are left alone)."""
+    count = _count(swarm, first, count)
+    width = gather_width(groups)
+    dev = swarm.device()
+    if out is None:
+        out = torch.empty((count, width), dtype=dtype, device=torch.device("cuda", dev))
+    code = _dtype_code(out.dtype)
+    stride = check_tensor(out, count, width, out.dtype, dev)
+    swarm.gather_device(first, count, groups, out.data_ptr(), code, stride, _stream(dev))
+    return out[:, :width] if out.shape[1] > width else out
+
+
+def set_input(swarm, mode, rows, first=0):
+    """UavSystem::setInput of `mode` for UAVs [first, first + rows.shape[0]) from a [count, width] FP32 / FP64 tensor (the payload layouts of
+    Swarm.set_input).  ACTUATOR rows must be dense: their width is the number of motors given."""
+    dev = swarm.device()
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2:
+        raise ValueError("rows must be a [count, width] tensor")
+    code = _dtype_code(rows.dtype)
+    count = rows.shape[0]
+    width = command_width(mode, rows.shape[1])
+    stride = check_tensor(rows, count, width, rows.dtype, dev)
+    if mode == ACTUATOR_CMD and count > 1 and stride != rows.shape[1]:
+        raise ValueError("actuator rows must be dense (row stride == number of motors)")
+    ptr = rows.data_ptr() if width > 0 and count > 0 else 0
+    swarm.set_input_device(first, count, mode, ptr, code, stride, _stream(dev))
+
+
+def crashed(swarm, first=0, count=None, out=None):
+    """UavSystem::hasCrashed of UAVs [first, first + count) as a bool tensor on the swarm's device"""
+    count = _count(swarm, first, count)
+    dev = swarm.device()
+    if out is None:
+        out = torch.empty(count, dtype=torch.bool, device=torch.device("cuda", dev))
+    check_tensor(out, count, None, torch.bool, dev)
+    swarm.get_crashed_device(first, count, out.data_ptr(), _stream(dev))
+    return out
+
+
+def reset(swarm, mask, pos, heading=None, takeoff=True, first=0):
+    """UavSystem(params, pos[k], heading[k]) again, on the device, for every UAV first + k with mask[k] set (mask: bool or uint8 vector of
+    count elements; pos: [count, 3], heading: [count] or None, both FP32 or FP64, read for masked rows only).  Commands, feed-forwards,
+    mode, airframe and hold flag are kept (mrs_swarm_reset_device)."""
+    dev = swarm.device()
+    if not isinstance(mask, torch.Tensor):
+        raise ValueError("mask must be a tensor")
+    count = mask.shape[0] if mask.dim() >= 1 else -1
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"mask has dtype {mask.dtype}, expected torch.bool or torch.uint8")
+    check_tensor(mask, count, None, mask.dtype, dev)
+    if not isinstance(pos, torch.Tensor):
+        raise ValueError("pos must be a tensor")
+    code = _dtype_code(pos.dtype)
+    if check_tensor(pos, count, 3, pos.dtype, dev) != 3 and count > 1:
+        raise ValueError("pos rows must be dense [count, 3]")
+    if pos.shape[1] != 3:
+        raise ValueError(f"pos must be [count, 3], got shape {tuple(pos.shape)}")
+    hptr = 0
+    if heading is not None:
+        check_tensor(heading, count, None, pos.dtype, dev)
+        hptr = heading.data_ptr()
+    swarm.reset_device(first, count, mask.data_ptr(), pos.data_ptr(), hptr, code, takeoff, _stream(dev))

@@ -773,6 +773,12 @@ public:
   void gatherDevice(int first, int count, uint32_t groups, void* dev_rows, int dtype, int stride, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_gather_device(s_, first, count, groups, dev_rows, dtype, stride, stream));
   }
+  // the k nearest other UAVs within `radius` of each UAV of [first, first + count): k slots of the MRS_NN_* fields per row (dev_rows
+  // may be null when fields == 0), their indices (-1: empty) and the number listed; null outputs are skipped
+  void nearestDevice(int first, int count, int k, double radius, uint32_t fields, void* dev_rows, int dtype, int stride, int32_t* dev_index,
+                     int index_stride, int32_t* dev_count, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_nearest_device(s_, first, count, k, radius, fields, dev_rows, dtype, stride, dev_index, index_stride, dev_count, stream));
+  }
   void crashedDevice(int first, int count, uint8_t* dev_out, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_get_crashed_device(s_, first, count, dev_out, stream));
   }

@@ -504,6 +504,37 @@ int mrs_swarm_get_crashed_device(mrs_swarm_t* s, int32_t first, int32_t count, u
 int mrs_swarm_reset_device(mrs_swarm_t* s, int32_t first, int32_t count, const uint8_t* dev_mask, const void* dev_pos, const void* dev_heading,
                            int32_t dtype, int32_t takeoff_patch_enabled, void* ext_stream);
 
+/* ---- nearest-neighbour observations: the k closest other UAVs within a sensing radius, for swarm policies on the device ----
+ * Query set: UAVs [first, first+count).  Candidates: every UAV of the swarm with a finite position, crashed ones included (obstacles);
+ * a UAV is never its own neighbour, and a query UAV with a non-finite position gets an empty row.  The neighbours of i are the UAVs
+ * j != i with d2 < radius * radius, d2 = ((dx*dx) + dy*dy) + dz*dz, dx = x_j - x_i, all in FP64 without FMA contraction (radius * radius
+ * rounded once on the host).  The first k of them by ascending (d2, j) are listed, nearest first; ties in d2 go to the lower index, so
+ * the result does not depend on arrival order or grid layout.
+ * Output row r belongs to UAV first + r: k slots of mrs_nearest_width(fields, 1) elements each, the MRS_NN_* fields of the slot
+ * concatenated in bit order (FP64, or the round-to-nearest FP32 cast); empty slots are 0, their index -1.  Elements [k*width, stride) of
+ * a row and [k, index_stride) of an index row are not touched.  dev_index (count x index_stride int32) and dev_count (count int32: the
+ * neighbours listed, at most k) may be NULL; dev_rows may be NULL when fields == 0; at least one output must be given.
+ * State, stream fence and host waits are those of mrs_swarm_gather_device (the call enters like it: a pending collision tick stays
+ * pending).  The call writes no simulation state and leaves the collision pass's tables alone: its scratch is its own (grown on demand,
+ * freed by mrs_swarm_destroy, not copied by clone).  Every argument is checked before anything is launched: ranges (MRS_ERR_RANGE),
+ * 1 <= k <= MRS_NN_MAX_K, a finite radius > 0, known field bits, stride >= k * width, index_stride >= k, and that every given pointer
+ * is device memory of the swarm's device large enough for its rows (MRS_ERR_ARG).  MRS_ERR_ARG on a sharded swarm. */
+/* fields of one neighbour slot of mrs_swarm_nearest_device, concatenated in bit order */
+enum {
+  MRS_NN_REL_POS      = 1 << 0, /* 3: x_j - x_i, world frame */
+  MRS_NN_REL_POS_BODY = 1 << 1, /* 3: R_i^T (x_j - x_i), as MRS_OBS_VEL_BODY forms R^T v */
+  MRS_NN_REL_VEL      = 1 << 2, /* 3: v_j - v_i, world frame */
+  MRS_NN_REL_VEL_BODY = 1 << 3, /* 3: R_i^T (v_j - v_i) */
+  MRS_NN_DIST         = 1 << 4, /* 1: sqrt(d2) */
+  MRS_NN_ALL          = 0x1F    /* 13 */
+};
+enum { MRS_NN_MAX_K = 32 };
+/* elements per row of mrs_swarm_nearest_device: k * (width of one slot of `fields`) (fields 0 -> 0; unknown bits or k outside
+ * [1, MRS_NN_MAX_K] -> MRS_ERR_ARG); host only, no GPU */
+int mrs_nearest_width(uint32_t fields, int32_t k, int32_t* width);
+int mrs_swarm_nearest_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t k, double radius, uint32_t fields, void* dev_rows, int32_t dtype,
+                             int32_t stride, int32_t* dev_index, int32_t index_stride, int32_t* dev_count, void* ext_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ UNITS = [
     ("collide.hip", "off"),
     ("outputs.hip", "off"),
     ("device_io.hip", "off"),  # off: its observation rows equal the publisher payloads of outputs.hip bit for bit
+    ("nearest.hip", "off"),  # off: d2 = ((dx*dx) + dy*dy) + dz*dz literally, which a numpy restatement reproduces bit for bit
     # host side (no kernels): C ABI, single-GPU tick, sharded tick, the three transports
     ("host_api.hip", "off"),
     ("tick_single.hip", "off"),

@@ -149,7 +149,11 @@ __global__ void __launch_bounds__(256) k_crashed_u8(const uint32_t* F, int first
 
 inline dim3 grid_of(int count) { return dim3((unsigned)((count + 255) / 256)); }
 
-// ---- host side ----
+}  // namespace
+
+// ---- host side (shared with nearest.hip through host_internal.h) ----
+namespace mrs_host {
+
 size_t dtype_bytes(int dtype) { return dtype == MRS_DTYPE_F32 ? sizeof(float) : sizeof(double); }
 
 int check_dtype(int dtype) {
@@ -202,7 +206,7 @@ int fence_out(mrs_swarm* s, hipStream_t ext) {
   return MRS_OK;
 }
 
-}  // namespace
+}  // namespace mrs_host
 
 extern "C" {
 

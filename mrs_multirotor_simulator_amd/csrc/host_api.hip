@@ -582,6 +582,7 @@ int mrs_swarm_destroy(mrs_swarm_t* s) {
   if (s->ev_copy) (void)hipEventDestroy(s->ev_copy);
   if (s->ev_dio_in) (void)hipEventDestroy(s->ev_dio_in);
   if (s->ev_dio_out) (void)hipEventDestroy(s->ev_dio_out);
+  nearest_release(s);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
   return MRS_OK;

@@ -4,6 +4,7 @@
 //   tick_single.hip       the hot path of one GPU: makeStep launches, lazily evaluated collision ticks (fused launches, stall + replay)
 //   tick_sharded.hip      the sharded tick: communicator bookkeeping, search path, serial and split segments of the export-set exchange
 //   device_io.hip         C ABI + kernels for device-resident callers: commands, observations, resets, crash flags in device rows
+//   nearest.hip           C ABI + kernels of the k-nearest-neighbour observations for device-resident callers
 //   transport_rccl.hip    RCCL bound at run time (dlopen)
 //   transport_local.hip   in-process loopback group, caller-supplied all-gather, measurement stand-in
 //   transport_peer.hip    peer-window exchange (direct writes into the peers' device memory)
@@ -287,6 +288,10 @@ struct mrs_swarm {
   int     in_turn = 0;   // the block the last mrs_swarm_input_staging handed out
   // device-resident callers (device_io.hip): the caller's stream -> swarm's stream fence and back, created at first use
   hipEvent_t ev_dio_in = nullptr, ev_dio_out = nullptr;
+  // nearest-neighbour observations (nearest.hip): one device block carved into bucket counts, starts, sorted records; grown on demand,
+  // never shared with the collision pass, not copied by clone
+  void*  nn_buf = nullptr;
+  size_t nn_bytes = 0;
   // collision scratch
   PosRecord*   dRec = nullptr;
   CollideWork* cwork = nullptr;
@@ -421,6 +426,15 @@ inline unsigned min_nonzero(unsigned a, unsigned b) { return a == 0u ? b : (b ==
 // the stall / warning index the host knows of: each chain of a split tick keeps mirrors of its own (one writer per word)
 inline unsigned stall_word(const volatile unsigned* hw) { return min_nonzero(hw[CTL_STALL], hw[CTL_STALL2]); }
 inline unsigned warn_word(const volatile unsigned* hw) { return min_nonzero(hw[CTL_WARN], hw[CTL_WARN2]); }
+// ---- device_io.hip: argument checks and the stream fence of the device-resident calls (nearest.hip uses them too) ----
+size_t dtype_bytes(int dtype);
+int    check_dtype(int dtype);
+int    check_device_ptr(const mrs_swarm* s, const void* p, size_t bytes, const char* what);
+size_t rows_bytes(int count, int stride, int width, int dtype);
+int    fence_in(mrs_swarm* s, hipStream_t ext);
+int    fence_out(mrs_swarm* s, hipStream_t ext);
+// ---- nearest.hip ----
+void   nearest_release(mrs_swarm* s);  // frees the scratch of mrs_swarm_nearest_device (mrs_swarm_destroy)
 // ---- transports (transport_*.hip) and the communicator bookkeeping (tick_sharded.hip) ----
 int  rccl_load(const char* path);
 int  rccl_check(int rc, const char* what);

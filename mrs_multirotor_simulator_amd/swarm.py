@@ -111,13 +111,17 @@ ABI_SYMBOLS = [
     "mrs_swarm_get_outputs_async", "mrs_swarm_outputs_wait", "mrs_cell_order",
     "mrs_swarm_get_poses", "mrs_swarm_get_poses_view", "mrs_swarm_get_poses_async", "mrs_swarm_poses_wait", "mrs_swarm_get_download_stats",
     "mrs_swarm_device", "mrs_swarm_gather_width", "mrs_swarm_set_input_device", "mrs_swarm_gather_device", "mrs_swarm_get_crashed_device",
-    "mrs_swarm_reset_device",
+    "mrs_swarm_reset_device", "mrs_nearest_width", "mrs_swarm_nearest_device",
 ]
 
 # device-resident callers (mrs_swarm_*_device): row element types and the observation groups of mrs_swarm_gather_device, in bit order
 DTYPE_F64, DTYPE_F32 = 0, 1
 OBS_POS, OBS_VEL, OBS_VEL_BODY, OBS_ROT, OBS_QUAT, OBS_OMEGA, OBS_IMU, OBS_RPM = (1 << b for b in range(8))
 OBS_ALL = 0xFF
+# fields of one neighbour slot of mrs_swarm_nearest_device, in bit order (widths 3, 3, 3, 3, 1)
+NN_REL_POS, NN_REL_POS_BODY, NN_REL_VEL, NN_REL_VEL_BODY, NN_DIST = (1 << b for b in range(5))
+NN_ALL = 0x1F
+NN_MAX_K = 32
 
 STATE_DTYPE = np.dtype([("x", "f8", 3), ("v", "f8", 3), ("v_prev", "f8", 3), ("R", "f8", (3, 3)), ("omega", "f8", 3), ("motor_rpm", "f8", 8),
                         ("imu_acceleration", "f8", 3), ("crashed", "i4"), ("n_motors", "i4")])
@@ -327,6 +331,8 @@ def load_library():
         "mrs_swarm_gather_device": [vp, i32, i32, C.c_uint32, vp, i32, i32, vp],
         "mrs_swarm_get_crashed_device": [vp, i32, i32, vp, vp],
         "mrs_swarm_reset_device": [vp, i32, i32, vp, vp, vp, i32, i32, vp],
+        "mrs_nearest_width": [C.c_uint32, i32, ip],
+        "mrs_swarm_nearest_device": [vp, i32, i32, i32, C.c_double, C.c_uint32, vp, i32, i32, vp, i32, vp, vp],
     }
     for name, args in sig.items():
         if os.environ.get("MRS_SWARM_LIB") and not hasattr(L, name):
@@ -360,6 +366,13 @@ def gather_width(groups):
     """elements per row of Swarm.gather_device for the OBS_* bits in `groups` (host only, no GPU)"""
     w = C.c_int32()
     _check(load_library().mrs_swarm_gather_width(C.c_uint32(int(groups)), C.byref(w)))
+    return int(w.value)
+
+
+def nearest_width(fields, k):
+    """elements per row of Swarm.nearest_device: k slots of the NN_* fields in `fields` (host only, no GPU)"""
+    w = C.c_int32()
+    _check(load_library().mrs_nearest_width(C.c_uint32(int(fields)), int(k), C.byref(w)))
     return int(w.value)
 
 
@@ -782,6 +795,11 @@ class Swarm:
     def reset_device(self, first, count, dev_mask, dev_pos, dev_heading, dtype, takeoff_patch_enabled, ext_stream):
         _check(_lib.mrs_swarm_reset_device(self._h, int(first), int(count), dev_mask or None, dev_pos or None, dev_heading or None, int(dtype),
                                            int(bool(takeoff_patch_enabled)), ext_stream or None))
+
+    def nearest_device(self, first, count, k, radius, fields, dev_rows, dtype, stride, dev_index, index_stride, dev_count, ext_stream):
+        _check(_lib.mrs_swarm_nearest_device(self._h, int(first), int(count), int(k), C.c_double(float(radius)), C.c_uint32(int(fields)),
+                                             dev_rows or None, int(dtype), int(stride), dev_index or None, int(index_stride), dev_count or None,
+                                             ext_stream or None))
 
     def get_diag(self):
         d = Diag()

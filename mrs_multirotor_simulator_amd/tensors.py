@@ -1,5 +1,5 @@
-"""torch tensors in and out of a Swarm without the host: commands, observations, masked resets and crash flags for a controller,
-policy or reward that lives on the swarm's GPU (include/mrs_swarm.h, "device-resident callers").
+"""torch tensors in and out of a Swarm without the host: commands, observations, nearest-neighbour observations, masked resets and
+crash flags for a controller, policy or reward that lives on the swarm's GPU (include/mrs_swarm.h, "device-resident callers").
 
 Every call passes torch's current stream of the swarm's device as the caller stream: the library fences its own stream against it, so
 tensors written on that stream before the call are what the kernel reads, and work queued after the call sees the result.  Tensors are
@@ -10,8 +10,9 @@ Imports torch; the package itself does not.
 """
 import torch
 
-from .swarm import (ACTUATOR_CMD, ATTITUDE_CMD, DTYPE_F32, DTYPE_F64, INPUT_UNKNOWN, MAX_MOTORS, OBS_ALL, OBS_IMU, OBS_OMEGA,  # noqa: F401
-                    OBS_POS, OBS_QUAT, OBS_ROT, OBS_RPM, OBS_VEL, OBS_VEL_BODY, TILT_HDG_RATE_CMD, gather_width)
+from .swarm import (ACTUATOR_CMD, ATTITUDE_CMD, DTYPE_F32, DTYPE_F64, INPUT_UNKNOWN, MAX_MOTORS, NN_ALL, NN_DIST, NN_MAX_K,  # noqa: F401
+                    NN_REL_POS, NN_REL_POS_BODY, NN_REL_VEL, NN_REL_VEL_BODY, OBS_ALL, OBS_IMU, OBS_OMEGA, OBS_POS, OBS_QUAT, OBS_ROT,
+                    OBS_RPM, OBS_VEL, OBS_VEL_BODY, TILT_HDG_RATE_CMD, gather_width, nearest_width)
 
 _DTYPES = {torch.float64: DTYPE_F64, torch.float32: DTYPE_F32}
 
@@ -136,3 +137,33 @@ def reset(swarm, mask, pos, heading=None, takeoff=True, first=0):
         check_tensor(heading, count, None, pos.dtype, dev)
         hptr = heading.data_ptr()
     swarm.reset_device(first, count, mask.data_ptr(), pos.data_ptr(), hptr, code, takeoff, _stream(dev))
+
+
+def nearest(swarm, k, radius, fields=NN_REL_POS | NN_DIST, first=0, count=None, dtype=torch.float32, out=None, index=None, counts=None):
+    """The k nearest other UAVs within `radius` of each UAV of [first, first + count), nearest first, ties to the lower index
+    (mrs_swarm_nearest_device).  Returns (rows, index, counts) on the swarm's device: rows [count, k * w] of `dtype` holding k slots of
+    the NN_* fields of `fields` in bit order (w = nearest_width(fields, 1); None when fields == 0), index int32 [count, k] (-1: empty
+    slot, whose fields are 0) and counts int32 [count] (neighbours listed).  `out` ([count, >= k * w]), `index` ([count, >= k]) and
+    `counts` ([count]) are used instead of new tensors when given; columns past the widths are left alone."""
+    count = _count(swarm, first, count)
+    width = nearest_width(fields, k)
+    dev = swarm.device()
+    tdev = torch.device("cuda", dev)
+    code, stride, rows_ptr = DTYPE_F32, 0, 0
+    if fields:
+        if out is None:
+            out = torch.empty((count, width), dtype=dtype, device=tdev)
+        code = _dtype_code(out.dtype)
+        stride = check_tensor(out, count, width, out.dtype, dev)
+        rows_ptr = out.data_ptr()
+    if index is None:
+        index = torch.empty((count, k), dtype=torch.int32, device=tdev)
+    istride = check_tensor(index, count, k, torch.int32, dev)
+    if counts is None:
+        counts = torch.empty(count, dtype=torch.int32, device=tdev)
+    check_tensor(counts, count, None, torch.int32, dev)
+    swarm.nearest_device(first, count, k, radius, fields, rows_ptr, code, stride, index.data_ptr(), istride, counts.data_ptr(), _stream(dev))
+    rows = None
+    if fields:
+        rows = out[:, :width] if out.shape[1] > width else out
+    return rows, (index[:, :k] if index.shape[1] > k else index), counts

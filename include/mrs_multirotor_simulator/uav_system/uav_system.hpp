@@ -779,6 +779,16 @@ public:
                      int index_stride, int32_t* dev_count, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_nearest_device(s_, first, count, k, radius, fields, dev_rows, dtype, stride, dev_index, index_stride, dev_count, stream));
   }
+  // the whole simulation state of UAVs [first, first + count) into dev_records[0 .. count-1] (device memory, 16-B aligned)
+  void saveDevice(int first, int count, mrs_uav_snapshot_t* dev_records, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_save_device(s_, first, count, dev_records, stream));
+  }
+  // UAV first + k <- dev_records[k], or <- dev_records[dev_index[k]] (-1: left alone); command, mode and airframe are kept;
+  // dev_status (count bytes, may be null): MRS_SNAP_LOADED or why the row was skipped
+  void loadDevice(int first, int count, const mrs_uav_snapshot_t* dev_records, int64_t n_records, const int32_t* dev_index = nullptr,
+                  uint8_t* dev_status = nullptr, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_load_device(s_, first, count, dev_records, n_records, dev_index, dev_status, stream));
+  }
   void crashedDevice(int first, int count, uint8_t* dev_out, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_get_crashed_device(s_, first, count, dev_out, stream));
   }

@@ -535,6 +535,42 @@ int mrs_nearest_width(uint32_t fields, int32_t k, int32_t* width);
 int mrs_swarm_nearest_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t k, double radius, uint32_t fields, void* dev_rows, int32_t dtype,
                              int32_t stride, int32_t* dev_index, int32_t index_stride, int32_t* dev_count, void* ext_stream);
 
+/* ---- state snapshots: the whole per-UAV simulation state into caller-owned device records and back (rewind, recorded resets, forks) ----
+ * One record holds everything a step reads of a UAV besides its command, feed-forwards and mode, bit for bit.  The 60 doubles are the
+ * state columns in their order (MultirotorModel::State x, v, v_prev, R row-major, omega, motor_rpm — all MRS_MAX_MOTORS columns as
+ * stored —, the IMU acceleration, the latched external force, _initial_pos_(2), and the 24 PID words in the order of
+ * mrs_swarm_get_pid).  v_prev is the value mrs_swarm_get_states returns (v unless setState split it).  `flags` holds the crash flag,
+ * the mutated takeoff patch and whether v_prev differs from v; `airframe` is the swarm's parameter-set (type) index of the UAV;
+ * `magic` is MRS_SNAP_MAGIC in every record save wrote.  496 B: an array of records keeps every row 16-B aligned. */
+enum { MRS_SNAP_CRASHED = 1, MRS_SNAP_TAKEOFF = 2, MRS_SNAP_VPREV_SPLIT = 4 };
+#define MRS_SNAP_MAGIC 0x50414E53u /* "SNAP" */
+typedef struct {
+  double   x[3], v[3], v_prev[3], R[9], omega[3];
+  double   motor_rpm[MRS_MAX_MOTORS];
+  double   imu_acceleration[3], external_force[3];
+  double   initial_z;
+  double   pid[24];
+  uint32_t flags;    /* MRS_SNAP_* */
+  uint32_t airframe; /* parameter-set (type) index */
+  uint32_t magic;    /* MRS_SNAP_MAGIC */
+  uint32_t _reserved;
+} mrs_uav_snapshot_t;
+/* save: the records of UAVs [first, first+count) into dev_records[0 .. count-1].  Enters like every state call: a pending collision
+ * tick is evaluated first, so a record holds the latched collision force and crash flags handleCollisions would have left. */
+int mrs_swarm_save_device(mrs_swarm_t* s, int32_t first, int32_t count, mrs_uav_snapshot_t* dev_records, void* ext_stream);
+/* load: UAV first + k <- dev_records[k] (dev_index NULL; n_records >= count), or <- dev_records[dev_index[k]] (one record may go to many
+ * UAVs).  Writes the state columns and the CRASHED / TAKEOFF / VPREV_SPLIT flags; keeps the command, the feed-forwards, the mode, the
+ * airframe and the hold flag (as mrs_swarm_reset_device), so the host's mirrors stay valid.  A row is skipped and dev_status[k] (NULL,
+ * or count bytes) says why: 0 loaded, 1 index -1, 2 the record's airframe is not the UAV's, 3 index outside [0, n_records), 4 no
+ * MRS_SNAP_MAGIC (zeroed or never-written memory).  The next collision tick repeats the neighbour search, and the external force
+ * acts (as after mrs_swarm_copy_uavs).
+ * Both calls: stream fence and host waits of mrs_swarm_reset_device.  Every argument is checked before anything is launched: the range
+ * (MRS_ERR_RANGE), and MRS_ERR_ARG for null, host or other-device pointers, rows past their allocation, records not 16-B aligned,
+ * n_records < count without an index, and a sharded swarm. */
+enum { MRS_SNAP_LOADED = 0, MRS_SNAP_SKIPPED = 1, MRS_SNAP_BAD_AIRFRAME = 2, MRS_SNAP_BAD_INDEX = 3, MRS_SNAP_BAD_MAGIC = 4 };
+int mrs_swarm_load_device(mrs_swarm_t* s, int32_t first, int32_t count, const mrs_uav_snapshot_t* dev_records, int64_t n_records,
+                          const int32_t* dev_index, uint8_t* dev_status, void* ext_stream);
+
 #ifdef __cplusplus
 }
 #endif

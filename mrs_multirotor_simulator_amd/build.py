@@ -19,6 +19,7 @@ UNITS = [
     ("outputs.hip", "off"),
     ("device_io.hip", "off"),  # off: its observation rows equal the publisher payloads of outputs.hip bit for bit
     ("nearest.hip", "off"),  # off: d2 = ((dx*dx) + dy*dy) + dz*dz literally, which a numpy restatement reproduces bit for bit
+    ("snapshot.hip", "off"),  # no arithmetic (records are copied bit for bit); off like every other unit
     # host side (no kernels): C ABI, single-GPU tick, sharded tick, the three transports
     ("host_api.hip", "off"),
     ("tick_single.hip", "off"),

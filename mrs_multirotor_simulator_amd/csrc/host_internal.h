@@ -5,6 +5,7 @@
 //   tick_sharded.hip      the sharded tick: communicator bookkeeping, search path, serial and split segments of the export-set exchange
 //   device_io.hip         C ABI + kernels for device-resident callers: commands, observations, resets, crash flags in device rows
 //   nearest.hip           C ABI + kernels of the k-nearest-neighbour observations for device-resident callers
+//   snapshot.hip          C ABI + kernels of the state snapshots (save / indexed load of whole per-UAV records) for device-resident callers
 //   transport_rccl.hip    RCCL bound at run time (dlopen)
 //   transport_local.hip   in-process loopback group, caller-supplied all-gather, measurement stand-in
 //   transport_peer.hip    peer-window exchange (direct writes into the peers' device memory)

@@ -111,7 +111,7 @@ ABI_SYMBOLS = [
     "mrs_swarm_get_outputs_async", "mrs_swarm_outputs_wait", "mrs_cell_order",
     "mrs_swarm_get_poses", "mrs_swarm_get_poses_view", "mrs_swarm_get_poses_async", "mrs_swarm_poses_wait", "mrs_swarm_get_download_stats",
     "mrs_swarm_device", "mrs_swarm_gather_width", "mrs_swarm_set_input_device", "mrs_swarm_gather_device", "mrs_swarm_get_crashed_device",
-    "mrs_swarm_reset_device", "mrs_nearest_width", "mrs_swarm_nearest_device",
+    "mrs_swarm_reset_device", "mrs_nearest_width", "mrs_swarm_nearest_device", "mrs_swarm_save_device", "mrs_swarm_load_device",
 ]
 
 # device-resident callers (mrs_swarm_*_device): row element types and the observation groups of mrs_swarm_gather_device, in bit order
@@ -122,6 +122,13 @@ OBS_ALL = 0xFF
 NN_REL_POS, NN_REL_POS_BODY, NN_REL_VEL, NN_REL_VEL_BODY, NN_DIST = (1 << b for b in range(5))
 NN_ALL = 0x1F
 NN_MAX_K = 32
+# state snapshots (mrs_swarm_save_device / mrs_swarm_load_device): one mrs_uav_snapshot_t record per UAV, 496 B
+SNAP_CRASHED, SNAP_TAKEOFF, SNAP_VPREV_SPLIT = 1, 2, 4
+SNAP_MAGIC = 0x50414E53
+SNAP_LOADED, SNAP_SKIPPED, SNAP_BAD_AIRFRAME, SNAP_BAD_INDEX, SNAP_BAD_MAGIC = 0, 1, 2, 3, 4  # status bytes of a load
+SNAPSHOT_DTYPE = np.dtype([("x", "f8", 3), ("v", "f8", 3), ("v_prev", "f8", 3), ("R", "f8", (3, 3)), ("omega", "f8", 3), ("motor_rpm", "f8", 8),
+                           ("imu_acceleration", "f8", 3), ("external_force", "f8", 3), ("initial_z", "f8"), ("pid", "f8", 24),
+                           ("flags", "u4"), ("airframe", "u4"), ("magic", "u4"), ("_reserved", "u4")])
 
 STATE_DTYPE = np.dtype([("x", "f8", 3), ("v", "f8", 3), ("v_prev", "f8", 3), ("R", "f8", (3, 3)), ("omega", "f8", 3), ("motor_rpm", "f8", 8),
                         ("imu_acceleration", "f8", 3), ("crashed", "i4"), ("n_motors", "i4")])
@@ -333,6 +340,8 @@ def load_library():
         "mrs_swarm_reset_device": [vp, i32, i32, vp, vp, vp, i32, i32, vp],
         "mrs_nearest_width": [C.c_uint32, i32, ip],
         "mrs_swarm_nearest_device": [vp, i32, i32, i32, C.c_double, C.c_uint32, vp, i32, i32, vp, i32, vp, vp],
+        "mrs_swarm_save_device": [vp, i32, i32, vp, vp],
+        "mrs_swarm_load_device": [vp, i32, i32, vp, C.c_int64, vp, vp, vp],
     }
     for name, args in sig.items():
         if os.environ.get("MRS_SWARM_LIB") and not hasattr(L, name):
@@ -800,6 +809,13 @@ class Swarm:
         _check(_lib.mrs_swarm_nearest_device(self._h, int(first), int(count), int(k), C.c_double(float(radius)), C.c_uint32(int(fields)),
                                              dev_rows or None, int(dtype), int(stride), dev_index or None, int(index_stride), dev_count or None,
                                              ext_stream or None))
+
+    def save_device(self, first, count, dev_records, ext_stream):
+        _check(_lib.mrs_swarm_save_device(self._h, int(first), int(count), dev_records or None, ext_stream or None))
+
+    def load_device(self, first, count, dev_records, n_records, dev_index, dev_status, ext_stream):
+        _check(_lib.mrs_swarm_load_device(self._h, int(first), int(count), dev_records or None, int(n_records), dev_index or None,
+                                          dev_status or None, ext_stream or None))
 
     def get_diag(self):
         d = Diag()

@@ -1,5 +1,5 @@
-"""torch tensors in and out of a Swarm without the host: commands, observations, nearest-neighbour observations, masked resets and
-crash flags for a controller, policy or reward that lives on the swarm's GPU (include/mrs_swarm.h, "device-resident callers").
+"""torch tensors in and out of a Swarm without the host: commands, observations, nearest-neighbour observations, masked resets, crash
+flags and state snapshots for a controller, policy or reward that lives on the swarm's GPU (include/mrs_swarm.h, "device-resident callers").
 
 Every call passes torch's current stream of the swarm's device as the caller stream: the library fences its own stream against it, so
 tensors written on that stream before the call are what the kernel reads, and work queued after the call sees the result.  Tensors are
@@ -12,9 +12,11 @@ import torch
 
 from .swarm import (ACTUATOR_CMD, ATTITUDE_CMD, DTYPE_F32, DTYPE_F64, INPUT_UNKNOWN, MAX_MOTORS, NN_ALL, NN_DIST, NN_MAX_K,  # noqa: F401
                     NN_REL_POS, NN_REL_POS_BODY, NN_REL_VEL, NN_REL_VEL_BODY, OBS_ALL, OBS_IMU, OBS_OMEGA, OBS_POS, OBS_QUAT, OBS_ROT,
-                    OBS_RPM, OBS_VEL, OBS_VEL_BODY, TILT_HDG_RATE_CMD, gather_width, nearest_width)
+                    OBS_RPM, OBS_VEL, OBS_VEL_BODY, SNAP_BAD_AIRFRAME, SNAP_BAD_INDEX, SNAP_BAD_MAGIC, SNAP_CRASHED, SNAP_LOADED,
+                    SNAP_MAGIC, SNAP_SKIPPED, SNAP_TAKEOFF, SNAP_VPREV_SPLIT, SNAPSHOT_DTYPE, TILT_HDG_RATE_CMD, gather_width, nearest_width)
 
 _DTYPES = {torch.float64: DTYPE_F64, torch.float32: DTYPE_F32}
+SNAP_BYTES = SNAPSHOT_DTYPE.itemsize  # 496: one mrs_uav_snapshot_t
 
 
 def check_tensor(t, rows, min_width, dtype, device_index):
@@ -167,3 +169,74 @@ def nearest(swarm, k, radius, fields=NN_REL_POS | NN_DIST, first=0, count=None, 
     if fields:
         rows = out[:, :width] if out.shape[1] > width else out
     return rows, (index[:, :k] if index.shape[1] > k else index), counts
+
+
+def _check_records(records, rows, dev):
+    """records: a dense torch.uint8 [rows, SNAP_BYTES] tensor on the swarm's device, 16-B aligned"""
+    check_tensor(records, rows, SNAP_BYTES, torch.uint8, dev)
+    if records.shape[1] != SNAP_BYTES:
+        raise ValueError(f"records must be [{rows}, {SNAP_BYTES}], got shape {tuple(records.shape)}")
+    if rows > 1 and records.stride(0) != SNAP_BYTES:
+        raise ValueError(f"records are not contiguous (row stride {records.stride(0)}, expected {SNAP_BYTES})")
+    if records.data_ptr() % 16:
+        raise ValueError("records must start on a 16-B boundary")
+
+
+def save(swarm, first=0, count=None, out=None):
+    """The whole simulation state of UAVs [first, first + count) as snapshot records (mrs_swarm_save_device): a torch.uint8
+    [count, SNAP_BYTES] tensor on the swarm's device, one SNAPSHOT_DTYPE record per row (snapshot_fields gives views of the fields).
+    `out` is used instead of a new tensor when given."""
+    count = _count(swarm, first, count)
+    dev = swarm.device()
+    if out is None:
+        out = torch.empty((count, SNAP_BYTES), dtype=torch.uint8, device=torch.device("cuda", dev))
+    _check_records(out, count, dev)
+    swarm.save_device(first, count, out.data_ptr(), _stream(dev))
+    return out
+
+
+def load(swarm, records, first=0, index=None, status=None):
+    """Write snapshot records back (mrs_swarm_load_device).  Without `index`, UAV first + k <- records[k] for every row of `records`;
+    with `index` (an int32 vector), UAV first + k <- records[index[k]] (one record may go to many UAVs; -1 leaves the UAV alone).
+    Command, feed-forwards, mode, airframe and hold flag are kept.  Returns the uint8 status vector (SNAP_LOADED, SNAP_SKIPPED,
+    SNAP_BAD_AIRFRAME, SNAP_BAD_INDEX, SNAP_BAD_MAGIC), written into `status` when given."""
+    dev = swarm.device()
+    if not isinstance(records, torch.Tensor) or records.dim() != 2:
+        raise ValueError("records must be a [n_records, SNAP_BYTES] torch.uint8 tensor")
+    n_records = records.shape[0]
+    _check_records(records, n_records, dev)
+    if index is None:
+        count, iptr = n_records, 0
+    else:
+        if not isinstance(index, torch.Tensor) or index.dim() != 1:
+            raise ValueError("index must be an int32 vector")
+        count = index.shape[0]
+        check_tensor(index, count, None, torch.int32, dev)
+        iptr = index.data_ptr()
+    if status is None:
+        status = torch.empty(count, dtype=torch.uint8, device=torch.device("cuda", dev))
+    check_tensor(status, count, None, torch.uint8, dev)
+    swarm.load_device(first, count, records.data_ptr(), n_records, iptr, status.data_ptr(), _stream(dev))
+    return status
+
+
+def snapshot_fields(records):
+    """Views of the fields of snapshot records ([n, SNAP_BYTES] torch.uint8) that share their memory: x, v, v_prev, omega,
+    imu_acceleration, external_force [n, 3], R [n, 3, 3], motor_rpm [n, 8], initial_z [n], pid [n, 24] (float64), flags, airframe,
+    magic [n] (int32; SNAP_* bits in flags).  Editing a view edits the records, so a caller can move saved UAVs before loading them."""
+    if not isinstance(records, torch.Tensor) or records.dtype != torch.uint8 or records.dim() != 2 or records.shape[1] != SNAP_BYTES:
+        raise ValueError("records must be a [n, SNAP_BYTES] torch.uint8 tensor")
+    if records.shape[0] > 1 and records.stride(0) != SNAP_BYTES or records.stride(1) != 1:
+        raise ValueError("records are not contiguous")
+    d, w = records.view(torch.float64), records.view(torch.int32)
+    out = {}
+    for name in SNAPSHOT_DTYPE.names:
+        dt, off = SNAPSHOT_DTYPE.fields[name][:2]
+        if name == "_reserved":
+            continue
+        if dt.base.kind == "f":
+            a, size = off // 8, max(1, dt.itemsize // 8)
+            out[name] = d[:, a] if not dt.shape else d[:, a:a + size].unflatten(1, dt.shape)
+        else:
+            out[name] = w[:, off // 4]
+    return out

@@ -5,9 +5,14 @@ Contract (driver): python bench.py --gpus N --steps K --warmup W ; for N > 1 the
 and a PLAIN `python bench.py --gpus N` starts those N ranks itself (a torch.distributed.run child, before this process touches a GPU).
 A "step" is one makeStep(dt = 1 ms) of every UAV of the rank's shard (one kernel launch over the whole batch, state resident in
 HBM).  Headline workload at every N: BASELINE.json configs[2] — 100 000 x500 UAVs per GPU, actuator-level references, no
-collisions (weak scaling: UAVs are independent, no data-path collective).  For N > 1 the same JSON line carries a `config5`
-sub-record: BASELINE configs[4], 1 000 000 UAVs with mutual collisions sharded over the N ranks, the collision exchange over RCCL.
-Rank 0 prints ONE JSON line.
+collisions (weak scaling: UAVs are independent, no data-path collective).  Rank 0 prints ONE JSON line.
+
+A plain run does what its headline figure needs and nothing else: set up, W warm-up steps, the K timed steps, --dump-outputs, the
+line.  --full adds everything else the benchmark measures: live rocprofv3 PMC traffic (child runs), the CPU baselines, at N = 1 the
+sub-records (other sizes, precisions and workloads), the neighbour-search figures of a collision workload, and the `config5`
+sub-record — BASELINE configs[4], 1 000 000 UAVs with mutual collisions sharded over the N ranks, the collision exchange over RCCL
+(at N > 1 also over peer windows, `config5_peer`).  Each extra can also be switched on or off on its own (--traffic, --sub-records,
+--config5, --config5-peer, --no-cpu-baseline); `auto` means "with --full".
 
 Timing: W warm-up steps, then ONE region of EXACTLY K timed steps, bracketed by barrier + synchronize on both sides.  `ms_per_step` /
 `value` = that region by the WALL clock (time.perf_counter() between the two brackets, MAX over ranks) / K — SURVEY §8d's definition;
@@ -84,14 +89,15 @@ NOTES = {
                 "regions; with two concurrent half-swarm launches per step `achieved` is the bytes of both over that time.  `achieved` prices "
                 "the ALGORITHMIC bytes (SURVEY 8d); `moved_GBps` the bytes the kernel really moves (elided v_prev / F_ext / init_z columns), "
                 "and `frac_of_achievable` holds those against the 6.3 TB/s a read+write stream reaches.  `traffic` = rocprofv3 --pmc "
-                "FETCH_SIZE x 2 + WRITE_SIZE per step (separate passes, child runs before this process touches the GPU).  In the "
+                "FETCH_SIZE x 2 + WRITE_SIZE per step (--full: separate passes, child runs before this process touches the GPU; a plain "
+                "run: the committed profile summary of the same configuration, `traffic_source` names it).  In the "
                 "`infinity-cache-resident` regime the state (touched_bytes) fits the 256 MiB Infinity Cache, so HBM bandwidth is not the "
                 "operative limit there (`bound`); the `hbm_streaming` sub-record is the same kernel on 4 M UAVs, where every byte comes from HBM",
     "roofline_collision": "whole tick = fused step + collision launch, plus the neighbour search amortised over the ticks between two searches, "
                           "over (step bytes + list-tick bytes); search_* = one search on its own (k_pack_insert<1> + k_query2<1, 3>, 16 searches "
                           "back to back between two hipEvents) against SURVEY 8d's (92 + 24 k) B per UAV, k measured on the run's positions; "
-                          "per-kernel times: profiles/r05_collision_tick_*",
-    "sub_records": "hbm_streaming: the headline kernel on 4 M UAVs; config4: BASELINE configs[3] (100 000 UAVs, position references + "
+                          "per-kernel times: profiles/r05_collision_tick_*.  The search_* figures of a collision headline come with --full",
+    "sub_records": "--full only (a plain run carries none): hbm_streaming: the headline kernel on 4 M UAVs; config4: BASELINE configs[3] (100 000 UAVs, position references + "
                    "collisions + ground) as mrs_swarm_tick_n runs it, and (spawned_in_cell_order) the same swarm spawned in the order mrs_cell_order suggests; literal: the bit-faithful flavour on the headline workload; config2: "
                    "BASELINE configs[1] (400 f550 on the tmux grid); io_tick: config 3 with the publisher payload of every UAV downloaded and a "
                    "command block uploaded every tick (SURVEY 8f rank 2), serial and pipelined; sharded_rank_standin: one rank of 8 x 125 000 "
@@ -195,18 +201,23 @@ def parse():
     ap.add_argument("--arith", choices=["literal", "fast"], default="fast",
                     help="fast: FMA + rsqrt arithmetic (within 1e-6 of the reference, the production flavour); literal: reference op order")
     ap.add_argument("--substeps", type=int, default=1, help="makeStep rounds fused per launch (state kept in registers)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: live PMC traffic, CPU baselines, sub-records, config-5 leg and collision search figures "
+                         "(each `auto` below means: with --full); a plain run only sets up, warms up, times the steps and dumps")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg (rank 0, N=1 only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="no cpu_baseline legs under --full")
     ap.add_argument("--min-measure-ms", type=float, default=50.0, help="sub-records and the config-5 leg: regions are repeated until this much was timed")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the state the headline path computed (rank 0's UAVs) as DIR/<name>.npy")
     ap.add_argument("--config5", choices=["auto", "on", "off"], default="auto",
-                    help="the 1 000 000-UAV collision leg (BASELINE configs[4]); auto = at every N for the default workload (one rank: the same "
-                         "path on a one-rank communicator — the figure the N-rank value is divided by)")
+                    help="the 1 000 000-UAV collision leg (BASELINE configs[4]); auto = under --full at every N for the default workload (one "
+                         "rank: the same path on a one-rank communicator — the figure the N-rank value is divided by)")
     ap.add_argument("--sub-records", choices=["auto", "on", "off"], default="auto",
-                    help="hbm_streaming (4 M UAVs) and config4 (100 k UAVs with collisions) sub-records; auto = in the default N=1 run")
-    ap.add_argument("--traffic", choices=["live", "profile", "off"], default="live",
-                    help="roofline.traffic: live = two rocprofv3 --pmc child runs of the same workload (N=1 only), profile = the committed summary")
+                    help="hbm_streaming (4 M UAVs), config4 (100 k UAVs with collisions) and the other sub-records; auto = in the default "
+                         "N=1 run under --full")
+    ap.add_argument("--traffic", choices=["auto", "live", "profile", "off"], default="auto",
+                    help="roofline.traffic: live = two rocprofv3 --pmc child runs of the same workload (N=1 only), profile = the committed "
+                         "summary; auto = live under --full, profile otherwise")
     ap.add_argument("--explain", action="store_true", help="print what the fields of the line mean and how they are measured, then exit")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # the short run rocprofv3 wraps for --traffic live
     ap.add_argument("--config5-timeout", type=float, default=240.0, help="seconds after which the config-5 leg is given up (the headline line is printed regardless)")
@@ -217,11 +228,28 @@ def parse():
                          "peers' device memory over xGMI, IPC handles carried by torch.distributed; never run across devices yet: opt-in)")
     ap.add_argument("--config5-peer", choices=["auto", "on", "off"], default="auto",
                     help="a second, GUARDED config-5 record with the peer-window exchange (`config5_peer`), run in child processes after the RCCL leg so "
-                         "that whatever happens to it cannot touch the line's other records or the exit status; auto = whenever N > 1")
+                         "that whatever happens to it cannot touch the line's other records or the exit status; auto = whenever the config-5 leg "
+                         "runs at N > 1")
     ap.add_argument("--only-config5", action="store_true", help=argparse.SUPPRESS)  # the child run behind config5_peer: that leg alone, one JSON object
     ap.add_argument("--config5-exchange", choices=["export", "full"], default="export",
                     help="export: boundary UAVs only between two searches; full: all 48-B records on every tick")
     return ap.parse_args()
+
+
+def resolve_extras(args):
+    """Decides, in one place, what this run does besides the headline: every `auto` becomes on or off (on only under --full), and
+    args gains run_subs / run_config5 / run_peer / run_cpu_baseline / search_figures.  Needs no GPU."""
+    full = args.full and not args.pmc_child
+    if args.traffic == "auto":
+        args.traffic = "live" if full else "profile"
+    args.run_subs = not args.pmc_child and (args.sub_records == "on" or (
+        args.sub_records == "auto" and full and args.gpus == 1 and args.workload == "actuator" and args.uavs == 100_000 and args.substeps == 1))
+    args.run_config5 = args.config5 == "on" or (args.config5 == "auto" and full and args.workload == "actuator")
+    args.run_peer = args.run_config5 and (args.config5_peer == "on" or (
+        args.config5_peer == "auto" and args.gpus > 1 and args.config5_transport == "rccl"))
+    args.run_cpu_baseline = full and not args.no_cpu_baseline
+    args.search_figures = full  # the headline collision leg's k-bar and timed searches (the sub-record legs always take them)
+    return args
 
 
 def spawn_ranks(args):
@@ -577,20 +605,23 @@ def step_leg(args, R, n, workload, steps, warmup, traffic=(None, "not requested"
             out["config"]["launches_replayed"], out["config"]["searches_queued_ahead"] = int(replayed), int(ahead)
             p = 0.06  # fraction of UAVs with a listed partner at 64 m^3 per UAV
             cb = COLLISION_BYTES["list_tick_per_uav"] + COLLISION_BYTES["list_tick_per_uav_with_partner"] * p
-            # the search itself (92 + 24 k-bar bytes per UAV): k-bar measured on the positions at the end of the run (list
-            # cells of collide.hip: edge sqrt(3) + skin + 0.018 m), the two search kernels timed live, back to back, by hipEvents
-            kbar = mean_search_candidates(x_end, 1.0 / (3.0 ** 0.5 + 0.5 + 0.0179491924))
-            search_ms = sw.debug_search_ms(reps=16)
-            search_bytes = (COLLISION_BYTES["search_tick_per_uav"] + COLLISION_BYTES["search_tick_per_candidate"] * kbar) * n
             out["roofline_collision"] = {
                 "bound": "infinity-cache" if resident else "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS,
                 "algorithmic_bytes_per_uav_list_tick": cb,
-                "algorithmic_bytes_per_uav_search_tick": COLLISION_BYTES["search_tick_per_uav"] + COLLISION_BYTES["search_tick_per_candidate"] * kbar,
-                "search_candidates_per_uav": kbar, "search_bytes": search_bytes, "search_ms": search_ms,
-                "search_achieved": search_bytes / (search_ms * 1e-3) / 1e9, "search_frac": search_bytes / (search_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                 "ticks_per_search": (int(ticks) / max(1, int(searches))),
                 "achieved_whole_tick": (b_alg + cb) * n / (kern_ms * 1e-3) / 1e9,
                 "frac_whole_tick": (b_alg + cb) * n / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
+            if args.search_figures or not headline:
+                # the search itself (92 + 24 k-bar bytes per UAV): k-bar measured on the positions at the end of the run (list
+                # cells of collide.hip: edge sqrt(3) + skin + 0.018 m), the two search kernels timed in launches of their own, back to
+                # back, by hipEvents
+                kbar = mean_search_candidates(x_end, 1.0 / (3.0 ** 0.5 + 0.5 + 0.0179491924))
+                search_ms = sw.debug_search_ms(reps=16)
+                search_bytes = (COLLISION_BYTES["search_tick_per_uav"] + COLLISION_BYTES["search_tick_per_candidate"] * kbar) * n
+                out["roofline_collision"].update({
+                    "algorithmic_bytes_per_uav_search_tick": COLLISION_BYTES["search_tick_per_uav"] + COLLISION_BYTES["search_tick_per_candidate"] * kbar,
+                    "search_candidates_per_uav": kbar, "search_bytes": search_bytes, "search_ms": search_ms,
+                    "search_achieved": search_bytes / (search_ms * 1e-3) / 1e9, "search_frac": search_bytes / (search_ms * 1e-3) / 1e9 / HBM_PEAK_GBS})
     del sw
     return out, st, cmd
 
@@ -876,7 +907,7 @@ def peer_leg_in_children(args):
 
 
 def main():
-    args = parse()
+    args = resolve_extras(parse())
     if args.explain:
         print(json.dumps(NOTES, indent=1))
         return
@@ -897,14 +928,12 @@ def main():
         if R.rank == 0:
             print(json.dumps(c5), flush=True)
         os._exit(0 if (c5 is None or "error" not in c5) else 3)  # (no waiting for ranks that may be stuck in a collective)
-    subs = args.sub_records == "on" or (args.sub_records == "auto" and args.gpus == 1 and args.workload == "actuator"
-                                        and args.uavs == 100_000 and args.substeps == 1 and not args.pmc_child)
     # roofline.traffic: the rocprofv3 --pmc child runs come FIRST, while this process has not initialised the GPU (children of a
     # process that holds the device are not started), and not at all when this run is itself being profiled
     live = {}
     if args.traffic == "live" and args.gpus == 1 and not args.pmc_child:
         profiled = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
-        jobs = [(args.uavs, args.workload)] + ([(HBM_STREAMING_UAVS, "actuator"), (100_000, "position+collisions")] if subs else [])
+        jobs = [(args.uavs, args.workload)] + ([(HBM_STREAMING_UAVS, "actuator"), (100_000, "position+collisions")] if args.run_subs else [])
         for job in jobs:
             live[job] = (None, "this run is itself under a profiler") if profiled else live_traffic(args, *job)
     no_traffic = (None, "not requested")
@@ -916,16 +945,16 @@ def main():
     if args.pmc_child:
         R.close()
         return
-    if R.rank == 0 and R.world == 1 and not args.no_cpu_baseline:
+    if R.rank == 0 and R.world == 1 and args.run_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, st, cmd)
     del st, cmd
-    if subs:
+    if args.run_subs:
         # the numbers the headline size cannot show (each a few seconds): the same kernel where every byte comes from HBM, and BASELINE
         # config 4 (collisions + ground) in the form tick_n runs it — fused step + collision launches, searches queued ahead
         rec, _, _ = step_leg(args, R, HBM_STREAMING_UAVS, "actuator", 200, 50, traffic=live.get((HBM_STREAMING_UAVS, "actuator"), no_traffic), min_ms=150.0)
         out["hbm_streaming"] = sub_record(rec)
         rec, st4, cmd4 = step_leg(args, R, 100_000, "position+collisions", 300, 100, traffic=live.get((100_000, "position+collisions"), no_traffic), min_ms=30.0)
-        if R.rank == 0 and not args.no_cpu_baseline:  # incl. the one CPU number that is the reference's OWN code: its nanoflann broadphase
+        if R.rank == 0 and args.run_cpu_baseline:  # incl. the one CPU number that is the reference's OWN code: its nanoflann broadphase
             rec["cpu_baseline"] = cpu_baseline(args, st4, cmd4, workload="position+collisions", uavs=100_000, seconds=min(args.cpu_seconds, 8.0))
         del st4, cmd4
         out["config4"] = sub_record(rec)
@@ -941,7 +970,7 @@ def main():
         out["literal"] = mini_record(rec)
         # BASELINE configs[1]: 400 f550 hexarotors, position cascade, no collisions (launch-bound: one wave per seven SIMDs)
         rec, st2, cmd2 = step_leg(args, R, 400, "config2", 2000, 200, min_ms=30.0, airframe="f550")
-        if R.rank == 0 and not args.no_cpu_baseline:
+        if R.rank == 0 and args.run_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(args, st2, cmd2, workload="config2", uavs=400, airframe="f550", seconds=min(args.cpu_seconds, 4.0))
         out["config2"] = mini_record(rec)
         # the same swarm with ten makeStep rounds per launch (mrs_swarm_step_n's substeps_per_launch: state kept in registers across the
@@ -983,7 +1012,7 @@ def main():
                 print(json.dumps(line), flush=True)
             return True
 
-    if args.config5 == "on" or (args.config5 == "auto" and not args.pmc_child and args.workload == "actuator"):
+    if args.run_config5:
         # The headline line must not depend on this second leg: if it fails or does not come back (a rank lost, a collective that
         # never completes), every rank gives up after --config5-timeout, rank 0 prints the line with the failure recorded, and the
         # processes leave without waiting for each other.
@@ -1019,8 +1048,7 @@ def main():
             give_up(f"{type(e).__name__}: {e}")
         watchdog.cancel()
         extra = {"config5": c5}
-        peer = args.config5_peer == "on" or (args.config5_peer == "auto" and R.world > 1 and args.config5_transport == "rccl")
-        if peer:
+        if args.run_peer:
             # the run's own process group ends first (every rank's RCCL result is in hand); the guarded leg then runs in children of rank 0
             # and can only add a record — a failure there is written into it and changes neither the other records nor the exit status
             R.close()
@@ -1029,7 +1057,7 @@ def main():
         if not emit(extra):  # the watchdog fired between the leg's return and cancel(): its line (and exit status) stand
             time.sleep(60)
             os._exit(3)
-        if not peer:
+        if not args.run_peer:
             R.close()
         return
     R.close()

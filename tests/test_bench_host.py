@@ -75,6 +75,33 @@ def test_guarded_peer_record_turns_a_failed_child_run_into_a_record():
     assert "error" in rec and rec.get("transport") == "peer", rec
 
 
+def test_a_plain_run_does_only_the_headline_and_full_adds_the_rest(monkeypatch):
+    """every extra of the line (live PMC traffic, CPU baselines, sub-records, config-5 legs, collision search figures) is off in a plain
+    run and on under --full; each switch of its own still turns its extra on or off"""
+    import bench
+
+    def resolved(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        return bench.resolve_extras(bench.parse())
+
+    def extras(a):
+        return {k for k in ("run_subs", "run_config5", "run_peer", "run_cpu_baseline", "search_figures") if getattr(a, k)}
+
+    plain = resolved("--gpus", "1", "--steps", "20", "--warmup", "5")
+    assert plain.traffic == "profile" and extras(plain) == set()
+    assert extras(resolved("--gpus", "2")) == set()
+    full = resolved("--gpus", "1", "--steps", "20", "--warmup", "5", "--full")
+    assert full.traffic == "live" and extras(full) == {"run_subs", "run_config5", "run_cpu_baseline", "search_figures"}
+    assert extras(resolved("--gpus", "2", "--full")) == {"run_config5", "run_peer", "run_cpu_baseline", "search_figures"}
+    assert extras(resolved("--full", "--uavs", "4096", "--no-cpu-baseline")) == {"run_config5", "search_figures"}
+    assert extras(resolved("--full", "--workload", "position+collisions", "--config5-peer", "on")) == {"run_cpu_baseline", "search_figures"}
+    alone = resolved("--config5", "on", "--sub-records", "on", "--traffic", "live")
+    assert alone.traffic == "live" and extras(alone) == {"run_subs", "run_config5"}
+    off = resolved("--full", "--config5", "off", "--sub-records", "off", "--traffic", "off")
+    assert off.traffic == "off" and extras(off) == {"run_cpu_baseline", "search_figures"}
+    assert extras(resolved("--full", "--pmc-child")) == set()  # the short run rocprofv3 wraps: launches only
+
+
 def test_cell_order_is_a_permutation_that_follows_space():
     """mrs_cell_order (host only): a permutation; UAVs that follow each other in it are close in space; unusable positions go last"""
     import numpy as np

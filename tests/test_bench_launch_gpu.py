@@ -247,3 +247,32 @@ def test_bench_dump_outputs_is_the_state_after_warmup_plus_steps(mrs, tmp_path):
     here = g.get_state(0, n)
     for k, a in here.items():
         assert np.array_equal(runs[0][k], a), k
+
+
+def test_plain_bench_line_is_the_headline_and_full_adds_the_rest():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times the headline and prints its line with no extra record; --full adds the
+    CPU baseline and the config-5 leg (smaller sizes here so that the test stays short)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+
+    def line(*extra):
+        p = subprocess.run([sys.executable, bench.__file__, "--gpus", "1", "--steps", "20", "--warmup", "5", "--uavs", "4096", *extra],
+                           capture_output=True, text=True, timeout=600, env=env)
+        assert p.returncode == 0, p.stderr[-2000:]
+        out = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, p.stdout[-2000:]
+        return json.loads(out[0])
+
+    plain = line()
+    assert plain["steps"] == 20 and plain["warmup"] == 5 and plain["regions"] == 1 and plain["ms_per_step"] > 0
+    assert plain["unit"] == "UAV-steps/s" and plain["higher_is_better"] is True and plain["dtype"] == "f64"
+    extras = ("cpu_baseline", "config5", "config5_peer", "hbm_streaming", "config4", "literal", "config2", "sharded_rank_standin", "io_tick")
+    assert not set(extras) & set(plain), sorted(plain)
+    assert "live" not in str(plain["roofline"]["traffic_source"])
+    full = line("--full", "--traffic", "off", "--cpu-seconds", "1", "--config5-uavs", "20000", "--min-measure-ms", "5")
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["all_cores"]["value"] > 0
+    assert "error" not in full["config5"] and full["config5"]["n_total"] == 20000 and full["config5"]["value"] > 0

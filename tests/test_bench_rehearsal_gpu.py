@@ -25,7 +25,7 @@ def _bench(*args, timeout=600, **env):
     return r, lines, time.time() - t0
 
 
-COMMON = ["--steps", "20", "--warmup", "5", "--uavs", "20000", "--config5-uavs", "200000", "--min-measure-ms", "5"]
+COMMON = ["--full", "--steps", "20", "--warmup", "5", "--uavs", "20000", "--config5-uavs", "200000", "--min-measure-ms", "5"]
 
 
 def test_bench_gpus_2_rehearsal_prints_one_line_with_both_config5_records():

@@ -12,9 +12,9 @@ timeout -k 10 1000 python -m pytest tests -x -q -m gpu -s > $OUT/gpu_tests.log 2
 tail -3 $OUT/gpu_tests.log
 : > $OUT/bench_all.jsonl
 b() { timeout -k 10 600 python bench.py "$@" 2>> $OUT/bench.err | tail -1 >> $OUT/bench_all.jsonl; }
-S="--sub-records off --config5 off --no-cpu-baseline"
-b
-b --steps 20 --warmup 5
+S="--full --sub-records off --config5 off --no-cpu-baseline"
+b --full
+b --full --steps 20 --warmup 5
 b --uavs 1000000 $S
 b --workload position $S
 b --workload position+collisions --uavs 50000 $S

@@ -42,8 +42,29 @@ def run_ranks(fns):
         raise (real + seen)[0] from RuntimeError(" | ".join(f"rank {k}: {e}" for k, e in enumerate(errs) if e is not None))
 
 
+def runs(keys):
+    """[(first, count, key)]: the maximal runs of equal consecutive entries of `keys`"""
+    out, a = [], 0
+    for i in range(1, len(keys) + 1):
+        if i == len(keys) or keys[i] != keys[a]:
+            out.append((a, i - a, keys[a]))
+            a = i
+    return out
+
+
+def set_inputs(sw, mode, rows, idx=None):
+    """per-UAV input modes and payload rows (None: no payload), by public index, of the UAVs idx (default: all) as set_input calls of
+    `sw` over the runs of equal mode and payload width; UAV idx[k] is UAV k of `sw`"""
+    idx = np.arange(len(mode)) if idx is None else idx
+    for a, c, (m, w) in runs([(int(mode[i]), 0 if rows[i] is None else len(rows[i])) for i in idx]):
+        sw.set_input(a, c, m, None if w == 0 else np.stack([rows[i] for i in idx[a:a + c]]))
+
+
 class VirtualShards:
-    """`world` shards of one swarm given in PUBLIC index order; order[k] = public index at sorted position k"""
+    """`world` shards of one swarm given in PUBLIC index order; order[k] = public index at sorted position k.
+    po: the airframe parameters of every UAV, or a list of them by public index (UAVs that share an airframe share the object);
+    mode / cmd: one input mode and a payload array [n_total, w], or a mode array and a list of payload rows (None: no payload), both
+    by public index."""
 
     def __init__(self, M, world, order, po, pos, heading, st, mode, cmd, arith, exchange, rendezvous=False):
         from mrs_multirotor_simulator_amd.sharded import shard_range
@@ -57,9 +78,17 @@ class VirtualShards:
             idx = order[lo:hi]
             g = M.Swarm(hi - lo, arith=arith)
             if hi > lo:
-                g.construct(0, hi - lo, po, None if pos is None else pos[idx], None if heading is None else heading[idx])
+                if isinstance(po, (list, tuple)):
+                    for a, c, _ in runs([id(po[i]) for i in idx]):
+                        sl = idx[a:a + c]
+                        g.construct(a, c, po[sl[0]], None if pos is None else pos[sl], None if heading is None else heading[sl])
+                else:
+                    g.construct(0, hi - lo, po, None if pos is None else pos[idx], None if heading is None else heading[idx])
                 g.set_state(0, hi - lo, st["x"][idx], st["v"][idx], st["R"][idx], st["omega"][idx], st["motor_rpm"][idx])
-                g.set_input(0, hi - lo, mode, cmd[idx])
+                if np.ndim(mode) == 0:
+                    g.set_input(0, hi - lo, mode, cmd[idx])
+                else:
+                    set_inputs(g, mode, cmd, idx)
             g.comm_init_loopback(self.group, r, self.n_total)
             g.set_exchange(exchange)
             self.shards.append((g, idx))

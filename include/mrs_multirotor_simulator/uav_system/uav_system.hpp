@@ -779,6 +779,12 @@ public:
                      int index_stride, int32_t* dev_count, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_nearest_device(s_, first, count, k, radius, fields, dev_rows, dtype, stride, dev_index, index_stride, dev_count, stream));
   }
+  // n_steps steps of the whole swarm; UAVs [first, first + count) take command row block t of dev_cmd before step t, and row block t of
+  // dev_obs receives their MRS_OBS_* groups after it (dev_obs may be null when groups == 0): the set-input / step / gather loop in one call
+  void rolloutDevice(int first, int count, int mode, double dt, int n_steps, const void* dev_cmd, int dtype, int cmd_stride, uint32_t groups,
+                     void* dev_obs, int obs_stride, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_rollout_device(s_, first, count, mode, dt, n_steps, dev_cmd, dtype, cmd_stride, groups, dev_obs, obs_stride, stream));
+  }
   // the whole simulation state of UAVs [first, first + count) into dev_records[0 .. count-1] (device memory, 16-B aligned)
   void saveDevice(int first, int count, mrs_uav_snapshot_t* dev_records, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_save_device(s_, first, count, dev_records, stream));

@@ -571,6 +571,29 @@ enum { MRS_SNAP_LOADED = 0, MRS_SNAP_SKIPPED = 1, MRS_SNAP_BAD_AIRFRAME = 2, MRS
 int mrs_swarm_load_device(mrs_swarm_t* s, int32_t first, int32_t count, const mrs_uav_snapshot_t* dev_records, int64_t n_records,
                           const int32_t* dev_index, uint8_t* dev_status, void* ext_stream);
 
+/* ---- device-resident rollouts: per-step commands in, observations out (sampling-based planners: MPPI, CEM, random shooting) ----
+ * Equals, bit for bit in LITERAL arithmetic, the loop
+ *   for t in [0, n_steps):
+ *     mrs_swarm_set_input_device(s, first, count, mode, row block t of dev_cmd, dtype, cmd_stride, ext_stream);
+ *     mrs_swarm_step_n(s, dt, 1, 1);
+ *     if (groups) mrs_swarm_gather_device(s, first, count, groups, row block t of dev_obs, dtype, obs_stride, ext_stream);
+ * run as launches of fused steps that read each step's command row and write each step's observation row in the step kernel.
+ * Command row (t, k), the setInput payload of UAV first + k before step t, starts at element ((size_t)t * count + k) * cmd_stride of
+ * dev_cmd, with the layout and width of mrs_swarm_set_input_device (ACTUATOR: min(cmd_stride, MRS_MAX_MOTORS) motors, checked against
+ * n_motors).  Observation row (t, k), the MRS_OBS_* groups of UAV first + k after step t, starts at element ((size_t)t * count + k) *
+ * obs_stride of dev_obs: the layout and the bits of mrs_swarm_gather_device.  One dtype serves both (FP32 commands are widened
+ * exactly, FP32 observations are the round-to-nearest cast); elements past a row's width are not touched.
+ * Every UAV of the swarm is stepped, as mrs_swarm_step_n steps it; UAVs outside the range keep their own commands and modes.  A UAV on
+ * hold is not stepped, but its command columns are written and its rows hold its unchanged state.  Afterwards the command columns of the
+ * range hold row block n_steps - 1 and its mode is `mode`.  The call enters like a state call (a pending collision tick is evaluated
+ * first and its force acts on the first step); collisions are not evaluated inside the rollout.  Stream order: ONE fence per call, that of
+ * the other device-resident calls.  Every argument is checked before anything is launched, and a refused call changes nothing: the range
+ * (MRS_ERR_RANGE), and MRS_ERR_ARG for the mode, the dtype, n_steps < 1, a dt that is not finite and > 0, cmd_stride below the command
+ * width, unknown group bits, obs_stride below the gather width, dev_obs NULL with groups != 0, pointers that are not device memory of the
+ * swarm's device or too small for all their rows, and a sharded swarm. */
+int mrs_swarm_rollout_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, const void* dev_cmd,
+                             int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,12 +4,9 @@
 // elements per UAV (FP64 or FP32).  The host entry points at the end validate every argument before anything is launched and fence
 // the caller's stream against the swarm's (include/mrs_swarm.h, "device-resident callers").
 #include "host_internal.h"
-#include "pose_math.h"
+#include "obs_row.h"
 
 namespace {
-
-// widths of the observation groups, in bit order (MRS_OBS_POS first)
-constexpr int kObsWidth[8] = {3, 3, 3, 9, 4, 3, 3, MRS_MAX_MOTORS};
 
 // Eigen::AngleAxisd(angle, UnitZ).toRotationMatrix() (Eigen/src/Geometry/AngleAxis.h), row-major out: the host's angle_axis_z
 // (host_api.hip) with the device's sin / cos
@@ -33,68 +30,29 @@ __device__ __forceinline__ void angle_axis_z_dev(double angle, double R[9]) {
   R[8] = ca[2] * ax[2] + c;
 }
 
-// observation groups of UAVs [first, first + count) into rows of `stride` elements, concatenated in bit order.  FP32 rows hold the
-// round-to-nearest cast of the FP64 value.  Direct per-lane stores, as k_pack_poses (LDS staging measured no better there).
+// what an observation row reads of UAV i: its state columns
+struct ColumnObs {
+  const SwarmDev& sw;
+  size_t          np;
+  int             i;
+  __device__ double col(int f) const { return sw.S[(size_t)f * np + i]; }
+  __device__ double x(int c) const { return col(F_X + c); }
+  __device__ double v(int c) const { return col(F_V + c); }
+  __device__ double R(int c) const { return col(F_R + c); }
+  __device__ double omega(int c) const { return col(F_W + c); }
+  __device__ double imu(int c) const { return col(F_IMU + c); }
+  __device__ double rpm(int m) const { return col(F_RPM + m); }
+  __device__ int    n_motors() const { return sw.T[sw.F[i] >> FLAG_TYPE_SHIFT].n_motors; }
+};
+
+// observation groups of UAVs [first, first + count) into rows of `stride` elements (obs_row.h).  Direct per-lane stores, as
+// k_pack_poses (LDS staging measured no better there).
 template <typename T>
 __global__ void __launch_bounds__(256) k_gather_rows(SwarmDev sw, int first, int count, uint32_t groups, T* rows, int stride) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= count) return;
-  const int    i  = first + k;
-  const size_t np = (size_t)sw.npad;
-#define LD(f) sw.S[(size_t)(f) * np + i]
-  double v[3], R[9];
-  if (groups & (MRS_OBS_VEL | MRS_OBS_VEL_BODY)) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) v[c] = LD(F_V + c);
-  }
-  if (groups & (MRS_OBS_VEL_BODY | MRS_OBS_ROT | MRS_OBS_QUAT)) {
-#pragma unroll
-    for (int c = 0; c < 9; c++) R[c] = LD(F_R + c);
-  }
-  T* o = rows + (size_t)k * (size_t)stride;
-  if (groups & MRS_OBS_POS) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) o[c] = (T)LD(F_X + c);
-    o += 3;
-  }
-  if (groups & MRS_OBS_VEL) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) o[c] = (T)v[c];
-    o += 3;
-  }
-  if (groups & MRS_OBS_VEL_BODY) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) o[c] = (T)body_velocity(R, v, c);
-    o += 3;
-  }
-  if (groups & MRS_OBS_ROT) {
-#pragma unroll
-    for (int c = 0; c < 9; c++) o[c] = (T)R[c];
-    o += 9;
-  }
-  if (groups & MRS_OBS_QUAT) {
-    double q[4];
-    quat_from_matrix(R, q);
-#pragma unroll
-    for (int c = 0; c < 4; c++) o[c] = (T)q[c];
-    o += 4;
-  }
-  if (groups & MRS_OBS_OMEGA) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) o[c] = (T)LD(F_W + c);
-    o += 3;
-  }
-  if (groups & MRS_OBS_IMU) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) o[c] = (T)LD(F_IMU + c);
-    o += 3;
-  }
-  if (groups & MRS_OBS_RPM) {  // 0 past n_motors, as k_pack_states
-    const int nm = sw.T[sw.F[i] >> FLAG_TYPE_SHIFT].n_motors;
-#pragma unroll
-    for (int m = 0; m < MRS_MAX_MOTORS; m++) o[m] = (T)(m < nm ? LD(F_RPM + m) : 0.0);
-  }
-#undef LD
+  const ColumnObs src{sw, (size_t)sw.npad, first + k};
+  mrs_obs_row(src, groups, rows + (size_t)k * (size_t)stride);
 }
 
 // setInput payload rows (FP64 or FP32, device-resident) into the command columns F_CMD + j, and the mode bits of the flag word: what
@@ -148,6 +106,25 @@ __global__ void __launch_bounds__(256) k_crashed_u8(const uint32_t* F, int first
 }
 
 inline dim3 grid_of(int count) { return dim3((unsigned)((count + 255) / 256)); }
+
+// payload elements of a command row of `mode`: the widths of mrs_swarm_set_input (ACTUATOR: the row's stride, at most MRS_MAX_MOTORS)
+int command_width(int mode, int stride) {
+  switch (mode) {
+    case MRS_INPUT_UNKNOWN: return 0;
+    case MRS_ACTUATOR_CMD: return stride < MRS_MAX_MOTORS ? stride : MRS_MAX_MOTORS;
+    case MRS_ATTITUDE_CMD: return 10;
+    case MRS_TILT_HDG_RATE_CMD: return 5;
+    default: return 4;
+  }
+}
+
+// an ACTUATOR payload of `width` motors must cover every motor of UAVs [first, first + count)
+bool actuator_width_ok(const mrs_swarm* s, int first, int count, int width) {
+  if (width >= MRS_MAX_MOTORS) return true;
+  for (int k = 0; k < count; k++)
+    if (s->keys[s->uav_type[(size_t)first + k]].mp.n_motors > width) return false;
+  return true;
+}
 
 }  // namespace
 
@@ -235,22 +212,12 @@ int mrs_swarm_set_input_device(mrs_swarm_t* s, int32_t first, int32_t count, int
   if (mode < MRS_INPUT_UNKNOWN || mode > MRS_POSITION_CMD) return fail(MRS_ERR_ARG, "bad input mode");
   if ((rc = check_dtype(dtype))) return rc;
   if (count == 0) return MRS_OK;
-  int width = 0;  // the payload widths of mrs_swarm_set_input
-  switch (mode) {
-    case MRS_INPUT_UNKNOWN: width = 0; break;
-    case MRS_ACTUATOR_CMD: width = stride < MRS_MAX_MOTORS ? stride : MRS_MAX_MOTORS; break;
-    case MRS_ATTITUDE_CMD: width = 10; break;
-    case MRS_TILT_HDG_RATE_CMD: width = 5; break;
-    default: width = 4; break;
-  }
+  const int width = command_width(mode, stride);  // the payload widths of mrs_swarm_set_input
   if (width > 0) {
     if (stride < width || width < 1) return fail(MRS_ERR_ARG, "stride too small for this mode");
     if ((rc = check_device_ptr(s, dev_rows, rows_bytes(count, stride, width, dtype), "dev_rows"))) return rc;
   }
-  if (mode == MRS_ACTUATOR_CMD && width < MRS_MAX_MOTORS) {
-    for (int k = 0; k < count; k++)
-      if (s->keys[s->uav_type[(size_t)first + k]].mp.n_motors > width) return fail(MRS_ERR_ARG, "actuator payload narrower than n_motors");
-  }
+  if (mode == MRS_ACTUATOR_CMD && !actuator_width_ok(s, first, count, width)) return fail(MRS_ERR_ARG, "actuator payload narrower than n_motors");
   HIPCHK(hipSetDevice(s->device));
   hipStream_t ext = (hipStream_t)ext_stream;
   if ((rc = fence_in(s, ext))) return rc;
@@ -333,6 +300,55 @@ int mrs_swarm_reset_device(mrs_swarm_t* s, int32_t first, int32_t count, const u
                        static_cast<const double*>(dev_pos), static_cast<const double*>(dev_heading), takeoff);
   HIPCHK(hipGetLastError());
   s->nbr_dirty = true;  // positions changed under the neighbour lists (what put_column notes for a host write of F_X)
+  return fence_out(s, ext);
+}
+
+int mrs_swarm_rollout_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, const void* dev_cmd,
+                             int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream) {
+  MRS_LOCK(s);  // (MRS_ENTER after the argument checks: a refused call launches nothing)
+  int rc = check_range(s, first, count);
+  if (rc) return rc;
+  if (s->comm_world > 0) return fail(MRS_ERR_ARG, "mrs_swarm_rollout_device: not on a sharded swarm");
+  if (mode < MRS_INPUT_UNKNOWN || mode > MRS_POSITION_CMD) return fail(MRS_ERR_ARG, "bad input mode");
+  if ((rc = check_dtype(dtype))) return rc;
+  if (n_steps < 1) return fail(MRS_ERR_ARG, "n_steps must be at least 1");
+  if (!(dt > 0) || !std::isfinite(dt)) return fail(MRS_ERR_ARG, "dt must be finite and > 0");
+  const int width = command_width(mode, cmd_stride);
+  if (width > 0 && (cmd_stride < width || width < 1)) return fail(MRS_ERR_ARG, "cmd_stride too small for this mode");
+  int32_t obs_width = 0;
+  if ((rc = mrs_swarm_gather_width(groups, &obs_width))) return rc;
+  if (groups != 0u && obs_stride < obs_width) return fail(MRS_ERR_ARG, "obs_stride smaller than the width of the selected groups");
+  if (count > 0) {
+    // rows of all n_steps row blocks; 64-bit: n_steps x count x stride can pass 2^31 elements
+    const size_t rows = (size_t)n_steps * (size_t)count;
+    if (width > 0 && (rc = check_device_ptr(s, dev_cmd, ((rows - 1) * (size_t)cmd_stride + (size_t)width) * dtype_bytes(dtype), "dev_cmd"))) return rc;
+    if (groups != 0u && (rc = check_device_ptr(s, dev_obs, ((rows - 1) * (size_t)obs_stride + (size_t)obs_width) * dtype_bytes(dtype), "dev_obs")))
+      return rc;
+    if (mode == MRS_ACTUATOR_CMD && !actuator_width_ok(s, first, count, width)) return fail(MRS_ERR_ARG, "actuator payload narrower than n_motors");
+  }
+  if (s->n == 0) return MRS_OK;
+  if ((rc = settle(s))) return rc;  // MRS_ENTER: a pending collision tick is evaluated first, its force acts on the first step
+  HIPCHK(hipSetDevice(s->device));
+  if ((rc = upload_types(s, dt))) return rc;
+  // the host's mirror of the modes first: the launcher picks the cascade or the model-only kernels as mrs_swarm_step_n would after the
+  // first mrs_swarm_set_input_device of the loop
+  if (count > 0) {
+    const uint8_t* m    = s->uav_mode.data() + first;
+    unsigned       diff = 0;
+    for (int k = 0; k < count; k++) diff |= (unsigned)(m[k] ^ (uint8_t)mode);
+    if (diff) track_mode(s, first, count, mode);
+  }
+  hipStream_t ext = (hipStream_t)ext_stream;
+  if ((rc = fence_in(s, ext))) return rc;
+  s->collide_since_step = false;
+  s->p_valid            = false;  // (plain steps do not refresh the position records)
+  const RolloutDev r{dev_cmd, groups != 0u ? dev_obs : nullptr, first, count, cmd_stride, width, obs_stride, 0, (uint32_t)mode << FLAG_MODE_SHIFT,
+                     groups, dtype == MRS_DTYPE_F32 ? 1 : 0};
+  const int variant = s->n_cascade > 0 ? 0 : 1;  // 0 all input modes | 1 model only
+  if (s->arith == MRS_ARITH_FAST)
+    HIPCHK(mrs_launch_rollout_fast(s->view(), r, dt, n_steps, variant, s->stream));
+  else
+    HIPCHK(mrs_launch_rollout_literal(s->view(), r, dt, n_steps, variant, s->stream));
   return fence_out(s, ext);
 }
 

@@ -1,0 +1,72 @@
+// obs_row.h — one observation row of a UAV: the MRS_OBS_* groups of include/mrs_swarm.h concatenated in bit order.  Shared by
+// mrs_swarm_gather_device (device_io.hip, values from the state columns) and mrs_swarm_rollout_device (rollout_device.inc, values
+// from the step kernel's registers), so both write the same bits.  The FAST step unit compiles with -ffp-contract=fast: the pragma
+// here and pose_math.h (the pragmas, and opaque products where the backend would fuse anyway) keep every expression of a row
+// uncontracted in either unit.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/mrs_swarm.h"
+#include "pose_math.h"
+
+// widths of the observation groups, in bit order (MRS_OBS_POS first)
+constexpr int kObsWidth[8] = {3, 3, 3, 9, 4, 3, 3, MRS_MAX_MOTORS};
+
+// The row of `groups` into o[0 .. width).  FP32 rows hold the round-to-nearest cast of the FP64 value.  Src supplies the values:
+// x(c), v(c), omega(c), imu(c) for c < 3, R(c) for c < 9 (row-major), n_motors() and rpm(m); a group's values are asked for only
+// when the group is selected.
+template <typename T, class Src>
+__device__ __forceinline__ void mrs_obs_row(const Src& src, const uint32_t groups, T* o) {
+#pragma clang fp contract(off)
+  double v[3], R[9];
+  if (groups & (MRS_OBS_VEL | MRS_OBS_VEL_BODY)) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) v[c] = src.v(c);
+  }
+  if (groups & (MRS_OBS_VEL_BODY | MRS_OBS_ROT | MRS_OBS_QUAT)) {
+#pragma unroll
+    for (int c = 0; c < 9; c++) R[c] = src.R(c);
+  }
+  if (groups & MRS_OBS_POS) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) o[c] = (T)src.x(c);
+    o += 3;
+  }
+  if (groups & MRS_OBS_VEL) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) o[c] = (T)v[c];
+    o += 3;
+  }
+  if (groups & MRS_OBS_VEL_BODY) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) o[c] = (T)body_velocity(R, v, c);
+    o += 3;
+  }
+  if (groups & MRS_OBS_ROT) {
+#pragma unroll
+    for (int c = 0; c < 9; c++) o[c] = (T)R[c];
+    o += 9;
+  }
+  if (groups & MRS_OBS_QUAT) {
+    double q[4];
+    quat_from_matrix(R, q);
+#pragma unroll
+    for (int c = 0; c < 4; c++) o[c] = (T)q[c];
+    o += 4;
+  }
+  if (groups & MRS_OBS_OMEGA) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) o[c] = (T)src.omega(c);
+    o += 3;
+  }
+  if (groups & MRS_OBS_IMU) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) o[c] = (T)src.imu(c);
+    o += 3;
+  }
+  if (groups & MRS_OBS_RPM) {  // 0 past n_motors, as k_pack_states
+    const int nm = src.n_motors();
+#pragma unroll
+    for (int m = 0; m < MRS_MAX_MOTORS; m++) o[m] = (T)(m < nm ? src.rpm(m) : 0.0);
+  }
+}

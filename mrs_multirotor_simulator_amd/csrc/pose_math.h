@@ -1,12 +1,14 @@
 // pose_math.h — per-UAV pose expressions shared by the kernel units that derive published quantities from the state columns
-// (outputs.hip: publisher payloads; device_io.hip: observation rows for device-resident callers).  Both units are compiled with
-// -ffp-contract=off, so one expression gives the same bits in either.
+// (outputs.hip: publisher payloads; device_io.hip and rollout_device.inc: observation rows for device-resident callers, obs_row.h).
+// Each function turns FP contraction off for itself (and body_velocity keeps its products unfused in a -ffp-contract=fast unit), so
+// one expression gives the same bits in every unit that includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
 // Eigen::Quaterniond(Matrix3d) (what mrs_lib::AttitudeConverter(R) stores): Eigen/src/Geometry/Quaternion.h,
 // quaternionbase_assign_impl<Other,3,3>.  R row-major; q = {x, y, z, w}.
 __device__ __forceinline__ void quat_from_matrix(const double m[9], double q[4]) {
+#pragma clang fp contract(off)  // (no product here feeds an add: nothing a -ffp-contract=fast unit could fuse either)
   double t = (m[0] + m[4]) + m[8];
   if (t > 0) {
     t    = sqrt(t + 1.0);
@@ -45,7 +47,18 @@ __device__ __forceinline__ void quat_from_matrix(const double m[9], double q[4])
   }
 }
 
+// A product the code generator must not fuse into the add that follows.  In a unit compiled with -ffp-contract=fast (the FAST step
+// unit, which includes this file through obs_row.h) the backend contracts every multiply-add it sees, whatever the pragma says; an empty
+// asm makes the product opaque there.  Elsewhere it is the plain product.
+__device__ __forceinline__ double mrs_unfused(double x) {
+#if defined(MRS_FAST) && MRS_FAST
+  asm("" : "+v"(x));
+#endif
+  return x;
+}
+
 // component c of R^T v (odom.twist.twist.linear, src/uav_system_ros.cpp:356); R row-major
 __device__ __forceinline__ double body_velocity(const double R[9], const double v[3], int c) {
-  return (R[c] * v[0] + R[3 + c] * v[1]) + R[6 + c] * v[2];
+#pragma clang fp contract(off)
+  return (mrs_unfused(R[c] * v[0]) + mrs_unfused(R[3 + c] * v[1])) + mrs_unfused(R[6 + c] * v[2]);
 }

@@ -1154,9 +1154,23 @@ DEV bool coll_fold_and_decide(CDT& cd0, const int part, const uint32_t stall_own
 // kernels only (collisions act between any two steps).
 // `took_part` (COLL kernels of a split sharded tick): set once the wave-uniform exits are behind the block — the block then owes its
 // epoch word / ticket to the launches that run beside this one (step_kernel_publish), whatever its lanes do afterwards.
-template <bool CASCADE, bool UNIFORM, int NU, bool MULTI, int SU, bool COLL, bool PIDPRE = false, bool SHARD = false, class SW, class CDT>
-DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, const int substeps_arg, CDT& cd0, int& blk_out, bool& took_part) {
+// HK: what a launch does around each fused sub-step besides stepping (MULTI only; rollout_device.inc).  enter() runs once per lane
+// after the wave-uniform exits and may finish the lane itself (true); cmd(s) runs at the top of sub-step s, before the controller
+// cascade, and obs(s) after post_step.  The default does nothing: every kernel of this file compiles as it did without the hook.
+struct NoStepHook {
+  template <class SW>
+  __device__ __forceinline__ bool enter(const SW&, int, Lane&, int) const { return false; }
+  template <class SW>
+  __device__ __forceinline__ void cmd(const SW&, int, int) const {}
+  template <class SW, class PT>
+  __device__ __forceinline__ void obs(const SW&, PT&, int, const Lane&, int) const {}
+};
+template <bool CASCADE, bool UNIFORM, int NU, bool MULTI, int SU, bool COLL, bool PIDPRE = false, bool SHARD = false, class HK = NoStepHook, class SW,
+          class CDT>
+DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, const int substeps_arg, CDT& cd0, int& blk_out, bool& took_part,
+                          const HK& hk = HK()) {
   static_assert(!COLL || (NU == 1 && !MULTI), "fused collision evaluation: one UAV per lane, one step per launch");
+  static_assert(__is_same(HK, NoStepHook) || (NU == 1 && MULTI && !COLL), "sub-step hooks: one UAV per lane, fused sub-steps, no collisions");
   // MULTI = false compiles the substep loop away: with the loop the state is loop-carried and the per-type constants are
   // hoisted in front of it, which costs the fused kernel ~120 registers (350 vs 227) and with them its second wave per SIMD
   const int substeps = MULTI ? substeps_arg : 1;
@@ -1352,6 +1366,7 @@ DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, co
     asm volatile("" ::: "memory");
   }
   MRS_STAMP(2)
+  if (hk.enter(sw, idx[0], L[0], substeps)) return;
   if (!COLL && (L[0].flags & FLAG_HOLD)) return;    // UavSystemRos::makeStep does not iterate this UAV (src/uav_system_ros.cpp:265)
 #pragma unroll
   for (int u = 0; u < NU; u++) {
@@ -1414,6 +1429,7 @@ DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, co
       int    src_;                                                                                                    \
       double cg_[4];                                                                                                  \
       if (L[u].y[0] != L[u].y[0] + 1e300) { MRS_STAMP(3) }                                                           \
+      hk.cmd(sw, idx[u], s);                                                                                          \
       control_cascade<CASCADE, !MULTI, PIDPRE>(sw, P, idx[u], L[u], dt, inv_dt, src_, cg_);                           \
       if (cg_[0] != cg_[0] + 1e300) { MRS_STAMP(4) }                                                                  \
       if (COLL) {                                                                                                     \
@@ -1432,6 +1448,7 @@ DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, co
     rk4_integrate<NU, SU>(sw, P, sc, L, idx, dt, MULTI ? y_backup : nullptr);                                                                     \
     _Pragma("unroll") for (int u = 0; u < NU; u++)                                                                    \
         post_step(sw, P, idx[u] < 0 ? idx[0] : idx[u], L[u], mean_in[u], dt, inv_dt);                                 \
+    hk.obs(sw, P, idx[0], L[0], s);                                                                                   \
   }
   double thrust_now = 0.0;  // SHARD kernels: allocation * rpm^2 of this step (after the motor low-pass), kept for the displacement bound
   if (UNIFORM) {

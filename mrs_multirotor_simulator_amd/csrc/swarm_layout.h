@@ -88,6 +88,18 @@ struct SwarmDev {
   int32_t             fast;     // MRS_ARITH_FAST swarm: the stand-alone collision passes use the FAST force expression too (collide_device.inc)
 };
 
+// ---- one launch of a device-resident rollout (mrs_swarm_rollout_device, rollout_device.inc): caller-owned rows of a run of steps ----
+struct RolloutDev {
+  const void* cmd;         // command row (t, k) at element ((t * count) + k) * cmd_stride: setInput payload of UAV first + k before step t
+  void*       obs;         // observation row (t, k) at element ((t * count) + k) * obs_stride: the `groups` of UAV first + k after step t
+  int32_t     first, count;
+  int32_t     cmd_stride, width, obs_stride;
+  int32_t     t0;          // the rollout step of the launch's first sub-step
+  uint32_t    mode_bits;   // input mode << FLAG_MODE_SHIFT
+  uint32_t    groups;      // MRS_OBS_* (0: no observation rows)
+  int32_t     f32;         // rows are FP32 (else FP64)
+};
+
 // 48-byte record exchanged for the collision pass (single- and multi-GPU): everything
 // MultirotorSimulator::handleCollisions reads of the partner UAV (src/multirotor_simulator.cpp:339-350)
 struct PosRecord {

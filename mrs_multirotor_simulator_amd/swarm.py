@@ -112,6 +112,7 @@ ABI_SYMBOLS = [
     "mrs_swarm_get_poses", "mrs_swarm_get_poses_view", "mrs_swarm_get_poses_async", "mrs_swarm_poses_wait", "mrs_swarm_get_download_stats",
     "mrs_swarm_device", "mrs_swarm_gather_width", "mrs_swarm_set_input_device", "mrs_swarm_gather_device", "mrs_swarm_get_crashed_device",
     "mrs_swarm_reset_device", "mrs_nearest_width", "mrs_swarm_nearest_device", "mrs_swarm_save_device", "mrs_swarm_load_device",
+    "mrs_swarm_rollout_device",
 ]
 
 # device-resident callers (mrs_swarm_*_device): row element types and the observation groups of mrs_swarm_gather_device, in bit order
@@ -342,6 +343,7 @@ def load_library():
         "mrs_swarm_nearest_device": [vp, i32, i32, i32, C.c_double, C.c_uint32, vp, i32, i32, vp, i32, vp, vp],
         "mrs_swarm_save_device": [vp, i32, i32, vp, vp],
         "mrs_swarm_load_device": [vp, i32, i32, vp, C.c_int64, vp, vp, vp],
+        "mrs_swarm_rollout_device": [vp, i32, i32, i32, C.c_double, i32, vp, i32, i32, C.c_uint32, vp, i32, vp],
     }
     for name, args in sig.items():
         if os.environ.get("MRS_SWARM_LIB") and not hasattr(L, name):
@@ -816,6 +818,11 @@ class Swarm:
     def load_device(self, first, count, dev_records, n_records, dev_index, dev_status, ext_stream):
         _check(_lib.mrs_swarm_load_device(self._h, int(first), int(count), dev_records or None, int(n_records), dev_index or None,
                                           dev_status or None, ext_stream or None))
+
+    def rollout_device(self, first, count, mode, dt, n_steps, dev_cmd, dtype, cmd_stride, groups, dev_obs, obs_stride, ext_stream):
+        _check(_lib.mrs_swarm_rollout_device(self._h, int(first), int(count), int(mode), C.c_double(float(dt)), int(n_steps), dev_cmd or None,
+                                             int(dtype), int(cmd_stride), C.c_uint32(int(groups)), dev_obs or None, int(obs_stride),
+                                             ext_stream or None))
 
     def get_diag(self):
         d = Diag()

@@ -1,5 +1,5 @@
-"""torch tensors in and out of a Swarm without the host: commands, observations, nearest-neighbour observations, masked resets, crash
-flags and state snapshots for a controller, policy or reward that lives on the swarm's GPU (include/mrs_swarm.h, "device-resident callers").
+"""torch tensors in and out of a Swarm without the host: commands, observations, rollouts, nearest-neighbour observations, masked resets,
+crash flags and state snapshots for a controller, policy or reward that lives on the swarm's GPU (include/mrs_swarm.h, "device-resident callers").
 
 Every call passes torch's current stream of the swarm's device as the caller stream: the library fences its own stream against it, so
 tensors written on that stream before the call are what the kernel reads, and work queued after the call sees the result.  Tensors are
@@ -103,6 +103,60 @@ def set_input(swarm, mode, rows, first=0):
         raise ValueError("actuator rows must be dense (row stride == number of motors)")
     ptr = rows.data_ptr() if width > 0 and count > 0 else 0
     swarm.set_input_device(first, count, mode, ptr, code, stride, _stream(dev))
+
+
+def _check_steps(t, name, steps, rows, min_width, dtype, device_index):
+    """Refuse `t` unless it is a [steps, rows, >= min_width] tensor on cuda:`device_index` of `dtype` (steps None: any number >= 1) whose
+    rows are contiguous and whose row blocks follow each other densely: stride(0) == rows * stride(1).  Returns the row stride."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
+    if t.device.type != "cuda":
+        raise ValueError(f"{name} is on {t.device}: device-resident calls need a tensor on cuda:{device_index}")
+    if t.device.index != device_index:
+        raise ValueError(f"{name} is on {t.device}, the swarm lives on cuda:{device_index}")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} has dtype {t.dtype}, expected {dtype}")
+    if t.dim() != 3 or t.shape[0] < 1 or (steps is not None and t.shape[0] != steps) or t.shape[1] != rows or t.shape[2] < min_width:
+        raise ValueError(f"{name}: expected a [{'T' if steps is None else steps}, {rows}, >= {min_width}] tensor, got shape {tuple(t.shape)}")
+    if t.shape[2] > 1 and t.stride(2) != 1:
+        raise ValueError(f"{name}: rows are not contiguous: the stride of the last dimension is {t.stride(2)}, must be 1")
+    stride = t.stride(1) if rows > 1 else t.shape[2]
+    if stride < t.shape[2]:
+        raise ValueError(f"{name}: rows overlap: row stride {stride} < row width {t.shape[2]}")
+    if t.shape[0] > 1 and t.stride(0) != rows * stride:
+        raise ValueError(f"{name}: the step dimension is not dense (stride(0) = {t.stride(0)}, expected {rows} x {stride})")
+    return stride
+
+
+def rollout(swarm, mode, commands, dt, groups=OBS_POS | OBS_VEL | OBS_QUAT, first=0, out=None):
+    """T steps of the whole swarm in which UAVs [first, first + count) take command row block t before step t and report the OBS_* groups
+    of `groups` after it (mrs_swarm_rollout_device): `for t: set_input(swarm, mode, commands[t], first); swarm.step_n(dt, 1);
+    gather(swarm, groups, first, count, out=out[t])`, bit for bit in LITERAL, in one call.  commands: [T, count, >= width] FP32 / FP64
+    (the payload layouts of set_input; ACTUATOR rows are dense).  out: [T, count, >= gather_width(groups)] of the same dtype, allocated
+    when None; returned (None when groups == 0).  UAVs outside the range are stepped with their own commands."""
+    dev = swarm.device()
+    if not isinstance(commands, torch.Tensor) or commands.dim() != 3:
+        raise ValueError("commands must be a [T, count, width] tensor")
+    code = _dtype_code(commands.dtype)
+    steps, count = commands.shape[0], commands.shape[1]
+    width = command_width(mode, commands.shape[2])
+    cstride = _check_steps(commands, "commands", None, count, width, commands.dtype, dev)
+    if mode == ACTUATOR_CMD and count > 1 and cstride != commands.shape[2]:
+        raise ValueError("actuator rows must be dense (row stride == number of motors)")
+    owidth = gather_width(groups)
+    optr, ostride = 0, owidth
+    if groups:
+        if out is None:
+            out = torch.empty((steps, count, owidth), dtype=commands.dtype, device=torch.device("cuda", dev))
+        if isinstance(out, torch.Tensor) and out.dtype != commands.dtype:
+            raise ValueError(f"out has dtype {out.dtype}, the commands {commands.dtype}: one dtype serves both")
+        ostride = _check_steps(out, "out", steps, count, owidth, commands.dtype, dev)
+        optr = out.data_ptr()
+    cptr = commands.data_ptr() if width > 0 and count > 0 else 0
+    swarm.rollout_device(first, count, mode, dt, steps, cptr, code, cstride, groups, optr, ostride, _stream(dev))
+    if not groups:
+        return None
+    return out[:, :, :owidth] if out.shape[2] > owidth else out
 
 
 def crashed(swarm, first=0, count=None, out=None):

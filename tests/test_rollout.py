@@ -1,0 +1,128 @@
+"""CPU-side checks of device-resident rollouts (include/mrs_swarm.h, "device-resident rollouts"): the call is exported and listed, the
+header prototype and the ctypes argtypes agree, tensors.rollout refuses what the library must never see, every rollout kernel of
+rollout_device.inc has a row in test_rollout_gpu.ROLLOUT_KERNELS, and tests/cpp/rollout_test.cpp compiles.  CPU tensors only: no
+pointer reaches the library."""
+import ctypes as C
+import os
+import re
+
+import pytest
+
+import test_rollout_gpu as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "mrs_multirotor_simulator_amd", "csrc", "rollout_device.inc")
+CTYPE = {"mrs_swarm_t*": C.c_void_p, "const void*": C.c_void_p, "void*": C.c_void_p, "int32_t": C.c_int32, "uint32_t": C.c_uint32,
+         "double": C.c_double}
+
+
+def test_symbol_is_exported_and_listed(mrs):
+    from mrs_multirotor_simulator_amd import swarm
+    assert hasattr(C.CDLL(swarm.LIB_PATH), "mrs_swarm_rollout_device")
+    assert "mrs_swarm_rollout_device" in swarm.ABI_SYMBOLS
+
+
+def test_header_prototype_equals_the_argtypes(mrs):
+    from mrs_multirotor_simulator_amd import swarm
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mrs_swarm.h")).read(), flags=re.S)
+    m = re.search(r"int\s+mrs_swarm_rollout_device\(([^)]*)\);", src)
+    assert m, "prototype"
+    params = [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
+    types = [re.match(r"(.*?)\s*\b\w+$", p).group(1).replace(" *", "*") for p in params]
+    assert [p.rsplit(" ", 1)[-1].lstrip("*") for p in params] == ["s", "first", "count", "mode", "dt", "n_steps", "dev_cmd", "dtype",
+                                                                  "cmd_stride", "groups", "dev_obs", "obs_stride", "ext_stream"]
+    got = swarm.load_library().mrs_swarm_rollout_device.argtypes
+    assert [CTYPE[t] for t in types] == list(got), (types, got)
+
+
+class _Dev:
+    def __init__(self, index):
+        self.type, self.index = "cuda", index
+
+    def __str__(self):
+        return f"cuda:{self.index}"
+
+
+class _Swarm:
+    """stands in for a Swarm on cuda:0: the library must never be reached"""
+    n = 100
+
+    def device(self):
+        return 0
+
+    def rollout_device(self, *a):
+        raise AssertionError("a refused tensor reached the library")
+
+
+def test_rollout_refuses_bad_tensors(monkeypatch):
+    """CPU tensors dressed as cuda tensors (only .device is faked; nothing is launched)"""
+    import torch
+    from mrs_multirotor_simulator_amd import tensors as T
+
+    class Fake(torch.Tensor):
+        pass
+
+    def on(t, index=0):
+        f = t.as_subclass(Fake)
+        f._fake_dev = _Dev(index)
+        return f
+
+    monkeypatch.setattr(Fake, "device", property(lambda self: getattr(self, "_fake_dev", _Dev(0))), raising=False)
+    g, f64, pos = _Swarm(), torch.float64, T.OBS_POS  # (mode 10: POSITION_CMD)
+    out = on(torch.zeros(5, 10, 3, dtype=f64))
+    cases = [
+        (torch.zeros(5, 10, 4, dtype=f64), out, "is on cpu"),                                   # CPU tensor
+        (on(torch.zeros(5, 10, 4, dtype=f64), 1), out, "the swarm lives on cuda:0"),           # another device
+        (on(torch.zeros(5, 10, 4, dtype=torch.float16)), out, "float32 or torch.float64"),     # dtype
+        (on(torch.zeros(5, 10, 4)), out, "one dtype serves both"),                              # mismatched dtypes
+        (on(torch.zeros(5, 10, 3, dtype=f64)), out, r">= 4\] tensor"),                         # too narrow
+        (on(torch.zeros(10, 4, dtype=f64)), out, r"\[T, count, width\]"),                       # no step dimension
+        (on(torch.zeros(5, 10, 4, dtype=f64)), on(torch.zeros(4, 10, 3, dtype=f64)), r"\[5, 10, >= 3\]"),  # out of other T
+        (on(torch.zeros(5, 10, 4, dtype=f64)), on(torch.zeros(5, 10, 2, dtype=f64)), r">= 3\]"),  # out too narrow
+        (on(torch.zeros(10, 5, 4, dtype=f64).transpose(0, 1)), out, "step dimension is not dense"),
+        (on(torch.zeros(5, 10, 8, dtype=f64)[::2, :, :4]), out, "step dimension is not dense"),
+        (on(torch.zeros(5, 4, 10, dtype=f64).transpose(1, 2)), out, "rows are not contiguous"),
+        (on(torch.zeros(5, 10, 4, dtype=f64)), on(torch.zeros(5, 3, 10, dtype=f64).transpose(1, 2)), "rows are not contiguous"),
+        (on(torch.zeros(5, 10, 4, dtype=f64)), torch.zeros(5, 10, 3, dtype=f64), "is on cpu"),  # out on the CPU
+    ]
+    for cmd, o, msg in cases:
+        with pytest.raises(ValueError, match=msg):
+            T.rollout(g, 10, cmd, 0.001, pos, out=o)
+    with pytest.raises(ValueError, match="actuator rows must be dense"):
+        T.rollout(g, T.ACTUATOR_CMD, on(torch.zeros(5, 10, 6, dtype=f64)[:, :, :4]), 0.001, pos, out=out)
+    with pytest.raises(ValueError, match="commands must be"):
+        T.rollout(g, 10, [[[0.0] * 4] * 10] * 5, 0.001, pos, out=out)
+
+
+def rollout_kernel_entry_points(text):
+    """names of the MRS_ROLLOUT_KERNEL(name, ...) instantiations (the idea of test_step_kernel_table.step_kernel_entry_points)"""
+    names = set()
+    for line in text.splitlines():
+        m = re.match(r"MRS_ROLLOUT_KERNEL\(\s*(\w+)\s*,", line.strip())
+        if m:
+            names.add(m.group(1))
+    return names
+
+
+def test_every_rollout_kernel_has_a_row():
+    with open(SRC) as f:
+        names = rollout_kernel_entry_points(f.read())
+    assert len(names) == 5, sorted(names)
+    table = set(R.ROLLOUT_KERNELS)
+    assert not names - table, f"rollout kernels without a row in ROLLOUT_KERNELS: {sorted(names - table)}"
+    assert not table - names, f"rows naming kernels rollout_device.inc no longer compiles: {sorted(table - names)}"
+    for kernel, where in R.ROLLOUT_KERNELS.items():
+        for w in where:
+            assert callable(getattr(R, w.split("[")[0], None)), f"{kernel}: {w} is no test of test_rollout_gpu"
+    # and none of them is a step-kernel line: the step-kernel matrix of test_step_variants_gpu stays as it is
+    step = open(os.path.join(ROOT, "mrs_multirotor_simulator_amd", "csrc", "step_device.inc")).read()
+    assert "rollout" not in " ".join(re.findall(r"MRS_STEP_KERNEL\w*\(\s*(\w+)", step))
+
+
+def test_rollout_test_compiles(mrs, tmp_path):
+    import subprocess
+    from mrs_multirotor_simulator_amd import swarm
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-DMRS_NO_EIGEN", "-D__HIP_PLATFORM_AMD__", "-I",
+                           os.path.join(ROOT, "include"), "-I", "/opt/rocm/include", os.path.join(ROOT, "tests", "cpp", "rollout_test.cpp"),
+                           "-o", str(tmp_path / "rollout_test"), "-L", os.path.dirname(swarm.LIB_PATH), "-lmrs_swarm", "-L", "/opt/rocm/lib",
+                           "-lamdhip64", "-lpthread"])

@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""A planner's rollout of T steps through the device-resident loop against one mrs_swarm_rollout_device call.  n x500 UAVs take FP32
+command rows of one mode before each step and report FP32 POS | VEL | QUAT rows after it:
+  loop     for t: tensors.set_input(cmd[t]); step_n(dt, 1); tensors.gather(out=obs[t])     (three dependent launches, two fences per step)
+  rollout  tensors.rollout(cmd, dt, out=obs)                                                 (fused steps; one fence per call)
+alternating in one process, per mode and size (a warm-up, then `reps` rounds).  Timed with hipEvents on torch's current stream; prints
+us per step (median, min-max).  In LITERAL (the default) both forms must end bit-identical: the tool asserts it (rows and state).  In FAST
+the rollout runs the fused kernels and the loop the single-step ones, which differ in the last bits: the tool prints the largest
+relative difference of the rows instead.
+
+    python tools/rollout_rate.py [sizes=100000,1000000] [T=64] [reps=5] [modes=ACTUATOR_CMD,ATTITUDE_RATE_CMD,VELOCITY_HDG_CMD] [forms=loop,rollout] [arith=literal]
+
+(`forms=rollout` runs the rollout alone, e.g. under rocprofv3 --kernel-trace --stats; the bit-identity check then has no partner.)
+"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+import mrs_multirotor_simulator_amd as M  # noqa: E402
+
+DT = 0.001
+
+
+def commands(mode, n, steps, rng):
+    if mode == M.ACTUATOR_CMD:
+        return rng.uniform(0.45, 0.6, (steps, n, 4))
+    if mode == M.ATTITUDE_RATE_CMD:
+        return np.concatenate([rng.uniform(-0.3, 0.3, (steps, n, 3)), rng.uniform(0.5, 0.6, (steps, n, 1))], axis=2)
+    return np.concatenate([rng.uniform(-1, 1, (steps, n, 3)), rng.uniform(-0.5, 0.5, (steps, n, 1))], axis=2)
+
+
+def main():
+    import torch
+    from mrs_multirotor_simulator_amd import tensors as T
+    sizes = [int(s) for s in sys.argv[1].split(",")] if len(sys.argv) > 1 else [100_000, 1_000_000]
+    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 64
+    reps = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+    modes = sys.argv[4].split(",") if len(sys.argv) > 4 else ["ACTUATOR_CMD", "ATTITUDE_RATE_CMD", "VELOCITY_HDG_CMD"]
+    forms = sys.argv[5].split(",") if len(sys.argv) > 5 else ["loop", "rollout"]
+    arith = sys.argv[6] if len(sys.argv) > 6 else "literal"
+    groups = T.OBS_POS | T.OBS_VEL | T.OBS_QUAT
+    rng = np.random.default_rng(5)
+    print(f"rollout of T = {steps} steps, FP32 commands and POS|VEL|QUAT rows, x500, {arith.upper()}; {reps} rounds after a warm-up, alternating")
+    for n in sizes:
+        st, _ = bench.make_inputs(n, "position+collisions", seed=3)
+        p = M.model_params("x500", ground_enabled=True, ground_z=0.0)
+        for mode_name in modes:
+            mode = getattr(M, mode_name)
+
+            def make():
+                g = M.Swarm(n, arith=M.ARITH_FAST if arith == "fast" else M.ARITH_LITERAL)
+                g.construct(0, n, p)
+                g.set_state(0, n, st["x"], st["v"], st["R"], st["omega"], st["motor_rpm"])
+                return g
+
+            swarms = {f: make() for f in forms}
+            dev = torch.device("cuda", swarms[forms[0]].device())
+            cmd = torch.tensor(commands(mode, n, steps, rng), dtype=torch.float32, device=dev)
+            obs = {f: torch.empty((steps, n, T.gather_width(groups)), dtype=torch.float32, device=dev) for f in forms}
+
+            def run(form):
+                g = swarms[form]
+                if form == "rollout":
+                    T.rollout(g, mode, cmd, DT, groups, out=obs[form])
+                    return
+                for t in range(steps):
+                    T.set_input(g, mode, cmd[t])
+                    g.step_n(DT, 1)
+                    T.gather(g, groups, out=obs[form][t])
+
+            for f in forms:  # warm-up: code objects, the type table, torch kernels
+                run(f)
+            torch.cuda.synchronize(dev)
+            times = {f: [] for f in forms}
+            for _ in range(reps):
+                for f in forms:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    run(f)
+                    e1.record()
+                    e1.synchronize()
+                    times[f].append(e0.elapsed_time(e1) * 1e3 / steps)
+            med = {f: float(np.median(times[f])) for f in forms}
+            line = f"  {n:>8d} UAVs  {mode_name:18s}"
+            for f in forms:
+                line += f"  {f} {med[f]:7.2f} us/step ({min(times[f]):.2f}-{max(times[f]):.2f})"
+            if len(forms) == 2:
+                line += f"  loop / rollout {med['loop'] / med['rollout']:.2f}x"
+                if arith == "fast":
+                    a, b = obs["loop"].double(), obs["rollout"].double()
+                    line += f"  max rel diff {float(((a - b).abs() / a.abs().clamp_min(1.0)).max()):.1e}"
+                    print(line, flush=True)
+                    for g in swarms.values():
+                        g.close()
+                    continue
+                assert torch.equal(obs["loop"].view(torch.int32), obs["rollout"].view(torch.int32)), f"{n} {mode_name}: rows differ"
+                a, b = swarms["loop"].get_states(), swarms["rollout"].get_states()
+                for fld in a.dtype.names:
+                    assert np.array_equal(a[fld].view(np.uint64) if a[fld].dtype == np.float64 else a[fld],
+                                          b[fld].view(np.uint64) if b[fld].dtype == np.float64 else b[fld]), f"{n} {mode_name}: {fld} differs"
+                line += "  bit-identical"
+            print(line, flush=True)
+            for g in swarms.values():
+                g.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -785,6 +785,13 @@ public:
                      void* dev_obs, int obs_stride, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_rollout_device(s_, first, count, mode, dt, n_steps, dev_cmd, dtype, cmd_stride, groups, dev_obs, obs_stride, stream));
   }
+  // the same at a control rate: command row block j is held for cmd_every steps (setInput latches), and a row block of dev_obs is written
+  // every obs_every steps; dev_cmd holds n_steps / cmd_every row blocks, dev_obs n_steps / obs_every (both rates divide n_steps)
+  void rolloutRateDevice(int first, int count, int mode, double dt, int n_steps, int cmd_every, int obs_every, const void* dev_cmd, int dtype,
+                         int cmd_stride, uint32_t groups, void* dev_obs, int obs_stride, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_rollout_rate_device(s_, first, count, mode, dt, n_steps, cmd_every, obs_every, dev_cmd, dtype, cmd_stride, groups,
+                                                     dev_obs, obs_stride, stream));
+  }
   // the whole simulation state of UAVs [first, first + count) into dev_records[0 .. count-1] (device memory, 16-B aligned)
   void saveDevice(int first, int count, mrs_uav_snapshot_t* dev_records, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_save_device(s_, first, count, dev_records, stream));

@@ -594,6 +594,30 @@ int mrs_swarm_load_device(mrs_swarm_t* s, int32_t first, int32_t count, const mr
 int mrs_swarm_rollout_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, const void* dev_cmd,
                              int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream);
 
+/* ---- control-rate rollouts: a command row block held for cmd_every steps, an observation row block every obs_every steps ----
+ * The simulator steps at 1 kHz, what commands it at 50-100 Hz: UavSystem::setInput latches (uav_system.hpp:175-248), so a command stays
+ * in force over the makeStep calls (:304-380) until the next setInput, and getState (:386) is asked for at the caller's own rate.
+ * Equals, bit for bit in LITERAL arithmetic, the loop
+ *   for t in [0, n_steps):
+ *     if (t % cmd_every == 0)
+ *       mrs_swarm_set_input_device(s, first, count, mode, row block t / cmd_every of dev_cmd, dtype, cmd_stride, ext_stream);
+ *     mrs_swarm_step_n(s, dt, 1, 1);
+ *     if (groups && (t + 1) % obs_every == 0)
+ *       mrs_swarm_gather_device(s, first, count, groups, row block (t + 1) / obs_every - 1 of dev_obs, dtype, obs_stride, ext_stream);
+ * dev_cmd holds n_steps / cmd_every row blocks and dev_obs n_steps / obs_every row blocks of `count` rows each: row (j, k) starts at
+ * element ((size_t)j * count + k) * stride, as in mrs_swarm_rollout_device.  The two rates are independent of each other; each must be
+ * >= 1 and divide n_steps (MRS_ERR_ARG).  obs_every == n_steps is the terminal-cost case: one row block per call.  Inside a command
+ * block nothing is read from dev_cmd, and nothing is written to dev_obs except at the end of an observation block.
+ * Everything else is the contract of mrs_swarm_rollout_device, which is this call with cmd_every = obs_every = 1: every UAV of the swarm
+ * is stepped; a UAV on hold is not stepped, its command columns are written and its rows hold its unchanged state; afterwards the
+ * command columns of the range hold the LAST row block and its mode is `mode`; the call enters like a state call; collisions are not
+ * evaluated inside; ONE stream fence per call; every argument is checked before anything is launched and a refused call changes
+ * nothing; refused on a sharded swarm.  The pointer checks use the decimated sizes: a dev_obs of exactly n_steps / obs_every row blocks
+ * is accepted, one row short is refused. */
+int mrs_swarm_rollout_rate_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every,
+                                  int32_t obs_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs,
+                                  int32_t obs_stride, void* ext_stream);
+
 #ifdef __cplusplus
 }
 #endif

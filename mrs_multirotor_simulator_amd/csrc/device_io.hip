@@ -303,15 +303,18 @@ int mrs_swarm_reset_device(mrs_swarm_t* s, int32_t first, int32_t count, const u
   return fence_out(s, ext);
 }
 
-int mrs_swarm_rollout_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, const void* dev_cmd,
-                             int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream) {
-  MRS_LOCK(s);  // (MRS_ENTER after the argument checks: a refused call launches nothing)
+// both rollout entry points, under the caller's lock (MRS_ENTER's settle after the argument checks: a refused call launches nothing)
+static int rollout_locked(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every, int32_t obs_every,
+                          const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream,
+                          const char* who) {
   int rc = check_range(s, first, count);
   if (rc) return rc;
-  if (s->comm_world > 0) return fail(MRS_ERR_ARG, "mrs_swarm_rollout_device: not on a sharded swarm");
+  if (s->comm_world > 0) return fail(MRS_ERR_ARG, std::string(who) + ": not on a sharded swarm");
   if (mode < MRS_INPUT_UNKNOWN || mode > MRS_POSITION_CMD) return fail(MRS_ERR_ARG, "bad input mode");
   if ((rc = check_dtype(dtype))) return rc;
   if (n_steps < 1) return fail(MRS_ERR_ARG, "n_steps must be at least 1");
+  if (cmd_every < 1 || n_steps % cmd_every != 0) return fail(MRS_ERR_ARG, "cmd_every must be at least 1 and divide n_steps");
+  if (obs_every < 1 || n_steps % obs_every != 0) return fail(MRS_ERR_ARG, "obs_every must be at least 1 and divide n_steps");
   if (!(dt > 0) || !std::isfinite(dt)) return fail(MRS_ERR_ARG, "dt must be finite and > 0");
   const int width = command_width(mode, cmd_stride);
   if (width > 0 && (cmd_stride < width || width < 1)) return fail(MRS_ERR_ARG, "cmd_stride too small for this mode");
@@ -319,10 +322,11 @@ int mrs_swarm_rollout_device(mrs_swarm_t* s, int32_t first, int32_t count, int32
   if ((rc = mrs_swarm_gather_width(groups, &obs_width))) return rc;
   if (groups != 0u && obs_stride < obs_width) return fail(MRS_ERR_ARG, "obs_stride smaller than the width of the selected groups");
   if (count > 0) {
-    // rows of all n_steps row blocks; 64-bit: n_steps x count x stride can pass 2^31 elements
-    const size_t rows = (size_t)n_steps * (size_t)count;
-    if (width > 0 && (rc = check_device_ptr(s, dev_cmd, ((rows - 1) * (size_t)cmd_stride + (size_t)width) * dtype_bytes(dtype), "dev_cmd"))) return rc;
-    if (groups != 0u && (rc = check_device_ptr(s, dev_obs, ((rows - 1) * (size_t)obs_stride + (size_t)obs_width) * dtype_bytes(dtype), "dev_obs")))
+    // rows of the n_steps / cmd_every and n_steps / obs_every row blocks; 64-bit: blocks x count x stride can pass 2^31 elements
+    const size_t cmd_rows = (size_t)(n_steps / cmd_every) * (size_t)count, obs_rows = (size_t)(n_steps / obs_every) * (size_t)count;
+    if (width > 0 && (rc = check_device_ptr(s, dev_cmd, ((cmd_rows - 1) * (size_t)cmd_stride + (size_t)width) * dtype_bytes(dtype), "dev_cmd")))
+      return rc;
+    if (groups != 0u && (rc = check_device_ptr(s, dev_obs, ((obs_rows - 1) * (size_t)obs_stride + (size_t)obs_width) * dtype_bytes(dtype), "dev_obs")))
       return rc;
     if (mode == MRS_ACTUATOR_CMD && !actuator_width_ok(s, first, count, width)) return fail(MRS_ERR_ARG, "actuator payload narrower than n_motors");
   }
@@ -342,14 +346,43 @@ int mrs_swarm_rollout_device(mrs_swarm_t* s, int32_t first, int32_t count, int32
   if ((rc = fence_in(s, ext))) return rc;
   s->collide_since_step = false;
   s->p_valid            = false;  // (plain steps do not refresh the position records)
-  const RolloutDev r{dev_cmd, groups != 0u ? dev_obs : nullptr, first, count, cmd_stride, width, obs_stride, 0, (uint32_t)mode << FLAG_MODE_SHIFT,
-                     groups, dtype == MRS_DTYPE_F32 ? 1 : 0};
   const int variant = s->n_cascade > 0 ? 0 : 1;  // 0 all input modes | 1 model only
+  if (cmd_every == 1 && obs_every == 1) {  // a row before and after every step: the kernels of rollout_device.inc
+    const RolloutDev r{dev_cmd, groups != 0u ? dev_obs : nullptr, first, count, cmd_stride, width, obs_stride, 0, (uint32_t)mode << FLAG_MODE_SHIFT,
+                       groups, dtype == MRS_DTYPE_F32 ? 1 : 0};
+    if (s->arith == MRS_ARITH_FAST)
+      HIPCHK(mrs_launch_rollout_fast(s->view(), r, dt, n_steps, variant, s->stream));
+    else
+      HIPCHK(mrs_launch_rollout_literal(s->view(), r, dt, n_steps, variant, s->stream));
+    return fence_out(s, ext);
+  }
+  RolloutRateDev r{};  // (row block 0 and the call's width, dtype and groups: the launcher sets each launch's schedule and first blocks)
+  r.cmd = dev_cmd, r.obs = groups != 0u ? dev_obs : nullptr;
+  r.first = first, r.count = count;
+  r.cmd_stride = cmd_stride, r.obs_stride = obs_stride;
+  r.cmd_sched = ((uint32_t)width | (dtype == MRS_DTYPE_F32 ? 32u : 0u)) << 24;
+  r.obs_sched = groups << 24;
+  r.mode_bits = (uint32_t)mode << FLAG_MODE_SHIFT;
   if (s->arith == MRS_ARITH_FAST)
-    HIPCHK(mrs_launch_rollout_fast(s->view(), r, dt, n_steps, variant, s->stream));
+    HIPCHK(mrs_launch_rollout_rate_fast(s->view(), r, dt, n_steps, cmd_every, obs_every, variant, s->stream));
   else
-    HIPCHK(mrs_launch_rollout_literal(s->view(), r, dt, n_steps, variant, s->stream));
+    HIPCHK(mrs_launch_rollout_rate_literal(s->view(), r, dt, n_steps, cmd_every, obs_every, variant, s->stream));
   return fence_out(s, ext);
+}
+
+int mrs_swarm_rollout_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, const void* dev_cmd,
+                             int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream) {
+  MRS_LOCK(s);
+  return rollout_locked(s, first, count, mode, dt, n_steps, 1, 1, dev_cmd, dtype, cmd_stride, groups, dev_obs, obs_stride, ext_stream,
+                        "mrs_swarm_rollout_device");
+}
+
+int mrs_swarm_rollout_rate_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every,
+                                  int32_t obs_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs,
+                                  int32_t obs_stride, void* ext_stream) {
+  MRS_LOCK(s);
+  return rollout_locked(s, first, count, mode, dt, n_steps, cmd_every, obs_every, dev_cmd, dtype, cmd_stride, groups, dev_obs, obs_stride, ext_stream,
+                        "mrs_swarm_rollout_rate_device");
 }
 
 }  // extern "C"

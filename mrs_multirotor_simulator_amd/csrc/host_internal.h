@@ -41,6 +41,10 @@ extern "C" hipError_t mrs_launch_step_literal(SwarmDev sw, double dt, int subste
 extern "C" hipError_t mrs_launch_step_fast(SwarmDev sw, double dt, int substeps, int cascade, int blk0, int nblk, int with_mixed, hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_literal(SwarmDev sw, RolloutDev r, double dt, int n_steps, int variant, hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_fast(SwarmDev sw, RolloutDev r, double dt, int n_steps, int variant, hipStream_t st);
+extern "C" hipError_t mrs_launch_rollout_rate_literal(SwarmDev sw, RolloutRateDev r, double dt, int n_steps, int cmd_every, int obs_every, int variant,
+                                                        hipStream_t st);
+extern "C" hipError_t mrs_launch_rollout_rate_fast(SwarmDev sw, RolloutRateDev r, double dt, int n_steps, int cmd_every, int obs_every, int variant,
+                                                     hipStream_t st);
 extern "C" hipError_t mrs_launch_pid_probe_literal(const double*, const double*, const double*, const double*, const double*, double*, int, int, hipStream_t);
 extern "C" hipError_t mrs_launch_pid_probe_fast(const double*, const double*, const double*, const double*, const double*, double*, int, int, hipStream_t);
 extern "C" hipError_t mrs_launch_pid_update_probe_literal(const double*, double*, const double*, const double*, double*, int, hipStream_t);

@@ -2,3 +2,4 @@
 #define MRS_FAST 0
 #include "step_device.inc"
 #include "rollout_device.inc"
+#include "rollout_rate_device.inc"

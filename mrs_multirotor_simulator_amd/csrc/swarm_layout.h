@@ -100,6 +100,34 @@ struct RolloutDev {
   int32_t     f32;         // rows are FP32 (else FP64)
 };
 
+// ---- one launch of a control-rate rollout (mrs_swarm_rollout_rate_device, rollout_rate_device.inc) ----
+// Command row block j is held for cmd_every steps and observation row block j is written after step (j + 1) * obs_every - 1
+// (mrs_swarm_rollout_rate_device).  A launch takes at most 64 sub-steps, so whatever the two rates are, the sub-steps of ONE launch that
+// read a command row (or write an observation row) are s0, s0 + p, s0 + 2p, ... with s0 < 64 and p <= 64 (a rate of 64 or more: at
+// most one such sub-step, p = 64).  The host hands each launch that schedule and the row pointers of its first due blocks, so the
+// kernel neither divides nor knows the rollout step.  The step kernels are short of scalar registers — every word that lives through
+// the sub-step loop is paid for in spills — so a schedule shares ONE word with the small fields its hook needs anyway.
+#define MRS_RO_S0(w) ((w) & 63u)                      // first due sub-step of the launch
+#define MRS_RO_P(w) ((((w) >> 6) & 63u) + 1u)          // distance of two due sub-steps, 1..64
+#define MRS_RO_M(w) ((((w) >> 12) & 4095u) + 1u)       // (x * M) >> 12 == x / P for every x < 64 (mrs_ro_sched)
+#define MRS_RO_HI(w) ((w) >> 24)                       // cmd_sched: width | f32 << 5; obs_sched: the MRS_OBS_* groups
+struct RolloutRateDev {
+  const void* cmd;         // command rows of the launch's FIRST due block; row (j, k) at element ((j * count) + k) * cmd_stride behind it:
+                           // the setInput payload of UAV first + k from the launch's j-th due sub-step on
+  void*       obs;         // likewise: the `groups` of UAV first + k after the launch's j-th due sub-step
+  int32_t     first, count;
+  int32_t     cmd_stride, obs_stride;
+  uint32_t    cmd_sched;   // MRS_RO_S0 / P / M | payload width << 24 | rows are FP32 << 29.  Width 0: no command row in this launch
+  uint32_t    obs_sched;   // MRS_RO_S0 / P / M | groups << 24.  Groups 0: no observation row in this launch
+  uint32_t    mode_bits;   // input mode << FLAG_MODE_SHIFT
+};
+// the schedule bits of a launch whose first due sub-step is s0 (< 64), for a rate of `every` steps
+inline uint32_t mrs_ro_sched(int s0, int every) {
+  const uint32_t p = every < 64 ? (uint32_t)every : 64u;
+  const uint32_t m = p == 1u ? 4096u : 4096u / p + 1u;  // x / p == (x * m) >> 12 for x < 64: the error x * (m - 4096 / p) / 4096 < 64 / 4096 <= 1 / p
+  return (uint32_t)s0 | (p - 1u) << 6 | (m - 1u) << 12;
+}
+
 // 48-byte record exchanged for the collision pass (single- and multi-GPU): everything
 // MultirotorSimulator::handleCollisions reads of the partner UAV (src/multirotor_simulator.cpp:339-350)
 struct PosRecord {

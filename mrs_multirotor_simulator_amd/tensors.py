@@ -128,17 +128,27 @@ def _check_steps(t, name, steps, rows, min_width, dtype, device_index):
     return stride
 
 
-def rollout(swarm, mode, commands, dt, groups=OBS_POS | OBS_VEL | OBS_QUAT, first=0, out=None):
-    """T steps of the whole swarm in which UAVs [first, first + count) take command row block t before step t and report the OBS_* groups
-    of `groups` after it (mrs_swarm_rollout_device): `for t: set_input(swarm, mode, commands[t], first); swarm.step_n(dt, 1);
-    gather(swarm, groups, first, count, out=out[t])`, bit for bit in LITERAL, in one call.  commands: [T, count, >= width] FP32 / FP64
-    (the payload layouts of set_input; ACTUATOR rows are dense).  out: [T, count, >= gather_width(groups)] of the same dtype, allocated
-    when None; returned (None when groups == 0).  UAVs outside the range are stepped with their own commands."""
+def rollout(swarm, mode, commands, dt, groups=OBS_POS | OBS_VEL | OBS_QUAT, first=0, out=None, hold=1, obs_every=None):
+    """B * hold steps of the whole swarm in which UAVs [first, first + count) take command row block j before step j * hold, keep it for
+    `hold` steps (setInput latches), and report the OBS_* groups of `groups` after every `obs_every` steps (default: `hold`, a row block
+    per command; B * hold: the final state only).  With hold == 1 (mrs_swarm_rollout_device): `for t: set_input(swarm, mode,
+    commands[t], first); swarm.step_n(dt, 1); gather(swarm, groups, first, count, out=out[t])`, bit for bit in LITERAL, in one call;
+    with obs_every == hold (mrs_swarm_rollout_rate_device): `for j: set_input(commands[j]); swarm.step_n(dt, hold); gather(out=out[j])`.
+    commands: [B, count, >= width] FP32 / FP64 (the payload layouts of set_input; ACTUATOR rows are dense).  obs_every must be >= 1 and
+    divide B * hold.  out: [B * hold // obs_every, count, >= gather_width(groups)] of the same dtype, allocated when None; returned
+    (None when groups == 0).  UAVs outside the range are stepped with their own commands."""
     dev = swarm.device()
     if not isinstance(commands, torch.Tensor) or commands.dim() != 3:
         raise ValueError("commands must be a [T, count, width] tensor")
+    hold = int(hold)
+    if hold < 1:
+        raise ValueError(f"hold must be at least 1, got {hold}")
     code = _dtype_code(commands.dtype)
-    steps, count = commands.shape[0], commands.shape[1]
+    blocks, count = commands.shape[0], commands.shape[1]
+    steps = blocks * hold
+    every = hold if obs_every is None else int(obs_every)
+    if every < 1 or steps % every != 0:
+        raise ValueError(f"obs_every must be at least 1 and divide the {steps} steps of the call, got {every}")
     width = command_width(mode, commands.shape[2])
     cstride = _check_steps(commands, "commands", None, count, width, commands.dtype, dev)
     if mode == ACTUATOR_CMD and count > 1 and cstride != commands.shape[2]:
@@ -147,13 +157,16 @@ def rollout(swarm, mode, commands, dt, groups=OBS_POS | OBS_VEL | OBS_QUAT, firs
     optr, ostride = 0, owidth
     if groups:
         if out is None:
-            out = torch.empty((steps, count, owidth), dtype=commands.dtype, device=torch.device("cuda", dev))
+            out = torch.empty((steps // every, count, owidth), dtype=commands.dtype, device=torch.device("cuda", dev))
         if isinstance(out, torch.Tensor) and out.dtype != commands.dtype:
             raise ValueError(f"out has dtype {out.dtype}, the commands {commands.dtype}: one dtype serves both")
-        ostride = _check_steps(out, "out", steps, count, owidth, commands.dtype, dev)
+        ostride = _check_steps(out, "out", steps // every, count, owidth, commands.dtype, dev)
         optr = out.data_ptr()
     cptr = commands.data_ptr() if width > 0 and count > 0 else 0
-    swarm.rollout_device(first, count, mode, dt, steps, cptr, code, cstride, groups, optr, ostride, _stream(dev))
+    if hold == 1 and every == 1:
+        swarm.rollout_device(first, count, mode, dt, steps, cptr, code, cstride, groups, optr, ostride, _stream(dev))
+    else:
+        swarm.rollout_rate_device(first, count, mode, dt, steps, hold, every, cptr, code, cstride, groups, optr, ostride, _stream(dev))
     if not groups:
         return None
     return out[:, :, :owidth] if out.shape[2] > owidth else out

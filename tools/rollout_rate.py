@@ -8,9 +8,18 @@ us per step (median, min-max).  In LITERAL (the default) both forms must end bit
 the rollout runs the fused kernels and the loop the single-step ones, which differ in the last bits: the tool prints the largest
 relative difference of the rows instead.
 
-    python tools/rollout_rate.py [sizes=100000,1000000] [T=64] [reps=5] [modes=ACTUATOR_CMD,ATTITUDE_RATE_CMD,VELOCITY_HDG_CMD] [forms=loop,rollout] [arith=literal]
+    python tools/rollout_rate.py [sizes=100000,1000000] [T=64] [reps=5] [modes=ACTUATOR_CMD,ATTITUDE_RATE_CMD,VELOCITY_HDG_CMD] [forms=loop,rollout] [arith=literal] [hold] [obs_every=hold]
 
 (`forms=rollout` runs the rollout alone, e.g. under rocprofv3 --kernel-trace --stats; the bit-identity check then has no partner.)
+
+With a `hold` (and an `obs_every`) the tool measures a CONTROL-RATE rollout instead: each command row is held for `hold` steps and a row
+block is due every `obs_every` steps (mrs_swarm_rollout_rate_device).  The same T steps three ways, alternating as above:
+  plain    tensors.rollout(cmd.repeat_interleave(hold, 0), dt, out=all T row blocks)         (what a caller did before the rates existed)
+  rate     tensors.rollout(cmd, dt, out=T / obs_every row blocks, hold=hold, obs_every=obs_every)
+  loop     set_input(cmd[j]) every `hold` steps; step_n(dt, to the next event); gather every `obs_every` steps
+and prints the bytes of rows one call of `plain` and of `rate` carries.  In both flavours rows plain[obs_every-1::obs_every] == rate and the
+final states must be bit-identical; in LITERAL the loop must equal them too (in FAST its largest relative difference is printed).
+`forms` then selects among plain,rate,loop (default: all three; `loop,rollout`, the default above, also means all three).
 """
 import os
 import sys
@@ -42,6 +51,10 @@ def main():
     modes = sys.argv[4].split(",") if len(sys.argv) > 4 else ["ACTUATOR_CMD", "ATTITUDE_RATE_CMD", "VELOCITY_HDG_CMD"]
     forms = sys.argv[5].split(",") if len(sys.argv) > 5 else ["loop", "rollout"]
     arith = sys.argv[6] if len(sys.argv) > 6 else "literal"
+    if len(sys.argv) > 7:
+        hold = int(sys.argv[7])
+        every = int(sys.argv[8]) if len(sys.argv) > 8 else hold
+        return main_rate(sizes, steps, reps, modes, ["plain", "rate", "loop"] if forms == ["loop", "rollout"] else forms, arith, hold, every)
     groups = T.OBS_POS | T.OBS_VEL | T.OBS_QUAT
     rng = np.random.default_rng(5)
     print(f"rollout of T = {steps} steps, FP32 commands and POS|VEL|QUAT rows, x500, {arith.upper()}; {reps} rounds after a warm-up, alternating")
@@ -103,6 +116,98 @@ def main():
                     assert np.array_equal(a[fld].view(np.uint64) if a[fld].dtype == np.float64 else a[fld],
                                           b[fld].view(np.uint64) if b[fld].dtype == np.float64 else b[fld]), f"{n} {mode_name}: {fld} differs"
                 line += "  bit-identical"
+            print(line, flush=True)
+            for g in swarms.values():
+                g.close()
+
+
+def bits_equal(a, b):
+    import torch
+    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+def main_rate(sizes, steps, reps, modes, forms, arith, hold, every):
+    import torch
+    from mrs_multirotor_simulator_amd import tensors as T
+    assert hold >= 1 and every >= 1 and steps % hold == 0 and steps % every == 0, "hold and obs_every must divide T"
+    assert set(forms) <= {"plain", "rate", "loop"}, forms
+    groups = T.OBS_POS | T.OBS_VEL | T.OBS_QUAT
+    ow = T.gather_width(groups)
+    rng = np.random.default_rng(5)
+    print(f"control-rate rollout of T = {steps} steps, hold {hold}, obs_every {every}, FP32 commands and POS|VEL|QUAT rows, x500, {arith.upper()}; "
+          f"{reps} rounds after a warm-up, alternating")
+    for n in sizes:
+        st, _ = bench.make_inputs(n, "position+collisions", seed=3)
+        p = M.model_params("x500", ground_enabled=True, ground_z=0.0)
+        for mode_name in modes:
+            mode = getattr(M, mode_name)
+            swarms = {}
+            for f in forms:
+                g = M.Swarm(n, arith=M.ARITH_FAST if arith == "fast" else M.ARITH_LITERAL)
+                g.construct(0, n, p)
+                g.set_state(0, n, st["x"], st["v"], st["R"], st["omega"], st["motor_rpm"])
+                swarms[f] = g
+            dev = torch.device("cuda", swarms[forms[0]].device())
+            cmd = torch.tensor(commands(mode, n, steps // hold, rng), dtype=torch.float32, device=dev)
+            rep = cmd.repeat_interleave(hold, 0) if "plain" in forms else None  # (made once: the caller's copy is not what is timed)
+            obs = {f: torch.empty((steps if f == "plain" else steps // every, n, ow), dtype=torch.float32, device=dev) for f in forms}
+
+            def run(form):
+                g = swarms[form]
+                if form == "plain":
+                    T.rollout(g, mode, rep, DT, groups, out=obs[form])
+                elif form == "rate":
+                    T.rollout(g, mode, cmd, DT, groups, out=obs[form], hold=hold, obs_every=every)
+                else:
+                    t = 0
+                    while t < steps:
+                        if t % hold == 0:
+                            T.set_input(g, mode, cmd[t // hold])
+                        nxt = min((t // hold + 1) * hold, (t // every + 1) * every)
+                        g.step_n(DT, nxt - t)
+                        t = nxt
+                        if t % every == 0:
+                            T.gather(g, groups, out=obs[form][t // every - 1])
+
+            for f in forms:  # warm-up: code objects, the type table, torch kernels
+                run(f)
+            torch.cuda.synchronize(dev)
+            times = {f: [] for f in forms}
+            for _ in range(reps):
+                for f in forms:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    run(f)
+                    e1.record()
+                    e1.synchronize()
+                    times[f].append(e0.elapsed_time(e1) * 1e3 / steps)
+            line = f"  {n:>8d} UAVs  {mode_name:18s}"
+            for f in forms:
+                line += f"  {f} {float(np.median(times[f])):7.2f} us/step ({min(times[f]):.2f}-{max(times[f]):.2f})"
+            width = cmd.shape[2]
+            if "plain" in forms:
+                line += f"  rows plain {(steps * n * (width + ow) * 4) / 1e6:.1f} MB"
+            if "rate" in forms:
+                line += f"  rows rate {((steps // hold) * n * width + (steps // every) * n * ow) * 4 / 1e6:.1f} MB"
+
+            def same_state(fa, fb):
+                a, b = swarms[fa].get_states(), swarms[fb].get_states()
+                for fld in a.dtype.names:
+                    assert np.array_equal(a[fld].view(np.uint64) if a[fld].dtype == np.float64 else a[fld],
+                                          b[fld].view(np.uint64) if b[fld].dtype == np.float64 else b[fld]), f"{n} {mode_name}: {fld} differs ({fa} / {fb})"
+
+            if "plain" in forms and "rate" in forms:
+                assert bits_equal(obs["plain"][every - 1::every], obs["rate"]), f"{n} {mode_name}: rows of plain[{every - 1}::{every}] and rate differ"
+                same_state("plain", "rate")
+                line += "  plain == rate"
+            if "loop" in forms and "rate" in forms:
+                if arith == "fast":
+                    a, b = obs["loop"].double(), obs["rate"].double()
+                    line += f"  loop vs rate max rel diff {float(((a - b).abs() / a.abs().clamp_min(1.0)).max()):.1e}"
+                else:
+                    assert bits_equal(obs["loop"], obs["rate"]), f"{n} {mode_name}: rows of loop and rate differ"
+                    same_state("loop", "rate")
+                    line += "  loop == rate"
             print(line, flush=True)
             for g in swarms.values():
                 g.close()

@@ -792,6 +792,18 @@ public:
     mrs_throw_on_error(mrs_swarm_rollout_rate_device(s_, first, count, mode, dt, n_steps, cmd_every, obs_every, dev_cmd, dtype, cmd_stride, groups,
                                                      dev_obs, obs_stride, stream));
   }
+  // applyForce (:293-298) of UAVs [first, first + count) from device rows: component c of row k at element k * stride + c, world frame, N
+  void applyForceDevice(int first, int count, const void* dev_force, int dtype, int stride, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_apply_force_device(s_, first, count, dev_force, dtype, stride, stream));
+  }
+  // rolloutRateDevice under a force schedule: force row block j of dev_force (n_steps / force_every row blocks of the same dtype) is
+  // applied before step j * force_every and stays latched for force_every steps; afterwards the range carries the last block
+  void rolloutForceDevice(int first, int count, int mode, double dt, int n_steps, int cmd_every, int obs_every, int force_every, const void* dev_cmd,
+                          int dtype, int cmd_stride, const void* dev_force, int force_stride, uint32_t groups, void* dev_obs, int obs_stride,
+                          void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_rollout_force_device(s_, first, count, mode, dt, n_steps, cmd_every, obs_every, force_every, dev_cmd, dtype, cmd_stride,
+                                                      dev_force, force_stride, groups, dev_obs, obs_stride, stream));
+  }
   // the whole simulation state of UAVs [first, first + count) into dev_records[0 .. count-1] (device memory, 16-B aligned)
   void saveDevice(int first, int count, mrs_uav_snapshot_t* dev_records, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_save_device(s_, first, count, dev_records, stream));

@@ -618,6 +618,39 @@ int mrs_swarm_rollout_rate_device(mrs_swarm_t* s, int32_t first, int32_t count, 
                                   int32_t obs_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs,
                                   int32_t obs_stride, void* ext_stream);
 
+/* ---- device-resident external forces: applyForce from device rows, and a force row block every force_every steps of a rollout ----
+ * UavSystem::applyForce (uav_system.hpp:293-298) latches external_force_ (multirotor_model.hpp:292-295), which enters v_dot at :346: the
+ * simulator's one disturbance channel (gusts, pushes).  mrs_swarm_apply_force_device is mrs_swarm_apply_force with device rows: row k,
+ * the force on UAV first + k in world frame and newtons, has component c at element k * stride + c of dev_force (FP64, or FP32 widened
+ * exactly).  The force stays latched until the next applyForce or the next evaluated collision tick (with handleCollisions enabled that
+ * tick sets every UAV's force, src/multirotor_simulator.cpp:357).  The call enters like the host call (a pending collision tick is
+ * evaluated first: it writes the same columns) and is fenced like the other device-resident calls.  Checked before anything is
+ * launched: the range (MRS_ERR_RANGE), and MRS_ERR_ARG for the dtype, stride < 3, a NULL pointer, a pointer that is not device memory of
+ * the swarm's device or too small for its rows, and a sharded swarm.  count == 0 is MRS_OK. */
+int mrs_swarm_apply_force_device(mrs_swarm_t* s, int32_t first, int32_t count, const void* dev_force, int32_t dtype, int32_t stride, void* ext_stream);
+/* mrs_swarm_rollout_rate_device under a force schedule.  Equals, bit for bit in LITERAL arithmetic, the loop
+ *   for t in [0, n_steps):
+ *     if (t % cmd_every == 0)
+ *       mrs_swarm_set_input_device(s, first, count, mode, row block t / cmd_every of dev_cmd, dtype, cmd_stride, ext_stream);
+ *     if (t % force_every == 0)
+ *       mrs_swarm_apply_force_device(s, first, count, row block t / force_every of dev_force, dtype, force_stride, ext_stream);
+ *     mrs_swarm_step_n(s, dt, 1, 1);
+ *     if (groups && (t + 1) % obs_every == 0)
+ *       mrs_swarm_gather_device(s, first, count, groups, row block (t + 1) / obs_every - 1 of dev_obs, dtype, obs_stride, ext_stream);
+ * dev_force holds n_steps / force_every row blocks of `count` rows; row (j, k) starts at element ((size_t)j * count + k) * force_stride.
+ * One dtype serves commands, forces and observations.  force_every must be >= 1 and divide n_steps (force_every == n_steps: one force for
+ * the whole call); the three rates are independent, and inside a force block nothing is read from dev_force.  UAVs outside the range keep
+ * their own commands, modes and forces.  A UAV on hold is not stepped; its command and force columns are written with the last row
+ * blocks that start in the call.  Crashed UAVs take their force rows and the force acts on them as in the reference.  Afterwards the
+ * force columns of the range hold the LAST force block (mrs_swarm_get_external_force returns it).  A pending collision tick is evaluated
+ * first; force block 0 then replaces that tick's force for the range, as the loop's first mrs_swarm_apply_force_device would.
+ * Everything else is the contract of mrs_swarm_rollout_rate_device, and so are the refusals, plus, as MRS_ERR_ARG: force_every < 1 or not
+ * dividing n_steps, force_stride < 3, and a dev_force that is NULL, not device memory or one row short of its n_steps / force_every
+ * blocks (exactly that many are accepted). */
+int mrs_swarm_rollout_force_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every,
+                                   int32_t obs_every, int32_t force_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride,
+                                   const void* dev_force, int32_t force_stride, uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,20 @@ __global__ void __launch_bounds__(256) k_scatter_cmd(SwarmDev sw, const T* rows,
   sw.F[i] = (sw.F[i] & ~FLAG_MODE_MASK) | mode_bits;
 }
 
+// applyForce rows (FP64 or FP32, device-resident, world frame, N) into the external-force columns: what mrs_swarm_apply_force's three
+// column uploads do, in one launch
+template <typename T>
+__global__ void __launch_bounds__(256) k_scatter_force(SwarmDev sw, const T* rows, int stride, int first, int count) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  const int    i  = first + k;
+  const size_t np = (size_t)sw.npad;
+  const T*     r  = rows + (size_t)k * (size_t)stride;
+  const double f[3] = {(double)r[0], (double)r[1], (double)r[2]};
+#pragma unroll
+  for (int c = 0; c < 3; c++) sw.S[(size_t)(F_FEXT + c) * np + i] = f[c];
+}
+
 // mrs_swarm_construct(params of the UAV's own type, pos, heading) for the UAVs whose mask byte is set, without the host: state,
 // IMU, external force and PID columns zero, R = AngleAxis(-heading, z), x = pos, _initial_pos_ z = pos z; crashed and v_prev-split
 // cleared, takeoff patch as given.  Commands, feed-forwards, the mode / feed-forward / type bits and the hold flag are kept.
@@ -303,10 +317,33 @@ int mrs_swarm_reset_device(mrs_swarm_t* s, int32_t first, int32_t count, const u
   return fence_out(s, ext);
 }
 
-// both rollout entry points, under the caller's lock (MRS_ENTER's settle after the argument checks: a refused call launches nothing)
+int mrs_swarm_apply_force_device(mrs_swarm_t* s, int32_t first, int32_t count, const void* dev_force, int32_t dtype, int32_t stride, void* ext_stream) {
+  MRS_ENTER(s);  // (a pending collision tick writes the same columns: it is evaluated first)
+  int rc = check_range(s, first, count);
+  if (rc) return rc;
+  if (s->comm_world > 0) return fail(MRS_ERR_ARG, "mrs_swarm_apply_force_device: not on a sharded swarm");
+  if ((rc = check_dtype(dtype))) return rc;
+  if (stride < 3) return fail(MRS_ERR_ARG, "stride smaller than the three force components");
+  if (count == 0) return MRS_OK;
+  if ((rc = check_device_ptr(s, dev_force, rows_bytes(count, stride, 3, dtype), "dev_force"))) return rc;
+  HIPCHK(hipSetDevice(s->device));
+  hipStream_t ext = (hipStream_t)ext_stream;
+  if ((rc = fence_in(s, ext))) return rc;
+  if (dtype == MRS_DTYPE_F32)
+    hipLaunchKernelGGL(k_scatter_force<float>, grid_of(count), dim3(256), 0, s->stream, s->view(), static_cast<const float*>(dev_force), stride, first,
+                       count);
+  else
+    hipLaunchKernelGGL(k_scatter_force<double>, grid_of(count), dim3(256), 0, s->stream, s->view(), static_cast<const double*>(dev_force), stride, first,
+                       count);
+  HIPCHK(hipGetLastError());
+  s->fext_active = true;
+  return fence_out(s, ext);
+}
+
+// the rollout entry points, under the caller's lock (MRS_ENTER's settle after the argument checks: a refused call launches nothing)
 static int rollout_locked(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every, int32_t obs_every,
-                          const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream,
-                          const char* who) {
+                          int32_t force_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, const void* dev_force, int32_t force_stride,
+                          uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream, bool forced, const char* who) {
   int rc = check_range(s, first, count);
   if (rc) return rc;
   if (s->comm_world > 0) return fail(MRS_ERR_ARG, std::string(who) + ": not on a sharded swarm");
@@ -315,6 +352,9 @@ static int rollout_locked(mrs_swarm_t* s, int32_t first, int32_t count, int32_t 
   if (n_steps < 1) return fail(MRS_ERR_ARG, "n_steps must be at least 1");
   if (cmd_every < 1 || n_steps % cmd_every != 0) return fail(MRS_ERR_ARG, "cmd_every must be at least 1 and divide n_steps");
   if (obs_every < 1 || n_steps % obs_every != 0) return fail(MRS_ERR_ARG, "obs_every must be at least 1 and divide n_steps");
+  if (forced && (force_every < 1 || n_steps % force_every != 0)) return fail(MRS_ERR_ARG, "force_every must be at least 1 and divide n_steps");
+  if (forced && force_stride < 3) return fail(MRS_ERR_ARG, "force_stride smaller than the three force components");
+  if (forced && !dev_force) return fail(MRS_ERR_ARG, "dev_force: null pointer");
   if (!(dt > 0) || !std::isfinite(dt)) return fail(MRS_ERR_ARG, "dt must be finite and > 0");
   const int width = command_width(mode, cmd_stride);
   if (width > 0 && (cmd_stride < width || width < 1)) return fail(MRS_ERR_ARG, "cmd_stride too small for this mode");
@@ -328,6 +368,10 @@ static int rollout_locked(mrs_swarm_t* s, int32_t first, int32_t count, int32_t 
       return rc;
     if (groups != 0u && (rc = check_device_ptr(s, dev_obs, ((obs_rows - 1) * (size_t)obs_stride + (size_t)obs_width) * dtype_bytes(dtype), "dev_obs")))
       return rc;
+    if (forced) {
+      const size_t force_rows = (size_t)(n_steps / force_every) * (size_t)count;
+      if ((rc = check_device_ptr(s, dev_force, ((force_rows - 1) * (size_t)force_stride + 3u) * dtype_bytes(dtype), "dev_force"))) return rc;
+    }
     if (mode == MRS_ACTUATOR_CMD && !actuator_width_ok(s, first, count, width)) return fail(MRS_ERR_ARG, "actuator payload narrower than n_motors");
   }
   if (s->n == 0) return MRS_OK;
@@ -347,6 +391,21 @@ static int rollout_locked(mrs_swarm_t* s, int32_t first, int32_t count, int32_t 
   s->collide_since_step = false;
   s->p_valid            = false;  // (plain steps do not refresh the position records)
   const int variant = s->n_cascade > 0 ? 0 : 1;  // 0 all input modes | 1 model only
+  if (forced) {  // a third schedule: the kernels of rollout_force_device.inc, whatever the rates are
+    if (count > 0) s->fext_active = true;  // (the loop's first mrs_swarm_apply_force_device: from here on the steps read the F_FEXT columns)
+    RolloutForceDev r{};
+    r.cmd = dev_cmd, r.obs = groups != 0u ? dev_obs : nullptr, r.force = count > 0 ? dev_force : nullptr;
+    r.first = first, r.count = count;
+    r.cmd_stride = cmd_stride, r.obs_stride = obs_stride, r.force_stride = force_stride;
+    r.cmd_sched = ((uint32_t)width | (dtype == MRS_DTYPE_F32 ? 32u : 0u)) << 24;
+    r.obs_sched = groups << 24;
+    r.mode_bits = (uint32_t)mode << FLAG_MODE_SHIFT;
+    if (s->arith == MRS_ARITH_FAST)
+      HIPCHK(mrs_launch_rollout_force_fast(s->view(), r, dt, n_steps, cmd_every, obs_every, force_every, variant, s->stream));
+    else
+      HIPCHK(mrs_launch_rollout_force_literal(s->view(), r, dt, n_steps, cmd_every, obs_every, force_every, variant, s->stream));
+    return fence_out(s, ext);
+  }
   if (cmd_every == 1 && obs_every == 1) {  // a row before and after every step: the kernels of rollout_device.inc
     const RolloutDev r{dev_cmd, groups != 0u ? dev_obs : nullptr, first, count, cmd_stride, width, obs_stride, 0, (uint32_t)mode << FLAG_MODE_SHIFT,
                        groups, dtype == MRS_DTYPE_F32 ? 1 : 0};
@@ -373,7 +432,7 @@ static int rollout_locked(mrs_swarm_t* s, int32_t first, int32_t count, int32_t 
 int mrs_swarm_rollout_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, const void* dev_cmd,
                              int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream) {
   MRS_LOCK(s);
-  return rollout_locked(s, first, count, mode, dt, n_steps, 1, 1, dev_cmd, dtype, cmd_stride, groups, dev_obs, obs_stride, ext_stream,
+  return rollout_locked(s, first, count, mode, dt, n_steps, 1, 1, 0, dev_cmd, dtype, cmd_stride, nullptr, 0, groups, dev_obs, obs_stride, ext_stream, false,
                         "mrs_swarm_rollout_device");
 }
 
@@ -381,8 +440,16 @@ int mrs_swarm_rollout_rate_device(mrs_swarm_t* s, int32_t first, int32_t count, 
                                   int32_t obs_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs,
                                   int32_t obs_stride, void* ext_stream) {
   MRS_LOCK(s);
-  return rollout_locked(s, first, count, mode, dt, n_steps, cmd_every, obs_every, dev_cmd, dtype, cmd_stride, groups, dev_obs, obs_stride, ext_stream,
-                        "mrs_swarm_rollout_rate_device");
+  return rollout_locked(s, first, count, mode, dt, n_steps, cmd_every, obs_every, 0, dev_cmd, dtype, cmd_stride, nullptr, 0, groups, dev_obs, obs_stride,
+                        ext_stream, false, "mrs_swarm_rollout_rate_device");
+}
+
+int mrs_swarm_rollout_force_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every,
+                                   int32_t obs_every, int32_t force_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride,
+                                   const void* dev_force, int32_t force_stride, uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream) {
+  MRS_LOCK(s);
+  return rollout_locked(s, first, count, mode, dt, n_steps, cmd_every, obs_every, force_every, dev_cmd, dtype, cmd_stride, dev_force, force_stride, groups,
+                        dev_obs, obs_stride, ext_stream, true, "mrs_swarm_rollout_force_device");
 }
 
 }  // extern "C"

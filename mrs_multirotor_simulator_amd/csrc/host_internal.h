@@ -45,6 +45,10 @@ extern "C" hipError_t mrs_launch_rollout_rate_literal(SwarmDev sw, RolloutRateDe
                                                         hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_rate_fast(SwarmDev sw, RolloutRateDev r, double dt, int n_steps, int cmd_every, int obs_every, int variant,
                                                      hipStream_t st);
+extern "C" hipError_t mrs_launch_rollout_force_literal(SwarmDev sw, RolloutForceDev r, double dt, int n_steps, int cmd_every, int obs_every, int force_every,
+                                                         int variant, hipStream_t st);
+extern "C" hipError_t mrs_launch_rollout_force_fast(SwarmDev sw, RolloutForceDev r, double dt, int n_steps, int cmd_every, int obs_every, int force_every,
+                                                      int variant, hipStream_t st);
 extern "C" hipError_t mrs_launch_pid_probe_literal(const double*, const double*, const double*, const double*, const double*, double*, int, int, hipStream_t);
 extern "C" hipError_t mrs_launch_pid_probe_fast(const double*, const double*, const double*, const double*, const double*, double*, int, int, hipStream_t);
 extern "C" hipError_t mrs_launch_pid_update_probe_literal(const double*, double*, const double*, const double*, double*, int, hipStream_t);

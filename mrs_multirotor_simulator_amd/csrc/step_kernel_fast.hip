@@ -3,3 +3,4 @@
 #include "step_device.inc"
 #include "rollout_device.inc"
 #include "rollout_rate_device.inc"
+#include "rollout_force_device.inc"

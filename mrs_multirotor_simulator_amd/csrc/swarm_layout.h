@@ -128,6 +128,22 @@ inline uint32_t mrs_ro_sched(int s0, int every) {
   return (uint32_t)s0 | (p - 1u) << 6 | (m - 1u) << 12;
 }
 
+// ---- one launch of a control-rate rollout under scheduled external forces (mrs_swarm_rollout_force_device, rollout_force_device.inc) ----
+// RolloutRateDev and a third schedule: force row block j (applyForce, world frame, N) is latched in the F_FEXT columns from step
+// j * force_every on.  The dtype bit stays in cmd_sched.
+struct RolloutForceDev {
+  const void* cmd;
+  void*       obs;
+  int32_t     first, count;
+  int32_t     cmd_stride, obs_stride;
+  uint32_t    cmd_sched;
+  uint32_t    obs_sched;
+  uint32_t    mode_bits;
+  const void* force;         // force rows of the launch's FIRST due block; row (j, k) at element ((j * count) + k) * force_stride behind it
+  int32_t     force_stride;
+  uint32_t    force_sched;   // MRS_RO_S0 / P / M | 3 << 24.  Width 0: no force row in this launch
+};
+
 // 48-byte record exchanged for the collision pass (single- and multi-GPU): everything
 // MultirotorSimulator::handleCollisions reads of the partner UAV (src/multirotor_simulator.cpp:339-350)
 struct PosRecord {

@@ -114,6 +114,8 @@ ABI_SYMBOLS = [
     "mrs_swarm_reset_device", "mrs_nearest_width", "mrs_swarm_nearest_device", "mrs_swarm_save_device", "mrs_swarm_load_device",
     "mrs_swarm_rollout_device",
     "mrs_swarm_rollout_rate_device",
+    "mrs_swarm_apply_force_device",
+    "mrs_swarm_rollout_force_device",
 ]
 
 # device-resident callers (mrs_swarm_*_device): row element types and the observation groups of mrs_swarm_gather_device, in bit order
@@ -346,6 +348,8 @@ def load_library():
         "mrs_swarm_load_device": [vp, i32, i32, vp, C.c_int64, vp, vp, vp],
         "mrs_swarm_rollout_device": [vp, i32, i32, i32, C.c_double, i32, vp, i32, i32, C.c_uint32, vp, i32, vp],
         "mrs_swarm_rollout_rate_device": [vp, i32, i32, i32, C.c_double, i32, i32, i32, vp, i32, i32, C.c_uint32, vp, i32, vp],
+        "mrs_swarm_apply_force_device": [vp, i32, i32, vp, i32, i32, vp],
+        "mrs_swarm_rollout_force_device": [vp, i32, i32, i32, C.c_double, i32, i32, i32, i32, vp, i32, i32, vp, i32, C.c_uint32, vp, i32, vp],
     }
     for name, args in sig.items():
         if os.environ.get("MRS_SWARM_LIB") and not hasattr(L, name):
@@ -831,6 +835,16 @@ class Swarm:
         _check(_lib.mrs_swarm_rollout_rate_device(self._h, int(first), int(count), int(mode), C.c_double(float(dt)), int(n_steps), int(cmd_every),
                                                   int(obs_every), dev_cmd or None, int(dtype), int(cmd_stride), C.c_uint32(int(groups)),
                                                   dev_obs or None, int(obs_stride), ext_stream or None))
+
+    def apply_force_device(self, first, count, dev_force, dtype, stride, ext_stream):
+        _check(_lib.mrs_swarm_apply_force_device(self._h, int(first), int(count), dev_force or None, int(dtype), int(stride), ext_stream or None))
+
+    def rollout_force_device(self, first, count, mode, dt, n_steps, cmd_every, obs_every, force_every, dev_cmd, dtype, cmd_stride, dev_force,
+                             force_stride, groups, dev_obs, obs_stride, ext_stream):
+        _check(_lib.mrs_swarm_rollout_force_device(self._h, int(first), int(count), int(mode), C.c_double(float(dt)), int(n_steps), int(cmd_every),
+                                                   int(obs_every), int(force_every), dev_cmd or None, int(dtype), int(cmd_stride),
+                                                   dev_force or None, int(force_stride), C.c_uint32(int(groups)), dev_obs or None,
+                                                   int(obs_stride), ext_stream or None))
 
     def get_diag(self):
         d = Diag()

@@ -105,6 +105,18 @@ def set_input(swarm, mode, rows, first=0):
     swarm.set_input_device(first, count, mode, ptr, code, stride, _stream(dev))
 
 
+def apply_force(swarm, rows, first=0):
+    """UavSystem::applyForce for UAVs [first, first + rows.shape[0]) from a [count, >= 3] FP32 / FP64 tensor: world frame, newtons, latched
+    until the next applyForce or evaluated collision tick (mrs_swarm_apply_force_device).  Columns past the third are padding."""
+    dev = swarm.device()
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2:
+        raise ValueError("rows must be a [count, >= 3] tensor")
+    code = _dtype_code(rows.dtype)
+    count = rows.shape[0]
+    stride = check_tensor(rows, count, 3, rows.dtype, dev)
+    swarm.apply_force_device(first, count, rows.data_ptr() if count > 0 else 0, code, stride, _stream(dev))
+
+
 def _check_steps(t, name, steps, rows, min_width, dtype, device_index):
     """Refuse `t` unless it is a [steps, rows, >= min_width] tensor on cuda:`device_index` of `dtype` (steps None: any number >= 1) whose
     rows are contiguous and whose row blocks follow each other densely: stride(0) == rows * stride(1).  Returns the row stride."""
@@ -128,7 +140,8 @@ def _check_steps(t, name, steps, rows, min_width, dtype, device_index):
     return stride
 
 
-def rollout(swarm, mode, commands, dt, groups=OBS_POS | OBS_VEL | OBS_QUAT, first=0, out=None, hold=1, obs_every=None):
+def rollout(swarm, mode, commands, dt, groups=OBS_POS | OBS_VEL | OBS_QUAT, first=0, out=None, hold=1, obs_every=None, forces=None,
+            force_hold=None):
     """B * hold steps of the whole swarm in which UAVs [first, first + count) take command row block j before step j * hold, keep it for
     `hold` steps (setInput latches), and report the OBS_* groups of `groups` after every `obs_every` steps (default: `hold`, a row block
     per command; B * hold: the final state only).  With hold == 1 (mrs_swarm_rollout_device): `for t: set_input(swarm, mode,
@@ -136,7 +149,11 @@ def rollout(swarm, mode, commands, dt, groups=OBS_POS | OBS_VEL | OBS_QUAT, firs
     with obs_every == hold (mrs_swarm_rollout_rate_device): `for j: set_input(commands[j]); swarm.step_n(dt, hold); gather(out=out[j])`.
     commands: [B, count, >= width] FP32 / FP64 (the payload layouts of set_input; ACTUATOR rows are dense).  obs_every must be >= 1 and
     divide B * hold.  out: [B * hold // obs_every, count, >= gather_width(groups)] of the same dtype, allocated when None; returned
-    (None when groups == 0).  UAVs outside the range are stepped with their own commands."""
+    (None when groups == 0).  UAVs outside the range are stepped with their own commands.
+    forces: [Bf, count, >= 3] of the commands' dtype: UAVs of the range take force row block j (applyForce: world frame, newtons) before
+    step j * force_hold and keep it for `force_hold` steps (default: B * hold // Bf; it must be >= 1 and Bf * force_hold == B * hold) —
+    the loop above with `apply_force(swarm, forces[j], first)` in it, in one call (mrs_swarm_rollout_force_device).  Afterwards the range
+    carries the last force block."""
     dev = swarm.device()
     if not isinstance(commands, torch.Tensor) or commands.dim() != 3:
         raise ValueError("commands must be a [T, count, width] tensor")
@@ -153,6 +170,12 @@ def rollout(swarm, mode, commands, dt, groups=OBS_POS | OBS_VEL | OBS_QUAT, firs
     cstride = _check_steps(commands, "commands", None, count, width, commands.dtype, dev)
     if mode == ACTUATOR_CMD and count > 1 and cstride != commands.shape[2]:
         raise ValueError("actuator rows must be dense (row stride == number of motors)")
+    if forces is not None:
+        fstride = _check_steps(forces, "forces", None, count, 3, commands.dtype, dev)
+        fhold = steps // forces.shape[0] if force_hold is None else int(force_hold)
+        if fhold < 1 or forces.shape[0] * fhold != steps:
+            raise ValueError(f"force_hold must be at least 1 and {forces.shape[0]} force blocks x force_hold must be the {steps} steps of the "
+                             f"call, got {fhold}")
     owidth = gather_width(groups)
     optr, ostride = 0, owidth
     if groups:
@@ -163,7 +186,10 @@ def rollout(swarm, mode, commands, dt, groups=OBS_POS | OBS_VEL | OBS_QUAT, firs
         ostride = _check_steps(out, "out", steps // every, count, owidth, commands.dtype, dev)
         optr = out.data_ptr()
     cptr = commands.data_ptr() if width > 0 and count > 0 else 0
-    if hold == 1 and every == 1:
+    if forces is not None:
+        swarm.rollout_force_device(first, count, mode, dt, steps, hold, every, fhold, cptr, code, cstride, forces.data_ptr(), fstride, groups,
+                                   optr, ostride, _stream(dev))
+    elif hold == 1 and every == 1:
         swarm.rollout_device(first, count, mode, dt, steps, cptr, code, cstride, groups, optr, ostride, _stream(dev))
     else:
         swarm.rollout_rate_device(first, count, mode, dt, steps, hold, every, cptr, code, cstride, groups, optr, ostride, _stream(dev))

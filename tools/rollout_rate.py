@@ -20,6 +20,15 @@ block is due every `obs_every` steps (mrs_swarm_rollout_rate_device).  The same 
 and prints the bytes of rows one call of `plain` and of `rate` carries.  In both flavours rows plain[obs_every-1::obs_every] == rate and the
 final states must be bit-identical; in LITERAL the loop must equal them too (in FAST its largest relative difference is printed).
 `forms` then selects among plain,rate,loop (default: all three; `loop,rollout`, the default above, also means all three).
+
+With `--force-every N` (anywhere on the command line, beside a `hold`) the tool measures the FORCE rollout: a force row block (FP32, a few
+newtons per axis) is applied every N steps (mrs_swarm_rollout_force_device).  The same T steps four ways, alternating:
+  rate     the rate rollout above on a swarm that has had a zero force applied (so every form reads the force columns)
+  force    tensors.rollout(cmd, dt, out=, hold=hold, obs_every=obs_every, forces=frc, force_hold=N)
+  force1   the same with force_hold=1 on frc.repeat_interleave(N, 0): a force row per step
+  loop     set_input every `hold` steps, apply_force every N steps, step_n(dt, to the next event), gather every `obs_every` steps
+`force`, `force1` and `loop` apply the same forces: in LITERAL they must end bit-identical (rows and state), and differ from `rate`.
+`forms` selects among rate,force,force1,loop (default: all four).
 """
 import os
 import sys
@@ -45,6 +54,11 @@ def commands(mode, n, steps, rng):
 def main():
     import torch
     from mrs_multirotor_simulator_amd import tensors as T
+    force_every = None
+    if "--force-every" in sys.argv:
+        k = sys.argv.index("--force-every")
+        force_every = int(sys.argv[k + 1])
+        del sys.argv[k:k + 2]
     sizes = [int(s) for s in sys.argv[1].split(",")] if len(sys.argv) > 1 else [100_000, 1_000_000]
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 64
     reps = int(sys.argv[3]) if len(sys.argv) > 3 else 5
@@ -54,7 +68,11 @@ def main():
     if len(sys.argv) > 7:
         hold = int(sys.argv[7])
         every = int(sys.argv[8]) if len(sys.argv) > 8 else hold
+        if force_every is not None:
+            return main_force(sizes, steps, reps, modes, ["rate", "force", "force1", "loop"] if forms == ["loop", "rollout"] else forms, arith, hold,
+                              every, force_every)
         return main_rate(sizes, steps, reps, modes, ["plain", "rate", "loop"] if forms == ["loop", "rollout"] else forms, arith, hold, every)
+    assert force_every is None, "--force-every needs a hold"
     groups = T.OBS_POS | T.OBS_VEL | T.OBS_QUAT
     rng = np.random.default_rng(5)
     print(f"rollout of T = {steps} steps, FP32 commands and POS|VEL|QUAT rows, x500, {arith.upper()}; {reps} rounds after a warm-up, alternating")
@@ -208,6 +226,98 @@ def main_rate(sizes, steps, reps, modes, forms, arith, hold, every):
                     assert bits_equal(obs["loop"], obs["rate"]), f"{n} {mode_name}: rows of loop and rate differ"
                     same_state("loop", "rate")
                     line += "  loop == rate"
+            print(line, flush=True)
+            for g in swarms.values():
+                g.close()
+
+
+def main_force(sizes, steps, reps, modes, forms, arith, hold, every, fhold):
+    import torch
+    from mrs_multirotor_simulator_amd import tensors as T
+    assert min(hold, every, fhold) >= 1 and steps % hold == 0 and steps % every == 0 and steps % fhold == 0, "the three rates must divide T"
+    assert set(forms) <= {"rate", "force", "force1", "loop"}, forms
+    groups = T.OBS_POS | T.OBS_VEL | T.OBS_QUAT
+    ow = T.gather_width(groups)
+    rng = np.random.default_rng(5)
+    print(f"force rollout of T = {steps} steps, hold {hold}, obs_every {every}, force_every {fhold}, FP32 commands, forces and POS|VEL|QUAT rows, "
+          f"x500, {arith.upper()}; {reps} rounds after a warm-up, alternating")
+    for n in sizes:
+        st, _ = bench.make_inputs(n, "position+collisions", seed=3)
+        p = M.model_params("x500", ground_enabled=True, ground_z=0.0)
+        for mode_name in modes:
+            mode = getattr(M, mode_name)
+            swarms = {}
+            for f in forms:
+                g = M.Swarm(n, arith=M.ARITH_FAST if arith == "fast" else M.ARITH_LITERAL)
+                g.construct(0, n, p)
+                g.set_state(0, n, st["x"], st["v"], st["R"], st["omega"], st["motor_rpm"])
+                g.apply_force(0, n, np.zeros((n, 3)))  # every form reads the force columns from its first step on
+                swarms[f] = g
+            dev = torch.device("cuda", swarms[forms[0]].device())
+            cmd = torch.tensor(commands(mode, n, steps // hold, rng), dtype=torch.float32, device=dev)
+            frc = torch.tensor(rng.uniform(-3.0, 3.0, (steps // fhold, n, 3)), dtype=torch.float32, device=dev)
+            frc1 = frc.repeat_interleave(fhold, 0) if "force1" in forms else None  # (made once: the caller's copy is not what is timed)
+            obs = {f: torch.empty((steps // every, n, ow), dtype=torch.float32, device=dev) for f in forms}
+
+            def run(form):
+                g = swarms[form]
+                if form == "rate":
+                    T.rollout(g, mode, cmd, DT, groups, out=obs[form], hold=hold, obs_every=every)
+                elif form == "force":
+                    T.rollout(g, mode, cmd, DT, groups, out=obs[form], hold=hold, obs_every=every, forces=frc, force_hold=fhold)
+                elif form == "force1":
+                    T.rollout(g, mode, cmd, DT, groups, out=obs[form], hold=hold, obs_every=every, forces=frc1, force_hold=1)
+                else:
+                    t = 0
+                    while t < steps:
+                        if t % hold == 0:
+                            T.set_input(g, mode, cmd[t // hold])
+                        if t % fhold == 0:
+                            T.apply_force(g, frc[t // fhold])
+                        nxt = min((t // hold + 1) * hold, (t // every + 1) * every, (t // fhold + 1) * fhold)
+                        g.step_n(DT, nxt - t)
+                        t = nxt
+                        if t % every == 0:
+                            T.gather(g, groups, out=obs[form][t // every - 1])
+
+            for f in forms:  # warm-up: code objects, the type table, torch kernels
+                run(f)
+            torch.cuda.synchronize(dev)
+            times = {f: [] for f in forms}
+            for _ in range(reps):
+                for f in forms:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    run(f)
+                    e1.record()
+                    e1.synchronize()
+                    times[f].append(e0.elapsed_time(e1) * 1e3 / steps)
+            line = f"  {n:>8d} UAVs  {mode_name:18s}"
+            for f in forms:
+                line += f"  {f} {float(np.median(times[f])):7.2f} us/step ({min(times[f]):.2f}-{max(times[f]):.2f})"
+            if "force" in forms and "loop" in forms:
+                line += "  force beats loop" if max(times["force"]) < min(times["loop"]) else "  FORCE DOES NOT BEAT LOOP"
+
+            def same_state(fa, fb):
+                a, b = swarms[fa].get_states(), swarms[fb].get_states()
+                for fld in a.dtype.names:
+                    assert np.array_equal(a[fld].view(np.uint64) if a[fld].dtype == np.float64 else a[fld],
+                                          b[fld].view(np.uint64) if b[fld].dtype == np.float64 else b[fld]), f"{n} {mode_name}: {fld} differs ({fa} / {fb})"
+
+            if "force" in forms and "force1" in forms:
+                assert bits_equal(obs["force"], obs["force1"]), f"{n} {mode_name}: rows of force and force1 differ"
+                same_state("force", "force1")
+                line += "  force == force1"
+            if "force" in forms and "rate" in forms:
+                assert not bits_equal(obs["force"], obs["rate"]), f"{n} {mode_name}: the forces moved nothing"
+            if "loop" in forms and "force" in forms:
+                if arith == "fast":
+                    a, b = obs["loop"].double(), obs["force"].double()
+                    line += f"  loop vs force max rel diff {float(((a - b).abs() / a.abs().clamp_min(1.0)).max()):.1e}"
+                else:
+                    assert bits_equal(obs["loop"], obs["force"]), f"{n} {mode_name}: rows of loop and force differ"
+                    same_state("loop", "force")
+                    line += "  loop == force"
             print(line, flush=True)
             for g in swarms.values():
                 g.close()

@@ -196,7 +196,9 @@ int mrs_swarm_step(mrs_swarm_t* s, double dt);
  * of those UAVs; the neighbour lists of the collision pass are rebuilt at the next collision tick. */
 int mrs_swarm_step_range(mrs_swarm_t* s, int32_t first, int32_t count, double dt);
 /* n_steps consecutive makeStep(dt) rounds; substeps_per_launch > 1 keeps the state in registers across that many
- * steps inside one launch (legal while commands are constant and collisions are off; results identical). */
+ * steps inside one launch (legal while commands are constant and collisions are off; results identical).  After the call every
+ * getter returns what n_steps single mrs_swarm_step calls leave behind; the IMU value (an output no step reads) is stored by the
+ * last launch of the call only. */
 int mrs_swarm_step_n(mrs_swarm_t* s, double dt, int32_t n_steps, int32_t substeps_per_launch);
 /* MultirotorSimulator::handleCollisions — src/multirotor_simulator.cpp:295-359 (kd-tree replaced by a spatial hash) */
 int mrs_swarm_handle_collisions(mrs_swarm_t* s, int32_t enabled, int32_t crash, double rebounce);

@@ -419,8 +419,8 @@ int     put_strided(mrs_swarm* s, int f, int first, int count, const double* src
 int     get_strided(mrs_swarm* s, int f, int first, int count, double* dst, int width, int j);
 int     flags_update(mrs_swarm* s, int first, int count, uint32_t and_mask, uint32_t or_mask);
 // ---- tick_single.hip ----
-int  launch_part(mrs_swarm* s, double dt, int substeps, int blk0, int nblk, int with_mixed, hipStream_t st);
-int  launch_step(mrs_swarm* s, double dt, int substeps);
+int  launch_part(mrs_swarm* s, double dt, int substeps, int blk0, int nblk, int with_mixed, hipStream_t st, bool imu_dead = false);
+int  launch_step(mrs_swarm* s, double dt, int substeps, bool imu_dead = false);
 int  begin_profile(mrs_swarm* s);
 int  finish_profile(mrs_swarm* s);
 int  collide_now(mrs_swarm* s, const mrs_swarm::Collide& c, bool force);

@@ -1174,6 +1174,9 @@ DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, co
   // MULTI = false compiles the substep loop away: with the loop the state is loop-carried and the per-type constants are
   // hoisted in front of it, which costs the fused kernel ~120 registers (350 vs 227) and with them its second wave per SIMD
   const int substeps = MULTI ? substeps_arg : 1;
+  // the launches of a plain run of steps may be told to leave the IMU columns alone (epilogue).  The collision / sharded ticks never
+  // are (a stall and its replay change after the fact which launch was the last one), nor the rollouts (hooked kernels)
+  constexpr bool IMU_OPT = !COLL && __is_same(HK, NoStepHook);
   // Prologue: every load the step starts from is issued BEFORE the first data-dependent exit (mixed block, tail lane, UAV on
   // hold), from addresses that are valid for every lane, and an asm memory barrier keeps the compiler from sinking them below
   // those exits — otherwise the block-type word, the flag word and the state would be three dependent memory round trips
@@ -1464,15 +1467,33 @@ DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, co
   for (int u = 0; u < NU; u++) {
     const int i = idx[u];
     if (i < 0) continue;
+    if (IMU_OPT) {
+      // The IMU columns are an output only — no step reads them — so a launch that is followed by another launch of the same run
+      // (MRS_OPT_IMU_DEAD, set by mrs_swarm_step_n on every launch but the last) leaves them alone: the stores stand apart from the
+      // others, under a wave-uniform branch on a kernel argument.
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-      sw.st(F_X + c, (unsigned)i * 8u, L[u].y[c]);
-      sw.st(F_V + c, (unsigned)i * 8u, L[u].y[3 + c]);
-      sw.st(F_W + c, (unsigned)i * 8u, L[u].y[15 + c]);
-      sw.st(F_IMU + c, (unsigned)i * 8u, L[u].imu[c]);
+      for (int c = 0; c < 3; c++) {
+        sw.st(F_X + c, (unsigned)i * 8u, L[u].y[c]);
+        sw.st(F_V + c, (unsigned)i * 8u, L[u].y[3 + c]);
+        sw.st(F_W + c, (unsigned)i * 8u, L[u].y[15 + c]);
+      }
+#pragma unroll
+      for (int c = 0; c < 9; c++) sw.st(F_R + c, (unsigned)i * 8u, L[u].y[6 + c]);
+      if (!(sw.opts & MRS_OPT_IMU_DEAD)) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) sw.st(F_IMU + c, (unsigned)i * 8u, L[u].imu[c]);
+      }
+    } else {  // fused collision ticks, sharded ticks, rollouts: every launch writes its IMU (their code is what it was)
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        sw.st(F_X + c, (unsigned)i * 8u, L[u].y[c]);
+        sw.st(F_V + c, (unsigned)i * 8u, L[u].y[3 + c]);
+        sw.st(F_W + c, (unsigned)i * 8u, L[u].y[15 + c]);
+        sw.st(F_IMU + c, (unsigned)i * 8u, L[u].imu[c]);
+      }
+#pragma unroll
+      for (int c = 0; c < 9; c++) sw.st(F_R + c, (unsigned)i * 8u, L[u].y[6 + c]);
     }
-#pragma unroll
-    for (int c = 0; c < 9; c++) sw.st(F_R + c, (unsigned)i * 8u, L[u].y[6 + c]);
     if (L[u].flags != flags_in[u]) sw.F[i] = L[u].flags;
     if (COLL) {
       CDT&       cd = fresh(cd0);

@@ -70,6 +70,10 @@ struct TypeParams {
 };
 
 // ---- device view of a swarm ----
+// SwarmDev::opts bit 1: a later launch of the same mrs_swarm_step_n call steps every UAV of this launch again before anybody can read
+// the F_IMU columns, so this launch does not store them (the IMU value is an output only: no step reads it).  Plain step kernels
+// only; the *_coll / sharded kernels and the rollout kernels never see the bit and do not test it.
+#define MRS_OPT_IMU_DEAD 2u
 struct PosRecord;
 struct SwarmDev {
   double*             S;      // F_COUNT x npad
@@ -79,7 +83,8 @@ struct SwarmDev {
   const uint32_t*     BT;     // per 64-UAV block: airframe type (0xFFFF = mixed types) | n_motors << 16
   const int32_t*      MB;     // indices of the mixed blocks (n_mixed entries)
   int32_t             n, npad, n_mixed;
-  uint32_t            opts;   // bit 0: some UAV may carry a non-zero external force (else the F_FEXT columns are not read)
+  uint32_t            opts;   // bit 0: some UAV may carry a non-zero external force (else the F_FEXT columns are not read);
+                              // MRS_OPT_IMU_DEAD: set by the host on its copy, per launch
   // skin test of the collision pass's neighbour lists (collide.hip); vl_flag == nullptr: no lists are live
   const PosRecord*    vl_rec;   // per-UAV record holding the position at the last list rebuild
   uint32_t*           vl_flag;  // set to 1 when some UAV is farther than sqrt(vl_lim2) from that position

@@ -6,16 +6,21 @@
 
 namespace mrs_host {
 // ---- hot path ----
-int launch_part(mrs_swarm* s, double dt, int substeps, int blk0, int nblk, int with_mixed, hipStream_t st) {
+// imu_dead: another launch of the same mrs_swarm_step_n call follows on this stream and steps the same UAVs again before anybody can
+// read the IMU columns — this one (and the mixed-block launch that rides with it) does not store them (MRS_OPT_IMU_DEAD).  Only
+// mrs_swarm_step_n passes true; every other caller's launch may be the last one somebody looks at.
+int launch_part(mrs_swarm* s, double dt, int substeps, int blk0, int nblk, int with_mixed, hipStream_t st, bool imu_dead) {
   const int variant = s->n_cascade > 0 ? 0 : 1;  // 0 all input modes | 1 model only
+  SwarmDev  v       = s->view();
+  if (imu_dead) v.opts |= MRS_OPT_IMU_DEAD;
   if (s->arith == MRS_ARITH_FAST)
-    HIPCHK(mrs_launch_step_fast(s->view(), dt, substeps, variant, blk0, nblk, with_mixed, st));
+    HIPCHK(mrs_launch_step_fast(v, dt, substeps, variant, blk0, nblk, with_mixed, st));
   else
-    HIPCHK(mrs_launch_step_literal(s->view(), dt, substeps, variant, blk0, nblk, with_mixed, st));
+    HIPCHK(mrs_launch_step_literal(v, dt, substeps, variant, blk0, nblk, with_mixed, st));
   return MRS_OK;
 }
 
-int launch_step(mrs_swarm* s, double dt, int substeps) {
+int launch_step(mrs_swarm* s, double dt, int substeps, bool imu_dead) {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   s->region_launches++;
   if (s->profiling == 2) {
@@ -29,19 +34,20 @@ int launch_step(mrs_swarm* s, double dt, int substeps) {
     s->ev_used += 2;
     HIPCHK(hipEventRecord(e0, s->stream));
   }
-  int rc = launch_part(s, dt, substeps, 0, (s->n + 63) / 64, 1, s->stream);
+  // (per-launch events: somebody times single launches — they all do the same work)
+  int rc = launch_part(s, dt, substeps, 0, (s->n + 63) / 64, 1, s->stream, imu_dead && s->profiling != 2);
   if (rc) return rc;
   if (s->profiling == 2) HIPCHK(hipEventRecord(e1, s->stream));
   return MRS_OK;
 }
 
 // one step as two independent half-swarm launches, one per stream (between fork_streams and join_streams)
-int launch_step_split(mrs_swarm* s, double dt, int substeps) {
+int launch_step_split(mrs_swarm* s, double dt, int substeps, bool imu_dead) {
   s->region_launches++;
   const int nb = (s->n + 63) / 64, half = nb / 2;
-  int rc = launch_part(s, dt, substeps, 0, half, 1, s->stream);
+  int rc = launch_part(s, dt, substeps, 0, half, 1, s->stream, imu_dead);
   if (rc) return rc;
-  return launch_part(s, dt, substeps, half, nb - half, 0, s->stream2);
+  return launch_part(s, dt, substeps, half, nb - half, 0, s->stream2, imu_dead);
 }
 int fork_streams(mrs_swarm* s) {
   HIPCHK(hipEventRecord(s->ev_fork, s->stream));
@@ -360,10 +366,16 @@ int mrs_swarm_step_n(mrs_swarm_t* s, double dt, int32_t n_steps, int32_t substep
     //  both streams are idle (upload_types synchronises when it copies), the second one needs no event to wait for)
     const bool quiet = idle_at_entry && !enqueued;
     if (split && !quiet && (rc = fork_streams(s))) return rc;
+    // Every launch iteration but the last leaves the IMU columns alone (MRS_OPT_IMU_DEAD): the value is an output only, and nothing
+    // can read the columns before this call returns — by then the last iteration (both halves of it, in the split form) has stepped
+    // every UAV that any earlier one stepped, and has written its IMU.  A run that ends early on a launch error leaves the state
+    // undefined, as before.  The first step above (step_one) and everything that goes through tick_n / tick_sharded_n / the fused
+    // collision launches always write: their stall / replay logs can change after the fact which launch was the last one.
     int left = n_steps;
     while (left > 0 && rc == MRS_OK) {
-      const int sub = left < substeps_per_launch ? left : substeps_per_launch;
-      rc = split ? launch_step_split(s, dt, sub) : launch_step(s, dt, sub);
+      const int  sub  = left < substeps_per_launch ? left : substeps_per_launch;
+      const bool last = left == sub;
+      rc = split ? launch_step_split(s, dt, sub, !last) : launch_step(s, dt, sub, !last);
       left -= sub;
     }
     if (split) {  // also on a failed launch: nothing else may touch the state before the second stream has been joined

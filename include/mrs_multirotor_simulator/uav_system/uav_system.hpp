@@ -804,6 +804,15 @@ public:
     mrs_throw_on_error(mrs_swarm_rollout_force_device(s_, first, count, mode, dt, n_steps, cmd_every, obs_every, force_every, dev_cmd, dtype, cmd_stride,
                                                       dev_force, force_stride, groups, dev_obs, obs_stride, stream));
   }
+  // rolloutRateDevice that sums a quadratic cost where it would write a row: after every cost_every steps the FP64 observation row of
+  // UAV first + k is compared with target row (j, k) (target_stride 0: one shared row per evaluation) under weight row j (weight_stride
+  // 0: one row for all), and sum_col (w * d) * d is added to dev_cost[k] (FP64; zeroed first unless accumulate)
+  void rolloutCostDevice(int first, int count, int mode, double dt, int n_steps, int cmd_every, int cost_every, const void* dev_cmd, int dtype,
+                         int cmd_stride, uint32_t groups, const void* dev_target, int target_stride, const void* dev_weight, int weight_stride,
+                         double* dev_cost, bool accumulate = false, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_rollout_cost_device(s_, first, count, mode, dt, n_steps, cmd_every, cost_every, dev_cmd, dtype, cmd_stride, groups,
+                                                     dev_target, target_stride, dev_weight, weight_stride, dev_cost, accumulate ? 1 : 0, stream));
+  }
   // the whole simulation state of UAVs [first, first + count) into dev_records[0 .. count-1] (device memory, 16-B aligned)
   void saveDevice(int first, int count, mrs_uav_snapshot_t* dev_records, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_save_device(s_, first, count, dev_records, stream));

@@ -653,6 +653,48 @@ int mrs_swarm_rollout_force_device(mrs_swarm_t* s, int32_t first, int32_t count,
                                    int32_t obs_every, int32_t force_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride,
                                    const void* dev_force, int32_t force_stride, uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream);
 
+/* ---- cost rollouts: a per-UAV quadratic cost summed inside the rollout (the number a sampling-based planner wants per sample) ----
+ * mrs_swarm_rollout_rate_device that, where it would write an observation row, compares the row with a target row and adds the weighted
+ * squared distance to one FP64 number per UAV.  Stands for the loop
+ *   for t in [0, n_steps):
+ *     if (t % cmd_every == 0)
+ *       mrs_swarm_set_input_device(s, first, count, mode, row block t / cmd_every of dev_cmd, dtype, cmd_stride, ext_stream);
+ *     mrs_swarm_step_n(s, dt, 1, 1);
+ *     if ((t + 1) % cost_every == 0)
+ *       rows[(t + 1) / cost_every - 1] = mrs_swarm_gather_device(s, first, count, groups, ..., MRS_DTYPE_F64, ...);
+ * followed, with E = n_steps / cost_every evaluations and w = the gather width of `groups`, by
+ *   c = accumulate ? dev_cost[k] : +0.0
+ *   for j in [0, E):
+ *     term = +0.0
+ *     for col in [0, w):                         (ascending, no column skipped)
+ *       d    = rows[j][k][col] - target[j][k or 0][col]
+ *       term = term + (weight[j or 0][col] * d) * d
+ *     c = c + term
+ *   dev_cost[k] = c
+ * for every UAV first + k of the range.  All of it is FP64, one rounding per operation and no fused multiply-add, in both arithmetic
+ * flavours; targets and weights have the commands' dtype (FP32 is widened exactly); dev_cost is always FP64; the residual is taken on
+ * the FP64 values of the row, not on a row rounded to FP32.  Nothing is special-cased: a non-finite target, a zero weight against a
+ * non-finite residual and a negative weight give what the lines above give, and the zeros of the MRS_OBS_RPM group past n_motors take
+ * part like any other column.
+ * Target row (j, k) starts at element ((size_t)j * count + k) * target_stride of dev_target; target_stride == 0: all UAVs share ONE row
+ * per evaluation and row j starts at element j * w (a dense [E, w] array).  Weight row j starts at element j * weight_stride of
+ * dev_weight; weight_stride == 0: one row of w elements serves every evaluation.  cost_every == n_steps is a terminal cost,
+ * cost_every == 1 a running cost; a heavier last weight row gives both.  Inside an evaluation block nothing is read from dev_target or
+ * dev_weight and dev_cost is not touched; no observation row is written at all.
+ * A UAV on hold is not stepped and adds one term of its unchanged state per evaluation; crashed UAVs are evaluated like any other;
+ * UAVs outside the range are stepped and own no element of dev_cost.  The result does not depend on how the call is cut into launches,
+ * and two calls over the halves of a horizon, the second with accumulate != 0, give the bits of one call over the whole.  Commands, the
+ * mode, the final state and everything else are the contract of mrs_swarm_rollout_rate_device (ONE stream fence per call; the call
+ * enters like a state call; refused on a sharded swarm), and so are its refusals, plus, as MRS_ERR_ARG with nothing changed:
+ * groups == 0, a NULL dev_target, dev_weight or dev_cost, cost_every < 1 or not dividing n_steps, a target_stride or weight_stride that
+ * is neither 0 nor at least w, and pointers that are not device memory of the swarm's device or too small for their rows (dev_cost:
+ * count doubles). */
+int mrs_swarm_rollout_cost_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every,
+                                  int32_t cost_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t groups,
+                                  const void* dev_target, int32_t target_stride, /* 0: one shared row per evaluation ([E, w]) */
+                                  const void* dev_weight, int32_t weight_stride, /* 0: one weight row for every evaluation */
+                                  double* dev_cost, int32_t accumulate, void* ext_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -340,10 +340,21 @@ int mrs_swarm_apply_force_device(mrs_swarm_t* s, int32_t first, int32_t count, c
   return fence_out(s, ext);
 }
 
+// what mrs_swarm_rollout_cost_device adds to a control-rate rollout (rollout_locked; obs_every is then the evaluation rate)
+struct CostArgs {
+  const void* target;
+  int32_t     target_stride;
+  const void* weight;
+  int32_t     weight_stride;
+  double*     cost;
+  int32_t     accumulate;
+};
+
 // the rollout entry points, under the caller's lock (MRS_ENTER's settle after the argument checks: a refused call launches nothing)
 static int rollout_locked(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every, int32_t obs_every,
                           int32_t force_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, const void* dev_force, int32_t force_stride,
-                          uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream, bool forced, const char* who) {
+                          uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream, bool forced, const char* who,
+                          const CostArgs* cost = nullptr) {
   int rc = check_range(s, first, count);
   if (rc) return rc;
   if (s->comm_world > 0) return fail(MRS_ERR_ARG, std::string(who) + ": not on a sharded swarm");
@@ -351,7 +362,8 @@ static int rollout_locked(mrs_swarm_t* s, int32_t first, int32_t count, int32_t 
   if ((rc = check_dtype(dtype))) return rc;
   if (n_steps < 1) return fail(MRS_ERR_ARG, "n_steps must be at least 1");
   if (cmd_every < 1 || n_steps % cmd_every != 0) return fail(MRS_ERR_ARG, "cmd_every must be at least 1 and divide n_steps");
-  if (obs_every < 1 || n_steps % obs_every != 0) return fail(MRS_ERR_ARG, "obs_every must be at least 1 and divide n_steps");
+  if (obs_every < 1 || n_steps % obs_every != 0)
+    return fail(MRS_ERR_ARG, cost ? "cost_every must be at least 1 and divide n_steps" : "obs_every must be at least 1 and divide n_steps");
   if (forced && (force_every < 1 || n_steps % force_every != 0)) return fail(MRS_ERR_ARG, "force_every must be at least 1 and divide n_steps");
   if (forced && force_stride < 3) return fail(MRS_ERR_ARG, "force_stride smaller than the three force components");
   if (forced && !dev_force) return fail(MRS_ERR_ARG, "dev_force: null pointer");
@@ -360,14 +372,33 @@ static int rollout_locked(mrs_swarm_t* s, int32_t first, int32_t count, int32_t 
   if (width > 0 && (cmd_stride < width || width < 1)) return fail(MRS_ERR_ARG, "cmd_stride too small for this mode");
   int32_t obs_width = 0;
   if ((rc = mrs_swarm_gather_width(groups, &obs_width))) return rc;
-  if (groups != 0u && obs_stride < obs_width) return fail(MRS_ERR_ARG, "obs_stride smaller than the width of the selected groups");
+  if (!cost && groups != 0u && obs_stride < obs_width) return fail(MRS_ERR_ARG, "obs_stride smaller than the width of the selected groups");
+  if (cost) {
+    if (groups == 0u) return fail(MRS_ERR_ARG, "no observation group selected: a cost needs columns");
+    if (!cost->target) return fail(MRS_ERR_ARG, "dev_target: null pointer");
+    if (!cost->weight) return fail(MRS_ERR_ARG, "dev_weight: null pointer");
+    if (!cost->cost) return fail(MRS_ERR_ARG, "dev_cost: null pointer");
+    if (cost->target_stride != 0 && cost->target_stride < obs_width)
+      return fail(MRS_ERR_ARG, "target_stride must be 0 (shared rows) or at least the width of the selected groups");
+    if (cost->weight_stride != 0 && cost->weight_stride < obs_width)
+      return fail(MRS_ERR_ARG, "weight_stride must be 0 (one row) or at least the width of the selected groups");
+  }
   if (count > 0) {
     // rows of the n_steps / cmd_every and n_steps / obs_every row blocks; 64-bit: blocks x count x stride can pass 2^31 elements
     const size_t cmd_rows = (size_t)(n_steps / cmd_every) * (size_t)count, obs_rows = (size_t)(n_steps / obs_every) * (size_t)count;
     if (width > 0 && (rc = check_device_ptr(s, dev_cmd, ((cmd_rows - 1) * (size_t)cmd_stride + (size_t)width) * dtype_bytes(dtype), "dev_cmd")))
       return rc;
-    if (groups != 0u && (rc = check_device_ptr(s, dev_obs, ((obs_rows - 1) * (size_t)obs_stride + (size_t)obs_width) * dtype_bytes(dtype), "dev_obs")))
+    if (!cost && groups != 0u &&
+        (rc = check_device_ptr(s, dev_obs, ((obs_rows - 1) * (size_t)obs_stride + (size_t)obs_width) * dtype_bytes(dtype), "dev_obs")))
       return rc;
+    if (cost) {  // (obs_rows: one target row per evaluation and UAV, unless the rows are shared)
+      const size_t evals = (size_t)(n_steps / obs_every), w = (size_t)obs_width;
+      const size_t tgt   = cost->target_stride ? (obs_rows - 1) * (size_t)cost->target_stride + w : evals * w;
+      const size_t wt    = cost->weight_stride ? (evals - 1) * (size_t)cost->weight_stride + w : w;
+      if ((rc = check_device_ptr(s, cost->target, tgt * dtype_bytes(dtype), "dev_target"))) return rc;
+      if ((rc = check_device_ptr(s, cost->weight, wt * dtype_bytes(dtype), "dev_weight"))) return rc;
+      if ((rc = check_device_ptr(s, cost->cost, (size_t)count * sizeof(double), "dev_cost"))) return rc;
+    }
     if (forced) {
       const size_t force_rows = (size_t)(n_steps / force_every) * (size_t)count;
       if ((rc = check_device_ptr(s, dev_force, ((force_rows - 1) * (size_t)force_stride + 3u) * dtype_bytes(dtype), "dev_force"))) return rc;
@@ -391,6 +422,22 @@ static int rollout_locked(mrs_swarm_t* s, int32_t first, int32_t count, int32_t 
   s->collide_since_step = false;
   s->p_valid            = false;  // (plain steps do not refresh the position records)
   const int variant = s->n_cascade > 0 ? 0 : 1;  // 0 all input modes | 1 model only
+  if (cost) {  // evaluations in place of observation rows: the kernels of rollout_cost_device.inc, whatever the rates are
+    if (count > 0 && !cost->accumulate) HIPCHK(hipMemsetAsync(cost->cost, 0, (size_t)count * sizeof(double), s->stream));  // (+0.0)
+    RolloutCostDev r{};
+    r.cmd = dev_cmd, r.target = cost->target, r.weight = cost->weight, r.cost = cost->cost;
+    r.first = first, r.count = count, r.cmd_stride = cmd_stride;
+    r.cmd_sched  = ((uint32_t)width | (dtype == MRS_DTYPE_F32 ? 32u : 0u)) << 24;
+    r.cost_sched = count > 0 ? groups << 24 : 0u;
+    r.mode_bits  = (uint32_t)mode << FLAG_MODE_SHIFT;
+    r.tgt_row = cost->target_stride, r.wt_row = cost->weight_stride;
+    r.tgt_blk = cost->target_stride ? (uint64_t)count * (uint64_t)cost->target_stride : (uint64_t)obs_width;
+    if (s->arith == MRS_ARITH_FAST)
+      HIPCHK(mrs_launch_rollout_cost_fast(s->view(), r, dt, n_steps, cmd_every, obs_every, variant, s->stream));
+    else
+      HIPCHK(mrs_launch_rollout_cost_literal(s->view(), r, dt, n_steps, cmd_every, obs_every, variant, s->stream));
+    return fence_out(s, ext);
+  }
   if (forced) {  // a third schedule: the kernels of rollout_force_device.inc, whatever the rates are
     if (count > 0) s->fext_active = true;  // (the loop's first mrs_swarm_apply_force_device: from here on the steps read the F_FEXT columns)
     RolloutForceDev r{};
@@ -450,6 +497,16 @@ int mrs_swarm_rollout_force_device(mrs_swarm_t* s, int32_t first, int32_t count,
   MRS_LOCK(s);
   return rollout_locked(s, first, count, mode, dt, n_steps, cmd_every, obs_every, force_every, dev_cmd, dtype, cmd_stride, dev_force, force_stride, groups,
                         dev_obs, obs_stride, ext_stream, true, "mrs_swarm_rollout_force_device");
+}
+
+int mrs_swarm_rollout_cost_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every,
+                                  int32_t cost_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t groups,
+                                  const void* dev_target, int32_t target_stride, const void* dev_weight, int32_t weight_stride, double* dev_cost,
+                                  int32_t accumulate, void* ext_stream) {
+  MRS_LOCK(s);
+  const CostArgs cost{dev_target, target_stride, dev_weight, weight_stride, dev_cost, accumulate};
+  return rollout_locked(s, first, count, mode, dt, n_steps, cmd_every, cost_every, 0, dev_cmd, dtype, cmd_stride, nullptr, 0, groups, nullptr, 0, ext_stream,
+                        false, "mrs_swarm_rollout_cost_device", &cost);
 }
 
 }  // extern "C"

@@ -49,6 +49,10 @@ extern "C" hipError_t mrs_launch_rollout_force_literal(SwarmDev sw, RolloutForce
                                                          int variant, hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_force_fast(SwarmDev sw, RolloutForceDev r, double dt, int n_steps, int cmd_every, int obs_every, int force_every,
                                                       int variant, hipStream_t st);
+extern "C" hipError_t mrs_launch_rollout_cost_literal(SwarmDev sw, RolloutCostDev r, double dt, int n_steps, int cmd_every, int cost_every, int variant,
+                                                        hipStream_t st);
+extern "C" hipError_t mrs_launch_rollout_cost_fast(SwarmDev sw, RolloutCostDev r, double dt, int n_steps, int cmd_every, int cost_every, int variant,
+                                                     hipStream_t st);
 extern "C" hipError_t mrs_launch_pid_probe_literal(const double*, const double*, const double*, const double*, const double*, double*, int, int, hipStream_t);
 extern "C" hipError_t mrs_launch_pid_probe_fast(const double*, const double*, const double*, const double*, const double*, double*, int, int, hipStream_t);
 extern "C" hipError_t mrs_launch_pid_update_probe_literal(const double*, double*, const double*, const double*, double*, int, hipStream_t);

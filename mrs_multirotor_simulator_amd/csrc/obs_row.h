@@ -70,3 +70,72 @@ __device__ __forceinline__ void mrs_obs_row(const Src& src, const uint32_t group
     for (int m = 0; m < MRS_MAX_MOTORS; m++) o[m] = (T)(m < nm ? src.rpm(m) : 0.0);
   }
 }
+
+// The weighted squared distance of the FP64 row of `groups` (the values mrs_obs_row<double> would write, in its column order) from the
+// target row tg[0 .. width) under the weights wt[0 .. width):
+//   term = +0.0;  for col ascending: d = row[col] - tg[col];  term = term + (wt[col] * d) * d
+// all of it FP64 and uncontracted; T = float targets and weights are widened exactly.  No column is skipped and nothing is
+// special-cased (a zero weight times a non-finite residual is what IEEE makes of it; the rpm group's zeros past n_motors take part).
+// Every value and every product goes through mrs_unfused: in the FAST unit the backend would otherwise fuse the multiply that produced
+// a value into the subtraction, or the last product into the sum.
+template <typename T, class Src>
+__device__ __forceinline__ double mrs_obs_row_cost(const Src& src, const uint32_t groups, const T* tg, const T* wt) {
+#pragma clang fp contract(off)
+  double term = 0.0;
+  double v[3], R[9];
+  const auto col = [&](double value, int c) {
+    const double d = mrs_unfused(value) - (double)tg[c];
+    term           = term + mrs_unfused(mrs_unfused((double)wt[c] * d) * d);
+  };
+  if (groups & (MRS_OBS_VEL | MRS_OBS_VEL_BODY)) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) v[c] = src.v(c);
+  }
+  if (groups & (MRS_OBS_VEL_BODY | MRS_OBS_ROT | MRS_OBS_QUAT)) {
+#pragma unroll
+    for (int c = 0; c < 9; c++) R[c] = src.R(c);
+  }
+  if (groups & MRS_OBS_POS) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) col(src.x(c), c);
+    tg += 3, wt += 3;
+  }
+  if (groups & MRS_OBS_VEL) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) col(v[c], c);
+    tg += 3, wt += 3;
+  }
+  if (groups & MRS_OBS_VEL_BODY) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) col(body_velocity(R, v, c), c);
+    tg += 3, wt += 3;
+  }
+  if (groups & MRS_OBS_ROT) {
+#pragma unroll
+    for (int c = 0; c < 9; c++) col(R[c], c);
+    tg += 9, wt += 9;
+  }
+  if (groups & MRS_OBS_QUAT) {
+    double q[4];
+    quat_from_matrix(R, q);
+#pragma unroll
+    for (int c = 0; c < 4; c++) col(q[c], c);
+    tg += 4, wt += 4;
+  }
+  if (groups & MRS_OBS_OMEGA) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) col(src.omega(c), c);
+    tg += 3, wt += 3;
+  }
+  if (groups & MRS_OBS_IMU) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) col(src.imu(c), c);
+    tg += 3, wt += 3;
+  }
+  if (groups & MRS_OBS_RPM) {
+    const int nm = src.n_motors();
+#pragma unroll
+    for (int m = 0; m < MRS_MAX_MOTORS; m++) col(m < nm ? src.rpm(m) : 0.0, m);
+  }
+  return term;
+}

@@ -4,3 +4,4 @@
 #include "rollout_device.inc"
 #include "rollout_rate_device.inc"
 #include "rollout_force_device.inc"
+#include "rollout_cost_device.inc"

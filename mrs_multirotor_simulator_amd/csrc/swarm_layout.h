@@ -149,6 +149,24 @@ struct RolloutForceDev {
   uint32_t    force_sched;   // MRS_RO_S0 / P / M | 3 << 24.  Width 0: no force row in this launch
 };
 
+// ---- one launch of a cost rollout (mrs_swarm_rollout_cost_device, rollout_cost_device.inc) ----
+// RolloutRateDev's command side, and in place of observation rows an evaluation schedule: after the launch's j-th due sub-step the
+// observation row of UAV first + k is compared with target row (j, k) under weight row j, and the term is added to cost[k].
+struct RolloutCostDev {
+  const void* cmd;
+  int32_t     first, count;
+  int32_t     cmd_stride;
+  uint32_t    cmd_sched;   // as RolloutRateDev's (the dtype bit serves commands, targets and weights)
+  uint32_t    cost_sched;  // MRS_RO_S0 / P / M | groups << 24.  Groups 0: no evaluation in this launch
+  uint32_t    mode_bits;
+  const void* target;      // target rows of the launch's FIRST due evaluation; row (j, k) at element j * tgt_blk + k * tgt_row behind it
+  const void* weight;      // weight rows likewise; row j at element j * wt_row
+  double*     cost;        // cost[k]: the running sum of UAV first + k, read and written by its lane at every due sub-step
+  uint64_t    tgt_blk;     // count * target_stride, or the row width when all UAVs share one target row per evaluation
+  int32_t     tgt_row;     // target_stride, or 0: shared targets
+  int32_t     wt_row;      // weight_stride, or 0: one weight row for every evaluation
+};
+
 // 48-byte record exchanged for the collision pass (single- and multi-GPU): everything
 // MultirotorSimulator::handleCollisions reads of the partner UAV (src/multirotor_simulator.cpp:339-350)
 struct PosRecord {

@@ -116,6 +116,7 @@ ABI_SYMBOLS = [
     "mrs_swarm_rollout_rate_device",
     "mrs_swarm_apply_force_device",
     "mrs_swarm_rollout_force_device",
+    "mrs_swarm_rollout_cost_device",
 ]
 
 # device-resident callers (mrs_swarm_*_device): row element types and the observation groups of mrs_swarm_gather_device, in bit order
@@ -350,6 +351,8 @@ def load_library():
         "mrs_swarm_rollout_rate_device": [vp, i32, i32, i32, C.c_double, i32, i32, i32, vp, i32, i32, C.c_uint32, vp, i32, vp],
         "mrs_swarm_apply_force_device": [vp, i32, i32, vp, i32, i32, vp],
         "mrs_swarm_rollout_force_device": [vp, i32, i32, i32, C.c_double, i32, i32, i32, i32, vp, i32, i32, vp, i32, C.c_uint32, vp, i32, vp],
+        "mrs_swarm_rollout_cost_device": [vp, i32, i32, i32, C.c_double, i32, i32, i32, vp, i32, i32, C.c_uint32, vp, i32, vp, i32, vp, i32,
+                                          vp],
     }
     for name, args in sig.items():
         if os.environ.get("MRS_SWARM_LIB") and not hasattr(L, name):
@@ -845,6 +848,13 @@ class Swarm:
                                                    int(obs_every), int(force_every), dev_cmd or None, int(dtype), int(cmd_stride),
                                                    dev_force or None, int(force_stride), C.c_uint32(int(groups)), dev_obs or None,
                                                    int(obs_stride), ext_stream or None))
+
+    def rollout_cost_device(self, first, count, mode, dt, n_steps, cmd_every, cost_every, dev_cmd, dtype, cmd_stride, groups, dev_target,
+                            target_stride, dev_weight, weight_stride, dev_cost, accumulate, ext_stream):
+        _check(_lib.mrs_swarm_rollout_cost_device(self._h, int(first), int(count), int(mode), C.c_double(float(dt)), int(n_steps), int(cmd_every),
+                                                  int(cost_every), dev_cmd or None, int(dtype), int(cmd_stride), C.c_uint32(int(groups)),
+                                                  dev_target or None, int(target_stride), dev_weight or None, int(weight_stride),
+                                                  dev_cost or None, int(bool(accumulate)), ext_stream or None))
 
     def get_diag(self):
         d = Diag()

@@ -198,6 +198,69 @@ def rollout(swarm, mode, commands, dt, groups=OBS_POS | OBS_VEL | OBS_QUAT, firs
     return out[:, :, :owidth] if out.shape[2] > owidth else out
 
 
+def rollout_cost(swarm, mode, commands, dt, groups, targets, weights, first=0, hold=1, cost_every=None, out=None, accumulate=False):
+    """rollout(hold=hold, obs_every=cost_every) that returns one FP64 number per UAV instead of row blocks: after every `cost_every` steps
+    (default: `hold`; B * hold: a terminal cost) the FP64 observation row of `groups` of UAV first + k is compared with its target row, and
+    `sum over columns of (weight * d) * d`, d = row - target, is added to the UAV's cost (mrs_swarm_rollout_cost_device; the arithmetic is
+    FP64, unfused, columns ascending, evaluations in order, in both flavours).  commands: as in rollout.  With E = B * hold // cost_every
+    evaluations and w = gather_width(groups): targets is [E, count, >= w] (a row per UAV) or [E, 1, w] (one dense row per evaluation for
+    all UAVs); weights is [E, >= w] (a row per evaluation: a heavier last row is a terminal cost) or [1, >= w]; both of the commands'
+    dtype.  out: a float64 [count] vector, allocated when None; accumulate=True adds to what `out` holds (two calls over the halves of a
+    horizon give the bits of one call), else it is overwritten.  Returns out.  No observation row is written."""
+    dev = swarm.device()
+    if not isinstance(commands, torch.Tensor) or commands.dim() != 3:
+        raise ValueError("commands must be a [T, count, width] tensor")
+    hold = int(hold)
+    if hold < 1:
+        raise ValueError(f"hold must be at least 1, got {hold}")
+    code = _dtype_code(commands.dtype)
+    blocks, count = commands.shape[0], commands.shape[1]
+    steps = blocks * hold
+    every = hold if cost_every is None else int(cost_every)
+    if every < 1 or steps % every != 0:
+        raise ValueError(f"cost_every must be at least 1 and divide the {steps} steps of the call, got {every}")
+    evals = steps // every
+    width = command_width(mode, commands.shape[2])
+    cstride = _check_steps(commands, "commands", None, count, width, commands.dtype, dev)
+    if mode == ACTUATOR_CMD and count > 1 and cstride != commands.shape[2]:
+        raise ValueError("actuator rows must be dense (row stride == number of motors)")
+    w = gather_width(groups)
+    if w == 0:
+        raise ValueError("groups must select at least one observation group: a cost needs columns")
+    for name, t in (("targets", targets), ("weights", weights)):
+        if isinstance(t, torch.Tensor) and t.dtype != commands.dtype:
+            raise ValueError(f"{name} has dtype {t.dtype}, the commands {commands.dtype}: one dtype serves commands, targets and weights")
+    if (not isinstance(targets, torch.Tensor) or targets.dim() != 3 or targets.shape[0] != evals or targets.shape[1] not in (1, count)
+            or targets.shape[2] < w):
+        raise ValueError(f"targets: expected a [{evals}, {count} or 1, >= {w}] tensor, got "
+                         f"{tuple(targets.shape) if isinstance(targets, torch.Tensor) else type(targets).__name__}")
+    if targets.shape[1] == 1:  # one row per evaluation: its stride is that of the first dimension
+        tstride = check_tensor(targets[:, 0, :], evals, w, commands.dtype, dev)
+        if count != 1:
+            if evals > 1 and tstride != w:
+                raise ValueError(f"targets: shared target rows must be dense, [{evals}, 1, {w}], got a row stride of {tstride}")
+            tstride = 0
+    else:
+        tstride = _check_steps(targets, "targets", evals, count, w, commands.dtype, dev)
+    if not isinstance(weights, torch.Tensor) or weights.dim() != 2 or weights.shape[0] not in (1, evals):
+        raise ValueError(f"weights: expected a [{evals} or 1, >= {w}] tensor, got "
+                         f"{tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights).__name__}")
+    wstride = check_tensor(weights, weights.shape[0], w, commands.dtype, dev)
+    if weights.shape[0] == 1:
+        wstride = 0
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs the `out` vector it adds to")
+        out = torch.empty(count, dtype=torch.float64, device=torch.device("cuda", dev))
+    if isinstance(out, torch.Tensor) and out.dtype != torch.float64:
+        raise ValueError(f"out has dtype {out.dtype}: the cost vector is always torch.float64")
+    check_tensor(out, count, None, torch.float64, dev)
+    cptr = commands.data_ptr() if width > 0 and count > 0 else 0
+    swarm.rollout_cost_device(first, count, mode, dt, steps, hold, every, cptr, code, cstride, groups, targets.data_ptr(), tstride,
+                              weights.data_ptr(), wstride, out.data_ptr(), bool(accumulate), _stream(dev))
+    return out
+
+
 def crashed(swarm, first=0, count=None, out=None):
     """UavSystem::hasCrashed of UAVs [first, first + count) as a bool tensor on the swarm's device"""
     count = _count(swarm, first, count)

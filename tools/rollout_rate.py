@@ -29,6 +29,17 @@ newtons per axis) is applied every N steps (mrs_swarm_rollout_force_device).  Th
   loop     set_input every `hold` steps, apply_force every N steps, step_n(dt, to the next event), gather every `obs_every` steps
 `force`, `force1` and `loop` apply the same forces: in LITERAL they must end bit-identical (rows and state), and differ from `rate`.
 `forms` selects among rate,force,force1,loop (default: all four).
+
+With `--cost` (anywhere on the command line) the tool measures the COST rollout (mrs_swarm_rollout_cost_device): a quadratic tracking cost
+per UAV, evaluated every `cost_every` steps against one shared FP32 target row per evaluation under one shared weight row.  Defaults:
+T = 320, modes ACTUATOR_CMD,VELOCITY_HDG_CMD, arith literal,fast, hold 10, and the ninth argument is a list of cost_every (1,10).  The
+same T steps three ways, alternating:
+  b     tensors.rollout(cmd, dt, out=T / cost_every row blocks, hold=hold, obs_every=cost_every)   (the rows a caller needs for the cost)
+  b+    b, then the torch reduction of those rows to one number per UAV: ((rows - target)**2 * weight).sum over evaluations and columns
+  f     tensors.rollout_cost(cmd, dt, targets, weights, hold=hold, cost_every=cost_every)
+and prints the bytes each form moves between the kernels and the caller's tensors.  A fourth swarm replays the horizon with FP64 rows, in
+chunks of 40 steps, and the restatement of the ABI comment is applied to them in torch (element-wise FP64 kernels, one rounding each):
+f's cost must equal it bit for bit, and the final states of b and f must agree.
 """
 import os
 import sys
@@ -54,6 +65,9 @@ def commands(mode, n, steps, rng):
 def main():
     import torch
     from mrs_multirotor_simulator_amd import tensors as T
+    cost = "--cost" in sys.argv
+    if cost:
+        sys.argv.remove("--cost")
     force_every = None
     if "--force-every" in sys.argv:
         k = sys.argv.index("--force-every")
@@ -65,6 +79,14 @@ def main():
     modes = sys.argv[4].split(",") if len(sys.argv) > 4 else ["ACTUATOR_CMD", "ATTITUDE_RATE_CMD", "VELOCITY_HDG_CMD"]
     forms = sys.argv[5].split(",") if len(sys.argv) > 5 else ["loop", "rollout"]
     arith = sys.argv[6] if len(sys.argv) > 6 else "literal"
+    if cost:
+        assert force_every is None, "--cost and --force-every exclude each other (no force schedule inside a cost rollout)"
+        hold = int(sys.argv[7]) if len(sys.argv) > 7 else 10
+        for ar in (sys.argv[6] if len(sys.argv) > 6 else "literal,fast").split(","):
+            for every in [int(e) for e in (sys.argv[8] if len(sys.argv) > 8 else "1,10").split(",")]:
+                main_cost(sizes, int(sys.argv[2]) if len(sys.argv) > 2 else 320, reps,
+                          modes if len(sys.argv) > 4 else ["ACTUATOR_CMD", "VELOCITY_HDG_CMD"], ar, hold, every)
+        return None
     if len(sys.argv) > 7:
         hold = int(sys.argv[7])
         every = int(sys.argv[8]) if len(sys.argv) > 8 else hold
@@ -318,6 +340,92 @@ def main_force(sizes, steps, reps, modes, forms, arith, hold, every, fhold):
                     assert bits_equal(obs["loop"], obs["force"]), f"{n} {mode_name}: rows of loop and force differ"
                     same_state("loop", "force")
                     line += "  loop == force"
+            print(line, flush=True)
+            for g in swarms.values():
+                g.close()
+
+
+def main_cost(sizes, steps, reps, modes, arith, hold, every):
+    import torch
+    from mrs_multirotor_simulator_amd import tensors as T
+    assert hold >= 1 and every >= 1 and steps % hold == 0 and steps % every == 0, "hold and cost_every must divide T"
+    groups = T.OBS_POS | T.OBS_VEL | T.OBS_QUAT
+    ow = T.gather_width(groups)
+    rng = np.random.default_rng(5)
+    forms = ["b", "b+", "f"]
+    E = steps // every
+    chunk = next(c for c in (40, 20, 10, hold * every) if c % hold == 0 and c % every == 0 and steps % c == 0)
+    print(f"cost rollout of T = {steps} steps, hold {hold}, cost_every {every}, FP32 commands, shared FP32 targets and weights, POS|VEL|QUAT, x500, "
+          f"{arith.upper()}; {reps} rounds after a warm-up, alternating")
+    for n in sizes:
+        st, _ = bench.make_inputs(n, "position+collisions", seed=3)
+        p = M.model_params("x500", ground_enabled=True, ground_z=0.0)
+        for mode_name in modes:
+            mode = getattr(M, mode_name)
+            swarms = {}
+            for f in forms + ["check"]:
+                g = M.Swarm(n, arith=M.ARITH_FAST if arith == "fast" else M.ARITH_LITERAL)
+                g.construct(0, n, p)
+                g.set_state(0, n, st["x"], st["v"], st["R"], st["omega"], st["motor_rpm"])
+                swarms[f] = g
+            dev = torch.device("cuda", swarms["b"].device())
+            cmd = torch.tensor(commands(mode, n, steps // hold, rng), dtype=torch.float32, device=dev)
+            tgt = torch.tensor(rng.normal(0.0, 2.0, (E, 1, ow)), dtype=torch.float32, device=dev)
+            wt = torch.tensor(rng.uniform(0.1, 2.0, (1, ow)), dtype=torch.float32, device=dev)
+            obs = {f: torch.empty((E, n, ow), dtype=torch.float32, device=dev) for f in ("b", "b+")}
+            cost = {f: torch.empty(n, dtype=torch.float64 if f == "f" else torch.float32, device=dev) for f in ("b+", "f")}
+
+            def run(form):
+                g = swarms[form]
+                if form == "f":
+                    T.rollout_cost(g, mode, cmd, DT, groups, tgt, wt, hold=hold, cost_every=every, out=cost["f"])
+                    return
+                T.rollout(g, mode, cmd, DT, groups, out=obs[form], hold=hold, obs_every=every)
+                if form == "b+":
+                    d = obs[form] - tgt
+                    torch.sum(d * d * wt, dim=(0, 2), out=cost["b+"])
+
+            # the reference first (the three timed forms replay this horizon again and again; the check is against their FIRST run):
+            # FP64 rows in chunks, the restatement in element-wise FP64 torch kernels
+            want = torch.zeros(n, dtype=torch.float64, device=dev)
+            t64, w64 = tgt.double(), wt.double()
+            for c0 in range(0, steps, chunk):
+                rows = T.rollout(swarms["check"], mode, cmd[c0 // hold:(c0 + chunk) // hold].double(), DT, groups, hold=hold, obs_every=every)
+                for j in range(chunk // every):
+                    term = torch.zeros(n, dtype=torch.float64, device=dev)
+                    for col in range(ow):
+                        d = rows[j, :, col] - t64[c0 // every + j, 0, col]
+                        term = term + (w64[0, col] * d) * d
+                    want = want + term
+                del rows
+            for f in forms:  # warm-up: code objects, the type table, torch kernels — and the run that is checked
+                run(f)
+            torch.cuda.synchronize(dev)
+            nan = torch.isnan(want)
+            assert torch.equal(torch.isnan(cost["f"]), nan) and torch.equal(cost["f"][~nan].view(torch.int64), want[~nan].view(torch.int64)), \
+                f"{n} {mode_name}: the cost is not the restatement on the FP64 rows"
+            for fa, fb in (("b", "f"), ("check", "f")):
+                a, b = swarms[fa].get_states(), swarms[fb].get_states()
+                for fld in a.dtype.names:
+                    assert np.array_equal(a[fld].view(np.uint64) if a[fld].dtype == np.float64 else a[fld],
+                                          b[fld].view(np.uint64) if b[fld].dtype == np.float64 else b[fld]), f"{n} {mode_name}: {fld} differs ({fa} / {fb})"
+            times = {f: [] for f in forms}
+            for _ in range(reps):
+                for f in forms:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    run(f)
+                    e1.record()
+                    e1.synchronize()
+                    times[f].append(e0.elapsed_time(e1) * 1e3 / steps)
+            line = f"  {n:>8d} UAVs  {mode_name:18s}"
+            for f in forms:
+                line += f"  {f} {float(np.median(times[f])):7.2f} us/step ({min(times[f]):.2f}-{max(times[f]):.2f})"
+            cmd_b, row_b = (steps // hold) * n * cmd.shape[2] * 4, E * n * ow * 4
+            line += f"  bytes b {(cmd_b + row_b) / 1e6:.1f} MB, b+ {(cmd_b + 4 * row_b + n * 4) / 1e6:.1f} MB (rows written, read, d*d*w written and read)"
+            line += f", f {(cmd_b + 2 * E * n * 8 + 2 * E * ow * 4) / 1e6:.1f} MB (cost element read and written per evaluation)"
+            line += "  cost == restatement, states agree"
+            line += "  f <= b" if np.median(times["f"]) <= np.median(times["b"]) else "  F SLOWER THAN B"
             print(line, flush=True)
             for g in swarms.values():
                 g.close()

@@ -317,7 +317,8 @@ int mrs_swarm_comm_init_loopback(mrs_swarm_t* s, mrs_loopback_group_t* g, int32_
  *   mrs_swarm_debug_chaos : this rank's host sleeps a random 0..max_sleep_us before every launch and, at random, decides on the
  *       stall / warning words as it read them one launch earlier — host skew the protocol must tolerate (0 switches it off);
  *   mrs_swarm_get_split_stats : ticks this rank ran in the split form (interior and boundary launches on two streams) and the
- *       64-UAV blocks its boundary launch covers since the last search */
+ *       64-UAV blocks its boundary launch covers since the last search; on a swarm that is not sharded, the steps that
+ *       mrs_swarm_step_n launched as two half-swarm launches on two streams */
 int mrs_loopback_group_set_rendezvous(mrs_loopback_group_t* g, int32_t on);
 int mrs_swarm_debug_chaos(mrs_swarm_t* s, int32_t max_sleep_us, uint64_t seed);
 int mrs_swarm_get_split_stats(mrs_swarm_t* s, int64_t* split_ticks, int64_t* boundary_blocks);

@@ -44,6 +44,7 @@ int launch_step(mrs_swarm* s, double dt, int substeps, bool imu_dead) {
 // one step as two independent half-swarm launches, one per stream (between fork_streams and join_streams)
 int launch_step_split(mrs_swarm* s, double dt, int substeps, bool imu_dead) {
   s->region_launches++;
+  s->x_split_ticks++;  // (mrs_swarm_get_split_stats: a sharded swarm never comes here, its own split ticks count there)
   const int nb = (s->n + 63) / 64, half = nb / 2;
   int rc = launch_part(s, dt, substeps, 0, half, 1, s->stream, imu_dead);
   if (rc) return rc;

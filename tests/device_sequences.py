@@ -1,0 +1,658 @@
+"""Random call sequences over the whole call surface, the device-resident calls included (test_random_device_sequences*.py).
+
+`run_sequence` is the frame of test_random_sequences_gpu.py (its fleets, its 18 host calls, its compare after every few calls) with the
+device-resident calls of include/mrs_swarm.h mixed in: commands, forces, observation rows, crash flags, masked resets, snapshot round
+trips, clone swaps, nearest-neighbour rows, the four rollout entry points and the pipelined downloads.  The oracle and plain numpy are
+the only references.  The product is reached through a `Device` (torch tensors on the swarm's GPU) or a `Stub` that checks every argument
+tuple against the header's rules and records it: the generator draws the same numbers for both, so the CPU test of the generator speaks
+for the GPU test's sequences.
+
+Steps are budgeted: a sequence never takes more than `cap` steps (rollout steps included), because the tolerances of the compare were
+set for the step totals of test_random_sequences_gpu.py; a stepping call that no longer fits is drawn shorter or becomes a gather."""
+import contextlib
+from collections import Counter
+
+import numpy as np
+
+import helpers
+from helpers import FIELD_FLOOR, Pair
+from oracle import oracle_swarm as O
+from test_device_io_gpu import _runs
+from test_nearest_gpu import compare_with_numpy
+from test_random_sequences_gpu import DT, build_fleet, check, compare_outputs, host_op, payload, rng_range
+from test_rollout_cost_gpu import restate
+
+N_UAVS = 150
+N_ITER = 50        # calls of a sequence
+N_ITER_LONG = 25   # ... of one whose rollout of LONG_HORIZON steps uses the step budget up
+# observation groups in bit order: (name, width, the field of helpers.FIELD_FLOOR whose floor the group takes)
+GROUPS = (("x", 3, "x"), ("v", 3, "v"), ("velocity_body", 3, "v"), ("R", 9, "R"), ("quat", 4, "R"), ("omega", 3, "omega"), ("imu", 3, "imu"),
+          ("rpm", 8, "motor_rpm"))
+QUAT_BIT = 4
+WIDTH = {0: 0, 1: 8, 2: 4, 3: 4, 4: 10, 5: 5, 6: 4, 7: 4, 8: 4, 9: 4, 10: 4}  # command columns per mode (ACTUATOR: 8 serve every airframe)
+HORIZONS = (1, 5, 12, 24)
+LONG_HORIZON = 66  # kRolloutMaxSteps + 2: one step-kernel launch past the cap
+BRANCH_EPS = 1e-9
+
+# op kinds: 0 .. 17 are the host calls of test_random_sequences_gpu.host_op
+(DEV_SET_INPUT, DEV_FORCE, GATHER, CRASHED, RESET, SNAPSHOT, CLONE, NEAREST, ROLL_PLAIN, ROLL_RATE, ROLL_FORCE, ROLL_COST, ASYNC_OUTPUTS, ASYNC_POSES,
+ FAST_UAVS) = range(18, 33)
+N_OPS = 33
+TICK_LONG = 33  # never drawn: the run of ticks that follows FAST_UAVS
+MODEL_ALL = 34  # never drawn: ACTUATOR_CMD for the whole swarm, which puts the step launches on the model-only kernels
+OP_NAMES = {**{k: f"host{k}" for k in range(18)}, DEV_SET_INPUT: "dev_set_input", DEV_FORCE: "dev_force", GATHER: "gather", CRASHED: "crashed",
+            RESET: "reset", SNAPSHOT: "snapshot", CLONE: "clone", NEAREST: "nearest", ROLL_PLAIN: "rollout", ROLL_RATE: "rollout_rate",
+            ROLL_FORCE: "rollout_force", ROLL_COST: "rollout_cost", ASYNC_OUTPUTS: "async_outputs", ASYNC_POSES: "async_poses", FAST_UAVS: "fast_uavs",
+            TICK_LONG: "tick_long", MODEL_ALL: "model_all"}
+ROLLOUTS = (ROLL_PLAIN, ROLL_RATE, ROLL_FORCE, ROLL_COST)
+STALL_FOLLOWERS = (ASYNC_OUTPUTS, ASYNC_POSES, GATHER, NEAREST, DEV_SET_INPUT)
+# calls that enter through MRS_ENTER_COMMANDS (or do not enter at all): a collision tick that is pending stays pending across them
+KEEP_PENDING = (0, 1, 2, 3, 9, 15, DEV_SET_INPUT, GATHER, ASYNC_OUTPUTS, ASYNC_POSES)
+
+
+def gather_width(groups):
+    return sum(w for b, (_, w, _) in enumerate(GROUPS) if groups >> b & 1)
+
+
+def group_floors(groups):
+    """the floor of every column of a row of `groups`"""
+    return np.concatenate([np.full(w, FIELD_FLOOR[f]) for b, (_, w, f) in enumerate(GROUPS) if groups >> b & 1])
+
+
+def ref_rows(o, first, count, groups):
+    """the FP64 observation rows [count, gather_width(groups)] of the oracle's UAVs, and their R [count, 3, 3]"""
+    st, out, imu = o.get_state(first, count), o.get_outputs(first, count), o.get_imu(first, count)
+    nm = np.array([o.get_params(first + k).n_motors for k in range(count)])
+    rpm = np.where(np.arange(O.MAX_MOTORS)[None, :] < nm[:, None], st["motor_rpm"], 0.0)
+    parts = (st["x"], st["v"], out["velocity_body"], st["R"].reshape(count, 9), out["orientation"], st["omega"], imu, rpm)
+    return np.concatenate([a for b, a in enumerate(parts) if groups >> b & 1], axis=1), st["R"]
+
+
+def near_quat_branch(R):
+    """True where R [.., 3, 3] is within BRANCH_EPS of a branch boundary of Eigen's Quaterniond(Matrix3d): a trace of 0, or, where the
+    diagonal decides (trace <= 0), a tie of its two largest entries.  There the quaternion is defined up to its overall sign only."""
+    d = np.diagonal(R, axis1=-2, axis2=-1)
+    tr = (d[..., 0] + d[..., 1]) + d[..., 2]
+    s = np.sort(d, axis=-1)
+    return (np.abs(tr) < BRANCH_EPS) | ((tr <= BRANCH_EPS) & (s[..., 2] - s[..., 1] < BRANCH_EPS))
+
+
+def compare_rows(got, want, R, groups, rtol, f32, what):
+    """observation rows of the product against the oracle's, every group on its own scale: per UAV, max |difference| over the group's
+    columns <= tol * max(max |reference| over them, the group's floor); tol = rtol, plus one float rounding 2^-24 for FP32 rows.
+    NaN / inf patterns must agree.  Returns the number of quaternions compared up to their sign (near_quat_branch)."""
+    W = gather_width(groups)
+    got, want, R = np.asarray(got, dtype=np.float64).reshape(-1, W), np.asarray(want, dtype=np.float64).reshape(-1, W), np.asarray(R).reshape(-1, 3, 3)
+    assert got.shape == want.shape, f"{what}: shape {got.shape} != {want.shape}"
+    tol = rtol + (2.0 ** -24 if f32 else 0.0)
+    col = sign_cases = 0
+    for b, (name, w, f) in enumerate(GROUPS):
+        if not groups >> b & 1:
+            continue
+        a, r = got[:, col:col + w], want[:, col:col + w]
+        col += w
+        bad = ~np.isfinite(r)
+        assert np.array_equal(np.isnan(a), np.isnan(r)), f"{what}: {name}: NaN pattern differs"
+        assert np.array_equal(a[bad & ~np.isnan(r)], r[bad & ~np.isnan(r)]), f"{what}: {name}: inf pattern differs"
+        with np.errstate(invalid="ignore"):
+            diff = np.where(bad, 0.0, np.abs(a - r)).max(axis=1)
+            if b == QUAT_BIT:
+                near = near_quat_branch(R)
+                sign_cases += int(near.sum())
+                diff = np.where(near, np.minimum(diff, np.where(bad, 0.0, np.abs(a + r)).max(axis=1)), diff)
+        scale = np.maximum(np.where(bad, 0.0, np.abs(r)).max(axis=1), FIELD_FLOOR[f])
+        err = diff / scale
+        i = int(np.argmax(err))
+        assert err[i] <= tol, f"{what}: {name}: row {i} is off by {err[i]:.3e} > {tol:.3e} relative to its own scale"
+    return sign_cases
+
+
+def cost_bound(rows, targets, weights, groups, rtol):
+    """first-order bound of the cost restatement's change when every row value moves by delta = rtol * max(|value|, its group's floor):
+    sum over evaluations and columns of |w| * (2 |d| delta + delta^2), d = row - target"""
+    rows = np.asarray(rows, dtype=np.float64)
+    tg, wt = np.asarray(targets).astype(np.float64), np.asarray(weights).astype(np.float64)
+    E, count, w = rows.shape
+    wt = np.broadcast_to(wt[:, None, :w], (E, count, w))  # (one row serves every evaluation)
+    with np.errstate(invalid="ignore", over="ignore"):
+        delta = rtol * np.maximum(np.abs(rows), group_floors(groups)[None, None, :])
+        d = np.abs(rows - tg[:, :, :w])
+        return (np.abs(wt) * (2.0 * d * delta + delta * delta)).sum(axis=(0, 2))
+
+
+# ---- the product side --------------------------------------------------------------------------------------------------------------
+
+class RecordingSwarm:
+    """stands where the product's Swarm stands when a sequence runs against the oracle alone: every call is recorded by name"""
+
+    def __init__(self, n, o):
+        self.n, self.o, self.calls = n, o, []
+
+    def input_staging(self, count, stride):
+        self.calls.append("input_staging")
+        return np.zeros((count, stride))
+
+    def get_outputs_view(self, first, count):  # (so that host call 16 has something to compare: the oracle with itself)
+        self.calls.append("get_outputs_view")
+        return self.o.get_outputs(first, count)
+
+    def __getattr__(self, name):
+        def call(*a, **kw):
+            self.calls.append(name)
+        return call
+
+
+class StubPair(Pair):
+    """a Pair whose product is a RecordingSwarm"""
+
+    def __init__(self, M, n):
+        self.M, self.n = M, n
+        self.o = O.OracleSwarm(n)
+        self.g = RecordingSwarm(n, self.o)
+
+    def compare(self, *a, **kw):
+        return 0.0
+
+
+class Stub:
+    """the device-resident calls as argument checks: what include/mrs_swarm.h and tensors.py accept, asserted; every tuple is recorded"""
+    real = False
+
+    def __init__(self, p):
+        self.p, self.calls, self.open = p, [], {"outputs": [], "poses": []}
+        self.next_ticket = 0
+
+    def _range(self, first, count):
+        assert 0 <= first and count >= 1 and first + count <= self.p.n, (first, count)
+
+    def _motors(self, first, count):
+        return max(self.p.o.get_params(first + k).n_motors for k in range(count))
+
+    def _commands(self, mode, rows, first, pad):
+        count, w = rows.shape[-2], rows.shape[-1]
+        self._range(first, count)
+        assert 0 <= mode <= 10 and pad >= 0
+        if mode == O.ACTUATOR_CMD:
+            assert pad == 0 and self._motors(first, count) <= w <= O.MAX_MOTORS, "actuator rows: dense, and as wide as n_motors"
+        else:
+            assert w >= max(WIDTH[mode], 1)
+        assert np.isfinite(rows).all()
+
+    def set_input(self, mode, rows, first, f32, pad):
+        assert rows.ndim == 2
+        self._commands(mode, rows, first, pad)
+        self.calls.append(("set_input", mode, rows.shape, first, f32, pad))
+
+    def apply_force(self, rows, first, f32, pad):
+        assert rows.ndim == 2 and rows.shape[1] == 3 and pad >= 0
+        self._range(first, rows.shape[0])
+        self.calls.append(("apply_force", rows.shape, first, f32, pad))
+
+    def gather(self, groups, first, count, f32, pad):
+        self._range(first, count)
+        assert 1 <= groups <= 255 and pad >= 0
+        self.calls.append(("gather", groups, first, count, f32, pad))
+
+    def crashed(self, first, count):
+        self._range(first, count)
+        self.calls.append(("crashed", first, count))
+
+    def reset(self, mask, pos, heading, takeoff, first, f32, u8):
+        count = len(mask)
+        self._range(first, count)
+        assert mask.dtype == bool and mask.any() and pos.shape == (count, 3) and (heading is None or heading.shape == (count,))
+        self.calls.append(("reset", int(mask.sum()), first, count, heading is not None, takeoff, f32, u8))
+
+    def save_load(self, first, count, index):
+        self._range(first, count)
+        if index is not None:
+            assert index.shape == (count,) and ((index == -1) | (index == np.arange(count))).all()
+        self.calls.append(("save_load", first, count, None if index is None else int((index < 0).sum())))
+
+    def clone_swap(self):
+        assert not self.open["outputs"] and not self.open["poses"], "a ticket would outlive its swarm"
+        self.calls.append(("clone",))
+
+    def nearest(self, k, radius, fields, first, count, f32):
+        self._range(first, count)
+        assert 1 <= k <= 32 and radius > 0 and 0 <= fields <= 31
+        self.calls.append(("nearest", k, radius, fields, first, count, f32))
+
+    def _rates(self, steps, hold, every, blocks):
+        assert steps >= 1 and hold >= 1 and every >= 1 and steps % hold == 0 and steps % every == 0 and blocks * hold == steps, (steps, hold, every, blocks)
+
+    def rollout(self, mode, cmd, first, groups, hold, every, forces, fhold, f32, pads):
+        assert cmd.ndim == 3
+        self._commands(mode, cmd, first, pads[0])
+        steps = cmd.shape[0] * hold
+        self._rates(steps, hold, every, cmd.shape[0])
+        assert 0 <= groups <= 255 and min(pads) >= 0
+        if forces is not None:
+            assert forces.shape[1:] == (cmd.shape[1], 3) and fhold >= 1 and forces.shape[0] * fhold == steps, (forces.shape, fhold, steps)
+        self.calls.append(("rollout", mode, cmd.shape, first, groups, hold, every, None if forces is None else (forces.shape, fhold), f32, pads))
+
+    def rollout_cost(self, mode, cmd, first, groups, targets, weights, hold, every, start, f32, pads):
+        assert cmd.ndim == 3
+        self._commands(mode, cmd, first, pads[0])
+        steps, count = cmd.shape[0] * hold, cmd.shape[1]
+        self._rates(steps, hold, every, cmd.shape[0])
+        E, w = steps // every, gather_width(groups)
+        assert 1 <= groups <= 255 and targets.shape == (E, count, w) and weights.shape in ((E, w), (1, w)) and min(pads) >= 0
+        assert start is None or start.shape == (count,)
+        self.calls.append(("rollout_cost", mode, cmd.shape, first, groups, weights.shape[0], hold, every, start is not None, f32, pads))
+
+    def async_issue(self, kind, first, count):
+        self._range(first, count)
+        self.open[kind].append(self.next_ticket)
+        assert len(self.open[kind]) <= 2, "more than two tickets of one kind"
+        self.calls.append(("async_issue", kind, first, count))
+        self.next_ticket += 1
+        return self.next_ticket - 1
+
+    def async_wait(self, kind, ticket):
+        assert self.open[kind] and self.open[kind][0] == ticket, "tickets are waited for in the order they were issued"
+        self.open[kind].pop(0)
+        self.calls.append(("async_wait", kind, ticket))
+
+    def finish(self):
+        return np.zeros(7, dtype=np.int64)
+
+
+PAD_VALUE = 7.25  # what the slack columns of every padded tensor hold before and after a call
+
+
+class Device:
+    """the device-resident calls through mrs_multirotor_simulator_amd.tensors: numpy in, numpy out; rows live in tensors with `pad`
+    slack columns, so that every stride is larger than its width, and the slack must come back untouched.  side=True: every tensor is
+    written, used and read under a torch stream of its own, so that the library's fences are what orders the data."""
+    real = True
+
+    def __init__(self, p, side):
+        import torch
+        from mrs_multirotor_simulator_amd import tensors as T
+        self.p, self.T, self.torch = p, T, torch
+        self.dev = torch.device("cuda", p.g.device())
+        self.stream = torch.cuda.Stream(self.dev) if side else None
+        self.totals = np.zeros(7, dtype=np.int64)  # fused_stats (4), download_stats (2), split_stats[0]
+
+    def ctx(self):
+        return self.torch.cuda.stream(self.stream) if self.stream is not None else contextlib.nullcontext()
+
+    def _dtype(self, f32):
+        return self.torch.float32 if f32 else self.torch.float64
+
+    def _up(self, a, pad, f32):
+        """`a` in the leading columns of a tensor with `pad` slack columns: (the whole tensor, the view that holds a)"""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        big = self.torch.full(a.shape[:-1] + (a.shape[-1] + pad,), PAD_VALUE, dtype=self._dtype(f32), device=self.dev)
+        view = big[..., :a.shape[-1]]
+        if a.size:
+            view.copy_(self.torch.from_numpy(a).to(self._dtype(f32)))
+        return big, view
+
+    def _empty(self, shape, pad, f32):
+        big = self.torch.full(tuple(shape[:-1]) + (shape[-1] + pad,), PAD_VALUE, dtype=self._dtype(f32), device=self.dev)
+        return big, big[..., :shape[-1]]
+
+    @staticmethod
+    def _down(big, width, what):
+        host = big.cpu().numpy()
+        assert (host[..., width:] == PAD_VALUE).all(), f"{what}: the slack columns were written"
+        return host[..., :width]
+
+    def set_input(self, mode, rows, first, f32, pad):
+        with self.ctx():
+            _, view = self._up(rows, pad, f32)
+            self.T.set_input(self.p.g, mode, view, first)
+
+    def apply_force(self, rows, first, f32, pad):
+        with self.ctx():
+            _, view = self._up(rows, pad, f32)
+            self.T.apply_force(self.p.g, view, first)
+
+    def gather(self, groups, first, count, f32, pad):
+        w = gather_width(groups)
+        with self.ctx():
+            big, view = self._empty((count, w), pad, f32)
+            self.T.gather(self.p.g, groups, first, count, out=view)
+            return self._down(big, w, "gather")
+
+    def crashed(self, first, count):
+        with self.ctx():
+            return self.T.crashed(self.p.g, first, count).cpu().numpy()
+
+    def reset(self, mask, pos, heading, takeoff, first, f32, u8):
+        torch = self.torch
+        with self.ctx():
+            m = torch.tensor(mask, device=self.dev)
+            hd = None if heading is None else torch.tensor(heading, dtype=self._dtype(f32), device=self.dev)
+            self.T.reset(self.p.g, m.to(torch.uint8) if u8 else m, torch.tensor(pos, dtype=self._dtype(f32), device=self.dev), hd, takeoff=takeoff,
+                         first=first)
+
+    def save_load(self, first, count, index):
+        with self.ctx():
+            rec = self.T.save(self.p.g, first, count)
+            idx = None if index is None else self.torch.tensor(index, dtype=self.torch.int32, device=self.dev)
+            return self.T.load(self.p.g, rec, first, index=idx).cpu().numpy()
+
+    def harvest(self):
+        g = self.p.g
+        self.totals += np.array([*g.fused_stats(), *g.download_stats(), g.split_stats()[0]], dtype=np.int64)
+
+    def clone_swap(self):
+        self.harvest()  # (the counters stay with the handle)
+        new = self.p.g.clone()
+        self.p.g.close()
+        self.p.g = new
+
+    def nearest(self, k, radius, fields, first, count, f32):
+        with self.ctx():
+            rows, idx, cnt = self.T.nearest(self.p.g, k, radius, fields, first, count, dtype=self._dtype(f32))
+            s = self.p.g.get_states()  # right after the call: the state it read
+            compare_with_numpy(self.T, rows, idx, cnt, s["x"], s["v"], s["R"].reshape(self.p.n, 3, 3), k, radius, fields, self._dtype(f32), first, count,
+                               label=("nearest", k, radius, fields, first, count))
+
+    def rollout(self, mode, cmd, first, groups, hold, every, forces, fhold, f32, pads):
+        steps, count, w = cmd.shape[0] * hold, cmd.shape[1], gather_width(groups)
+        with self.ctx():
+            _, c = self._up(cmd, pads[0], f32)
+            f = None if forces is None else self._up(forces, pads[2], f32)[1]
+            big, out = self._empty((steps // every, count, w), pads[1], f32) if groups else (None, None)
+            self.T.rollout(self.p.g, mode, c, DT, groups, first=first, out=out, hold=hold, obs_every=every, forces=f, force_hold=fhold)
+            return self._down(big, w, "rollout") if groups else None
+
+    def rollout_cost(self, mode, cmd, first, groups, targets, weights, hold, every, start, f32, pads):
+        torch = self.torch
+        with self.ctx():
+            _, c = self._up(cmd, pads[0], f32)
+            _, tg = self._up(targets, pads[1], f32)
+            _, wt = self._up(weights, pads[2], f32)
+            out = None if start is None else torch.tensor(start, dtype=torch.float64, device=self.dev)
+            got = self.T.rollout_cost(self.p.g, mode, c, DT, groups, tg, wt, first=first, hold=hold, cost_every=every, out=out, accumulate=start is not None)
+            return got.cpu().numpy()
+
+    def async_issue(self, kind, first, count):
+        return self.p.g.get_outputs_async(first, count) if kind == "outputs" else self.p.g.get_poses_async(first, count)
+
+    def async_wait(self, kind, ticket):
+        return (self.p.g.outputs_wait(ticket) if kind == "outputs" else self.p.g.poses_wait(ticket)).copy()
+
+    def finish(self):
+        self.harvest()
+        return self.totals
+
+
+# (seed, FAST arithmetic, fleet, the long rollout, model-only phases): odd seeds run their tensor calls under a torch stream of their own
+SEEDS = [(s, s % 3 == 2, "mixed" if (s // 2) % 2 else "x500", 16 <= s < 20, s >= 20) for s in range(28)]
+RNG_BASE = 5000
+# the largest step total of the 24 sequences of test_random_sequences_gpu.py (test_random_device_sequences.py counts both modules' totals)
+STEP_CAP = 76
+# child-process variants of the GPU module: (environment, (seed, ...) one per fleet, host call 12 in runs of at least four launches)
+VARIANTS = {"split": ({"MRS_SPLIT_MIN_BLOCKS": "1"}, (4, 7), True),
+            "pointer": ({"MRS_NO_BUFFER_ADDRESSING": "1"}, (1, 2), False),
+            "split+pointer": ({"MRS_SPLIT_MIN_BLOCKS": "1", "MRS_NO_BUFFER_ADDRESSING": "1"}, (8, 3), True)}
+
+
+def seed_rtol(fast):
+    return 1e-7 if fast else helpers.RTOL_LITERAL  # the tolerances of test_random_sequences_gpu.py, as they are
+
+
+# ---- the generator -----------------------------------------------------------------------------------------------------------------
+
+def divisors(steps, extra=()):
+    return [d for d in (1, 2, 3, 4, 5, 6) if steps % d == 0] + [e for e in extra if e > 6]
+
+
+def pick(rng, seq):
+    return seq[int(rng.integers(0, len(seq)))]
+
+
+def f32_round(a):
+    return np.asarray(a).astype(np.float32).astype(np.float64)
+
+
+def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, long_rollout=False, model=False):
+    """one random sequence on the Pair `p`, whose product side is reached through `dev` as well.
+    split: host call 12 steps in runs of five to seven launches, so that the two-stream form of step_n is taken.
+    long_rollout: a shorter sequence whose first rollout takes LONG_HORIZON steps.
+    model: every fifth call gives the whole swarm actuator commands, through the host call, the device call or a one-step rollout in
+    turn, so that the launches that follow use the model-only kernels until a call puts some UAVs under the controller cascade again;
+    half of the time that call is made a rollout.
+    Returns a dict: steps, the Counter of op kinds, the op log, quaternions compared up to sign, rollouts that followed a pending
+    collision tick, tickets waited for, the worst cost bound relative to its cost, and the product's counters (Device.finish)."""
+    n, n_iter = p.n, N_ITER_LONG if long_rollout else N_ITER
+    kinds, oplog = Counter(), []
+    res = dict(steps=0, kinds=kinds, log=oplog, quat_sign_cases=0, rollouts_behind_pending=0, worst_cost_ratio=0.0, tickets_waited=0)
+    pos = build_fleet(p, rng, n, fleet, seed)
+    p.both("set_input", 0, n, O.POSITION_CMD, payload(rng, 10, n, pos))
+    tickets = {"outputs": [], "poses": []}  # per kind, oldest first: (ticket, iteration it is due, the oracle's outputs of its range)
+    pending, forced, long_left, ticked, stepped, model_due = False, [], long_rollout, False, False, False
+
+    def wait_oldest(kind, what):
+        ticket, _, want = tickets[kind].pop(0)
+        got = dev.async_wait(kind, ticket)
+        res["tickets_waited"] += 1
+        if got is not None:
+            compare_outputs(got, want, fast, rtol, f"{what}: {kind} ticket {ticket}")
+
+    def rows_check(got, want, R, groups, f32, what):
+        if got is not None:
+            res["quat_sign_cases"] += compare_rows(got, want, R, groups, rtol, f32, what)
+
+    for it in range(n_iter):
+        what = f"seed {seed}, call {it}"
+        for kind in tickets:
+            while tickets[kind] and tickets[kind][0][1] <= it:
+                wait_oldest(kind, what)
+        room = cap - res["steps"] - 2 * sum(1 for j in range(it, n_iter) if j % 5 == 4)  # (the two steps before every compare are kept free)
+        model_due = model_due or (model and it % 5 == 0)
+        was_forced = bool(forced)
+        op = forced.pop(0) if forced else int(rng.integers(0, N_OPS))
+        first, count = rng_range(rng, n)
+        if model_due and not was_forced:  # (calls that belong together stay together)
+            forced, op, first, count, model_due = [op], MODEL_ALL, 0, n, False  # (the call drawn for this turn comes next)
+        x = p.o.get_state(first, count)["x"]
+        # the step budget: the long rollout comes first, seven steps stay free for the first run of ticks behind fast UAVs, and a rollout
+        # takes at most half of what is left then, so that stepping calls stay possible until the end of the sequence
+        free = room - (LONG_HORIZON if long_left else 0 if ticked else 7)
+        if split and not stepped and op != 12:
+            free -= 14  # (... and, where the two-stream form of step_n is what the sequence is run for, fourteen for its first step run)
+        need = {12: 14 if split else 10, 14: 7}
+        if (op in need and free < need[op]) or (op == TICK_LONG and room < 7) or (op in ROLLOUTS and room < (LONG_HORIZON if long_left else 1)):
+            op = GATHER  # no room left for the steps of this call
+        kinds[op] += 1
+        oplog.append((it, OP_NAMES[op], first, count))
+        if op == 12 and split:  # at least four launches behind the one that may carry a pending collision tick: the two-stream form is taken
+            k, sub = int(rng.integers(5, 8)), int(rng.integers(1, 3))
+            p.o.step_n(DT, k * sub)
+            p.g.step_n(DT, k * sub, sub)
+            res["steps"] += k * sub
+            stepped = True
+        elif op < 18:
+            res["steps"] += host_op(p, mrs, O, rng, op, first, count, x, fast, rtol, what)
+        elif op == MODEL_ALL:
+            how = (it // 5) % 3 if room >= 1 else (it // 5) % 2
+            pl = payload(rng, O.ACTUATOR_CMD, n, x)
+            p.o.set_input(0, n, O.ACTUATOR_CMD, pl)
+            if how == 0:
+                p.g.set_input(0, n, O.ACTUATOR_CMD, pl)
+            elif how == 1:
+                dev.set_input(O.ACTUATOR_CMD, pl, 0, False, 0)
+            else:
+                p.o.step(DT)
+                dev.rollout(O.ACTUATOR_CMD, pl[None], 0, 0, 1, 1, None, None, False, (0, 0, 0))
+                res["steps"] += 1
+            if rng.integers(0, 2):
+                forced.insert(0, pick(rng, ROLLOUTS))
+        elif op == TICK_LONG:
+            k = int(rng.integers(4, 8))
+            for _ in range(k):
+                p.o.step(DT)
+                p.o.handle_collisions(True, False, 60.0)
+            p.g.tick_n(DT, k, True, False, 60.0)
+            res["steps"] += k
+            ticked = True
+        elif op == DEV_SET_INPUT:
+            mode, f32, pad = int(rng.integers(0, 11)), bool(rng.integers(0, 2)), int(rng.integers(0, 4))
+            if mode == 0:
+                cnt = min(count, 5)
+                p.o.set_input(first, cnt, 0, None)
+                dev.set_input(0, np.zeros((cnt, 1)), first, f32, pad)
+            else:
+                pl = payload(rng, mode, count, x)
+                pl = f32_round(pl) if f32 else pl
+                p.o.set_input(first, count, mode, pl)
+                dev.set_input(mode, pl, first, f32, 0 if mode == O.ACTUATOR_CMD else pad)
+        elif op == DEV_FORCE:
+            f32, pad = bool(rng.integers(0, 2)), int(rng.integers(0, 4))
+            f = rng.normal(0, 3, (count, 3))
+            f = f32_round(f) if f32 else f
+            p.o.apply_force(first, count, f)
+            dev.apply_force(f, first, f32, pad)
+        elif op == GATHER:
+            groups, f32, pad = int(rng.integers(1, 256)), bool(rng.integers(0, 2)), int(rng.integers(0, 4))
+            want, R = ref_rows(p.o, first, count, groups)
+            rows_check(dev.gather(groups, first, count, f32, pad), want, R, groups, f32, f"{what}: gather {groups:#x}")
+        elif op == CRASHED:
+            got = dev.crashed(first, count)
+            if got is not None:
+                assert np.array_equal(got, p.o.has_crashed(first, count).astype(bool)), f"{what}: crash flags of {first}+{count}"
+        elif op == RESET:
+            mask = rng.random(count) < 0.3
+            mask[int(rng.integers(0, count))] = True
+            f32, heading, takeoff, u8 = (bool(v) for v in rng.integers(0, 2, 4))
+            newpos, hd = rng.uniform(0, 9, (count, 3)) + [0, 0, 0.5], rng.uniform(-3, 3, count)
+            if f32:
+                newpos, hd = f32_round(newpos), f32_round(hd)
+            for i in np.flatnonzero(mask):  # (runs of one UAV: every UAV is constructed with the parameters it has now)
+                po = p.o.get_params(first + int(i))
+                po.takeoff_patch_enabled = int(takeoff)  # the flag of the call replaces the UAV's own
+                p.o.construct(first + int(i), 1, po, newpos[i:i + 1], hd[i:i + 1] if heading else None)
+            dev.reset(mask, newpos, hd if heading else None, takeoff, first, f32, u8)
+            # the oracle's construct forgets what the product's reset keeps: both sides are told all of it anew
+            for lo, hi in _runs(mask):
+                a, c = first + int(lo), int(hi - lo)
+                p.both("set_mixer_params", a, c, desaturation=bool(rng.integers(0, 2)))
+                for which in ("set_rate_params", "set_attitude_params", "set_velocity_params", "set_position_params"):
+                    p.both(which, a, c, kp=float(rng.uniform(1.0, 5.0)))
+                for kind in range(4):
+                    p.both("set_feedforward", a, c, kind, np.concatenate([rng.uniform(-0.5, 0.5, (c, 3)), rng.uniform(-0.2, 0.2, (c, 1))], axis=1))
+                p.both("set_hold", a, c, bool(rng.integers(0, 4) == 0))
+                mode = int(rng.integers(1, 11))
+                p.both("set_input", a, c, mode, payload(rng, mode, c, newpos[lo:hi]))
+        elif op == SNAPSHOT:
+            index = None
+            if rng.integers(0, 2):
+                index = np.where(rng.random(count) < 0.3, -1, np.arange(count)).astype(np.int32)
+            status = dev.save_load(first, count, index)
+            if status is not None:
+                want = np.zeros(count, dtype=np.uint8) if index is None else (index < 0).astype(np.uint8)  # SNAP_LOADED 0, SNAP_SKIPPED 1
+                assert np.array_equal(status, want), f"{what}: status bytes of the load"
+        elif op == CLONE:
+            for kind in tickets:  # (a ticket belongs to the handle that issued it)
+                while tickets[kind]:
+                    wait_oldest(kind, what)
+            dev.clone_swap()
+        elif op == NEAREST:
+            k, radius, fields, f32 = int(rng.integers(1, 9)), float(rng.uniform(0.5, 4.0)), int(rng.integers(0, 32)), bool(rng.integers(0, 2))
+            dev.nearest(k, radius, fields, first, count, f32)
+        elif op in ROLLOUTS:
+            mode, f32 = int(rng.integers(0, 11)), bool(rng.integers(0, 2))
+            if long_left:
+                steps, long_left = LONG_HORIZON, False
+            else:
+                steps = pick(rng, [h for h in HORIZONS if h <= max(1, free // 2)])
+            hold = every = 1
+            if op != ROLL_PLAIN:
+                hold, every = pick(rng, divisors(steps)), pick(rng, divisors(steps, (steps,)))
+            fhold = pick(rng, divisors(steps, (steps,))) if op == ROLL_FORCE else None
+            groups = int(rng.integers(1, 256))
+            if op != ROLL_COST and rng.integers(0, 5) == 0:
+                groups = 0  # no observation rows at all
+            pads = tuple(int(v) for v in rng.integers(0, 4, 3))
+            if mode == O.ACTUATOR_CMD:
+                pads = (0,) + pads[1:]  # actuator rows are dense
+            if count == 1:
+                pads = (0, 0, 0)  # (tensors.py takes the width of a lone row for its stride: row blocks of one padded row are not dense)
+            blocks = steps // hold
+            cmd = np.zeros((blocks, count, 1)) if mode == 0 else np.stack([payload(rng, mode, count, x) for _ in range(blocks)])
+            forces = rng.normal(0, 3, (steps // fhold, count, 3)) if op == ROLL_FORCE else None
+            if f32:
+                cmd, forces = f32_round(cmd), None if forces is None else f32_round(forces)
+            res["rollouts_behind_pending"] += int(pending)
+            if pending and not forced and rng.integers(0, 2):
+                forced.append(13)  # the rollout settles the pending tick: the next tick must not be evaluated from what that one left behind
+            # the oracle's side: the loop of the header comment, literally
+            want, Rs = [], []
+            for t in range(steps):
+                if t % hold == 0:
+                    p.o.set_input(first, count, mode, cmd[t // hold] if mode else None)
+                if forces is not None and t % fhold == 0:
+                    p.o.apply_force(first, count, forces[t // fhold])
+                p.o.step(DT)
+                if groups and (t + 1) % every == 0:
+                    rows, R = ref_rows(p.o, first, count, groups)
+                    want.append(rows)
+                    Rs.append(R)
+            res["steps"] += steps
+            oplog[-1] += (mode, steps, hold, every, fhold, groups, f32)
+            if op != ROLL_COST:
+                got = dev.rollout(mode, cmd, first, groups, hold, every, forces, fhold, f32, pads)
+                if groups:
+                    rows_check(got, np.array(want), np.array(Rs), groups, f32, f"{what}: {OP_NAMES[op]} of {steps} steps, mode {mode}")
+            else:
+                want = np.array(want)
+                E, w = want.shape[0], want.shape[2]
+                finite = np.isfinite(want)
+                off = rng.uniform(0.5, 3.0, want.shape) * rng.choice([-1.0, 1.0], want.shape) * group_floors(groups)
+                targets = np.where(finite, want, 0.0) + off  # within a few units (of each group's scale) of the rows
+                weights = rng.uniform(0.1, 2.0, (E if rng.integers(0, 2) else 1, w))
+                start = rng.uniform(0.0, 5.0, count) if rng.integers(0, 3) == 0 else None
+                if f32:
+                    targets, weights = f32_round(targets), f32_round(weights)
+                cost = restate(want, targets, weights, start)
+                bound = cost_bound(want, targets, weights, groups, rtol)
+                own = cost - (0.0 if start is None else start)  # the cost of this call
+                ok = np.isfinite(cost)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    ratio = np.where(own[ok] > 0, bound[ok] / own[ok], bound[ok])  # (a cost of 0 counts against the absolute bound)
+                res["worst_cost_ratio"] = max(res["worst_cost_ratio"], float(ratio.max(initial=0.0)))
+                got = dev.rollout_cost(mode, cmd, first, groups, targets, weights, hold, every, start, f32, pads)
+                if got is not None:
+                    assert np.array_equal(np.isfinite(got), ok), f"{what}: non-finite costs differ"
+                    err = np.abs(got[ok] - cost[ok])
+                    i = int(np.argmax(err - bound[ok])) if ok.any() else 0
+                    assert (err <= bound[ok]).all(), (f"{what}: cost of UAV {first + int(np.flatnonzero(ok)[i])} is off by {err[i]:.3e}, the bound is "
+                                                     f"{bound[ok][i]:.3e} (cost {cost[ok][i]:.6e})")
+        elif op in (ASYNC_OUTPUTS, ASYNC_POSES):
+            kind = "outputs" if op == ASYNC_OUTPUTS else "poses"
+            if len(tickets[kind]) == 2:
+                wait_oldest(kind, what)
+            want = p.o.get_outputs(first, count).copy()
+            tickets[kind].append((dev.async_issue(kind, first, count), it + int(rng.integers(1, 7)), want))
+        elif op == FAST_UAVS:  # the stall recipe: a handful of UAVs fast enough to leave their skin within two steps
+            cnt = min(count, 6)
+            st = p.o.get_state(first, cnt)
+            st["v"][:] = [0.0, 170.0, 0.0]
+            p.both("set_state", first, cnt, st["x"], st["v"], st["R"], st["omega"], st["motor_rpm"])
+            # ... then a run of ticks that stalls, and two of the calls that must replay it and leave its last tick pending
+            forced += [TICK_LONG] + [pick(rng, STALL_FOLLOWERS) for _ in range(2)]
+        if op == 14 and not forced and rng.integers(0, 3) == 0:
+            forced.append(pick(rng, ROLLOUTS))  # a rollout right behind the pending tick of a run
+        if op in (13, 14, TICK_LONG):
+            pending = True
+        elif op not in KEEP_PENDING and not (op == MODEL_ALL and how < 2):
+            pending = False
+        if it % 5 == 4:
+            p.step(DT, 2)
+            res["steps"] += 2
+            pending = False
+            if dev.real:
+                check(p, rtol, f"{what} ({it + 1} calls)")
+    for kind in tickets:
+        while tickets[kind]:
+            wait_oldest(kind, f"seed {seed}, end")
+    assert res["steps"] <= cap, (res["steps"], cap)
+    assert not long_left, "the long rollout did not happen"
+    res["stats"] = dev.finish()
+    return res

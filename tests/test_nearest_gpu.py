@@ -19,9 +19,14 @@ DT = 0.001
 
 def check_against_numpy(T, g, x, v, R, k, radius, fields, dtype, first=0, count=None, label=""):
     """one tensors.nearest call against nearest_ref / nearest_rows on the state (x, v, R) it must have read"""
-    import torch
     count = g.n - first if count is None else count
     rows, idx, cnt = T.nearest(g, k, radius, fields, first, count, dtype=dtype)
+    return compare_with_numpy(T, rows, idx, cnt, x, v, R, k, radius, fields, dtype, first, count, label)
+
+
+def compare_with_numpy(T, rows, idx, cnt, x, v, R, k, radius, fields, dtype, first, count, label=""):
+    """the (rows, index, counts) of a tensors.nearest call against nearest_ref / nearest_rows on the state (x, v, R) it read"""
+    import torch
     ridx, rcnt, rdd = nearest_ref(x, first, count, k, radius)
     assert np.array_equal(cnt.cpu().numpy(), rcnt), label
     assert np.array_equal(idx.cpu().numpy(), ridx), label

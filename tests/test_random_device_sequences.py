@@ -1,0 +1,225 @@
+"""The generator of test_random_device_sequences_gpu.py (tests/device_sequences.py) against the oracle alone, with a stub in place of the
+product that checks every argument tuple against the header's rules and records it; and the reference rows the GPU module compares
+observation rows with, against tests/independent_model.py and against Eigen's four quaternion branches.  No GPU.
+
+Step totals (counted here): the 24 sequences of test_random_sequences_gpu.py take 39 .. 76 steps; the sequences of device_sequences.SEEDS
+and VARIANTS take at most STEP_CAP = 76, rollout steps included."""
+import numpy as np
+import pytest
+
+import device_sequences as D
+import helpers
+import independent_model as IM
+import test_random_sequences_gpu as E
+from oracle import oracle_swarm as O
+from test_rollout_cost_gpu import restate
+
+
+def dry_run(mrs, seed, split=False):
+    _, fast, fleet, long_rollout, model = D.SEEDS[seed]
+    p = D.StubPair(mrs, D.N_UAVS)
+    dev = D.Stub(p)
+    res = D.run_sequence(p, dev, mrs, np.random.default_rng(D.RNG_BASE + seed), seed, fast, fleet, D.seed_rtol(fast), D.STEP_CAP, split=split,
+                         long_rollout=long_rollout, model=model)
+    st = p.o.get_state()
+    res["non_finite_uavs"] = int((~np.isfinite(np.concatenate([st[k].reshape(p.n, -1) for k in st], axis=1))).any(axis=1).sum())
+    res["calls"], res["product_calls"] = dev.calls, p.g.calls
+    assert not dev.open["outputs"] and not dev.open["poses"], "tickets left open at the end of the sequence"
+    return res
+
+
+@pytest.fixture(scope="module")
+def runs(mrs):
+    """every sequence the GPU module runs: {(variant or None, seed): result}"""
+    out = {(None, seed): dry_run(mrs, seed) for seed, *_ in D.SEEDS}
+    for name, (_, seeds, split) in D.VARIANTS.items():
+        for seed in seeds:
+            out[name, seed] = dry_run(mrs, seed, split=split)
+    return out
+
+
+def test_step_cap_is_the_largest_total_of_the_existing_sequences(mrs):
+    totals = []
+    for seed, fast, fleet in E.SEEDS:
+        p = D.StubPair(mrs, 150)
+        totals.append(E.drive(p, mrs, O, np.random.default_rng(1000 + seed), 150, seed, fast, fleet, 0.0, compare=False))
+        assert "step_n" in p.g.calls and "tick_n" in p.g.calls
+    print(f"test_random_sequences_gpu.py: steps per seed {totals}")
+    assert max(totals) == D.STEP_CAP and min(totals) == 39
+
+
+def test_every_sequence_keeps_the_step_budget(runs):
+    for key, r in runs.items():
+        assert r["steps"] <= D.STEP_CAP, (key, r["steps"])
+    print("steps per sequence:", {k: r["steps"] for k, r in runs.items()})
+    assert max(r["steps"] for r in runs.values()) == 76  # (the figure of the GPU module's docstring)
+    for seed, _, _, long_rollout, _ in D.SEEDS:  # the long rollout happened, and left room for nothing but the compares
+        longs = [e for e in runs[None, seed]["log"] if len(e) > 4 and e[5] == D.LONG_HORIZON]
+        assert len(longs) == int(long_rollout), (seed, longs)
+
+
+def test_every_op_kind_occurs(runs):
+    kinds = sum((r["kinds"] for (variant, _), r in runs.items() if variant is None), D.Counter())
+    for op in range(D.N_OPS + 2):
+        assert kinds[op] >= 5, f"{D.OP_NAMES[op]} occurs {kinds[op]} times over all seeds"
+    # all four entry points of the rollouts take the long horizon once, both dtypes occur, and so do the tensor calls of every kind
+    names = [c[0] for r in runs.values() for c in r["calls"]]
+    for name in ("set_input", "apply_force", "gather", "crashed", "reset", "save_load", "clone", "nearest", "rollout", "rollout_cost", "async_issue",
+                 "async_wait"):
+        assert names.count(name) >= 5, name
+    assert sum(r["rollouts_behind_pending"] for r in runs.values()) >= 3
+    for variant, (_, seeds, split) in D.VARIANTS.items():
+        for s in seeds:  # host call 12 occurs in every sequence of the split variants (there in runs of 5 .. 7 launches)
+            assert not split or runs[variant, s]["kinds"][12] >= 1, (variant, s)
+        assert {D.SEEDS[s][2] for s in seeds} == {"x500", "mixed"}, variant
+
+
+def test_fast_uavs_are_followed_by_ticks_and_calls_that_replay_them(runs):
+    n, seen, followers = 0, set(), [D.OP_NAMES[op] for op in D.STALL_FOLLOWERS]
+    for r in runs.values():
+        names = [e[1] for e in r["log"]]
+        for i, name in enumerate(names[:-3]):
+            if name == "fast_uavs" and names[i + 1] == "tick_long":
+                assert names[i + 2] in followers and names[i + 3] in followers
+                n += 1
+                seen.update(names[i + 2:i + 4])
+    assert n >= 10 and seen == set(followers), (n, seen)
+
+
+def test_the_oracle_stays_usable(runs):
+    for key, r in runs.items():
+        assert r["non_finite_uavs"] <= D.N_UAVS // 10, (key, r["non_finite_uavs"])
+        assert r["worst_cost_ratio"] <= 1e-3, (key, r["worst_cost_ratio"])
+    assert max(r["worst_cost_ratio"] for r in runs.values()) > 0.0  # (costs were evaluated at all)
+
+
+# ---- the reference rows ------------------------------------------------------------------------------------------------------------
+
+def eigen_quaternion(R):
+    """Eigen::Quaterniond(Matrix3d), (x, y, z, w), and the branch taken: 3 for a positive trace, else the index of the largest diagonal entry"""
+    t = R[0, 0] + R[1, 1] + R[2, 2]
+    q = np.zeros(4)
+    if t > 0:
+        t = np.sqrt(t + 1.0)
+        q[3] = 0.5 * t
+        t = 0.5 / t
+        q[:3] = (R[2, 1] - R[1, 2]) * t, (R[0, 2] - R[2, 0]) * t, (R[1, 0] - R[0, 1]) * t
+        return q, 3
+    i = 0
+    if R[1, 1] > R[0, 0]:
+        i = 1
+    if R[2, 2] > R[i, i]:
+        i = 2
+    j, k = (i + 1) % 3, (i + 2) % 3
+    t = np.sqrt(R[i, i] - R[j, j] - R[k, k] + 1.0)
+    q[i] = 0.5 * t
+    t = 0.5 / t
+    q[3], q[j], q[k] = (R[k, j] - R[j, k]) * t, (R[j, i] + R[i, j]) * t, (R[k, i] + R[i, k]) * t
+    return q, i
+
+
+@pytest.mark.parametrize("airframe", ["x500", "f550"])
+def test_reference_rows_against_the_independent_model(airframe):
+    from test_independent_restatement import make_pair
+    rng = np.random.default_rng(77)
+    o, u, po = make_pair(O, airframe, rng, ground_enabled=True, ground_z=0.0)
+    nm = int(po.n_motors)
+    st = helpers.random_state(rng, 1, nm, tilted=True)
+    o.set_state(0, 1, st["x"], st["v"], st["R"], st["omega"], st["motor_rpm"])
+    u.x, u.v, u.R, u.omega, u.motor_rpm = st["x"][0].copy(), st["v"][0].copy(), st["R"][0].copy(), st["omega"][0].copy(), st["motor_rpm"][0][:nm].copy()
+    cmd = np.concatenate([rng.uniform(-2, 2, 3), rng.uniform(-1, 1, 1)])
+    o.set_input(0, 1, O.VELOCITY_HDG_CMD, cmd[None, :])
+    u.set_input(IM.VELOCITY_HDG_CMD, cmd)
+    for _ in range(40):
+        o.step(0.001)
+        u.make_step(0.001)
+    rows, R = D.ref_rows(o, 0, 1, 0xFF)
+    assert rows.shape == (1, 36) == (1, D.gather_width(0xFF)) and R.shape == (1, 3, 3)
+    q, _ = eigen_quaternion(u.R)
+    want = np.concatenate([u.x, u.v, u.R.T @ u.v, u.R.reshape(9), q, u.omega, u.imu, u.motor_rpm, np.zeros(8 - nm)])
+    assert np.abs(u.imu).max() > 0 and np.abs(u.omega).max() > 0
+    scale = np.maximum(np.abs(want), D.group_floors(0xFF))
+    assert (np.abs(rows[0] - want) / scale).max() <= 1e-9
+    # a subset of the groups: bit order, the columns of the full row
+    sub, _ = D.ref_rows(o, 0, 1, 0x91)  # POS | QUAT | RPM
+    assert np.array_equal(sub[0], np.concatenate([rows[0, 0:3], rows[0, 18:22], rows[0, 28:36]]))
+    assert D.gather_width(0x91) == 15 and len(D.group_floors(0x91)) == 15
+
+
+def test_reference_quaternions_take_all_four_branches():
+    from scipy.spatial.transform import Rotation
+    from test_pose_payload_gpu import rotations
+    rng = np.random.default_rng(5)
+    n = 64
+    o = O.OracleSwarm(n)
+    o.construct(0, n, helpers.oracle_params("x500"))
+    Rs = rotations(rng, n)
+    st = helpers.random_state(rng, n, 4)
+    o.set_state(0, n, st["x"], st["v"], Rs, st["omega"], st["motor_rpm"])
+    rows, R = D.ref_rows(o, 0, n, 1 << D.QUAT_BIT)
+    assert np.array_equal(R, Rs)
+    branches = set()
+    for i in range(n):
+        q, branch = eigen_quaternion(Rs[i])
+        branches.add(branch)
+        assert np.abs(rows[i] - q).max() <= 4e-16, i
+        ref = Rotation.from_matrix(Rs[i]).as_quat()
+        assert min(np.abs(rows[i] - ref).max(), np.abs(rows[i] + ref).max()) <= 1e-12, i
+    assert branches == {0, 1, 2, 3}
+
+
+def test_branch_boundaries_of_the_quaternion():
+    from scipy.spatial.transform import Rotation
+    third = Rotation.from_rotvec(np.array([1.0, 1.0, 1.0]) / np.sqrt(3.0) * (2.0 * np.pi / 3.0)).as_matrix()  # trace 0
+    half_xy = np.array([[0.0, 1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, -1.0]])  # half a turn about (1, 1, 0): R00 == R11 are the largest
+    cases = [(np.eye(3), False), (np.diag([1.0, -1.0, -1.0]), False), (third, True), (half_xy, True),
+             (Rotation.from_rotvec([0.3, -0.2, 2.0]).as_matrix(), False)]
+    got = D.near_quat_branch(np.array([c[0] for c in cases]))
+    assert list(got) == [c[1] for c in cases]
+    # a quaternion of the other sign passes at a boundary and nowhere else
+    q = np.array([[0.5, 0.5, 0.5, 0.5]])
+    assert D.compare_rows(-q, q, third[None], 1 << D.QUAT_BIT, 1e-11, False, "boundary") == 1
+    with pytest.raises(AssertionError, match="quat"):
+        D.compare_rows(-q, q, np.eye(3)[None], 1 << D.QUAT_BIT, 1e-11, False, "no boundary")
+
+
+def test_compare_rows_measures_every_group_on_its_own_scale():
+    rng = np.random.default_rng(9)
+    o = O.OracleSwarm(8)
+    o.construct(0, 8, helpers.oracle_params("x500"))
+    st = helpers.random_state(rng, 8, 4, tilted=True)
+    o.set_state(0, 8, st["x"], st["v"], st["R"], st["omega"], st["motor_rpm"])
+    want, R = D.ref_rows(o, 0, 8, 0xFF)
+    assert D.compare_rows(want.copy(), want, R, 0xFF, 1e-11, False, "same") == 0
+    assert D.compare_rows(want.astype(np.float32), want, R, 0xFF, 1e-11, True, "one float rounding") == 0
+    with pytest.raises(AssertionError):
+        D.compare_rows(want.astype(np.float32), want, R, 0xFF, 1e-11, False, "FP32 rows at the FP64 tolerance")
+    for col, name in ((1, "x"), (10, "R"), (23, "omega"), (30, "rpm")):
+        off = want.copy()
+        off[3, col] += 3e-11 * max(abs(want[3, col]), 1000.0 if name == "rpm" else 1.0) * 10
+        with pytest.raises(AssertionError, match=name):
+            D.compare_rows(off, want, R, 0xFF, 1e-11, False, "perturbed")
+    off = want.copy()
+    off[3, 30] += 5e-9  # far below the rpm group's scale, though above 1e-11 of a unit
+    assert D.compare_rows(off, want, R, 0xFF, 1e-11, False, "rpm scale") == 0
+    nan = want.copy()
+    nan[2, 4] = np.nan
+    with pytest.raises(AssertionError, match="NaN pattern"):
+        D.compare_rows(nan, want, R, 0xFF, 1e-11, False, "NaN")
+
+
+def test_cost_bound_covers_a_perturbation_of_the_rows():
+    rng = np.random.default_rng(13)
+    groups, rtol = 0x83, 1e-7  # POS | VEL | RPM
+    w = D.gather_width(groups)
+    rows = np.concatenate([rng.normal(0, 5, (4, 10, 6)), rng.uniform(2000, 5000, (4, 10, 8))], axis=2)
+    targets = rows + rng.uniform(0.5, 3.0, rows.shape) * rng.choice([-1.0, 1.0], rows.shape) * D.group_floors(groups)
+    for weights in (rng.uniform(0.1, 2.0, (4, w)), rng.uniform(0.1, 2.0, (1, w))):
+        cost, bound = restate(rows, targets, weights), D.cost_bound(rows, targets, weights, groups, rtol)
+        assert (bound > 0).all() and (bound <= 1e-3 * cost).all()
+        delta = rtol * np.maximum(np.abs(rows), D.group_floors(groups))
+        for sign in (rng.choice([-1.0, 1.0], rows.shape), np.sign(rows - targets)):
+            moved = restate(rows + sign * delta, targets, weights)
+            assert (np.abs(moved - cost) <= bound * (1 + 1e-9)).all()
+        worst = restate(rows + np.sign(rows - targets) * delta, targets, weights)
+        assert (np.abs(worst - cost) >= 0.99 * bound).all()  # the bound is attained, not generous

@@ -1,0 +1,114 @@
+"""Differential test of the device-resident call surface under random call sequences (tests/device_sequences.py): the frame of
+test_random_sequences_gpu.py — about 150 UAVs in two fleets, dense enough to collide all the time, the ground enabled, both arithmetic
+flavours, all 18 host calls of that module — with the device-resident calls mixed in: commands and forces from FP64 / FP32 rows with
+padded strides, observation rows, crash flags, masked resets, snapshot round trips, clone swaps, nearest-neighbour rows, the four rollout
+entry points (FP64 and FP32, held commands, strided observation / cost rows, force rows, once 66 steps), pipelined output and pose
+downloads waited for one to six calls later, and UAVs made fast enough to stall the lazily evaluated collision ticks.  The last eight
+seeds put the whole swarm under actuator commands every fifth call, so that the calls that follow meet the model-only step kernels and
+have to move the launches back to the cascade kernels themselves.  The CPU oracle and
+plain numpy are the only references: no twin product swarm.  State, PIDs, IMU, forces and crash flags are compared after every five
+calls, observation rows per group on the group's own scale, costs against the first-order bound of their restatement.
+
+Odd seeds run every tensor call under a torch stream of their own: the library's fences are then what orders the data.
+
+Tolerances are those of test_random_sequences_gpu.py (RTOL_LITERAL, 1e-7 for FAST), which were set for its step totals: the largest of
+its 24 sequences takes 76 steps, and no sequence here takes more (rollout steps included; the largest takes 76).
+test_random_device_sequences.py counts both on the CPU and checks the generator against the oracle alone.
+
+After the seeds, the counters of the library summed over them must show what the sequences are there for: a stall that was replayed, a
+pipelined download re-issued by a replay and then waited for, a rollout behind a collision tick that was still pending.  Three variants
+run in child processes (two seeds each, one per fleet): the two-stream form of step_n (MRS_SPLIT_MIN_BLOCKS=1: three blocks), the
+pointer-addressed kernels (MRS_NO_BUFFER_ADDRESSING=1), and both."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from device_sequences import N_UAVS, RNG_BASE, SEEDS, STEP_CAP, VARIANTS, Device, run_sequence, seed_rtol
+from helpers import Pair
+
+pytestmark = pytest.mark.gpu
+TESTS = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(TESTS)
+CHILD_TIMEOUT = 300
+STAT_NAMES = ("fused", "stalls", "replayed", "ahead", "packs", "reissued", "split_steps")
+
+_results = {}  # seed -> what run_sequence returned
+_dead = []     # the first child process that died by a signal or timed out: nothing more is started on the GPU
+
+
+def run_seed(mrs, seed, split=False):
+    _, fast, fleet, long_rollout, model = SEEDS[seed]
+    p = Pair(mrs, N_UAVS, arith=mrs.ARITH_FAST if fast else mrs.ARITH_LITERAL)
+    dev = Device(p, side=bool(seed % 2))
+    res = run_sequence(p, dev, mrs, np.random.default_rng(RNG_BASE + seed), seed, fast, fleet, seed_rtol(fast), STEP_CAP, split=split,
+                       long_rollout=long_rollout, model=model)
+    assert p.g.get_diag() == p.o.get_diag()
+    return res
+
+
+def figures(res):
+    st = dict(zip(STAT_NAMES, (int(v) for v in res["stats"])))
+    return dict(steps=res["steps"], stalls=st["stalls"], replayed=st["replayed"], reissued=st["reissued"], tickets_waited=res["tickets_waited"],
+                quat_sign_cases=res["quat_sign_cases"], rollouts_behind_pending=res["rollouts_behind_pending"], split_steps=st["split_steps"],
+                fused=st["fused"])
+
+
+@pytest.mark.parametrize("seed,fast,fleet,long_rollout,model", SEEDS)
+def test_random_device_sequences_match_oracle(mrs, seed, fast, fleet, long_rollout, model):
+    res = run_seed(mrs, seed)
+    print(f"seed {seed} ({'FAST' if fast else 'LITERAL'}, {fleet}): {figures(res)}")
+    _results[seed] = res
+
+
+def test_the_sequences_met_what_they_are_for():
+    assert len(_results) == len(SEEDS), f"only {len(_results)} of the {len(SEEDS)} seeds ran to their end: this check speaks for all of them"
+    total = {k: sum(figures(r)[k] for r in _results.values()) for k in figures(next(iter(_results.values())))}
+    print(f"all seeds: {total}")
+    assert total["stalls"] >= 1 and total["replayed"] >= 1, f"no stall of the lazy collision ticks was replayed: {total}"
+    assert total["reissued"] >= 1 and total["tickets_waited"] >= 1, f"no pipelined download was re-issued by a replay and waited for: {total}"
+    assert total["rollouts_behind_pending"] >= 1, f"no rollout followed a collision tick that was still pending: {total}"
+
+
+def child_main(out_path, variant):
+    import mrs_multirotor_simulator_amd as M
+    M.load_library()
+    _, seeds, split = VARIANTS[variant]
+    out = {}
+    for seed in seeds:
+        out[str(seed)] = figures(run_seed(M, seed, split=split))
+        print(f"{variant}: seed {seed}: {out[str(seed)]}", flush=True)
+    with open(out_path, "w") as f:
+        json.dump(out, f)
+
+
+@pytest.mark.parametrize("variant", list(VARIANTS))
+def test_variant_in_a_child_process(mrs, tmp_path, variant):
+    if _dead:
+        pytest.fail(f"an earlier child process of this module died ({_dead[0]}): no further GPU process is started")
+    env_add, seeds, split = VARIANTS[variant]
+    out = str(tmp_path / "variant.json")
+    env = {k: v for k, v in os.environ.items() if not k.startswith("MRS_")}
+    env.update(env_add)
+    code = f"import sys; sys.path[:0] = [{ROOT!r}, {TESTS!r}]; import test_random_device_sequences_gpu as T; T.child_main({out!r}, {variant!r})"
+    try:
+        p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=CHILD_TIMEOUT)
+    except subprocess.TimeoutExpired:
+        _dead.append(f"{variant} child timed out after {CHILD_TIMEOUT} s")
+        pytest.fail(_dead[0])
+    if p.returncode < 0:
+        _dead.append(f"{variant} child ended by signal {-p.returncode}")
+        pytest.fail(f"{_dead[0]}\n{p.stderr[-3000:]}")
+    print(p.stdout)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    with open(out) as f:
+        got = json.load(f)
+    assert sorted(got) == sorted(str(s) for s in seeds)
+    for seed, fig in got.items():
+        if split:  # the two-stream form was taken: steps launched as two half-swarm launches
+            assert fig["split_steps"] >= 4, f"{variant}, seed {seed}: step_n never took the two-stream form: {fig}"
+        else:
+            assert fig["split_steps"] == 0, f"{variant}, seed {seed}: {fig}"

@@ -813,6 +813,15 @@ public:
     mrs_throw_on_error(mrs_swarm_rollout_cost_device(s_, first, count, mode, dt, n_steps, cmd_every, cost_every, dev_cmd, dtype, cmd_stride, groups,
                                                      dev_target, target_stride, dev_weight, weight_stride, dev_cost, accumulate ? 1 : 0, stream));
   }
+  // n_ticks ticks of timerMain — makeStep of every UAV, then handleCollisions(crash, rebounce) — with the rows of rolloutRateDevice and,
+  // where an observation row block is due, hasCrashed of the range as count bytes of dev_crashed (n_ticks / obs_every dense blocks; may
+  // be null, as dev_obs when groups == 0).  The last tick's collision stays pending, as after a tick loop.
+  void rolloutTickDevice(int first, int count, int mode, double dt, int n_ticks, int cmd_every, int obs_every, const void* dev_cmd, int dtype,
+                         int cmd_stride, uint32_t groups, void* dev_obs, int obs_stride, uint8_t* dev_crashed, bool crash, double rebounce,
+                         void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_rollout_tick_device(s_, first, count, mode, dt, n_ticks, cmd_every, obs_every, dev_cmd, dtype, cmd_stride, groups,
+                                                     dev_obs, obs_stride, dev_crashed, crash ? 1 : 0, rebounce, stream));
+  }
   // the whole simulation state of UAVs [first, first + count) into dev_records[0 .. count-1] (device memory, 16-B aligned)
   void saveDevice(int first, int count, mrs_uav_snapshot_t* dev_records, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_save_device(s_, first, count, dev_records, stream));

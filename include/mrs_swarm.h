@@ -696,6 +696,38 @@ int mrs_swarm_rollout_cost_device(mrs_swarm_t* s, int32_t first, int32_t count, 
                                   const void* dev_weight, int32_t weight_stride, /* 0: one weight row for every evaluation */
                                   double* dev_cost, int32_t accumulate, void* ext_stream);
 
+/* ---- tick rollouts: timerMain over n_ticks ticks in one call — makeStep of every UAV, then handleCollisions — with device rows ----
+ * MultirotorSimulator::timerMain (src/multirotor_simulator.cpp:211-217) is makeStep for every UAV, then handleCollisions (:295-359).  A
+ * swarm policy or a multi-agent planner needs the contacts, the rebounce forces and the crash flags inside its horizon.  Equals, bit for
+ * bit in LITERAL arithmetic, the loop
+ *   for t in [0, n_ticks):
+ *     if (t % cmd_every == 0)
+ *       mrs_swarm_set_input_device(s, first, count, mode, row block t / cmd_every of dev_cmd, dtype, cmd_stride, ext_stream);
+ *     mrs_swarm_step(s, dt);             evaluates the collision tick pending from tick t - 1 (fused with the step when the lists allow it)
+ *     if ((t + 1) % obs_every == 0) {    row block j = (t + 1) / obs_every - 1
+ *       if (groups) mrs_swarm_gather_device(s, first, count, groups, row block j of dev_obs, dtype, obs_stride, ext_stream);
+ *       if (dev_crashed) mrs_swarm_get_crashed_device(s, first, count, dev_crashed + j * count, ext_stream);
+ *     }
+ *     mrs_swarm_handle_collisions(s, 1, crash, rebounce);    stays pending: the next step, of this call or a later one, evaluates it
+ * dev_cmd and dev_obs are the row blocks of mrs_swarm_rollout_rate_device.  dev_crashed (may be NULL) holds n_ticks / obs_every dense
+ * blocks of `count` bytes: block j is UavSystem::hasCrashed of the range at the instant observation block j is taken — after makeStep of
+ * the tick and before that tick's handleCollisions, where the reference's publishers see the swarm — so it holds every collision up to
+ * the previous tick.  groups and dev_crashed are independent: either may be 0 / NULL.  handleCollisions is always enabled here (there is
+ * no argument that switches it off: without collisions mrs_swarm_rollout_rate_device is the call); crash != 0 is the crash mode, else the
+ * elastic one with `rebounce`.
+ * The call enters like a state call, except that a collision tick pending at entry is evaluated by the first launch of the call; the
+ * last tick's collision stays pending as after mrs_swarm_tick_n.  The call waits for its own launches before it returns (a replay after
+ * stale neighbour lists writes into the caller's rows, which need only live until the call returns): ONE host wait per call, where the
+ * loop above has one or more per tick.  ONE stream fence per call.  A UAV on hold takes part in the collisions and is not iterated; it
+ * gets its command rows, and observation and crash rows of its unchanged state (its crash flag included, if the evaluation set it).
+ * Crashed UAVs and UAVs outside the range are treated as in mrs_swarm_rollout_rate_device.  Every argument is checked before anything is
+ * launched and a refused call changes nothing: the refusals of mrs_swarm_rollout_rate_device (a sharded swarm among them), plus, as
+ * MRS_ERR_ARG, a dev_crashed that is not device memory of the swarm's device or shorter than n_ticks / obs_every * count bytes, and a
+ * rebounce that is not finite. */
+int mrs_swarm_rollout_tick_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_ticks, int32_t cmd_every,
+                                  int32_t obs_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs,
+                                  int32_t obs_stride, uint8_t* dev_crashed, int32_t crash, double rebounce, void* ext_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -197,6 +197,12 @@ int fence_out(mrs_swarm* s, hipStream_t ext) {
   return MRS_OK;
 }
 
+int launch_crashed_u8(mrs_swarm* s, int first, int count, uint8_t* dev_out) {
+  hipLaunchKernelGGL(k_crashed_u8, grid_of(count), dim3(256), 0, s->stream, s->dF, first, count, dev_out);
+  HIPCHK(hipGetLastError());
+  return MRS_OK;
+}
+
 }  // namespace mrs_host
 
 extern "C" {
@@ -507,6 +513,77 @@ int mrs_swarm_rollout_cost_device(mrs_swarm_t* s, int32_t first, int32_t count, 
   const CostArgs cost{dev_target, target_stride, dev_weight, weight_stride, dev_cost, accumulate};
   return rollout_locked(s, first, count, mode, dt, n_steps, cmd_every, cost_every, 0, dev_cmd, dtype, cmd_stride, nullptr, 0, groups, nullptr, 0, ext_stream,
                         false, "mrs_swarm_rollout_cost_device", &cost);
+}
+
+// timerMain over n_ticks ticks with caller rows: every tick is step_one (tick_single.hip) with the row blocks of that tick, then the
+// tick's handleCollisions stays pending as after mrs_swarm_tick_n.  The launches of the call carry their row descriptors through the
+// stall / replay log, and the call drains the log before it returns.
+int mrs_swarm_rollout_tick_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_ticks, int32_t cmd_every,
+                                  int32_t obs_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs,
+                                  int32_t obs_stride, uint8_t* dev_crashed, int32_t crash, double rebounce, void* ext_stream) {
+  MRS_LOCK(s);
+  int rc = check_range(s, first, count);
+  if (rc) return rc;
+  if (s->comm_world > 0) return fail(MRS_ERR_ARG, "mrs_swarm_rollout_tick_device: not on a sharded swarm");
+  if (mode < MRS_INPUT_UNKNOWN || mode > MRS_POSITION_CMD) return fail(MRS_ERR_ARG, "bad input mode");
+  if ((rc = check_dtype(dtype))) return rc;
+  if (n_ticks < 1) return fail(MRS_ERR_ARG, "n_ticks must be at least 1");
+  if (cmd_every < 1 || n_ticks % cmd_every != 0) return fail(MRS_ERR_ARG, "cmd_every must be at least 1 and divide n_ticks");
+  if (obs_every < 1 || n_ticks % obs_every != 0) return fail(MRS_ERR_ARG, "obs_every must be at least 1 and divide n_ticks");
+  if (!(dt > 0) || !std::isfinite(dt)) return fail(MRS_ERR_ARG, "dt must be finite and > 0");
+  if (!std::isfinite(rebounce)) return fail(MRS_ERR_ARG, "rebounce must be finite");
+  const int width = command_width(mode, cmd_stride);
+  if (width > 0 && (cmd_stride < width || width < 1)) return fail(MRS_ERR_ARG, "cmd_stride too small for this mode");
+  int32_t obs_width = 0;
+  if ((rc = mrs_swarm_gather_width(groups, &obs_width))) return rc;
+  if (groups != 0u && obs_stride < obs_width) return fail(MRS_ERR_ARG, "obs_stride smaller than the width of the selected groups");
+  const size_t elem = dtype_bytes(dtype);
+  if (count > 0) {  // 64-bit: blocks x count x stride can pass 2^31 elements
+    const size_t cmd_rows = (size_t)(n_ticks / cmd_every) * (size_t)count, obs_rows = (size_t)(n_ticks / obs_every) * (size_t)count;
+    if (width > 0 && (rc = check_device_ptr(s, dev_cmd, ((cmd_rows - 1) * (size_t)cmd_stride + (size_t)width) * elem, "dev_cmd"))) return rc;
+    if (groups != 0u && (rc = check_device_ptr(s, dev_obs, ((obs_rows - 1) * (size_t)obs_stride + (size_t)obs_width) * elem, "dev_obs"))) return rc;
+    if (dev_crashed && (rc = check_device_ptr(s, dev_crashed, obs_rows, "dev_crashed"))) return rc;
+    if (mode == MRS_ACTUATOR_CMD && !actuator_width_ok(s, first, count, width)) return fail(MRS_ERR_ARG, "actuator payload narrower than n_motors");
+  }
+  if (s->n == 0) return MRS_OK;
+  HIPCHK(hipSetDevice(s->device));
+  // like a command call: launches queued by earlier calls must have run before the mode mirror (which picks the kernel variant of a
+  // replay) changes; a collision tick pending at entry stays pending — the first launch of this call evaluates it
+  if (!s->log.empty() && (rc = drain(s))) return rc;
+  if ((rc = upload_types(s, dt))) return rc;
+  if (count > 0) {
+    const uint8_t* m    = s->uav_mode.data() + first;
+    unsigned       diff = 0;
+    for (int k = 0; k < count; k++) diff |= (unsigned)(m[k] ^ (uint8_t)mode);
+    if (diff) track_mode(s, first, count, mode);
+  }
+  hipStream_t ext = (hipStream_t)ext_stream;
+  if ((rc = fence_in(s, ext))) return rc;
+  if ((rc = begin_profile(s))) return rc;
+  RolloutTickDev row{};
+  row.first = first, row.count = count;
+  row.cmd_stride = cmd_stride, row.obs_stride = obs_stride;
+  row.cmd_word  = (uint32_t)width | (dtype == MRS_DTYPE_F32 ? 32u : 0u);
+  row.groups    = groups;
+  row.mode_bits = (uint32_t)mode << FLAG_MODE_SHIFT;
+  for (int t = 0; t < n_ticks; t++) {
+    row.cmd = row.obs = nullptr;
+    row.crashed = nullptr;
+    if (count > 0 && width > 0 && t % cmd_every == 0)
+      row.cmd = static_cast<const char*>(dev_cmd) + (size_t)(t / cmd_every) * (size_t)count * (size_t)cmd_stride * elem;
+    if (count > 0 && (t + 1) % obs_every == 0) {
+      const size_t j = (size_t)((t + 1) / obs_every - 1);
+      if (groups != 0u) row.obs = static_cast<char*>(dev_obs) + j * (size_t)count * (size_t)obs_stride * elem;
+      if (dev_crashed) row.crashed = dev_crashed + j * (size_t)count;
+    }
+    if ((rc = step_one(s, dt, &row))) return rc;
+    if ((rc = mrs_swarm_handle_collisions(s, 1, crash, rebounce))) return rc;
+  }
+  // a replay after a stall writes into the caller's rows, which are only guaranteed to live until the call returns: nothing of this
+  // call stays in the log (one host wait per call); the last tick's collision stays pending
+  if ((rc = drain(s))) return rc;
+  if ((rc = finish_profile(s))) return rc;
+  return fence_out(s, ext);
 }
 
 }  // extern "C"

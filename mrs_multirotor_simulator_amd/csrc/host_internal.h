@@ -53,6 +53,8 @@ extern "C" hipError_t mrs_launch_rollout_cost_literal(SwarmDev sw, RolloutCostDe
                                                         hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_cost_fast(SwarmDev sw, RolloutCostDev r, double dt, int n_steps, int cmd_every, int cost_every, int variant,
                                                      hipStream_t st);
+extern "C" hipError_t mrs_launch_rollout_tick_literal(SwarmDev sw, CollDev cd, RolloutTickDev r, double dt, int variant, hipStream_t st);
+extern "C" hipError_t mrs_launch_rollout_tick_fast(SwarmDev sw, CollDev cd, RolloutTickDev r, double dt, int variant, hipStream_t st);
 extern "C" hipError_t mrs_launch_pid_probe_literal(const double*, const double*, const double*, const double*, const double*, double*, int, int, hipStream_t);
 extern "C" hipError_t mrs_launch_pid_probe_fast(const double*, const double*, const double*, const double*, const double*, double*, int, int, hipStream_t);
 extern "C" hipError_t mrs_launch_pid_update_probe_literal(const double*, double*, const double*, const double*, double*, int, hipStream_t);
@@ -322,6 +324,8 @@ struct mrs_swarm {
   // pin: which position buffer the launch read; packs: the pipelined downloads packed right behind this launch, in the order they were
   // issued (re-issued when the launch is replayed after a stall: what they packed then was the state of an earlier tick).  At most
   // two per kind can still hold their slot, so four entries are enough (the _async call drops those whose slot has been recycled).
+  // rows: the launch is one tick of mrs_swarm_rollout_tick_device and `row` names the caller's row blocks of that tick — a replay
+  // writes into them what the no-op launch did not (the call drains the log before it returns: the rows live that long).
   struct PackRef { int32_t kind, ticket; };
   struct TickRec {
     double  dt;
@@ -330,6 +334,8 @@ struct mrs_swarm {
     int     pin = 0;
     int     n_packs = 0;
     PackRef packs[2 * PAYLOAD_KINDS] = {};
+    bool           rows = false;
+    RolloutTickDev row{};
   };
   Collide              pend;                        // requested after the most recent step, not evaluated yet
   // A fused launch consumes the force it evaluates from registers and does not write the F_ext columns (24 B per UAV and tick).
@@ -429,7 +435,7 @@ int  begin_profile(mrs_swarm* s);
 int  finish_profile(mrs_swarm* s);
 int  collide_now(mrs_swarm* s, const mrs_swarm::Collide& c, bool force);
 int  wait_for_progress(mrs_swarm* s, const volatile unsigned* hw, unsigned index, int lead);
-int  step_one(mrs_swarm* s, double dt);
+int  step_one(mrs_swarm* s, double dt, const RolloutTickDev* row = nullptr);  // row: the tick's caller rows (mrs_swarm_rollout_tick_device)
 int  drain(mrs_swarm* s);
 // the slot of `kind` that still holds the download `ticket` (nullptr: a ticket of the other kind, or its slot has been recycled)
 inline mrs_swarm::OutSlot* held_slot(mrs_swarm* s, int kind, int32_t ticket) {
@@ -448,6 +454,7 @@ int    check_device_ptr(const mrs_swarm* s, const void* p, size_t bytes, const c
 size_t rows_bytes(int count, int stride, int width, int dtype);
 int    fence_in(mrs_swarm* s, hipStream_t ext);
 int    fence_out(mrs_swarm* s, hipStream_t ext);
+int    launch_crashed_u8(mrs_swarm* s, int first, int count, uint8_t* dev_out);  // hasCrashed of a range as bytes, on the swarm's stream
 // ---- nearest.hip ----
 void   nearest_release(mrs_swarm* s);  // frees the scratch of mrs_swarm_nearest_device (mrs_swarm_destroy)
 // ---- transports (transport_*.hip) and the communicator bookkeeping (tick_sharded.hip) ----

@@ -1157,6 +1157,10 @@ DEV bool coll_fold_and_decide(CDT& cd0, const int part, const uint32_t stall_own
 // HK: what a launch does around each fused sub-step besides stepping (MULTI only; rollout_device.inc).  enter() runs once per lane
 // after the wave-uniform exits and may finish the lane itself (true); cmd(s) runs at the top of sub-step s, before the controller
 // cascade, and obs(s) after post_step.  The default does nothing: every kernel of this file compiles as it did without the hook.
+// One hook type, RolloutTickHook (rollout_tick_device.inc), rides on the single-GPU COLL kernels instead: one step per launch, and
+// held(), the last thing a held lane does — in COLL kernels a held lane takes part in the collisions and leaves inside
+// MRS_COLLIDE_THEN, so enter() cannot finish it.
+struct RolloutTickHook;
 struct NoStepHook {
   template <class SW>
   __device__ __forceinline__ bool enter(const SW&, int, Lane&, int) const { return false; }
@@ -1164,13 +1168,16 @@ struct NoStepHook {
   __device__ __forceinline__ void cmd(const SW&, int, int) const {}
   template <class SW, class PT>
   __device__ __forceinline__ void obs(const SW&, PT&, int, const Lane&, int) const {}
+  template <class SW>
+  __device__ __forceinline__ void held(const SW&, int, const Lane&, uint32_t) const {}
 };
 template <bool CASCADE, bool UNIFORM, int NU, bool MULTI, int SU, bool COLL, bool PIDPRE = false, bool SHARD = false, class HK = NoStepHook, class SW,
           class CDT>
 DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, const int substeps_arg, CDT& cd0, int& blk_out, bool& took_part,
                           const HK& hk = HK()) {
   static_assert(!COLL || (NU == 1 && !MULTI), "fused collision evaluation: one UAV per lane, one step per launch");
-  static_assert(__is_same(HK, NoStepHook) || (NU == 1 && MULTI && !COLL), "sub-step hooks: one UAV per lane, fused sub-steps, no collisions");
+  static_assert(__is_same(HK, NoStepHook) || (NU == 1 && MULTI && !COLL) || (__is_same(HK, RolloutTickHook) && NU == 1 && !MULTI && COLL && !SHARD),
+                "sub-step hooks: one UAV per lane, fused sub-steps, no collisions (the tick hook: one step, single-GPU collisions)");
   // MULTI = false compiles the substep loop away: with the loop the state is loop-carried and the per-type constants are
   // hoisted in front of it, which costs the fused kernel ~120 registers (350 vs 227) and with them its second wave per SIMD
   const int substeps = MULTI ? substeps_arg : 1;
@@ -1419,6 +1426,7 @@ DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, co
       if (L[0].stale) report_stall<SHARD>(cd, part, cd.tau, /*exact=*/true);                                                 \
       const uint32_t fl = flags_in[0] | (L[0].flags & FLAG_CRASHED); /* nothing else of the UAV changes: it is not iterated */ \
       if (fl != flags_in[0]) sw.F[i] = fl;                                                                            \
+      if constexpr (COLL && !__is_same(HK, NoStepHook)) hk.held(sw, i, L[0], fl);                                     \
       return;                                                                                                         \
     }                                                                                                                 \
   }

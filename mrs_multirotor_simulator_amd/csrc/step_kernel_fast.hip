@@ -5,3 +5,4 @@
 #include "rollout_rate_device.inc"
 #include "rollout_force_device.inc"
 #include "rollout_cost_device.inc"
+#include "rollout_tick_device.inc"

@@ -167,6 +167,21 @@ struct RolloutCostDev {
   int32_t     wt_row;      // weight_stride, or 0: one weight row for every evaluation
 };
 
+// ---- the rows of ONE tick of a tick rollout (mrs_swarm_rollout_tick_device, rollout_tick_device.inc) ----
+// One launch is one tick, so the host works out each launch's row blocks itself: no schedule words.  The descriptor travels with the
+// launch's record in the stall / replay log (mrs_swarm::TickRec): a replayed launch writes the rows its no-op did not.
+struct RolloutTickDev {
+  const void* cmd;         // the command row block that starts at this tick (row k at element k * cmd_stride), or null: none starts
+  void*       obs;         // the observation row block that ends with this tick (row k at element k * obs_stride), or null
+  uint8_t*    crashed;     // the crash row block that ends with this tick (byte k), or null
+  int32_t     first, count;
+  int32_t     cmd_stride, obs_stride;
+  uint32_t    cmd_word;    // payload width | rows are FP32 << 5 (commands and observations)
+  uint32_t    groups;      // MRS_OBS_* of the observation rows
+  uint32_t    mode_bits;   // input mode << FLAG_MODE_SHIFT
+  int32_t     _pad;
+};
+
 // 48-byte record exchanged for the collision pass (single- and multi-GPU): everything
 // MultirotorSimulator::handleCollisions reads of the partner UAV (src/multirotor_simulator.cpp:339-350)
 struct PosRecord {

@@ -169,6 +169,27 @@ int wait_for_progress(mrs_swarm* s, const volatile unsigned* hw, unsigned index,
   return MRS_OK;
 }
 
+// One tick of mrs_swarm_rollout_tick_device without the fused form (no lists, lists incomplete, no collision tick since the previous
+// step): any collision tick has been evaluated on its own before; one step of the control-rate rollout kernels with this tick's row
+// blocks, then the crash bytes of a block that ends here.  The rows equal those of the fused launch.
+int launch_row_step(mrs_swarm* s, double dt, const RolloutTickDev& row) {
+  s->region_launches++;
+  RolloutRateDev r{};
+  r.cmd = row.cmd, r.obs = row.obs;
+  r.first = row.first, r.count = row.count;
+  r.cmd_stride = row.cmd_stride, r.obs_stride = row.obs_stride;
+  r.cmd_sched = (row.cmd ? row.cmd_word : (row.cmd_word & 32u)) << 24;  // (width 0: no command block starts at this tick)
+  r.obs_sched = row.obs ? row.groups << 24 : 0u;
+  r.mode_bits = row.mode_bits;
+  const int variant = s->n_cascade > 0 ? 0 : 1;
+  if (s->arith == MRS_ARITH_FAST)
+    HIPCHK(mrs_launch_rollout_rate_fast(s->view(), r, dt, 1, 1, 1, variant, s->stream));
+  else
+    HIPCHK(mrs_launch_rollout_rate_literal(s->view(), r, dt, 1, 1, 1, variant, s->stream));
+  if (row.crashed && row.count > 0) return launch_crashed_u8(s, row.first, row.count, row.crashed);
+  return MRS_OK;
+}
+
 // one fused launch: evaluate collision tick `e.eval` (if any) from the lists, then makeStep(e.dt)
 int launch_fused(mrs_swarm* s, const mrs_swarm::TickRec& e) {
   const volatile unsigned* hw = mrs_collide_host_words(s->cwork);
@@ -195,7 +216,12 @@ int launch_fused(mrs_swarm* s, const mrs_swarm::TickRec& e) {
     s->ev_used += 2;
     HIPCHK(hipEventRecord(e0, s->stream));
   }
-  if (s->arith == MRS_ARITH_FAST)
+  if (e.rows) {  // a tick of mrs_swarm_rollout_tick_device: the same launch with the caller's rows of this tick
+    if (s->arith == MRS_ARITH_FAST)
+      HIPCHK(mrs_launch_rollout_tick_fast(v, cd, e.row, e.dt, variant, s->stream));
+    else
+      HIPCHK(mrs_launch_rollout_tick_literal(v, cd, e.row, e.dt, variant, s->stream));
+  } else if (s->arith == MRS_ARITH_FAST)
     HIPCHK(mrs_launch_step_coll_fast(v, cd, e.dt, variant, 0, s->stream));
   else
     HIPCHK(mrs_launch_step_coll_literal(v, cd, e.dt, variant, 0, s->stream));
@@ -268,8 +294,13 @@ int drain(mrs_swarm* s) {
       } else {  // (lists incomplete: dense neighbourhoods) every tick on its own
         if (e.eval.on && (rc = collide_now(s, e.eval, false))) return rc;
         s->p_valid = false;
-        s->region_launches++;
-        if ((rc = launch_part(s, e.dt, 1, 0, (s->n + 63) / 64, 1, s->stream))) return rc;
+        if (e.rows) {
+          if (e.dt != s->table_dt && (rc = upload_types(s, e.dt))) return rc;
+          if ((rc = launch_row_step(s, e.dt, e.row))) return rc;
+        } else {
+          s->region_launches++;
+          if ((rc = launch_part(s, e.dt, 1, 0, (s->n + 63) / 64, 1, s->stream))) return rc;
+        }
       }
       // the pipelined downloads packed behind the no-op took the state of an earlier tick: once more, behind the real launch, every one
       // whose slot still holds its ticket, in the order they were issued
@@ -303,7 +334,7 @@ int settle(mrs_swarm* s) {
 }
 
 // one makeStep of every UAV; the collision tick requested since the previous step (if any) is evaluated by the same launch
-int step_one(mrs_swarm* s, double dt) {
+int step_one(mrs_swarm* s, double dt, const RolloutTickDev* row) {
   int rc;
   if (s->collide_since_step && s->use_lists && s->use_fused) {
     const volatile unsigned* hw = mrs_collide_host_words(s->cwork);
@@ -313,6 +344,7 @@ int step_one(mrs_swarm* s, double dt) {
     if (s->pend.on && !fused_usable(s) && (rc = settle(s))) return rc;  // first tick / after host writes: the pass on its own
     if (fused_usable(s)) {
       mrs_swarm::TickRec e{dt, s->pend, false};
+      if (row) e.rows = true, e.row = *row;
       if (s->pend.on && hw && hw[CTL_WARN] > s->search_mark) {
         // some UAV has used up most of its skin: repeat the search NOW, in stream order — it evaluates the pending collision tick
         // itself — instead of running into the stall a few ticks on (no synchronisation, nothing to replay)
@@ -330,6 +362,7 @@ int step_one(mrs_swarm* s, double dt) {
   if ((rc = settle(s))) return rc;
   s->collide_since_step = false;
   s->p_valid            = false;  // a plain step kernel does not refresh the position records
+  if (row) return launch_row_step(s, dt, *row);
   return launch_step(s, dt, 1);
 }
 

@@ -261,6 +261,73 @@ def rollout_cost(swarm, mode, commands, dt, groups, targets, weights, first=0, h
     return out
 
 
+def rollout_ticks(swarm, mode, commands, dt, crash, rebounce, groups=OBS_POS | OBS_VEL | OBS_QUAT, first=0, out=None, hold=1, obs_every=None,
+                  crashed=None):
+    """B * hold ticks of the whole swarm in one call (mrs_swarm_rollout_tick_device): each tick is a step of every UAV, then the
+    collision pass `swarm.handle_collisions(True, crash, rebounce)`.  UAVs [first, first + count) take command row block j before tick
+    j * hold and keep it for `hold` ticks; after every `obs_every` ticks (default: `hold`) the OBS_* groups of `groups` and the crash
+    flags of the range are reported, taken after the tick's step and before its collision pass.  It is the loop `for t: set_input(...);
+    swarm.tick_n(dt, 1, True, crash, rebounce); gather(...); crashed(...)` with the rows taken between the step and the collision pass,
+    bit for bit in LITERAL, with one host wait per call.
+    commands, out: as in rollout.  crashed: a dense torch.bool or torch.uint8 [B * hold // obs_every, count] tensor, allocated (bool) when
+    None; crashed=False asks for no crash rows.  Returns (rows or None when groups == 0, crashed or None).  The collision pass of the last
+    tick stays pending: the next step or tick evaluates it."""
+    dev = swarm.device()
+    if not isinstance(commands, torch.Tensor) or commands.dim() != 3:
+        raise ValueError("commands must be a [T, count, width] tensor")
+    hold = int(hold)
+    if hold < 1:
+        raise ValueError(f"hold must be at least 1, got {hold}")
+    code = _dtype_code(commands.dtype)
+    blocks, count = commands.shape[0], commands.shape[1]
+    ticks = blocks * hold
+    every = hold if obs_every is None else int(obs_every)
+    if every < 1 or ticks % every != 0:
+        raise ValueError(f"obs_every must be at least 1 and divide the {ticks} ticks of the call, got {every}")
+    width = command_width(mode, commands.shape[2])
+    cstride = _check_steps(commands, "commands", None, count, width, commands.dtype, dev)
+    if mode == ACTUATOR_CMD and count > 1 and cstride != commands.shape[2]:
+        raise ValueError("actuator rows must be dense (row stride == number of motors)")
+    owidth = gather_width(groups)
+    optr, ostride = 0, owidth
+    if groups:
+        if out is None:
+            out = torch.empty((ticks // every, count, owidth), dtype=commands.dtype, device=torch.device("cuda", dev))
+        if isinstance(out, torch.Tensor) and out.dtype != commands.dtype:
+            raise ValueError(f"out has dtype {out.dtype}, the commands {commands.dtype}: one dtype serves both")
+        ostride = _check_steps(out, "out", ticks // every, count, owidth, commands.dtype, dev)
+        optr = out.data_ptr()
+    kptr = 0
+    if crashed is False:
+        crashed = None
+    else:
+        if crashed is None:
+            crashed = torch.empty((ticks // every, count), dtype=torch.bool, device=torch.device("cuda", dev))
+        _check_crash_rows(crashed, ticks // every, count, dev)
+        kptr = crashed.data_ptr()
+    cptr = commands.data_ptr() if width > 0 and count > 0 else 0
+    swarm.rollout_tick_device(first, count, mode, dt, ticks, hold, every, cptr, code, cstride, groups, optr, ostride, kptr, bool(crash),
+                              float(rebounce), _stream(dev))
+    rows = None if not groups else (out[:, :, :owidth] if out.shape[2] > owidth else out)
+    return rows, crashed
+
+
+def _check_crash_rows(t, blocks, rows, device_index):
+    """Refuse `t` unless it is a dense [blocks, rows] torch.bool / torch.uint8 tensor on cuda:`device_index` (block j at byte j * rows)."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"crashed: expected a torch.Tensor, got {type(t).__name__}")
+    if t.device.type != "cuda":
+        raise ValueError(f"crashed is on {t.device}: device-resident calls need a tensor on cuda:{device_index}")
+    if t.device.index != device_index:
+        raise ValueError(f"crashed is on {t.device}, the swarm lives on cuda:{device_index}")
+    if t.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"crashed has dtype {t.dtype}, expected torch.bool or torch.uint8")
+    if t.dim() != 2 or t.shape[0] != blocks or t.shape[1] != rows:
+        raise ValueError(f"crashed: expected a [{blocks}, {rows}] tensor, got shape {tuple(t.shape)}")
+    if (rows > 1 and t.stride(1) != 1) or (blocks > 1 and t.stride(0) != rows):
+        raise ValueError(f"crashed: the crash rows are not dense (strides {tuple(t.stride())}, expected ({rows}, 1))")
+
+
 def crashed(swarm, first=0, count=None, out=None):
     """UavSystem::hasCrashed of UAVs [first, first + count) as a bool tensor on the swarm's device"""
     count = _count(swarm, first, count)

@@ -1,0 +1,189 @@
+"""CPU-side checks of tick rollouts (include/mrs_swarm.h, "tick rollouts"): mrs_swarm_rollout_tick_device is exported and listed, its
+header prototype is the one specified and agrees with the ctypes argtypes, tensors.rollout_ticks refuses CPU tensors, wrong dtypes,
+crash rows that are not dense and wrong block counts before the library is reached, and tests/cpp/rollout_tick_test.cpp compiles.  CPU
+tensors only: no pointer reaches the library.
+
+The call has kernels of its own (rollout_tick_device.inc, MRS_ROLLOUT_TICK_KERNEL lines): exactly four, each with a row in
+test_rollout_tick_gpu.ROLLOUT_TICK_KERNELS and the shape of the single-GPU MRS_STEP_KERNEL_COLL line it mirrors; the file holds no
+step-kernel line and no line of the other rollout macros, so the tables of the earlier tests stay as they are."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import pytest
+
+import test_rollout_tick_gpu as RT
+from test_rollout import CTYPE, ROOT, _Dev
+
+CSRC = os.path.join(ROOT, "mrs_multirotor_simulator_amd", "csrc")
+SRC = os.path.join(CSRC, "rollout_tick_device.inc")
+
+NAMES = ["s", "first", "count", "mode", "dt", "n_ticks", "cmd_every", "obs_every", "dev_cmd", "dtype", "cmd_stride", "groups", "dev_obs",
+         "obs_stride", "dev_crashed", "crash", "rebounce", "ext_stream"]
+TYPES = dict(CTYPE, **{"uint8_t*": C.c_void_p})
+
+# the tick kernel and the single-GPU *_coll kernel of step_device.inc it mirrors
+MIRRORS = {
+    "mrs_uav_rollout_tick_buf": "mrs_uav_step_coll_buf",
+    "mrs_uav_model_rollout_tick_buf": "mrs_uav_model_step_coll_buf",
+    "mrs_uav_rollout_tick": "mrs_uav_step_coll",
+    "mrs_uav_rollout_tick_mixed": "mrs_uav_step_mixed_coll",
+}
+
+
+def test_symbol_is_exported_and_listed(mrs):
+    from mrs_multirotor_simulator_amd import swarm, tensors
+    assert hasattr(C.CDLL(swarm.LIB_PATH), "mrs_swarm_rollout_tick_device")
+    assert "mrs_swarm_rollout_tick_device" in swarm.ABI_SYMBOLS
+    assert callable(getattr(swarm.Swarm, "rollout_tick_device", None)) and callable(getattr(tensors, "rollout_ticks", None))
+
+
+def test_header_prototype_equals_the_argtypes(mrs):
+    from mrs_multirotor_simulator_amd import swarm
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mrs_swarm.h")).read(), flags=re.S)
+    m = re.search(r"int\s+mrs_swarm_rollout_tick_device\(([^)]*)\);", src)
+    assert m, "prototype"
+    params = [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
+    types = [re.match(r"(.*?)\s*\b\w+$", p).group(1).replace(" *", "*") for p in params]
+    assert [p.rsplit(" ", 1)[-1].lstrip("*") for p in params] == NAMES
+    got = swarm.load_library().mrs_swarm_rollout_tick_device.argtypes
+    assert [TYPES[t] for t in types] == list(got), (types, got)
+    # the control-rate call with the crash rows and the collision arguments between obs_stride and the stream
+    rate = swarm.load_library().mrs_swarm_rollout_rate_device.argtypes
+    assert list(got[:14]) + [got[-1]] == list(rate) and list(got[14:17]) == [C.c_void_p, C.c_int32, C.c_double]
+    assert "src/multirotor_simulator.cpp:211-217" in open(os.path.join(ROOT, "include", "mrs_swarm.h")).read()
+
+
+def _lines(path, macro):
+    """the argument lists of the `macro(...)` instantiation lines of a file"""
+    out = {}
+    for line in open(path):
+        m = re.match(rf"{macro}\(\s*(\w+)\s*,\s*(\(.*?\))\s*,\s*(.*)\)\s*$", line.strip())
+        if m:
+            out[m.group(1)] = [m.group(2).replace(" ", "")] + [a.strip() for a in m.group(3).split(",")]
+    return out
+
+
+def test_every_rollout_tick_kernel_has_a_row_and_the_shape_of_its_mirror():
+    tick = _lines(SRC, "MRS_ROLLOUT_TICK_KERNEL")
+    assert len(tick) == 4, sorted(tick)
+    table = set(RT.ROLLOUT_TICK_KERNELS)
+    assert not set(tick) - table, f"tick kernels without a row in ROLLOUT_TICK_KERNELS: {sorted(set(tick) - table)}"
+    assert not table - set(tick), f"rows naming kernels rollout_tick_device.inc no longer compiles: {sorted(table - set(tick))}"
+    for kernel, where in RT.ROLLOUT_TICK_KERNELS.items():
+        for w in where:
+            assert callable(getattr(RT, w.split("[")[0], None)), f"{kernel}: {w} is no test of test_rollout_tick_gpu"
+    # (bounds, CASCADE, UNIFORM, ACC, SU) of the mirrored line, which is a single-GPU one (SHARD == false)
+    coll = _lines(os.path.join(CSRC, "step_device.inc"), "MRS_STEP_KERNEL_COLL")
+    single = {k for k, v in coll.items() if v[-1] == "false"}
+    assert single == set(MIRRORS.values()), sorted(single)
+    assert set(tick) == set(MIRRORS)
+    for name, args in tick.items():
+        assert args == coll[MIRRORS[name]][:-1], (name, args, coll[MIRRORS[name]])
+    for unit in ("step_kernel_fast.hip", "step_kernel_literal.hip"):
+        text = open(os.path.join(CSRC, unit)).read()
+        assert text.rstrip().endswith('#include "rollout_tick_device.inc"'), f"{unit}: the tick kernels come last"
+
+
+def test_no_other_kernel_lines_in_the_file():
+    text = open(SRC).read()
+    assert "MRS_STEP_KERNEL" not in text
+    for macro in ("MRS_ROLLOUT_KERNEL", "MRS_ROLLOUT_RATE_KERNEL", "MRS_ROLLOUT_FORCE_KERNEL", "MRS_ROLLOUT_COST_KERNEL"):
+        assert not re.search(rf"^\s*(#define\s+)?{macro}\(", text, flags=re.M), macro
+    assert "mrs_ro_sched" not in text and "MRS_RO_" not in text, "one launch is one tick: no schedule words"
+
+
+class _Swarm:
+    """stands in for a Swarm on cuda:0: the library call may not be reached"""
+    n = 100
+
+    def device(self):
+        return 0
+
+    def rollout_tick_device(self, *a):
+        raise AssertionError("a refused call reached the library (rollout_tick_device)")
+
+
+def _fakes(monkeypatch):
+    import torch
+
+    class Fake(torch.Tensor):
+        pass
+
+    def on(t, index=0):
+        f = t.as_subclass(Fake)
+        f._fake_dev = _Dev(index)
+        return f
+
+    monkeypatch.setattr(Fake, "device", property(lambda self: getattr(self, "_fake_dev", _Dev(0))), raising=False)
+    return on
+
+
+def test_rollout_ticks_refuses_bad_tensors(monkeypatch):
+    """CPU tensors dressed as cuda tensors (only .device is faked; nothing is launched)"""
+    import torch
+    from mrs_multirotor_simulator_amd import tensors as T
+    on = _fakes(monkeypatch)
+    g, f64, pos = _Swarm(), torch.float64, T.OBS_POS  # (mode 10: POSITION_CMD)
+
+    def cmd(**kw):
+        return on(torch.zeros(6, 10, 4, dtype=kw.get("dtype", f64)), kw.get("index", 0))  # B = 6
+
+    def out(blocks=6, width=3):
+        return on(torch.zeros(blocks, 10, width, dtype=f64))
+
+    def cr(blocks=6, rows=10, dtype=torch.bool):
+        return on(torch.zeros(blocks, rows, dtype=dtype))
+
+    cases = [
+        (torch.zeros(6, 10, 4, dtype=f64), dict(out=out(), crashed=cr()), "is on cpu"),                    # CPU commands
+        (cmd(index=1), dict(out=out(), crashed=cr()), "the swarm lives on cuda:0"),                        # another device
+        (cmd(dtype=torch.float16), dict(out=out(), crashed=cr()), "float32 or torch.float64"),             # dtype
+        (cmd(dtype=torch.float32), dict(out=out(), crashed=cr()), "one dtype serves both"),                # mismatched dtypes
+        (on(torch.zeros(6, 10, 3, dtype=f64)), dict(out=out(), crashed=cr()), r">= 4\] tensor"),           # too narrow
+        (on(torch.zeros(10, 4, dtype=f64)), dict(out=out(), crashed=cr()), r"\[T, count, width\]"),         # no tick dimension
+        (cmd(), dict(out=torch.zeros(6, 10, 3, dtype=f64), crashed=cr()), "is on cpu"),                    # out on the CPU
+        (cmd(), dict(out=out(5), crashed=cr()), r"\[6, 10, >= 3\]"),                                       # out of another block count
+        (cmd(), dict(out=out(6, 2), crashed=cr()), r">= 3\]"),                                             # out too narrow
+        (cmd(), dict(out=out(), crashed=torch.zeros(6, 10, dtype=torch.bool)), "crashed is on cpu"),       # crash rows on the CPU
+        (cmd(), dict(out=out(), crashed=on(torch.zeros(6, 10, dtype=torch.bool), 1)), "crashed is on cuda:1"),
+        (cmd(), dict(out=out(), crashed=cr(dtype=torch.int32)), "torch.bool or torch.uint8"),              # crash dtype
+        (cmd(), dict(out=out(), crashed=cr(dtype=torch.float32)), "torch.bool or torch.uint8"),
+        (cmd(), dict(out=out(), crashed=cr(5)), r"crashed: expected a \[6, 10\]"),                         # wrong block count
+        (cmd(), dict(out=out(), crashed=cr(6, 11)), r"crashed: expected a \[6, 10\]"),                     # wrong row count
+        (cmd(), dict(out=out(), crashed=on(torch.zeros(60, dtype=torch.bool))), r"crashed: expected a \[6, 10\]"),
+        (cmd(), dict(out=out(), crashed=on(torch.zeros(6, 20, dtype=torch.bool)[:, ::2])), "not dense"),   # strided bytes
+        (cmd(), dict(out=out(), crashed=on(torch.zeros(6, 12, dtype=torch.bool)[:, :10])), "not dense"),   # padded blocks
+        (cmd(), dict(out=out(), crashed=on(torch.zeros(10, 6, dtype=torch.uint8).t())), "not dense"),      # transposed
+        (cmd(), dict(out=out(), crashed=[[0] * 10] * 6), "crashed: expected a torch.Tensor"),
+        (cmd(), dict(out=out(3), crashed=cr(6), hold=2, obs_every=4), r"crashed: expected a \[3, 10\]"),   # the decimated block count
+        (cmd(), dict(out=out(12), crashed=cr(3), hold=2, obs_every=4), r"\[3, 10, >= 3\]"),
+        (cmd(), dict(out=out(), crashed=cr(), hold=0), "hold must be at least 1"),
+        (cmd(), dict(out=out(), crashed=cr(), hold=2, obs_every=0), "obs_every must be at least 1 and divide"),
+        (cmd(), dict(out=out(), crashed=cr(), hold=2, obs_every=5), "obs_every must be at least 1 and divide the 12 ticks"),
+    ]
+    for c, kw, msg in cases:
+        with pytest.raises(ValueError, match=msg):
+            T.rollout_ticks(g, 10, c, 0.001, True, 100.0, pos, **kw)
+    with pytest.raises(ValueError, match="actuator rows must be dense"):
+        T.rollout_ticks(g, T.ACTUATOR_CMD, on(torch.zeros(6, 10, 6, dtype=f64)[:, :, :4]), 0.001, True, 100.0, pos, out=out(), crashed=cr())
+    with pytest.raises(ValueError, match="commands must be"):
+        T.rollout_ticks(g, 10, [[[0.0] * 4] * 10] * 6, 0.001, True, 100.0, pos, out=out(), crashed=cr())
+    # a well-formed call passes every check of the tensor layer: it is the stand-in's library call that raises (no GPU: no stream to
+    # ask for), with bool or uint8 crash rows, without crash rows and without observation rows
+    monkeypatch.setattr(T, "_stream", lambda dev: 0)
+    for kw in (dict(out=out(), crashed=cr()), dict(out=out(), crashed=cr(dtype=torch.uint8)), dict(out=out(), crashed=False),
+               dict(out=out(3), crashed=cr(3), hold=2, obs_every=4), dict(out=out(1), crashed=cr(1), obs_every=6)):
+        with pytest.raises(AssertionError, match="rollout_tick_device"):
+            T.rollout_ticks(g, 10, cmd(), 0.001, True, 100.0, pos, **kw)
+    with pytest.raises(AssertionError, match="rollout_tick_device"):
+        T.rollout_ticks(g, 10, cmd(), 0.001, False, 100.0, 0, crashed=cr())
+
+
+def test_rollout_tick_test_compiles(mrs, tmp_path):
+    from mrs_multirotor_simulator_amd import swarm
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-DMRS_NO_EIGEN", "-D__HIP_PLATFORM_AMD__", "-I",
+                           os.path.join(ROOT, "include"), "-I", "/opt/rocm/include", os.path.join(ROOT, "tests", "cpp", "rollout_tick_test.cpp"),
+                           "-o", str(tmp_path / "rollout_tick_test"), "-L", os.path.dirname(swarm.LIB_PATH), "-lmrs_swarm", "-L", "/opt/rocm/lib",
+                           "-lamdhip64", "-lpthread"])

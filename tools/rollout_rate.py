@@ -40,9 +40,25 @@ same T steps three ways, alternating:
 and prints the bytes each form moves between the kernels and the caller's tensors.  A fourth swarm replays the horizon with FP64 rows, in
 chunks of 40 steps, and the restatement of the ABI comment is applied to them in torch (element-wise FP64 kernels, one rounding each):
 f's cost must equal it bit for bit, and the final states of b and f must agree.
+
+With `--ticks` (anywhere on the command line) the tool measures the TICK rollout (mrs_swarm_rollout_tick_device): T ticks of timerMain —
+a step of every UAV, then the collision pass in elastic mode — on the `position+collisions` inputs of bench.py, POSITION_CMD rows held for
+`hold` ticks, POS | VEL | QUAT rows (FP32) every `hold` ticks, with and without crash rows.  Defaults: sizes 100000, T = 200, arith fast,
+and the seventh argument is a list of holds (1,10).  The same T ticks three ways, alternating, timed with the host clock around work
+that ends in a synchronisation of the device:
+  tick     tensors.rollout_ticks(cmd, dt, False, 100.0, out=, hold=hold, crashed=)            (one call, one host wait)
+  loop     per tick: tensors.set_input every `hold` ticks; step_n(dt, 1); every `hold` ticks tensors.gather and tensors.crashed;
+           handle_collisions(True, False, 100.0)                                               (the calls the tick rollout stands for)
+  bare     tick_n(dt, T, True, False, 100.0), then synchronize: no commands, no rows              (the floor)
+and prints us per tick (median, min-max), the bytes of rows per tick, and whether the call beats the loop in every round.  In LITERAL
+`tick` and `loop` must end bit-identical (rows, crash bytes and state): the tool asserts it.  The fifth argument selects among
+tick,loop,bare (e.g. `bare` alone, with MRS_SWARM_LIB naming the library of another commit).
+
+    python tools/rollout_rate.py --ticks [sizes=100000] [T=200] [reps=5] [-] [forms=tick,loop,bare] [arith=fast] [holds=1,10]
 """
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -65,6 +81,12 @@ def commands(mode, n, steps, rng):
 def main():
     import torch
     from mrs_multirotor_simulator_amd import tensors as T
+    if "--ticks" in sys.argv:
+        sys.argv.remove("--ticks")
+        return main_ticks([int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [100_000], int(sys.argv[2]) if len(sys.argv) > 2 else 200,
+                          int(sys.argv[3]) if len(sys.argv) > 3 else 5, sys.argv[6] if len(sys.argv) > 6 else "fast",
+                          [int(h) for h in (sys.argv[7] if len(sys.argv) > 7 else "1,10").split(",")],
+                          sys.argv[5].split(",") if len(sys.argv) > 5 else ["tick", "loop", "bare"])
     cost = "--cost" in sys.argv
     if cost:
         sys.argv.remove("--cost")
@@ -343,6 +365,86 @@ def main_force(sizes, steps, reps, modes, forms, arith, hold, every, fhold):
             print(line, flush=True)
             for g in swarms.values():
                 g.close()
+
+
+def main_ticks(sizes, ticks, reps, arith, holds, forms):
+    import torch
+    from mrs_multirotor_simulator_amd import tensors as T
+    groups = T.OBS_POS | T.OBS_VEL | T.OBS_QUAT
+    ow = T.gather_width(groups)
+    rng = np.random.default_rng(5)
+    rebounce = 100.0
+    assert set(forms) <= {"tick", "loop", "bare"}, forms
+    print(f"tick rollout of T = {ticks} ticks (step + elastic collision pass), POSITION_CMD, FP32 commands and POS|VEL|QUAT rows, x500, "
+          f"{arith.upper()}; {reps} rounds after a warm-up, alternating; host clock around a device synchronisation")
+    for n in sizes:
+        st, goal = bench.make_inputs(n, "position+collisions", seed=3)
+        p = M.model_params("x500", ground_enabled=True, ground_z=0.0)
+        for hold in holds:
+            assert hold >= 1 and ticks % hold == 0, "hold must divide T"
+            for crash_rows in (False, True):
+                swarms = {}
+                for f in forms:
+                    g = M.Swarm(n, arith=M.ARITH_FAST if arith == "fast" else M.ARITH_LITERAL)
+                    g.construct(0, n, p)
+                    g.set_state(0, n, st["x"], st["v"], st["R"], st["omega"], st["motor_rpm"])
+                    g.set_input(0, n, M.POSITION_CMD, goal)
+                    swarms[f] = g
+                dev = torch.device("cuda", swarms[forms[0]].device())
+                cmd = torch.tensor(goal[None] + rng.normal(0.0, 0.05, (ticks // hold, n, 4)), dtype=torch.float32, device=dev)
+                obs = {f: torch.empty((ticks // hold, n, ow), dtype=torch.float32, device=dev) for f in forms if f != "bare"}
+                cr = {f: torch.zeros((ticks // hold, n), dtype=torch.bool, device=dev) for f in forms if f != "bare"}
+
+                def run(form):
+                    g = swarms[form]
+                    if form == "tick":
+                        T.rollout_ticks(g, M.POSITION_CMD, cmd, DT, False, rebounce, groups, out=obs[form], hold=hold,
+                                        crashed=cr[form] if crash_rows else False)
+                    elif form == "bare":
+                        g.tick_n(DT, ticks, True, False, rebounce)
+                    else:
+                        for t in range(ticks):
+                            if t % hold == 0:
+                                T.set_input(g, M.POSITION_CMD, cmd[t // hold])
+                            g.step_n(DT, 1)
+                            if (t + 1) % hold == 0:
+                                T.gather(g, groups, out=obs[form][t // hold])
+                                if crash_rows:
+                                    T.crashed(g, out=cr[form][t // hold])
+                            g.handle_collisions(True, False, rebounce)
+                    g.synchronize()
+                    torch.cuda.synchronize(dev)
+
+                for f in forms:  # warm-up: code objects, the type table, torch kernels, the first neighbour search
+                    run(f)
+                if arith != "fast" and "tick" in forms and "loop" in forms:  # the first run of both forms starts from the same state
+                    assert bits_equal(obs["loop"], obs["tick"]) and torch.equal(cr["loop"], cr["tick"]), f"{n} hold {hold}: rows of loop and tick differ"
+                    a, b = swarms["loop"].get_states(), swarms["tick"].get_states()
+                    for fld in a.dtype.names:
+                        assert np.array_equal(a[fld].view(np.uint64) if a[fld].dtype == np.float64 else a[fld],
+                                              b[fld].view(np.uint64) if b[fld].dtype == np.float64 else b[fld]), f"{n} hold {hold}: {fld} differs"
+                times = {f: [] for f in forms}
+                for _ in range(reps):
+                    for f in forms:
+                        torch.cuda.synchronize(dev)
+                        t0 = time.perf_counter()
+                        run(f)
+                        times[f].append((time.perf_counter() - t0) * 1e6 / ticks)
+                line = f"  {n:>8d} UAVs  hold {hold:3d}  crash rows {'yes' if crash_rows else 'no ':3s}"
+                for f in forms:
+                    line += f"  {f} {float(np.median(times[f])):7.2f} us/tick ({min(times[f]):.2f}-{max(times[f]):.2f})"
+                row_bytes = (n * 4 * 4 + n * ow * 4 + (n if crash_rows else 0)) / hold
+                line += f"  rows {row_bytes / 1e6:.2f} MB/tick"
+                if "tick" in forms and "bare" in forms:
+                    line += f"  tick - bare {float(np.median(times['tick'])) - float(np.median(times['bare'])):+.2f} us"
+                if "tick" in forms and "loop" in forms:
+                    line += "  tick beats loop" if max(times["tick"]) < min(times["loop"]) else "  TICK DOES NOT BEAT LOOP"
+                for f in forms:
+                    stats = swarms[f].fused_stats()
+                    line += f"  ({f}: {stats[0]} fused launches, {stats[1]} stalls, {stats[2]} replayed, {stats[3]} searches ahead)"
+                print(line, flush=True)
+                for g in swarms.values():
+                    g.close()
 
 
 def main_cost(sizes, steps, reps, modes, arith, hold, every):

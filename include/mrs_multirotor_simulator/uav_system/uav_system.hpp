@@ -822,6 +822,21 @@ public:
     mrs_throw_on_error(mrs_swarm_rollout_tick_device(s_, first, count, mode, dt, n_ticks, cmd_every, obs_every, dev_cmd, dtype, cmd_stride, groups,
                                                      dev_obs, obs_stride, dev_crashed, crash ? 1 : 0, rebounce, stream));
   }
+  // rolloutCostDevice whose command rows are nominal commands: at the start of command block b the command of UAV first + k is
+  // cmd row (b, k) + G (ref row (b, k) - the FP64 observation row of fb_groups before the step), formed in the step kernel.  dev_gain:
+  // gain_per_uav false: dense [gain_blocks, W_c, W_o]; true: dense [gain_blocks, W_c, W_o, count], UAV-minor.  dev_ref: rows as the
+  // cost targets (ref_stride 0: one shared dense row per block).  gain_blocks / ref_blocks: 1 or n_steps / cmd_every.
+  // cost_groups 0 with null dev_target / dev_weight / dev_cost: no cost, the result is the state
+  void rolloutFeedbackDevice(int first, int count, int mode, double dt, int n_steps, int cmd_every, int cost_every, const void* dev_cmd, int dtype,
+                             int cmd_stride, uint32_t fb_groups, const void* dev_gain, bool gain_per_uav, int gain_blocks, const void* dev_ref,
+                             int ref_stride, int ref_blocks, uint32_t cost_groups = 0, const void* dev_target = nullptr, int target_stride = 0,
+                             const void* dev_weight = nullptr, int weight_stride = 0, double* dev_cost = nullptr, bool accumulate = false,
+                             void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_rollout_feedback_device(s_, first, count, mode, dt, n_steps, cmd_every, cost_every, dev_cmd, dtype, cmd_stride,
+                                                         fb_groups, dev_gain, gain_per_uav ? 1 : 0, gain_blocks, dev_ref, ref_stride, ref_blocks,
+                                                         cost_groups, dev_target, target_stride, dev_weight, weight_stride, dev_cost,
+                                                         accumulate ? 1 : 0, stream));
+  }
   // the whole simulation state of UAVs [first, first + count) into dev_records[0 .. count-1] (device memory, 16-B aligned)
   void saveDevice(int first, int count, mrs_uav_snapshot_t* dev_records, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_save_device(s_, first, count, dev_records, stream));

@@ -696,6 +696,53 @@ int mrs_swarm_rollout_cost_device(mrs_swarm_t* s, int32_t first, int32_t count, 
                                   const void* dev_weight, int32_t weight_stride, /* 0: one weight row for every evaluation */
                                   double* dev_cost, int32_t accumulate, void* ext_stream);
 
+/* ---- feedback rollouts: closed-loop linear state feedback inside the rollout (the samples are controllers, not command sequences) ----
+ * mrs_swarm_rollout_cost_device whose command rows are NOMINAL commands: the command written at the start of a command block is
+ * cmd_row + G (ref_row - obs_row), formed in the step kernel from the state it holds.  W_o = the gather width of fb_groups (at least
+ * one group), W_c = the command width of `mode` as the rollouts define it (MRS_ACTUATOR_CMD: the motors of the row, i.e. cmd_stride,
+ * at most MRS_MAX_MOTORS); B = n_steps / cmd_every command blocks.  At the top of step t, when t % cmd_every == 0, with b = t / cmd_every,
+ * for UAV first + k:
+ *   o[0 .. W_o) = the FP64 observation row of fb_groups that mrs_swarm_gather_device(MRS_DTYPE_F64) would return at this moment (the
+ *                 state BEFORE the step)
+ *   for j ascending:  e[j] = ref[b][k][j] - o[j]
+ *   for each c < W_c: acc = cmd[b][k][c];  for j ascending: acc = acc + (G[b][k][c][j] * e[j]);  u[c] = acc
+ *   u -> the command columns, as mrs_swarm_set_input_device(mode, u) stores a row
+ * Every operation is FP64 with one rounding and no fused multiply-add, in both arithmetic flavours; FP32 inputs are widened exactly.
+ * No column is skipped and nothing is special-cased: a zero gain times a non-finite residual is what IEEE makes of it, and the zeros
+ * of the MRS_OBS_RPM group past n_motors take part.  A NaN setpoint or observation is its residual with its own sign and payload (the
+ * setpoint's if both are NaN), as a host subtraction propagates it, so that the loop run with host arithmetic writes the same command
+ * bits for a UAV whose state is NaN.  Inside a command block the command stays as written: the feedback is sampled at
+ * the command rate, like a real control loop.  The call stands for the loop
+ *   mrs_swarm_gather_device(fb_groups, MRS_DTYPE_F64) -> the lines above -> mrs_swarm_set_input_device(mode, u) -> cmd_every steps
+ * with the evaluations of mrs_swarm_rollout_cost_device (cost_every, cost_groups, dev_target, dev_weight, dev_cost, accumulate) beside
+ * it, and gives that loop's bits.  cost_groups == 0 with dev_target, dev_weight and dev_cost NULL is a pure closed-loop run whose
+ * result is the swarm's state.  A UAV on hold is not stepped; its command is still formed (from its unchanged state) and written and
+ * its cost evaluated; crashed UAVs get what the loop gives them.  The feedback has no memory: a horizon cut into two calls, the second
+ * with accumulate != 0, gives the bits of one call.
+ * Layouts (one dtype serves commands, gains, setpoints, targets and weights; dev_cost is FP64):
+ *   dev_cmd, dev_target, dev_weight   as mrs_swarm_rollout_cost_device
+ *   dev_ref      setpoint rows, as the cost targets: row (b, k) at element ((size_t)b * count + k) * ref_stride; ref_stride == 0: all
+ *                UAVs share ONE dense row of W_o elements per block ([ref_blocks, W_o])
+ *   dev_gain     gain_per_uav == 0: dense row-major [gain_blocks, W_c, W_o], one matrix for all UAVs;
+ *                gain_per_uav == 1: dense [gain_blocks, W_c, W_o, count], UAV-MINOR: G[b][k][c][j] at element
+ *                ((b * W_c + c) * W_o + j) * count + k.  A UAV's gain is W_c * W_o elements (4 x 18 doubles: 576 B, more than the 492 B
+ *                a step moves); with one matrix per UAV contiguous every load of a 64-lane wave would touch 64 cache lines, UAV-minor
+ *                makes each of the W_c * W_o loads one coalesced 512-B request
+ *   gain_blocks, ref_blocks   B (a block per command block) or 1 (one block serves the whole call)
+ * Everything else (the step, the mode, the stream fence, launch cutting, refusal on a sharded swarm, the argument checks before any
+ * launch) is the contract of mrs_swarm_rollout_cost_device, and so are its refusals, plus, as MRS_ERR_ARG with nothing changed: a mode
+ * without a payload, fb_groups without a group or with unknown bits, a NULL dev_gain or dev_ref, gain_per_uav other than 0 or 1,
+ * gain_blocks or ref_blocks that are neither 1 nor B, a ref_stride that is neither 0 nor at least W_o, cost_groups == 0 with a cost
+ * pointer, and pointers that are not device memory of the swarm's device or too small for their rows. */
+int mrs_swarm_rollout_feedback_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every,
+                                      int32_t cost_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t fb_groups,
+                                      const void* dev_gain, int32_t gain_per_uav, /* 0: [Bg, W_c, W_o] | 1: [Bg, W_c, W_o, count] */
+                                      int32_t gain_blocks,                        /* 1 or B */
+                                      const void* dev_ref, int32_t ref_stride,    /* 0: one shared row per block ([Bg, W_o]) */
+                                      int32_t ref_blocks,                         /* 1 or B */
+                                      uint32_t cost_groups, const void* dev_target, int32_t target_stride, const void* dev_weight,
+                                      int32_t weight_stride, double* dev_cost, int32_t accumulate, void* ext_stream);
+
 /* ---- tick rollouts: timerMain over n_ticks ticks in one call — makeStep of every UAV, then handleCollisions — with device rows ----
  * MultirotorSimulator::timerMain (src/multirotor_simulator.cpp:211-217) is makeStep for every UAV, then handleCollisions (:295-359).  A
  * swarm policy or a multi-agent planner needs the contacts, the rebounce forces and the crash flags inside its horizon.  Equals, bit for

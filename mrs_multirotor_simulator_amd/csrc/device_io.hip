@@ -356,11 +356,20 @@ struct CostArgs {
   int32_t     accumulate;
 };
 
+// what mrs_swarm_rollout_feedback_device adds to a cost rollout (rollout_locked; `groups` are then the cost groups and may be 0: no cost)
+struct FeedbackArgs {
+  uint32_t    groups;
+  const void* gain;
+  int32_t     gain_per_uav, gain_blocks;
+  const void* ref;
+  int32_t     ref_stride, ref_blocks;
+};
+
 // the rollout entry points, under the caller's lock (MRS_ENTER's settle after the argument checks: a refused call launches nothing)
 static int rollout_locked(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every, int32_t obs_every,
                           int32_t force_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, const void* dev_force, int32_t force_stride,
                           uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream, bool forced, const char* who,
-                          const CostArgs* cost = nullptr) {
+                          const CostArgs* cost = nullptr, const FeedbackArgs* fb = nullptr) {
   int rc = check_range(s, first, count);
   if (rc) return rc;
   if (s->comm_world > 0) return fail(MRS_ERR_ARG, std::string(who) + ": not on a sharded swarm");
@@ -379,7 +388,25 @@ static int rollout_locked(mrs_swarm_t* s, int32_t first, int32_t count, int32_t 
   int32_t obs_width = 0;
   if ((rc = mrs_swarm_gather_width(groups, &obs_width))) return rc;
   if (!cost && groups != 0u && obs_stride < obs_width) return fail(MRS_ERR_ARG, "obs_stride smaller than the width of the selected groups");
-  if (cost) {
+  const bool costed = cost && !(fb && groups == 0u);  // (a feedback rollout without cost groups: a pure closed-loop run)
+  int32_t    fb_width = 0;
+  if (fb) {
+    if (width < 1) return fail(MRS_ERR_ARG, "a feedback rollout needs a mode with a payload");
+    if ((rc = mrs_swarm_gather_width(fb->groups, &fb_width))) return rc;
+    if (fb_width < 1) return fail(MRS_ERR_ARG, "no feedback group selected: fb_groups must select at least one observation group");
+    if (!fb->gain) return fail(MRS_ERR_ARG, "dev_gain: null pointer");
+    if (!fb->ref) return fail(MRS_ERR_ARG, "dev_ref: null pointer");
+    if (fb->gain_per_uav != 0 && fb->gain_per_uav != 1) return fail(MRS_ERR_ARG, "gain_per_uav must be 0 (shared gains) or 1");
+    if (fb->gain_blocks != 1 && fb->gain_blocks != n_steps / cmd_every)
+      return fail(MRS_ERR_ARG, "gain_blocks must be 1 or the number of command blocks");
+    if (fb->ref_blocks != 1 && fb->ref_blocks != n_steps / cmd_every)
+      return fail(MRS_ERR_ARG, "ref_blocks must be 1 or the number of command blocks");
+    if (fb->ref_stride != 0 && fb->ref_stride < fb_width)
+      return fail(MRS_ERR_ARG, "ref_stride must be 0 (shared rows) or at least the width of the feedback groups");
+    if (!costed && (cost->target || cost->weight || cost->cost))
+      return fail(MRS_ERR_ARG, "cost_groups == 0 takes no dev_target, dev_weight or dev_cost");
+  }
+  if (costed) {
     if (groups == 0u) return fail(MRS_ERR_ARG, "no observation group selected: a cost needs columns");
     if (!cost->target) return fail(MRS_ERR_ARG, "dev_target: null pointer");
     if (!cost->weight) return fail(MRS_ERR_ARG, "dev_weight: null pointer");
@@ -397,7 +424,14 @@ static int rollout_locked(mrs_swarm_t* s, int32_t first, int32_t count, int32_t 
     if (!cost && groups != 0u &&
         (rc = check_device_ptr(s, dev_obs, ((obs_rows - 1) * (size_t)obs_stride + (size_t)obs_width) * dtype_bytes(dtype), "dev_obs")))
       return rc;
-    if (cost) {  // (obs_rows: one target row per evaluation and UAV, unless the rows are shared)
+    if (fb) {  // 64-bit: blocks x payload x row width x count can pass 2^31 elements
+      const size_t gains = (size_t)fb->gain_blocks * (size_t)width * (size_t)fb_width * (fb->gain_per_uav ? (size_t)count : (size_t)1);
+      const size_t refs  = fb->ref_stride ? ((size_t)fb->ref_blocks * (size_t)count - 1) * (size_t)fb->ref_stride + (size_t)fb_width
+                                          : (size_t)fb->ref_blocks * (size_t)fb_width;
+      if ((rc = check_device_ptr(s, fb->gain, gains * dtype_bytes(dtype), "dev_gain"))) return rc;
+      if ((rc = check_device_ptr(s, fb->ref, refs * dtype_bytes(dtype), "dev_ref"))) return rc;
+    }
+    if (costed) {  // (obs_rows: one target row per evaluation and UAV, unless the rows are shared)
       const size_t evals = (size_t)(n_steps / obs_every), w = (size_t)obs_width;
       const size_t tgt   = cost->target_stride ? (obs_rows - 1) * (size_t)cost->target_stride + w : evals * w;
       const size_t wt    = cost->weight_stride ? (evals - 1) * (size_t)cost->weight_stride + w : w;
@@ -428,6 +462,31 @@ static int rollout_locked(mrs_swarm_t* s, int32_t first, int32_t count, int32_t 
   s->collide_since_step = false;
   s->p_valid            = false;  // (plain steps do not refresh the position records)
   const int variant = s->n_cascade > 0 ? 0 : 1;  // 0 all input modes | 1 model only
+  if (fb) {  // the command is formed in the kernel: the kernels of rollout_feedback_device.inc, whatever the rates are
+    if (count > 0 && costed && !cost->accumulate) HIPCHK(hipMemsetAsync(cost->cost, 0, (size_t)count * sizeof(double), s->stream));  // (+0.0)
+    RolloutFeedbackDev r{};
+    r.cmd = dev_cmd, r.gain = fb->gain, r.ref = fb->ref;
+    r.first = first, r.count = count, r.cmd_stride = cmd_stride;
+    r.cmd_sched = ((uint32_t)width | (dtype == MRS_DTYPE_F32 ? 32u : 0u)) << 24;
+    r.mode_bits = (uint32_t)mode << FLAG_MODE_SHIFT;
+    if (costed) {
+      r.target = cost->target, r.weight = cost->weight, r.cost = cost->cost;
+      r.cost_sched = count > 0 ? groups << 24 : 0u;
+      r.tgt_row = cost->target_stride, r.wt_row = cost->weight_stride;
+      r.tgt_blk = cost->target_stride ? (uint64_t)count * (uint64_t)cost->target_stride : (uint64_t)obs_width;
+    }
+    const uint64_t per = fb->gain_per_uav ? (uint64_t)count : 1u;
+    r.gain_col = (uint32_t)per, r.gain_lane = fb->gain_per_uav ? 1 : 0;
+    r.gain_blk = fb->gain_blocks == 1 ? 0u : (uint64_t)width * (uint64_t)fb_width * per;
+    r.ref_row  = fb->ref_stride;
+    r.ref_blk  = fb->ref_blocks == 1 ? 0u : fb->ref_stride ? (uint64_t)count * (uint64_t)fb->ref_stride : (uint64_t)fb_width;
+    r.fb_word  = fb->groups | (uint32_t)fb_width << 8;
+    if (s->arith == MRS_ARITH_FAST)
+      HIPCHK(mrs_launch_rollout_feedback_fast(s->view(), r, dt, n_steps, cmd_every, obs_every, variant, s->stream));
+    else
+      HIPCHK(mrs_launch_rollout_feedback_literal(s->view(), r, dt, n_steps, cmd_every, obs_every, variant, s->stream));
+    return fence_out(s, ext);
+  }
   if (cost) {  // evaluations in place of observation rows: the kernels of rollout_cost_device.inc, whatever the rates are
     if (count > 0 && !cost->accumulate) HIPCHK(hipMemsetAsync(cost->cost, 0, (size_t)count * sizeof(double), s->stream));  // (+0.0)
     RolloutCostDev r{};
@@ -513,6 +572,18 @@ int mrs_swarm_rollout_cost_device(mrs_swarm_t* s, int32_t first, int32_t count, 
   const CostArgs cost{dev_target, target_stride, dev_weight, weight_stride, dev_cost, accumulate};
   return rollout_locked(s, first, count, mode, dt, n_steps, cmd_every, cost_every, 0, dev_cmd, dtype, cmd_stride, nullptr, 0, groups, nullptr, 0, ext_stream,
                         false, "mrs_swarm_rollout_cost_device", &cost);
+}
+
+int mrs_swarm_rollout_feedback_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every,
+                                      int32_t cost_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t fb_groups,
+                                      const void* dev_gain, int32_t gain_per_uav, int32_t gain_blocks, const void* dev_ref, int32_t ref_stride,
+                                      int32_t ref_blocks, uint32_t cost_groups, const void* dev_target, int32_t target_stride,
+                                      const void* dev_weight, int32_t weight_stride, double* dev_cost, int32_t accumulate, void* ext_stream) {
+  MRS_LOCK(s);
+  const CostArgs     cost{dev_target, target_stride, dev_weight, weight_stride, dev_cost, accumulate};
+  const FeedbackArgs fb{fb_groups, dev_gain, gain_per_uav, gain_blocks, dev_ref, ref_stride, ref_blocks};
+  return rollout_locked(s, first, count, mode, dt, n_steps, cmd_every, cost_every, 0, dev_cmd, dtype, cmd_stride, nullptr, 0, cost_groups, nullptr, 0,
+                        ext_stream, false, "mrs_swarm_rollout_feedback_device", &cost, &fb);
 }
 
 // timerMain over n_ticks ticks with caller rows: every tick is step_one (tick_single.hip) with the row blocks of that tick, then the

@@ -55,6 +55,10 @@ extern "C" hipError_t mrs_launch_rollout_cost_fast(SwarmDev sw, RolloutCostDev r
                                                      hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_tick_literal(SwarmDev sw, CollDev cd, RolloutTickDev r, double dt, int variant, hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_tick_fast(SwarmDev sw, CollDev cd, RolloutTickDev r, double dt, int variant, hipStream_t st);
+extern "C" hipError_t mrs_launch_rollout_feedback_literal(SwarmDev sw, RolloutFeedbackDev r, double dt, int n_steps, int cmd_every, int cost_every,
+                                                            int variant, hipStream_t st);
+extern "C" hipError_t mrs_launch_rollout_feedback_fast(SwarmDev sw, RolloutFeedbackDev r, double dt, int n_steps, int cmd_every, int cost_every,
+                                                         int variant, hipStream_t st);
 extern "C" hipError_t mrs_launch_pid_probe_literal(const double*, const double*, const double*, const double*, const double*, double*, int, int, hipStream_t);
 extern "C" hipError_t mrs_launch_pid_probe_fast(const double*, const double*, const double*, const double*, const double*, double*, int, int, hipStream_t);
 extern "C" hipError_t mrs_launch_pid_update_probe_literal(const double*, double*, const double*, const double*, double*, int, hipStream_t);

@@ -139,3 +139,74 @@ __device__ __forceinline__ double mrs_obs_row_cost(const Src& src, const uint32_
   }
   return term;
 }
+
+// Linear state feedback on the FP64 row of `groups` (the values mrs_obs_row<double> would write, in its column order): on entry u[c]
+// holds the nominal command of payload element c < wc, on return
+//   for col ascending: e = ref[col] - row[col];  for each c < wc: u[c] = u[c] + (G[c][col] * e)
+// which is, accumulator by accumulator, the sum over ascending columns of the contract (mrs_swarm_rollout_feedback_device): the column
+// is the outer loop here so that one residual and the wc accumulators are live, never the row.  G[c][col] is read at
+// gain[c * g_row + col * g_col] (shared gains: g_col 1, g_row the row width, a wave-uniform address; per-UAV gains: g_col the UAV
+// count, the lane's own element behind a coalesced 512-B request per (c, col)).  All of it FP64 and uncontracted; T = float inputs are
+// widened exactly.  No column is skipped and nothing is special-cased, as in mrs_obs_row_cost, and the values and products go through
+// mrs_unfused for the reason given there.
+template <int NC, typename T, class Src>
+__device__ __forceinline__ void mrs_obs_row_feedback(const Src& src, const uint32_t groups, const T* ref, const T* gain, const size_t g_col,
+                                                     const size_t g_row, const int wc, double (&u)[NC]) {
+#pragma clang fp contract(off)
+  double v[3], R[9];
+  const auto col = [&](double value) {
+    // A NaN operand is the residual, bits as they are (the setpoint's if both are NaN), which is what a host subtraction makes of it:
+    // gfx950 forms r - o as r + (-o), and the negation would flip the sign bit of a NaN observation on its way into the command.
+    const double r = (double)*ref, o = mrs_unfused(value);
+    const double d = r - o;
+    const double e = r != r ? r : (o != o ? o : d);
+#pragma unroll
+    for (int c = 0; c < NC; c++)
+      if (c < wc) u[c] = u[c] + mrs_unfused((double)gain[(size_t)c * g_row] * e);
+    ref++;
+    gain += g_col;
+  };
+  if (groups & (MRS_OBS_VEL | MRS_OBS_VEL_BODY)) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) v[c] = src.v(c);
+  }
+  if (groups & (MRS_OBS_VEL_BODY | MRS_OBS_ROT | MRS_OBS_QUAT)) {
+#pragma unroll
+    for (int c = 0; c < 9; c++) R[c] = src.R(c);
+  }
+  if (groups & MRS_OBS_POS) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) col(src.x(c));
+  }
+  if (groups & MRS_OBS_VEL) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) col(v[c]);
+  }
+  if (groups & MRS_OBS_VEL_BODY) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) col(body_velocity(R, v, c));
+  }
+  if (groups & MRS_OBS_ROT) {
+#pragma unroll
+    for (int c = 0; c < 9; c++) col(R[c]);
+  }
+  if (groups & MRS_OBS_QUAT) {
+    double q[4];
+    quat_from_matrix(R, q);
+#pragma unroll
+    for (int c = 0; c < 4; c++) col(q[c]);
+  }
+  if (groups & MRS_OBS_OMEGA) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) col(src.omega(c));
+  }
+  if (groups & MRS_OBS_IMU) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) col(src.imu(c));
+  }
+  if (groups & MRS_OBS_RPM) {
+    const int nm = src.n_motors();
+#pragma unroll
+    for (int m = 0; m < MRS_MAX_MOTORS; m++) col(m < nm ? src.rpm(m) : 0.0);
+  }
+}

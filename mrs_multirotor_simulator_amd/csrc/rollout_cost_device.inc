@@ -25,6 +25,8 @@ struct RolloutCostHook {
   __device__ __forceinline__ void cmd(const SW& sw, int i, int s) const {
     rate().cmd(sw, i, s);
   }
+  template <class SW, class PT>
+  __device__ __forceinline__ void cmd_lane(const SW&, PT&, int, const Lane&, int) const {}
   // the term of evaluation block `blk` of this launch (obs_row.h).  64-bit row addresses: blocks x count x stride passes 2^31.  The
   // target address is per lane (tgt_row == 0: the same for every lane) and the weight address is wave-uniform; both are read with
   // vector loads, a shared row as a broadcast: scalar loads would hold a row's worth of scalar registers the kernels do not have

@@ -55,6 +55,8 @@ struct RolloutHook {
         if (j < r.width) sw.st(F_CMD + j, off8, p[j]);
     }
   }
+  template <class SW, class PT>
+  __device__ __forceinline__ void cmd_lane(const SW&, PT&, int, const Lane&, int) const {}
   template <class Src>
   __device__ __forceinline__ void write_obs(const Src& src, int i, int s) const {
     const size_t a = at(i, s, r.obs_stride);

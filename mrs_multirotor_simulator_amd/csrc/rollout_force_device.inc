@@ -70,6 +70,8 @@ struct RolloutForceHook {
     if (MRS_RO_HI(w) == 0u || j < 0) return;
     force_row(sw, i, j, RolloutRateHook::fresh_word(r.cmd_sched));
   }
+  template <class SW, class PT>
+  __device__ __forceinline__ void cmd_lane(const SW&, PT&, int, const Lane&, int) const {}
   template <class Src>
   __device__ __forceinline__ void write_obs(const Src& src, int i, int blk, uint32_t groups, uint32_t cmd_word) const {
     const size_t a = at(i, blk, r.obs_stride);

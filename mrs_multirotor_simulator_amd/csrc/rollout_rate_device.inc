@@ -64,6 +64,8 @@ struct RolloutRateHook {
     if (j < 0) return;
     cmd_row(sw, i, j, w);
   }
+  template <class SW, class PT>
+  __device__ __forceinline__ void cmd_lane(const SW&, PT&, int, const Lane&, int) const {}
   template <class Src>
   __device__ __forceinline__ void write_obs(const Src& src, int i, int blk, uint32_t groups, uint32_t cmd_word) const {
     const size_t a = at(i, blk, r.obs_stride);

@@ -67,6 +67,8 @@ struct RolloutTickHook {
   }
   template <class SW>
   __device__ __forceinline__ void cmd(const SW&, int, int) const {}
+  template <class SW, class PT>
+  __device__ __forceinline__ void cmd_lane(const SW&, PT&, int, const Lane&, int) const {}
 
   // the observation row and the crash byte of UAV i
   template <class Src>

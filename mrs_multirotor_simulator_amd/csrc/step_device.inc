@@ -1156,7 +1156,7 @@ DEV bool coll_fold_and_decide(CDT& cd0, const int part, const uint32_t stall_own
 // epoch word / ticket to the launches that run beside this one (step_kernel_publish), whatever its lanes do afterwards.
 // HK: what a launch does around each fused sub-step besides stepping (MULTI only; rollout_device.inc).  enter() runs once per lane
 // after the wave-uniform exits and may finish the lane itself (true); cmd(s) runs at the top of sub-step s, before the controller
-// cascade, and obs(s) after post_step.  The default does nothing: every kernel of this file compiles as it did without the hook.
+// cascade, cmd_lane(s) behind it with the lane (the state BEFORE the sub-step: rollout_feedback_device.inc), and obs(s) after post_step.  The default does nothing: every kernel of this file compiles as it did without the hook.
 // One hook type, RolloutTickHook (rollout_tick_device.inc), rides on the single-GPU COLL kernels instead: one step per launch, and
 // held(), the last thing a held lane does — in COLL kernels a held lane takes part in the collisions and leaves inside
 // MRS_COLLIDE_THEN, so enter() cannot finish it.
@@ -1166,6 +1166,8 @@ struct NoStepHook {
   __device__ __forceinline__ bool enter(const SW&, int, Lane&, int) const { return false; }
   template <class SW>
   __device__ __forceinline__ void cmd(const SW&, int, int) const {}
+  template <class SW, class PT>
+  __device__ __forceinline__ void cmd_lane(const SW&, PT&, int, const Lane&, int) const {}
   template <class SW, class PT>
   __device__ __forceinline__ void obs(const SW&, PT&, int, const Lane&, int) const {}
   template <class SW>
@@ -1441,6 +1443,7 @@ DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, co
       double cg_[4];                                                                                                  \
       if (L[u].y[0] != L[u].y[0] + 1e300) { MRS_STAMP(3) }                                                           \
       hk.cmd(sw, idx[u], s);                                                                                          \
+      hk.cmd_lane(sw, P, idx[u], L[u], s);                                                                            \
       control_cascade<CASCADE, !MULTI, PIDPRE>(sw, P, idx[u], L[u], dt, inv_dt, src_, cg_);                           \
       if (cg_[0] != cg_[0] + 1e300) { MRS_STAMP(4) }                                                                  \
       if (COLL) {                                                                                                     \

@@ -167,6 +167,35 @@ struct RolloutCostDev {
   int32_t     wt_row;      // weight_stride, or 0: one weight row for every evaluation
 };
 
+// ---- one launch of a feedback rollout (mrs_swarm_rollout_feedback_device, rollout_feedback_device.inc) ----
+// RolloutCostDev, whose command side becomes the NOMINAL command, and the gains and setpoints of the launch's command blocks: at the
+// launch's j-th due command sub-step the F_CMD columns of UAV first + k take cmd row (j, k) + G(j, k) (ref row (j, k) - observation
+// row of fb_groups).  G(j, k)[c][col] sits at element j * gain_blk + k * gain_lane + (c * row width + col) * gain_col of `gain`:
+// shared gains are dense [payload, row width] matrices (gain_lane 0, gain_col 1), per-UAV gains are UAV-minor
+// [payload, row width, count] (gain_lane 1, gain_col count), so that a wave's load of one gain element is one coalesced request.
+struct RolloutFeedbackDev {
+  const void* cmd;
+  int32_t     first, count;
+  int32_t     cmd_stride;
+  uint32_t    cmd_sched;   // as RolloutRateDev's (the dtype bit serves commands, gains, setpoints, targets and weights)
+  uint32_t    cost_sched;  // as RolloutCostDev's.  Groups 0: no evaluation in this launch (or in the whole call: target, weight, cost null)
+  uint32_t    mode_bits;
+  const void* target;
+  const void* weight;
+  double*     cost;
+  uint64_t    tgt_blk;
+  int32_t     tgt_row;
+  int32_t     wt_row;
+  const void* gain;        // gains of the launch's FIRST due command block
+  const void* ref;         // setpoint rows likewise; row (j, k) at element j * ref_blk + k * ref_row
+  uint64_t    gain_blk;    // elements between two gain blocks; 0: one block serves every command block
+  uint64_t    ref_blk;     // count * ref_stride, or the row width when all UAVs share one row per block; 0: one block serves all
+  uint32_t    gain_col;    // 1, or count: per-UAV gains
+  int32_t     gain_lane;   // 0, or 1: per-UAV gains
+  int32_t     ref_row;     // ref_stride, or 0: shared setpoints
+  uint32_t    fb_word;     // fb_groups | row width of fb_groups << 8
+};
+
 // ---- the rows of ONE tick of a tick rollout (mrs_swarm_rollout_tick_device, rollout_tick_device.inc) ----
 // One launch is one tick, so the host works out each launch's row blocks itself: no schedule words.  The descriptor travels with the
 // launch's record in the stall / replay log (mrs_swarm::TickRec): a replayed launch writes the rows its no-op did not.

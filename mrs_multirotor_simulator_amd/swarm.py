@@ -117,6 +117,7 @@ ABI_SYMBOLS = [
     "mrs_swarm_apply_force_device",
     "mrs_swarm_rollout_force_device",
     "mrs_swarm_rollout_cost_device",
+    "mrs_swarm_rollout_feedback_device",
     "mrs_swarm_rollout_tick_device",
 ]
 
@@ -354,6 +355,8 @@ def load_library():
         "mrs_swarm_rollout_force_device": [vp, i32, i32, i32, C.c_double, i32, i32, i32, i32, vp, i32, i32, vp, i32, C.c_uint32, vp, i32, vp],
         "mrs_swarm_rollout_cost_device": [vp, i32, i32, i32, C.c_double, i32, i32, i32, vp, i32, i32, C.c_uint32, vp, i32, vp, i32, vp, i32,
                                           vp],
+        "mrs_swarm_rollout_feedback_device": [vp, i32, i32, i32, C.c_double, i32, i32, i32, vp, i32, i32, C.c_uint32, vp, i32, i32, vp, i32, i32,
+                                              C.c_uint32, vp, i32, vp, i32, vp, i32, vp],
         "mrs_swarm_rollout_tick_device": [vp, i32, i32, i32, C.c_double, i32, i32, i32, vp, i32, i32, C.c_uint32, vp, i32, vp, i32, C.c_double,
                                           vp],
     }
@@ -858,6 +861,16 @@ class Swarm:
                                                   int(cost_every), dev_cmd or None, int(dtype), int(cmd_stride), C.c_uint32(int(groups)),
                                                   dev_target or None, int(target_stride), dev_weight or None, int(weight_stride),
                                                   dev_cost or None, int(bool(accumulate)), ext_stream or None))
+
+    def rollout_feedback_device(self, first, count, mode, dt, n_steps, cmd_every, cost_every, dev_cmd, dtype, cmd_stride, fb_groups, dev_gain,
+                                gain_per_uav, gain_blocks, dev_ref, ref_stride, ref_blocks, cost_groups, dev_target, target_stride, dev_weight,
+                                weight_stride, dev_cost, accumulate, ext_stream):
+        _check(_lib.mrs_swarm_rollout_feedback_device(self._h, int(first), int(count), int(mode), C.c_double(float(dt)), int(n_steps),
+                                                      int(cmd_every), int(cost_every), dev_cmd or None, int(dtype), int(cmd_stride),
+                                                      C.c_uint32(int(fb_groups)), dev_gain or None, int(gain_per_uav), int(gain_blocks),
+                                                      dev_ref or None, int(ref_stride), int(ref_blocks), C.c_uint32(int(cost_groups)),
+                                                      dev_target or None, int(target_stride), dev_weight or None, int(weight_stride),
+                                                      dev_cost or None, int(bool(accumulate)), ext_stream or None))
 
     def rollout_tick_device(self, first, count, mode, dt, n_ticks, cmd_every, obs_every, dev_cmd, dtype, cmd_stride, groups, dev_obs, obs_stride,
                             dev_crashed, crash, rebounce, ext_stream):

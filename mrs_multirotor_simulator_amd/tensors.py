@@ -328,6 +328,110 @@ def _check_crash_rows(t, blocks, rows, device_index):
         raise ValueError(f"crashed: the crash rows are not dense (strides {tuple(t.stride())}, expected ({rows}, 1))")
 
 
+def _row_blocks(t, name, blocks, count, w, dtype, dev):
+    """Row blocks that are [blocks, count, >= w] (a row per UAV) or [blocks, 1, w] (one dense row per block for all UAVs), as the targets
+    of rollout_cost.  Returns the row stride, 0 for shared rows."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[0] != blocks or t.shape[1] not in (1, count) or t.shape[2] < w:
+        raise ValueError(f"{name}: expected a [{blocks}, {count} or 1, >= {w}] tensor, got "
+                         f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if t.shape[1] == 1:  # one row per block: its stride is that of the first dimension
+        stride = check_tensor(t[:, 0, :], blocks, w, dtype, dev)
+        if count != 1:
+            if blocks > 1 and stride != w:
+                raise ValueError(f"{name}: shared rows must be dense, [{blocks}, 1, {w}], got a row stride of {stride}")
+            return 0
+        return stride
+    return _check_steps(t, name, blocks, count, w, dtype, dev)
+
+
+def rollout_feedback(swarm, mode, commands, dt, fb_groups, gains, refs, cost_groups=0, targets=None, weights=None, first=0, hold=1,
+                     cost_every=None, out=None, accumulate=False):
+    """rollout_cost whose commands are NOMINAL commands: at the start of command block b (every `hold` steps) the command of UAV
+    first + k is formed in the step kernel as `commands[b, k] + G[b, k] @ (refs[b, k] - o)`, o being the FP64 observation row of
+    `fb_groups` before the step (what gather(fb_groups, float64) would return), and held for the block
+    (mrs_swarm_rollout_feedback_device: FP64, unfused, e[j] = ref[j] - o[j], then per payload element c the sum over ascending j of
+    G[c][j] * e[j] added to the nominal command, in both flavours).  The call is the loop gather -> that arithmetic -> set_input ->
+    `hold` steps, bit for bit, without a launch or a host round trip per tick; the feedback has no memory, so a horizon cut into calls
+    (accumulate=True from the second on) gives the bits of one call.
+    With B = commands.shape[0], W_c = command_width(mode) and W_o = gather_width(fb_groups) >= 1, Bg in {1, B} (one block for the whole
+    call, or one per command block):
+      refs   [Bg, count, >= W_o] (a setpoint row per UAV) or [Bg, 1, W_o] (one dense row per block for all UAVs);
+      gains  3-D [Bg, W_c, W_o], dense: one gain matrix for all UAVs; or
+             4-D [Bg, W_c, W_o, count], dense, UAV-MINOR: a gain matrix per UAV.  A UAV's gain is W_c * W_o numbers (4 x 18 doubles are
+             576 B, more than a step moves); with the UAV index last each of the W_c * W_o loads of a 64-lane wave is one coalesced
+             request, where a matrix per row would touch 64 cache lines per load.  From a [Bg, count, W_c, W_o] tensor:
+             `g.permute(0, 2, 3, 1).contiguous()`.
+    One dtype serves commands, gains, refs, targets and weights.  cost_groups, targets, weights, cost_every, out, accumulate: as in
+    rollout_cost; cost_groups == 0 (then targets, weights and out stay None) is a pure closed-loop run and returns None."""
+    dev = swarm.device()
+    if not isinstance(commands, torch.Tensor) or commands.dim() != 3:
+        raise ValueError("commands must be a [T, count, width] tensor")
+    hold = int(hold)
+    if hold < 1:
+        raise ValueError(f"hold must be at least 1, got {hold}")
+    code = _dtype_code(commands.dtype)
+    blocks, count = commands.shape[0], commands.shape[1]
+    steps = blocks * hold
+    every = hold if cost_every is None else int(cost_every)
+    if every < 1 or steps % every != 0:
+        raise ValueError(f"cost_every must be at least 1 and divide the {steps} steps of the call, got {every}")
+    evals = steps // every
+    width = command_width(mode, commands.shape[2])
+    if width < 1:
+        raise ValueError("a feedback rollout needs a mode with a payload")
+    cstride = _check_steps(commands, "commands", None, count, width, commands.dtype, dev)
+    if mode == ACTUATOR_CMD and count > 1 and cstride != commands.shape[2]:
+        raise ValueError("actuator rows must be dense (row stride == number of motors)")
+    wo = gather_width(fb_groups)
+    if wo == 0:
+        raise ValueError("fb_groups must select at least one observation group: a feedback needs columns")
+    for name, t in (("gains", gains), ("refs", refs), ("targets", targets), ("weights", weights)):
+        if isinstance(t, torch.Tensor) and t.dtype != commands.dtype:
+            raise ValueError(f"{name} has dtype {t.dtype}, the commands {commands.dtype}: one dtype serves commands, gains, refs, targets "
+                             "and weights")
+    if not isinstance(gains, torch.Tensor) or gains.dim() not in (3, 4):
+        raise ValueError(f"gains: expected a [Bg, {width}, {wo}] (shared) or [Bg, {width}, {wo}, {count}] (per UAV, UAV-minor) tensor, got "
+                         f"{tuple(gains.shape) if isinstance(gains, torch.Tensor) else type(gains).__name__}")
+    per_uav = gains.dim() == 4
+    want = (width, wo, count) if per_uav else (width, wo)
+    if gains.shape[0] not in (1, blocks) or tuple(gains.shape[1:]) != want:
+        raise ValueError(f"gains: expected a [{blocks} or 1, {', '.join(str(x) for x in want)}] tensor, got {tuple(gains.shape)}")
+    if gains.device.type != "cuda" or gains.device.index != dev:
+        raise ValueError(f"gains is on {gains.device}, the swarm lives on cuda:{dev}")
+    if not gains.is_contiguous():
+        raise ValueError("gains must be dense" + (": [Bg, W_c, W_o, count] with the UAV index last (g.permute(0, 2, 3, 1).contiguous())"
+                                                  if per_uav else ": [Bg, W_c, W_o], row-major"))
+    if not isinstance(refs, torch.Tensor) or refs.dim() != 3 or refs.shape[0] not in (1, blocks):
+        raise ValueError(f"refs: expected a [{blocks} or 1, {count} or 1, >= {wo}] tensor, got "
+                         f"{tuple(refs.shape) if isinstance(refs, torch.Tensor) else type(refs).__name__}")
+    rstride = _row_blocks(refs, "refs", refs.shape[0], count, wo, commands.dtype, dev)
+    tptr = wptr = optr = tstride = wstride = 0
+    if cost_groups == 0:
+        if targets is not None or weights is not None or out is not None or accumulate:
+            raise ValueError("cost_groups == 0 is a run without a cost: targets, weights and out must stay None")
+    else:
+        w = gather_width(cost_groups)
+        tstride = _row_blocks(targets, "targets", evals, count, w, commands.dtype, dev)
+        if not isinstance(weights, torch.Tensor) or weights.dim() != 2 or weights.shape[0] not in (1, evals):
+            raise ValueError(f"weights: expected a [{evals} or 1, >= {w}] tensor, got "
+                             f"{tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights).__name__}")
+        wstride = check_tensor(weights, weights.shape[0], w, commands.dtype, dev)
+        if weights.shape[0] == 1:
+            wstride = 0
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs the `out` vector it adds to")
+            out = torch.empty(count, dtype=torch.float64, device=torch.device("cuda", dev))
+        if isinstance(out, torch.Tensor) and out.dtype != torch.float64:
+            raise ValueError(f"out has dtype {out.dtype}: the cost vector is always torch.float64")
+        check_tensor(out, count, None, torch.float64, dev)
+        tptr, wptr, optr = targets.data_ptr(), weights.data_ptr(), out.data_ptr()
+    swarm.rollout_feedback_device(first, count, mode, dt, steps, hold, every, commands.data_ptr() if count > 0 else 0, code, cstride, fb_groups,
+                                  gains.data_ptr(), int(per_uav), gains.shape[0], refs.data_ptr(), rstride, refs.shape[0], cost_groups, tptr,
+                                  tstride, wptr, wstride, optr, bool(accumulate), _stream(dev))
+    return out
+
+
 def crashed(swarm, first=0, count=None, out=None):
     """UavSystem::hasCrashed of UAVs [first, first + count) as a bool tensor on the swarm's device"""
     count = _count(swarm, first, count)

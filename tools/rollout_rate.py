@@ -55,6 +55,20 @@ and prints us per tick (median, min-max), the bytes of rows per tick, and whethe
 tick,loop,bare (e.g. `bare` alone, with MRS_SWARM_LIB naming the library of another commit).
 
     python tools/rollout_rate.py --ticks [sizes=100000] [T=200] [reps=5] [-] [forms=tick,loop,bare] [arith=fast] [holds=1,10]
+
+With `--feedback` (anywhere on the command line) the tool measures the FEEDBACK rollout (mrs_swarm_rollout_feedback_device): the command of
+a block is the nominal FP32 row plus G (ref - observation row of POS | VEL | ROT | OMEGA, 18 columns), formed in the step kernel, with the
+cost of `--cost` evaluated every `hold` steps.  Defaults: sizes 100000, T = 320, modes ACTUATOR_CMD,ATTITUDE_RATE_CMD, arith fast, and the
+seventh argument is a list of holds (10,1; cost_every = hold).  The same T steps four ways, alternating:
+  c     tensors.rollout_cost(cmd, dt, targets, weights, hold=hold)                              (open loop: what the feedback is added to)
+  fs    tensors.rollout_feedback(cmd, dt, fb_groups, gains [1, W_c, 18], refs, ..., hold=hold)   (one gain matrix for all UAVs)
+  fu    the same with gains [1, W_c, 18, n], UAV-minor: the shared matrix repeated per UAV        (a gain matrix per UAV)
+  loop  per block: tensors.gather(fb_groups) -> cmd + (ref - o) @ G^T (torch.matmul) -> tensors.set_input -> step_n(dt, hold)
+        (the closed loop through torch that the call replaces; FP32 rows, no cost)
+`fs` and `fu` apply the same gains: cost and final state must be bit-identical, and differ from `c`; the largest relative difference of
+the loop's final positions from theirs is printed (the loop rounds the row to FP32 and sums in another order).
+
+    python tools/rollout_rate.py --feedback [sizes=100000] [T=320] [reps=5] [modes=ACTUATOR_CMD,ATTITUDE_RATE_CMD] [forms=c,fs,fu,loop] [arith=fast] [holds=10,1]
 """
 import os
 import sys
@@ -87,6 +101,15 @@ def main():
                           int(sys.argv[3]) if len(sys.argv) > 3 else 5, sys.argv[6] if len(sys.argv) > 6 else "fast",
                           [int(h) for h in (sys.argv[7] if len(sys.argv) > 7 else "1,10").split(",")],
                           sys.argv[5].split(",") if len(sys.argv) > 5 else ["tick", "loop", "bare"])
+    if "--feedback" in sys.argv:
+        sys.argv.remove("--feedback")
+        for ar in (sys.argv[6] if len(sys.argv) > 6 else "fast").split(","):
+            for hold in [int(h) for h in (sys.argv[7] if len(sys.argv) > 7 else "10,1").split(",")]:
+                main_feedback([int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [100_000], int(sys.argv[2]) if len(sys.argv) > 2 else 320,
+                              int(sys.argv[3]) if len(sys.argv) > 3 else 5,
+                              sys.argv[4].split(",") if len(sys.argv) > 4 and sys.argv[4] != "-" else ["ACTUATOR_CMD", "ATTITUDE_RATE_CMD"],
+                              sys.argv[5].split(",") if len(sys.argv) > 5 and sys.argv[5] != "-" else ["c", "fs", "fu", "loop"], ar, hold)
+        return None
     cost = "--cost" in sys.argv
     if cost:
         sys.argv.remove("--cost")
@@ -528,6 +551,88 @@ def main_cost(sizes, steps, reps, modes, arith, hold, every):
             line += f", f {(cmd_b + 2 * E * n * 8 + 2 * E * ow * 4) / 1e6:.1f} MB (cost element read and written per evaluation)"
             line += "  cost == restatement, states agree"
             line += "  f <= b" if np.median(times["f"]) <= np.median(times["b"]) else "  F SLOWER THAN B"
+            print(line, flush=True)
+            for g in swarms.values():
+                g.close()
+
+
+def main_feedback(sizes, steps, reps, modes, forms, arith, hold):
+    import torch
+    from mrs_multirotor_simulator_amd import tensors as T
+    assert hold >= 1 and steps % hold == 0, "hold must divide T"
+    fb, groups = T.OBS_POS | T.OBS_VEL | T.OBS_ROT | T.OBS_OMEGA, T.OBS_POS | T.OBS_VEL | T.OBS_QUAT
+    wo, ow = T.gather_width(fb), T.gather_width(groups)
+    rng = np.random.default_rng(5)
+    B = E = steps // hold
+    print(f"feedback rollout of T = {steps} steps, hold = cost_every = {hold}, FP32 commands, gains, setpoints, targets and weights, feedback on "
+          f"POS|VEL|ROT|OMEGA ({wo} columns), x500, {arith.upper()}; {reps} rounds after a warm-up, alternating")
+    for n in sizes:
+        st, _ = bench.make_inputs(n, "position+collisions", seed=3)
+        p = M.model_params("x500", ground_enabled=True, ground_z=0.0)
+        for mode_name in modes:
+            mode = getattr(M, mode_name)
+            swarms = {}
+            for f in forms:
+                g = M.Swarm(n, arith=M.ARITH_FAST if arith == "fast" else M.ARITH_LITERAL)
+                g.construct(0, n, p)
+                g.set_state(0, n, st["x"], st["v"], st["R"], st["omega"], st["motor_rpm"])
+                swarms[f] = g
+            dev = torch.device("cuda", next(iter(swarms.values())).device())
+            cmd = torch.tensor(commands(mode, n, B, rng), dtype=torch.float32, device=dev)
+            wc = cmd.shape[2]
+            gs = torch.tensor(rng.normal(0.0, 1e-3, (1, wc, wo)), dtype=torch.float32, device=dev)
+            gu = gs[..., None].expand(1, wc, wo, n).contiguous()  # UAV-minor
+            gt = gs[0].t().contiguous()
+            ref = torch.tensor(np.concatenate([[0.0, 0.0, 5.0], np.zeros(3), np.eye(3).ravel(), np.zeros(3)])[None, None, :], dtype=torch.float32, device=dev)
+            tgt = torch.tensor(rng.normal(0.0, 2.0, (E, 1, ow)), dtype=torch.float32, device=dev)
+            wt = torch.tensor(rng.uniform(0.1, 2.0, (1, ow)), dtype=torch.float32, device=dev)
+            cost = {f: torch.empty(n, dtype=torch.float64, device=dev) for f in ("c", "fs", "fu")}
+            row = torch.empty((n, wo), dtype=torch.float32, device=dev)
+
+            def run(form):
+                g = swarms[form]
+                if form == "c":
+                    T.rollout_cost(g, mode, cmd, DT, groups, tgt, wt, hold=hold, out=cost["c"])
+                elif form in ("fs", "fu"):
+                    T.rollout_feedback(g, mode, cmd, DT, fb, gs if form == "fs" else gu, ref, groups, tgt, wt, hold=hold, out=cost[form])
+                else:
+                    for b in range(B):
+                        T.gather(g, fb, out=row)
+                        T.set_input(g, mode, torch.addmm(cmd[b], ref[0] - row, gt))
+                        g.step_n(DT, hold)
+
+            for f in forms:  # warm-up: code objects, the type table, torch kernels — and the run that is checked
+                run(f)
+            torch.cuda.synchronize(dev)
+            note = ""
+            if "fs" in forms and "fu" in forms:
+                a, b = swarms["fs"].get_states(), swarms["fu"].get_states()
+                for fld in a.dtype.names:
+                    assert np.array_equal(a[fld].view(np.uint64) if a[fld].dtype == np.float64 else a[fld],
+                                          b[fld].view(np.uint64) if b[fld].dtype == np.float64 else b[fld]), f"{n} {mode_name}: {fld} differs (fs / fu)"
+                assert torch.equal(cost["fs"].view(torch.int64), cost["fu"].view(torch.int64)), f"{n} {mode_name}: the costs of fs and fu differ"
+                note += "  fs == fu (cost and state)"
+                if "c" in forms:
+                    assert not torch.equal(cost["fs"], cost["c"]), f"{n} {mode_name}: the feedback changed nothing"
+                if "loop" in forms:
+                    xl = swarms["loop"].get_states()["x"]
+                    note += f"  loop vs fs: max rel. position difference {float(np.nanmax(np.abs(xl - a['x']) / (1.0 + np.abs(a['x'])))):.1e}"
+            times = {f: [] for f in forms}
+            for _ in range(reps):
+                for f in forms:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    run(f)
+                    e1.record()
+                    e1.synchronize()
+                    times[f].append(e0.elapsed_time(e1) * 1e3 / steps)
+            line = f"  {n:>8d} UAVs  {mode_name:18s}"
+            for f in forms:
+                line += f"  {f} {float(np.median(times[f])):7.2f} us/step ({min(times[f]):.2f}-{max(times[f]):.2f})"
+            line += f"  gains fs {wc * wo * 4} B, fu {wc * wo * n * 4 / 1e6:.1f} MB read per block" + note
+            for f in ("fs", "fu"):
+                if f in forms and "loop" in forms and np.median(times[f]) > np.median(times["loop"]):
+                    line += f"  {f.upper()} SLOWER THAN THE LOOP"
             print(line, flush=True)
             for g in swarms.values():
                 g.close()

@@ -346,222 +346,230 @@ int mrs_swarm_apply_force_device(mrs_swarm_t* s, int32_t first, int32_t count, c
   return fence_out(s, ext);
 }
 
-// what mrs_swarm_rollout_cost_device adds to a control-rate rollout (rollout_locked; obs_every is then the evaluation rate)
-struct CostArgs {
+// Every argument of the rollout entry points as one record; a call leaves what it does not have at zero.  `kind` is the entry point:
+// it decides which of the optional parts are checked and which kernel family runs.
+enum RolloutKind { ROLLOUT_ROWS, ROLLOUT_FORCE, ROLLOUT_COST, ROLLOUT_FEEDBACK, ROLLOUT_TICK };
+struct RolloutArgs {
+  const char* who;
+  RolloutKind kind;
+  int32_t     first, count, mode;
+  double      dt;
+  int32_t     n_steps, cmd_every, obs_every;  // (n_ticks of a tick rollout; cost_every of a cost or feedback rollout)
+  const void* dev_cmd;
+  int32_t     dtype, cmd_stride;
+  uint32_t    groups;  // of the observation rows, or of the cost (a feedback rollout's may be 0: no cost)
+  void*       dev_obs;
+  int32_t     obs_stride;
+  void*       ext_stream;
+  // mrs_swarm_rollout_force_device
+  int32_t     force_every;
+  const void* dev_force;
+  int32_t     force_stride;
+  // mrs_swarm_rollout_cost_device, mrs_swarm_rollout_feedback_device
   const void* target;
   int32_t     target_stride;
   const void* weight;
   int32_t     weight_stride;
   double*     cost;
   int32_t     accumulate;
-};
-
-// what mrs_swarm_rollout_feedback_device adds to a cost rollout (rollout_locked; `groups` are then the cost groups and may be 0: no cost)
-struct FeedbackArgs {
-  uint32_t    groups;
+  // mrs_swarm_rollout_feedback_device
+  uint32_t    fb_groups;
   const void* gain;
   int32_t     gain_per_uav, gain_blocks;
   const void* ref;
   int32_t     ref_stride, ref_blocks;
+  // mrs_swarm_rollout_tick_device
+  uint8_t*    dev_crashed;
+  int32_t     crash;
+  double      rebounce;
+};
+// what the checks work out on their way
+struct RolloutWidths {
+  int     cmd;      // payload elements of a command row
+  int32_t obs, fb;  // elements of a row of `groups` and of `fb_groups`
+  bool    costed;   // the call evaluates a cost (a feedback rollout without cost groups is a pure closed-loop run)
 };
 
-// the rollout entry points, under the caller's lock (MRS_ENTER's settle after the argument checks: a refused call launches nothing)
-static int rollout_locked(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every, int32_t obs_every,
-                          int32_t force_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, const void* dev_force, int32_t force_stride,
-                          uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream, bool forced, const char* who,
-                          const CostArgs* cost = nullptr, const FeedbackArgs* fb = nullptr) {
-  int rc = check_range(s, first, count);
+// The argument checks of every rollout entry point, in the order in which a call with several faults reports them.  `steps` and `every`
+// are the nouns of the messages: n_steps or n_ticks, obs_every or cost_every.  Nothing is launched and nothing is changed here.
+static int check_rollout_args(mrs_swarm_t* s, const RolloutArgs& a, const std::string& steps, const std::string& every, RolloutWidths& w) {
+  const bool forced = a.kind == ROLLOUT_FORCE, fb = a.kind == ROLLOUT_FEEDBACK, cost = fb || a.kind == ROLLOUT_COST;
+  int        rc     = check_range(s, a.first, a.count);
   if (rc) return rc;
-  if (s->comm_world > 0) return fail(MRS_ERR_ARG, std::string(who) + ": not on a sharded swarm");
-  if (mode < MRS_INPUT_UNKNOWN || mode > MRS_POSITION_CMD) return fail(MRS_ERR_ARG, "bad input mode");
-  if ((rc = check_dtype(dtype))) return rc;
-  if (n_steps < 1) return fail(MRS_ERR_ARG, "n_steps must be at least 1");
-  if (cmd_every < 1 || n_steps % cmd_every != 0) return fail(MRS_ERR_ARG, "cmd_every must be at least 1 and divide n_steps");
-  if (obs_every < 1 || n_steps % obs_every != 0)
-    return fail(MRS_ERR_ARG, cost ? "cost_every must be at least 1 and divide n_steps" : "obs_every must be at least 1 and divide n_steps");
-  if (forced && (force_every < 1 || n_steps % force_every != 0)) return fail(MRS_ERR_ARG, "force_every must be at least 1 and divide n_steps");
-  if (forced && force_stride < 3) return fail(MRS_ERR_ARG, "force_stride smaller than the three force components");
-  if (forced && !dev_force) return fail(MRS_ERR_ARG, "dev_force: null pointer");
-  if (!(dt > 0) || !std::isfinite(dt)) return fail(MRS_ERR_ARG, "dt must be finite and > 0");
-  const int width = command_width(mode, cmd_stride);
-  if (width > 0 && (cmd_stride < width || width < 1)) return fail(MRS_ERR_ARG, "cmd_stride too small for this mode");
-  int32_t obs_width = 0;
-  if ((rc = mrs_swarm_gather_width(groups, &obs_width))) return rc;
-  if (!cost && groups != 0u && obs_stride < obs_width) return fail(MRS_ERR_ARG, "obs_stride smaller than the width of the selected groups");
-  const bool costed = cost && !(fb && groups == 0u);  // (a feedback rollout without cost groups: a pure closed-loop run)
-  int32_t    fb_width = 0;
+  if (s->comm_world > 0) return fail(MRS_ERR_ARG, std::string(a.who) + ": not on a sharded swarm");
+  if (a.mode < MRS_INPUT_UNKNOWN || a.mode > MRS_POSITION_CMD) return fail(MRS_ERR_ARG, "bad input mode");
+  if ((rc = check_dtype(a.dtype))) return rc;
+  if (a.n_steps < 1) return fail(MRS_ERR_ARG, steps + " must be at least 1");
+  if (a.cmd_every < 1 || a.n_steps % a.cmd_every != 0) return fail(MRS_ERR_ARG, "cmd_every must be at least 1 and divide " + steps);
+  if (a.obs_every < 1 || a.n_steps % a.obs_every != 0) return fail(MRS_ERR_ARG, every + " must be at least 1 and divide " + steps);
+  if (forced && (a.force_every < 1 || a.n_steps % a.force_every != 0)) return fail(MRS_ERR_ARG, "force_every must be at least 1 and divide " + steps);
+  if (forced && a.force_stride < 3) return fail(MRS_ERR_ARG, "force_stride smaller than the three force components");
+  if (forced && !a.dev_force) return fail(MRS_ERR_ARG, "dev_force: null pointer");
+  if (!(a.dt > 0) || !std::isfinite(a.dt)) return fail(MRS_ERR_ARG, "dt must be finite and > 0");
+  if (!std::isfinite(a.rebounce)) return fail(MRS_ERR_ARG, "rebounce must be finite");
+  w.cmd = command_width(a.mode, a.cmd_stride);
+  if (w.cmd > 0 && (a.cmd_stride < w.cmd || w.cmd < 1)) return fail(MRS_ERR_ARG, "cmd_stride too small for this mode");
+  w.obs = w.fb = 0;
+  if ((rc = mrs_swarm_gather_width(a.groups, &w.obs))) return rc;
+  if (!cost && a.groups != 0u && a.obs_stride < w.obs) return fail(MRS_ERR_ARG, "obs_stride smaller than the width of the selected groups");
+  w.costed = cost && !(fb && a.groups == 0u);
   if (fb) {
-    if (width < 1) return fail(MRS_ERR_ARG, "a feedback rollout needs a mode with a payload");
-    if ((rc = mrs_swarm_gather_width(fb->groups, &fb_width))) return rc;
-    if (fb_width < 1) return fail(MRS_ERR_ARG, "no feedback group selected: fb_groups must select at least one observation group");
-    if (!fb->gain) return fail(MRS_ERR_ARG, "dev_gain: null pointer");
-    if (!fb->ref) return fail(MRS_ERR_ARG, "dev_ref: null pointer");
-    if (fb->gain_per_uav != 0 && fb->gain_per_uav != 1) return fail(MRS_ERR_ARG, "gain_per_uav must be 0 (shared gains) or 1");
-    if (fb->gain_blocks != 1 && fb->gain_blocks != n_steps / cmd_every)
-      return fail(MRS_ERR_ARG, "gain_blocks must be 1 or the number of command blocks");
-    if (fb->ref_blocks != 1 && fb->ref_blocks != n_steps / cmd_every)
-      return fail(MRS_ERR_ARG, "ref_blocks must be 1 or the number of command blocks");
-    if (fb->ref_stride != 0 && fb->ref_stride < fb_width)
+    if (w.cmd < 1) return fail(MRS_ERR_ARG, "a feedback rollout needs a mode with a payload");
+    if ((rc = mrs_swarm_gather_width(a.fb_groups, &w.fb))) return rc;
+    if (w.fb < 1) return fail(MRS_ERR_ARG, "no feedback group selected: fb_groups must select at least one observation group");
+    if (!a.gain) return fail(MRS_ERR_ARG, "dev_gain: null pointer");
+    if (!a.ref) return fail(MRS_ERR_ARG, "dev_ref: null pointer");
+    if (a.gain_per_uav != 0 && a.gain_per_uav != 1) return fail(MRS_ERR_ARG, "gain_per_uav must be 0 (shared gains) or 1");
+    if (a.gain_blocks != 1 && a.gain_blocks != a.n_steps / a.cmd_every) return fail(MRS_ERR_ARG, "gain_blocks must be 1 or the number of command blocks");
+    if (a.ref_blocks != 1 && a.ref_blocks != a.n_steps / a.cmd_every) return fail(MRS_ERR_ARG, "ref_blocks must be 1 or the number of command blocks");
+    if (a.ref_stride != 0 && a.ref_stride < w.fb)
       return fail(MRS_ERR_ARG, "ref_stride must be 0 (shared rows) or at least the width of the feedback groups");
-    if (!costed && (cost->target || cost->weight || cost->cost))
-      return fail(MRS_ERR_ARG, "cost_groups == 0 takes no dev_target, dev_weight or dev_cost");
+    if (!w.costed && (a.target || a.weight || a.cost)) return fail(MRS_ERR_ARG, "cost_groups == 0 takes no dev_target, dev_weight or dev_cost");
   }
-  if (costed) {
-    if (groups == 0u) return fail(MRS_ERR_ARG, "no observation group selected: a cost needs columns");
-    if (!cost->target) return fail(MRS_ERR_ARG, "dev_target: null pointer");
-    if (!cost->weight) return fail(MRS_ERR_ARG, "dev_weight: null pointer");
-    if (!cost->cost) return fail(MRS_ERR_ARG, "dev_cost: null pointer");
-    if (cost->target_stride != 0 && cost->target_stride < obs_width)
+  if (w.costed) {
+    if (a.groups == 0u) return fail(MRS_ERR_ARG, "no observation group selected: a cost needs columns");
+    if (!a.target) return fail(MRS_ERR_ARG, "dev_target: null pointer");
+    if (!a.weight) return fail(MRS_ERR_ARG, "dev_weight: null pointer");
+    if (!a.cost) return fail(MRS_ERR_ARG, "dev_cost: null pointer");
+    if (a.target_stride != 0 && a.target_stride < w.obs)
       return fail(MRS_ERR_ARG, "target_stride must be 0 (shared rows) or at least the width of the selected groups");
-    if (cost->weight_stride != 0 && cost->weight_stride < obs_width)
+    if (a.weight_stride != 0 && a.weight_stride < w.obs)
       return fail(MRS_ERR_ARG, "weight_stride must be 0 (one row) or at least the width of the selected groups");
   }
-  if (count > 0) {
-    // rows of the n_steps / cmd_every and n_steps / obs_every row blocks; 64-bit: blocks x count x stride can pass 2^31 elements
-    const size_t cmd_rows = (size_t)(n_steps / cmd_every) * (size_t)count, obs_rows = (size_t)(n_steps / obs_every) * (size_t)count;
-    if (width > 0 && (rc = check_device_ptr(s, dev_cmd, ((cmd_rows - 1) * (size_t)cmd_stride + (size_t)width) * dtype_bytes(dtype), "dev_cmd")))
-      return rc;
-    if (!cost && groups != 0u &&
-        (rc = check_device_ptr(s, dev_obs, ((obs_rows - 1) * (size_t)obs_stride + (size_t)obs_width) * dtype_bytes(dtype), "dev_obs")))
-      return rc;
-    if (fb) {  // 64-bit: blocks x payload x row width x count can pass 2^31 elements
-      const size_t gains = (size_t)fb->gain_blocks * (size_t)width * (size_t)fb_width * (fb->gain_per_uav ? (size_t)count : (size_t)1);
-      const size_t refs  = fb->ref_stride ? ((size_t)fb->ref_blocks * (size_t)count - 1) * (size_t)fb->ref_stride + (size_t)fb_width
-                                          : (size_t)fb->ref_blocks * (size_t)fb_width;
-      if ((rc = check_device_ptr(s, fb->gain, gains * dtype_bytes(dtype), "dev_gain"))) return rc;
-      if ((rc = check_device_ptr(s, fb->ref, refs * dtype_bytes(dtype), "dev_ref"))) return rc;
-    }
-    if (costed) {  // (obs_rows: one target row per evaluation and UAV, unless the rows are shared)
-      const size_t evals = (size_t)(n_steps / obs_every), w = (size_t)obs_width;
-      const size_t tgt   = cost->target_stride ? (obs_rows - 1) * (size_t)cost->target_stride + w : evals * w;
-      const size_t wt    = cost->weight_stride ? (evals - 1) * (size_t)cost->weight_stride + w : w;
-      if ((rc = check_device_ptr(s, cost->target, tgt * dtype_bytes(dtype), "dev_target"))) return rc;
-      if ((rc = check_device_ptr(s, cost->weight, wt * dtype_bytes(dtype), "dev_weight"))) return rc;
-      if ((rc = check_device_ptr(s, cost->cost, (size_t)count * sizeof(double), "dev_cost"))) return rc;
-    }
-    if (forced) {
-      const size_t force_rows = (size_t)(n_steps / force_every) * (size_t)count;
-      if ((rc = check_device_ptr(s, dev_force, ((force_rows - 1) * (size_t)force_stride + 3u) * dtype_bytes(dtype), "dev_force"))) return rc;
-    }
-    if (mode == MRS_ACTUATOR_CMD && !actuator_width_ok(s, first, count, width)) return fail(MRS_ERR_ARG, "actuator payload narrower than n_motors");
+  if (a.count <= 0) return MRS_OK;
+  // rows of the n_steps / cmd_every and n_steps / obs_every row blocks; 64-bit: blocks x count x stride can pass 2^31 elements
+  const size_t elem = dtype_bytes(a.dtype), count = (size_t)a.count, width = (size_t)w.cmd;
+  const size_t cmd_rows = (size_t)(a.n_steps / a.cmd_every) * count, obs_rows = (size_t)(a.n_steps / a.obs_every) * count;
+  if (w.cmd > 0 && (rc = check_device_ptr(s, a.dev_cmd, ((cmd_rows - 1) * (size_t)a.cmd_stride + width) * elem, "dev_cmd"))) return rc;
+  if (!cost && a.groups != 0u && (rc = check_device_ptr(s, a.dev_obs, ((obs_rows - 1) * (size_t)a.obs_stride + (size_t)w.obs) * elem, "dev_obs")))
+    return rc;
+  if (a.dev_crashed && (rc = check_device_ptr(s, a.dev_crashed, obs_rows, "dev_crashed"))) return rc;
+  if (fb) {  // 64-bit: blocks x payload x row width x count can pass 2^31 elements
+    const size_t gains = (size_t)a.gain_blocks * width * (size_t)w.fb * (a.gain_per_uav ? count : (size_t)1);
+    const size_t refs  = a.ref_stride ? ((size_t)a.ref_blocks * count - 1) * (size_t)a.ref_stride + (size_t)w.fb : (size_t)a.ref_blocks * (size_t)w.fb;
+    if ((rc = check_device_ptr(s, a.gain, gains * elem, "dev_gain"))) return rc;
+    if ((rc = check_device_ptr(s, a.ref, refs * elem, "dev_ref"))) return rc;
   }
+  if (w.costed) {  // (obs_rows: one target row per evaluation and UAV, unless the rows are shared)
+    const size_t evals = (size_t)(a.n_steps / a.obs_every), ow = (size_t)w.obs;
+    const size_t tgt   = a.target_stride ? (obs_rows - 1) * (size_t)a.target_stride + ow : evals * ow;
+    const size_t wt    = a.weight_stride ? (evals - 1) * (size_t)a.weight_stride + ow : ow;
+    if ((rc = check_device_ptr(s, a.target, tgt * elem, "dev_target"))) return rc;
+    if ((rc = check_device_ptr(s, a.weight, wt * elem, "dev_weight"))) return rc;
+    if ((rc = check_device_ptr(s, a.cost, count * sizeof(double), "dev_cost"))) return rc;
+  }
+  if (forced) {
+    const size_t force_rows = (size_t)(a.n_steps / a.force_every) * count;
+    if ((rc = check_device_ptr(s, a.dev_force, ((force_rows - 1) * (size_t)a.force_stride + 3u) * elem, "dev_force"))) return rc;
+  }
+  if (a.mode == MRS_ACTUATOR_CMD && !actuator_width_ok(s, a.first, a.count, w.cmd)) return fail(MRS_ERR_ARG, "actuator payload narrower than n_motors");
+  return MRS_OK;
+}
+
+// the host's mirror of the modes: the launchers pick the cascade or the model-only kernels as mrs_swarm_step_n would after the first
+// mrs_swarm_set_input_device of the loop the call stands for
+static void rollout_track_mode(mrs_swarm_t* s, const RolloutArgs& a) {
+  const uint8_t* m    = s->uav_mode.data() + a.first;
+  unsigned       diff = 0;
+  for (int k = 0; k < a.count; k++) diff |= (unsigned)(m[k] ^ (uint8_t)a.mode);
+  if (diff) track_mode(s, a.first, a.count, a.mode);
+}
+
+// the rollout entry points but the tick rollout, under the caller's lock (MRS_ENTER's settle after the argument checks: a refused call
+// launches nothing)
+static int rollout_locked(mrs_swarm_t* s, const RolloutArgs& a) {
+  const bool    fb = a.kind == ROLLOUT_FEEDBACK, cost = fb || a.kind == ROLLOUT_COST;
+  RolloutWidths w;
+  int           rc = check_rollout_args(s, a, "n_steps", cost ? "cost_every" : "obs_every", w);
+  if (rc) return rc;
   if (s->n == 0) return MRS_OK;
   if ((rc = settle(s))) return rc;  // MRS_ENTER: a pending collision tick is evaluated first, its force acts on the first step
   HIPCHK(hipSetDevice(s->device));
-  if ((rc = upload_types(s, dt))) return rc;
-  // the host's mirror of the modes first: the launcher picks the cascade or the model-only kernels as mrs_swarm_step_n would after the
-  // first mrs_swarm_set_input_device of the loop
-  if (count > 0) {
-    const uint8_t* m    = s->uav_mode.data() + first;
-    unsigned       diff = 0;
-    for (int k = 0; k < count; k++) diff |= (unsigned)(m[k] ^ (uint8_t)mode);
-    if (diff) track_mode(s, first, count, mode);
-  }
-  hipStream_t ext = (hipStream_t)ext_stream;
+  if ((rc = upload_types(s, a.dt))) return rc;
+  rollout_track_mode(s, a);
+  hipStream_t ext = (hipStream_t)a.ext_stream;
   if ((rc = fence_in(s, ext))) return rc;
   s->collide_since_step = false;
   s->p_valid            = false;  // (plain steps do not refresh the position records)
-  const int variant = s->n_cascade > 0 ? 0 : 1;  // 0 all input modes | 1 model only
-  if (fb) {  // the command is formed in the kernel: the kernels of rollout_feedback_device.inc, whatever the rates are
-    if (count > 0 && costed && !cost->accumulate) HIPCHK(hipMemsetAsync(cost->cost, 0, (size_t)count * sizeof(double), s->stream));  // (+0.0)
+  const int      variant = s->n_cascade > 0 ? 0 : 1;  // 0 all input modes | 1 model only
+  const bool     fast = s->arith == MRS_ARITH_FAST, f32 = a.dtype == MRS_DTYPE_F32;
+  const uint32_t cmd_word = ((uint32_t)w.cmd | (f32 ? 32u : 0u)) << 24, mode_bits = (uint32_t)a.mode << FLAG_MODE_SHIFT;
+  const int      first = a.first, count = a.count, n_steps = a.n_steps, cmd_every = a.cmd_every, obs_every = a.obs_every;
+  void* const    obs = a.groups != 0u ? a.dev_obs : nullptr;
+  // (each descriptor: row block 0 and the call's width, dtype and groups; the launcher sets each launch's schedule and first blocks)
+  if (w.costed && count > 0 && !a.accumulate) HIPCHK(hipMemsetAsync(a.cost, 0, (size_t)count * sizeof(double), s->stream));  // (+0.0)
+  const uint64_t tgt_blk = a.target_stride ? (uint64_t)count * (uint64_t)a.target_stride : (uint64_t)w.obs;
+  if (fb) {  // the command is formed in the kernel: the feedback kernels of rollout_cost_device.inc, whatever the rates are
     RolloutFeedbackDev r{};
-    r.cmd = dev_cmd, r.gain = fb->gain, r.ref = fb->ref;
-    r.first = first, r.count = count, r.cmd_stride = cmd_stride;
-    r.cmd_sched = ((uint32_t)width | (dtype == MRS_DTYPE_F32 ? 32u : 0u)) << 24;
-    r.mode_bits = (uint32_t)mode << FLAG_MODE_SHIFT;
-    if (costed) {
-      r.target = cost->target, r.weight = cost->weight, r.cost = cost->cost;
-      r.cost_sched = count > 0 ? groups << 24 : 0u;
-      r.tgt_row = cost->target_stride, r.wt_row = cost->weight_stride;
-      r.tgt_blk = cost->target_stride ? (uint64_t)count * (uint64_t)cost->target_stride : (uint64_t)obs_width;
+    r.cmd = a.dev_cmd, r.gain = a.gain, r.ref = a.ref;
+    r.first = first, r.count = count, r.cmd_stride = a.cmd_stride;
+    r.cmd_sched = cmd_word, r.mode_bits = mode_bits;
+    if (w.costed) {
+      r.target = a.target, r.weight = a.weight, r.cost = a.cost;
+      r.cost_sched = count > 0 ? a.groups << 24 : 0u;
+      r.tgt_row = a.target_stride, r.wt_row = a.weight_stride, r.tgt_blk = tgt_blk;
     }
-    const uint64_t per = fb->gain_per_uav ? (uint64_t)count : 1u;
-    r.gain_col = (uint32_t)per, r.gain_lane = fb->gain_per_uav ? 1 : 0;
-    r.gain_blk = fb->gain_blocks == 1 ? 0u : (uint64_t)width * (uint64_t)fb_width * per;
-    r.ref_row  = fb->ref_stride;
-    r.ref_blk  = fb->ref_blocks == 1 ? 0u : fb->ref_stride ? (uint64_t)count * (uint64_t)fb->ref_stride : (uint64_t)fb_width;
-    r.fb_word  = fb->groups | (uint32_t)fb_width << 8;
-    if (s->arith == MRS_ARITH_FAST)
-      HIPCHK(mrs_launch_rollout_feedback_fast(s->view(), r, dt, n_steps, cmd_every, obs_every, variant, s->stream));
-    else
-      HIPCHK(mrs_launch_rollout_feedback_literal(s->view(), r, dt, n_steps, cmd_every, obs_every, variant, s->stream));
-    return fence_out(s, ext);
-  }
-  if (cost) {  // evaluations in place of observation rows: the kernels of rollout_cost_device.inc, whatever the rates are
-    if (count > 0 && !cost->accumulate) HIPCHK(hipMemsetAsync(cost->cost, 0, (size_t)count * sizeof(double), s->stream));  // (+0.0)
+    const uint64_t per = a.gain_per_uav ? (uint64_t)count : 1u;
+    r.gain_col = (uint32_t)per, r.gain_lane = a.gain_per_uav ? 1 : 0;
+    r.gain_blk = a.gain_blocks == 1 ? 0u : (uint64_t)w.cmd * (uint64_t)w.fb * per;
+    r.ref_row  = a.ref_stride;
+    r.ref_blk  = a.ref_blocks == 1 ? 0u : a.ref_stride ? (uint64_t)count * (uint64_t)a.ref_stride : (uint64_t)w.fb;
+    r.fb_word  = a.fb_groups | (uint32_t)w.fb << 8;
+    HIPCHK((fast ? mrs_launch_rollout_feedback_fast : mrs_launch_rollout_feedback_literal)(s->view(), r, a.dt, n_steps, cmd_every, obs_every, variant, s->stream));
+  } else if (cost) {  // evaluations in place of observation rows: the cost kernels of rollout_cost_device.inc, whatever the rates are
     RolloutCostDev r{};
-    r.cmd = dev_cmd, r.target = cost->target, r.weight = cost->weight, r.cost = cost->cost;
-    r.first = first, r.count = count, r.cmd_stride = cmd_stride;
-    r.cmd_sched  = ((uint32_t)width | (dtype == MRS_DTYPE_F32 ? 32u : 0u)) << 24;
-    r.cost_sched = count > 0 ? groups << 24 : 0u;
-    r.mode_bits  = (uint32_t)mode << FLAG_MODE_SHIFT;
-    r.tgt_row = cost->target_stride, r.wt_row = cost->weight_stride;
-    r.tgt_blk = cost->target_stride ? (uint64_t)count * (uint64_t)cost->target_stride : (uint64_t)obs_width;
-    if (s->arith == MRS_ARITH_FAST)
-      HIPCHK(mrs_launch_rollout_cost_fast(s->view(), r, dt, n_steps, cmd_every, obs_every, variant, s->stream));
-    else
-      HIPCHK(mrs_launch_rollout_cost_literal(s->view(), r, dt, n_steps, cmd_every, obs_every, variant, s->stream));
-    return fence_out(s, ext);
-  }
-  if (forced) {  // a third schedule: the kernels of rollout_force_device.inc, whatever the rates are
+    r.cmd = a.dev_cmd, r.target = a.target, r.weight = a.weight, r.cost = a.cost;
+    r.first = first, r.count = count, r.cmd_stride = a.cmd_stride;
+    r.cmd_sched = cmd_word, r.mode_bits = mode_bits;
+    r.cost_sched = count > 0 ? a.groups << 24 : 0u;
+    r.tgt_row = a.target_stride, r.wt_row = a.weight_stride, r.tgt_blk = tgt_blk;
+    HIPCHK((fast ? mrs_launch_rollout_cost_fast : mrs_launch_rollout_cost_literal)(s->view(), r, a.dt, n_steps, cmd_every, obs_every, variant, s->stream));
+  } else if (a.kind == ROLLOUT_FORCE) {  // a third schedule: the force kernels of rollout_rate_device.inc, whatever the rates are
     if (count > 0) s->fext_active = true;  // (the loop's first mrs_swarm_apply_force_device: from here on the steps read the F_FEXT columns)
     RolloutForceDev r{};
-    r.cmd = dev_cmd, r.obs = groups != 0u ? dev_obs : nullptr, r.force = count > 0 ? dev_force : nullptr;
+    r.cmd = a.dev_cmd, r.obs = obs, r.force = count > 0 ? a.dev_force : nullptr;
     r.first = first, r.count = count;
-    r.cmd_stride = cmd_stride, r.obs_stride = obs_stride, r.force_stride = force_stride;
-    r.cmd_sched = ((uint32_t)width | (dtype == MRS_DTYPE_F32 ? 32u : 0u)) << 24;
-    r.obs_sched = groups << 24;
-    r.mode_bits = (uint32_t)mode << FLAG_MODE_SHIFT;
-    if (s->arith == MRS_ARITH_FAST)
-      HIPCHK(mrs_launch_rollout_force_fast(s->view(), r, dt, n_steps, cmd_every, obs_every, force_every, variant, s->stream));
-    else
-      HIPCHK(mrs_launch_rollout_force_literal(s->view(), r, dt, n_steps, cmd_every, obs_every, force_every, variant, s->stream));
-    return fence_out(s, ext);
+    r.cmd_stride = a.cmd_stride, r.obs_stride = a.obs_stride, r.force_stride = a.force_stride;
+    r.cmd_sched = cmd_word, r.obs_sched = a.groups << 24, r.mode_bits = mode_bits;
+    HIPCHK((fast ? mrs_launch_rollout_force_fast : mrs_launch_rollout_force_literal)(s->view(), r, a.dt, n_steps, cmd_every, obs_every, a.force_every, variant,
+                                                                                     s->stream));
+  } else if (cmd_every == 1 && obs_every == 1) {  // a row before and after every step: the kernels of rollout_device.inc
+    const RolloutDev r{a.dev_cmd, obs, first, count, a.cmd_stride, w.cmd, a.obs_stride, 0, mode_bits, a.groups, f32 ? 1 : 0};
+    HIPCHK((fast ? mrs_launch_rollout_fast : mrs_launch_rollout_literal)(s->view(), r, a.dt, n_steps, variant, s->stream));
+  } else {  // the rate kernels of rollout_rate_device.inc
+    RolloutRateDev r{};
+    r.cmd = a.dev_cmd, r.obs = obs;
+    r.first = first, r.count = count;
+    r.cmd_stride = a.cmd_stride, r.obs_stride = a.obs_stride;
+    r.cmd_sched = cmd_word, r.obs_sched = a.groups << 24, r.mode_bits = mode_bits;
+    HIPCHK((fast ? mrs_launch_rollout_rate_fast : mrs_launch_rollout_rate_literal)(s->view(), r, a.dt, n_steps, cmd_every, obs_every, variant, s->stream));
   }
-  if (cmd_every == 1 && obs_every == 1) {  // a row before and after every step: the kernels of rollout_device.inc
-    const RolloutDev r{dev_cmd, groups != 0u ? dev_obs : nullptr, first, count, cmd_stride, width, obs_stride, 0, (uint32_t)mode << FLAG_MODE_SHIFT,
-                       groups, dtype == MRS_DTYPE_F32 ? 1 : 0};
-    if (s->arith == MRS_ARITH_FAST)
-      HIPCHK(mrs_launch_rollout_fast(s->view(), r, dt, n_steps, variant, s->stream));
-    else
-      HIPCHK(mrs_launch_rollout_literal(s->view(), r, dt, n_steps, variant, s->stream));
-    return fence_out(s, ext);
-  }
-  RolloutRateDev r{};  // (row block 0 and the call's width, dtype and groups: the launcher sets each launch's schedule and first blocks)
-  r.cmd = dev_cmd, r.obs = groups != 0u ? dev_obs : nullptr;
-  r.first = first, r.count = count;
-  r.cmd_stride = cmd_stride, r.obs_stride = obs_stride;
-  r.cmd_sched = ((uint32_t)width | (dtype == MRS_DTYPE_F32 ? 32u : 0u)) << 24;
-  r.obs_sched = groups << 24;
-  r.mode_bits = (uint32_t)mode << FLAG_MODE_SHIFT;
-  if (s->arith == MRS_ARITH_FAST)
-    HIPCHK(mrs_launch_rollout_rate_fast(s->view(), r, dt, n_steps, cmd_every, obs_every, variant, s->stream));
-  else
-    HIPCHK(mrs_launch_rollout_rate_literal(s->view(), r, dt, n_steps, cmd_every, obs_every, variant, s->stream));
   return fence_out(s, ext);
 }
 
 int mrs_swarm_rollout_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, const void* dev_cmd,
                              int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream) {
   MRS_LOCK(s);
-  return rollout_locked(s, first, count, mode, dt, n_steps, 1, 1, 0, dev_cmd, dtype, cmd_stride, nullptr, 0, groups, dev_obs, obs_stride, ext_stream, false,
-                        "mrs_swarm_rollout_device");
+  return rollout_locked(s, RolloutArgs{"mrs_swarm_rollout_device", ROLLOUT_ROWS, first, count, mode, dt, n_steps, 1, 1, dev_cmd, dtype, cmd_stride, groups,
+                                       dev_obs, obs_stride, ext_stream});
 }
 
 int mrs_swarm_rollout_rate_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every,
                                   int32_t obs_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs,
                                   int32_t obs_stride, void* ext_stream) {
   MRS_LOCK(s);
-  return rollout_locked(s, first, count, mode, dt, n_steps, cmd_every, obs_every, 0, dev_cmd, dtype, cmd_stride, nullptr, 0, groups, dev_obs, obs_stride,
-                        ext_stream, false, "mrs_swarm_rollout_rate_device");
+  return rollout_locked(s, RolloutArgs{"mrs_swarm_rollout_rate_device", ROLLOUT_ROWS, first, count, mode, dt, n_steps, cmd_every, obs_every, dev_cmd, dtype,
+                                       cmd_stride, groups, dev_obs, obs_stride, ext_stream});
 }
 
 int mrs_swarm_rollout_force_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every,
                                    int32_t obs_every, int32_t force_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride,
                                    const void* dev_force, int32_t force_stride, uint32_t groups, void* dev_obs, int32_t obs_stride, void* ext_stream) {
   MRS_LOCK(s);
-  return rollout_locked(s, first, count, mode, dt, n_steps, cmd_every, obs_every, force_every, dev_cmd, dtype, cmd_stride, dev_force, force_stride, groups,
-                        dev_obs, obs_stride, ext_stream, true, "mrs_swarm_rollout_force_device");
+  RolloutArgs a{"mrs_swarm_rollout_force_device", ROLLOUT_FORCE, first, count, mode, dt, n_steps, cmd_every, obs_every, dev_cmd, dtype, cmd_stride, groups,
+                dev_obs, obs_stride, ext_stream};
+  a.force_every = force_every, a.dev_force = dev_force, a.force_stride = force_stride;
+  return rollout_locked(s, a);
 }
 
 int mrs_swarm_rollout_cost_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every,
@@ -569,9 +577,11 @@ int mrs_swarm_rollout_cost_device(mrs_swarm_t* s, int32_t first, int32_t count, 
                                   const void* dev_target, int32_t target_stride, const void* dev_weight, int32_t weight_stride, double* dev_cost,
                                   int32_t accumulate, void* ext_stream) {
   MRS_LOCK(s);
-  const CostArgs cost{dev_target, target_stride, dev_weight, weight_stride, dev_cost, accumulate};
-  return rollout_locked(s, first, count, mode, dt, n_steps, cmd_every, cost_every, 0, dev_cmd, dtype, cmd_stride, nullptr, 0, groups, nullptr, 0, ext_stream,
-                        false, "mrs_swarm_rollout_cost_device", &cost);
+  RolloutArgs a{"mrs_swarm_rollout_cost_device", ROLLOUT_COST, first, count, mode, dt, n_steps, cmd_every, cost_every, dev_cmd, dtype, cmd_stride, groups,
+                nullptr, 0, ext_stream};
+  a.target = dev_target, a.target_stride = target_stride, a.weight = dev_weight, a.weight_stride = weight_stride;
+  a.cost = dev_cost, a.accumulate = accumulate;
+  return rollout_locked(s, a);
 }
 
 int mrs_swarm_rollout_feedback_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_steps, int32_t cmd_every,
@@ -580,10 +590,13 @@ int mrs_swarm_rollout_feedback_device(mrs_swarm_t* s, int32_t first, int32_t cou
                                       int32_t ref_blocks, uint32_t cost_groups, const void* dev_target, int32_t target_stride,
                                       const void* dev_weight, int32_t weight_stride, double* dev_cost, int32_t accumulate, void* ext_stream) {
   MRS_LOCK(s);
-  const CostArgs     cost{dev_target, target_stride, dev_weight, weight_stride, dev_cost, accumulate};
-  const FeedbackArgs fb{fb_groups, dev_gain, gain_per_uav, gain_blocks, dev_ref, ref_stride, ref_blocks};
-  return rollout_locked(s, first, count, mode, dt, n_steps, cmd_every, cost_every, 0, dev_cmd, dtype, cmd_stride, nullptr, 0, cost_groups, nullptr, 0,
-                        ext_stream, false, "mrs_swarm_rollout_feedback_device", &cost, &fb);
+  RolloutArgs a{"mrs_swarm_rollout_feedback_device", ROLLOUT_FEEDBACK, first, count, mode, dt, n_steps, cmd_every, cost_every, dev_cmd, dtype, cmd_stride,
+                cost_groups, nullptr, 0, ext_stream};
+  a.target = dev_target, a.target_stride = target_stride, a.weight = dev_weight, a.weight_stride = weight_stride;
+  a.cost = dev_cost, a.accumulate = accumulate;
+  a.fb_groups = fb_groups, a.gain = dev_gain, a.gain_per_uav = gain_per_uav, a.gain_blocks = gain_blocks;
+  a.ref = dev_ref, a.ref_stride = ref_stride, a.ref_blocks = ref_blocks;
+  return rollout_locked(s, a);
 }
 
 // timerMain over n_ticks ticks with caller rows: every tick is step_one (tick_single.hip) with the row blocks of that tick, then the
@@ -593,41 +606,21 @@ int mrs_swarm_rollout_tick_device(mrs_swarm_t* s, int32_t first, int32_t count, 
                                   int32_t obs_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs,
                                   int32_t obs_stride, uint8_t* dev_crashed, int32_t crash, double rebounce, void* ext_stream) {
   MRS_LOCK(s);
-  int rc = check_range(s, first, count);
+  RolloutArgs a{"mrs_swarm_rollout_tick_device", ROLLOUT_TICK, first, count, mode, dt, n_ticks, cmd_every, obs_every, dev_cmd, dtype, cmd_stride, groups,
+                dev_obs, obs_stride, ext_stream};
+  a.dev_crashed = dev_crashed, a.crash = crash, a.rebounce = rebounce;
+  RolloutWidths w;
+  int           rc = check_rollout_args(s, a, "n_ticks", "obs_every", w);
   if (rc) return rc;
-  if (s->comm_world > 0) return fail(MRS_ERR_ARG, "mrs_swarm_rollout_tick_device: not on a sharded swarm");
-  if (mode < MRS_INPUT_UNKNOWN || mode > MRS_POSITION_CMD) return fail(MRS_ERR_ARG, "bad input mode");
-  if ((rc = check_dtype(dtype))) return rc;
-  if (n_ticks < 1) return fail(MRS_ERR_ARG, "n_ticks must be at least 1");
-  if (cmd_every < 1 || n_ticks % cmd_every != 0) return fail(MRS_ERR_ARG, "cmd_every must be at least 1 and divide n_ticks");
-  if (obs_every < 1 || n_ticks % obs_every != 0) return fail(MRS_ERR_ARG, "obs_every must be at least 1 and divide n_ticks");
-  if (!(dt > 0) || !std::isfinite(dt)) return fail(MRS_ERR_ARG, "dt must be finite and > 0");
-  if (!std::isfinite(rebounce)) return fail(MRS_ERR_ARG, "rebounce must be finite");
-  const int width = command_width(mode, cmd_stride);
-  if (width > 0 && (cmd_stride < width || width < 1)) return fail(MRS_ERR_ARG, "cmd_stride too small for this mode");
-  int32_t obs_width = 0;
-  if ((rc = mrs_swarm_gather_width(groups, &obs_width))) return rc;
-  if (groups != 0u && obs_stride < obs_width) return fail(MRS_ERR_ARG, "obs_stride smaller than the width of the selected groups");
-  const size_t elem = dtype_bytes(dtype);
-  if (count > 0) {  // 64-bit: blocks x count x stride can pass 2^31 elements
-    const size_t cmd_rows = (size_t)(n_ticks / cmd_every) * (size_t)count, obs_rows = (size_t)(n_ticks / obs_every) * (size_t)count;
-    if (width > 0 && (rc = check_device_ptr(s, dev_cmd, ((cmd_rows - 1) * (size_t)cmd_stride + (size_t)width) * elem, "dev_cmd"))) return rc;
-    if (groups != 0u && (rc = check_device_ptr(s, dev_obs, ((obs_rows - 1) * (size_t)obs_stride + (size_t)obs_width) * elem, "dev_obs"))) return rc;
-    if (dev_crashed && (rc = check_device_ptr(s, dev_crashed, obs_rows, "dev_crashed"))) return rc;
-    if (mode == MRS_ACTUATOR_CMD && !actuator_width_ok(s, first, count, width)) return fail(MRS_ERR_ARG, "actuator payload narrower than n_motors");
-  }
+  const int    width = w.cmd;
+  const size_t elem  = dtype_bytes(dtype);
   if (s->n == 0) return MRS_OK;
   HIPCHK(hipSetDevice(s->device));
   // like a command call: launches queued by earlier calls must have run before the mode mirror (which picks the kernel variant of a
   // replay) changes; a collision tick pending at entry stays pending — the first launch of this call evaluates it
   if (!s->log.empty() && (rc = drain(s))) return rc;
   if ((rc = upload_types(s, dt))) return rc;
-  if (count > 0) {
-    const uint8_t* m    = s->uav_mode.data() + first;
-    unsigned       diff = 0;
-    for (int k = 0; k < count; k++) diff |= (unsigned)(m[k] ^ (uint8_t)mode);
-    if (diff) track_mode(s, first, count, mode);
-  }
+  rollout_track_mode(s, a);
   hipStream_t ext = (hipStream_t)ext_stream;
   if ((rc = fence_in(s, ext))) return rc;
   if ((rc = begin_profile(s))) return rc;

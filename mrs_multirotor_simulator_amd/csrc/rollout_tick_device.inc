@@ -132,15 +132,14 @@ MRS_ROLLOUT_TICK_KERNEL(mrs_uav_rollout_tick_mixed, (64, MRS_WAVES_PER_SIMD), tr
 #undef MRS_ROLLOUT_TICK_KERNEL
 
 // One tick of the whole swarm: the fused step + collision-evaluation launch of mrs_launch_step_coll (single GPU) with the rows of `r`.
-// variant and the buffer / pointer choice as there (MRS_NO_BUFFER_ADDRESSING forces pointers).
+// variant and the buffer / pointer choice as there (rollout_buffer_addressing).
 extern "C" hipError_t KNAME(mrs_launch_rollout_tick)(SwarmDev sw, CollDev cd, RolloutTickDev r, double dt, int variant, hipStream_t st) {
   const int nb = (sw.n + 63) / 64;
   if (nb <= 0) return hipSuccess;
   sw.blk0 = 0;
-  const dim3        g(nb), b(64);
-  const double      inv_dt = 1.0 / dt;
-  static const bool no_buf = getenv("MRS_NO_BUFFER_ADDRESSING") != nullptr;
-  const bool        buf    = !no_buf && (unsigned long long)F_COUNT * (unsigned long long)sw.npad * 8ull < (1ull << 32);
+  const dim3   g(nb), b(64);
+  const double inv_dt = 1.0 / dt;
+  const bool   buf    = rollout_buffer_addressing(sw);
   if (buf && variant == 1)
     hipLaunchKernelGGL(KNAME(mrs_uav_model_rollout_tick_buf), g, b, 0, st, sw, dt, inv_dt, cd, r);
   else if (buf)

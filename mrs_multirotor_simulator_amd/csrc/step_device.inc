@@ -1156,7 +1156,7 @@ DEV bool coll_fold_and_decide(CDT& cd0, const int part, const uint32_t stall_own
 // epoch word / ticket to the launches that run beside this one (step_kernel_publish), whatever its lanes do afterwards.
 // HK: what a launch does around each fused sub-step besides stepping (MULTI only; rollout_device.inc).  enter() runs once per lane
 // after the wave-uniform exits and may finish the lane itself (true); cmd(s) runs at the top of sub-step s, before the controller
-// cascade, cmd_lane(s) behind it with the lane (the state BEFORE the sub-step: rollout_feedback_device.inc), and obs(s) after post_step.  The default does nothing: every kernel of this file compiles as it did without the hook.
+// cascade, cmd_lane(s) behind it with the lane (the state BEFORE the sub-step: the feedback hook of rollout_cost_device.inc), and obs(s) after post_step.  The default does nothing: every kernel of this file compiles as it did without the hook.
 // One hook type, RolloutTickHook (rollout_tick_device.inc), rides on the single-GPU COLL kernels instead: one step per launch, and
 // held(), the last thing a held lane does — in COLL kernels a held lane takes part in the collisions and leaves inside
 // MRS_COLLIDE_THEN, so enter() cannot finish it.

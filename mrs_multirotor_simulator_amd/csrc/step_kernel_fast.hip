@@ -3,7 +3,5 @@
 #include "step_device.inc"
 #include "rollout_device.inc"
 #include "rollout_rate_device.inc"
-#include "rollout_force_device.inc"
 #include "rollout_cost_device.inc"
-#include "rollout_feedback_device.inc"
 #include "rollout_tick_device.inc"

@@ -132,8 +132,40 @@ inline uint32_t mrs_ro_sched(int s0, int every) {
   const uint32_t m = p == 1u ? 4096u : 4096u / p + 1u;  // x / p == (x * m) >> 12 for x < 64: the error x * (m - 4096 / p) / 4096 < 64 / 4096 <= 1 / p
   return (uint32_t)s0 | (p - 1u) << 6 | (m - 1u) << 12;
 }
+// How a hook reads a schedule word: one text for the kernels and for the host (tests/cpp/rollout_sched_test.cpp).
+#if defined(__HIP__)
+#define MRS_HD __attribute__((host)) __attribute__((device)) inline __attribute__((always_inline))
+#else
+#define MRS_HD inline
+#endif
+// sub-step s (< 64) is the j-th due one of the schedule w (-1: it is not due)
+MRS_HD int mrs_ro_due(uint32_t w, int s) {
+  const unsigned x = (unsigned)s - MRS_RO_S0(w);
+  const unsigned j = (x * MRS_RO_M(w)) >> 12;
+  return ((unsigned)s >= MRS_RO_S0(w) && j * MRS_RO_P(w) == x) ? (int)j : -1;
+}
+// due sub-steps of the schedule w among the first `substeps`
+MRS_HD int mrs_ro_due_count(uint32_t w, int substeps) {
+  if ((unsigned)substeps <= MRS_RO_S0(w)) return 0;
+  return (int)((((unsigned)substeps - 1u - MRS_RO_S0(w)) * MRS_RO_M(w)) >> 12) + 1;
+}
+// One schedule of the launch that takes the steps t0 .. t0 + sub - 1 (sub <= 64) of a call, from the call's word (its top byte: width and
+// dtype, groups, or 3 for a force row) and its rate.  Blocks of a START schedule begin at a due step (commands, forces: block j from step
+// j * every on), blocks of an END schedule end with one (observations, evaluations: block j behind step (j + 1) * every - 1).  `word`
+// is the launch's schedule word and `blk0` the call's block of its first due sub-step: the launch's rows start there.  No due step in
+// the launch: a start schedule keeps the dtype bit alone (the command word's; a force word has none and becomes 0), an end schedule is 0.
+struct mrs_ro_launch {
+  uint32_t  word;
+  long long blk0;
+};
+inline mrs_ro_launch mrs_ro_launch_sched(uint32_t call_word, int t0, int sub, int every, bool start) {
+  const int       s0   = start ? (every - t0 % every) % every : every - 1 - t0 % every;
+  const long long blk0 = start ? ((long long)t0 + s0) / every : t0 / every;
+  if (s0 < sub) return {(call_word & 0xFF000000u) | mrs_ro_sched(s0, every), blk0};
+  return {start ? call_word & (32u << 24) : 0u, blk0};
+}
 
-// ---- one launch of a control-rate rollout under scheduled external forces (mrs_swarm_rollout_force_device, rollout_force_device.inc) ----
+// ---- one launch of a control-rate rollout under scheduled external forces (mrs_swarm_rollout_force_device, rollout_rate_device.inc) ----
 // RolloutRateDev and a third schedule: force row block j (applyForce, world frame, N) is latched in the F_FEXT columns from step
 // j * force_every on.  The dtype bit stays in cmd_sched.
 struct RolloutForceDev {
@@ -167,7 +199,7 @@ struct RolloutCostDev {
   int32_t     wt_row;      // weight_stride, or 0: one weight row for every evaluation
 };
 
-// ---- one launch of a feedback rollout (mrs_swarm_rollout_feedback_device, rollout_feedback_device.inc) ----
+// ---- one launch of a feedback rollout (mrs_swarm_rollout_feedback_device, rollout_cost_device.inc) ----
 // RolloutCostDev, whose command side becomes the NOMINAL command, and the gains and setpoints of the launch's command blocks: at the
 // launch's j-th due command sub-step the F_CMD columns of UAV first + k take cmd row (j, k) + G(j, k) (ref row (j, k) - observation
 // row of fb_groups).  G(j, k)[c][col] sits at element j * gain_blk + k * gain_lane + (c * row width + col) * gain_col of `gain`:

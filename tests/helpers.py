@@ -147,3 +147,89 @@ def assert_close(a, b, rtol, what=""):
     e = rel_linf(a, b)
     assert e <= rtol, f"{what}: relative L-inf error {e:.3e} > {rtol:.1e}"
     return e
+
+
+# the rollout kernels, as the sources define them -------------------------------------------------------------------------------
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mrs_multirotor_simulator_amd", "csrc")
+STEP_UNITS = ("step_kernel_fast.hip", "step_kernel_literal.hip")
+ROLLOUT_FAMILIES = ["", "_rate", "_force", "_cost", "_feedback"]  # the infixes of the MRS_ROLLOUT_FAMILY lines, in definition order
+
+
+def macro_lines(text, macro):
+    """{kernel: [bounds, argument, ...]} of the `macro(kernel, (bounds), ...)` instantiation lines of a source text, in order"""
+    out = {}
+    for line in text.splitlines():
+        m = re.match(rf"{macro}\(\s*([\w#]+)\s*,\s*(\(.*?\))\s*,\s*(.*?)\)\s*\\?$", line.strip())
+        if m:
+            out[m.group(1)] = [m.group(2).replace(" ", "")] + [a.strip() for a in m.group(3).split(",")]
+    return out
+
+
+class RolloutKernels:
+    """The rollout kernels both step units compile, from the sources: every MRS_ROLLOUT_FAMILY(infix, descriptor, hook) line of the
+    included rollout files times the MRS_ROLLOUT_SHAPE lines of that macro, and the MRS_ROLLOUT_TICK_KERNEL lines.
+      families : {infix: {kernel: [bounds, CASCADE, UNIFORM, BUF]}}, infixes and kernels in definition order
+      types    : {infix: (descriptor, hook)}
+      tick     : {kernel: [bounds, CASCADE, UNIFORM, ACC, SU]}
+      order    : every kernel name in definition order
+      files    : the rollout files in include order; texts : {file: text}"""
+
+    def __init__(self):
+        lists = []
+        for unit in STEP_UNITS:
+            text = open(os.path.join(CSRC, unit)).read()
+            lists.append(re.findall(r'^#include "(\w+\.inc)"$', text, flags=re.M))
+            assert text.rstrip().endswith('#include "%s"' % lists[-1][-1]), unit
+        assert lists[0] == lists[1], "both step units compile the same files in the same order"
+        assert lists[0][0] == "step_device.inc"
+        self.files = [f for f in lists[0] if f.startswith("rollout_")]
+        assert self.files == lists[0][1:], "the rollout files come behind step_device.inc, and nothing else does"
+        self.texts = {f: open(os.path.join(CSRC, f)).read() for f in self.files}
+        shapes = macro_lines(self.texts["rollout_device.inc"], "MRS_ROLLOUT_SHAPE")
+        assert all(v[-2:] == ["DevType", "HookType"] for v in shapes.values()), shapes
+        self.families, self.types, self.tick, self.order = {}, {}, {}, []
+        for f in self.files:
+            for infix, dev, hook in re.findall(r"^MRS_ROLLOUT_FAMILY\((\w*), (\w+), (\w+)\)$", self.texts[f], flags=re.M):
+                assert infix not in self.families, infix
+                self.types[infix] = (dev, hook)
+                self.families[infix] = {k.replace("##infix##", infix).replace("##infix", infix): v[:-2] for k, v in shapes.items()}
+                self.order += list(self.families[infix])
+            tick = macro_lines(self.texts[f], "MRS_ROLLOUT_TICK_KERNEL")
+            self.tick.update(tick)
+            self.order += list(tick)
+        step = open(os.path.join(CSRC, "step_device.inc")).read()
+        self.step_kernels = re.findall(r"MRS_STEP_KERNEL\w*\(\s*(\w+)", step)
+
+    def check_table(self, names, table, module, what):
+        """the kernels `names` and the rows of a *_KERNELS table of a GPU test module correspond, every row names tests of that
+        module, and none of the kernels is compiled twice or is a step-kernel line of step_device.inc"""
+        names, rows = set(names), set(table)
+        assert not names - rows, f"{what} kernels without a row: {sorted(names - rows)}"
+        assert not rows - names, f"rows naming {what} kernels that are no longer compiled: {sorted(rows - names)}"
+        for kernel, where in table.items():
+            assert where, kernel
+            for w in where:
+                assert callable(getattr(module, w.split("[")[0], None)), f"{kernel}: {w} is no test of {module.__name__}"
+        assert len(self.order) == len(set(self.order)), "a rollout kernel is defined twice"
+        assert "rollout" not in " ".join(self.step_kernels) and not set(self.order) & set(self.step_kernels)
+        assert not any("MRS_STEP_KERNEL" in t for t in self.texts.values()), "the step-kernel table of test_step_kernel_table stays as it is"
+
+    def check_family(self, infix, table, module, mirrors=None):
+        """family `infix` is five kernels with a row each in `table`; it comes behind the family `mirrors` (an infix) and has its
+        shapes, launch bounds included, kernel for kernel"""
+        fam = self.families[infix]
+        assert len(fam) == 5, sorted(fam)
+        self.check_table(fam, table, module, f"rollout{infix}")
+        assert list(self.families) == ROLLOUT_FAMILIES, "the families, in the order the later ones build on the earlier"
+        if mirrors is not None:
+            assert ROLLOUT_FAMILIES.index(mirrors) < ROLLOUT_FAMILIES.index(infix)
+            assert {k.replace("rollout" + infix, "rollout" + mirrors): v for k, v in fam.items()} == self.families[mirrors]
+
+
+_rollout_kernels = []
+
+
+def rollout_kernels():
+    if not _rollout_kernels:
+        _rollout_kernels.append(RolloutKernels())
+    return _rollout_kernels[0]

@@ -1,6 +1,6 @@
 """CPU-side checks of device-resident rollouts (include/mrs_swarm.h, "device-resident rollouts"): the call is exported and listed, the
-header prototype and the ctypes argtypes agree, tensors.rollout refuses what the library must never see, every rollout kernel of
-rollout_device.inc has a row in test_rollout_gpu.ROLLOUT_KERNELS, and tests/cpp/rollout_test.cpp compiles.  CPU tensors only: no
+header prototype and the ctypes argtypes agree, tensors.rollout refuses what the library must never see, every kernel of the plain
+rollout family (helpers.rollout_kernels) has a row in test_rollout_gpu.ROLLOUT_KERNELS, and tests/cpp/rollout_test.cpp compiles.  CPU tensors only: no
 pointer reaches the library."""
 import ctypes as C
 import os
@@ -9,9 +9,9 @@ import re
 import pytest
 
 import test_rollout_gpu as R
+from helpers import rollout_kernels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "mrs_multirotor_simulator_amd", "csrc", "rollout_device.inc")
 CTYPE = {"mrs_swarm_t*": C.c_void_p, "const void*": C.c_void_p, "void*": C.c_void_p, "int32_t": C.c_int32, "uint32_t": C.c_uint32,
          "double": C.c_double}
 
@@ -94,29 +94,9 @@ def test_rollout_refuses_bad_tensors(monkeypatch):
         T.rollout(g, 10, [[[0.0] * 4] * 10] * 5, 0.001, pos, out=out)
 
 
-def rollout_kernel_entry_points(text):
-    """names of the MRS_ROLLOUT_KERNEL(name, ...) instantiations (the idea of test_step_kernel_table.step_kernel_entry_points)"""
-    names = set()
-    for line in text.splitlines():
-        m = re.match(r"MRS_ROLLOUT_KERNEL\(\s*(\w+)\s*,", line.strip())
-        if m:
-            names.add(m.group(1))
-    return names
-
-
 def test_every_rollout_kernel_has_a_row():
-    with open(SRC) as f:
-        names = rollout_kernel_entry_points(f.read())
-    assert len(names) == 5, sorted(names)
-    table = set(R.ROLLOUT_KERNELS)
-    assert not names - table, f"rollout kernels without a row in ROLLOUT_KERNELS: {sorted(names - table)}"
-    assert not table - names, f"rows naming kernels rollout_device.inc no longer compiles: {sorted(table - names)}"
-    for kernel, where in R.ROLLOUT_KERNELS.items():
-        for w in where:
-            assert callable(getattr(R, w.split("[")[0], None)), f"{kernel}: {w} is no test of test_rollout_gpu"
-    # and none of them is a step-kernel line: the step-kernel matrix of test_step_variants_gpu stays as it is
-    step = open(os.path.join(ROOT, "mrs_multirotor_simulator_amd", "csrc", "step_device.inc")).read()
-    assert "rollout" not in " ".join(re.findall(r"MRS_STEP_KERNEL\w*\(\s*(\w+)", step))
+    """the first family: five kernels, a row each, and none of them a step-kernel line (test_step_variants_gpu's matrix stays as it is)"""
+    rollout_kernels().check_family("", R.ROLLOUT_KERNELS, R)
 
 
 def test_rollout_test_compiles(mrs, tmp_path):

@@ -4,8 +4,8 @@ dtypes, a wrong number of evaluations, target and weight shapes it cannot addres
 before the library is reached, a well-formed call reaches rollout_cost_device and nothing else, and tests/cpp/rollout_cost_test.cpp
 compiles.  CPU tensors only: no pointer reaches the library.
 
-The cost has kernels of its own (rollout_cost_device.inc, MRS_ROLLOUT_COST_KERNEL lines): every one of them has a row in
-test_rollout_cost_gpu.ROLLOUT_COST_KERNELS, one per rate kernel, and the file holds no line of the other three kernel macros."""
+The cost has kernels of its own (the _cost family of helpers.rollout_kernels): every one of them has a row in
+test_rollout_cost_gpu.ROLLOUT_COST_KERNELS, one per rate kernel, and none of them belongs to one of the three families before it."""
 import ctypes as C
 import inspect
 import os
@@ -15,10 +15,9 @@ import subprocess
 import pytest
 
 import test_rollout_cost_gpu as RC
+from helpers import rollout_kernels
 from test_rollout import CTYPE, ROOT
 from test_rollout_rate import _fakes
-
-SRC = os.path.join(ROOT, "mrs_multirotor_simulator_amd", "csrc", "rollout_cost_device.inc")
 
 NAMES = ["s", "first", "count", "mode", "dt", "n_steps", "cmd_every", "cost_every", "dev_cmd", "dtype", "cmd_stride", "groups", "dev_target",
          "target_stride", "dev_weight", "weight_stride", "dev_cost", "accumulate", "ext_stream"]
@@ -167,32 +166,13 @@ def test_strides_handed_to_the_library(monkeypatch):
 
 
 def test_every_rollout_cost_kernel_has_a_row():
+    """one cost kernel per rate kernel, with its shape and launch bounds, compiled by both step units behind the force family"""
     import test_rollout_rate_gpu as RR
-    text = open(SRC).read()
-    names = set()
-    for line in text.splitlines():
-        m = re.match(r"MRS_ROLLOUT_COST_KERNEL\(\s*(\w+)\s*,", line.strip())
-        if m:
-            names.add(m.group(1))
-    assert len(names) == 5, sorted(names)
-    table = set(RC.ROLLOUT_COST_KERNELS)
-    assert not names - table, f"cost kernels without a row in ROLLOUT_COST_KERNELS: {sorted(names - table)}"
-    assert not table - names, f"rows naming kernels rollout_cost_device.inc no longer compiles: {sorted(table - names)}"
-    for kernel, where in RC.ROLLOUT_COST_KERNELS.items():
-        for w in where:
-            assert callable(getattr(RC, w.split("[")[0], None)), f"{kernel}: {w} is no test of test_rollout_cost_gpu"
-    # one cost kernel per rate kernel, with its shape and launch bounds
-    assert {n.replace("rollout_cost", "rollout_rate") for n in names} == set(RR.ROLLOUT_RATE_KERNELS)
-    rate_text = open(os.path.join(os.path.dirname(SRC), "rollout_rate_device.inc")).read()
-    shapes = {m.group(1).replace("rollout_rate", "rollout_cost"): m.group(2) for m in re.finditer(r"^MRS_ROLLOUT_RATE_KERNEL\((\w+),(.*)\)$", rate_text, flags=re.M)}
-    assert shapes == {m.group(1): m.group(2) for m in re.finditer(r"^MRS_ROLLOUT_COST_KERNEL\((\w+),(.*)\)$", text, flags=re.M)}
-    # both step units include the file behind the force file
-    for unit in ("step_kernel_fast.hip", "step_kernel_literal.hip"):
-        u = open(os.path.join(os.path.dirname(SRC), unit)).read()
-        assert '#include "rollout_cost_device.inc"' in u and u.index('#include "rollout_force_device.inc"') < u.index('#include "rollout_cost_device.inc"'), unit
-    # and it holds no line of the other three kernel macros: their tables stay as they are
-    assert "MRS_STEP_KERNEL" not in text
-    assert not re.search(r"^MRS_ROLLOUT_(RATE_|FORCE_)?KERNEL\(", text, flags=re.M)
+    k = rollout_kernels()
+    k.check_family("_cost", RC.ROLLOUT_COST_KERNELS, RC, mirrors="_rate")
+    assert set(k.families["_rate"]) == set(RR.ROLLOUT_RATE_KERNELS)
+    assert list(k.families).index("_force") < list(k.families).index("_cost")
+    assert not set(k.families["_cost"]) & (set(k.families[""]) | set(k.families["_rate"]) | set(k.families["_force"]))
 
 
 def test_restatement_helper_is_the_stated_loop():

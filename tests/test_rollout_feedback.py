@@ -5,8 +5,8 @@ parameters of Swarm.rollout_feedback_device agree; the width helpers refuse unkn
 cannot address before the library is reached and hands the strides on; tests/cpp/rollout_feedback_test.cpp compiles.  CPU tensors only:
 no pointer reaches the library.
 
-The call has kernels of its own (rollout_feedback_device.inc, MRS_ROLLOUT_FEEDBACK_KERNEL lines): every one of them has a row in
-test_rollout_feedback_gpu.FEEDBACK_KERNELS, one per cost kernel, and the file holds no line of the other kernel macros."""
+The call has kernels of its own (the _feedback family of helpers.rollout_kernels): every one of them has a row in
+test_rollout_feedback_gpu.FEEDBACK_KERNELS, one per cost kernel, and none of them belongs to another family or to the tick kernels."""
 import ctypes as C
 import inspect
 import os
@@ -17,11 +17,9 @@ import numpy as np
 import pytest
 
 import test_rollout_feedback_gpu as RF
+from helpers import rollout_kernels
 from test_rollout import CTYPE, ROOT
 from test_rollout_rate import _fakes
-
-CSRC = os.path.join(ROOT, "mrs_multirotor_simulator_amd", "csrc")
-SRC = os.path.join(CSRC, "rollout_feedback_device.inc")
 
 NAMES = ["s", "first", "count", "mode", "dt", "n_steps", "cmd_every", "cost_every", "dev_cmd", "dtype", "cmd_stride", "fb_groups", "dev_gain",
          "gain_per_uav", "gain_blocks", "dev_ref", "ref_stride", "ref_blocks", "cost_groups", "dev_target", "target_stride", "dev_weight",
@@ -233,33 +231,13 @@ def test_strides_handed_to_the_library(monkeypatch):
 
 
 def test_every_feedback_kernel_has_a_row():
+    """one feedback kernel per cost kernel, with its shape, compiled by both step units behind the cost family"""
     import test_rollout_cost_gpu as RC
-    text = open(SRC).read()
-    names = set(re.findall(r"^MRS_ROLLOUT_FEEDBACK_KERNEL\(\s*(\w+)\s*,", text, flags=re.M))
-    assert len(names) == 5, sorted(names)
-    table = set(RF.FEEDBACK_KERNELS)
-    assert not names - table, f"feedback kernels without a row in FEEDBACK_KERNELS: {sorted(names - table)}"
-    assert not table - names, f"rows naming kernels rollout_feedback_device.inc no longer compiles: {sorted(table - names)}"
-    for kernel, where in RF.FEEDBACK_KERNELS.items():
-        assert where, kernel
-        for w in where:
-            assert callable(getattr(RF, w.split("[")[0], None)), f"{kernel}: {w} is no test of test_rollout_feedback_gpu"
-    # one feedback kernel per cost kernel, with its shape
-    assert {n.replace("rollout_feedback", "rollout_cost") for n in names} == set(RC.ROLLOUT_COST_KERNELS)
-    cost_text = open(os.path.join(CSRC, "rollout_cost_device.inc")).read()
-
-    def shape(m):  # (CASCADE, UNIFORM, BUF: the launch bounds are the feedback file's own)
-        return m.group(2).rsplit(")", 1)[1]
-
-    shapes = {m.group(1).replace("rollout_cost", "rollout_feedback"): shape(m) for m in re.finditer(r"^MRS_ROLLOUT_COST_KERNEL\((\w+),(.*)\)$", cost_text, flags=re.M)}
-    assert shapes == {m.group(1): shape(m) for m in re.finditer(r"^MRS_ROLLOUT_FEEDBACK_KERNEL\((\w+),(.*)\)$", text, flags=re.M)}
-    # both step units include the file behind the cost file
-    for unit in ("step_kernel_fast.hip", "step_kernel_literal.hip"):
-        u = open(os.path.join(CSRC, unit)).read()
-        assert u.index('#include "rollout_cost_device.inc"') < u.index('#include "rollout_feedback_device.inc"'), unit
-    # and it holds no line of the other kernel macros: their tables stay as they are
-    assert "MRS_STEP_KERNEL" not in text
-    assert not re.search(r"^MRS_ROLLOUT_(RATE_|FORCE_|COST_|TICK_)?KERNEL\(", text, flags=re.M)
+    k = rollout_kernels()
+    k.check_family("_feedback", RF.FEEDBACK_KERNELS, RF, mirrors="_cost")
+    assert set(k.families["_cost"]) == set(RC.ROLLOUT_COST_KERNELS)
+    others = [n for f, fam in k.families.items() if f != "_feedback" for n in fam] + list(k.tick)
+    assert not set(k.families["_feedback"]) & set(others)
 
 
 def test_rollout_feedback_test_compiles(mrs, tmp_path):

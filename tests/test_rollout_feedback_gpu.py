@@ -17,7 +17,7 @@ The reference is always a twin swarm of the same flavour, advanced one command b
 test_rollout_cost_gpu.restate is applied to its FP64 rows for the cost.  Every comparison is bit for bit; a NaN cost is compared as a
 class (test_rollout_cost_gpu).  In LITERAL the state is also compared with the plain set_input / step_n loop.
 
-FEEDBACK_KERNELS maps every entry point of rollout_feedback_device.inc to the tests that force it (test_rollout_feedback.py keeps it
+FEEDBACK_KERNELS maps every entry point of the feedback family of rollout_cost_device.inc to the tests that force it (test_rollout_feedback.py keeps it
 complete)."""
 import ctypes as C
 import math
@@ -50,7 +50,7 @@ assert all(s % h == 0 and s % e == 0 for h, e, s in RATES) and 70 > LAUNCH_CAP a
 NAN_OK = np.array([2400 - FIRST])  # the UAV of the range whose velocity the fixture makes non-finite (test_step_variants_gpu.single_scenario)
 assert 0 <= NAN_OK[0] < COUNT
 
-# which tests force each entry point of rollout_feedback_device.inc (both flavours)
+# which tests force each entry point of the feedback family of rollout_cost_device.inc (both flavours)
 FEEDBACK_KERNELS = {
     "mrs_uav_rollout_feedback": ("test_pointer_form",),
     "mrs_uav_rollout_feedback_buf": ("test_cost_and_state_equal_the_reference[cascade-LITERAL]", "test_cost_and_state_equal_the_reference[cascade-FAST]"),

@@ -4,7 +4,7 @@ its ctypes argtypes and parameter names, tensors.rollout(forces=, force_hold=) a
 the library is reached, a well-formed call with forces reaches rollout_force_device and nothing else, and
 tests/cpp/rollout_force_test.cpp compiles.  CPU tensors only: no pointer reaches the library.
 
-The forces have kernels of their own (rollout_force_device.inc, MRS_ROLLOUT_FORCE_KERNEL lines): every one of them has a row in
+The forces have kernels of their own (the _force family of helpers.rollout_kernels): every one of them has a row in
 test_rollout_force_gpu.ROLLOUT_FORCE_KERNELS and a rate counterpart, and the tables of the step, plain and rate kernels stay as they are."""
 import ctypes as C
 import os
@@ -14,11 +14,10 @@ import subprocess
 import pytest
 
 import test_rollout_force_gpu as RF
+from helpers import rollout_kernels
 from test_rollout import CTYPE, ROOT
 from test_rollout_rate import NAMES as RATE_NAMES
 from test_rollout_rate import _fakes
-
-SRC = os.path.join(ROOT, "mrs_multirotor_simulator_amd", "csrc", "rollout_force_device.inc")
 
 # the rate call with force_every behind obs_every and dev_force, force_stride behind cmd_stride
 NAMES = RATE_NAMES[:8] + ["force_every"] + RATE_NAMES[8:11] + ["dev_force", "force_stride"] + RATE_NAMES[11:]
@@ -165,31 +164,11 @@ def test_apply_force_refuses_bad_tensors(monkeypatch):
 
 
 def test_every_rollout_force_kernel_has_a_row():
-    names = set()
-    with open(SRC) as f:
-        for line in f:
-            m = re.match(r"MRS_ROLLOUT_FORCE_KERNEL\(\s*(\w+)\s*,", line.strip())
-            if m:
-                names.add(m.group(1))
-    assert len(names) == 5, sorted(names)
-    assert len(re.findall(r"^MRS_ROLLOUT_FORCE_KERNEL\(", open(SRC).read(), flags=re.M)) == 5
-    table = set(RF.ROLLOUT_FORCE_KERNELS)
-    assert not names - table, f"force kernels without a row in ROLLOUT_FORCE_KERNELS: {sorted(names - table)}"
-    assert not table - names, f"rows naming kernels rollout_force_device.inc no longer compiles: {sorted(table - names)}"
-    for kernel, where in RF.ROLLOUT_FORCE_KERNELS.items():
-        assert where, kernel
-        for w in where:
-            assert callable(getattr(RF, w.split("[")[0], None)), f"{kernel}: {w} is no test of test_rollout_force_gpu"
-    # one force kernel per rate kernel, and both step units compile them behind the rate kernels
-    assert {n.replace("rollout_force", "rollout_rate") for n in names} == set(RF.RR.ROLLOUT_RATE_KERNELS)
-    for unit in ("step_kernel_fast.hip", "step_kernel_literal.hip"):
-        text = open(os.path.join(os.path.dirname(SRC), unit)).read()
-        assert '#include "rollout_force_device.inc"' in text, unit
-        assert text.index('#include "rollout_rate_device.inc"') < text.index('#include "rollout_force_device.inc"'), unit
-    # and none of them is a step-kernel, a plain or a rate rollout line: the tables of the other tests stay as they are
-    text = open(SRC).read()
-    assert "MRS_STEP_KERNEL" not in text
-    assert not re.search(r"^MRS_ROLLOUT_KERNEL\(", text, flags=re.M) and not re.search(r"^MRS_ROLLOUT_RATE_KERNEL\(", text, flags=re.M)
+    """one force kernel per rate kernel, compiled by both step units behind the rate family and apart from the plain and the rate one"""
+    k = rollout_kernels()
+    k.check_family("_force", RF.ROLLOUT_FORCE_KERNELS, RF, mirrors="_rate")
+    assert set(k.families["_rate"]) == set(RF.RR.ROLLOUT_RATE_KERNELS)
+    assert not set(k.families["_force"]) & (set(k.families[""]) | set(k.families["_rate"]))
 
 
 def test_rollout_force_test_compiles(mrs, tmp_path):

@@ -52,7 +52,7 @@ FORCE_MAX = 4.0  # N per axis: the order of the airframes' weight
 RATES = ((1, 1, 1, 5), (4, 4, 2, 8), (3, 6, 4, 132), (10, 5, 7, 70), (70, 140, 35, 140), (5, 130, 130, 130), (130, 5, 1, 130), (2, 2, 70, 140))
 assert all(s % c == 0 and s % o == 0 and s % f == 0 for c, o, f, s in RATES) and 70 > LAUNCH_CAP and 132 == 2 * LAUNCH_CAP + 4
 
-# which test forces each entry point of rollout_force_device.inc (both flavours; test_rollout_force.py keeps the table complete)
+# which test forces each kernel of the force family of rollout_rate_device.inc (both flavours; test_rollout_force.py keeps the table complete)
 ROLLOUT_FORCE_KERNELS = {
     "mrs_uav_rollout_force": ("test_pointer_form",),
     "mrs_uav_rollout_force_buf": ("test_literal_equals_the_loop[cascade]", "test_equals_apply_force_and_the_rate_rollout[cascade-FAST]"),

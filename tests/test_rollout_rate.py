@@ -3,8 +3,11 @@ listed, its header prototype and ctypes argtypes agree, tensors.rollout refuses 
 undecimated size before the library is reached, everything test_rollout.test_rollout_refuses_bad_tensors refuses is still refused at
 hold = 3, and tests/cpp/rollout_rate_test.cpp compiles.  CPU tensors only: no pointer reaches the library.
 
-The rates have kernels of their own (rollout_rate_device.inc, MRS_ROLLOUT_RATE_KERNEL lines): every one of them has a row in
-test_rollout_rate_gpu.ROLLOUT_RATE_KERNELS, and the five MRS_ROLLOUT_KERNEL lines of rollout_device.inc stay as test_rollout.py knows them."""
+The rates have kernels of their own (the _rate family of helpers.rollout_kernels): every one of them has a row in
+test_rollout_rate_gpu.ROLLOUT_RATE_KERNELS, and the five kernels of the plain family stay as test_rollout.py knows them.
+
+The per-launch schedule (swarm_layout.h: mrs_ro_launch_sched, mrs_ro_due, mrs_ro_due_count) is checked against brute force by
+tests/cpp/rollout_sched_test.cpp, on the host."""
 import ctypes as C
 import os
 import re
@@ -13,9 +16,8 @@ import subprocess
 import pytest
 
 import test_rollout_rate_gpu as RR
+from helpers import CSRC, rollout_kernels
 from test_rollout import CTYPE, ROOT, _Dev
-
-SRC = os.path.join(ROOT, "mrs_multirotor_simulator_amd", "csrc", "rollout_rate_device.inc")
 
 NAMES = ["s", "first", "count", "mode", "dt", "n_steps", "cmd_every", "obs_every", "dev_cmd", "dtype", "cmd_stride", "groups", "dev_obs",
          "obs_stride", "ext_stream"]
@@ -144,36 +146,33 @@ def test_rollout_refuses_bad_tensors_at_a_hold(monkeypatch):
 
 
 def test_every_rollout_rate_kernel_has_a_row():
-    names = set()
-    with open(SRC) as f:
-        for line in f:
-            m = re.match(r"MRS_ROLLOUT_RATE_KERNEL\(\s*(\w+)\s*,", line.strip())
-            if m:
-                names.add(m.group(1))
-    assert len(names) == 5, sorted(names)
-    table = set(RR.ROLLOUT_RATE_KERNELS)
-    assert not names - table, f"rate kernels without a row in ROLLOUT_RATE_KERNELS: {sorted(names - table)}"
-    assert not table - names, f"rows naming kernels rollout_rate_device.inc no longer compiles: {sorted(table - names)}"
-    for kernel, where in RR.ROLLOUT_RATE_KERNELS.items():
-        for w in where:
-            assert callable(getattr(RR, w.split("[")[0], None)), f"{kernel}: {w} is no test of test_rollout_rate_gpu"
-    # one rate kernel per plain rollout kernel, and both step units compile them
-    assert {n.replace("rollout_rate", "rollout") for n in names} == set(RR.R.ROLLOUT_KERNELS)
-    for unit in ("step_kernel_fast.hip", "step_kernel_literal.hip"):
-        assert '#include "rollout_rate_device.inc"' in open(os.path.join(os.path.dirname(SRC), unit)).read(), unit
-    # and none of them is a step-kernel or a plain rollout line: the tables of test_step_kernel_table and test_rollout stay as they are
-    assert "MRS_STEP_KERNEL" not in open(SRC).read() and not re.search(r"^MRS_ROLLOUT_KERNEL\(", open(SRC).read(), flags=re.M)
+    """one rate kernel per plain rollout kernel, compiled by both step units behind the plain family and apart from it"""
+    k = rollout_kernels()
+    k.check_family("_rate", RR.ROLLOUT_RATE_KERNELS, RR, mirrors="")
+    assert set(k.families[""]) == set(RR.R.ROLLOUT_KERNELS) and not set(k.families[""]) & set(k.families["_rate"])
 
 
 def test_schedule_division_is_exact():
     """RolloutRateDev's schedule: (x * M) >> 12 == x / P for every sub-step distance x < 64 and period P <= 64, with M as mrs_ro_sched
     (swarm_layout.h) computes it, and M - 1 fits its 12 bits"""
-    src = open(os.path.join(os.path.dirname(SRC), "swarm_layout.h")).read()
+    src = open(os.path.join(CSRC, "swarm_layout.h")).read()
     assert "p == 1u ? 4096u : 4096u / p + 1u" in src and "(((w) >> 12) & 4095u) + 1u" in src
     for p in range(1, 65):
         m = 4096 if p == 1 else 4096 // p + 1
         assert m - 1 < 4096
         assert all((x * m) >> 12 == x // p for x in range(64)), p
+
+
+def test_launch_schedule_against_brute_force(tmp_path):
+    """tests/cpp/rollout_sched_test.cpp: every rate 1..70, launch start 0..448 and launch length 1..64, start and end schedules"""
+    exe = str(tmp_path / "rollout_sched_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, os.path.join(ROOT, "tests", "cpp", "rollout_sched_test.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "launches with due steps ok" in out.stdout, out.stdout + out.stderr
+    # the hooks read the schedule through the text this program checked, not through a copy of it
+    texts = rollout_kernels().texts
+    assert all(" due(" not in t and "due_count(" not in t.replace("mrs_ro_due_count(", "") for t in texts.values())
+    assert "mrs_ro_due(" in texts["rollout_device.inc"] and "mrs_ro_due_count(" in texts["rollout_rate_device.inc"]
 
 
 def test_rollout_rate_test_compiles(mrs, tmp_path):

@@ -3,9 +3,9 @@ header prototype is the one specified and agrees with the ctypes argtypes, tenso
 crash rows that are not dense and wrong block counts before the library is reached, and tests/cpp/rollout_tick_test.cpp compiles.  CPU
 tensors only: no pointer reaches the library.
 
-The call has kernels of its own (rollout_tick_device.inc, MRS_ROLLOUT_TICK_KERNEL lines): exactly four, each with a row in
-test_rollout_tick_gpu.ROLLOUT_TICK_KERNELS and the shape of the single-GPU MRS_STEP_KERNEL_COLL line it mirrors; the file holds no
-step-kernel line and no line of the other rollout macros, so the tables of the earlier tests stay as they are."""
+The call has kernels of its own (the tick kernels of helpers.rollout_kernels): exactly four, each with a row in
+test_rollout_tick_gpu.ROLLOUT_TICK_KERNELS and the shape of the single-GPU MRS_STEP_KERNEL_COLL line it mirrors; they belong to no
+rollout family and are no step-kernel line, so the tables of the earlier tests stay as they are."""
 import ctypes as C
 import os
 import re
@@ -14,10 +14,8 @@ import subprocess
 import pytest
 
 import test_rollout_tick_gpu as RT
+from helpers import CSRC, macro_lines, rollout_kernels
 from test_rollout import CTYPE, ROOT, _Dev
-
-CSRC = os.path.join(ROOT, "mrs_multirotor_simulator_amd", "csrc")
-SRC = os.path.join(CSRC, "rollout_tick_device.inc")
 
 NAMES = ["s", "first", "count", "mode", "dt", "n_ticks", "cmd_every", "obs_every", "dev_cmd", "dtype", "cmd_stride", "groups", "dev_obs",
          "obs_stride", "dev_crashed", "crash", "rebounce", "ext_stream"]
@@ -55,43 +53,30 @@ def test_header_prototype_equals_the_argtypes(mrs):
     assert "src/multirotor_simulator.cpp:211-217" in open(os.path.join(ROOT, "include", "mrs_swarm.h")).read()
 
 
-def _lines(path, macro):
-    """the argument lists of the `macro(...)` instantiation lines of a file"""
-    out = {}
-    for line in open(path):
-        m = re.match(rf"{macro}\(\s*(\w+)\s*,\s*(\(.*?\))\s*,\s*(.*)\)\s*$", line.strip())
-        if m:
-            out[m.group(1)] = [m.group(2).replace(" ", "")] + [a.strip() for a in m.group(3).split(",")]
-    return out
-
-
 def test_every_rollout_tick_kernel_has_a_row_and_the_shape_of_its_mirror():
-    tick = _lines(SRC, "MRS_ROLLOUT_TICK_KERNEL")
-    assert len(tick) == 4, sorted(tick)
-    table = set(RT.ROLLOUT_TICK_KERNELS)
-    assert not set(tick) - table, f"tick kernels without a row in ROLLOUT_TICK_KERNELS: {sorted(set(tick) - table)}"
-    assert not table - set(tick), f"rows naming kernels rollout_tick_device.inc no longer compiles: {sorted(table - set(tick))}"
-    for kernel, where in RT.ROLLOUT_TICK_KERNELS.items():
-        for w in where:
-            assert callable(getattr(RT, w.split("[")[0], None)), f"{kernel}: {w} is no test of test_rollout_tick_gpu"
+    k = rollout_kernels()
+    assert len(k.tick) == 4, sorted(k.tick)
+    k.check_table(k.tick, RT.ROLLOUT_TICK_KERNELS, RT, "tick")
     # (bounds, CASCADE, UNIFORM, ACC, SU) of the mirrored line, which is a single-GPU one (SHARD == false)
-    coll = _lines(os.path.join(CSRC, "step_device.inc"), "MRS_STEP_KERNEL_COLL")
-    single = {k for k, v in coll.items() if v[-1] == "false"}
+    coll = macro_lines(open(os.path.join(CSRC, "step_device.inc")).read(), "MRS_STEP_KERNEL_COLL")
+    single = {n for n, v in coll.items() if v[-1] == "false"}
     assert single == set(MIRRORS.values()), sorted(single)
-    assert set(tick) == set(MIRRORS)
-    for name, args in tick.items():
+    assert set(k.tick) == set(MIRRORS)
+    for name, args in k.tick.items():
         assert args == coll[MIRRORS[name]][:-1], (name, args, coll[MIRRORS[name]])
-    for unit in ("step_kernel_fast.hip", "step_kernel_literal.hip"):
-        text = open(os.path.join(CSRC, unit)).read()
-        assert text.rstrip().endswith('#include "rollout_tick_device.inc"'), f"{unit}: the tick kernels come last"
+    # both step units compile the tick kernels last (rollout_kernels checks that the two include lists are one)
+    assert k.files[-1] == "rollout_tick_device.inc" and k.order[-4:] == list(k.tick)
 
 
 def test_no_other_kernel_lines_in_the_file():
-    text = open(SRC).read()
+    """the tick kernels are the only kernels of their file: no family, no shape and no step-kernel line, and no schedule words"""
+    k = rollout_kernels()
+    text = k.texts["rollout_tick_device.inc"]
     assert "MRS_STEP_KERNEL" not in text
-    for macro in ("MRS_ROLLOUT_KERNEL", "MRS_ROLLOUT_RATE_KERNEL", "MRS_ROLLOUT_FORCE_KERNEL", "MRS_ROLLOUT_COST_KERNEL"):
+    for macro in ("MRS_ROLLOUT_FAMILY", "MRS_ROLLOUT_SHAPE"):
         assert not re.search(rf"^\s*(#define\s+)?{macro}\(", text, flags=re.M), macro
-    assert "mrs_ro_sched" not in text and "MRS_RO_" not in text, "one launch is one tick: no schedule words"
+    assert not set(k.tick) & {n for fam in k.families.values() for n in fam}
+    assert "mrs_ro_sched" not in text and "MRS_RO_" not in text and "mrs_ro_" not in text, "one launch is one tick: no schedule words"
 
 
 class _Swarm:

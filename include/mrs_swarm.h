@@ -338,7 +338,7 @@ int mrs_debug_stream_delay(void* stream, double microseconds);
 int mrs_swarm_comm_init_standin(mrs_swarm_t* s, int32_t world, int32_t rank, int64_t n_total, double collective_latency_us, double slab_width);
 /* Peer-window exchange — the collectives of the sharded tick as direct writes into the peers' device memory over xGMI, no
  * collective library and no host in the tick (one small kernel per collective on the swarm's stream: push into every peer's
- * window, signal, wait for every peer's signal, pull — csrc/collide.hip k_peer_allgather).  xGMI is point to point: a rank's block
+ * window, signal, wait for every peer's signal, pull — csrc/transport_peer.hip k_peer_allgather).  xGMI is point to point: a rank's block
  * reaches every peer in ONE hop, where a ring all-gather pays 2 (world - 1) hops behind its own kernel launch.
  *   mrs_swarm_peer_window_create : allocates this rank's window (4096 + 2 * world * slot bytes, slot = the largest shard's full
  *       gather) and returns its address (`window`, for peers in the same process) and / or its 64-byte IPC handle (`ipc_handle64`,

@@ -2,9 +2,11 @@
 
 hipcc cross-compiles without a GPU, so this also is the "does it build" check on the CPU-only container.
 """
+import contextlib
 import os
 import shutil
 import subprocess
+import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -16,11 +18,13 @@ UNITS = [
     ("step_kernel_literal.hip", "off"),
     ("step_kernel_fast.hip", "fast"),
     ("collide.hip", "off"),
+    ("collide_export.hip", "off"),
     ("outputs.hip", "off"),
     ("device_io.hip", "off"),  # off: its observation rows equal the publisher payloads of outputs.hip bit for bit
     ("nearest.hip", "off"),  # off: d2 = ((dx*dx) + dy*dy) + dz*dz literally, which a numpy restatement reproduces bit for bit
     ("snapshot.hip", "off"),  # no arithmetic (records are copied bit for bit); off like every other unit
-    # host side (no kernels): C ABI, single-GPU tick, sharded tick, the three transports
+    # host side: C ABI, single-GPU tick, sharded tick, the three transports (transport_local and transport_peer hold the kernels of
+    # their collectives, the others none)
     ("host_api.hip", "off"),
     ("tick_single.hip", "off"),
     ("tick_sharded.hip", "off"),
@@ -28,7 +32,7 @@ UNITS = [
     ("transport_local.hip", "off"),
     ("transport_peer.hip", "off"),
 ]
-DEPS = ["step_device.inc", "rollout_device.inc", "rollout_rate_device.inc", "rollout_cost_device.inc", "rollout_tick_device.inc", "collide_device.inc", "swarm_layout.h", "pose_math.h", "obs_row.h", "host_internal.h", "sharded_protocol.h", os.path.join("..", "..", "include", "mrs_swarm.h")]
+DEPS = ["step_device.inc", "rollout_device.inc", "rollout_rate_device.inc", "rollout_cost_device.inc", "rollout_tick_device.inc", "collide_device.inc", "collide_work.h", "swarm_layout.h", "pose_math.h", "obs_row.h", "host_internal.h", "sharded_protocol.h", os.path.join("..", "..", "include", "mrs_swarm.h")]
 
 
 def _hipcc():
@@ -45,29 +49,46 @@ def _stale(target, sources):
     return any(os.path.getmtime(s) > t for s in sources)
 
 
-def build_library(force=False, verbose=False):
+def _run(cmd, verbose):
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+
+
+def build_library(force=False, verbose=False, out=None, extra_flags=None):
+    """out, extra_flags: a variant for the measurement tools (tools/build_variants.sh), linked to `out`.  extra_flags maps unit names
+    to lists of extra compiler flags: those units are compiled into a temporary directory, every other unit is the regular object."""
+    extra_flags = extra_flags or {}
+    if not set(extra_flags) <= {src for src, _ in UNITS} or (extra_flags and not out):
+        raise ValueError("a variant names units of UNITS and is linked to a path of its own")
     hipcc = _hipcc()
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     deps = [os.path.join(CSRC, d) for d in DEPS]
-    objs = []
-    for src, contract in UNITS:
-        s = os.path.join(CSRC, src)
-        o = os.path.join(objdir, src.replace(".hip", ".o"))
-        if force or _stale(o, [s] + deps):
-            cmd = [hipcc, "-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", f"-ffp-contract={contract}",
-                   "-fno-fast-math", "-Wall", "-Wno-unused-function", "-c", s, "-o", o]
-            if verbose:
-                print(" ".join(cmd))
-            subprocess.check_call(cmd)
-        objs.append(o)
-    if force or _stale(LIB, objs):
-        cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    return LIB
+    lib = out or LIB
+    with tempfile.TemporaryDirectory() if extra_flags else contextlib.nullcontext() as vardir:
+        objs = []
+        for src, contract in UNITS:
+            s = os.path.join(CSRC, src)
+            o = os.path.join(vardir if src in extra_flags else objdir, src.replace(".hip", ".o"))
+            if force or src in extra_flags or _stale(o, [s] + deps):
+                _run([hipcc, "-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", f"-ffp-contract={contract}", "-fno-fast-math", "-Wall",
+                      "-Wno-unused-function", *extra_flags.get(src, ()), "-c", s, "-o", o], verbose)
+            objs.append(o)
+        if force or extra_flags or _stale(lib, objs):
+            _run([hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", lib] + objs, verbose)
+    return lib
 
 
-if __name__ == "__main__":
-    print(build_library(force=True, verbose=True))
+if __name__ == "__main__":  # no options: the library, from scratch; --out PATH [--flags UNIT=FLAGS ...]: a variant
+    import argparse
+    import shlex
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    ap.add_argument("--flags", action="append", default=[], metavar="UNIT=FLAGS", help="e.g. collide.hip=-DMRS_SKIN=0.75")
+    a = ap.parse_args()
+    variant = {}
+    for unit, _, flags in (f.partition("=") for f in a.flags):
+        variant.setdefault(unit, []).extend(shlex.split(flags))
+    print(build_library(force=not a.out, verbose=not a.out, out=a.out, extra_flags=variant))

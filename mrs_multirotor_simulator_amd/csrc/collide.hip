@@ -31,41 +31,14 @@
 // and the query kernel returns at once), host
 // writes to positions or airframe constants force a rebuild, and a UAV with more than LIST_CAP listed neighbours keeps
 // the pass in rebuild mode.  Results are identical to searching every tick.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
+//
+// The export-set exchange of sharded swarms lives in collide_export.hip (shared geometry and work object: collide_work.h); the
+// kernels of the stand-in collective and of the peer-window all-gather live with their transports (transport_local.hip, transport_peer.hip).
 #include <string.h>
 
-#include "swarm_layout.h"
-#include "collide_device.inc"
+#include "collide_work.h"
 
 namespace {
-
-// cells are floor(pos * INV_CELL): any consistent assignment with an edge above the search radius works, and the multiply
-// avoids three ~70-cycle IEEE divisions per cell_of
-constexpr double INV_CELL      = 1.0 / 1.75;  // plain search: edge 1.75 m > sqrt(3.0) = 1.7320508
-#ifndef MRS_SKIN
-#define MRS_SKIN 0.5  // (compile-time so that the cell arithmetic stays in constants; tools/variant_bench.sh sweeps it)
-#endif
-constexpr double SKIN          = MRS_SKIN;    // neighbour lists: how far apart beyond sqrt(3) a listed pair may be
-constexpr double SQRT3_UP      = 1.7320508075688775;                      // >= sqrt(3)
-constexpr double INV_CELL_WIDE = 1.0 / (SQRT3_UP + SKIN + 0.0179491924);  // list rebuild: edge 2.25 m > sqrt(3) + SKIN = 2.2320508 (SKIN 0.5)
-constexpr double LIST_R2       = (SQRT3_UP + SKIN) * (SQRT3_UP + SKIN) * (1.0 + 1e-9) + 1e-5;  // > (sqrt(3) + SKIN)^2 (4.98206 at SKIN 0.5)
-// Sharded swarms keep their lists longer: a search there is two collectives, a host synchronisation and a dozen launches (~200 us
-// against 37 us on one GPU), so the wider skin — half as many searches, 1.3 instead of 0.7 listed partners per UAV at 64 m^3 — pays
-// (one GPU, SKIN swept: 0.5 m 22.9 us per tick, 1.0 m 23.6).  Mode 2 of the WIDE / LISTS template arguments below.
-#ifndef MRS_SKIN_SHARDED
-#define MRS_SKIN_SHARDED 1.0
-#endif
-constexpr double SKIN2          = MRS_SKIN_SHARDED;
-constexpr double INV_CELL_WIDE2 = 1.0 / (SQRT3_UP + SKIN2 + 0.0179491924);
-constexpr double LIST_R2_2      = (SQRT3_UP + SKIN2) * (SQRT3_UP + SKIN2) * (1.0 + 1e-9) + 1e-5;
-constexpr double POS_LIMIT     = MRS_POS_LIMIT;  // |coordinate| beyond this (or non-finite) never collides here
-// fused evaluation: a UAV beyond this fraction of the distance that invalidates the lists makes the host queue the next search in
-// stream order (no stall, no replay); the remaining 25 % (6 cm) are ten ticks at 6 m/s — more than the host runs ahead of the device
-static const double WARN_FRACTION = getenv("MRS_WARN_FRACTION") ? atof(getenv("MRS_WARN_FRACTION")) : 0.75;
-constexpr int    LIST_CAP      = 24;          // listed neighbours per UAV (0.7 expected at 64 m^3 per UAV, 4.6 at 10 m^3: P(> 24) ~ 1e-11;
-                                              // with 8, one UAV in 10^4 overflowed at 30 m^3 per UAV and kept a 100 k swarm searching)
 
 struct Cell { int x, y, z; bool ok; };
 
@@ -1075,82 +1048,19 @@ static int query_lpu(long long n_own) {
 
 }  // namespace
 
-struct CollideWork {
-  long long cap_n = 0;
-  uint32_t  cap_T = 0;
-  int       cur   = 0;  // which head table the next tick fills; the other one is being wiped by that tick's query
-  uint2 *   head[2] = {nullptr, nullptr}, *next = nullptr;
-  // neighbour lists (single-GPU ticks)
-  PosRecord* rec_build = nullptr;  // records of the last rebuild: reference positions of the skin test + airframe constants
-  uint32_t * nbr = nullptr, *nbr_cnt = nullptr, *ctl = nullptr;
-  int        fcur = 0;             // which of ctl[0..1] the next tick reads
-  bool       lists_live = false;   // rec_build / nbr describe this swarm as of some earlier tick
-  double*    g_bbox = nullptr;       // gathered mode: this rank's bounding box widened by the list radius (6 doubles)
-  PosRecord* g_rec_build = nullptr;  // gathered mode: all records as of this rank's last rebuild
-  long long  g_cap = 0;
-  bool       g_lists_live = false;
-  // halo exchange of a search tick (mrs_collide_halo_*): instead of every rank's ALL records, the records that can be within the list
-  // radius of another rank's UAVs travel — [header | entries] of 64 B, the header's `j` = count, `pad` = flags
-  HaloEntry* h_send = nullptr;   // [1 + h_cap]
-  HaloEntry* h_recv = nullptr;   // [world][1 + h_cap]
-  long long  h_cap = 0, h_alloc = 0;  // entries per block in use; entries allocated (all blocks together, headers included)
-  int        h_world = 0;
-  uint32_t*  h_ctl = nullptr;    // [0] entries appended, [1] flags (MRS_HALO_*)
-  double*    g_box_out = nullptr;  // where a search of the export-set exchange also leaves its box (mrs_collide_set_box_out)
-  double*    h_part = nullptr;     // partial boxes of k_halo_select, one per block
-  long long  h_part_cap = 0;
-  bool       g_export_form = false;  // the last gathered search was one of the export-set exchange: lists end up in slot form, and of
-                                     // the record copy only this rank's own range (the skin references) is kept
-  // fused step + collision evaluation (step_device.inc *_coll): double-buffered positions, control words, pinned host mirror
-  // (three buffers: in a split sharded tick the interior launch of tick t+1 writes its output while the boundary launch of tick t
-  //  still reads its input — with two buffers those would be the same array)
-  Pos4*     P[3]  = {nullptr, nullptr, nullptr};
-  int       pcur  = 0;        // P[pcur] holds the positions after the most recent step (when the host says they are valid)
-  long long p_cap = 0;
-  uint32_t* fctl  = nullptr;  // CTL_WORDS device words
-  uint32_t* hostw = nullptr;  // CTL_WORDS pinned host words (stall, progress mirrored by the kernels)
-  // export-set exchange (multi-GPU ticks between searches): own UAVs listed by another rank, their slots in the padded collective
-  uint32_t*     exp_slot = nullptr;   // [n_local]
-  long long     exp_slot_cap = 0;
-  // split sharded ticks: class of every 64-UAV block, list of the boundary blocks, epoch word per block (swarm_layout.h)
-  uint32_t *    blk_class = nullptr, *blk_list = nullptr, *epoch = nullptr;
-  uint32_t*     host_heads = nullptr;  // pinned: heads of the slot maps + boundary-block count of the last search
-  long long     blk_cap = 0;
-  Pos4*         x_send = nullptr;     // [1 + x_cap]: header + exported positions of this rank
-  Pos4*         x_recv = nullptr;     // [world][1 + x_cap]
-  PartnerConst* x_const = nullptr;    // [world][1 + x_cap]
-  long long     x_cap = 0;            // export slots per rank in the collective
-  int           x_world = 0;
-};
-
+// Gives every buffer back.  ensure_tables also does this when the tables grow, so what is no buffer survives: the tables' size and turn
+// (cap_n, cap_T, cur — set anew by that caller), fcur, pcur, g_export_form, h_world, x_world, and g_box_out, which points into the
+// caller's slot-map block (mrs_collide_set_box_out).  A new field of CollideWork that is no buffer and has to survive goes into `keep`.
 static void free_work(CollideWork* w) {
-  (void)hipFree(w->head[0]); (void)hipFree(w->head[1]); (void)hipFree(w->next);
-  (void)hipFree(w->rec_build); (void)hipFree(w->nbr); (void)hipFree(w->nbr_cnt); (void)hipFree(w->ctl); (void)hipFree(w->g_rec_build);
-  (void)hipFree(w->g_bbox);
-  w->g_bbox = nullptr;
-  (void)hipFree(w->h_send); (void)hipFree(w->h_ctl); (void)hipFree(w->h_part);  // (h_recv lives in h_send's allocation)
-  w->h_part = nullptr; w->h_part_cap = 0;
-  w->h_send = w->h_recv = nullptr; w->h_ctl = nullptr; w->h_cap = w->h_alloc = 0;
-  (void)hipFree(w->exp_slot); (void)hipFree(w->x_send);  // (x_recv and x_const live in x_send's allocation)
-  w->exp_slot = nullptr; w->x_send = w->x_recv = nullptr; w->x_const = nullptr;
-  w->exp_slot_cap = w->x_cap = 0;
-  (void)hipFree(w->blk_class); (void)hipFree(w->blk_list); (void)hipFree(w->epoch);
-  w->blk_class = w->blk_list = w->epoch = nullptr;
-  w->blk_cap = 0;
-  (void)hipFree(w->P[0]); (void)hipFree(w->P[1]); (void)hipFree(w->P[2]); (void)hipFree(w->fctl);
+  void* const dev[] = {w->head[0], w->head[1], w->next, w->rec_build, w->nbr, w->nbr_cnt, w->ctl, w->g_rec_build, w->g_bbox, w->h_send, w->h_ctl,
+                       w->h_part, w->exp_slot, w->x_send, w->blk_class, w->blk_list, w->epoch, w->P[0], w->P[1], w->P[2], w->fctl};
+  for (void* p : dev) (void)hipFree(p);  // (h_recv lives in h_send's allocation, x_recv and x_const in x_send's)
   if (w->hostw) (void)hipHostFree(w->hostw);
   if (w->host_heads) (void)hipHostFree(w->host_heads);
-  w->host_heads = nullptr;
-  w->P[0] = w->P[1] = w->P[2] = nullptr;
-  w->p_cap = 0;
-  w->fctl = w->hostw = nullptr;
-  w->g_rec_build = nullptr;
-  w->g_cap = 0;
-  w->g_lists_live = false;
-  w->head[0] = w->head[1] = w->next = nullptr;
-  w->rec_build = nullptr;
-  w->nbr = w->nbr_cnt = w->ctl = nullptr;
-  w->lists_live = false;
+  CollideWork keep;
+  keep.cap_n = w->cap_n; keep.cap_T = w->cap_T; keep.cur = w->cur; keep.fcur = w->fcur; keep.pcur = w->pcur;
+  keep.g_export_form = w->g_export_form; keep.h_world = w->h_world; keep.x_world = w->x_world; keep.g_box_out = w->g_box_out;
+  *w = keep;
 }
 
 extern "C" void mrs_collide_free(CollideWork* w) {
@@ -1170,21 +1080,12 @@ extern "C" hipError_t mrs_launch_pack_positions(SwarmDev sw, PosRecord* out, hip
   return hipGetLastError();
 }
 
-// the mode word the collision code passes around as `crash` (collide_device.inc): the flavour of the force expression follows the swarm
-static inline int mode_word(const SwarmDev& sw, int crash) { return (crash ? MRS_MODE_CRASH : 0) | (sw.fast ? MRS_MODE_FAST : 0); }
-
-#define CK(e)                        \
-  do {                               \
-    hipError_t _e = (e);             \
-    if (_e != hipSuccess) return _e; \
-  } while (0)
-
 // What the step kernel needs for the skin test (all null/zero while no neighbour lists are live).
 extern "C" void mrs_collide_step_hook(const CollideWork* w, const PosRecord** rec, uint32_t** flag, double* lim2) {
   const bool on = w && w->lists_live;
   *rec  = on ? w->rec_build : nullptr;
   *flag = on ? w->ctl + w->fcur : nullptr;
-  *lim2 = (0.5 * SKIN) * (0.5 * SKIN) * (1.0 - 1e-9);
+  *lim2 = skin_lim2(SKIN);
 }
 
 // bits of a record index + 1 in an entry of the list-building format (2^ib > n_total; the cell tag keeps the other 32 - ib)
@@ -1212,8 +1113,8 @@ static hipError_t ensure_tables(CollideWork* w, long long n_total, hipStream_t s
   return hipSuccess;
 }
 
-// buffers of the fused step + collision evaluation for n local UAVs
-static hipError_t ensure_fused(CollideWork* w, long long n, hipStream_t st) {
+// buffers of the fused step + collision evaluation for n local UAVs (collide_export.hip sizes them too)
+hipError_t ensure_fused(CollideWork* w, long long n, hipStream_t st) {
   if (!w->fctl) {
     CK(hipMalloc(&w->fctl, sizeof(uint32_t) * CTL_WORDS));
     CK(hipMemsetAsync(w->fctl, 0, sizeof(uint32_t) * CTL_WORDS, st));
@@ -1230,6 +1131,26 @@ static hipError_t ensure_fused(CollideWork* w, long long n, hipStream_t st) {
     w->pcur  = 0;
   }
   return hipSuccess;
+}
+
+// the neighbour lists of cap_n UAVs and the control words of the list ticks, allocated with the first list tick after the tables
+static hipError_t ensure_lists(CollideWork* w, hipStream_t st) {
+  if (w->nbr) return hipSuccess;
+  CK(hipMalloc(&w->nbr, sizeof(uint32_t) * (size_t)LIST_CAP * (size_t)w->cap_n));
+  CK(hipMalloc(&w->nbr_cnt, sizeof(uint32_t) * (size_t)w->cap_n));
+  CK(hipMemsetAsync(w->nbr, 0, sizeof(uint32_t) * (size_t)LIST_CAP * (size_t)w->cap_n, st));  // rows beyond a UAV's count are read (not used)
+  CK(hipMemsetAsync(w->nbr_cnt, 0, sizeof(uint32_t) * (size_t)w->cap_n, st));
+  CK(hipMalloc(&w->ctl, sizeof(uint32_t) * 8));  // [0..1] skin flags, [2] rebuild counter, [4..5] "head table t holds entries"
+  w->fcur = 0;
+  return hipMemsetAsync(w->ctl, 0, sizeof(uint32_t) * 8, st);
+}
+
+// a list tick that cannot continue from the one before: both head tables and the flags start from nothing
+static hipError_t empty_tables(CollideWork* w, hipStream_t st) {
+  CK(hipMemsetAsync(w->head[0], 0, sizeof(uint2) * (size_t)w->cap_T, st));
+  CK(hipMemsetAsync(w->head[1], 0, sizeof(uint2) * (size_t)w->cap_T, st));
+  w->fcur = 0;
+  return hipMemsetAsync(w->ctl, 0, sizeof(uint32_t) * 8, st);
 }
 
 // Plain search every tick over ready (gathered) records — the multi-GPU path, and single-GPU ticks with lists switched off
@@ -1256,8 +1177,6 @@ extern "C" hipError_t mrs_collide_run(SwarmDev sw, CollideWork** work, const Pos
   return hipGetLastError();
 }
 
-// Single-GPU tick with neighbour lists.  force_rebuild: the host changed positions or airframe constants since the last call.
-// number of list rebuilds so far (device counter; synchronises the stream)
 // debugging aid (not part of the public header): the eight control words
 extern "C" hipError_t mrs_collide_debug_words(const CollideWork* w, hipStream_t st, unsigned* out8) {
   for (int k = 0; k < 8; k++) out8[k] = 0;
@@ -1279,6 +1198,7 @@ extern "C" hipError_t mrs_collide_copy_lists(const CollideWork* w, long long n, 
   return hipStreamSynchronize(st);
 }
 
+// number of list rebuilds so far (device counter; synchronises the stream)
 extern "C" hipError_t mrs_collide_rebuilds(const CollideWork* w, hipStream_t st, unsigned* out) {
   *out = 0;
   if (!w || !w->ctl) return hipSuccess;
@@ -1286,6 +1206,7 @@ extern "C" hipError_t mrs_collide_rebuilds(const CollideWork* w, hipStream_t st,
   return hipStreamSynchronize(st);
 }
 
+// Single-GPU tick with neighbour lists.  force_rebuild: the host changed positions or airframe constants since the last call.
 // guard_tau != 0: the pass is queued in stream order behind fused step launches (tick index of the last one = guard_tau): it does
 // nothing if those have stalled, and stalls what follows if the new lists come out incomplete
 extern "C" hipError_t mrs_collide_run_lists(SwarmDev sw, CollideWork** work, int crash, double rebounce, int force_rebuild, unsigned guard_tau,
@@ -1296,21 +1217,10 @@ extern "C" hipError_t mrs_collide_run_lists(SwarmDev sw, CollideWork** work, int
   crash = mode_word(sw, crash);
   CK(ensure_tables(w, n, st));
   if (!w->rec_build) CK(hipMalloc(&w->rec_build, sizeof(PosRecord) * (size_t)w->cap_n));
-  if (!w->nbr) {
-    CK(hipMalloc(&w->nbr, sizeof(uint32_t) * (size_t)LIST_CAP * (size_t)w->cap_n));
-    CK(hipMalloc(&w->nbr_cnt, sizeof(uint32_t) * (size_t)w->cap_n));
-    CK(hipMemsetAsync(w->nbr, 0, sizeof(uint32_t) * (size_t)LIST_CAP * (size_t)w->cap_n, st));  // rows beyond a UAV's count are read (not used)
-    CK(hipMemsetAsync(w->nbr_cnt, 0, sizeof(uint32_t) * (size_t)w->cap_n, st));
-    CK(hipMalloc(&w->ctl, sizeof(uint32_t) * 8));  // [0..1] skin flags, [2] rebuild counter, [4..5] "head table t holds entries"
-    CK(hipMemsetAsync(w->ctl, 0, sizeof(uint32_t) * 8, st));
-    w->fcur = 0;
-  }
+  CK(ensure_lists(w, st));
   CK(ensure_fused(w, w->cap_n, st));
   if (!w->lists_live) {  // first list tick, or plain-search ticks came in between: start from empty tables and flags
-    CK(hipMemsetAsync(w->head[0], 0, sizeof(uint2) * (size_t)w->cap_T, st));
-    CK(hipMemsetAsync(w->head[1], 0, sizeof(uint2) * (size_t)w->cap_T, st));
-    CK(hipMemsetAsync(w->ctl, 0, sizeof(uint32_t) * 8, st));
-    w->fcur = 0;
+    CK(empty_tables(w, st));
   }
   const int force = (force_rebuild || !w->lists_live) ? 1 : 0;
   const uint32_t T = w->cap_T, mask = T - 1;
@@ -1336,14 +1246,7 @@ extern "C" hipError_t mrs_collide_run_lists_gathered(SwarmDev sw, CollideWork** 
   CollideWork* w = *work;
   crash = mode_word(sw, crash);
   CK(ensure_tables(w, n_total, st));
-  if (!w->nbr) {
-    CK(hipMalloc(&w->nbr, sizeof(uint32_t) * (size_t)LIST_CAP * (size_t)w->cap_n));
-    CK(hipMalloc(&w->nbr_cnt, sizeof(uint32_t) * (size_t)w->cap_n));
-    CK(hipMemsetAsync(w->nbr, 0, sizeof(uint32_t) * (size_t)LIST_CAP * (size_t)w->cap_n, st));
-    CK(hipMemsetAsync(w->nbr_cnt, 0, sizeof(uint32_t) * (size_t)w->cap_n, st));
-    CK(hipMalloc(&w->ctl, sizeof(uint32_t) * 8));
-    CK(hipMemsetAsync(w->ctl, 0, sizeof(uint32_t) * 8, st));
-  }
+  CK(ensure_lists(w, st));
   if (n_total > w->g_cap) {
     CK(hipStreamSynchronize(st));
     (void)hipFree(w->g_rec_build);
@@ -1355,11 +1258,8 @@ extern "C" hipError_t mrs_collide_run_lists_gathered(SwarmDev sw, CollideWork** 
   if (!w->g_lists_live || w->g_export_form != export_form) {
     // first gathered search, or other modes came in between: empty tables and flags, rebuild.  Consecutive searches of the export-set
     // exchange skip this: the two head tables keep wiping each other, and nobody compares against the foreign part of the record copy.
-    CK(hipMemsetAsync(w->head[0], 0, sizeof(uint2) * (size_t)w->cap_T, st));
-    CK(hipMemsetAsync(w->head[1], 0, sizeof(uint2) * (size_t)w->cap_T, st));
-    CK(hipMemsetAsync(w->ctl, 0, sizeof(uint32_t) * 8, st));
+    CK(empty_tables(w, st));
     if (!export_form) CK(hipMemsetAsync(w->g_rec_build, 0xFF, sizeof(PosRecord) * (size_t)w->g_cap, st));  // NaN records
-    w->fcur = 0;
     w->g_lists_live = false;
   }
   const int      force = (w->g_lists_live && !force_rebuild) ? 0 : 1;
@@ -1370,7 +1270,7 @@ extern "C" hipError_t mrs_collide_run_lists_gathered(SwarmDev sw, CollideWork** 
   w->cur ^= 1;
   const unsigned gN = (unsigned)((n_total + 255) / 256);
   const int      ib = index_bits(n_total);
-  const double   lim2 = (0.5 * SKIN2) * (0.5 * SKIN2) * (1.0 - 1e-9);
+  const double   lim2 = skin_lim2(SKIN2);
   if (!w->g_bbox) CK(hipMalloc(&w->g_bbox, sizeof(double) * 6 * (BBOX_BLOCKS + 1)));  // the box, then the partial boxes
   if (force) {
     // (the search is decided: the comparison of all records with those of the last search would only cost time — 14 us at 1 M records;
@@ -1533,7 +1433,6 @@ extern "C" hipError_t mrs_collide_halo_prepare(CollideWork** work, int world, lo
   }
   return hipSuccess;
 }
-extern "C" long long mrs_collide_halo_capacity(const CollideWork* w) { return w ? w->h_cap : 0; }
 extern "C" void*     mrs_collide_halo_send(const CollideWork* w) { return w ? (void*)w->h_send : nullptr; }
 extern "C" void*     mrs_collide_halo_recv(const CollideWork* w) { return w ? (void*)w->h_recv : nullptr; }
 
@@ -1565,6 +1464,10 @@ extern "C" void mrs_collide_set_box_out(CollideWork** work, double* box_out) {
 }
 extern "C" int mrs_collide_halo_ready(const CollideWork* w, long long n_total) {
   return w && w->nbr && w->g_rec_build && n_total <= w->g_cap && w->g_lists_live && w->g_export_form && w->g_bbox ? 1 : 0;
+}
+// the next gathered tick starts from empty tables and searches (the lists are of another exchange's form, or incomplete)
+extern "C" void mrs_collide_invalidate_gathered(CollideWork* w) {
+  if (w) w->g_lists_live = false;
 }
 
 // the search itself on the table the halo exchange has filled: own box, insert (own records + received entries), list-building query
@@ -1601,7 +1504,7 @@ extern "C" hipError_t mrs_collide_fused_dev(const SwarmDev* sw, CollideWork* w, 
   cd->ctl      = w->fctl;
   cd->hostw    = w->hostw;
   cd->rebounce = rebounce;
-  cd->lim2     = (0.5 * SKIN) * (0.5 * SKIN) * (1.0 - 1e-9);
+  cd->lim2     = skin_lim2(SKIN);
   cd->lim2_warn = cd->lim2 * (WARN_FRACTION * WARN_FRACTION);
   cd->tau      = tau;
   cd->n        = sw->n;
@@ -1628,571 +1531,7 @@ extern "C" hipError_t mrs_collide_fused_reset(CollideWork* w, hipStream_t st) {
   w->hostw[CTL_STALL2] = w->hostw[CTL_WARN2] = 0u;
   return hipSuccess;
 }
-
-// ================================================================================================================================
-// Export-set exchange (multi-GPU): between two searches a rank only needs the positions of the FOREIGN UAVs its neighbour lists
-// name, and only has to publish the own UAVs some other rank lists.  Those two sets mirror each other — "j within the list radius
-// of i" is decided by the same squared distance on both sides, from the same gathered records — so a rank finds its export set in
-// its own lists: own UAV i is exported iff its list holds a foreign UAV.  A search tick (full gather, mrs_collide_run_lists_gathered)
-// is followed by
-//   k_export_mark      : export slot e_i for every own UAV with a foreign neighbour (any injective numbering will do)
-//   all-gather         : the slot maps of all ranks (4 B per UAV), headed by each rank's count
-//   k_export_translate : list entries (global record slots) -> local UAV index | FOREIGN + slot in the padded export collective;
-//                        airframe constants and search-time positions of the foreign partners are copied next to those slots
-// and every tick until the next search all-gathers 32 B per EXPORTED UAV instead of 48 B per UAV.
-// ================================================================================================================================
-namespace {
-
-__global__ void k_fill_positions(SwarmDev sw, Pos4* pos_now) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= sw.n) return;
-  const size_t np = (size_t)sw.npad;
-  const Pos4   pp = {sw.S[(size_t)(F_X + 0) * np + i], sw.S[(size_t)(F_X + 1) * np + i], sw.S[(size_t)(F_X + 2) * np + i],
-                     (double)(sw.F[i] >> FLAG_TYPE_SHIFT)};
-  pos_now[i]      = pp;
-}
-
-// one launch: control words (the error word stays: it is reported at the end of the call), slot map (padding UAVs: no slot), block
-// classes, and the export allocation — send block, gathered blocks, partner constants — zeroed (headers!)
-__global__ void k_search_reset(uint32_t* fctl, uint32_t* map, long long n_map, uint32_t* blk_class, int n_blocks, uint4* xalloc, long long n_xvec) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_map) map[i] = MRS_NO_SLOT;
-  if (i < n_blocks) blk_class[i] = 0u;
-  if (i < CTL_WORDS && i != CTL_ERROR && i != CTL_BADSLOT) fctl[i] = 0u;  // (sticky: the host reads both once per call, a call may hold several searches)
-  for (long long v = i; v < n_xvec; v += (long long)gridDim.x * blockDim.x) xalloc[v] = make_uint4(0u, 0u, 0u, 0u);
-}
-
-// map: [0] export count of this rank, [1] lanes over the list capacity so far, [2 + i] slot of own UAV i
-// ... and the position records of the UAVs as the search found them (what the first fused launch after the search reads)
-// ... and the displacement bound on the state the search found (pred_hdt >= 0): the lists are new, every UAV sits on its reference
-// position — if nobody can leave its skin within MRS_PRED_HORIZON steps, no stall index <= MRS_PRED_HORIZON can exist and the ticks
-// right after the search need no serial phase (CTL_PRED, sent to every rank with the head of the slot map)
-__global__ void k_export_mark(SwarmDev sw, Pos4* pos_now, long long n_max, int rank, const uint32_t* nbr, const uint32_t* nbr_cnt, uint32_t* exp_slot,
-                              uint32_t* map, uint32_t* fctl, uint32_t* blk_class, double pred_hdt, double pred_lim, double rebounce) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int n = sw.n;
-  if (i >= n) return;
-  const size_t   np = (size_t)sw.npad;
-  const uint32_t fl = sw.F[i];
-  double         y[18];
-#pragma unroll
-  for (int c = 0; c < 18; c++) y[c] = (pred_hdt >= 0.0 || c < 3) ? sw.S[(size_t)(c < 6 ? F_X + c : (c < 15 ? F_R + (c - 6) : F_W + (c - 15))) * np + i] : 0.0;
-  {
-    const Pos4 pp = {y[0], y[1], y[2], (double)(fl >> FLAG_TYPE_SHIFT)};
-    pos_now[i]    = pp;
-  }
-  const uint32_t cnt = nbr_cnt[i];
-  if (pred_hdt >= 0.0) {
-    const TypeParams& P = sw.T[fl >> FLAG_TYPE_SHIFT];
-    double            thrust = 0.0;  // allocation * rpm^2 with the motor speeds as they are (multirotor_model.hpp:332-335)
-    for (int m = 0; m < P.n_motors; m++) {
-      const double r = sw.S[(size_t)(F_RPM + m) * np + i];
-      thrust += P.alloc[3 * MRS_MAXM + m] * (r * r);
-    }
-    const bool   takeoff = (fl & FLAG_TAKEOFF) != 0u;
-    const double init_z  = takeoff ? sw.S[(size_t)F_INITZ * np + i] : 0.0;
-    const bool   usable  = mrs_pos_usable(y[0], y[1], y[2]);
-    if (usable && mrs_may_leave(y, 0.0, thrust, cnt, rebounce, pred_hdt, pred_lim, P.pred_a0, P.pred_thr, P.pred_drag, P.ground_enabled, P.ground_z, takeoff, init_z))
-      fctl[CTL_PRED] = 1u;  // (same value from every lane that finds one)
-  }
-  bool           exported = false;
-  for (uint32_t k = 0; k < cnt; k++) {
-    const uint32_t g = nbr[(size_t)k * (size_t)n + (size_t)i];
-    if ((long long)g / n_max != (long long)rank) exported = true;
-  }
-  uint32_t e = MRS_NO_SLOT;
-  if (exported) e = atomicAdd(&fctl[CTL_EXPORTS], 1u);
-  exp_slot[i] = e;
-  map[2 + i]  = e;
-  if (exported) atomicOr(&blk_class[i >> 6], MRS_BLK_BOUNDARY);  // the block is stepped by the boundary launch of a split tick
-}
-
-// Behind the marking launch (its block classes are complete): the boundary blocks in a list (any order) and their number; the interior
-// blocks that list a UAV of a boundary block (MRS_BLK_LAYER1: they wait for that block's epoch word in a split tick) and their number
-// (CTL_NL1: the residency bound of the split form); the head of the rank's slot map — export count (final), bit 31: some own UAV may
-// leave its skin within the horizon; lanes over the list capacity.  One thread per own UAV; list entries are still global record slots.
-__global__ void k_class_list(int n, long long n_max, int rank, const uint32_t* nbr, const uint32_t* nbr_cnt, uint32_t* blk_class, uint32_t* blk_list,
-                             uint32_t* fctl, uint32_t* map, const uint32_t* ctl) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) {
-    map[0] = fctl[CTL_EXPORTS] | (fctl[CTL_PRED] ? 0x80000000u : 0u);
-    map[1] = ctl[6];  // lanes over the list capacity (cumulative, collide.hip k_query)
-  }
-  if (i >= n) return;
-  const uint32_t mine = blk_class[i >> 6];
-  if ((i & 63) == 0 && (mine & MRS_BLK_BOUNDARY)) blk_list[atomicAdd(&fctl[CTL_NBND], 1u)] = (uint32_t)(i >> 6);
-  if (mine & MRS_BLK_BOUNDARY) return;
-  const uint32_t cnt = nbr_cnt[i];
-  bool           l1  = false;
-  for (uint32_t k = 0; k < cnt; k++) {
-    const long long g = (long long)nbr[(size_t)k * (size_t)n + (size_t)i], q = g / n_max;
-    if (q == (long long)rank && (blk_class[(g - q * n_max) >> 6] & MRS_BLK_BOUNDARY)) l1 = true;
-  }
-  // (the layer-1 blocks are listed from the back of the block list — the boundary blocks fill it from the front, a block is never both)
-  if (l1 && !(atomicOr(&blk_class[i >> 6], MRS_BLK_LAYER1) & MRS_BLK_LAYER1)) blk_list[(uint32_t)((n + 63) / 64) - 1u - atomicAdd(&fctl[CTL_NL1], 1u)] = (uint32_t)(i >> 6);
-}
-
-// start of a run of split ticks behind launch `tau`: every block counts as finished by that launch, nobody has arrived yet
-__global__ void k_handoff_init(uint32_t* fctl, uint32_t* epoch, int n_blocks, uint32_t tau) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < n_blocks) epoch[b] = tau;
-  if (b == 0) fctl[CTL_I_STARTED] = tau;
-}
-
-__global__ void k_export_header(uint32_t* map, const uint32_t* fctl, const uint32_t* ctl) {  // (a rank without UAVs)
-  map[0] = fctl[CTL_EXPORTS];
-  map[1] = ctl[6];
-}
-
-__global__ void k_export_translate(int n, long long n_max, int rank, long long map_stride, int block, uint32_t* nbr, const uint32_t* nbr_cnt,
-                                   const uint32_t* maps, const PosRecord* rec_all, Pos4* x_recv, PartnerConst* x_const, uint32_t* fctl) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t cnt = nbr_cnt[i];
-  for (uint32_t k = 0; k < cnt; k++) {
-    const size_t    at = (size_t)k * (size_t)n + (size_t)i;
-    const uint32_t  g  = nbr[at];
-    const long long q  = (long long)g / n_max, j = (long long)g - q * n_max;
-    if (q == (long long)rank) {
-      nbr[at] = (uint32_t)j;
-      continue;
-    }
-    const uint32_t e = maps[(size_t)q * (size_t)map_stride + 2 + (size_t)j];
-    if (e == MRS_NO_SLOT || (long long)e + 1 >= (long long)block) {  // cannot happen (symmetry / capacity checked by the host): keep the entry harmless
-      atomicAdd(&fctl[CTL_BADSLOT], 1u);
-      nbr[at] = MRS_NBR_FOREIGN | (uint32_t)(q * block);  // the owner's header record: w = stall word, position (0,0,0) + zero constants
-      continue;
-    }
-    const uint32_t slot = (uint32_t)(q * block + 1 + e);
-    nbr[at] = MRS_NBR_FOREIGN | slot;
-    const PosRecord r = rec_all[g];  // several lanes may write the same slot: same values
-    const Pos4         pp = {r.x, r.y, r.z, 0.0};
-    const PartnerConst cc = {r.mass, r.arm_length, r.prop_radius, 0.0};
-    x_recv[slot]  = pp;
-    x_const[slot] = cc;
-  }
-}
-
-// handleCollisions of the tick after the most recent step, evaluated on its own from the lists (local partners: position records,
-// foreign partners: gathered export buffer — both current): the settle step at the end of a run of sharded ticks
-// own_from_records: the UAV's own position comes from the position records too (cd.p_in) and crash flags are left alone — the
-// force a fused launch evaluated but did not latch (CollDev::write_force == 0), re-derived from the very positions it used
-template <bool OWN_FROM_RECORDS>
-__global__ void k_list_eval_cd(SwarmDev sw, CollDev cd) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= sw.n) return;
-  const size_t      np = (size_t)sw.npad;
-  const TypeParams& P  = sw.T[sw.F[i] >> FLAG_TYPE_SHIFT];
-  PosRecord         me;
-  if (OWN_FROM_RECORDS) {
-    const Pos4 pp = cd.p_in[i];
-    me.x = pp.x; me.y = pp.y; me.z = pp.z;
-  } else {
-    me.x = sw.S[(size_t)(F_X + 0) * np + i];
-    me.y = sw.S[(size_t)(F_X + 1) * np + i];
-    me.z = sw.S[(size_t)(F_X + 2) * np + i];
-  }
-  me.mass = P.mass; me.arm_length = P.arm_length; me.prop_radius = P.prop_radius;
-  double f[3];
-  bool   crashed;
-  const uint32_t cnt = cd.nbr_cnt[i];
-  double         ox, oy, oz, om, oa, op;
-  mrs_partner_flat(cd, cnt ? cd.nbr[i] : (uint32_t)i, ox, oy, oz, om, oa, op);
-  mrs_list_eval(cd, i, me.x, me.y, me.z, me.mass, me.arm_length, me.prop_radius, cnt, ox, oy, oz, om, oa, op, f, crashed);
-  sw.S[(size_t)(F_FEXT + 0) * np + i] = f[0];
-  sw.S[(size_t)(F_FEXT + 1) * np + i] = f[1];
-  sw.S[(size_t)(F_FEXT + 2) * np + i] = f[2];
-  if (crashed && !OWN_FROM_RECORDS) sw.F[i] |= FLAG_CRASHED;
-}
-
-// the stall words of all ranks (headers of the gathered export buffer) folded into this rank's control words: run at the end of a
-// batch of ticks, whose last launch nobody has looked behind yet
-// progress_tau != 0: also stands in for the fused launch of a rank that holds no UAVs (it reports progress and the warning word)
-__global__ void k_fold_stall(const Pos4* x_recv, int world, int block, Pos4* x_send, uint32_t* fctl, volatile uint32_t* hostw, uint32_t progress_tau) {
-  uint32_t* own   = (uint32_t*)x_send;  // the rank's own header words (MRS_HDR_*): what it knows, what its next collective carries
-  uint32_t  stall = own[MRS_HDR_STALL], warn = own[MRS_HDR_WARN], herr = 0u;
-  // (a communicator of ONE rank: the launches keep their words where a single GPU keeps them)
-  if (fctl[CTL_STALL] != 0u && (stall == 0u || fctl[CTL_STALL] < stall)) stall = fctl[CTL_STALL];
-  if (fctl[CTL_WARN] != 0u && (warn == 0u || fctl[CTL_WARN] < warn)) warn = fctl[CTL_WARN];
-  for (int q = 0; q < world; q++) {
-    const uint32_t* hq = (const uint32_t*)(x_recv + (size_t)q * (size_t)block);
-    const uint32_t  h = hq[MRS_HDR_STALL], wq = hq[MRS_HDR_WARN];
-    herr |= hq[MRS_HDR_ERROR];
-    if (h != 0u && (stall == 0u || h < stall)) stall = h;
-    if (wq != 0u && (warn == 0u || wq < warn)) warn = wq;
-  }
-  if ((herr & 3u) != 0u) fctl[CTL_ERROR] |= (herr & 3u) << 8;  // some rank's kernels reported an error: every rank's call fails
-  own[MRS_HDR_STALL] = stall;
-  own[MRS_HDR_WARN]  = warn;
-  __hip_atomic_store(&hostw[CTL_STALL], stall, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(&hostw[CTL_WARN], warn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(&hostw[CTL_STALL2], stall, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // (nothing else runs: both chains' mirrors agree)
-  __hip_atomic_store(&hostw[CTL_WARN2], warn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (progress_tau != 0u && (stall == 0u || progress_tau <= stall))
-    __hip_atomic_store(&hostw[CTL_PROGRESS], progress_tau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-}  // namespace
-
-// sizes of the export-set exchange for `world` ranks and `cap` export slots per rank; buffers zeroed (headers!)
-// zero == 0: the caller's next launch is the search's reset kernel, which zeroes the allocation itself (one launch less per search)
-extern "C" hipError_t mrs_collide_export_prepare(SwarmDev sw, CollideWork** work, int world, long long cap, int zero, hipStream_t st) {
-  if (!*work) *work = new CollideWork();
-  CollideWork* w = *work;
-  CK(ensure_fused(w, sw.n > 0 ? sw.n : 1, st));
-  if ((long long)sw.n > w->exp_slot_cap) {
-    CK(hipStreamSynchronize(st));
-    (void)hipFree(w->exp_slot);
-    CK(hipMalloc(&w->exp_slot, sizeof(uint32_t) * (size_t)(sw.n > 0 ? sw.n : 1)));
-    w->exp_slot_cap = sw.n;
-  }
-  const long long n_blocks = ((long long)(sw.n > 0 ? sw.n : 1) + 63) / 64;
-  if (n_blocks > w->blk_cap) {
-    CK(hipStreamSynchronize(st));
-    (void)hipFree(w->blk_class); (void)hipFree(w->blk_list); (void)hipFree(w->epoch);
-    CK(hipMalloc(&w->blk_class, sizeof(uint32_t) * (size_t)n_blocks));
-    CK(hipMalloc(&w->blk_list, sizeof(uint32_t) * (size_t)n_blocks));
-    CK(hipMalloc(&w->epoch, sizeof(uint32_t) * (size_t)n_blocks));
-    CK(hipMemsetAsync(w->blk_class, 0, sizeof(uint32_t) * (size_t)n_blocks, st));
-    CK(hipMemsetAsync(w->epoch, 0, sizeof(uint32_t) * (size_t)n_blocks, st));
-    w->blk_cap = n_blocks;
-  }
-  if (cap > w->x_cap || world != w->x_world) {
-    CK(hipStreamSynchronize(st));
-    (void)hipFree(w->x_send);  // (one allocation: send block, gathered blocks, partner constants — zeroed by one launch per search)
-    const size_t block = (size_t)cap + 1;
-    char* base = nullptr;
-    CK(hipMalloc(&base, sizeof(Pos4) * block * (size_t)(1 + 2 * world)));
-    w->x_send  = (Pos4*)base;
-    w->x_recv  = w->x_send + block;
-    w->x_const = (PartnerConst*)(w->x_recv + block * (size_t)world);
-    w->x_cap   = cap;
-    w->x_world = world;
-  }
-  const size_t block = (size_t)w->x_cap + 1;
-  static_assert(sizeof(Pos4) == sizeof(PartnerConst), "one stride for the three parts of the export allocation");
-  if (zero) CK(hipMemsetAsync(w->x_send, 0, sizeof(Pos4) * block * (size_t)(1 + 2 * world), st));
-  return hipSuccess;
-}
-
-// one wave that watches the 100 MHz wall clock for `microseconds` (mrs_debug_stream_delay: stands in for a collective's latency)
-namespace {
-__global__ void k_stream_delay(long long ticks) {
-  const long long t0 = wall_clock64();
-  unsigned        k  = 0;
-  while (wall_clock64() - t0 < ticks && k < 400000000u) k++;
-}
-}  // namespace
-namespace {
-// The collective of the measurement stand-in as ONE kernel that lasts `ticks` of the 100 MHz clock (one wave watches it — a real
-// collective keeps a few waves busy, not the chip): the rank's own block of `bytes` bytes is copied to the places
-// of ranks rank-1, rank, rank+1 of `recv`; when the blocks are 48-byte records (`kind` 1), absent ranks read as NaN records and the
-// two images are moved one slab width to either side.  Likewise the 64-byte entries of a halo exchange (kind 2; absent ranks: an
-// empty header) and the search box at the tail of a slot map (kind 3, `aux` = its first 16-byte vector; absent ranks: NaN bounds).
-__global__ void k_standin_gather(const uint4* send, uint4* recv, long long vec_per_rank, int rank, int world, int kind, long long aux, double width,
-                                 long long ticks) {
-  const long long t_start = wall_clock64();
-  const long long total = vec_per_rank * (long long)world;
-  for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < total; v += (long long)gridDim.x * blockDim.x) {
-    const int       q = (int)(v / vec_per_rank);
-    const long long j = v - (long long)q * vec_per_rank;
-    const int       d = q - rank;
-    if (d < -1 || d > 1) {
-      if (kind == 1 || (kind == 3 && j >= aux && j < aux + 3)) recv[v] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-      if (kind == 2 && j < 4) recv[v] = make_uint4(0u, 0u, 0u, 0u);
-      continue;
-    }
-    uint4 x = send[j];
-    // a 48-byte record = three 16-byte vectors, a halo entry four, the first holds x and y; a box = xmin ymin | zmin xmax | ymax zmax
-    const bool lo = d != 0 && ((kind == 1 && j % 3 == 0) || (kind == 2 && j % 4 == 0) || (kind == 3 && j == aux));
-    const bool hi = d != 0 && kind == 3 && j == aux + 1;
-    if (lo) {
-      double px = __builtin_bit_cast(double, make_uint2(x.x, x.y));
-      px += (double)d * width;
-      const uint2 b = __builtin_bit_cast(uint2, px);
-      x.x = b.x; x.y = b.y;
-    }
-    if (hi) {
-      double px = __builtin_bit_cast(double, make_uint2(x.z, x.w));
-      px += (double)d * width;
-      const uint2 b = __builtin_bit_cast(uint2, px);
-      x.z = b.x; x.w = b.y;
-    }
-    recv[v] = x;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < 64) {  // ONE wave keeps the kernel alive until the collective's latency is over
-    unsigned k = 0;
-    while (wall_clock64() - t_start < ticks && k < 400000000u) k++;
-  }
-}
-}  // namespace
-extern "C" hipError_t mrs_launch_standin_gather(const void* send, void* recv, size_t bytes, int rank, int world, double latency_us, int kind, long long aux,
-                                                double width, hipStream_t st) {
-  if (bytes % 16 != 0) return hipErrorInvalidValue;
-  const long long vec = (long long)(bytes / 16);
-  long long       blocks = (vec * world + 255) / 256;
-  if (blocks > 512) blocks = 512;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_standin_gather, dim3((unsigned)blocks), dim3(256), 0, st, (const uint4*)send, (uint4*)recv, vec, rank, world, kind, aux, width,
-                     (long long)(latency_us * 100.0));
-  return hipGetLastError();
-}
-// ---- peer-window all-gather: the exchange of a sharded swarm WITHOUT a collective library in the tick ----
-// Every rank owns a WINDOW in its own device memory (fine-grained, mapped into every peer: hipIpcOpenMemHandle across processes,
-// plain pointers inside one): [world flag lines of 64 B | pad to 4096 | 2 parities x world slots of slot_bytes].  One kernel per
-// rank and collective, no host in between.  A group of `bpp` blocks serves ONE peer q (the group of the own rank copies the own
-// block into the receive buffer and is done):
-//   1. push   — the group's shares of the rank's block go straight into slot [seq & 1][rank] of q's window (system-scope stores:
-//               one hop over xGMI);
-//   2. signal — every block fences its stores (system scope); the last block of the group (a ticket when bpp > 1) writes seq into
-//               flag[rank] of q's window;
-//   3. wait   — one lane polls flag[q] of the OWN window until q has signalled seq (bounded: 10 s, then the error word is set and
-//               the kernel ends — the call reports it), acquire;
-//   4. pull   — q's slot is copied from the own window into the receive buffer (system-scope loads: another device wrote the lines).
-// On exit the receive buffer holds what an all-gather would have put there, so the caller's kernels do not know the difference;
-// no block waits for another block of its own launch except through the ticket, which needs no residency (it is taken after the work).
-// Two parities suffice: a peer can only be one collective ahead (it cannot finish seq+1 without this rank's flag for seq+1, which
-// is written by this rank's kernel seq+1, i.e. after its kernel seq has ended), so what it writes while this rank still pulls seq
-// goes to the other parity.
-// Cost: one one-way latency + the copy, where a ring all-gather pays 2 (world - 1) hops behind a kernel launch of its own.
-namespace {
-typedef __attribute__((address_space(1))) unsigned long long peer_u64;
-typedef __attribute__((address_space(1))) unsigned           peer_u32;
-template <class U> struct PeerWord;
-template <> struct PeerWord<unsigned long long> { typedef peer_u64 G; };
-template <> struct PeerWord<unsigned>           { typedef peer_u32 G; };
-#define MRS_PEER_THREADS 512
-
-template <class U>
-__global__ __launch_bounds__(MRS_PEER_THREADS) void k_peer_allgather(MrsPeerWindows pw, const U* __restrict__ send, U* __restrict__ recv, long long units,
-                                                                     int rank, int bpp, unsigned seq, unsigned long long slot_bytes,
-                                                                     unsigned* tickets, unsigned ticket_target, unsigned* err_host, int world) {
-  typedef typename PeerWord<U>::G G;
-  const int       q = (int)blockIdx.x / bpp, j = (int)blockIdx.x - q * bpp;
-  const long long share = (units + bpp - 1) / bpp, lo = (long long)j * share, hi = lo + share < units ? lo + share : units;
-  if (q == rank) {
-    for (long long u = lo + threadIdx.x; u < hi; u += MRS_PEER_THREADS) recv[(long long)rank * units + u] = send[u];
-    return;
-  }
-  // 1. push
-  G* there = (G*)((char*)pw.win[q] + 4096ull + ((unsigned long long)(seq & 1u) * (unsigned)world + (unsigned)rank) * slot_bytes);
-  for (long long u = lo + threadIdx.x; u < hi; u += MRS_PEER_THREADS) __hip_atomic_store(there + u, send[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  // 2. signal
-  __threadfence_system();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    bool last = true;
-    if (bpp > 1) last = __hip_atomic_fetch_add((peer_u32*)(tickets + q), 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1u == ticket_target;
-    if (last) __hip_atomic_store((peer_u32*)((char*)pw.win[q] + 64 * rank), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    // 3. wait
-    const peer_u32* flag = (const peer_u32*)((const char*)pw.win[rank] + 64 * q);
-    const long long t0   = wall_clock64();
-    // (an exchange of this rank has given up before: the results are void already, the call will say so — what is still queued
-    //  must not wait its 10 s again, launch after launch)
-    //  (the mark is kept in device memory too — tickets[MRS_MAX_PEERS] —: the pinned host word is a PCIe round trip away)
-    const bool dead = __hip_atomic_load((peer_u32*)(tickets + MRS_MAX_PEERS), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-    while (!dead && (int)(__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - seq) < 0) {
-      if (wall_clock64() - t0 > MRS_WAIT_TICKS) {
-        // (pinned host words, plain stores — no PCIe atomic: [0] = set, [1] = the collective, [2] = the peer, [3] = what its flag said)
-        __hip_atomic_store((peer_u32*)err_host + 1, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store((peer_u32*)err_host + 2, (unsigned)q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store((peer_u32*)err_host + 3, __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store((peer_u32*)err_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store((peer_u32*)(tickets + MRS_MAX_PEERS), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(2);
-    }
-  }
-  __syncthreads();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-  // 4. pull
-  const G* here = (const G*)((const char*)pw.win[rank] + 4096ull + ((unsigned long long)(seq & 1u) * (unsigned)world + (unsigned)q) * slot_bytes);
-  for (long long u = lo + threadIdx.x; u < hi; u += MRS_PEER_THREADS)
-    recv[(long long)q * units + u] = __hip_atomic_load(here + u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-}  // namespace
-// `ticket_total`: tickets every peer's word has seen from all earlier launches of this rank (the caller adds the returned `bpp`)
-extern "C" hipError_t mrs_launch_peer_allgather(const MrsPeerWindows* pw, const void* send, void* recv, size_t bytes, int rank, int world, unsigned seq,
-                                                size_t slot_bytes, unsigned* tickets, unsigned ticket_total, unsigned* err_host, unsigned* bpp_out,
-                                                hipStream_t st) {
-  if (bytes == 0 || bytes % 4 != 0 || bytes > slot_bytes || world < 1 || world > MRS_MAX_PEERS) return hipErrorInvalidValue;
-  const bool      wide  = bytes % 8 == 0;
-  const long long units = (long long)(bytes / (wide ? 8 : 4));
-  long long       bpp   = ((long long)bytes + 131071) / 131072;  // one block per peer up to 128 KiB (the per-tick export blocks), then one per 128 KiB
-  if (bpp > 16) bpp = 16;
-  *bpp_out = bpp > 1 ? (unsigned)bpp : 0u;  // (a group of one block takes no ticket)
-  const dim3 grid((unsigned)(bpp * world)), block(MRS_PEER_THREADS);
-  if (wide)
-    hipLaunchKernelGGL(k_peer_allgather<unsigned long long>, grid, block, 0, st, *pw, (const unsigned long long*)send, (unsigned long long*)recv, units, rank,
-                       (int)bpp, seq, (unsigned long long)slot_bytes, tickets, ticket_total + (unsigned)bpp, err_host, world);
-  else
-    hipLaunchKernelGGL(k_peer_allgather<unsigned>, grid, block, 0, st, *pw, (const unsigned*)send, (unsigned*)recv, units, rank, (int)bpp, seq,
-                       (unsigned long long)slot_bytes, tickets, ticket_total + (unsigned)bpp, err_host, world);
-  return hipGetLastError();
-}
-extern "C" hipError_t mrs_launch_stream_delay(hipStream_t st, double microseconds) {
-  hipLaunchKernelGGL(k_stream_delay, dim3(1), dim3(64), 0, st, (long long)(microseconds * 100.0));
-  return hipGetLastError();
-}
-
-namespace {
-__global__ void k_heads_to_host(const uint32_t* maps, long long stride, int world, const uint32_t* fctl, volatile uint32_t* host, const HaloEntry* halo,
-                                unsigned hcap) {
-  const int q = threadIdx.x;
-  {  // the halo headers of a search that ran on a halo exchange: the largest number of entries any rank wanted to send, all flags
-    unsigned long long cnt = 0ull, fl = 0ull;
-    if (halo && q < world) {
-      const HaloEntry h = halo[(size_t)q * (size_t)(1u + hcap)];
-      cnt = h.j > 0xFFFFFFFFull ? 0xFFFFFFFFull : h.j;
-      fl  = h.pad;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long c2 = __shfl_xor(cnt, o), f2 = __shfl_xor(fl, o);
-      cnt = c2 > cnt ? c2 : cnt;
-      fl |= f2;
-    }
-    if (q == 0) {
-      __hip_atomic_store(&host[2 * world + 2], (uint32_t)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(&host[2 * world + 3], (uint32_t)fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
-  if (q < world) {
-    __hip_atomic_store(&host[2 * q], maps[(size_t)q * (size_t)stride], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(&host[2 * q + 1], maps[(size_t)q * (size_t)stride + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  if (q == 0) {
-    __hip_atomic_store(&host[2 * world], fctl[CTL_NBND], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(&host[2 * world + 1], fctl[CTL_NL1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-}  // namespace
-// what the host needs of a search — every rank's export count and overflow counter, this rank's boundary-block count — in pinned host
-// memory after ONE small launch (two device-to-host copies cost a search 30 us); valid after the stream has been synchronised
-// halo != 0: the search ran on a halo exchange; words [2 world + 2] = most entries wanted by a rank, [2 world + 3] = the flags of all ranks
-extern "C" hipError_t mrs_collide_heads_to_host(CollideWork* w, const uint32_t* maps, long long stride, int world, int halo, const uint32_t** out, hipStream_t st) {
-  if (!w || world > 64) return hipErrorInvalidValue;
-  if (!w->host_heads) CK(hipHostMalloc(&w->host_heads, sizeof(uint32_t) * 160, hipHostMallocMapped | hipHostMallocCoherent));
-  hipLaunchKernelGGL(k_heads_to_host, dim3(1), dim3(64), 0, st, maps, stride, world, w->fctl, w->host_heads, halo ? w->h_recv : nullptr, (unsigned)w->h_cap);
-  *out = w->host_heads;
-  return hipGetLastError();
-}
-
-extern "C" const uint32_t* mrs_collide_host_heads(const CollideWork* w) { return w ? w->host_heads : nullptr; }
-// a search has replaced the lists: launch indices restart at 1, the pinned mirrors of the control words start from nothing
-extern "C" void mrs_collide_host_words_reset(CollideWork* w) {
-  if (!w || !w->hostw) return;
-  w->hostw[CTL_STALL] = w->hostw[CTL_PROGRESS] = w->hostw[CTL_WARN] = w->hostw[CTL_STALL2] = w->hostw[CTL_WARN2] = 0u;
-}
-extern "C" long long mrs_collide_export_capacity(const CollideWork* w) { return w ? w->x_cap : 0; }
-extern "C" const uint32_t* mrs_collide_ctl_words(const CollideWork* w) { return w ? w->fctl : nullptr; }
-extern "C" void*     mrs_collide_export_send(const CollideWork* w) { return w ? (void*)w->x_send : nullptr; }
-extern "C" void*     mrs_collide_export_recv(const CollideWork* w) { return w ? (void*)w->x_recv : nullptr; }
-
-// after a search over gathered records: mark the export set, write this rank's slot map (2 + n_max words) for the all-gather
-// pred_hdt >= 0: also the displacement bound over that time on the state the search found (k_export_mark)
-extern "C" hipError_t mrs_collide_export_mark(SwarmDev sw, CollideWork* w, long long n_max, long long map_words, int rank, uint32_t* map_send, double pred_hdt,
-                                              double rebounce, hipStream_t st) {
-  // (the host mirrors of the control words are reset by the host once it has read what the old segment left in them: mrs_collide_host_words_reset)
-  const long long n_xvec = (long long)(sizeof(Pos4) * ((size_t)w->x_cap + 1) * (size_t)(1 + 2 * w->x_world) / sizeof(uint4));
-  long long       grid   = (map_words + 255) / 256;
-  if (grid < 64) grid = 64;
-  hipLaunchKernelGGL(k_search_reset, dim3((unsigned)grid), dim3(256), 0, st, w->fctl, map_send, map_words, w->blk_class, (sw.n + 63) / 64, (uint4*)w->x_send, n_xvec);
-  if (sw.n > 0) {
-    const int n_blocks = (sw.n + 63) / 64;
-    (void)n_blocks;
-    hipLaunchKernelGGL(k_export_mark, dim3((sw.n + 255) / 256), dim3(256), 0, st, sw, w->P[w->pcur], n_max, rank, w->nbr, w->nbr_cnt, w->exp_slot, map_send,
-                       w->fctl, w->blk_class, pred_hdt, 0.5 * SKIN2 * (1.0 - 1e-9), rebounce);
-    hipLaunchKernelGGL(k_class_list, dim3((sw.n + 255) / 256), dim3(256), 0, st, sw.n, n_max, rank, w->nbr, w->nbr_cnt, w->blk_class, w->blk_list, w->fctl,
-                       map_send, w->ctl ? w->ctl : w->fctl);
-  } else {
-    hipLaunchKernelGGL(k_export_header, dim3(1), dim3(1), 0, st, map_send, w->fctl, w->ctl ? w->ctl : w->fctl);  // (never searched: word 6 of fctl is 0)
-  }
-  return hipGetLastError();
-}
-
-// after the all-gather of the slot maps (and with buffers of sufficient capacity): rewrite the lists, seed the gathered export buffer
-extern "C" hipError_t mrs_collide_export_translate(SwarmDev sw, CollideWork* w, long long n_max, long long map_stride, int rank, const uint32_t* maps,
-                                                   const PosRecord* rec_all, hipStream_t st) {
-  if (sw.n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_export_translate, dim3((sw.n + 255) / 256), dim3(256), 0, st, sw.n, n_max, rank, map_stride, (int)(w->x_cap + 1), w->nbr, w->nbr_cnt,
-                     maps, rec_all, w->x_recv, w->x_const, w->fctl);
-  return hipGetLastError();
-}
-
-// CollDev of a sharded fused launch (export-set exchange); rec_own = this rank's records as of the search (gathered buffer + offset)
-extern "C" hipError_t mrs_collide_export_dev(const SwarmDev* sw, CollideWork* w, long long my_offset, unsigned tau, int eval, int crash, double rebounce,
-                                             CollDev* cd) {
-  if (!w || !w->fctl || !w->P[0] || !w->x_send || !w->g_rec_build) return hipErrorInvalidValue;
-  memset(cd, 0, sizeof *cd);
-  cd->nbr      = w->nbr;
-  cd->nbr_cnt  = w->nbr_cnt;
-  cd->rec      = w->g_rec_build + my_offset;
-  cd->p_in     = w->P[w->pcur];
-  cd->p_out    = w->P[(w->pcur + 1) % 3];
-  cd->ctl      = w->fctl;
-  cd->hostw    = w->hostw;
-  cd->g_pos    = w->x_recv;
-  cd->g_const  = w->x_const;
-  cd->send     = w->x_send;
-  cd->exp_slot = w->exp_slot;
-  cd->rebounce = rebounce;
-  cd->lim2     = (0.5 * SKIN2) * (0.5 * SKIN2) * (1.0 - 1e-9);
-  cd->lim2_warn = cd->lim2 * (WARN_FRACTION * WARN_FRACTION);  // the warning travels in the collective's headers (tick_sharded.hip: export_ticks)
-  cd->tau      = tau;
-  cd->n        = sw->n;
-  cd->eval     = eval;
-  cd->crash    = crash;
-  cd->world    = w->x_world;
-  cd->block    = (int)(w->x_cap + 1);
-  cd->part      = MRS_PART_FULL;
-  cd->blk_class = w->blk_class;
-  cd->blk_list  = w->blk_list;
-  cd->epoch     = w->epoch;
-  cd->pred_lim  = 0.5 * SKIN2 * (1.0 - 1e-9);
-  cd->pred_hdt  = -1.0;  // (nothing announced unless the caller says so: mrs_collide_export_part)
-  return hipSuccess;
-}
-
-// the part of a split tick this launch is (MRS_PART_*) and the step of the displacement bound
-// announce: the protocol runs split ticks (on any rank), so "may leave its skin within MRS_PRED_HORIZON steps" has to be reported ahead
-extern "C" void mrs_collide_export_part(CollDev* cd, int part, unsigned n_bnd, double dt, int announce) {
-  cd->part          = part;
-  cd->n_bnd         = n_bnd;
-  cd->pred_hdt      = announce ? (double)MRS_PRED_HORIZON * dt : -1.0;
-}
-
-// a run of split ticks starts behind launch `tau` (everything before it has completed in stream order)
-extern "C" hipError_t mrs_collide_handoff_init(CollideWork* w, int n, unsigned tau, hipStream_t st) {
-  if (!w || !w->epoch) return hipErrorInvalidValue;
-  const int n_blocks = (n + 63) / 64;
-  hipLaunchKernelGGL(k_handoff_init, dim3((n_blocks + 255) / 256), dim3(256), 0, st, w->fctl, w->epoch, n_blocks, tau);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t mrs_collide_export_eval(SwarmDev sw, CollDev cd, hipStream_t st) {
-  if (sw.n <= 0) return hipSuccess;
-  cd.crash = mode_word(sw, cd.crash);
-  hipLaunchKernelGGL(k_list_eval_cd<false>, dim3((sw.n + 255) / 256), dim3(256), 0, st, sw, cd);
-  return hipGetLastError();
-}
-
-// the force of the collision tick a fused launch evaluated without latching it: same lists, same position records (index `pin`)
-extern "C" hipError_t mrs_collide_latch_force(SwarmDev sw, CollideWork* w, int pin, int crash, double rebounce, hipStream_t st) {
-  if (sw.n <= 0 || !w || !w->P[0]) return hipSuccess;
-  CollDev cd;
-  memset(&cd, 0, sizeof cd);
-  cd.nbr = w->nbr; cd.nbr_cnt = w->nbr_cnt; cd.rec = w->rec_build; cd.p_in = w->P[pin % 3];
-  cd.rebounce = rebounce; cd.n = sw.n; cd.eval = 1; cd.crash = mode_word(sw, crash); cd.world = 1;
-  hipLaunchKernelGGL(k_list_eval_cd<true>, dim3((sw.n + 255) / 256), dim3(256), 0, st, sw, cd);
-  return hipGetLastError();
-}
 extern "C" int mrs_collide_fused_pin(const CollideWork* w) { return w ? w->pcur : 0; }
-
-extern "C" hipError_t mrs_collide_export_fold_stall(CollideWork* w, unsigned progress_tau, hipStream_t st) {
-  hipLaunchKernelGGL(k_fold_stall, dim3(1), dim3(1), 0, st, w->x_recv, w->x_world, (int)(w->x_cap + 1), w->x_send, w->fctl, w->hostw, progress_tau);
-  return hipGetLastError();
-}
 
 // control words of the fused machinery (synchronises the stream)
 extern "C" hipError_t mrs_collide_fused_words(const CollideWork* w, hipStream_t st, unsigned* out8) {
@@ -2200,8 +1539,4 @@ extern "C" hipError_t mrs_collide_fused_words(const CollideWork* w, hipStream_t 
   if (!w || !w->fctl) return hipSuccess;
   CK(hipMemcpyAsync(out8, w->fctl, CTL_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, st));
   return hipStreamSynchronize(st);
-}
-
-extern "C" void mrs_collide_invalidate_gathered(CollideWork* w) {
-  if (w) w->g_lists_live = false;
 }

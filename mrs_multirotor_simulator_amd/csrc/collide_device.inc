@@ -1,10 +1,10 @@
-// collide_device.inc — device functions shared by collide.hip (searches, standalone list evaluation) and step_device.inc (the
+// collide_device.inc — device functions shared by collide.hip (searches), collide_export.hip (standalone list evaluation) and step_device.inc (the
 // collision evaluation fused into the step kernels): the literal predicate and force expression of
 // MultirotorSimulator::handleCollisions, src/multirotor_simulator.cpp:321-358.
 // Contraction is switched off inside these functions and the FAST force expression is spelled out in explicit fma / rsq / rcp
 // operations, so every translation unit evaluates a flavour with the same operations: a tick gives the same bits whichever
 // kernel happens to evaluate it (a fused step launch, the stand-alone pass, mrs_collide_latch_force).  The flavour follows the
-// SWARM: the step kernels know it at compile time (MRS_FAST), collide.hip gets it at run time in bit 1 of the `crash` mode word
+// SWARM: the step kernels know it at compile time (MRS_FAST), collide*.hip get it at run time in bit 1 of the `crash` mode word
 // (MRS_MODE_FAST, set at its extern "C" boundary from SwarmDev::fast) — a FAST swarm's stand-alone passes use the FAST expression too,
 // so get_external_force reports the force the step consumed and a run does not depend on which path evaluated which tick.
 #pragma once
@@ -76,7 +76,7 @@ CDEV bool mrs_pos_usable(double x, double y, double z) {
 // Thrust over the horizon: every motor's low-pass moves its speed towards an input within [min_rpm, max_rpm], so a speed stays below
 // max(its value now, max_rpm) and, the thrust column being non-negative, allocation * rpm^2 <= (thrust now) + sum_m alloc[3][m] max_rpm^2
 // — also for motor speeds the host SET beyond max_rpm (a non-finite thrust makes the bound non-finite: "may leave").
-// Used by the step kernels' epilogue (every launch, h = MRS_PRED_HORIZON) and by the search (collide.hip k_export_mark: the ticks right
+// Used by the step kernels' epilogue (every launch, h = MRS_PRED_HORIZON) and by the search (collide_export.hip k_export_mark: the ticks right
 // after a search need no serial phase when nobody can leave within the horizon).
 CDEV bool mrs_may_leave(const double y[18], double dd, double thrust_now, uint32_t listed, double rebounce, double hdt, double lim, double pa0, double pthr,
                         double pdrag, int ground_enabled, double ground_z, bool takeoff, double init_z) {

@@ -7,8 +7,8 @@
 //   nearest.hip           C ABI + kernels of the k-nearest-neighbour observations for device-resident callers
 //   snapshot.hip          C ABI + kernels of the state snapshots (save / indexed load of whole per-UAV records) for device-resident callers
 //   transport_rccl.hip    RCCL bound at run time (dlopen)
-//   transport_local.hip   in-process loopback group, caller-supplied all-gather, measurement stand-in
-//   transport_peer.hip    peer-window exchange (direct writes into the peers' device memory)
+//   transport_local.hip   in-process loopback group, caller-supplied all-gather, measurement stand-in (with its kernels)
+//   transport_peer.hip    peer-window exchange (direct writes into the peers' device memory; with its kernel)
 // sharded_protocol.h holds the pure decision functions of the sharded protocol (tested without a GPU: tests/cpp/sharded_protocol_test.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -36,7 +36,7 @@
 #define M_PI 3.14159265358979323846
 #endif
 
-// ---- launchers exported by the kernel units (step_kernel_*.hip, collide.hip, outputs.hip) ----
+// ---- step_kernel_literal.hip / step_kernel_fast.hip ----
 extern "C" hipError_t mrs_launch_step_literal(SwarmDev sw, double dt, int substeps, int cascade, int blk0, int nblk, int with_mixed, hipStream_t st);
 extern "C" hipError_t mrs_launch_step_fast(SwarmDev sw, double dt, int substeps, int cascade, int blk0, int nblk, int with_mixed, hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_literal(SwarmDev sw, RolloutDev r, double dt, int n_steps, int variant, hipStream_t st);
@@ -65,47 +65,26 @@ extern "C" hipError_t mrs_launch_pid_update_probe_literal(const double*, double*
 extern "C" hipError_t mrs_launch_pid_update_probe_fast(const double*, double*, const double*, const double*, double*, int, hipStream_t);
 extern "C" hipError_t mrs_launch_component_probe_literal(SwarmDev, int, int, int, const double*, int, double*, int, double, hipStream_t);
 extern "C" hipError_t mrs_launch_component_probe_fast(SwarmDev, int, int, int, const double*, int, double*, int, double, hipStream_t);
-// collide.hip
+extern "C" hipError_t mrs_launch_step_coll_literal(SwarmDev sw, CollDev cd, double dt, int variant, int grid_blocks, hipStream_t st);
+extern "C" hipError_t mrs_launch_step_coll_fast(SwarmDev sw, CollDev cd, double dt, int variant, int grid_blocks, hipStream_t st);
+// ---- collide.hip: searches, neighbour lists, the halo exchange of a search, bookkeeping of the fused evaluation ----
+struct CollideWork;
+extern "C" void       mrs_collide_free(CollideWork* w);
 extern "C" hipError_t mrs_launch_flags_update(uint32_t* F, int first, int count, uint32_t and_mask, uint32_t or_mask, hipStream_t st);
 extern "C" hipError_t mrs_launch_pack_positions(SwarmDev sw, PosRecord* out, hipStream_t st);
-struct CollideWork;
+extern "C" void       mrs_collide_step_hook(const CollideWork* w, const PosRecord** rec, uint32_t** flag, double* lim2);
 extern "C" hipError_t mrs_collide_run(SwarmDev sw, CollideWork** work, const PosRecord* rec, long long n_total, long long my_offset,
                                       int crash, double rebounce, int rec_is_local_scratch, hipStream_t st);
 extern "C" hipError_t mrs_collide_run_lists(SwarmDev sw, CollideWork** work, int crash, double rebounce, int force_rebuild, unsigned guard_tau,
                                             hipStream_t st);
 extern "C" hipError_t mrs_collide_run_lists_gathered(SwarmDev sw, CollideWork** work, const PosRecord* rec, long long n_total, long long my_offset,
                                                      int crash, double rebounce, int force_rebuild, hipStream_t st);
-extern "C" hipError_t mrs_collide_export_prepare(SwarmDev sw, CollideWork** work, int world, long long cap, int zero, hipStream_t st);
-extern "C" long long  mrs_collide_export_capacity(const CollideWork* w);
-extern "C" const uint32_t* mrs_collide_host_heads(const CollideWork* w);
-extern "C" void       mrs_collide_host_words_reset(CollideWork* w);
-extern "C" void*      mrs_collide_export_send(const CollideWork* w);
-extern "C" void*      mrs_collide_export_recv(const CollideWork* w);
-extern "C" hipError_t mrs_collide_export_mark(SwarmDev sw, CollideWork* w, long long n_max, long long map_words, int rank, uint32_t* map_send, double pred_hdt,
-                                              double rebounce, hipStream_t st);
-extern "C" hipError_t mrs_collide_export_translate(SwarmDev sw, CollideWork* w, long long n_max, long long map_stride, int rank, const uint32_t* maps,
-                                                   const PosRecord* rec_all, hipStream_t st);
-extern "C" hipError_t mrs_collide_export_dev(const SwarmDev* sw, CollideWork* w, long long my_offset, unsigned tau, int eval, int crash, double rebounce,
-                                             CollDev* cd);
-extern "C" hipError_t mrs_collide_export_eval(SwarmDev sw, CollDev cd, hipStream_t st);
-extern "C" hipError_t mrs_collide_export_fold_stall(CollideWork* w, unsigned progress_tau, hipStream_t st);
-extern "C" hipError_t mrs_collide_fused_words(const CollideWork* w, hipStream_t st, unsigned* out8);
 extern "C" void       mrs_collide_invalidate_gathered(CollideWork* w);
-extern "C" void mrs_collide_step_hook(const CollideWork* w, const PosRecord** rec, uint32_t** flag, double* lim2);
 extern "C" void       mrs_collide_list_geometry(int* list_cap, double* list_radius);
 extern "C" hipError_t mrs_collide_copy_lists(const CollideWork* w, long long n, uint32_t* count, uint32_t* nbr, int rows, hipStream_t st);
 extern "C" hipError_t mrs_collide_rebuilds(const CollideWork* w, hipStream_t st, unsigned* out);
 extern "C" hipError_t mrs_collide_debug_words(const CollideWork* w, hipStream_t st, unsigned* out8);
-extern "C" void mrs_collide_free(CollideWork* w);
-extern "C" hipError_t mrs_launch_step_coll_literal(SwarmDev sw, CollDev cd, double dt, int variant, int grid_blocks, hipStream_t st);
-extern "C" hipError_t mrs_launch_step_coll_fast(SwarmDev sw, CollDev cd, double dt, int variant, int grid_blocks, hipStream_t st);
-extern "C" void       mrs_collide_export_part(CollDev* cd, int part, unsigned n_bnd, double dt, int announce);
-extern "C" hipError_t mrs_collide_handoff_init(CollideWork* w, int n, unsigned tau, hipStream_t st);
-extern "C" const uint32_t* mrs_collide_ctl_words(const CollideWork* w);
-extern "C" hipError_t mrs_collide_heads_to_host(CollideWork* w, const uint32_t* maps, long long stride, int world, int halo, const uint32_t** out, hipStream_t st);
-// halo exchange of a search tick (collide.hip)
 extern "C" hipError_t mrs_collide_halo_prepare(CollideWork** work, int world, long long cap, hipStream_t st);
-extern "C" long long  mrs_collide_halo_capacity(const CollideWork* w);
 extern "C" void*      mrs_collide_halo_send(const CollideWork* w);
 extern "C" void*      mrs_collide_halo_recv(const CollideWork* w);
 extern "C" int        mrs_collide_halo_ready(const CollideWork* w, long long n_total);
@@ -115,23 +94,36 @@ extern "C" void       mrs_collide_set_box_out(CollideWork** work, double* box_ou
 extern "C" hipError_t mrs_collide_run_lists_halo(SwarmDev sw, CollideWork** work, PosRecord* table, long long n_total, long long n_max, int rank, int world,
                                                  int crash, double rebounce, hipStream_t st);
 extern "C" hipError_t mrs_collide_fused_dev(const SwarmDev* sw, CollideWork* w, unsigned tau, int eval, int crash, double rebounce, CollDev* cd);
-extern "C" void mrs_collide_fused_advance(CollideWork* w);
-extern "C" const volatile unsigned* mrs_collide_host_words(const CollideWork* w);
-extern "C" hipError_t mrs_collide_fused_reset(CollideWork* w, hipStream_t st);
-extern "C" hipError_t mrs_collide_latch_force(SwarmDev sw, CollideWork* w, int pin, int crash, double rebounce, hipStream_t st);
+extern "C" void       mrs_collide_fused_advance(CollideWork* w);
 extern "C" int        mrs_collide_fused_pin(const CollideWork* w);
-// outputs.hip
+extern "C" hipError_t mrs_collide_fused_reset(CollideWork* w, hipStream_t st);
+extern "C" hipError_t mrs_collide_fused_words(const CollideWork* w, hipStream_t st, unsigned* out8);
+extern "C" const volatile unsigned* mrs_collide_host_words(const CollideWork* w);
+// ---- collide_export.hip: the export-set exchange of sharded swarms ----
+extern "C" hipError_t mrs_collide_export_prepare(SwarmDev sw, CollideWork** work, int world, long long cap, int zero, hipStream_t st);
+extern "C" long long  mrs_collide_export_capacity(const CollideWork* w);
+extern "C" void*      mrs_collide_export_send(const CollideWork* w);
+extern "C" void*      mrs_collide_export_recv(const CollideWork* w);
+extern "C" hipError_t mrs_collide_export_mark(SwarmDev sw, CollideWork* w, long long n_max, long long map_words, int rank, uint32_t* map_send, double pred_hdt,
+                                              double rebounce, hipStream_t st);
+extern "C" hipError_t mrs_collide_export_translate(SwarmDev sw, CollideWork* w, long long n_max, long long map_stride, int rank, const uint32_t* maps,
+                                                   const PosRecord* rec_all, hipStream_t st);
+extern "C" hipError_t mrs_collide_heads_to_host(CollideWork* w, const uint32_t* maps, long long stride, int world, int halo, const uint32_t** out, hipStream_t st);
+extern "C" const uint32_t* mrs_collide_host_heads(const CollideWork* w);
+extern "C" void       mrs_collide_host_words_reset(CollideWork* w);
+extern "C" hipError_t mrs_collide_export_dev(const SwarmDev* sw, CollideWork* w, long long my_offset, unsigned tau, int eval, int crash, double rebounce,
+                                             CollDev* cd);
+extern "C" void       mrs_collide_export_part(CollDev* cd, int part, unsigned n_bnd, double dt, int announce);
+extern "C" hipError_t mrs_collide_handoff_init(CollideWork* w, int n, unsigned tau, hipStream_t st);
+extern "C" hipError_t mrs_collide_export_eval(SwarmDev sw, CollDev cd, hipStream_t st);
+extern "C" hipError_t mrs_collide_export_fold_stall(CollideWork* w, unsigned progress_tau, hipStream_t st);
+extern "C" hipError_t mrs_collide_latch_force(SwarmDev sw, CollideWork* w, int pin, int crash, double rebounce, hipStream_t st);
+// ---- outputs.hip ----
 extern "C" hipError_t mrs_launch_timeout_input(SwarmDev sw, int first, int count, hipStream_t st);
 extern "C" hipError_t mrs_launch_unpack_rows(SwarmDev sw, const double* rows, int stride, int width, int base, int first, int count, hipStream_t st);
 extern "C" hipError_t mrs_launch_pack_outputs(SwarmDev sw, int first, int count, mrs_uav_output_t* dev_out, hipStream_t st);
 extern "C" hipError_t mrs_launch_pack_poses(SwarmDev sw, int first, int count, mrs_uav_pose_t* dev_out, hipStream_t st);
 extern "C" hipError_t mrs_launch_pack_states(SwarmDev sw, int first, int count, mrs_uav_state_t* dev_out, hipStream_t st);
-extern "C" hipError_t mrs_launch_peer_allgather(const MrsPeerWindows* pw, const void* send, void* recv, size_t bytes, int rank, int world, unsigned seq,
-                                                size_t slot_bytes, unsigned* tickets, unsigned ticket_total, unsigned* err_host, unsigned* bpp_out,
-                                                hipStream_t st);
-extern "C" hipError_t mrs_launch_standin_gather(const void* send, void* recv, size_t bytes, int rank, int world, double latency_us, int kind, long long aux, double width,
-                                                hipStream_t st);
-extern "C" hipError_t mrs_launch_stream_delay(hipStream_t st, double microseconds);
 
 namespace mrs_host {
 int fail(int code, const std::string& msg);  // remembers msg for mrs_last_error() (thread-local), returns code
@@ -213,7 +205,7 @@ struct mrs_swarm {
   // are images of itself one slab width away, and every collective costs a fixed latency
   bool   comm_standin = false;
   double standin_delay_us = 0.0, standin_width = 0.0, standin_gbps = 0.0;  // gbps > 0: bytes of a collective / that rate on top of the latency
-  // peer-window exchange (mrs_swarm_peer_window_create / mrs_swarm_comm_init_peer; collide.hip k_peer_allgather): ranks write their
+  // peer-window exchange (mrs_swarm_peer_window_create / mrs_swarm_comm_init_peer; transport_peer.hip k_peer_allgather): ranks write their
   // blocks straight into each other's device memory, one kernel per collective on the swarm's stream, no collective library
   bool               comm_peer = false;
   void*              peer_window = nullptr;       // this rank's window (fine-grained device memory)

@@ -250,7 +250,7 @@ struct PosRecord {
   double mass, arm_length, prop_radius;
 };
 
-// ---- fused step + collision evaluation (step_device.inc *_coll kernels; buffers owned by collide.hip) ----
+// ---- fused step + collision evaluation (step_device.inc *_coll kernels; buffers owned by CollideWork, collide_work.h) ----
 // A collision tick between two neighbour searches is evaluated by the NEXT step kernel: its prologue reads the positions of
 // the listed partners as they were after the previous step, forms the force / crash flag handleCollisions would have
 // latched (src/multirotor_simulator.cpp:321-358) and the step consumes it from registers.  Positions are double-buffered in
@@ -298,7 +298,7 @@ enum {
 #define MRS_BLK_BOUNDARY 1u  // some UAV of the block lists a foreign UAV: the block is stepped by the boundary launch
 #define MRS_BLK_LAYER1   2u  // interior block, some UAV of it lists a UAV of a boundary block: waits for that block's epoch word
 #define MRS_PRED_HORIZON 4u  // steps by which "may leave its skin" is announced ahead (why 4: DESIGN §5)
-// peer-window exchange (collide.hip k_peer_allgather): the windows of all ranks as this process addresses them
+// peer-window exchange (transport_peer.hip k_peer_allgather): the windows of all ranks as this process addresses them
 #define MRS_MAX_PEERS 64
 struct MrsPeerWindows {
   void* win[MRS_MAX_PEERS];

@@ -2,6 +2,7 @@
 // process, one host thread each: virtual shards on one device — what the tests use on the one-GPU box — or several devices of a
 // node without RCCL), a caller-supplied all-gather, and the measurement stand-in (ONE rank of `world` alone on a device).
 #include "host_internal.h"
+#include "collide_device.inc"  // wall_clock64
 
 // ---- in-process collective: `world` swarms of one process, one host thread each -------------------------------------------------
 struct mrs_loopback_group {
@@ -39,6 +40,73 @@ struct mrs_loopback_group {
     }
   }
 };
+
+// ---- kernels of the measurement stand-in ------------------------------------------------------------------------------------------
+// one wave that watches the 100 MHz wall clock for `microseconds` (mrs_debug_stream_delay: stands in for a collective's latency)
+namespace {
+__global__ void k_stream_delay(long long ticks) {
+  const long long t0 = wall_clock64();
+  unsigned        k  = 0;
+  while (wall_clock64() - t0 < ticks && k < 400000000u) k++;
+}
+
+// The collective of the measurement stand-in as ONE kernel that lasts `ticks` of the 100 MHz clock (one wave watches it — a real
+// collective keeps a few waves busy, not the chip): the rank's own block of `bytes` bytes is copied to the places
+// of ranks rank-1, rank, rank+1 of `recv`; when the blocks are 48-byte records (`kind` 1), absent ranks read as NaN records and the
+// two images are moved one slab width to either side.  Likewise the 64-byte entries of a halo exchange (kind 2; absent ranks: an
+// empty header) and the search box at the tail of a slot map (kind 3, `aux` = its first 16-byte vector; absent ranks: NaN bounds).
+__global__ void k_standin_gather(const uint4* send, uint4* recv, long long vec_per_rank, int rank, int world, int kind, long long aux, double width,
+                                 long long ticks) {
+  const long long t_start = wall_clock64();
+  const long long total = vec_per_rank * (long long)world;
+  for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < total; v += (long long)gridDim.x * blockDim.x) {
+    const int       q = (int)(v / vec_per_rank);
+    const long long j = v - (long long)q * vec_per_rank;
+    const int       d = q - rank;
+    if (d < -1 || d > 1) {
+      if (kind == 1 || (kind == 3 && j >= aux && j < aux + 3)) recv[v] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+      if (kind == 2 && j < 4) recv[v] = make_uint4(0u, 0u, 0u, 0u);
+      continue;
+    }
+    uint4 x = send[j];
+    // a 48-byte record = three 16-byte vectors, a halo entry four, the first holds x and y; a box = xmin ymin | zmin xmax | ymax zmax
+    const bool lo = d != 0 && ((kind == 1 && j % 3 == 0) || (kind == 2 && j % 4 == 0) || (kind == 3 && j == aux));
+    const bool hi = d != 0 && kind == 3 && j == aux + 1;
+    if (lo) {
+      double px = __builtin_bit_cast(double, make_uint2(x.x, x.y));
+      px += (double)d * width;
+      const uint2 b = __builtin_bit_cast(uint2, px);
+      x.x = b.x; x.y = b.y;
+    }
+    if (hi) {
+      double px = __builtin_bit_cast(double, make_uint2(x.z, x.w));
+      px += (double)d * width;
+      const uint2 b = __builtin_bit_cast(uint2, px);
+      x.z = b.x; x.w = b.y;
+    }
+    recv[v] = x;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 64) {  // ONE wave keeps the kernel alive until the collective's latency is over
+    unsigned k = 0;
+    while (wall_clock64() - t_start < ticks && k < 400000000u) k++;
+  }
+}
+}  // namespace
+static hipError_t launch_standin_gather(const void* send, void* recv, size_t bytes, int rank, int world, double latency_us, int kind, long long aux, double width,
+                                        hipStream_t st) {
+  if (bytes % 16 != 0) return hipErrorInvalidValue;
+  const long long vec = (long long)(bytes / 16);
+  long long       blocks = (vec * world + 255) / 256;
+  if (blocks > 512) blocks = 512;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_standin_gather, dim3((unsigned)blocks), dim3(256), 0, st, (const uint4*)send, (uint4*)recv, vec, rank, world, kind, aux, width,
+                     (long long)(latency_us * 100.0));
+  return hipGetLastError();
+}
+static hipError_t launch_stream_delay(hipStream_t st, double microseconds) {
+  hipLaunchKernelGGL(k_stream_delay, dim3(1), dim3(64), 0, st, (long long)(microseconds * 100.0));
+  return hipGetLastError();
+}
 
 namespace mrs_host {
 // all-gather among the swarms of a loopback group: every rank copies every rank's send buffer into its own receive buffer, device
@@ -131,7 +199,7 @@ int standin_allgather(mrs_swarm* s, const void* send, void* recv, size_t bytes) 
   // at that many GB/s — on top of the fixed latency; without it the 42 MB of a search tick's record gather cost as much as 54 KB
   const double gbps    = s->standin_gbps;  // (read when the stand-in communicator is bound)
   const double wire_us = gbps > 0.0 ? (double)bytes * (double)(s->comm_world - 1) / (gbps * 1e3) : 0.0;
-  HIPCHK(mrs_launch_standin_gather(send, recv, bytes, s->comm_rank, s->comm_world, s->standin_delay_us + wire_us, kind, aux, s->standin_width, s->cstream));
+  HIPCHK(launch_standin_gather(send, recv, bytes, s->comm_rank, s->comm_world, s->standin_delay_us + wire_us, kind, aux, s->standin_width, s->cstream));
   return MRS_OK;
 }
 }  // namespace mrs_host
@@ -227,7 +295,7 @@ int mrs_swarm_comm_init_loopback(mrs_swarm_t* s, mrs_loopback_group_t* g, int32_
 
 int mrs_debug_stream_delay(void* stream, double microseconds) {
   if (!(microseconds >= 0) || microseconds > 1e6) return fail(MRS_ERR_ARG, "bad delay");
-  HIPCHK(mrs_launch_stream_delay((hipStream_t)stream, microseconds));
+  HIPCHK(launch_stream_delay((hipStream_t)stream, microseconds));
   return MRS_OK;
 }
 

@@ -37,7 +37,7 @@ def check_lists(M, pos, what):
     g.construct(0, n, helpers.to_product_params(M, helpers.oracle_params("x500")), pos, np.zeros(n))
     count, nbr, cap, radius = g.debug_neighbour_lists()
     assert cap == 24 and nbr.shape == (24, n)
-    r2 = radius * radius * (1.0 + 1e-9) + 1e-5  # collide.hip LIST_R2
+    r2 = radius * radius * (1.0 + 1e-9) + 1e-5  # collide_work.h LIST_R2
     want = brute_lists(pos, r2)
     longest = max(len(w) for w in want)
     assert longest <= cap, f"{what}: the scenario overflows the lists ({longest} neighbours)"

@@ -1,4 +1,4 @@
-"""The peer-window exchange (include/mrs_swarm.h: mrs_swarm_peer_window_create / mrs_swarm_comm_init_peer; csrc/collide.hip
+"""The peer-window exchange (include/mrs_swarm.h: mrs_swarm_peer_window_create / mrs_swarm_comm_init_peer; csrc/transport_peer.hip
 k_peer_allgather): the collectives of the sharded tick as direct device-to-device writes with device-side signalling, no collective
 library and no host in the tick.  Ranks in SEPARATE processes on the one GPU of the test box — the form a multi-GPU node runs, one
 xGMI hop shorter: separate address spaces and HIP contexts, windows mapped with hipIpcOpenMemHandle, the 64-byte handles the only

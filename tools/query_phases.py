@@ -1,19 +1,14 @@
 #!/usr/bin/env python3
 """Per-phase durations inside k_query (collide.hip) from in-kernel timestamps: builds a -DMRS_QUERY_CLOCK library in /tmp whose
 query writes the A/B/C phase durations (10-ns ticks of the constant clock) into the force columns.  Timing aid only."""
-import os, subprocess, sys
+import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mrs_multirotor_simulator_amd", "csrc"); OBJ = os.path.join(ROOT, "mrs_multirotor_simulator_amd", "build")
 sys.path.insert(0, ROOT)
-subprocess.check_call([sys.executable, "-m", "mrs_multirotor_simulator_amd.build"], cwd=ROOT, stdout=subprocess.DEVNULL)
+from mrs_multirotor_simulator_amd import build
 os.makedirs("/tmp/qph", exist_ok=True)
-o = "/tmp/qph/collide.o"
-subprocess.check_call(["hipcc", "-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-ffp-contract=off", "-DMRS_QUERY_CLOCK=" + os.environ.get("QPH_CLOCK", "1")] + sys.argv[2:] + ["-c",
-                       os.path.join(CSRC, "collide.hip"), "-o", o])
-lib = "/tmp/qph/libmrs_swarm_clock.so"
-subprocess.check_call(["hipcc", "-shared", "-fPIC", "--offload-arch=gfx950", "-o", lib, o] + [os.path.join(OBJ, f) for f in
-                      ("step_kernel_literal.o", "step_kernel_fast.o", "outputs.o", "host_api.o", "tick_single.o", "tick_sharded.o", "transport_rccl.o", "transport_local.o", "transport_peer.o")])
+lib = build.build_library(out="/tmp/qph/libmrs_swarm_clock.so",
+                          extra_flags={"collide.hip": ["-DMRS_QUERY_CLOCK=" + os.environ.get("QPH_CLOCK", "1")] + sys.argv[2:]})
 os.environ["MRS_SWARM_LIB"] = lib
 if os.environ.get("QPH_LISTS", "0") == "1":
     sys.exit("the list-building query has its own stamps: tools/search_phases.py (this tool times the plain search-every-tick query)")

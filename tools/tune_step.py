@@ -8,8 +8,6 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mrs_multirotor_simulator_amd", "csrc")
-OBJ = os.path.join(ROOT, "mrs_multirotor_simulator_amd", "build")
 
 VARIANTS = {
     "default": "",
@@ -42,7 +40,6 @@ def main():
     args = ap.parse_args()
     sys.path.insert(0, ROOT)
     from mrs_multirotor_simulator_amd import build
-    build.build_library()
     out_dir = "/tmp/mrs_variants"
     os.makedirs(out_dir, exist_ok=True)
     for name in args.variants.split(","):
@@ -50,15 +47,8 @@ def main():
             _, la, sa = name.split("_")
             VARIANTS[name] = f"-DMRS_LD_AUX={la} -DMRS_ST_AUX={sa}"
         flags = (VARIANTS[name] + " " + args.extra).split()
-        objs = []
-        for v, c in (("literal", "off"), ("fast", "fast")):
-            o = os.path.join(out_dir, f"{name}_{v}.o")
-            subprocess.check_call(["hipcc", "-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", f"-ffp-contract={c}",
-                                   "-fno-fast-math"] + flags + ["-c", os.path.join(CSRC, f"step_kernel_{v}.hip"), "-o", o])
-            objs.append(o)
-        lib = os.path.join(out_dir, f"libmrs_{name}.so")
-        subprocess.check_call(["hipcc", "-shared", "-fPIC", "--offload-arch=gfx950", "-o", lib] + objs +
-                              [os.path.join(OBJ, "collide.o"), os.path.join(OBJ, "outputs.o"), *[os.path.join(OBJ, o) for o in ("host_api.o", "tick_single.o", "tick_sharded.o", "transport_rccl.o", "transport_local.o", "transport_peer.o")]])
+        lib = build.build_library(out=os.path.join(out_dir, f"libmrs_{name}.so"),
+                                  extra_flags={"step_kernel_literal.hip": flags, "step_kernel_fast.hip": flags})
         for arith in args.arith.split(","):
             env = dict(os.environ, MRS_SWARM_LIB=lib)
             r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--warmup", "50",

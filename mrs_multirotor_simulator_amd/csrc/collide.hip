@@ -1048,26 +1048,15 @@ static int query_lpu(long long n_own) {
 
 }  // namespace
 
-// Gives every buffer back.  ensure_tables also does this when the tables grow, so what is no buffer survives: the tables' size and turn
-// (cap_n, cap_T, cur — set anew by that caller), fcur, pcur, g_export_form, h_world, x_world, and g_box_out, which points into the
-// caller's slot-map block (mrs_collide_set_box_out).  A new field of CollideWork that is no buffer and has to survive goes into `keep`.
+// Gives every buffer back when the tables grow (ensure_tables): all of them are sized by the swarm the tables were made for.  Every
+// other field keeps its value; ensure_tables resets the ones that described the buffers.
+template <class... B> static void reset_all(B&... b) { (b.reset(), ...); }
 static void free_work(CollideWork* w) {
-  void* const dev[] = {w->head[0], w->head[1], w->next, w->rec_build, w->nbr, w->nbr_cnt, w->ctl, w->g_rec_build, w->g_bbox, w->h_send, w->h_ctl,
-                       w->h_part, w->exp_slot, w->x_send, w->blk_class, w->blk_list, w->epoch, w->P[0], w->P[1], w->P[2], w->fctl};
-  for (void* p : dev) (void)hipFree(p);  // (h_recv lives in h_send's allocation, x_recv and x_const in x_send's)
-  if (w->hostw) (void)hipHostFree(w->hostw);
-  if (w->host_heads) (void)hipHostFree(w->host_heads);
-  CollideWork keep;
-  keep.cap_n = w->cap_n; keep.cap_T = w->cap_T; keep.cur = w->cur; keep.fcur = w->fcur; keep.pcur = w->pcur;
-  keep.g_export_form = w->g_export_form; keep.h_world = w->h_world; keep.x_world = w->x_world; keep.g_box_out = w->g_box_out;
-  *w = keep;
+  reset_all(w->head[0], w->head[1], w->next, w->rec_build, w->nbr, w->nbr_cnt, w->ctl, w->g_rec_build, w->g_bbox, w->h_send, w->h_ctl, w->h_part,
+            w->exp_slot, w->x_send, w->blk_class, w->blk_list, w->epoch, w->P[0], w->P[1], w->P[2], w->fctl, w->hostw, w->host_heads);
 }
 
-extern "C" void mrs_collide_free(CollideWork* w) {
-  if (!w) return;
-  free_work(w);
-  delete w;
-}
+extern "C" void mrs_collide_free(CollideWork* w) { delete w; }
 
 extern "C" hipError_t mrs_launch_flags_update(uint32_t* F, int first, int count, uint32_t and_mask, uint32_t or_mask, hipStream_t st) {
   hipLaunchKernelGGL(k_flags_update, dim3((count + 255) / 256), dim3(256), 0, st, F, first, count, and_mask, or_mask);
@@ -1101,9 +1090,13 @@ static hipError_t ensure_tables(CollideWork* w, long long n_total, hipStream_t s
   if (n_total > w->cap_n || T > w->cap_T) {
     CK(hipStreamSynchronize(st));
     free_work(w);
-    CK(hipMalloc(&w->head[0], sizeof(uint2) * ((size_t)T + 1)));  // (+1: k_query2 reads two entries at a time, the spare one stays empty)
-    CK(hipMalloc(&w->head[1], sizeof(uint2) * ((size_t)T + 1)));
-    CK(hipMalloc(&w->next, sizeof(uint2) * (size_t)n_total));
+    w->cap_n = 0, w->cap_T = 0;  // (until the new tables exist: a failed allocation below leaves no size that describes a missing buffer)
+    w->lists_live = w->g_lists_live = false;
+    w->h_cap = w->x_cap = 0;
+    w->h_recv = nullptr, w->x_recv = nullptr, w->x_const = nullptr;
+    CK(w->head[0].alloc((size_t)T + 1));  // (+1: k_query2 reads two entries at a time, the spare one stays empty)
+    CK(w->head[1].alloc((size_t)T + 1));
+    CK(w->next.alloc((size_t)n_total));
     CK(hipMemsetAsync(w->head[0], 0, sizeof(uint2) * ((size_t)T + 1), st));  // afterwards every query wipes the table of the next tick
     CK(hipMemsetAsync(w->head[1], 0, sizeof(uint2) * ((size_t)T + 1), st));
     w->cap_n = n_total;
@@ -1115,32 +1108,28 @@ static hipError_t ensure_tables(CollideWork* w, long long n_total, hipStream_t s
 
 // buffers of the fused step + collision evaluation for n local UAVs (collide_export.hip sizes them too)
 hipError_t ensure_fused(CollideWork* w, long long n, hipStream_t st) {
-  if (!w->fctl) {
-    CK(hipMalloc(&w->fctl, sizeof(uint32_t) * CTL_WORDS));
+  if (!w->fctl || !w->hostw) {
+    CK(w->fctl.alloc(CTL_WORDS));
     CK(hipMemsetAsync(w->fctl, 0, sizeof(uint32_t) * CTL_WORDS, st));
-    CK(hipHostMalloc(&w->hostw, sizeof(uint32_t) * CTL_WORDS, hipHostMallocMapped | hipHostMallocCoherent));
+    CK(w->hostw.alloc(CTL_WORDS, hipHostMallocMapped | hipHostMallocCoherent));
     for (int k = 0; k < CTL_WORDS; k++) w->hostw[k] = 0u;
   }
-  if (n > w->p_cap) {
+  if ((size_t)n > w->P[2].capacity()) {  // (the last of the three to be allocated)
     CK(hipStreamSynchronize(st));
-    (void)hipFree(w->P[0]); (void)hipFree(w->P[1]); (void)hipFree(w->P[2]);
-    CK(hipMalloc(&w->P[0], sizeof(Pos4) * (size_t)n));
-    CK(hipMalloc(&w->P[1], sizeof(Pos4) * (size_t)n));
-    CK(hipMalloc(&w->P[2], sizeof(Pos4) * (size_t)n));
-    w->p_cap = n;
-    w->pcur  = 0;
+    for (auto& p : w->P) CK(p.alloc((size_t)n));
+    w->pcur = 0;
   }
   return hipSuccess;
 }
 
 // the neighbour lists of cap_n UAVs and the control words of the list ticks, allocated with the first list tick after the tables
 static hipError_t ensure_lists(CollideWork* w, hipStream_t st) {
-  if (w->nbr) return hipSuccess;
-  CK(hipMalloc(&w->nbr, sizeof(uint32_t) * (size_t)LIST_CAP * (size_t)w->cap_n));
-  CK(hipMalloc(&w->nbr_cnt, sizeof(uint32_t) * (size_t)w->cap_n));
+  if (w->ctl) return hipSuccess;  // (the last of the three to be allocated)
+  CK(w->nbr.alloc((size_t)LIST_CAP * (size_t)w->cap_n));
+  CK(w->nbr_cnt.alloc((size_t)w->cap_n));
   CK(hipMemsetAsync(w->nbr, 0, sizeof(uint32_t) * (size_t)LIST_CAP * (size_t)w->cap_n, st));  // rows beyond a UAV's count are read (not used)
   CK(hipMemsetAsync(w->nbr_cnt, 0, sizeof(uint32_t) * (size_t)w->cap_n, st));
-  CK(hipMalloc(&w->ctl, sizeof(uint32_t) * 8));  // [0..1] skin flags, [2] rebuild counter, [4..5] "head table t holds entries"
+  CK(w->ctl.alloc(8));  // [0..1] skin flags, [2] rebuild counter, [4..5] "head table t holds entries"
   w->fcur = 0;
   return hipMemsetAsync(w->ctl, 0, sizeof(uint32_t) * 8, st);
 }
@@ -1216,7 +1205,7 @@ extern "C" hipError_t mrs_collide_run_lists(SwarmDev sw, CollideWork** work, int
   const long long n = sw.n;
   crash = mode_word(sw, crash);
   CK(ensure_tables(w, n, st));
-  if (!w->rec_build) CK(hipMalloc(&w->rec_build, sizeof(PosRecord) * (size_t)w->cap_n));
+  CK(w->rec_build.reserve((size_t)w->cap_n));
   CK(ensure_lists(w, st));
   CK(ensure_fused(w, w->cap_n, st));
   if (!w->lists_live) {  // first list tick, or plain-search ticks came in between: start from empty tables and flags
@@ -1247,19 +1236,17 @@ extern "C" hipError_t mrs_collide_run_lists_gathered(SwarmDev sw, CollideWork** 
   crash = mode_word(sw, crash);
   CK(ensure_tables(w, n_total, st));
   CK(ensure_lists(w, st));
-  if (n_total > w->g_cap) {
+  if ((size_t)n_total > w->g_rec_build.capacity()) {
     CK(hipStreamSynchronize(st));
-    (void)hipFree(w->g_rec_build);
-    CK(hipMalloc(&w->g_rec_build, sizeof(PosRecord) * (size_t)n_total));
-    w->g_cap        = n_total;
     w->g_lists_live = false;
+    CK(w->g_rec_build.reserve((size_t)n_total));
   }
   const bool export_form = force_rebuild != 0;  // (the export-set exchange searches on its own decision, and only then comes here)
   if (!w->g_lists_live || w->g_export_form != export_form) {
     // first gathered search, or other modes came in between: empty tables and flags, rebuild.  Consecutive searches of the export-set
     // exchange skip this: the two head tables keep wiping each other, and nobody compares against the foreign part of the record copy.
     CK(empty_tables(w, st));
-    if (!export_form) CK(hipMemsetAsync(w->g_rec_build, 0xFF, sizeof(PosRecord) * (size_t)w->g_cap, st));  // NaN records
+    if (!export_form) CK(hipMemsetAsync(w->g_rec_build, 0xFF, sizeof(PosRecord) * w->g_rec_build.capacity(), st));  // NaN records
     w->g_lists_live = false;
   }
   const int      force = (w->g_lists_live && !force_rebuild) ? 0 : 1;
@@ -1271,7 +1258,7 @@ extern "C" hipError_t mrs_collide_run_lists_gathered(SwarmDev sw, CollideWork** 
   const unsigned gN = (unsigned)((n_total + 255) / 256);
   const int      ib = index_bits(n_total);
   const double   lim2 = skin_lim2(SKIN2);
-  if (!w->g_bbox) CK(hipMalloc(&w->g_bbox, sizeof(double) * 6 * (BBOX_BLOCKS + 1)));  // the box, then the partial boxes
+  CK(w->g_bbox.reserve(6 * (BBOX_BLOCKS + 1)));  // the box, then the partial boxes
   if (force) {
     // (the search is decided: the comparison of all records with those of the last search would only cost time — 14 us at 1 M records;
     //  its other job, clearing the flag word the query may raise, is done by k_own_bbox_final)
@@ -1414,21 +1401,18 @@ extern "C" hipError_t mrs_collide_halo_prepare(CollideWork** work, int world, lo
   CollideWork* w = *work;
   if (cap < 1 || world < 1) return hipErrorInvalidValue;
   const long long need = (cap + 1) * (long long)(1 + world);
-  if (need > w->h_alloc) {
+  if ((size_t)need > w->h_send.capacity()) {
     CK(hipStreamSynchronize(st));
-    (void)hipFree(w->h_send);
-    w->h_send = nullptr;
-    w->h_alloc = 0;
-    const long long alloc = need + need / 4;
-    CK(hipMalloc(&w->h_send, sizeof(HaloEntry) * (size_t)alloc));
-    CK(hipMemsetAsync(w->h_send, 0, sizeof(HaloEntry) * (size_t)alloc, st));
-    w->h_alloc = alloc;
+    w->h_cap = 0, w->h_recv = nullptr;
+    const size_t alloc = (size_t)(need + need / 4);
+    CK(w->h_send.reserve(alloc));
+    CK(hipMemsetAsync(w->h_send, 0, sizeof(HaloEntry) * alloc, st));
   }
   w->h_recv  = w->h_send + (cap + 1);  // (a collective writes every block whole: what another capacity left behind is overwritten)
   w->h_cap   = cap;
   w->h_world = world;
   if (!w->h_ctl) {
-    CK(hipMalloc(&w->h_ctl, sizeof(uint32_t) * 4));
+    CK(w->h_ctl.alloc(4));
     CK(hipMemsetAsync(w->h_ctl, 0, sizeof(uint32_t) * 4, st));
   }
   return hipSuccess;
@@ -1444,14 +1428,8 @@ extern "C" hipError_t mrs_collide_halo_select(SwarmDev sw, CollideWork* w, PosRe
   if (!w || !w->h_send) return hipErrorInvalidValue;
   const double    margin = SKIN2, widening = SQRT3_UP + SKIN2 + 1e-6;  // (the widening of k_own_bbox_final)
   const long long blocks = sw.n > 0 ? (sw.n + 255) / 256 : 1;
-  if (blocks > w->h_part_cap) {
-    CK(hipStreamSynchronize(st));
-    (void)hipFree(w->h_part);
-    w->h_part = nullptr;
-    w->h_part_cap = 0;
-    CK(hipMalloc(&w->h_part, sizeof(double) * 6 * (size_t)blocks));
-    w->h_part_cap = blocks;
-  }
+  if (6 * (size_t)blocks > w->h_part.capacity()) CK(hipStreamSynchronize(st));
+  CK(w->h_part.reserve(6 * (size_t)blocks));
   hipLaunchKernelGGL(k_halo_select, dim3((unsigned)blocks), dim3(256), 0, st, sw, table + (size_t)rank * (size_t)n_max, maps, stride, boxw, world, rank, margin,
                      margin - widening - 1e-9, w->h_send, (unsigned)w->h_cap, w->h_ctl, w->h_part);
   hipLaunchKernelGGL(k_halo_header, dim3(1), dim3(1), 0, st, w->h_send, w->h_ctl, not_ready ? MRS_HALO_MOVED : 0u);
@@ -1463,7 +1441,7 @@ extern "C" void mrs_collide_set_box_out(CollideWork** work, double* box_out) {
   (*work)->g_box_out = box_out;
 }
 extern "C" int mrs_collide_halo_ready(const CollideWork* w, long long n_total) {
-  return w && w->nbr && w->g_rec_build && n_total <= w->g_cap && w->g_lists_live && w->g_export_form && w->g_bbox ? 1 : 0;
+  return w && w->nbr && w->g_rec_build && (size_t)n_total <= w->g_rec_build.capacity() && w->g_lists_live && w->g_export_form && w->g_bbox ? 1 : 0;
 }
 // the next gathered tick starts from empty tables and searches (the lists are of another exchange's form, or incomplete)
 extern "C" void mrs_collide_invalidate_gathered(CollideWork* w) {

@@ -214,30 +214,21 @@ extern "C" hipError_t mrs_collide_export_prepare(SwarmDev sw, CollideWork** work
   if (!*work) *work = new CollideWork();
   CollideWork* w = *work;
   CK(ensure_fused(w, sw.n > 0 ? sw.n : 1, st));
-  if ((long long)sw.n > w->exp_slot_cap) {
+  const size_t n_own = sw.n > 0 ? (size_t)sw.n : 0;
+  if (n_own > w->exp_slot.capacity()) CK(hipStreamSynchronize(st));
+  CK(w->exp_slot.reserve(n_own));
+  const size_t n_blocks = ((n_own ? n_own : 1) + 63) / 64;
+  if (n_blocks > w->epoch.capacity()) {  // (the last of the three to be allocated)
     CK(hipStreamSynchronize(st));
-    (void)hipFree(w->exp_slot);
-    CK(hipMalloc(&w->exp_slot, sizeof(uint32_t) * (size_t)(sw.n > 0 ? sw.n : 1)));
-    w->exp_slot_cap = sw.n;
-  }
-  const long long n_blocks = ((long long)(sw.n > 0 ? sw.n : 1) + 63) / 64;
-  if (n_blocks > w->blk_cap) {
-    CK(hipStreamSynchronize(st));
-    (void)hipFree(w->blk_class); (void)hipFree(w->blk_list); (void)hipFree(w->epoch);
-    CK(hipMalloc(&w->blk_class, sizeof(uint32_t) * (size_t)n_blocks));
-    CK(hipMalloc(&w->blk_list, sizeof(uint32_t) * (size_t)n_blocks));
-    CK(hipMalloc(&w->epoch, sizeof(uint32_t) * (size_t)n_blocks));
-    CK(hipMemsetAsync(w->blk_class, 0, sizeof(uint32_t) * (size_t)n_blocks, st));
-    CK(hipMemsetAsync(w->epoch, 0, sizeof(uint32_t) * (size_t)n_blocks, st));
-    w->blk_cap = n_blocks;
+    for (auto* b : {&w->blk_class, &w->blk_list, &w->epoch}) CK(b->alloc(n_blocks));
+    CK(hipMemsetAsync(w->blk_class, 0, sizeof(uint32_t) * n_blocks, st));
+    CK(hipMemsetAsync(w->epoch, 0, sizeof(uint32_t) * n_blocks, st));
   }
   if (cap > w->x_cap || world != w->x_world) {
     CK(hipStreamSynchronize(st));
-    (void)hipFree(w->x_send);  // (one allocation: send block, gathered blocks, partner constants — zeroed by one launch per search)
+    w->x_cap = 0, w->x_recv = nullptr, w->x_const = nullptr;
     const size_t block = (size_t)cap + 1;
-    char* base = nullptr;
-    CK(hipMalloc(&base, sizeof(Pos4) * block * (size_t)(1 + 2 * world)));
-    w->x_send  = (Pos4*)base;
+    CK(w->x_send.alloc(block * (size_t)(1 + 2 * world)));  // (one allocation: send block, gathered blocks, partner constants — zeroed by one launch per search)
     w->x_recv  = w->x_send + block;
     w->x_const = (PartnerConst*)(w->x_recv + block * (size_t)world);
     w->x_cap   = cap;
@@ -285,7 +276,7 @@ __global__ void k_heads_to_host(const uint32_t* maps, long long stride, int worl
 // halo != 0: the search ran on a halo exchange; words [2 world + 2] = most entries wanted by a rank, [2 world + 3] = the flags of all ranks
 extern "C" hipError_t mrs_collide_heads_to_host(CollideWork* w, const uint32_t* maps, long long stride, int world, int halo, const uint32_t** out, hipStream_t st) {
   if (!w || world > 64) return hipErrorInvalidValue;
-  if (!w->host_heads) CK(hipHostMalloc(&w->host_heads, sizeof(uint32_t) * 160, hipHostMallocMapped | hipHostMallocCoherent));
+  CK(w->host_heads.reserve(160, hipHostMallocMapped | hipHostMallocCoherent));
   hipLaunchKernelGGL(k_heads_to_host, dim3(1), dim3(64), 0, st, maps, stride, world, w->fctl, w->host_heads, halo ? w->h_recv : nullptr, (unsigned)w->h_cap);
   *out = w->host_heads;
   return hipGetLastError();
@@ -309,7 +300,7 @@ extern "C" hipError_t mrs_collide_export_mark(SwarmDev sw, CollideWork* w, long 
   const long long n_xvec = (long long)(sizeof(Pos4) * ((size_t)w->x_cap + 1) * (size_t)(1 + 2 * w->x_world) / sizeof(uint4));
   long long       grid   = (map_words + 255) / 256;
   if (grid < 64) grid = 64;
-  hipLaunchKernelGGL(k_search_reset, dim3((unsigned)grid), dim3(256), 0, st, w->fctl, map_send, map_words, w->blk_class, (sw.n + 63) / 64, (uint4*)w->x_send, n_xvec);
+  hipLaunchKernelGGL(k_search_reset, dim3((unsigned)grid), dim3(256), 0, st, w->fctl, map_send, map_words, w->blk_class, (sw.n + 63) / 64, (uint4*)w->x_send.get(), n_xvec);
   if (sw.n > 0) {
     hipLaunchKernelGGL(k_export_mark, dim3((sw.n + 255) / 256), dim3(256), 0, st, sw, w->P[w->pcur], n_max, rank, w->nbr, w->nbr_cnt, w->exp_slot, map_send,
                        w->fctl, w->blk_class, pred_hdt, skin_pred_lim(SKIN2), rebounce);

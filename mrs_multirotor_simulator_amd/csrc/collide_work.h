@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "hip_owned.h"
 #include "swarm_layout.h"
 #include "collide_device.inc"
 
@@ -41,48 +42,45 @@ constexpr double skin_lim2(double skin) { return (0.5 * skin) * (0.5 * skin) * (
 // ... and the limit of the displacement bound that announces it ahead (mrs_may_leave, collide_device.inc)
 constexpr double skin_pred_lim(double skin) { return 0.5 * skin * (1.0 - 1e-9); }
 
+// Every buffer is an owner (hip_owned.h) that knows its own size; the capacities kept beside them say how the buffers are laid out
+// (cap_n / cap_T: UAVs and slots of the hash tables; h_cap / x_cap: entries per block of the halo and export allocations).
 struct CollideWork {
   long long cap_n = 0;
   uint32_t  cap_T = 0;
   int       cur   = 0;  // which head table the next tick fills; the other one is being wiped by that tick's query
-  uint2 *   head[2] = {nullptr, nullptr}, *next = nullptr;
+  DevBuf<uint2> head[2], next;
   // neighbour lists (single-GPU ticks)
-  PosRecord* rec_build = nullptr;  // records of the last rebuild: reference positions of the skin test + airframe constants
-  uint32_t * nbr = nullptr, *nbr_cnt = nullptr, *ctl = nullptr;
+  DevBuf<PosRecord> rec_build;     // records of the last rebuild: reference positions of the skin test + airframe constants
+  DevBuf<uint32_t>  nbr, nbr_cnt, ctl;
   int        fcur = 0;             // which of ctl[0..1] the next tick reads
   bool       lists_live = false;   // rec_build / nbr describe this swarm as of some earlier tick
-  double*    g_bbox = nullptr;       // gathered mode: this rank's bounding box widened by the list radius (6 doubles)
-  PosRecord* g_rec_build = nullptr;  // gathered mode: all records as of this rank's last rebuild
-  long long  g_cap = 0;
+  DevBuf<double>    g_bbox;          // gathered mode: this rank's bounding box widened by the list radius (6 doubles)
+  DevBuf<PosRecord> g_rec_build;     // gathered mode: all records as of this rank's last rebuild
   bool       g_lists_live = false;
   // halo exchange of a search tick (mrs_collide_halo_*): instead of every rank's ALL records, the records that can be within the list
   // radius of another rank's UAVs travel — [header | entries] of 64 B, the header's `j` = count, `pad` = flags
-  HaloEntry* h_send = nullptr;   // [1 + h_cap]
+  DevBuf<HaloEntry> h_send;      // [1 + h_cap], then h_recv (one allocation for all blocks together, headers included)
   HaloEntry* h_recv = nullptr;   // [world][1 + h_cap]
-  long long  h_cap = 0, h_alloc = 0;  // entries per block in use; entries allocated (all blocks together, headers included)
+  long long  h_cap = 0;          // entries per block in use
   int        h_world = 0;
-  uint32_t*  h_ctl = nullptr;    // [0] entries appended, [1] flags (MRS_HALO_*)
-  double*    g_box_out = nullptr;  // where a search of the export-set exchange also leaves its box (mrs_collide_set_box_out)
-  double*    h_part = nullptr;     // partial boxes of k_halo_select, one per block
-  long long  h_part_cap = 0;
+  DevBuf<uint32_t> h_ctl;        // [0] entries appended, [1] flags (MRS_HALO_*)
+  double*    g_box_out = nullptr;  // where a search of the export-set exchange also leaves its box (mrs_collide_set_box_out): borrowed
+  DevBuf<double> h_part;           // partial boxes of k_halo_select, 6 doubles per block
   bool       g_export_form = false;  // the last gathered search was one of the export-set exchange: lists end up in slot form, and of
                                      // the record copy only this rank's own range (the skin references) is kept
   // fused step + collision evaluation (step_device.inc *_coll): double-buffered positions, control words, pinned host mirror
   // (three buffers: in a split sharded tick the interior launch of tick t+1 writes its output while the boundary launch of tick t
   //  still reads its input — with two buffers those would be the same array)
-  Pos4*     P[3]  = {nullptr, nullptr, nullptr};
+  DevBuf<Pos4> P[3];
   int       pcur  = 0;        // P[pcur] holds the positions after the most recent step (when the host says they are valid)
-  long long p_cap = 0;
-  uint32_t* fctl  = nullptr;  // CTL_WORDS device words
-  uint32_t* hostw = nullptr;  // CTL_WORDS pinned host words (stall, progress mirrored by the kernels)
+  DevBuf<uint32_t>    fctl;   // CTL_WORDS device words
+  PinnedBuf<uint32_t> hostw;  // CTL_WORDS pinned host words (stall, progress mirrored by the kernels)
   // export-set exchange (multi-GPU ticks between searches): own UAVs listed by another rank, their slots in the padded collective
-  uint32_t*     exp_slot = nullptr;   // [n_local]
-  long long     exp_slot_cap = 0;
+  DevBuf<uint32_t> exp_slot;          // [n_local]
   // split sharded ticks: class of every 64-UAV block, list of the boundary blocks, epoch word per block (swarm_layout.h)
-  uint32_t *    blk_class = nullptr, *blk_list = nullptr, *epoch = nullptr;
-  uint32_t*     host_heads = nullptr;  // pinned: heads of the slot maps + boundary-block count of the last search
-  long long     blk_cap = 0;
-  Pos4*         x_send = nullptr;     // [1 + x_cap]: header + exported positions of this rank
+  DevBuf<uint32_t>    blk_class, blk_list, epoch;
+  PinnedBuf<uint32_t> host_heads;     // heads of the slot maps + boundary-block count of the last search
+  DevBuf<Pos4>  x_send;               // [1 + x_cap]: header + exported positions of this rank, then x_recv and x_const (one allocation)
   Pos4*         x_recv = nullptr;     // [world][1 + x_cap]
   PartnerConst* x_const = nullptr;    // [world][1 + x_cap]
   long long     x_cap = 0;            // export slots per rank in the collective

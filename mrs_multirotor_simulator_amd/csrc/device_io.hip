@@ -183,8 +183,8 @@ size_t rows_bytes(int count, int stride, int width, int dtype) {
 // the stream fence of every call: the swarm's stream waits for what the caller queued on `ext` so far ...
 int fence_in(mrs_swarm* s, hipStream_t ext) {
   if (ext == s->stream) return MRS_OK;
-  if (!s->ev_dio_in) HIPCHK(hipEventCreateWithFlags(&s->ev_dio_in, hipEventDisableTiming));
-  if (!s->ev_dio_out) HIPCHK(hipEventCreateWithFlags(&s->ev_dio_out, hipEventDisableTiming));
+  HIPCHK(s->ev_dio_in.create(hipEventDisableTiming));
+  HIPCHK(s->ev_dio_out.create(hipEventDisableTiming));
   HIPCHK(hipEventRecord(s->ev_dio_in, ext));
   HIPCHK(hipStreamWaitEvent(s->stream, s->ev_dio_in, 0));
   return MRS_OK;

@@ -250,8 +250,8 @@ int upload_blocks(mrs_swarm* s) {
     if (t == 0xFFFFu) s->mixed_blocks.push_back(b);
   }
   HIPCHK(hipStreamSynchronize(s->stream));
-  if (!s->dBT) HIPCHK(hipMalloc(&s->dBT, sizeof(uint32_t) * (size_t)nb));
-  if (!s->dMB) HIPCHK(hipMalloc(&s->dMB, sizeof(int32_t) * (size_t)nb));
+  HIPCHK(s->dBT.reserve((size_t)nb));
+  HIPCHK(s->dMB.reserve((size_t)nb));
   HIPCHK(hipMemcpyAsync(s->dBT, s->block_type.data(), sizeof(uint32_t) * (size_t)nb, hipMemcpyHostToDevice, s->stream));
   if (!s->mixed_blocks.empty())
     HIPCHK(hipMemcpyAsync(s->dMB, s->mixed_blocks.data(), sizeof(int32_t) * s->mixed_blocks.size(), hipMemcpyHostToDevice, s->stream));
@@ -275,14 +275,11 @@ int upload_types(mrs_swarm* s, double dt) {
     s->table_dt = dt;
   }
   const int need = (int)s->tparams.size();
-  if (need > s->dT_cap) {
-    // the old table may still be read by launches in flight on the stream
-    HIPCHK(hipStreamSynchronize(s->stream));
-    if (s->dT) HIPCHK(hipFree(s->dT));
-    int cap = 16;
-    while (cap < need) cap *= 2;
-    HIPCHK(hipMalloc(&s->dT, sizeof(TypeParams) * (size_t)cap));
-    s->dT_cap = cap;
+  if ((size_t)need > s->dT.capacity()) {
+    HIPCHK(hipStreamSynchronize(s->stream));  // the old table may still be read by launches in flight on the stream
+    size_t cap = 16;
+    while (cap < (size_t)need) cap *= 2;
+    HIPCHK(s->dT.reserve(cap));
   }
   HIPCHK(hipMemcpyAsync(s->dT, s->tparams.data(), sizeof(TypeParams) * (size_t)need, hipMemcpyHostToDevice, s->stream));
   HIPCHK(hipStreamSynchronize(s->stream));  // tparams (pageable) may change right after we return
@@ -458,7 +455,7 @@ int mrs_swarm_create(int32_t n_uavs, int32_t device_id, mrs_swarm_t** out) {
   if (device_id >= ndev) return fail(MRS_ERR_ARG, "device_id out of range");
   HIPCHK(hipSetDevice(device_id));
   mrs_swarm* s = new mrs_swarm();
-  // any failure below hands the half-built object (streams, events, device buffers) back through mrs_swarm_destroy
+  // any failure below hands the half-built object back through mrs_swarm_destroy (which waits for its streams before it deletes it)
   struct Guard {
     mrs_swarm* p;
     ~Guard() {
@@ -470,7 +467,7 @@ int mrs_swarm_create(int32_t n_uavs, int32_t device_id, mrs_swarm_t** out) {
   if (const char* e = getenv("MRS_NEIGHBOUR_LISTS")) s->use_lists = atoi(e) != 0;
   if (s->npad == 0) s->npad = 64;
   s->device = device_id;
-  HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  HIPCHK(s->stream.create(hipStreamNonBlocking));
   {
     // The runtime maps streams onto a handful of hardware queues (GPU_MAX_HW_QUEUES, 4 by default) round-robin; once other
     // libraries in the process (torch, RCCL) have created theirs, two default-priority streams of ours can end up on the same
@@ -478,12 +475,12 @@ int mrs_swarm_create(int32_t n_uavs, int32_t device_id, mrs_swarm_t** out) {
     int least = 0, greatest = 0;
     HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
     if (const char* e = getenv("MRS_STREAM2_PRIORITY")) greatest = atoi(e);
-    HIPCHK(hipStreamCreateWithPriority(&s->stream2, hipStreamNonBlocking, greatest));
+    HIPCHK(s->stream2.create_priority(hipStreamNonBlocking, greatest));
   }
-  HIPCHK(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&s->ev_join_b, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&s->ev_copy, hipEventDisableTiming));
+  HIPCHK(s->ev_fork.create(hipEventDisableTiming));
+  HIPCHK(s->ev_join.create(hipEventDisableTiming));
+  HIPCHK(s->ev_join_b.create(hipEventDisableTiming));
+  HIPCHK(s->ev_copy.create(hipEventDisableTiming));
   s->cstream = s->stream;
   if (const char* e = getenv("MRS_SPLIT_CU_RESERVE")) s->cu_reserve = atoi(e);
   if (s->cu_reserve > 0) {
@@ -493,10 +490,10 @@ int mrs_swarm_create(int32_t n_uavs, int32_t device_id, mrs_swarm_t** out) {
     if (s->cu_reserve >= ncu / 2) return fail(MRS_ERR_ARG, "MRS_SPLIT_CU_RESERVE: at most half of the device's compute units");
     std::vector<uint32_t> mb((size_t)words, 0u), mi((size_t)words, 0u);
     for (int b = 0; b < ncu; b++) (b < s->cu_reserve ? mb : mi)[(size_t)(b / 32)] |= 1u << (b % 32);
-    HIPCHK(hipExtStreamCreateWithCUMask(&s->stream_b, (uint32_t)words, mb.data()));
-    HIPCHK(hipExtStreamCreateWithCUMask(&s->stream_i, (uint32_t)words, mi.data()));
+    HIPCHK(s->stream_b.create_cu_mask((uint32_t)words, mb.data()));
+    HIPCHK(s->stream_i.create_cu_mask((uint32_t)words, mi.data()));
   }
-  HIPCHK(hipEventCreate(&s->ev_end2));
+  HIPCHK(s->ev_end2.create());
   {
     int ncu = 0;
     HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device_id));
@@ -509,9 +506,9 @@ int mrs_swarm_create(int32_t n_uavs, int32_t device_id, mrs_swarm_t** out) {
   if (const char* e = getenv("MRS_EARLY_SEARCH")) s->early_search = atoi(e) != 0;
   if (const char* e = getenv("MRS_SHARD_SPLIT_MIN_BLOCKS")) s->split_min_blocks = atoi(e) > 0 ? atoi(e) : 1;
   if (const char* e = getenv("MRS_SHARD_SPLIT_MAX_FRACTION")) s->split_max_fraction = atof(e);
-  HIPCHK(hipMalloc(&s->dS, sizeof(double) * (size_t)F_COUNT * s->npad));
-  HIPCHK(hipMalloc(&s->dF, sizeof(uint32_t) * (size_t)s->npad));
-  HIPCHK(hipMalloc(&s->dDiag, sizeof(unsigned long long) * 4));
+  HIPCHK(s->dS.alloc((size_t)F_COUNT * s->npad));
+  HIPCHK(s->dF.alloc((size_t)s->npad));
+  HIPCHK(s->dDiag.alloc(4));
   HIPCHK(hipMemsetAsync(s->dS, 0, sizeof(double) * (size_t)F_COUNT * s->npad, s->stream));
   HIPCHK(hipMemsetAsync(s->dF, 0, sizeof(uint32_t) * (size_t)s->npad, s->stream));
   HIPCHK(hipMemsetAsync(s->dDiag, 0, sizeof(unsigned long long) * 4, s->stream));
@@ -529,61 +526,11 @@ int mrs_swarm_create(int32_t n_uavs, int32_t device_id, mrs_swarm_t** out) {
 int mrs_swarm_destroy(mrs_swarm_t* s) {
   if (!s) return MRS_OK;
   (void)hipSetDevice(s->device);
-  if (s->stream) (void)hipStreamSynchronize(s->stream);
-  if (s->stream2) (void)hipStreamSynchronize(s->stream2);
-  if (s->stream_b) (void)hipStreamSynchronize(s->stream_b);
-  if (s->stream_i) (void)hipStreamSynchronize(s->stream_i);
-  for (auto e : s->ev) (void)hipEventDestroy(e);
-  mrs_collide_free(s->cwork);
-  if (s->dRec) (void)hipFree(s->dRec);
-  if (s->dSt) (void)hipFree(s->dSt);
-  if (s->hSt) (void)hipHostFree(s->hSt);
-  for (auto& b : s->ostage) {
-    if (b.d) (void)hipFree(b.d);
-    if (b.h) (void)hipHostFree(b.h);
-  }
-  for (hipStream_t st : {s->stream_io, s->stream_up})
-    if (st) (void)hipStreamSynchronize(st);  // (a copy may still be in flight into / out of the pinned blocks freed below)
-  for (auto& ring : s->oslot)
-    for (auto& o : ring) {
-      if (o.d) (void)hipFree(o.d);
-      if (o.h) (void)hipHostFree(o.h);
-      if (o.packed) (void)hipEventDestroy(o.packed);
-      if (o.done) (void)hipEventDestroy(o.done);
-    }
-  for (auto& i : s->islot) {
-    if (i.d) (void)hipFree(i.d);
-    if (i.h) (void)hipHostFree(i.h);
-    if (i.copied) (void)hipEventDestroy(i.copied);
-    if (i.unpacked) (void)hipEventDestroy(i.unpacked);
-  }
-  for (hipStream_t st : {s->stream_io, s->stream_up})
-    if (st) (void)hipStreamDestroy(st);
-  if (s->dT) (void)hipFree(s->dT);
-  if (s->dBT) (void)hipFree(s->dBT);
-  if (s->dMB) (void)hipFree(s->dMB);
-  if (s->dIota) (void)hipFree(s->dIota);
-  if (s->dDiag) (void)hipFree(s->dDiag);
-  if (s->dF) (void)hipFree(s->dF);
-  if (s->dS) (void)hipFree(s->dS);
+  for (hipStream_t st : {s->stream.get(), s->stream2.get(), s->stream_b.get(), s->stream_i.get(), s->stream_io.get(), s->stream_up.get()})
+    if (st) (void)hipStreamSynchronize(st);  // (a launch or a copy may still be in flight on what the owners free below)
   if (s->rccl_comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(s->rccl_comm);
-  peer_release(s);
-  if (s->comm_send) (void)hipFree(s->comm_send);
-  if (s->comm_recv) (void)hipFree(s->comm_recv);
-  if (s->x_map_send) (void)hipFree(s->x_map_send);
-  if (s->x_map_recv) (void)hipFree(s->x_map_recv);
-  if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
-  if (s->ev_join) (void)hipEventDestroy(s->ev_join);
-  if (s->ev_end2) (void)hipEventDestroy(s->ev_end2);
-  if (s->stream2) (void)hipStreamDestroy(s->stream2);
-  if (s->stream_b) (void)hipStreamDestroy(s->stream_b);
-  if (s->stream_i) (void)hipStreamDestroy(s->stream_i);
-  if (s->ev_join_b) (void)hipEventDestroy(s->ev_join_b);
-  if (s->ev_copy) (void)hipEventDestroy(s->ev_copy);
-  if (s->ev_dio_in) (void)hipEventDestroy(s->ev_dio_in);
-  if (s->ev_dio_out) (void)hipEventDestroy(s->ev_dio_out);
-  nearest_release(s);
-  if (s->stream) (void)hipStreamDestroy(s->stream);
+  peer_release(s);  // closes the peers' windows mapped here
+  mrs_collide_free(s->cwork);
   delete s;
   return MRS_OK;
 }
@@ -1087,15 +1034,9 @@ static int fetch_payload(mrs_swarm* s, int kind, int32_t first, int32_t count) {
   if (rc) return rc;
   mrs_swarm::OutStage& b     = s->ostage[kind];
   const size_t         bytes = payload_bytes(kind) * (size_t)count;
-  if (count > b.cap) {
-    HIPCHK(hipStreamSynchronize(s->stream));
-    if (b.d) HIPCHK(hipFree(b.d));
-    if (b.h) HIPCHK(hipHostFree(b.h));
-    b.d = nullptr; b.h = nullptr; b.cap = 0;
-    HIPCHK(hipMalloc(&b.d, bytes));
-    HIPCHK(hipHostMalloc(&b.h, bytes, hipHostMallocDefault));
-    b.cap = count;
-  }
+  if (bytes > b.d.capacity() || bytes > b.h.capacity()) HIPCHK(hipStreamSynchronize(s->stream));
+  HIPCHK(b.d.reserve(bytes));
+  HIPCHK(b.h.reserve(bytes));
   HIPCHK(launch_pack(s, kind, first, count, b.d, s->stream));
   HIPCHK(hipMemcpyAsync(b.h, b.d, bytes, hipMemcpyDeviceToHost, s->stream));
   HIPCHK(hipStreamSynchronize(s->stream));
@@ -1124,9 +1065,9 @@ static int get_payload_view(mrs_swarm* s, int kind, int32_t first, int32_t count
 }
 
 static int ensure_io_stream(mrs_swarm* s) {
-  if (s->stream_io) return MRS_OK;
-  HIPCHK(hipStreamCreateWithFlags(&s->stream_io, hipStreamNonBlocking));
-  HIPCHK(hipStreamCreateWithFlags(&s->stream_up, hipStreamNonBlocking));
+  if (s->stream_io && s->stream_up) return MRS_OK;
+  HIPCHK(s->stream_io.create(hipStreamNonBlocking));
+  HIPCHK(s->stream_up.create(hipStreamNonBlocking));
   return MRS_OK;
 }
 
@@ -1154,19 +1095,12 @@ static int download_async(mrs_swarm* s, int kind, int32_t first, int32_t count, 
   if ((rc = ensure_io_stream(s))) return rc;
   const int32_t       t = s->out_tickets;
   mrs_swarm::OutSlot& o = s->oslot[kind][s->out_turn[kind] & 1];
-  if (!o.packed) {
-    HIPCHK(hipEventCreateWithFlags(&o.packed, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&o.done, hipEventDisableTiming));
-  }
-  if (count > o.cap) {
-    HIPCHK(hipEventSynchronize(o.done));  // (nobody copies out of the old buffer any more)
-    if (o.d) HIPCHK(hipFree(o.d));
-    if (o.h) HIPCHK(hipHostFree(o.h));
-    o.d = nullptr; o.h = nullptr; o.cap = 0;
-    HIPCHK(hipMalloc(&o.d, payload_bytes(kind) * (size_t)count));
-    HIPCHK(hipHostMalloc(&o.h, payload_bytes(kind) * (size_t)count, hipHostMallocDefault));
-    o.cap = count;
-  }
+  HIPCHK(o.packed.create(hipEventDisableTiming));
+  HIPCHK(o.done.create(hipEventDisableTiming));
+  const size_t bytes = payload_bytes(kind) * (size_t)count;
+  if (bytes > o.d.capacity() || bytes > o.h.capacity()) HIPCHK(hipEventSynchronize(o.done));  // (nobody copies out of the old buffer any more)
+  HIPCHK(o.d.reserve(bytes));
+  HIPCHK(o.h.reserve(bytes));
   o.kind   = kind;
   o.ticket = t;
   o.first  = first;
@@ -1268,22 +1202,14 @@ int mrs_swarm_get_states(mrs_swarm_t* s, int32_t first, int32_t count, mrs_uav_s
   if (count == 0) return MRS_OK;
   HIPCHK(hipSetDevice(s->device));
   if ((rc = upload_types(s, s->table_dt > 0 ? s->table_dt : 0.001))) return rc;
-  if (count > s->st_cap) {
-    HIPCHK(hipStreamSynchronize(s->stream));
-    if (s->dSt) HIPCHK(hipFree(s->dSt));
-    if (s->hSt) HIPCHK(hipHostFree(s->hSt));
-    s->dSt = nullptr;
-    s->hSt = nullptr;
-    s->st_cap = 0;
-    HIPCHK(hipMalloc(&s->dSt, sizeof(mrs_uav_state_t) * (size_t)count));
-    HIPCHK(hipHostMalloc(&s->hSt, sizeof(mrs_uav_state_t) * (size_t)count, hipHostMallocMapped));
-    s->st_cap = count;
-  }
+  if ((size_t)count > s->dSt.capacity() || (size_t)count > s->hSt.capacity()) HIPCHK(hipStreamSynchronize(s->stream));
+  HIPCHK(s->dSt.reserve((size_t)count));
+  HIPCHK(s->hSt.reserve((size_t)count, hipHostMallocMapped));
   // few UAVs (the facade's lone object, a pool's round): the pack kernel stores straight into the pinned block — no copy command
   // behind it (a DMA of a few hundred bytes costs the stream ~8 us, a third of a single object's makeStep + getState)
   static const int direct_max = getenv("MRS_DIRECT_STATE_MAX") ? atoi(getenv("MRS_DIRECT_STATE_MAX")) : 1024;
   mrs_uav_state_t* host_dev = nullptr;
-  if (count <= direct_max && hipHostGetDevicePointer((void**)&host_dev, s->hSt, 0) == hipSuccess && host_dev) {
+  if (count <= direct_max && hipHostGetDevicePointer((void**)&host_dev, s->hSt.get(), 0) == hipSuccess && host_dev) {
     HIPCHK(mrs_launch_pack_states(s->view(), first, count, host_dev, s->stream));
   } else {
     HIPCHK(mrs_launch_pack_states(s->view(), first, count, s->dSt, s->stream));
@@ -1301,23 +1227,15 @@ int mrs_swarm_input_staging(mrs_swarm_t* s, int32_t count, int32_t stride, doubl
   HIPCHK(hipSetDevice(s->device));
   int rc = ensure_io_stream(s);
   if (rc) return rc;
-  const int64_t need = (int64_t)count * stride;
+  const size_t need = (size_t)count * (size_t)stride;
   s->in_turn ^= 1;  // the other block: the commit of the previous one may still be copying
   mrs_swarm::InSlot& b = s->islot[s->in_turn];
-  if (!b.copied) {
-    HIPCHK(hipEventCreateWithFlags(&b.copied, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&b.unpacked, hipEventDisableTiming));
-  }
+  HIPCHK(b.copied.create(hipEventDisableTiming));
+  HIPCHK(b.unpacked.create(hipEventDisableTiming));
   HIPCHK(hipEventSynchronize(b.copied));  // the commit two calls ago has read these rows (that copy only: no stream is waited for)
-  if (need > b.cap) {
-    HIPCHK(hipEventSynchronize(b.unpacked));
-    if (b.h) HIPCHK(hipHostFree(b.h));
-    if (b.d) HIPCHK(hipFree(b.d));
-    b.h = nullptr; b.d = nullptr; b.cap = 0;
-    HIPCHK(hipHostMalloc(&b.h, sizeof(double) * (size_t)need, hipHostMallocDefault));
-    HIPCHK(hipMalloc(&b.d, sizeof(double) * (size_t)need));
-    b.cap = need;
-  }
+  if (need > b.h.capacity() || need > b.d.capacity()) HIPCHK(hipEventSynchronize(b.unpacked));
+  HIPCHK(b.h.reserve(need));
+  HIPCHK(b.d.reserve(need));
   *rows = b.h;
   return MRS_OK;
 }
@@ -1329,7 +1247,7 @@ int mrs_swarm_commit_input(mrs_swarm_t* s, int32_t first, int32_t count, int32_t
   if (mode < MRS_ACTUATOR_CMD || mode > MRS_POSITION_CMD) return fail(MRS_ERR_ARG, "bad input mode");
   if (count == 0) return MRS_OK;
   mrs_swarm::InSlot& b = s->islot[s->in_turn];
-  if (!b.h || (int64_t)count * stride > b.cap) return fail(MRS_ERR_ARG, "no staging rows of this shape (call mrs_swarm_input_staging first)");
+  if (!b.h || (size_t)count * (size_t)stride > b.d.capacity()) return fail(MRS_ERR_ARG, "no staging rows of this shape (call mrs_swarm_input_staging first)");
   int width = 4;
   if (mode == MRS_ACTUATOR_CMD) width = stride < MRS_MAX_MOTORS ? stride : MRS_MAX_MOTORS;
   if (mode == MRS_ATTITUDE_CMD) width = 10;
@@ -1381,8 +1299,8 @@ int mrs_debug_pid_sequences(int32_t device_id, int32_t arith, int32_t n_seq, int
   if (n_seq == 0 || n_steps == 0) return MRS_OK;
   if (device_id >= 0) HIPCHK(hipSetDevice(device_id));
   const size_t cells = (size_t)n_seq * (size_t)n_steps;
-  double*      d     = nullptr;  // params | err | dt | event | new_sat | out
-  HIPCHK(hipMalloc(&d, sizeof(double) * ((size_t)n_seq * 5 + cells * 5)));
+  DevBuf<double> d;  // params | err | dt | event | new_sat | out
+  HIPCHK(d.alloc((size_t)n_seq * 5 + cells * 5));
   double *dp = d, *de = dp + (size_t)n_seq * 5, *dd = de + cells, *dv = dd + cells, *ds = dv + cells, *dout = ds + cells;
   hipError_t e = hipMemcpy(dp, params, sizeof(double) * (size_t)n_seq * 5, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(de, err, sizeof(double) * cells, hipMemcpyHostToDevice);
@@ -1393,7 +1311,6 @@ int mrs_debug_pid_sequences(int32_t device_id, int32_t arith, int32_t n_seq, int
     e = arith == MRS_ARITH_FAST ? mrs_launch_pid_probe_fast(dp, de, dd, dv, ds, dout, n_seq, n_steps, nullptr)
                                 : mrs_launch_pid_probe_literal(dp, de, dd, dv, ds, dout, n_seq, n_steps, nullptr);
   if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(double) * cells, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
   if (e != hipSuccess) return fail(MRS_ERR_HIP, std::string("pid probe: ") + hipGetErrorString(e));
   return MRS_OK;
 }
@@ -1404,8 +1321,8 @@ int mrs_debug_pid_update(int32_t device_id, int32_t arith, int32_t n, const doub
   if (arith != MRS_ARITH_LITERAL && arith != MRS_ARITH_FAST) return fail(MRS_ERR_ARG, "unknown arithmetic flavour");
   if (n == 0) return MRS_OK;
   if (device_id >= 0) HIPCHK(hipSetDevice(device_id));
-  double* d = nullptr;  // params 5n | state 2n | err n | dt n | out n
-  HIPCHK(hipMalloc(&d, sizeof(double) * (size_t)n * 10));
+  DevBuf<double> d;  // params 5n | state 2n | err n | dt n | out n
+  HIPCHK(d.alloc((size_t)n * 10));
   double *dp = d, *ds = dp + (size_t)n * 5, *de = ds + (size_t)n * 2, *dd = de + n, *dout = dd + n;
   hipError_t e = hipMemcpy(dp, params, sizeof(double) * (size_t)n * 5, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(ds, state, sizeof(double) * (size_t)n * 2, hipMemcpyHostToDevice);
@@ -1415,7 +1332,6 @@ int mrs_debug_pid_update(int32_t device_id, int32_t arith, int32_t n, const doub
     e = arith == MRS_ARITH_FAST ? mrs_launch_pid_update_probe_fast(dp, ds, de, dd, dout, n, nullptr) : mrs_launch_pid_update_probe_literal(dp, ds, de, dd, dout, n, nullptr);
   if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(state, ds, sizeof(double) * (size_t)n * 2, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
   if (e != hipSuccess) return fail(MRS_ERR_HIP, std::string("pid update: ") + hipGetErrorString(e));
   return MRS_OK;
 }
@@ -1432,9 +1348,9 @@ int mrs_swarm_debug_component(mrs_swarm_t* s, int32_t component, int32_t first, 
   if (count == 0) return MRS_OK;
   HIPCHK(hipSetDevice(s->device));
   if ((rc = upload_types(s, s->table_dt > 0 ? s->table_dt : 0.001))) return rc;
-  double*      d   = nullptr;
   const size_t nin = (size_t)count * in_stride, nout = (size_t)count * out_stride;
-  HIPCHK(hipMalloc(&d, sizeof(double) * (nin + nout)));
+  DevBuf<double> d;
+  HIPCHK(d.alloc(nin + nout));
   hipError_t e = hipMemcpyAsync(d, in, sizeof(double) * nin, hipMemcpyHostToDevice, s->stream);
   if (e == hipSuccess) e = hipMemsetAsync(d + nin, 0, sizeof(double) * nout, s->stream);
   if (e == hipSuccess)
@@ -1442,7 +1358,6 @@ int mrs_swarm_debug_component(mrs_swarm_t* s, int32_t component, int32_t first, 
                                    : mrs_launch_component_probe_literal(s->view(), component, first, count, d, in_stride, d + nin, out_stride, dt, s->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(out, d + nin, sizeof(double) * nout, hipMemcpyDeviceToHost, s->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-  (void)hipFree(d);
   if (e != hipSuccess) return fail(MRS_ERR_HIP, std::string("component probe: ") + hipGetErrorString(e));
   return MRS_OK;
 }
@@ -1452,6 +1367,16 @@ int mrs_swarm_debug_collision_words(mrs_swarm_t* s, uint32_t* out8) {
   if (!s || !out8) return fail(MRS_ERR_ARG, "null argument");
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(mrs_collide_debug_words(s->cwork, s->stream, out8));
+  return MRS_OK;
+}
+
+// debugging aid: device buffers, pinned blocks, events and streams the library holds in this process right now (hip_owned.h)
+int mrs_debug_live_resources(int64_t out[4]) {
+  if (!out) return fail(MRS_ERR_ARG, "null out");
+  out[0] = hip_owned::live_dev.load();
+  out[1] = hip_owned::live_pinned.load();
+  out[2] = hip_owned::live_events.load();
+  out[3] = hip_owned::live_streams.load();
   return MRS_OK;
 }
 

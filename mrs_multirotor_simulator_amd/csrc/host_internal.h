@@ -10,6 +10,9 @@
 //   transport_local.hip   in-process loopback group, caller-supplied all-gather, measurement stand-in (with its kernels)
 //   transport_peer.hip    peer-window exchange (direct writes into the peers' device memory; with its kernel)
 // sharded_protocol.h holds the pure decision functions of the sharded protocol (tested without a GPU: tests/cpp/sharded_protocol_test.cpp).
+// hip_owned.h holds the owners (DevBuf, PinnedBuf, Event, Stream) of every GPU resource below: a swarm frees what it holds when it is
+// deleted, members in reverse order of declaration — the streams are declared first and die last.  A buffer that grows on demand
+// carries its own capacity; what the grow has to wait for stays at the call site, one line before reserve().
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,6 +34,7 @@
 
 #include "../../include/mrs_swarm.h"
 #include "swarm_layout.h"
+#include "hip_owned.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -170,20 +174,24 @@ struct mrs_swarm {
   std::recursive_mutex mtx;
   int32_t  n = 0, npad = 0, device = 0;
   int32_t  arith = MRS_ARITH_LITERAL;
-  hipStream_t stream = nullptr;
+  Stream   stream;
   // a run of steps without collisions in between is issued as two half-swarm launches per step on two streams: the halves are
   // independent, so the drain of one launch overlaps the ramp of the other (tools/two_streams.py: +11 % at 100 k, +19 % at 200 k)
-  hipStream_t stream2 = nullptr;
+  Stream stream2;
   // Split sharded ticks with reserved compute units (MRS_SPLIT_CU_RESERVE = R > 0; tools/cu_mask_probe.hip): the boundary launch and the
   // collective run on `stream_b`, whose queue may use R CUs only (mask bits 0..R-1: bit i is CU i / 8 of XCD i % 8), the interior
   // launch on `stream_i`, whose queue uses all the others — the lone waves of the boundary chain no longer share SIMDs with the
   // streaming interior waves.  `cstream`: where collectives and boundary launches go right now (`stream` outside split segments).
-  hipStream_t stream_b = nullptr, stream_i = nullptr, cstream = nullptr;
-  hipEvent_t  ev_join_b = nullptr;
-  hipEvent_t  ev_copy = nullptr;   // mrs_swarm_copy_uavs between two swarms: orders the copy against the other swarm's stream
+  Stream      stream_b, stream_i;
+  // copy streams: download (stream_io) and command upload (stream_up) — one per direction, PCIe is full duplex.  (The download cut
+  // in two halves on two streams — two DMA engines — was measured and dropped: 0.40 against 0.38 ms per 13.6-MB tick.)
+  Stream      stream_io, stream_up;
+  hipStream_t cstream = nullptr;   // (an alias, not an owner)
+  Event       ev_join_b;
+  Event       ev_copy;             // mrs_swarm_copy_uavs between two swarms: orders the copy against the other swarm's stream
   int         cu_reserve = 0;
-  hipEvent_t  ev_fork = nullptr, ev_join = nullptr;
-  hipEvent_t  ev_end2 = nullptr;   // profiling: end of the second stream's part of a split run (recorded before the join)
+  Event       ev_fork, ev_join;
+  Event       ev_end2;             // profiling: end of the second stream's part of a split run (recorded before the join)
   bool        prof_split = false;  // the end events of the running profile region have been recorded by the split run itself
   // every C-ABI call bumps op_seq (MRS_LOCK); mrs_swarm_synchronize notes the value it leaves behind: a run of steps that is the very
   // next call finds both streams idle and starts its second stream without the fork event
@@ -194,8 +202,7 @@ struct mrs_swarm {
   void*      rccl_comm = nullptr;
   int        comm_world = 0, comm_rank = 0;   // comm_world > 0: a communicator of some kind is bound
   int64_t    comm_n_total = 0, comm_n_max = 0;
-  PosRecord* comm_send = nullptr;
-  PosRecord* comm_recv = nullptr;
+  DevBuf<PosRecord> comm_send, comm_recv;
   // collective backend other than RCCL: a caller-supplied all-gather (mrs_swarm_comm_init_custom) or an in-process group of
   // swarms driven by one host thread each (mrs_swarm_comm_init_loopback)
   mrs_allgather_fn      comm_fn = nullptr;
@@ -208,21 +215,21 @@ struct mrs_swarm {
   // peer-window exchange (mrs_swarm_peer_window_create / mrs_swarm_comm_init_peer; transport_peer.hip k_peer_allgather): ranks write their
   // blocks straight into each other's device memory, one kernel per collective on the swarm's stream, no collective library
   bool               comm_peer = false;
-  void*              peer_window = nullptr;       // this rank's window (fine-grained device memory)
+  DevBuf<void>       peer_window;                 // this rank's window (fine-grained device memory)
   size_t             peer_slot_bytes = 0, peer_window_bytes = 0;
   int                peer_world = 0, peer_rank = 0;
   int64_t            peer_n_total = 0;
   MrsPeerWindows     peer_windows{};              // every rank's window as this process addresses it
   std::vector<void*> peer_opened;                 // the ones mapped here through an IPC handle (closed by comm_destroy)
   unsigned           peer_seq = 0, peer_tickets = 0;
-  unsigned*          peer_ticket = nullptr;       // device words, one per peer: blocks of all exchange kernels so far that have pushed their share for it
-  unsigned*          peer_err = nullptr;          // pinned host word: an exchange kernel waited in vain for a peer
+  DevBuf<unsigned>   peer_ticket;                 // device words, one per peer: blocks of all exchange kernels so far that have pushed their share for it
+  PinnedBuf<unsigned> peer_err;                   // pinned host word: an exchange kernel waited in vain for a peer
   // export-set exchange: between two searches only boundary UAVs travel
   int       exchange = MRS_EXCHANGE_EXPORT_SETS;
   bool      x_ok = false;           // export lists are live: the next tick can be a fused launch + export-set all-gather
   int       x_fallback_left = 0;    // ticks to stay on the full exchange after an incomplete (overflowing) search
-  uint32_t* x_map_send = nullptr;   // [2 + n_max] slot map of this rank
-  uint32_t* x_map_recv = nullptr;   // [world][2 + n_max]
+  DevBuf<uint32_t> x_map_send;      // [2 + n_max] slot map of this rank
+  DevBuf<uint32_t> x_map_recv;      // [world][2 + n_max]
   int64_t   x_export_count = 0;
   std::vector<unsigned> x_last_overflow;
   int64_t   x_searches = 0, x_ticks = 0, x_noop_ticks = 0;
@@ -247,11 +254,10 @@ struct mrs_swarm {
   int       chaos_max_us = 0;
   uint64_t  chaos_state = 0x9E3779B97F4A7C15ull;
   unsigned  chaos_T = 0, chaos_W = 0;
-  double*   dS = nullptr;
-  uint32_t* dF = nullptr;
-  TypeParams* dT = nullptr;
-  int32_t   dT_cap = 0;
-  unsigned long long* dDiag = nullptr;
+  DevBuf<double>     dS;
+  DevBuf<uint32_t>   dF;
+  DevBuf<TypeParams> dT;
+  DevBuf<unsigned long long> dDiag;
   std::vector<TypeKey>    keys;
   std::vector<TypeParams> tparams;
   std::map<std::string, int> key_index;
@@ -262,15 +268,13 @@ struct mrs_swarm {
   double table_dt    = -1.0;
   // publisher payloads of the synchronous calls (mrs_swarm_get_outputs* / get_poses*): device pack buffer + pinned host staging per
   // kind, so that a view of one kind survives a call of the other
-  struct OutStage {
-    void*   d = nullptr;
-    void*   h = nullptr;
-    int32_t cap = 0;
+  struct OutStage {  // (both count bytes)
+    DevBuf<void>    d;
+    PinnedBuf<void> h;
   };
   OutStage ostage[PAYLOAD_KINDS];
-  mrs_uav_state_t*  dSt = nullptr;   // packed states (mrs_swarm_get_states): device buffer + pinned host staging
-  mrs_uav_state_t*  hSt = nullptr;
-  int32_t           st_cap = 0;
+  DevBuf<mrs_uav_state_t>    dSt;   // packed states (mrs_swarm_get_states): device buffer + pinned host staging
+  PinnedBuf<mrs_uav_state_t> hSt;
   // Pipelined publisher download (mrs_swarm_get_outputs_async / mrs_swarm_outputs_wait): two pack buffers with a pinned block each;
   // the pack kernel runs on the step stream behind everything queued so far, the device-to-host copy on `stream_io`, so the download
   // of tick t overlaps step t + 1.  `packed` orders copy behind pack, `done` is what the host waits for (and what the next pack into
@@ -279,34 +283,31 @@ struct mrs_swarm {
   // tickets of both kinds come from one counter.
   struct OutSlot {
     int32_t    kind = PAYLOAD_WIDE;
-    void *     d = nullptr, *h = nullptr;
-    int32_t    cap = 0, ticket = -1, first = 0, count = 0;
-    hipEvent_t packed = nullptr, done = nullptr;
+    DevBuf<void>    d;  // (both count bytes)
+    PinnedBuf<void> h;
+    int32_t    ticket = -1, first = 0, count = 0;
+    Event      packed, done;
   };
   OutSlot     oslot[PAYLOAD_KINDS][2];
   int32_t     out_turn[PAYLOAD_KINDS] = {};  // the slot of each kind the next _async call takes (alternating)
   int64_t     n_packs_issued = 0, n_packs_reissued = 0;
-  // copy streams: download (stream_io) and command upload (stream_up) — one per direction, PCIe is full duplex.  (The download cut
-  // in two halves on two streams — two DMA engines — was measured and dropped: 0.40 against 0.38 ms per 13.6-MB tick.)
-  hipStream_t stream_io = nullptr, stream_up = nullptr;
   int32_t     out_tickets = 0;
   // staged command upload: two pinned row blocks + device copies, handed out in turn — the caller fills block k + 1 while the copy of
   // block k may still be in flight (`copied`: the host may refill the rows; `unpacked`: the device copy may be overwritten)
   struct InSlot {
-    double *   h = nullptr, *d = nullptr;
-    int64_t    cap = 0;  // doubles
-    hipEvent_t copied = nullptr, unpacked = nullptr;
+    PinnedBuf<double> h;
+    DevBuf<double>    d;
+    Event      copied, unpacked;
   };
   InSlot  islot[2];
   int     in_turn = 0;   // the block the last mrs_swarm_input_staging handed out
   // device-resident callers (device_io.hip): the caller's stream -> swarm's stream fence and back, created at first use
-  hipEvent_t ev_dio_in = nullptr, ev_dio_out = nullptr;
+  Event ev_dio_in, ev_dio_out;
   // nearest-neighbour observations (nearest.hip): one device block carved into bucket counts, starts, sorted records; grown on demand,
   // never shared with the collision pass, not copied by clone
-  void*  nn_buf = nullptr;
-  size_t nn_bytes = 0;
+  DevBuf<void> nn_buf;  // (counts bytes)
   // collision scratch
-  PosRecord*   dRec = nullptr;
+  DevBuf<PosRecord> dRec;
   CollideWork* cwork = nullptr;
   bool         use_lists = true;   // single-GPU collision ticks reuse neighbour lists between rebuilds (tuning: MRS_NEIGHBOUR_LISTS=0)
   bool         nbr_dirty = true;   // the host wrote positions or airframe constants since the last collision tick
@@ -352,7 +353,7 @@ struct mrs_swarm {
   int64_t              n_stalls = 0, n_noop_launches = 0, n_fused = 0;
   // profiling
   int  profiling = 0;  // 0 off, 1 one event pair around the whole step_n/tick_n region, 2 one pair per step launch
-  std::vector<hipEvent_t> ev;
+  std::vector<Event> ev;
   int  ev_used = 0;
   int  region_launches = 0;
   double last_ms = 0.0;
@@ -363,11 +364,10 @@ struct mrs_swarm {
   // per-64-block airframe type (0xFFFF = mixed) and the list of mixed blocks
   std::vector<uint32_t> block_type;
   std::vector<int32_t>  mixed_blocks;
-  uint32_t* dBT = nullptr;
-  int32_t*  dMB = nullptr;
+  DevBuf<uint32_t> dBT;
+  DevBuf<int32_t>  dMB;
   bool      blocks_dirty = true;
-  int32_t*  dIota = nullptr;  // 0, 1, 2, ...: block list of a partial step (mrs_swarm_step_range)
-  int       iota_cap = 0;
+  DevBuf<int32_t> dIota;  // 0, 1, 2, ...: block list of a partial step (mrs_swarm_step_range)
 
   bool      fext_active = false;  // apply_force / collisions were used at least once
 
@@ -451,8 +451,6 @@ size_t rows_bytes(int count, int stride, int width, int dtype);
 int    fence_in(mrs_swarm* s, hipStream_t ext);
 int    fence_out(mrs_swarm* s, hipStream_t ext);
 int    launch_crashed_u8(mrs_swarm* s, int first, int count, uint8_t* dev_out);  // hasCrashed of a range as bytes, on the swarm's stream
-// ---- nearest.hip ----
-void   nearest_release(mrs_swarm* s);  // frees the scratch of mrs_swarm_nearest_device (mrs_swarm_destroy)
 // ---- transports (transport_*.hip) and the communicator bookkeeping (tick_sharded.hip) ----
 int  rccl_load(const char* path);
 int  rccl_check(int rc, const char* what);

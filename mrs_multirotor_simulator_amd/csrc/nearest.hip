@@ -336,14 +336,6 @@ int nn_order() {
 
 }  // namespace
 
-namespace mrs_host {
-void nearest_release(mrs_swarm* s) {
-  if (s->nn_buf) (void)hipFree(s->nn_buf);
-  s->nn_buf   = nullptr;
-  s->nn_bytes = 0;
-}
-}  // namespace mrs_host
-
 extern "C" {
 
 int mrs_nearest_width(uint32_t fields, int32_t k, int32_t* width) {
@@ -391,12 +383,8 @@ int mrs_swarm_nearest_device(mrs_swarm_t* s, int32_t first, int32_t count, int32
   const size_t off_st   = off_cnt + sizeof(int32_t) * ncnt;
   const size_t off_bs   = off_st + sizeof(int32_t) * ncnt;
   const size_t bytes    = off_bs + sizeof(int32_t) * (size_t)nchunks;
-  if (bytes > s->nn_bytes) {
-    nearest_release(s);
-    HIPCHK(hipMalloc(&s->nn_buf, bytes));
-    s->nn_bytes = bytes;
-  }
-  char*    base  = static_cast<char*>(s->nn_buf);
+  HIPCHK(s->nn_buf.reserve(bytes));  // (every launch that reads the block is on the swarm's stream; hipFree waits for the device)
+  char*    base  = static_cast<char*>(s->nn_buf.get());
   NnRec*   rec   = reinterpret_cast<NnRec*>(base);
   int32_t* rank  = reinterpret_cast<int32_t*>(base + off_rank);
   int32_t* bkt   = reinterpret_cast<int32_t*>(base + off_bkt);

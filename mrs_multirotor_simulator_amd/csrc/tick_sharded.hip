@@ -44,10 +44,10 @@ int comm_buffers(mrs_swarm* s, int world, int rank, int64_t n_total) {
   s->halo_trace = getenv("MRS_HALO_TRACE") && atoi(getenv("MRS_HALO_TRACE")) != 0;
   s->x_last_overflow.assign((size_t)world, 0u);
   if (const char* e = getenv("MRS_EXCHANGE")) s->exchange = atoi(e) == 1 ? MRS_EXCHANGE_FULL_GATHER : MRS_EXCHANGE_EXPORT_SETS;
-  HIPCHK(hipMalloc(&s->comm_send, sizeof(PosRecord) * (size_t)s->comm_n_max));
-  HIPCHK(hipMalloc(&s->comm_recv, sizeof(PosRecord) * (size_t)s->comm_n_max * (size_t)world));
-  HIPCHK(hipMalloc(&s->x_map_send, sizeof(uint32_t) * (size_t)map_stride(s)));
-  HIPCHK(hipMalloc(&s->x_map_recv, sizeof(uint32_t) * (size_t)map_stride(s) * (size_t)world));
+  HIPCHK(s->comm_send.alloc((size_t)s->comm_n_max));
+  HIPCHK(s->comm_recv.alloc((size_t)s->comm_n_max * (size_t)world));
+  HIPCHK(s->x_map_send.alloc((size_t)map_stride(s)));
+  HIPCHK(s->x_map_recv.alloc((size_t)map_stride(s) * (size_t)world));
   HIPCHK(hipMemsetAsync(s->x_map_recv, 0, sizeof(uint32_t) * (size_t)map_stride(s) * (size_t)world, s->stream));  // (the stand-in collective leaves absent ranks' maps alone)
   HIPCHK(hipMemsetAsync(s->comm_send, 0xFF, sizeof(PosRecord) * (size_t)s->comm_n_max, s->stream));  // NaN padding records never collide
   HIPCHK(hipMemsetAsync(s->x_map_send, 0xFF, sizeof(uint32_t) * (size_t)map_stride(s), s->stream));      // (the box at its tail: NaN bounds until a search writes it — for good on a rank without UAVs)
@@ -118,13 +118,11 @@ int mrs_swarm_comm_destroy(mrs_swarm_t* s) {
   s->x_ok       = false;
   s->halo_ok    = false;
   mrs_collide_invalidate_gathered(s->cwork);
-  if (s->comm_send) (void)hipFree(s->comm_send);
-  if (s->comm_recv) (void)hipFree(s->comm_recv);
+  s->comm_send.reset();
+  s->comm_recv.reset();
   if (s->cwork) mrs_collide_set_box_out(&s->cwork, nullptr);
-  if (s->x_map_send) (void)hipFree(s->x_map_send);
-  if (s->x_map_recv) (void)hipFree(s->x_map_recv);
-  s->comm_send = s->comm_recv = nullptr;
-  s->x_map_send = s->x_map_recv = nullptr;
+  s->x_map_send.reset();
+  s->x_map_recv.reset();
   return rc;
 }
 

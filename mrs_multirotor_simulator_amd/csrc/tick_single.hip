@@ -20,15 +20,21 @@ int launch_part(mrs_swarm* s, double dt, int substeps, int blk0, int nblk, int w
   return MRS_OK;
 }
 
+// the profiling events: at least `count` of them exist afterwards
+static int ensure_events(mrs_swarm* s, size_t count) {
+  while (s->ev.size() < count) {
+    Event e;
+    HIPCHK(e.create());
+    s->ev.push_back(std::move(e));
+  }
+  return MRS_OK;
+}
+
 int launch_step(mrs_swarm* s, double dt, int substeps, bool imu_dead) {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   s->region_launches++;
   if (s->profiling == 2) {
-    while ((int)s->ev.size() < s->ev_used + 2) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      s->ev.push_back(e);
-    }
+    if (int rc = ensure_events(s, (size_t)s->ev_used + 2)) return rc;
     e0 = s->ev[(size_t)s->ev_used];
     e1 = s->ev[(size_t)s->ev_used + 1];
     s->ev_used += 2;
@@ -66,11 +72,7 @@ int begin_profile(mrs_swarm* s) {
   s->region_launches  = 0;
   s->prof_split       = false;
   if (s->profiling == 1) {
-    while (s->ev.size() < 2) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      s->ev.push_back(e);
-    }
+    if (int rc = ensure_events(s, 2)) return rc;
     HIPCHK(hipEventRecord(s->ev[0], s->stream));
   }
   return MRS_OK;
@@ -156,7 +158,7 @@ int wait_for_progress(mrs_swarm* s, const volatile unsigned* hw, unsigned index,
     __builtin_ia32_pause();
     if ((spins & 0xFFFFul) != 0) continue;
     // a launch that failed asynchronously never writes its words — on whichever stream of a split tick it ran
-    for (hipStream_t st : {s->stream, s->stream2, s->stream_i, s->stream_b}) {
+    for (hipStream_t st : {s->stream.get(), s->stream2.get(), s->stream_i.get(), s->stream_b.get()}) {
       if (!st) continue;
       const hipError_t q = hipStreamQuery(st);
       if (q != hipSuccess && q != hipErrorNotReady) return fail(MRS_ERR_HIP, std::string("fused launches: ") + hipGetErrorString(q));
@@ -206,11 +208,7 @@ int launch_fused(mrs_swarm* s, const mrs_swarm::TickRec& e) {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   s->region_launches++;
   if (s->profiling == 2) {
-    while ((int)s->ev.size() < s->ev_used + 2) {
-      hipEvent_t ev;
-      HIPCHK(hipEventCreate(&ev));
-      s->ev.push_back(ev);
-    }
+    if (int rc = ensure_events(s, (size_t)s->ev_used + 2)) return rc;
     e0 = s->ev[(size_t)s->ev_used];
     e1 = s->ev[(size_t)s->ev_used + 1];
     s->ev_used += 2;
@@ -436,17 +434,14 @@ int mrs_swarm_step_range(mrs_swarm_t* s, int32_t first, int32_t count, double dt
   HIPCHK(hipSetDevice(s->device));
   if ((rc = upload_types(s, dt))) return rc;
   const int nb = (count + 63) / 64;
-  if (nb > s->iota_cap) {
+  if ((size_t)nb > s->dIota.capacity()) {
     HIPCHK(hipStreamSynchronize(s->stream));
-    if (s->dIota) HIPCHK(hipFree(s->dIota));
-    s->dIota = nullptr;
     int cap = 16;
     while (cap < nb) cap *= 2;
     std::vector<int32_t> iota((size_t)cap);
     for (int b = 0; b < cap; b++) iota[(size_t)b] = b;
-    HIPCHK(hipMalloc(&s->dIota, sizeof(int32_t) * (size_t)cap));
+    HIPCHK(s->dIota.reserve((size_t)cap));
     HIPCHK(hipMemcpy(s->dIota, iota.data(), sizeof(int32_t) * (size_t)cap, hipMemcpyHostToDevice));
-    s->iota_cap = cap;
   }
   SwarmDev v = s->view();
   v.S += first;  // column f of UAV first + i sits at S[f * npad + first + i]: the same stride, shifted base
@@ -475,7 +470,7 @@ int mrs_swarm_pack_positions(mrs_swarm_t* s, void** dev_ptr, int64_t* n_bytes) {
   HIPCHK(hipSetDevice(s->device));
   int rc = upload_types(s, s->table_dt > 0 ? s->table_dt : 0.001);
   if (rc) return rc;
-  if (!s->dRec) HIPCHK(hipMalloc(&s->dRec, sizeof(PosRecord) * (size_t)s->npad));
+  HIPCHK(s->dRec.reserve((size_t)s->npad));
   HIPCHK(mrs_launch_pack_positions(s->view(), s->dRec, s->stream));
   if (dev_ptr) *dev_ptr = s->dRec;
   if (n_bytes) *n_bytes = (int64_t)sizeof(PosRecord) * s->n;
@@ -531,7 +526,7 @@ int mrs_swarm_handle_collisions(mrs_swarm_t* s, int32_t enabled, int32_t crash, 
   if ((rc = settle(s))) return rc;
   if ((rc = upload_types(s, s->table_dt > 0 ? s->table_dt : 0.001))) return rc;
   s->fext_active = true;
-  if (!s->dRec) HIPCHK(hipMalloc(&s->dRec, sizeof(PosRecord) * (size_t)s->npad));
+  HIPCHK(s->dRec.reserve((size_t)s->npad));
   HIPCHK(mrs_collide_run(s->view(), &s->cwork, s->dRec, s->n, 0, crash, rebounce, /*rec_is_local_scratch=*/1, s->stream));
   return MRS_OK;
 }
@@ -584,11 +579,7 @@ int mrs_swarm_debug_search_ms(mrs_swarm_t* s, int32_t reps, int32_t crash, doubl
   if (rc) return rc;
   const mrs_swarm::Collide c{true, 1, crash, rebounce};
   if ((rc = collide_now(s, c, /*force=*/true))) return rc;  // buffers exist, tables are in their steady state
-  while (s->ev.size() < 2) {
-    hipEvent_t e;
-    HIPCHK(hipEventCreate(&e));
-    s->ev.push_back(e);
-  }
+  if ((rc = ensure_events(s, 2))) return rc;
   HIPCHK(hipEventRecord(s->ev[0], s->stream));
   for (int k = 0; k < reps; k++) HIPCHK(mrs_collide_run_lists(s->view(), &s->cwork, crash, rebounce, 1, 0u, s->stream));
   HIPCHK(hipEventRecord(s->ev[1], s->stream));

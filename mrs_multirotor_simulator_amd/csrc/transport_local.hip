@@ -10,17 +10,15 @@ struct mrs_loopback_group {
   std::atomic<int>         arrived{0};
   std::atomic<unsigned>    generation{0};
   std::vector<const void*> send;
-  std::vector<hipEvent_t>  ev_ready, ev_copied;
-  std::vector<int>         device;
+  std::vector<Event>       ev_ready, ev_copied;  // (one per rank, created by the rank that joins; all freed with the group)
   std::atomic<int>         failed{0};
   // rendezvous mode (mrs_loopback_group_set_rendezvous): no barrier — a rank stages its block, publishes the index of the collective
   // and only waits until every peer has published the same index (it cannot enqueue copies of data a peer has not enqueued yet);
   // staging buffers and events alternate between two sets, so a fast rank never waits for a slow one to have COPIED
   int                                     rendezvous = 0;
   std::unique_ptr<std::atomic<unsigned>[]> seq;           // seq[q] = collectives rank q has published
-  std::vector<void*>                      stage[2];
-  std::vector<size_t>                     stage_cap[2];
-  std::vector<hipEvent_t>                 ev_ready2[2], ev_copied2[2];
+  std::vector<DevBuf<void>>               stage[2];      // (count bytes)
+  std::vector<Event>                      ev_ready2[2], ev_copied2[2];
   void barrier() {  // sense-reversing spin barrier (at most a handful of threads, all inside the same library call)
     const unsigned gen = generation.load(std::memory_order_acquire);
     if (arrived.fetch_add(1, std::memory_order_acq_rel) + 1 == world) {
@@ -119,13 +117,8 @@ static int loopback_allgather_rendezvous(mrs_loopback_group* g, int rank, const 
   // the staging buffer of this parity was last read by the peers in collective k - 2: their "copied" events were recorded before they
   // published k - 1, which this rank waited for in collective k - 1
   for (int q = 0; q < g->world && e == hipSuccess && k >= 2u; q++) e = hipStreamWaitEvent(st, g->ev_copied2[par][(size_t)q], 0);
-  if (e == hipSuccess && bytes > g->stage_cap[par][r]) {
-    e = hipStreamSynchronize(st);
-    if (g->stage[par][r]) (void)hipFree(g->stage[par][r]);
-    g->stage[par][r] = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&g->stage[par][r], bytes);
-    g->stage_cap[par][r] = e == hipSuccess ? bytes : 0;
-  }
+  if (e == hipSuccess && bytes > g->stage[par][r].capacity()) e = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = g->stage[par][r].reserve(bytes);
   if (e == hipSuccess && bytes) e = hipMemcpyAsync(g->stage[par][r], send, bytes, hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess) e = hipEventRecord(g->ev_ready2[par][r], st);
   if (e != hipSuccess) g->failed.store(1);
@@ -235,16 +228,14 @@ int mrs_loopback_group_create(int32_t world, mrs_loopback_group_t** out) {
   mrs_loopback_group* g = new mrs_loopback_group();
   g->world = world;
   g->send.assign((size_t)world, nullptr);
-  g->ev_ready.assign((size_t)world, nullptr);
-  g->ev_copied.assign((size_t)world, nullptr);
-  g->device.assign((size_t)world, -1);
+  g->ev_ready.resize((size_t)world);
+  g->ev_copied.resize((size_t)world);
   g->seq.reset(new std::atomic<unsigned>[(size_t)world]);
   for (int q = 0; q < world; q++) g->seq[(size_t)q].store(0u);
   for (int par = 0; par < 2; par++) {
-    g->stage[par].assign((size_t)world, nullptr);
-    g->stage_cap[par].assign((size_t)world, 0);
-    g->ev_ready2[par].assign((size_t)world, nullptr);
-    g->ev_copied2[par].assign((size_t)world, nullptr);
+    g->stage[par].resize((size_t)world);
+    g->ev_ready2[par].resize((size_t)world);
+    g->ev_copied2[par].resize((size_t)world);
   }
   *out = g;
   return MRS_OK;
@@ -259,18 +250,7 @@ int mrs_loopback_group_set_rendezvous(mrs_loopback_group_t* g, int32_t on) {
 }
 
 int mrs_loopback_group_destroy(mrs_loopback_group_t* g) {
-  if (!g) return MRS_OK;
-  for (int q = 0; q < g->world; q++) {
-    if (g->device[(size_t)q] >= 0) (void)hipSetDevice(g->device[(size_t)q]);
-    if (g->ev_ready[(size_t)q]) (void)hipEventDestroy(g->ev_ready[(size_t)q]);
-    if (g->ev_copied[(size_t)q]) (void)hipEventDestroy(g->ev_copied[(size_t)q]);
-    for (int par = 0; par < 2; par++) {
-      if (g->ev_ready2[par][(size_t)q]) (void)hipEventDestroy(g->ev_ready2[par][(size_t)q]);
-      if (g->ev_copied2[par][(size_t)q]) (void)hipEventDestroy(g->ev_copied2[par][(size_t)q]);
-      if (g->stage[par][(size_t)q]) (void)hipFree(g->stage[par][(size_t)q]);
-    }
-  }
-  delete g;
+  delete g;  // (events and staging blocks of every rank: hipEventDestroy and hipFree find the device of what they are given)
   return MRS_OK;
 }
 
@@ -281,14 +261,13 @@ int mrs_swarm_comm_init_loopback(mrs_swarm_t* s, mrs_loopback_group_t* g, int32_
   if (rc) return rc;
   if (g->ev_ready[(size_t)rank]) return fail(MRS_ERR_ARG, "this rank of the loopback group is taken");
   HIPCHK(hipSetDevice(s->device));
-  HIPCHK(hipEventCreateWithFlags(&g->ev_ready[(size_t)rank], hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&g->ev_copied[(size_t)rank], hipEventDisableTiming));
+  HIPCHK(g->ev_ready[(size_t)rank].create(hipEventDisableTiming));
+  HIPCHK(g->ev_copied[(size_t)rank].create(hipEventDisableTiming));
   for (int par = 0; par < 2; par++) {
-    HIPCHK(hipEventCreateWithFlags(&g->ev_ready2[par][(size_t)rank], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&g->ev_copied2[par][(size_t)rank], hipEventDisableTiming));
+    HIPCHK(g->ev_ready2[par][(size_t)rank].create(hipEventDisableTiming));
+    HIPCHK(g->ev_copied2[par][(size_t)rank].create(hipEventDisableTiming));
     HIPCHK(hipEventRecord(g->ev_copied2[par][(size_t)rank], s->stream));  // (an event that was never recorded must not be waited for)
   }
-  g->device[(size_t)rank] = s->device;
   s->comm_group           = g;
   return comm_buffers(s, g->world, rank, n_total);
 }

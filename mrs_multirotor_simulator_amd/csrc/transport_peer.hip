@@ -119,11 +119,9 @@ int peer_failed(mrs_swarm* s) {
 void peer_release(mrs_swarm* s) {
   for (void* p : s->peer_opened) (void)hipIpcCloseMemHandle(p);
   s->peer_opened.clear();
-  if (s->peer_window) (void)hipFree(s->peer_window);
-  if (s->peer_ticket) (void)hipFree(s->peer_ticket);
-  if (s->peer_err) (void)hipHostFree(s->peer_err);
-  s->peer_window = nullptr;
-  s->peer_ticket = s->peer_err = nullptr;
+  s->peer_window.reset();
+  s->peer_ticket.reset();
+  s->peer_err.reset();
   s->peer_world  = 0;
   s->comm_peer   = false;
 }
@@ -159,12 +157,12 @@ int mrs_swarm_peer_window_create(mrs_swarm_t* s, int32_t world, int32_t rank, in
     }
   } release{s};
   const char* kind = getenv("MRS_PEER_WINDOW_MEMORY");
-  if (kind && strcmp(kind, "coarse") == 0)
-    HIPCHK(hipMalloc(&s->peer_window, s->peer_window_bytes));
-  else
-    HIPCHK(hipExtMallocWithFlags(&s->peer_window, s->peer_window_bytes, kind && strcmp(kind, "finegrained") == 0 ? hipDeviceMallocFinegrained : hipDeviceMallocUncached));
-  HIPCHK(hipMalloc((void**)&s->peer_ticket, sizeof(unsigned) * (MRS_MAX_PEERS + 1)));  // (+ the give-up mark the exchange kernels read)
-  HIPCHK(hipHostMalloc((void**)&s->peer_err, 64, hipHostMallocMapped));
+  static_assert(hipDeviceMallocDefault == 0, "DevBuf::alloc: kind 0 is plain hipMalloc");
+  HIPCHK(s->peer_window.alloc(s->peer_window_bytes, kind && strcmp(kind, "coarse") == 0        ? hipDeviceMallocDefault
+                                                    : kind && strcmp(kind, "finegrained") == 0 ? hipDeviceMallocFinegrained
+                                                                                               : hipDeviceMallocUncached));
+  HIPCHK(s->peer_ticket.alloc(MRS_MAX_PEERS + 1));  // (+ the give-up mark the exchange kernels read)
+  HIPCHK(s->peer_err.alloc(16, hipHostMallocMapped));
   *s->peer_err = 0u;
   HIPCHK(hipMemsetAsync(s->peer_window, 0, 4096, s->stream));  // flags: no collective has happened
   HIPCHK(hipMemsetAsync(s->peer_ticket, 0, sizeof(unsigned) * (MRS_MAX_PEERS + 1), s->stream));

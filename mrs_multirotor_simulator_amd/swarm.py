@@ -185,6 +185,14 @@ def debug_pid_sequences(arith, params, err, dt, event, new_sat, device=-1):
     return out
 
 
+def debug_live_resources():
+    """(device buffers, pinned blocks, events, streams) the library holds in this process right now (debugging aid, not in the header)."""
+    load_library()
+    out = (C.c_int64 * 4)()
+    _check(_lib.mrs_debug_live_resources(out))
+    return tuple(out)
+
+
 def rccl_unique_id(librccl_path=None):
     """128-byte communicator id, created on rank 0 and handed to the other ranks over any host channel."""
     load_library()
@@ -315,6 +323,7 @@ def load_library():
         "mrs_swarm_get_fused_stats": [vp] + [C.POINTER(C.c_int64)] * 4,
         "mrs_swarm_debug_component": [vp, i32, i32, i32, dp, i32, dp, i32, f64],
         "mrs_debug_pid_update": [i32, i32, i32, dp, dp, dp, dp, dp],
+        "mrs_debug_live_resources": [C.POINTER(C.c_int64)],
         "mrs_swarm_set_state_pos": [vp, i32, i32, dp, dp],
         "mrs_swarm_set_pid": [vp, i32, i32, dp],
         "mrs_swarm_clone": [vp, C.POINTER(vp)],

@@ -822,6 +822,17 @@ public:
     mrs_throw_on_error(mrs_swarm_rollout_tick_device(s_, first, count, mode, dt, n_ticks, cmd_every, obs_every, dev_cmd, dtype, cmd_stride, groups,
                                                      dev_obs, obs_stride, dev_crashed, crash ? 1 : 0, rebounce, stream));
   }
+  // rolloutTickDevice that returns one FP64 number per UAV instead of row blocks: after every cost_every ticks, between the tick's step
+  // and its collision pass, the term of rolloutCostDevice is added to dev_cost[k] (groups 0 with null dev_target / dev_weight: no
+  // term), and then crash_cost if the UAV has crashed (a level: paid at every evaluation from the crash on).  No row is written.
+  void rolloutTickCostDevice(int first, int count, int mode, double dt, int n_ticks, int cmd_every, int cost_every, const void* dev_cmd, int dtype,
+                             int cmd_stride, uint32_t groups, const void* dev_target, int target_stride, const void* dev_weight,
+                             int weight_stride, double crash_cost, double* dev_cost, bool accumulate, bool crash, double rebounce,
+                             void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_rollout_tick_cost_device(s_, first, count, mode, dt, n_ticks, cmd_every, cost_every, dev_cmd, dtype, cmd_stride,
+                                                          groups, dev_target, target_stride, dev_weight, weight_stride, crash_cost, dev_cost,
+                                                          accumulate ? 1 : 0, crash ? 1 : 0, rebounce, stream));
+  }
   // rolloutCostDevice whose command rows are nominal commands: at the start of command block b the command of UAV first + k is
   // cmd row (b, k) + G (ref row (b, k) - the FP64 observation row of fb_groups before the step), formed in the step kernel.  dev_gain:
   // gain_per_uav false: dense [gain_blocks, W_c, W_o]; true: dense [gain_blocks, W_c, W_o, count], UAV-minor.  dev_ref: rows as the

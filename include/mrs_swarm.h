@@ -775,6 +775,54 @@ int mrs_swarm_rollout_tick_device(mrs_swarm_t* s, int32_t first, int32_t count, 
                                   int32_t obs_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs,
                                   int32_t obs_stride, uint8_t* dev_crashed, int32_t crash, double rebounce, void* ext_stream);
 
+/* ---- cost tick rollouts: a per-UAV cost with a crash penalty, summed inside a tick rollout ----
+ * mrs_swarm_rollout_tick_device that returns one FP64 number per UAV instead of row blocks: the horizon cost of a swarm policy or a
+ * multi-agent planner with the contacts of timerMain in it (src/multirotor_simulator.cpp:211-217, handleCollisions :295-359), and with the
+ * crash flag, the one thing a collision-aware horizon produces that the state rows do not show, as a cost.  Stands for the loop of
+ * mrs_swarm_rollout_tick_device with obs_every = cost_every, FP64 rows of `groups` (MRS_DTYPE_F64) and crash rows,
+ *   for t in [0, n_ticks):
+ *     if (t % cmd_every == 0)
+ *       mrs_swarm_set_input_device(s, first, count, mode, row block t / cmd_every of dev_cmd, dtype, cmd_stride, ext_stream);
+ *     mrs_swarm_step(s, dt);              evaluates the collision tick pending from tick t - 1
+ *     if ((t + 1) % cost_every == 0) {    j = (t + 1) / cost_every - 1
+ *       if (groups) rows[j] = mrs_swarm_gather_device(s, first, count, groups, ..., MRS_DTYPE_F64, ...);
+ *       crashed[j] = mrs_swarm_get_crashed_device(s, first, count, ...);
+ *     }
+ *     mrs_swarm_handle_collisions(s, 1, crash, rebounce);    stays pending
+ * followed, with E = n_ticks / cost_every evaluations and w = the gather width of `groups`, for every UAV first + k by
+ *   c = accumulate ? dev_cost[k] : +0.0
+ *   for j in [0, E):
+ *     if (groups) {
+ *       term = +0.0
+ *       for col in [0, w):                         (ascending, no column skipped)
+ *         d    = rows[j][k][col] - target[j][k or 0][col]
+ *         term = term + (weight[j or 0][col] * d) * d
+ *       c = c + term
+ *     }
+ *     if (crashed[j][k]) c = c + crash_cost
+ *   dev_cost[k] = c
+ * All of it is FP64, one rounding per operation and no fused multiply-add, in both arithmetic flavours; targets and weights have the
+ * commands' dtype (FP32 is widened exactly); nothing is special-cased.  The term and the crash cost are two separately rounded
+ * additions, in that order, and the crash add is performed whenever the byte is set, whatever crash_cost is (0, negative, non-finite).
+ * crashed[j][k] is UavSystem::hasCrashed where the tick rollout takes its crash rows: after the tick's makeStep, before that tick's
+ * handleCollisions.  It is a level, not an edge: a UAV that crashed early pays at every later evaluation; a crash caused by the last
+ * tick's collision pass stays pending with that pass, is not charged by this call, and is charged by the next horizon (accumulate != 0
+ * chains the two).  Target and weight layouts, target_stride == 0 and weight_stride == 0 are those of mrs_swarm_rollout_cost_device.
+ * groups == 0 with dev_target and dev_weight NULL is the crash cost alone.  No observation row and no crash byte is written.
+ * Everything else is the contract of mrs_swarm_rollout_tick_device: the entry (a collision tick pending at entry is evaluated by the
+ * first launch), the last tick's collision staying pending, ONE host wait and ONE stream fence per call, UAVs on hold (they take part in
+ * the collisions, are not iterated, get their command rows, and add one term of their unchanged state per evaluation plus the crash cost
+ * if their flag is set), crashed UAVs, UAVs outside the range (they own no element of dev_cost), and the refusal on a sharded swarm.
+ * Every argument is checked before anything is launched and a refused call changes nothing: the refusals of
+ * mrs_swarm_rollout_tick_device and of mrs_swarm_rollout_cost_device, except that groups == 0 is refused only when a dev_target or
+ * dev_weight comes with it; groups != 0 with a NULL dev_target or dev_weight, a dev_cost that is NULL or shorter than count doubles,
+ * cost_every < 1 or not dividing n_ticks, and a rebounce that is not finite are refused. */
+int mrs_swarm_rollout_tick_cost_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_ticks,
+                                       int32_t cmd_every, int32_t cost_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride,
+                                       uint32_t groups, const void* dev_target, int32_t target_stride, const void* dev_weight,
+                                       int32_t weight_stride, double crash_cost, double* dev_cost, int32_t accumulate, int32_t crash,
+                                       double rebounce, void* ext_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,14 @@ __global__ void __launch_bounds__(256) k_crashed_u8(const uint32_t* F, int first
   out[k] = (F[first + k] & FLAG_CRASHED) ? 1 : 0;
 }
 
+// the crash add of a cost tick rollout's evaluation (mrs_swarm_rollout_tick_cost_device) for a tick without the fused form: one FP64
+// addition per crashed UAV of the range, behind the term the cost rollout kernels added, performed whatever crash_cost is
+__global__ void __launch_bounds__(256) k_crash_cost(const uint32_t* F, int first, int count, double* cost, double crash_cost) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  if (F[first + k] & FLAG_CRASHED) cost[k] = cost[k] + crash_cost;
+}
+
 inline dim3 grid_of(int count) { return dim3((unsigned)((count + 255) / 256)); }
 
 // payload elements of a command row of `mode`: the widths of mrs_swarm_set_input (ACTUATOR: the row's stride, at most MRS_MAX_MOTORS)
@@ -199,6 +207,12 @@ int fence_out(mrs_swarm* s, hipStream_t ext) {
 
 int launch_crashed_u8(mrs_swarm* s, int first, int count, uint8_t* dev_out) {
   hipLaunchKernelGGL(k_crashed_u8, grid_of(count), dim3(256), 0, s->stream, s->dF, first, count, dev_out);
+  HIPCHK(hipGetLastError());
+  return MRS_OK;
+}
+
+int launch_crash_cost(mrs_swarm* s, int first, int count, double* dev_cost, double crash_cost) {
+  hipLaunchKernelGGL(k_crash_cost, grid_of(count), dim3(256), 0, s->stream, s->dF, first, count, dev_cost, crash_cost);
   HIPCHK(hipGetLastError());
   return MRS_OK;
 }
@@ -348,16 +362,16 @@ int mrs_swarm_apply_force_device(mrs_swarm_t* s, int32_t first, int32_t count, c
 
 // Every argument of the rollout entry points as one record; a call leaves what it does not have at zero.  `kind` is the entry point:
 // it decides which of the optional parts are checked and which kernel family runs.
-enum RolloutKind { ROLLOUT_ROWS, ROLLOUT_FORCE, ROLLOUT_COST, ROLLOUT_FEEDBACK, ROLLOUT_TICK };
+enum RolloutKind { ROLLOUT_ROWS, ROLLOUT_FORCE, ROLLOUT_COST, ROLLOUT_FEEDBACK, ROLLOUT_TICK, ROLLOUT_TICK_COST };
 struct RolloutArgs {
   const char* who;
   RolloutKind kind;
   int32_t     first, count, mode;
   double      dt;
-  int32_t     n_steps, cmd_every, obs_every;  // (n_ticks of a tick rollout; cost_every of a cost or feedback rollout)
+  int32_t     n_steps, cmd_every, obs_every;  // (n_ticks of a tick rollout; cost_every of a cost, feedback or cost tick rollout)
   const void* dev_cmd;
   int32_t     dtype, cmd_stride;
-  uint32_t    groups;  // of the observation rows, or of the cost (a feedback rollout's may be 0: no cost)
+  uint32_t    groups;  // of the observation rows, or of the cost (a feedback rollout's may be 0: no cost; a cost tick rollout's: crash cost only)
   void*       dev_obs;
   int32_t     obs_stride;
   void*       ext_stream;
@@ -378,7 +392,7 @@ struct RolloutArgs {
   int32_t     gain_per_uav, gain_blocks;
   const void* ref;
   int32_t     ref_stride, ref_blocks;
-  // mrs_swarm_rollout_tick_device
+  // mrs_swarm_rollout_tick_device, mrs_swarm_rollout_tick_cost_device (which has no dev_crashed)
   uint8_t*    dev_crashed;
   int32_t     crash;
   double      rebounce;
@@ -393,7 +407,8 @@ struct RolloutWidths {
 // The argument checks of every rollout entry point, in the order in which a call with several faults reports them.  `steps` and `every`
 // are the nouns of the messages: n_steps or n_ticks, obs_every or cost_every.  Nothing is launched and nothing is changed here.
 static int check_rollout_args(mrs_swarm_t* s, const RolloutArgs& a, const std::string& steps, const std::string& every, RolloutWidths& w) {
-  const bool forced = a.kind == ROLLOUT_FORCE, fb = a.kind == ROLLOUT_FEEDBACK, cost = fb || a.kind == ROLLOUT_COST;
+  const bool forced = a.kind == ROLLOUT_FORCE, fb = a.kind == ROLLOUT_FEEDBACK, tc = a.kind == ROLLOUT_TICK_COST;
+  const bool cost   = fb || tc || a.kind == ROLLOUT_COST;
   int        rc     = check_range(s, a.first, a.count);
   if (rc) return rc;
   if (s->comm_world > 0) return fail(MRS_ERR_ARG, std::string(a.who) + ": not on a sharded swarm");
@@ -427,9 +442,13 @@ static int check_rollout_args(mrs_swarm_t* s, const RolloutArgs& a, const std::s
     if (!w.costed && (a.target || a.weight || a.cost)) return fail(MRS_ERR_ARG, "cost_groups == 0 takes no dev_target, dev_weight or dev_cost");
   }
   if (w.costed) {
-    if (a.groups == 0u) return fail(MRS_ERR_ARG, "no observation group selected: a cost needs columns");
-    if (!a.target) return fail(MRS_ERR_ARG, "dev_target: null pointer");
-    if (!a.weight) return fail(MRS_ERR_ARG, "dev_weight: null pointer");
+    if (tc && a.groups == 0u) {  // the crash cost alone
+      if (a.target || a.weight) return fail(MRS_ERR_ARG, "groups == 0 (the crash cost alone) takes no dev_target or dev_weight");
+    } else {
+      if (a.groups == 0u) return fail(MRS_ERR_ARG, "no observation group selected: a cost needs columns");
+      if (!a.target) return fail(MRS_ERR_ARG, "dev_target: null pointer");
+      if (!a.weight) return fail(MRS_ERR_ARG, "dev_weight: null pointer");
+    }
     if (!a.cost) return fail(MRS_ERR_ARG, "dev_cost: null pointer");
     if (a.target_stride != 0 && a.target_stride < w.obs)
       return fail(MRS_ERR_ARG, "target_stride must be 0 (shared rows) or at least the width of the selected groups");
@@ -454,8 +473,8 @@ static int check_rollout_args(mrs_swarm_t* s, const RolloutArgs& a, const std::s
     const size_t evals = (size_t)(a.n_steps / a.obs_every), ow = (size_t)w.obs;
     const size_t tgt   = a.target_stride ? (obs_rows - 1) * (size_t)a.target_stride + ow : evals * ow;
     const size_t wt    = a.weight_stride ? (evals - 1) * (size_t)a.weight_stride + ow : ow;
-    if ((rc = check_device_ptr(s, a.target, tgt * elem, "dev_target"))) return rc;
-    if ((rc = check_device_ptr(s, a.weight, wt * elem, "dev_weight"))) return rc;
+    if (a.groups != 0u && (rc = check_device_ptr(s, a.target, tgt * elem, "dev_target"))) return rc;
+    if (a.groups != 0u && (rc = check_device_ptr(s, a.weight, wt * elem, "dev_weight"))) return rc;
     if ((rc = check_device_ptr(s, a.cost, count * sizeof(double), "dev_cost"))) return rc;
   }
   if (forced) {
@@ -645,6 +664,67 @@ int mrs_swarm_rollout_tick_device(mrs_swarm_t* s, int32_t first, int32_t count, 
   }
   // a replay after a stall writes into the caller's rows, which are only guaranteed to live until the call returns: nothing of this
   // call stays in the log (one host wait per call); the last tick's collision stays pending
+  if ((rc = drain(s))) return rc;
+  if ((rc = finish_profile(s))) return rc;
+  return fence_out(s, ext);
+}
+
+// mrs_swarm_rollout_tick_device whose ticks carry an evaluation in place of row blocks: the same loop of step_one and pending
+// collision ticks, the same single drain.  dev_cost is zeroed once on the swarm's stream, behind the entry fence and in front of the
+// first launch, unless the call accumulates; the memset is not part of the launch log, so a replay after a stall does not repeat it,
+// and the replayed launches add what their no-ops did not.
+int mrs_swarm_rollout_tick_cost_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_ticks, int32_t cmd_every,
+                                       int32_t cost_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t groups,
+                                       const void* dev_target, int32_t target_stride, const void* dev_weight, int32_t weight_stride,
+                                       double crash_cost, double* dev_cost, int32_t accumulate, int32_t crash, double rebounce, void* ext_stream) {
+  MRS_LOCK(s);
+  RolloutArgs a{"mrs_swarm_rollout_tick_cost_device", ROLLOUT_TICK_COST, first, count, mode, dt, n_ticks, cmd_every, cost_every, dev_cmd, dtype, cmd_stride,
+                groups, nullptr, 0, ext_stream};
+  a.target = dev_target, a.target_stride = target_stride, a.weight = dev_weight, a.weight_stride = weight_stride;
+  a.cost = dev_cost, a.accumulate = accumulate;
+  a.crash = crash, a.rebounce = rebounce;
+  RolloutWidths w;
+  int           rc = check_rollout_args(s, a, "n_ticks", "cost_every", w);
+  if (rc) return rc;
+  const int    width = w.cmd;
+  const size_t elem  = dtype_bytes(dtype);
+  if (s->n == 0) return MRS_OK;
+  HIPCHK(hipSetDevice(s->device));
+  if (!s->log.empty() && (rc = drain(s))) return rc;  // (as mrs_swarm_rollout_tick_device: a collision tick pending at entry stays pending)
+  if ((rc = upload_types(s, dt))) return rc;
+  rollout_track_mode(s, a);
+  hipStream_t ext = (hipStream_t)ext_stream;
+  if ((rc = fence_in(s, ext))) return rc;
+  if ((rc = begin_profile(s))) return rc;
+  if (count > 0 && !accumulate) HIPCHK(hipMemsetAsync(dev_cost, 0, (size_t)count * sizeof(double), s->stream));  // (+0.0)
+  RolloutTickCostDev c{};
+  c.first = first, c.count = count;
+  c.cmd_stride = cmd_stride;
+  c.tgt_row = target_stride, c.wt_row = weight_stride, c.width = w.obs;
+  c.cmd_word   = (uint32_t)width | (dtype == MRS_DTYPE_F32 ? 32u : 0u);
+  c.groups     = groups;
+  c.mode_bits  = (uint32_t)mode << FLAG_MODE_SHIFT;
+  c.crash_cost = crash_cost;
+  // elements between two target row blocks: a row per UAV, or one dense row for all
+  const size_t tgt_blk = target_stride ? (size_t)count * (size_t)target_stride : (size_t)w.obs;
+  for (int t = 0; t < n_ticks; t++) {
+    c.cmd = c.target = c.weight = nullptr;
+    c.cost = nullptr;
+    if (count > 0 && width > 0 && t % cmd_every == 0)
+      c.cmd = static_cast<const char*>(dev_cmd) + (size_t)(t / cmd_every) * (size_t)count * (size_t)cmd_stride * elem;
+    if (count > 0 && (t + 1) % cost_every == 0) {
+      const size_t j = (size_t)((t + 1) / cost_every - 1);
+      c.cost = dev_cost;
+      if (groups != 0u) {
+        c.target = static_cast<const char*>(dev_target) + j * tgt_blk * elem;
+        c.weight = static_cast<const char*>(dev_weight) + j * (size_t)weight_stride * elem;
+      }
+    }
+    if ((rc = step_one(s, dt, nullptr, &c))) return rc;
+    if ((rc = mrs_swarm_handle_collisions(s, 1, crash, rebounce))) return rc;
+  }
+  // nothing of this call stays in the log: a replay adds to the caller's vector and reads the caller's rows, which are only guaranteed
+  // to live until the call returns (one host wait per call); the last tick's collision stays pending
   if ((rc = drain(s))) return rc;
   if ((rc = finish_profile(s))) return rc;
   return fence_out(s, ext);

@@ -59,6 +59,8 @@ extern "C" hipError_t mrs_launch_rollout_cost_fast(SwarmDev sw, RolloutCostDev r
                                                      hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_tick_literal(SwarmDev sw, CollDev cd, RolloutTickDev r, double dt, int variant, hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_tick_fast(SwarmDev sw, CollDev cd, RolloutTickDev r, double dt, int variant, hipStream_t st);
+extern "C" hipError_t mrs_launch_rollout_tick_cost_literal(SwarmDev sw, CollDev cd, RolloutTickCostDev r, double dt, int variant, hipStream_t st);
+extern "C" hipError_t mrs_launch_rollout_tick_cost_fast(SwarmDev sw, CollDev cd, RolloutTickCostDev r, double dt, int variant, hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_feedback_literal(SwarmDev sw, RolloutFeedbackDev r, double dt, int n_steps, int cmd_every, int cost_every,
                                                             int variant, hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_feedback_fast(SwarmDev sw, RolloutFeedbackDev r, double dt, int n_steps, int cmd_every, int cost_every,
@@ -323,6 +325,8 @@ struct mrs_swarm {
   // two per kind can still hold their slot, so four entries are enough (the _async call drops those whose slot has been recycled).
   // rows: the launch is one tick of mrs_swarm_rollout_tick_device and `row` names the caller's row blocks of that tick — a replay
   // writes into them what the no-op launch did not (the call drains the log before it returns: the rows live that long).
+  // cost: the launch is one tick of mrs_swarm_rollout_tick_cost_device and `cost` names that tick's command block and evaluation — a
+  // replay adds to the caller's cost vector what the no-op launch did not (it never got as far as the vector).
   struct PackRef { int32_t kind, ticket; };
   struct TickRec {
     double  dt;
@@ -333,6 +337,8 @@ struct mrs_swarm {
     PackRef packs[2 * PAYLOAD_KINDS] = {};
     bool           rows = false;
     RolloutTickDev row{};
+    bool               costed = false;
+    RolloutTickCostDev cost{};
   };
   Collide              pend;                        // requested after the most recent step, not evaluated yet
   // A fused launch consumes the force it evaluates from registers and does not write the F_ext columns (24 B per UAV and tick).
@@ -431,7 +437,8 @@ int  begin_profile(mrs_swarm* s);
 int  finish_profile(mrs_swarm* s);
 int  collide_now(mrs_swarm* s, const mrs_swarm::Collide& c, bool force);
 int  wait_for_progress(mrs_swarm* s, const volatile unsigned* hw, unsigned index, int lead);
-int  step_one(mrs_swarm* s, double dt, const RolloutTickDev* row = nullptr);  // row: the tick's caller rows (mrs_swarm_rollout_tick_device)
+// row: the tick's caller rows (mrs_swarm_rollout_tick_device); cost: the tick's evaluation (mrs_swarm_rollout_tick_cost_device); not both
+int  step_one(mrs_swarm* s, double dt, const RolloutTickDev* row = nullptr, const RolloutTickCostDev* cost = nullptr);
 int  drain(mrs_swarm* s);
 // the slot of `kind` that still holds the download `ticket` (nullptr: a ticket of the other kind, or its slot has been recycled)
 inline mrs_swarm::OutSlot* held_slot(mrs_swarm* s, int kind, int32_t ticket) {
@@ -451,6 +458,7 @@ size_t rows_bytes(int count, int stride, int width, int dtype);
 int    fence_in(mrs_swarm* s, hipStream_t ext);
 int    fence_out(mrs_swarm* s, hipStream_t ext);
 int    launch_crashed_u8(mrs_swarm* s, int first, int count, uint8_t* dev_out);  // hasCrashed of a range as bytes, on the swarm's stream
+int    launch_crash_cost(mrs_swarm* s, int first, int count, double* dev_cost, double crash_cost);  // cost[k] += crash_cost where crashed
 // ---- transports (transport_*.hip) and the communicator bookkeeping (tick_sharded.hip) ----
 int  rccl_load(const char* path);
 int  rccl_check(int rc, const char* what);

@@ -243,6 +243,28 @@ struct RolloutTickDev {
   int32_t     _pad;
 };
 
+// ---- ONE tick of a cost tick rollout (mrs_swarm_rollout_tick_cost_device, rollout_tick_cost_device.inc) ----
+// RolloutTickDev's command side, and in place of row blocks the evaluation that ends with this tick: the observation row of UAV first + k
+// is compared with its target row under the weight row, the term is added to cost[k], and crash_cost is added behind it when the UAV's
+// crash flag is set.  The host works out the pointers of each tick: no schedule words.  The descriptor travels with the launch's record
+// in the stall / replay log: a replayed launch adds what its no-op did not.
+struct RolloutTickCostDev {
+  const void* cmd;         // the command row block that starts at this tick (row k at element k * cmd_stride), or null: none starts
+  const void* target;      // the target row block of the evaluation that ends with this tick (row k at element k * tgt_row), or null
+  const void* weight;      // its weight row, or null
+  double*     cost;        // cost[k]: the running sum of UAV first + k, or null: no evaluation ends with this tick
+  int32_t     first, count;
+  int32_t     cmd_stride;
+  int32_t     tgt_row;     // target_stride, or 0: all UAVs share the target row
+  int32_t     wt_row;      // weight_stride, or 0: one weight row for every evaluation (the host's: the kernels read `weight` as it is)
+  int32_t     width;       // elements of a row of `groups` (the host's)
+  uint32_t    cmd_word;    // payload width | rows are FP32 << 5 (commands, targets and weights)
+  uint32_t    groups;      // MRS_OBS_* of the cost; 0: the crash add alone (target and weight null)
+  uint32_t    mode_bits;   // input mode << FLAG_MODE_SHIFT
+  int32_t     _pad;
+  double      crash_cost;
+};
+
 // 48-byte record exchanged for the collision pass (single- and multi-GPU): everything
 // MultirotorSimulator::handleCollisions reads of the partner UAV (src/multirotor_simulator.cpp:339-350)
 struct PosRecord {

@@ -192,6 +192,31 @@ int launch_row_step(mrs_swarm* s, double dt, const RolloutTickDev& row) {
   return MRS_OK;
 }
 
+// One tick of mrs_swarm_rollout_tick_cost_device without the fused form, as launch_row_step: one step of the cost rollout kernels with
+// this tick's command block and evaluation (the term), then the crash add of an evaluation that ends here.  The two adds round as the
+// fused launch's do, so the cost equals the fused launch's bit for bit.
+int launch_cost_step(mrs_swarm* s, double dt, const RolloutTickCostDev& c) {
+  s->region_launches++;
+  RolloutCostDev r{};
+  r.cmd = c.cmd;
+  r.first = c.first, r.count = c.count;
+  r.cmd_stride = c.cmd_stride;
+  r.cmd_sched  = (c.cmd ? c.cmd_word : (c.cmd_word & 32u)) << 24;  // (width 0: no command block starts at this tick)
+  r.cost_sched = (c.cost && c.groups != 0u) ? c.groups << 24 : 0u;  // (groups 0: no evaluation ends here, or the crash add alone)
+  r.mode_bits  = c.mode_bits;
+  if (r.cost_sched != 0u) {
+    r.target = c.target, r.weight = c.weight, r.cost = c.cost;
+    r.tgt_row = c.tgt_row, r.tgt_blk = 0, r.wt_row = 0;  // (one evaluation: the block and weight-row distances are never used)
+  }
+  const int variant = s->n_cascade > 0 ? 0 : 1;
+  if (s->arith == MRS_ARITH_FAST)
+    HIPCHK(mrs_launch_rollout_cost_fast(s->view(), r, dt, 1, 1, 1, variant, s->stream));
+  else
+    HIPCHK(mrs_launch_rollout_cost_literal(s->view(), r, dt, 1, 1, 1, variant, s->stream));
+  if (c.cost && c.count > 0) return launch_crash_cost(s, c.first, c.count, c.cost, c.crash_cost);
+  return MRS_OK;
+}
+
 // one fused launch: evaluate collision tick `e.eval` (if any) from the lists, then makeStep(e.dt)
 int launch_fused(mrs_swarm* s, const mrs_swarm::TickRec& e) {
   const volatile unsigned* hw = mrs_collide_host_words(s->cwork);
@@ -219,6 +244,11 @@ int launch_fused(mrs_swarm* s, const mrs_swarm::TickRec& e) {
       HIPCHK(mrs_launch_rollout_tick_fast(v, cd, e.row, e.dt, variant, s->stream));
     else
       HIPCHK(mrs_launch_rollout_tick_literal(v, cd, e.row, e.dt, variant, s->stream));
+  } else if (e.costed) {  // a tick of mrs_swarm_rollout_tick_cost_device: the same launch with this tick's evaluation
+    if (s->arith == MRS_ARITH_FAST)
+      HIPCHK(mrs_launch_rollout_tick_cost_fast(v, cd, e.cost, e.dt, variant, s->stream));
+    else
+      HIPCHK(mrs_launch_rollout_tick_cost_literal(v, cd, e.cost, e.dt, variant, s->stream));
   } else if (s->arith == MRS_ARITH_FAST)
     HIPCHK(mrs_launch_step_coll_fast(v, cd, e.dt, variant, 0, s->stream));
   else
@@ -292,9 +322,9 @@ int drain(mrs_swarm* s) {
       } else {  // (lists incomplete: dense neighbourhoods) every tick on its own
         if (e.eval.on && (rc = collide_now(s, e.eval, false))) return rc;
         s->p_valid = false;
-        if (e.rows) {
+        if (e.rows || e.costed) {
           if (e.dt != s->table_dt && (rc = upload_types(s, e.dt))) return rc;
-          if ((rc = launch_row_step(s, e.dt, e.row))) return rc;
+          if ((rc = e.rows ? launch_row_step(s, e.dt, e.row) : launch_cost_step(s, e.dt, e.cost))) return rc;
         } else {
           s->region_launches++;
           if ((rc = launch_part(s, e.dt, 1, 0, (s->n + 63) / 64, 1, s->stream))) return rc;
@@ -332,7 +362,7 @@ int settle(mrs_swarm* s) {
 }
 
 // one makeStep of every UAV; the collision tick requested since the previous step (if any) is evaluated by the same launch
-int step_one(mrs_swarm* s, double dt, const RolloutTickDev* row) {
+int step_one(mrs_swarm* s, double dt, const RolloutTickDev* row, const RolloutTickCostDev* cost) {
   int rc;
   if (s->collide_since_step && s->use_lists && s->use_fused) {
     const volatile unsigned* hw = mrs_collide_host_words(s->cwork);
@@ -343,6 +373,7 @@ int step_one(mrs_swarm* s, double dt, const RolloutTickDev* row) {
     if (fused_usable(s)) {
       mrs_swarm::TickRec e{dt, s->pend, false};
       if (row) e.rows = true, e.row = *row;
+      if (cost) e.costed = true, e.cost = *cost;
       if (s->pend.on && hw && hw[CTL_WARN] > s->search_mark) {
         // some UAV has used up most of its skin: repeat the search NOW, in stream order — it evaluates the pending collision tick
         // itself — instead of running into the stall a few ticks on (no synchronisation, nothing to replay)
@@ -361,6 +392,7 @@ int step_one(mrs_swarm* s, double dt, const RolloutTickDev* row) {
   s->collide_since_step = false;
   s->p_valid            = false;  // a plain step kernel does not refresh the position records
   if (row) return launch_row_step(s, dt, *row);
+  if (cost) return launch_cost_step(s, dt, *cost);
   return launch_step(s, dt, 1);
 }
 

@@ -312,6 +312,63 @@ def rollout_ticks(swarm, mode, commands, dt, crash, rebounce, groups=OBS_POS | O
     return rows, crashed
 
 
+def rollout_tick_cost(swarm, mode, commands, dt, crash, rebounce, groups, targets, weights, crash_cost=0.0, first=0, hold=1, cost_every=None,
+                      out=None, accumulate=False):
+    """rollout_ticks(hold=hold, obs_every=cost_every) that returns one FP64 number per UAV instead of row blocks
+    (mrs_swarm_rollout_tick_cost_device): after every `cost_every` ticks (default: `hold`), between the tick's step and its collision
+    pass, the term of rollout_cost (the FP64 row of `groups` against its target row under the weight row) is added to the UAV's cost,
+    and then `crash_cost` if the UAV has crashed — two separately rounded FP64 additions, in that order.  The crash flag is a level: a
+    UAV that crashed early pays at every later evaluation; a crash caused by the last tick's collision pass stays pending with it and is
+    charged by the next horizon.  commands, targets, weights, out, accumulate: as in rollout_cost.  groups == 0 (then targets and
+    weights stay None) is the crash cost alone.  Returns out.  No observation row and no crash byte is written; the collision pass of
+    the last tick stays pending."""
+    dev = swarm.device()
+    if not isinstance(commands, torch.Tensor) or commands.dim() != 3:
+        raise ValueError("commands must be a [T, count, width] tensor")
+    hold = int(hold)
+    if hold < 1:
+        raise ValueError(f"hold must be at least 1, got {hold}")
+    code = _dtype_code(commands.dtype)
+    blocks, count = commands.shape[0], commands.shape[1]
+    ticks = blocks * hold
+    every = hold if cost_every is None else int(cost_every)
+    if every < 1 or ticks % every != 0:
+        raise ValueError(f"cost_every must be at least 1 and divide the {ticks} ticks of the call, got {every}")
+    evals = ticks // every
+    width = command_width(mode, commands.shape[2])
+    cstride = _check_steps(commands, "commands", None, count, width, commands.dtype, dev)
+    if mode == ACTUATOR_CMD and count > 1 and cstride != commands.shape[2]:
+        raise ValueError("actuator rows must be dense (row stride == number of motors)")
+    w = gather_width(groups)
+    tptr, tstride, wptr, wstride = 0, 0, 0, 0
+    if w == 0:
+        if targets is not None or weights is not None:
+            raise ValueError("groups == 0 is the crash cost alone: it takes no targets and no weights")
+    else:
+        for name, t in (("targets", targets), ("weights", weights)):
+            if isinstance(t, torch.Tensor) and t.dtype != commands.dtype:
+                raise ValueError(f"{name} has dtype {t.dtype}, the commands {commands.dtype}: one dtype serves commands, targets and weights")
+        tstride = _row_blocks(targets, "targets", evals, count, w, commands.dtype, dev)
+        if not isinstance(weights, torch.Tensor) or weights.dim() != 2 or weights.shape[0] not in (1, evals):
+            raise ValueError(f"weights: expected a [{evals} or 1, >= {w}] tensor, got "
+                             f"{tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights).__name__}")
+        wstride = check_tensor(weights, weights.shape[0], w, commands.dtype, dev)
+        if weights.shape[0] == 1:
+            wstride = 0
+        tptr, wptr = targets.data_ptr(), weights.data_ptr()
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs the `out` vector it adds to")
+        out = torch.empty(count, dtype=torch.float64, device=torch.device("cuda", dev))
+    if isinstance(out, torch.Tensor) and out.dtype != torch.float64:
+        raise ValueError(f"out has dtype {out.dtype}: the cost vector is always torch.float64")
+    check_tensor(out, count, None, torch.float64, dev)
+    cptr = commands.data_ptr() if width > 0 and count > 0 else 0
+    swarm.rollout_tick_cost_device(first, count, mode, dt, ticks, hold, every, cptr, code, cstride, groups, tptr, tstride, wptr, wstride,
+                                   float(crash_cost), out.data_ptr(), bool(accumulate), bool(crash), float(rebounce), _stream(dev))
+    return out
+
+
 def _check_crash_rows(t, blocks, rows, device_index):
     """Refuse `t` unless it is a dense [blocks, rows] torch.bool / torch.uint8 tensor on cuda:`device_index` (block j at byte j * rows)."""
     if not isinstance(t, torch.Tensor):

@@ -52,7 +52,13 @@ that ends in a synchronisation of the device:
   bare     tick_n(dt, T, True, False, 100.0), then synchronize: no commands, no rows              (the floor)
 and prints us per tick (median, min-max), the bytes of rows per tick, and whether the call beats the loop in every round.  In LITERAL
 `tick` and `loop` must end bit-identical (rows, crash bytes and state): the tool asserts it.  The fifth argument selects among
-tick,loop,bare (e.g. `bare` alone, with MRS_SWARM_LIB naming the library of another commit).
+tick,loop,bare,cost,rows64 (e.g. `bare` alone, with MRS_SWARM_LIB naming the library of another commit).  The last two are not in the
+default; they measure the COST tick rollout (mrs_swarm_rollout_tick_cost_device) against what a caller did without it:
+  cost     tensors.rollout_tick_cost(cmd, dt, False, 100.0, POS | VEL | QUAT, targets [E, 1, 10], weights [1, 10], 1000.0, hold=hold,
+           cost_every=hold, out=)                                                                (one call, 8 B per UAV come back)
+  rows64   tensors.rollout_ticks with FP64 rows of the same groups and crash rows every `hold` ticks (FP64 commands: one dtype serves
+           both), then the torch reduction ((w * d) * d).sum over columns and evaluations + crash_cost * crashed.sum to one number per UAV
+With both, the two costs of the first run must agree to 1e-9 relative (the reduction sums in another order).
 
     python tools/rollout_rate.py --ticks [sizes=100000] [T=200] [reps=5] [-] [forms=tick,loop,bare] [arith=fast] [holds=1,10]
 
@@ -397,7 +403,8 @@ def main_ticks(sizes, ticks, reps, arith, holds, forms):
     ow = T.gather_width(groups)
     rng = np.random.default_rng(5)
     rebounce = 100.0
-    assert set(forms) <= {"tick", "loop", "bare"}, forms
+    assert set(forms) <= {"tick", "loop", "bare", "cost", "rows64"}, forms
+    crash_cost = 1000.0
     print(f"tick rollout of T = {ticks} ticks (step + elastic collision pass), POSITION_CMD, FP32 commands and POS|VEL|QUAT rows, x500, "
           f"{arith.upper()}; {reps} rounds after a warm-up, alternating; host clock around a device synchronisation")
     for n in sizes:
@@ -415,14 +422,27 @@ def main_ticks(sizes, ticks, reps, arith, holds, forms):
                     swarms[f] = g
                 dev = torch.device("cuda", swarms[forms[0]].device())
                 cmd = torch.tensor(goal[None] + rng.normal(0.0, 0.05, (ticks // hold, n, 4)), dtype=torch.float32, device=dev)
-                obs = {f: torch.empty((ticks // hold, n, ow), dtype=torch.float32, device=dev) for f in forms if f != "bare"}
-                cr = {f: torch.zeros((ticks // hold, n), dtype=torch.bool, device=dev) for f in forms if f != "bare"}
+                obs = {f: torch.empty((ticks // hold, n, ow), dtype=torch.float64 if f == "rows64" else torch.float32, device=dev)
+                       for f in forms if f not in ("bare", "cost")}
+                cr = {f: torch.zeros((ticks // hold, n), dtype=torch.bool, device=dev) for f in forms if f not in ("bare", "cost")}
+                # the cost forms: one shared target row per evaluation around the goal, one weight row; FP64 twins for the torch reduction
+                tg = torch.tensor(np.concatenate([goal[:1, :3], np.zeros((1, ow - 3))], axis=1)[None] + rng.normal(0.0, 0.5, (ticks // hold, 1, ow)),
+                                  dtype=torch.float32, device=dev)
+                wt = torch.tensor(rng.uniform(0.1, 2.0, (1, ow)), dtype=torch.float32, device=dev)
+                tg64, wt64, cmd64 = tg.double(), wt.double(), cmd.double() if "rows64" in forms else None
+                cost = {f: torch.empty(n, dtype=torch.float64, device=dev) for f in forms if f in ("cost", "rows64")}
 
                 def run(form):
                     g = swarms[form]
                     if form == "tick":
                         T.rollout_ticks(g, M.POSITION_CMD, cmd, DT, False, rebounce, groups, out=obs[form], hold=hold,
                                         crashed=cr[form] if crash_rows else False)
+                    elif form == "cost":
+                        T.rollout_tick_cost(g, M.POSITION_CMD, cmd, DT, False, rebounce, groups, tg, wt, crash_cost, hold=hold, out=cost[form])
+                    elif form == "rows64":  # (the crash rows are part of what the caller needs, whatever crash_rows says)
+                        T.rollout_ticks(g, M.POSITION_CMD, cmd64, DT, False, rebounce, groups, out=obs[form], hold=hold, crashed=cr[form])
+                        d = obs[form] - tg64
+                        cost[form].copy_(((wt64 * d) * d).sum(dim=(0, 2)) + crash_cost * cr[form].sum(dim=0))
                     elif form == "bare":
                         g.tick_n(DT, ticks, True, False, rebounce)
                     else:
@@ -446,6 +466,8 @@ def main_ticks(sizes, ticks, reps, arith, holds, forms):
                     for fld in a.dtype.names:
                         assert np.array_equal(a[fld].view(np.uint64) if a[fld].dtype == np.float64 else a[fld],
                                               b[fld].view(np.uint64) if b[fld].dtype == np.float64 else b[fld]), f"{n} hold {hold}: {fld} differs"
+                if "cost" in forms and "rows64" in forms:  # (the first run of both forms starts from the same state)
+                    assert torch.allclose(cost["cost"], cost["rows64"], rtol=1e-9, atol=0.0), f"{n} hold {hold}: the cost and the reduction of the rows differ"
                 times = {f: [] for f in forms}
                 for _ in range(reps):
                     for f in forms:
@@ -460,6 +482,11 @@ def main_ticks(sizes, ticks, reps, arith, holds, forms):
                 line += f"  rows {row_bytes / 1e6:.2f} MB/tick"
                 if "tick" in forms and "bare" in forms:
                     line += f"  tick - bare {float(np.median(times['tick'])) - float(np.median(times['bare'])):+.2f} us"
+                if "cost" in forms and "bare" in forms:
+                    line += f"  cost - bare {float(np.median(times['cost'])) - float(np.median(times['bare'])):+.2f} us"
+                if "cost" in forms and "rows64" in forms:
+                    line += (f"  rows64 moves {(n * ow * 8 + n) / hold / 1e6:.2f} MB/tick out and back, cost {n * 8 / ticks / 1e6:.4f}"
+                             + ("  cost beats rows64" if max(times["cost"]) < min(times["rows64"]) else "  COST DOES NOT BEAT ROWS64"))
                 if "tick" in forms and "loop" in forms:
                     line += "  tick beats loop" if max(times["tick"]) < min(times["loop"]) else "  TICK DOES NOT BEAT LOOP"
                 for f in forms:

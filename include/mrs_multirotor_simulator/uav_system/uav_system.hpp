@@ -848,6 +848,21 @@ public:
                                                          cost_groups, dev_target, target_stride, dev_weight, weight_stride, dev_cost,
                                                          accumulate ? 1 : 0, stream));
   }
+  // rolloutTickCostDevice whose command rows are nominal commands, as rolloutFeedbackDevice's: at every tick that starts a command
+  // block the command is cmd row + G (ref row - the FP64 observation row of fb_groups before the step), formed in the fused step +
+  // collision kernel.  dev_gain, dev_ref: as rolloutFeedbackDevice.  cost_groups 0 with a dev_cost: the crash cost alone; with dev_cost
+  // null too: a pure closed-loop run whose result is the swarm's state.
+  void rolloutTickFeedbackDevice(int first, int count, int mode, double dt, int n_ticks, int cmd_every, int cost_every, const void* dev_cmd,
+                                 int dtype, int cmd_stride, uint32_t fb_groups, const void* dev_gain, bool gain_per_uav, int gain_blocks,
+                                 const void* dev_ref, int ref_stride, int ref_blocks, uint32_t cost_groups, const void* dev_target,
+                                 int target_stride, const void* dev_weight, int weight_stride, double crash_cost, double* dev_cost,
+                                 bool accumulate, bool crash, double rebounce, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_rollout_tick_feedback_device(s_, first, count, mode, dt, n_ticks, cmd_every, cost_every, dev_cmd, dtype,
+                                                              cmd_stride, fb_groups, dev_gain, gain_per_uav ? 1 : 0, gain_blocks, dev_ref,
+                                                              ref_stride, ref_blocks, cost_groups, dev_target, target_stride, dev_weight,
+                                                              weight_stride, crash_cost, dev_cost, accumulate ? 1 : 0, crash ? 1 : 0, rebounce,
+                                                              stream));
+  }
   // the whole simulation state of UAVs [first, first + count) into dev_records[0 .. count-1] (device memory, 16-B aligned)
   void saveDevice(int first, int count, mrs_uav_snapshot_t* dev_records, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_save_device(s_, first, count, dev_records, stream));

@@ -823,6 +823,48 @@ int mrs_swarm_rollout_tick_cost_device(mrs_swarm_t* s, int32_t first, int32_t co
                                        int32_t weight_stride, double crash_cost, double* dev_cost, int32_t accumulate, int32_t crash,
                                        double rebounce, void* ext_stream);
 
+/* ---- feedback tick rollouts: closed-loop linear state feedback inside a tick rollout (controllers as samples, contacts in the horizon) ----
+ * mrs_swarm_rollout_tick_cost_device whose command rows are NOMINAL commands, as mrs_swarm_rollout_feedback_device's are: linear-policy
+ * search for a swarm, tube-MPPI around a nominal plan in a crowded airspace, one law over many initial states with crash penalties — with
+ * the contacts of timerMain in the horizon (src/multirotor_simulator.cpp:211-217, handleCollisions :295-359).  With B = n_ticks / cmd_every
+ * command blocks, W_o the gather width of fb_groups and W_c the command width of `mode`, the call stands for the loop
+ *   for t in [0, n_ticks):
+ *     if (t % cmd_every == 0) {           b = t / cmd_every
+ *       o = mrs_swarm_gather_device(s, first, count, fb_groups, ..., MRS_DTYPE_F64, ...);    the state BEFORE the step; a collision tick
+ *                                                                                            pending from tick t - 1 stays pending
+ *       for every UAV first + k: u[k] = the law of mrs_swarm_rollout_feedback_device on
+ *                                       (cmd[b][k], G[gain_blocks == 1 ? 0 : b][k or shared], ref[ref_blocks == 1 ? 0 : b][k or shared], o[k])
+ *       mrs_swarm_set_input_device(s, first, count, mode, u, MRS_DTYPE_F64, W_c, ext_stream);
+ *     }
+ *     mrs_swarm_step(s, dt);              evaluates the collision tick pending from tick t - 1
+ *     if ((t + 1) % cost_every == 0 && dev_cost)
+ *       the evaluation of mrs_swarm_rollout_tick_cost_device: the term of cost_groups if cost_groups != 0, then the crash add
+ *     mrs_swarm_handle_collisions(s, 1, crash, rebounce);    stays pending
+ * The law is the feedback rollout's, word for word: FP64 with one rounding per operation and no fused multiply-add in both arithmetic
+ * flavours, columns ascending and none skipped, FP32 inputs widened exactly, a NaN setpoint or observation being its residual with its
+ * own bits (the setpoint's if both are NaN), and the layouts of dev_gain (gain_per_uav == 0: [gain_blocks, W_c, W_o]; 1: [gain_blocks,
+ * W_c, W_o, count], UAV-minor) and dev_ref (ref_stride == 0: one shared dense row per block).  The row the law reads does not depend on
+ * whether the pending collision tick has been evaluated: the evaluation writes the external force and the crash flag, and no observation
+ * group reads either.  The evaluation is the cost tick rollout's, word for word: two separately rounded additions, the term first, the
+ * crash add performed whenever the flag is set whatever crash_cost is, the flag a level and not an edge, cost_groups == 0 with dev_target
+ * and dev_weight NULL the crash cost alone.  dev_cost == NULL with cost_groups == 0 and dev_target and dev_weight NULL is a pure
+ * closed-loop run with no evaluation at all, whose result is the swarm's state: cost_every is still checked, crash_cost is ignored.
+ * Everything else is the contract of mrs_swarm_rollout_tick_device: the entry (a collision tick pending at entry is evaluated by the
+ * first launch), the last tick's collision staying pending, ONE host wait and ONE stream fence per call, crashed UAVs, UAVs outside the
+ * range (stepped with their own commands, no element of dev_cost), and the refusal on a sharded swarm.  A UAV on hold is not iterated
+ * and takes part in the collisions; its command is still formed (from its unchanged state) and written, and its cost evaluated.  The
+ * feedback has no memory: a horizon cut into two calls, the second with accumulate != 0, gives the bits of one call.
+ * Every argument is checked before anything is launched and a refused call changes nothing: the refusals of
+ * mrs_swarm_rollout_feedback_device and of mrs_swarm_rollout_tick_cost_device together, except that cost_groups == 0 is refused only when
+ * a dev_target or dev_weight comes with it, and cost_groups != 0 needs all of dev_target, dev_weight and dev_cost. */
+int mrs_swarm_rollout_tick_feedback_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_ticks,
+                                           int32_t cmd_every, int32_t cost_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride,
+                                           uint32_t fb_groups, const void* dev_gain, int32_t gain_per_uav, int32_t gain_blocks,
+                                           const void* dev_ref, int32_t ref_stride, int32_t ref_blocks, uint32_t cost_groups,
+                                           const void* dev_target, int32_t target_stride, const void* dev_weight, int32_t weight_stride,
+                                           double crash_cost, double* dev_cost, int32_t accumulate, int32_t crash, double rebounce,
+                                           void* ext_stream);
+
 #ifdef __cplusplus
 }
 #endif

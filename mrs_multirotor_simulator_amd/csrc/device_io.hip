@@ -119,8 +119,9 @@ __global__ void __launch_bounds__(256) k_crashed_u8(const uint32_t* F, int first
   out[k] = (F[first + k] & FLAG_CRASHED) ? 1 : 0;
 }
 
-// the crash add of a cost tick rollout's evaluation (mrs_swarm_rollout_tick_cost_device) for a tick without the fused form: one FP64
-// addition per crashed UAV of the range, behind the term the cost rollout kernels added, performed whatever crash_cost is
+// the crash add of a cost tick or feedback tick rollout's evaluation (mrs_swarm_rollout_tick_cost_device,
+// mrs_swarm_rollout_tick_feedback_device) for a tick without the fused form: one FP64 addition per crashed UAV of the range, behind the
+// term the cost or feedback rollout kernels added, performed whatever crash_cost is
 __global__ void __launch_bounds__(256) k_crash_cost(const uint32_t* F, int first, int count, double* cost, double crash_cost) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= count) return;
@@ -362,13 +363,13 @@ int mrs_swarm_apply_force_device(mrs_swarm_t* s, int32_t first, int32_t count, c
 
 // Every argument of the rollout entry points as one record; a call leaves what it does not have at zero.  `kind` is the entry point:
 // it decides which of the optional parts are checked and which kernel family runs.
-enum RolloutKind { ROLLOUT_ROWS, ROLLOUT_FORCE, ROLLOUT_COST, ROLLOUT_FEEDBACK, ROLLOUT_TICK, ROLLOUT_TICK_COST };
+enum RolloutKind { ROLLOUT_ROWS, ROLLOUT_FORCE, ROLLOUT_COST, ROLLOUT_FEEDBACK, ROLLOUT_TICK, ROLLOUT_TICK_COST, ROLLOUT_TICK_FEEDBACK };
 struct RolloutArgs {
   const char* who;
   RolloutKind kind;
   int32_t     first, count, mode;
   double      dt;
-  int32_t     n_steps, cmd_every, obs_every;  // (n_ticks of a tick rollout; cost_every of a cost, feedback or cost tick rollout)
+  int32_t     n_steps, cmd_every, obs_every;  // (n_ticks of a tick rollout; cost_every of a cost, feedback, cost tick or feedback tick rollout)
   const void* dev_cmd;
   int32_t     dtype, cmd_stride;
   uint32_t    groups;  // of the observation rows, or of the cost (a feedback rollout's may be 0: no cost; a cost tick rollout's: crash cost only)
@@ -386,13 +387,13 @@ struct RolloutArgs {
   int32_t     weight_stride;
   double*     cost;
   int32_t     accumulate;
-  // mrs_swarm_rollout_feedback_device
+  // mrs_swarm_rollout_feedback_device, mrs_swarm_rollout_tick_feedback_device
   uint32_t    fb_groups;
   const void* gain;
   int32_t     gain_per_uav, gain_blocks;
   const void* ref;
   int32_t     ref_stride, ref_blocks;
-  // mrs_swarm_rollout_tick_device, mrs_swarm_rollout_tick_cost_device (which has no dev_crashed)
+  // mrs_swarm_rollout_tick_device, mrs_swarm_rollout_tick_cost_device and mrs_swarm_rollout_tick_feedback_device (which have no dev_crashed)
   uint8_t*    dev_crashed;
   int32_t     crash;
   double      rebounce;
@@ -407,7 +408,9 @@ struct RolloutWidths {
 // The argument checks of every rollout entry point, in the order in which a call with several faults reports them.  `steps` and `every`
 // are the nouns of the messages: n_steps or n_ticks, obs_every or cost_every.  Nothing is launched and nothing is changed here.
 static int check_rollout_args(mrs_swarm_t* s, const RolloutArgs& a, const std::string& steps, const std::string& every, RolloutWidths& w) {
-  const bool forced = a.kind == ROLLOUT_FORCE, fb = a.kind == ROLLOUT_FEEDBACK, tc = a.kind == ROLLOUT_TICK_COST;
+  // tf: a feedback tick rollout has the feedback rollout's parts (fb) and the cost tick rollout's evaluation (tc)
+  const bool tf = a.kind == ROLLOUT_TICK_FEEDBACK;
+  const bool forced = a.kind == ROLLOUT_FORCE, fb = tf || a.kind == ROLLOUT_FEEDBACK, tc = tf || a.kind == ROLLOUT_TICK_COST;
   const bool cost   = fb || tc || a.kind == ROLLOUT_COST;
   int        rc     = check_range(s, a.first, a.count);
   if (rc) return rc;
@@ -427,7 +430,8 @@ static int check_rollout_args(mrs_swarm_t* s, const RolloutArgs& a, const std::s
   w.obs = w.fb = 0;
   if ((rc = mrs_swarm_gather_width(a.groups, &w.obs))) return rc;
   if (!cost && a.groups != 0u && a.obs_stride < w.obs) return fail(MRS_ERR_ARG, "obs_stride smaller than the width of the selected groups");
-  w.costed = cost && !(fb && a.groups == 0u);
+  // (no cost groups: a feedback rollout evaluates nothing; a feedback tick rollout with a dev_cost evaluates the crash cost alone)
+  w.costed = cost && !(fb && a.groups == 0u && !(tf && a.cost));
   if (fb) {
     if (w.cmd < 1) return fail(MRS_ERR_ARG, "a feedback rollout needs a mode with a payload");
     if ((rc = mrs_swarm_gather_width(a.fb_groups, &w.fb))) return rc;
@@ -725,6 +729,81 @@ int mrs_swarm_rollout_tick_cost_device(mrs_swarm_t* s, int32_t first, int32_t co
   }
   // nothing of this call stays in the log: a replay adds to the caller's vector and reads the caller's rows, which are only guaranteed
   // to live until the call returns (one host wait per call); the last tick's collision stays pending
+  if ((rc = drain(s))) return rc;
+  if ((rc = finish_profile(s))) return rc;
+  return fence_out(s, ext);
+}
+
+// mrs_swarm_rollout_tick_cost_device whose command rows are nominal commands: every tick at which a command block starts carries that
+// block's nominal commands, gains and setpoints, and the launch forms the command from the state before the step.  The same loop of
+// step_one and pending collision ticks, the same single drain, the same memset outside the launch log.  Without a dev_cost no tick
+// carries an evaluation: a pure closed-loop run.
+int mrs_swarm_rollout_tick_feedback_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_ticks, int32_t cmd_every,
+                                           int32_t cost_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t fb_groups,
+                                           const void* dev_gain, int32_t gain_per_uav, int32_t gain_blocks, const void* dev_ref, int32_t ref_stride,
+                                           int32_t ref_blocks, uint32_t cost_groups, const void* dev_target, int32_t target_stride,
+                                           const void* dev_weight, int32_t weight_stride, double crash_cost, double* dev_cost, int32_t accumulate,
+                                           int32_t crash, double rebounce, void* ext_stream) {
+  MRS_LOCK(s);
+  RolloutArgs a{"mrs_swarm_rollout_tick_feedback_device", ROLLOUT_TICK_FEEDBACK, first, count, mode, dt, n_ticks, cmd_every, cost_every, dev_cmd, dtype,
+                cmd_stride, cost_groups, nullptr, 0, ext_stream};
+  a.target = dev_target, a.target_stride = target_stride, a.weight = dev_weight, a.weight_stride = weight_stride;
+  a.cost = dev_cost, a.accumulate = accumulate;
+  a.fb_groups = fb_groups, a.gain = dev_gain, a.gain_per_uav = gain_per_uav, a.gain_blocks = gain_blocks;
+  a.ref = dev_ref, a.ref_stride = ref_stride, a.ref_blocks = ref_blocks;
+  a.crash = crash, a.rebounce = rebounce;
+  RolloutWidths w;
+  int           rc = check_rollout_args(s, a, "n_ticks", "cost_every", w);
+  if (rc) return rc;
+  const int    width = w.cmd;  // (at least 1: checked)
+  const size_t elem  = dtype_bytes(dtype);
+  if (s->n == 0) return MRS_OK;
+  HIPCHK(hipSetDevice(s->device));
+  if (!s->log.empty() && (rc = drain(s))) return rc;  // (as mrs_swarm_rollout_tick_device: a collision tick pending at entry stays pending)
+  if ((rc = upload_types(s, dt))) return rc;
+  rollout_track_mode(s, a);
+  hipStream_t ext = (hipStream_t)ext_stream;
+  if ((rc = fence_in(s, ext))) return rc;
+  if ((rc = begin_profile(s))) return rc;
+  if (w.costed && count > 0 && !accumulate) HIPCHK(hipMemsetAsync(dev_cost, 0, (size_t)count * sizeof(double), s->stream));  // (+0.0)
+  RolloutTickFeedbackDev f{};
+  f.first = first, f.count = count;
+  f.cmd_stride = cmd_stride;
+  f.ref_row = ref_stride, f.tgt_row = target_stride;
+  f.gain_lane = gain_per_uav ? 1 : 0, f.gain_col = gain_per_uav ? (uint32_t)count : 1u;
+  f.fb_word    = fb_groups | (uint32_t)w.fb << 8;
+  f.cmd_word   = (uint32_t)width | (dtype == MRS_DTYPE_F32 ? 32u : 0u);
+  f.groups     = cost_groups;
+  f.mode_bits  = (uint32_t)mode << FLAG_MODE_SHIFT;
+  f.crash_cost = crash_cost;
+  // elements between two blocks: gains (a matrix, or a matrix per UAV), setpoint rows and target rows (a row per UAV, or one dense row
+  // for all); gain_blocks / ref_blocks 1: one block serves every command block
+  const size_t per      = gain_per_uav ? (size_t)count : (size_t)1;
+  const size_t gain_blk = gain_blocks == 1 ? 0u : (size_t)width * (size_t)w.fb * per;
+  const size_t ref_blk  = ref_blocks == 1 ? 0u : ref_stride ? (size_t)count * (size_t)ref_stride : (size_t)w.fb;
+  const size_t tgt_blk  = target_stride ? (size_t)count * (size_t)target_stride : (size_t)w.obs;
+  for (int t = 0; t < n_ticks; t++) {
+    f.cmd = f.gain = f.ref = f.target = f.weight = nullptr;
+    f.cost = nullptr;
+    if (count > 0 && t % cmd_every == 0) {
+      const size_t b = (size_t)(t / cmd_every);
+      f.cmd  = static_cast<const char*>(dev_cmd) + b * (size_t)count * (size_t)cmd_stride * elem;
+      f.gain = static_cast<const char*>(dev_gain) + b * gain_blk * elem;
+      f.ref  = static_cast<const char*>(dev_ref) + b * ref_blk * elem;
+    }
+    if (w.costed && count > 0 && (t + 1) % cost_every == 0) {
+      const size_t j = (size_t)((t + 1) / cost_every - 1);
+      f.cost = dev_cost;
+      if (cost_groups != 0u) {
+        f.target = static_cast<const char*>(dev_target) + j * tgt_blk * elem;
+        f.weight = static_cast<const char*>(dev_weight) + j * (size_t)weight_stride * elem;
+      }
+    }
+    if ((rc = step_one(s, dt, nullptr, nullptr, &f))) return rc;
+    if ((rc = mrs_swarm_handle_collisions(s, 1, crash, rebounce))) return rc;
+  }
+  // nothing of this call stays in the log: a replay reads the caller's rows and gains and adds to the caller's vector, which are only
+  // guaranteed to live until the call returns (one host wait per call); the last tick's collision stays pending
   if ((rc = drain(s))) return rc;
   if ((rc = finish_profile(s))) return rc;
   return fence_out(s, ext);

@@ -61,6 +61,8 @@ extern "C" hipError_t mrs_launch_rollout_tick_literal(SwarmDev sw, CollDev cd, R
 extern "C" hipError_t mrs_launch_rollout_tick_fast(SwarmDev sw, CollDev cd, RolloutTickDev r, double dt, int variant, hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_tick_cost_literal(SwarmDev sw, CollDev cd, RolloutTickCostDev r, double dt, int variant, hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_tick_cost_fast(SwarmDev sw, CollDev cd, RolloutTickCostDev r, double dt, int variant, hipStream_t st);
+extern "C" hipError_t mrs_launch_rollout_tick_feedback_literal(SwarmDev sw, CollDev cd, RolloutTickFeedbackDev r, double dt, int variant, hipStream_t st);
+extern "C" hipError_t mrs_launch_rollout_tick_feedback_fast(SwarmDev sw, CollDev cd, RolloutTickFeedbackDev r, double dt, int variant, hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_feedback_literal(SwarmDev sw, RolloutFeedbackDev r, double dt, int n_steps, int cmd_every, int cost_every,
                                                             int variant, hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_feedback_fast(SwarmDev sw, RolloutFeedbackDev r, double dt, int n_steps, int cmd_every, int cost_every,
@@ -327,6 +329,8 @@ struct mrs_swarm {
   // writes into them what the no-op launch did not (the call drains the log before it returns: the rows live that long).
   // cost: the launch is one tick of mrs_swarm_rollout_tick_cost_device and `cost` names that tick's command block and evaluation — a
   // replay adds to the caller's cost vector what the no-op launch did not (it never got as far as the vector).
+  // fed: the launch is one tick of mrs_swarm_rollout_tick_feedback_device and `fb` names that tick's nominal commands, gains, setpoints
+  // and evaluation — a replay forms the command from the state the no-op launch left alone, and adds what it did not.
   struct PackRef { int32_t kind, ticket; };
   struct TickRec {
     double  dt;
@@ -339,6 +343,8 @@ struct mrs_swarm {
     RolloutTickDev row{};
     bool               costed = false;
     RolloutTickCostDev cost{};
+    bool                   fed = false;
+    RolloutTickFeedbackDev fb{};
   };
   Collide              pend;                        // requested after the most recent step, not evaluated yet
   // A fused launch consumes the force it evaluates from registers and does not write the F_ext columns (24 B per UAV and tick).
@@ -437,8 +443,10 @@ int  begin_profile(mrs_swarm* s);
 int  finish_profile(mrs_swarm* s);
 int  collide_now(mrs_swarm* s, const mrs_swarm::Collide& c, bool force);
 int  wait_for_progress(mrs_swarm* s, const volatile unsigned* hw, unsigned index, int lead);
-// row: the tick's caller rows (mrs_swarm_rollout_tick_device); cost: the tick's evaluation (mrs_swarm_rollout_tick_cost_device); not both
-int  step_one(mrs_swarm* s, double dt, const RolloutTickDev* row = nullptr, const RolloutTickCostDev* cost = nullptr);
+// row: the tick's caller rows (mrs_swarm_rollout_tick_device); cost: the tick's evaluation (mrs_swarm_rollout_tick_cost_device); fb: the
+// tick's feedback law and evaluation (mrs_swarm_rollout_tick_feedback_device); at most one of them
+int  step_one(mrs_swarm* s, double dt, const RolloutTickDev* row = nullptr, const RolloutTickCostDev* cost = nullptr,
+              const RolloutTickFeedbackDev* fb = nullptr);
 int  drain(mrs_swarm* s);
 // the slot of `kind` that still holds the download `ticket` (nullptr: a ticket of the other kind, or its slot has been recycled)
 inline mrs_swarm::OutSlot* held_slot(mrs_swarm* s, int kind, int32_t ticket) {

@@ -265,6 +265,34 @@ struct RolloutTickCostDev {
   double      crash_cost;
 };
 
+// ---- ONE tick of a feedback tick rollout (mrs_swarm_rollout_tick_feedback_device, rollout_tick_feedback_device.inc) ----
+// RolloutTickCostDev whose command side becomes the NOMINAL command, with the gains and setpoints of the command block that starts at
+// this tick: the F_CMD columns of UAV first + k take cmd row k + G(k) (ref row k - the observation row of fb_groups before the step).
+// G(k)[c][col] sits at element k * gain_lane + (c * row width + col) * gain_col of `gain`, as RolloutFeedbackDev's.  The host works out
+// the pointers of each tick, the gain and setpoint blocks included (one block serving every command block: the same pointer at every
+// start): no block distances and no rate words.  The descriptor travels with the launch's record in the stall / replay log: a replayed
+// launch sees the state its no-op left alone, forms the same command and adds once.
+struct RolloutTickFeedbackDev {
+  const void* cmd;         // the nominal command row block that starts at this tick (row k at element k * cmd_stride), or null: none starts
+  const void* gain;        // the gains of that block, or null
+  const void* ref;         // its setpoint rows (row k at element k * ref_row), or null
+  const void* target;      // the target row block of the evaluation that ends with this tick (row k at element k * tgt_row), or null
+  const void* weight;      // its weight row, or null
+  double*     cost;        // cost[k]: the running sum of UAV first + k, or null: no evaluation ends with this tick (or in the whole call)
+  int32_t     first, count;
+  int32_t     cmd_stride;
+  int32_t     ref_row;     // ref_stride, or 0: all UAVs share the setpoint row
+  int32_t     tgt_row;     // target_stride, or 0: all UAVs share the target row
+  int32_t     gain_lane;   // 0, or 1: per-UAV gains
+  uint32_t    gain_col;    // 1, or count: per-UAV gains (UAV-minor)
+  uint32_t    fb_word;     // fb_groups | row width of fb_groups << 8
+  uint32_t    cmd_word;    // payload width | rows are FP32 << 5 (commands, gains, setpoints, targets and weights)
+  uint32_t    groups;      // MRS_OBS_* of the cost; 0: the crash add alone (target and weight null)
+  uint32_t    mode_bits;   // input mode << FLAG_MODE_SHIFT
+  int32_t     _pad;
+  double      crash_cost;
+};
+
 // 48-byte record exchanged for the collision pass (single- and multi-GPU): everything
 // MultirotorSimulator::handleCollisions reads of the partner UAV (src/multirotor_simulator.cpp:339-350)
 struct PosRecord {

@@ -217,6 +217,35 @@ int launch_cost_step(mrs_swarm* s, double dt, const RolloutTickCostDev& c) {
   return MRS_OK;
 }
 
+// One tick of mrs_swarm_rollout_tick_feedback_device without the fused form, as launch_cost_step: one step of the feedback rollout kernels
+// with this tick's nominal commands, gains, setpoints and evaluation (the command from the state before the step, the term), then the
+// crash add of an evaluation that ends here.  The law and the two adds round as the fused launch's do: the same bits.
+int launch_feedback_step(mrs_swarm* s, double dt, const RolloutTickFeedbackDev& f) {
+  s->region_launches++;
+  RolloutFeedbackDev r{};
+  r.first = f.first, r.count = f.count;
+  r.cmd_stride = f.cmd_stride;
+  r.cmd_sched  = (f.cmd ? f.cmd_word : (f.cmd_word & 32u)) << 24;  // (width 0: no command block starts at this tick)
+  r.cost_sched = (f.cost && f.groups != 0u) ? f.groups << 24 : 0u;  // (groups 0: no evaluation ends here, or the crash add alone)
+  r.mode_bits  = f.mode_bits;
+  r.fb_word    = f.fb_word;
+  if (f.cmd) {  // (one command block: the block distances are never used)
+    r.cmd = f.cmd, r.gain = f.gain, r.ref = f.ref;
+    r.gain_col = f.gain_col, r.gain_lane = f.gain_lane, r.ref_row = f.ref_row;
+  }
+  if (r.cost_sched != 0u) {
+    r.target = f.target, r.weight = f.weight, r.cost = f.cost;
+    r.tgt_row = f.tgt_row, r.tgt_blk = 0, r.wt_row = 0;
+  }
+  const int variant = s->n_cascade > 0 ? 0 : 1;
+  if (s->arith == MRS_ARITH_FAST)
+    HIPCHK(mrs_launch_rollout_feedback_fast(s->view(), r, dt, 1, 1, 1, variant, s->stream));
+  else
+    HIPCHK(mrs_launch_rollout_feedback_literal(s->view(), r, dt, 1, 1, 1, variant, s->stream));
+  if (f.cost && f.count > 0) return launch_crash_cost(s, f.first, f.count, f.cost, f.crash_cost);
+  return MRS_OK;
+}
+
 // one fused launch: evaluate collision tick `e.eval` (if any) from the lists, then makeStep(e.dt)
 int launch_fused(mrs_swarm* s, const mrs_swarm::TickRec& e) {
   const volatile unsigned* hw = mrs_collide_host_words(s->cwork);
@@ -249,6 +278,11 @@ int launch_fused(mrs_swarm* s, const mrs_swarm::TickRec& e) {
       HIPCHK(mrs_launch_rollout_tick_cost_fast(v, cd, e.cost, e.dt, variant, s->stream));
     else
       HIPCHK(mrs_launch_rollout_tick_cost_literal(v, cd, e.cost, e.dt, variant, s->stream));
+  } else if (e.fed) {  // a tick of mrs_swarm_rollout_tick_feedback_device: the same launch with this tick's feedback law and evaluation
+    if (s->arith == MRS_ARITH_FAST)
+      HIPCHK(mrs_launch_rollout_tick_feedback_fast(v, cd, e.fb, e.dt, variant, s->stream));
+    else
+      HIPCHK(mrs_launch_rollout_tick_feedback_literal(v, cd, e.fb, e.dt, variant, s->stream));
   } else if (s->arith == MRS_ARITH_FAST)
     HIPCHK(mrs_launch_step_coll_fast(v, cd, e.dt, variant, 0, s->stream));
   else
@@ -322,9 +356,10 @@ int drain(mrs_swarm* s) {
       } else {  // (lists incomplete: dense neighbourhoods) every tick on its own
         if (e.eval.on && (rc = collide_now(s, e.eval, false))) return rc;
         s->p_valid = false;
-        if (e.rows || e.costed) {
+        if (e.rows || e.costed || e.fed) {
           if (e.dt != s->table_dt && (rc = upload_types(s, e.dt))) return rc;
-          if ((rc = e.rows ? launch_row_step(s, e.dt, e.row) : launch_cost_step(s, e.dt, e.cost))) return rc;
+          if ((rc = e.rows ? launch_row_step(s, e.dt, e.row) : e.costed ? launch_cost_step(s, e.dt, e.cost) : launch_feedback_step(s, e.dt, e.fb)))
+            return rc;
         } else {
           s->region_launches++;
           if ((rc = launch_part(s, e.dt, 1, 0, (s->n + 63) / 64, 1, s->stream))) return rc;
@@ -362,7 +397,7 @@ int settle(mrs_swarm* s) {
 }
 
 // one makeStep of every UAV; the collision tick requested since the previous step (if any) is evaluated by the same launch
-int step_one(mrs_swarm* s, double dt, const RolloutTickDev* row, const RolloutTickCostDev* cost) {
+int step_one(mrs_swarm* s, double dt, const RolloutTickDev* row, const RolloutTickCostDev* cost, const RolloutTickFeedbackDev* fb) {
   int rc;
   if (s->collide_since_step && s->use_lists && s->use_fused) {
     const volatile unsigned* hw = mrs_collide_host_words(s->cwork);
@@ -374,6 +409,7 @@ int step_one(mrs_swarm* s, double dt, const RolloutTickDev* row, const RolloutTi
       mrs_swarm::TickRec e{dt, s->pend, false};
       if (row) e.rows = true, e.row = *row;
       if (cost) e.costed = true, e.cost = *cost;
+      if (fb) e.fed = true, e.fb = *fb;
       if (s->pend.on && hw && hw[CTL_WARN] > s->search_mark) {
         // some UAV has used up most of its skin: repeat the search NOW, in stream order — it evaluates the pending collision tick
         // itself — instead of running into the stall a few ticks on (no synchronisation, nothing to replay)
@@ -393,6 +429,7 @@ int step_one(mrs_swarm* s, double dt, const RolloutTickDev* row, const RolloutTi
   s->p_valid            = false;  // a plain step kernel does not refresh the position records
   if (row) return launch_row_step(s, dt, *row);
   if (cost) return launch_cost_step(s, dt, *cost);
+  if (fb) return launch_feedback_step(s, dt, *fb);
   return launch_step(s, dt, 1);
 }
 

@@ -120,6 +120,7 @@ ABI_SYMBOLS = [
     "mrs_swarm_rollout_feedback_device",
     "mrs_swarm_rollout_tick_device",
     "mrs_swarm_rollout_tick_cost_device",
+    "mrs_swarm_rollout_tick_feedback_device",
 ]
 
 # device-resident callers (mrs_swarm_*_device): row element types and the observation groups of mrs_swarm_gather_device, in bit order
@@ -371,6 +372,8 @@ def load_library():
                                           vp],
         "mrs_swarm_rollout_tick_cost_device": [vp, i32, i32, i32, C.c_double, i32, i32, i32, vp, i32, i32, C.c_uint32, vp, i32, vp, i32,
                                                C.c_double, vp, i32, i32, C.c_double, vp],
+        "mrs_swarm_rollout_tick_feedback_device": [vp, i32, i32, i32, C.c_double, i32, i32, i32, vp, i32, i32, C.c_uint32, vp, i32, i32, vp, i32,
+                                                   i32, C.c_uint32, vp, i32, vp, i32, C.c_double, vp, i32, i32, C.c_double, vp],
     }
     for name, args in sig.items():
         if os.environ.get("MRS_SWARM_LIB") and not hasattr(L, name):
@@ -899,6 +902,17 @@ class Swarm:
                                                        int(weight_stride), C.c_double(float(crash_cost)), dev_cost or None,
                                                        int(bool(accumulate)), int(bool(crash)), C.c_double(float(rebounce)),
                                                        ext_stream or None))
+
+    def rollout_tick_feedback_device(self, first, count, mode, dt, n_ticks, cmd_every, cost_every, dev_cmd, dtype, cmd_stride, fb_groups,
+                                     dev_gain, gain_per_uav, gain_blocks, dev_ref, ref_stride, ref_blocks, cost_groups, dev_target,
+                                     target_stride, dev_weight, weight_stride, crash_cost, dev_cost, accumulate, crash, rebounce, ext_stream):
+        _check(_lib.mrs_swarm_rollout_tick_feedback_device(self._h, int(first), int(count), int(mode), C.c_double(float(dt)), int(n_ticks),
+                                                           int(cmd_every), int(cost_every), dev_cmd or None, int(dtype), int(cmd_stride),
+                                                           C.c_uint32(int(fb_groups)), dev_gain or None, int(gain_per_uav), int(gain_blocks),
+                                                           dev_ref or None, int(ref_stride), int(ref_blocks), C.c_uint32(int(cost_groups)),
+                                                           dev_target or None, int(target_stride), dev_weight or None, int(weight_stride),
+                                                           C.c_double(float(crash_cost)), dev_cost or None, int(bool(accumulate)),
+                                                           int(bool(crash)), C.c_double(float(rebounce)), ext_stream or None))
 
     def get_diag(self):
         d = Diag()

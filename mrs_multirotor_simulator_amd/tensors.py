@@ -489,6 +489,94 @@ def rollout_feedback(swarm, mode, commands, dt, fb_groups, gains, refs, cost_gro
     return out
 
 
+def rollout_tick_feedback(swarm, mode, commands, dt, crash, rebounce, fb_groups, gains, refs, cost_groups=0, targets=None, weights=None,
+                          crash_cost=0.0, first=0, hold=1, cost_every=None, out=None, accumulate=False):
+    """rollout_tick_cost whose commands are NOMINAL commands, as rollout_feedback's are (mrs_swarm_rollout_tick_feedback_device): at the
+    start of command block b (every `hold` ticks) the command of UAV first + k is formed in the fused step + collision kernel as
+    `commands[b, k] + G[b, k] @ (refs[b, k] - o)`, o being the FP64 observation row of `fb_groups` before the step, and held for the
+    block; every `cost_every` ticks (default: `hold`), between the tick's step and its collision pass, the evaluation of
+    rollout_tick_cost is added to the UAV's cost.  The call is the loop gather -> the feedback law -> set_input -> tick, bit for bit,
+    with one host wait and one stream fence per call instead of one per command block; the feedback has no memory, so a horizon cut
+    into calls (accumulate=True from the second on) gives the bits of one call.  gains, refs: as in rollout_feedback.  cost_groups,
+    targets, weights, crash_cost, out, accumulate: as in rollout_tick_cost, except that `out` is not allocated when cost_groups == 0:
+      cost_groups != 0                 the term and the crash cost (out is allocated if None);
+      cost_groups == 0 with an `out`   the crash cost alone (targets and weights stay None);
+      cost_groups == 0, out None       a pure closed-loop run with no evaluation at all: returns None.
+    Returns out.  The collision pass of the last tick stays pending."""
+    dev = swarm.device()
+    if not isinstance(commands, torch.Tensor) or commands.dim() != 3:
+        raise ValueError("commands must be a [T, count, width] tensor")
+    hold = int(hold)
+    if hold < 1:
+        raise ValueError(f"hold must be at least 1, got {hold}")
+    code = _dtype_code(commands.dtype)
+    blocks, count = commands.shape[0], commands.shape[1]
+    ticks = blocks * hold
+    every = hold if cost_every is None else int(cost_every)
+    if every < 1 or ticks % every != 0:
+        raise ValueError(f"cost_every must be at least 1 and divide the {ticks} ticks of the call, got {every}")
+    evals = ticks // every
+    width = command_width(mode, commands.shape[2])
+    if width < 1:
+        raise ValueError("a feedback rollout needs a mode with a payload")
+    cstride = _check_steps(commands, "commands", None, count, width, commands.dtype, dev)
+    if mode == ACTUATOR_CMD and count > 1 and cstride != commands.shape[2]:
+        raise ValueError("actuator rows must be dense (row stride == number of motors)")
+    wo = gather_width(fb_groups)
+    if wo == 0:
+        raise ValueError("fb_groups must select at least one observation group: a feedback needs columns")
+    for name, t in (("gains", gains), ("refs", refs), ("targets", targets), ("weights", weights)):
+        if isinstance(t, torch.Tensor) and t.dtype != commands.dtype:
+            raise ValueError(f"{name} has dtype {t.dtype}, the commands {commands.dtype}: one dtype serves commands, gains, refs, targets "
+                             "and weights")
+    if not isinstance(gains, torch.Tensor) or gains.dim() not in (3, 4):
+        raise ValueError(f"gains: expected a [Bg, {width}, {wo}] (shared) or [Bg, {width}, {wo}, {count}] (per UAV, UAV-minor) tensor, got "
+                         f"{tuple(gains.shape) if isinstance(gains, torch.Tensor) else type(gains).__name__}")
+    per_uav = gains.dim() == 4
+    want = (width, wo, count) if per_uav else (width, wo)
+    if gains.shape[0] not in (1, blocks) or tuple(gains.shape[1:]) != want:
+        raise ValueError(f"gains: expected a [{blocks} or 1, {', '.join(str(x) for x in want)}] tensor, got {tuple(gains.shape)}")
+    if gains.device.type != "cuda" or gains.device.index != dev:
+        raise ValueError(f"gains is on {gains.device}, the swarm lives on cuda:{dev}")
+    if not gains.is_contiguous():
+        raise ValueError("gains must be dense" + (": [Bg, W_c, W_o, count] with the UAV index last (g.permute(0, 2, 3, 1).contiguous())"
+                                                  if per_uav else ": [Bg, W_c, W_o], row-major"))
+    if not isinstance(refs, torch.Tensor) or refs.dim() != 3 or refs.shape[0] not in (1, blocks):
+        raise ValueError(f"refs: expected a [{blocks} or 1, {count} or 1, >= {wo}] tensor, got "
+                         f"{tuple(refs.shape) if isinstance(refs, torch.Tensor) else type(refs).__name__}")
+    rstride = _row_blocks(refs, "refs", refs.shape[0], count, wo, commands.dtype, dev)
+    tptr = wptr = optr = tstride = wstride = 0
+    if cost_groups == 0:
+        if targets is not None or weights is not None:
+            raise ValueError("cost_groups == 0 is the crash cost alone (with an `out`) or a run without a cost: it takes no targets and no weights")
+        if out is None and accumulate:
+            raise ValueError("accumulate=True needs the `out` vector it adds to")
+    else:
+        w = gather_width(cost_groups)
+        tstride = _row_blocks(targets, "targets", evals, count, w, commands.dtype, dev)
+        if not isinstance(weights, torch.Tensor) or weights.dim() != 2 or weights.shape[0] not in (1, evals):
+            raise ValueError(f"weights: expected a [{evals} or 1, >= {w}] tensor, got "
+                             f"{tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights).__name__}")
+        wstride = check_tensor(weights, weights.shape[0], w, commands.dtype, dev)
+        if weights.shape[0] == 1:
+            wstride = 0
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs the `out` vector it adds to")
+            out = torch.empty(count, dtype=torch.float64, device=torch.device("cuda", dev))
+        tptr, wptr = targets.data_ptr(), weights.data_ptr()
+    if out is not None:
+        if isinstance(out, torch.Tensor) and out.dtype != torch.float64:
+            raise ValueError(f"out has dtype {out.dtype}: the cost vector is always torch.float64")
+        check_tensor(out, count, None, torch.float64, dev)
+        optr = out.data_ptr()
+    swarm.rollout_tick_feedback_device(first, count, mode, dt, ticks, hold, every, commands.data_ptr() if count > 0 else 0, code, cstride,
+                                       fb_groups, gains.data_ptr(), int(per_uav), gains.shape[0], refs.data_ptr(), rstride, refs.shape[0],
+                                       cost_groups, tptr, tstride, wptr, wstride, float(crash_cost), optr, bool(accumulate), bool(crash),
+                                       float(rebounce), _stream(dev))
+    return out
+
+
 def crashed(swarm, first=0, count=None, out=None):
     """UavSystem::hasCrashed of UAVs [first, first + count) as a bool tensor on the swarm's device"""
     count = _count(swarm, first, count)

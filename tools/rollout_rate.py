@@ -52,13 +52,21 @@ that ends in a synchronisation of the device:
   bare     tick_n(dt, T, True, False, 100.0), then synchronize: no commands, no rows              (the floor)
 and prints us per tick (median, min-max), the bytes of rows per tick, and whether the call beats the loop in every round.  In LITERAL
 `tick` and `loop` must end bit-identical (rows, crash bytes and state): the tool asserts it.  The fifth argument selects among
-tick,loop,bare,cost,rows64 (e.g. `bare` alone, with MRS_SWARM_LIB naming the library of another commit).  The last two are not in the
+tick,loop,bare,cost,rows64,feedback,torchloop (e.g. `bare` alone, with MRS_SWARM_LIB naming the library of another commit).  The last two are not in the
 default; they measure the COST tick rollout (mrs_swarm_rollout_tick_cost_device) against what a caller did without it:
   cost     tensors.rollout_tick_cost(cmd, dt, False, 100.0, POS | VEL | QUAT, targets [E, 1, 10], weights [1, 10], 1000.0, hold=hold,
            cost_every=hold, out=)                                                                (one call, 8 B per UAV come back)
   rows64   tensors.rollout_ticks with FP64 rows of the same groups and crash rows every `hold` ticks (FP64 commands: one dtype serves
            both), then the torch reduction ((w * d) * d).sum over columns and evaluations + crash_cost * crashed.sum to one number per UAV
 With both, the two costs of the first run must agree to 1e-9 relative (the reduction sums in another order).
+Two more forms, not in the default either, measure the FEEDBACK tick rollout (mrs_swarm_rollout_tick_feedback_device) against the closed
+loop through torch that it replaces:
+  feedback   tensors.rollout_tick_feedback(cmd, dt, False, 100.0, POS | VEL | ROT | OMEGA, gains [1, 4, 18], refs [1, n, 18], and the
+             cost of `cost`, hold=hold, out=): the command of a block is the nominal row plus G (ref - the 18-column row before the step)
+  torchloop  per block: tensors.gather(POS | VEL | ROT | OMEGA) -> cmd + (ref - o) @ G^T (torch.matmul) -> tensors.set_input ->
+             tick_n(dt, hold, True, False, 100.0)       (one host wait and one stream fence per block; FP32 rows, no cost)
+The largest relative difference of torchloop's final positions from feedback's after the first run is printed (the loop rounds the row to
+FP32 and sums in another order).
 
     python tools/rollout_rate.py --ticks [sizes=100000] [T=200] [reps=5] [-] [forms=tick,loop,bare] [arith=fast] [holds=1,10]
 
@@ -403,8 +411,10 @@ def main_ticks(sizes, ticks, reps, arith, holds, forms):
     ow = T.gather_width(groups)
     rng = np.random.default_rng(5)
     rebounce = 100.0
-    assert set(forms) <= {"tick", "loop", "bare", "cost", "rows64"}, forms
+    assert set(forms) <= {"tick", "loop", "bare", "cost", "rows64", "feedback", "torchloop"}, forms
     crash_cost = 1000.0
+    fb_groups = T.OBS_POS | T.OBS_VEL | T.OBS_ROT | T.OBS_OMEGA
+    fw = T.gather_width(fb_groups)
     print(f"tick rollout of T = {ticks} ticks (step + elastic collision pass), POSITION_CMD, FP32 commands and POS|VEL|QUAT rows, x500, "
           f"{arith.upper()}; {reps} rounds after a warm-up, alternating; host clock around a device synchronisation")
     for n in sizes:
@@ -412,7 +422,7 @@ def main_ticks(sizes, ticks, reps, arith, holds, forms):
         p = M.model_params("x500", ground_enabled=True, ground_z=0.0)
         for hold in holds:
             assert hold >= 1 and ticks % hold == 0, "hold must divide T"
-            for crash_rows in (False, True):
+            for crash_rows in ((False, True) if {"tick", "loop"} & set(forms) else (False,)):  # (only tick and loop have optional crash rows)
                 swarms = {}
                 for f in forms:
                     g = M.Swarm(n, arith=M.ARITH_FAST if arith == "fast" else M.ARITH_LITERAL)
@@ -422,15 +432,22 @@ def main_ticks(sizes, ticks, reps, arith, holds, forms):
                     swarms[f] = g
                 dev = torch.device("cuda", swarms[forms[0]].device())
                 cmd = torch.tensor(goal[None] + rng.normal(0.0, 0.05, (ticks // hold, n, 4)), dtype=torch.float32, device=dev)
+                rowless = ("bare", "cost", "feedback", "torchloop")
                 obs = {f: torch.empty((ticks // hold, n, ow), dtype=torch.float64 if f == "rows64" else torch.float32, device=dev)
-                       for f in forms if f not in ("bare", "cost")}
-                cr = {f: torch.zeros((ticks // hold, n), dtype=torch.bool, device=dev) for f in forms if f not in ("bare", "cost")}
+                       for f in forms if f not in rowless}
+                cr = {f: torch.zeros((ticks // hold, n), dtype=torch.bool, device=dev) for f in forms if f not in rowless}
                 # the cost forms: one shared target row per evaluation around the goal, one weight row; FP64 twins for the torch reduction
                 tg = torch.tensor(np.concatenate([goal[:1, :3], np.zeros((1, ow - 3))], axis=1)[None] + rng.normal(0.0, 0.5, (ticks // hold, 1, ow)),
                                   dtype=torch.float32, device=dev)
                 wt = torch.tensor(rng.uniform(0.1, 2.0, (1, ow)), dtype=torch.float32, device=dev)
                 tg64, wt64, cmd64 = tg.double(), wt.double(), cmd.double() if "rows64" in forms else None
-                cost = {f: torch.empty(n, dtype=torch.float64, device=dev) for f in forms if f in ("cost", "rows64")}
+                cost = {f: torch.empty(n, dtype=torch.float64, device=dev) for f in forms if f in ("cost", "rows64", "feedback")}
+                # the feedback forms: one small gain matrix for all UAVs, a setpoint row per UAV around its initial state (one block each)
+                gain = torch.tensor(rng.normal(0.0, 1e-3, (1, 4, fw)), dtype=torch.float32, device=dev)
+                fb_ref = None
+                if "feedback" in forms or "torchloop" in forms:
+                    fb_ref = (T.gather(swarms[forms[0]], fb_groups) + torch.tensor(rng.normal(0.0, 0.5, (n, fw)), dtype=torch.float32, device=dev))[None]
+                    o_row = torch.empty((n, fw), dtype=torch.float32, device=dev)
 
                 def run(form):
                     g = swarms[form]
@@ -443,6 +460,14 @@ def main_ticks(sizes, ticks, reps, arith, holds, forms):
                         T.rollout_ticks(g, M.POSITION_CMD, cmd64, DT, False, rebounce, groups, out=obs[form], hold=hold, crashed=cr[form])
                         d = obs[form] - tg64
                         cost[form].copy_(((wt64 * d) * d).sum(dim=(0, 2)) + crash_cost * cr[form].sum(dim=0))
+                    elif form == "feedback":
+                        T.rollout_tick_feedback(g, M.POSITION_CMD, cmd, DT, False, rebounce, fb_groups, gain, fb_ref, groups, tg, wt, crash_cost,
+                                                hold=hold, out=cost[form])
+                    elif form == "torchloop":
+                        for b in range(ticks // hold):
+                            T.gather(g, fb_groups, out=o_row)
+                            T.set_input(g, M.POSITION_CMD, cmd[b] + torch.matmul(fb_ref[0] - o_row, gain[0].t()))
+                            g.tick_n(DT, hold, True, False, rebounce)
                     elif form == "bare":
                         g.tick_n(DT, ticks, True, False, rebounce)
                     else:
@@ -468,6 +493,10 @@ def main_ticks(sizes, ticks, reps, arith, holds, forms):
                                               b[fld].view(np.uint64) if b[fld].dtype == np.float64 else b[fld]), f"{n} hold {hold}: {fld} differs"
                 if "cost" in forms and "rows64" in forms:  # (the first run of both forms starts from the same state)
                     assert torch.allclose(cost["cost"], cost["rows64"], rtol=1e-9, atol=0.0), f"{n} hold {hold}: the cost and the reduction of the rows differ"
+                fb_diff = None
+                if "feedback" in forms and "torchloop" in forms:  # (the first run of both forms starts from the same state)
+                    xa, xb = swarms["feedback"].get_states()["x"], swarms["torchloop"].get_states()["x"]
+                    fb_diff = float(np.max(np.abs(xa - xb) / np.maximum(np.abs(xa), 1.0)))
                 times = {f: [] for f in forms}
                 for _ in range(reps):
                     for f in forms:
@@ -487,6 +516,11 @@ def main_ticks(sizes, ticks, reps, arith, holds, forms):
                 if "cost" in forms and "rows64" in forms:
                     line += (f"  rows64 moves {(n * ow * 8 + n) / hold / 1e6:.2f} MB/tick out and back, cost {n * 8 / ticks / 1e6:.4f}"
                              + ("  cost beats rows64" if max(times["cost"]) < min(times["rows64"]) else "  COST DOES NOT BEAT ROWS64"))
+                if "feedback" in forms and "bare" in forms:
+                    line += f"  feedback - bare {float(np.median(times['feedback'])) - float(np.median(times['bare'])):+.2f} us"
+                if "feedback" in forms and "torchloop" in forms:
+                    line += (f"  torchloop vs feedback positions {fb_diff:.1e}"
+                             + ("  feedback beats torchloop" if max(times["feedback"]) < min(times["torchloop"]) else "  FEEDBACK DOES NOT BEAT TORCHLOOP"))
                 if "tick" in forms and "loop" in forms:
                     line += "  tick beats loop" if max(times["tick"]) < min(times["loop"]) else "  TICK DOES NOT BEAT LOOP"
                 for f in forms:

@@ -921,7 +921,7 @@ __global__ void __launch_bounds__(64) k_query2(SwarmDev sw, const PosRecord* rec
           const Cell oc = cell_of<LISTS>(oxy.x, oxy.y, oz_);
           if (oc.ok && oc.x == mc.x + ox && oc.y == mc.y + oy && oc.z == mc.z + oz) {  // (else: another cell that shares bucket and tag bits)
             const double d0 = mxy.x - oxy.x, d1 = mxy.y - oxy.y, d2 = mz_ - oz_;
-            const double dd = ((0.0 + d0 * d0) + d1 * d1) + d2 * d2;
+            const double dd = mrs_dist2(d0, d1, d2);
             if (dd < (LISTS == 2 ? LIST_R2_2 : LIST_R2)) {
               const uint32_t k = atomicAdd(&nl_n[ow], 1u);
               if (k < (uint32_t)LIST_CAP) nl_j[ow][k] = it.x;

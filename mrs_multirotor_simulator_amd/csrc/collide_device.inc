@@ -9,6 +9,7 @@
 // so get_external_force reports the force the step consumed and a run does not depend on which path evaluated which tick.
 #pragma once
 #include "swarm_layout.h"
+#include "pose_math.h"  // mrs_unfused
 
 #define CDEV static __device__ __forceinline__
 
@@ -100,6 +101,16 @@ CDEV bool mrs_may_leave(const double y[18], double dd, double thrust_now, uint32
   return !ok;
 }
 
+// nanoflann's squared distance (L2_Adaptor::evalMetric, nanoflann.hpp:443-486), ((0 + d0^2) + d1^2) + d2^2, every product rounded on its
+// own: the neighbour set and the contacts hang on strict comparisons of this number, and one fused product moves a pair that sits
+// on a threshold across it.  The pragma keeps the sum apart in the units compiled with -ffp-contract=off; in the FAST step unit
+// (-ffp-contract=fast) the backend fuses every multiply-add whatever the pragma says, so there the products go through mrs_unfused
+// (pose_math.h).  tests/test_collision_thresholds_gpu.py holds every kernel to it.
+CDEV double mrs_dist2(double d0, double d1, double d2) {
+#pragma clang fp contract(off)
+  return ((0.0 + mrs_unfused(d0 * d0)) + mrs_unfused(d1 * d1)) + mrs_unfused(d2 * d2);
+}
+
 // Scalar forms (the struct forms below forward to them): the fused evaluation keeps the partner in registers, and a struct-valued
 // loop variable made of values from two address spaces ends up in scratch memory behind a generic pointer.
 // nanoflann RadiusResultSet(3.0) on the SQUARED distance (:326, nanoflann.hpp:273-305), then the reference's d^2 < crit (:346);
@@ -108,7 +119,7 @@ CDEV bool mrs_qualifies_s(double mx, double my, double mz, double marm, double m
                           int crash) {
 #pragma clang fp contract(off)
   const double d0 = mx - ox, d1 = my - oy, d2 = mz - oz;
-  const double dist = ((0.0 + d0 * d0) + d1 * d1) + d2 * d2;
+  const double dist = mrs_dist2(d0, d1, d2);
   if (!(dist < 3.0)) return false;
   const double crit_ij = ((marm + mprop) + oarm) + oprop;
   const double crit_ji = ((oarm + oprop) + marm) + mprop;
@@ -120,7 +131,7 @@ CDEV void mrs_apply_partner_s(double mx, double my, double mz, double mmass, dou
                               double oarm, double oprop, int crash, double rebounce, double& fx, double& fy, double& fz, bool& crashed) {
 #pragma clang fp contract(off)
   const double d0 = mx - ox, d1 = my - oy, d2 = mz - oz;
-  const double dist    = ((0.0 + d0 * d0) + d1 * d1) + d2 * d2;
+  const double dist    = mrs_dist2(d0, d1, d2);
   const double crit_ij = ((marm + mprop) + oarm) + oprop;
   const double crit_ji = ((oarm + oprop) + marm) + mprop;
 #if defined(MRS_FAST)
@@ -257,7 +268,7 @@ CDEV void mrs_eval_partner(CD& cd, const TypeParams* T, uint32_t my_type, uint32
   {
 #pragma clang fp contract(off)
     const double d0 = mx - ox, d1 = my - oy, d2 = mz - oz;
-    if (!((((0.0 + d0 * d0) + d1 * d1) + d2 * d2) < 3.0)) return;
+    if (!(mrs_dist2(d0, d1, d2) < 3.0)) return;
   }
   double om = mmass, oa = marm, op = mprop;
   if (e & MRS_NBR_FOREIGN) {

@@ -14,6 +14,9 @@
   order the radius search returns them (helpers.reference_kdtree reads them).
 * pid_reference_vectors_4242.npz — OUTPUT OF THE REFERENCE'S OWN CODE: the PIDController above on a second stimulus set
   (pid_sequences(seed=4242, n_seq=40, n_steps=120)).
+* collision_threshold_sets.npz — OUTPUT OF THE REFERENCE'S OWN CODE: the same kd-tree on the threshold-3.0 cases of
+  tests/collision_thresholds.py (pairs whose squared distance is 3.0 exactly, an ulp below it, or on either side of it depending on
+  whether the sum is contracted), in space and in the plane z = 0; points and CSR neighbour lists as the radius search returns them.
 * oracle_trajectories.npz — regression vectors of the CPU oracle (NOT reference outputs: the reference's dynamics cannot be
   built here) for BASELINE config 1 and a 64-UAV mixed-mode swarm; they freeze the oracle so that a later
   edit of oracle/uav_oracle.c cannot silently move the parity target.
@@ -67,6 +70,18 @@ def kdtree_scenarios():
         off, idx, d2 = O.ref_radius_neighbours(pts, 3.0, 10)
         out[f"{key}_points"], out[f"{key}_offsets"], out[f"{key}_indices"], out[f"{key}_d2"] = pts, off, idx, d2
     np.savez_compressed(os.path.join(HERE, "reference_kdtree_scenarios.npz"), **out)
+
+
+def collision_threshold_sets():
+    assert O.ref_lib() is not None, "oracle/_ref must be built from the reference tree (oracle/Makefile)"
+    import collision_thresholds as ct
+    import test_collision_thresholds
+    out = {}
+    for key, planar in (("space", False), ("plane", True)):
+        pts, _ = test_collision_thresholds.radius_points(ct.cases(planar))
+        off, idx, d2 = O.ref_radius_neighbours(pts, 3.0, 10)
+        out[f"{key}_points"], out[f"{key}_offsets"], out[f"{key}_indices"], out[f"{key}_d2"] = pts, off, idx, d2
+    np.savez_compressed(os.path.join(HERE, "collision_threshold_sets.npz"), **out)
 
 
 def oracle_trajectories():
@@ -265,5 +280,6 @@ if __name__ == "__main__":
     pid_reference()
     kdtree_scenarios()
     pid_reference_4242()
+    collision_threshold_sets()
     for f in sorted(os.listdir(HERE)):
         print(f, os.path.getsize(os.path.join(HERE, f)))

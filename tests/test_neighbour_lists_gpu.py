@@ -82,8 +82,11 @@ def test_lists_of_a_dense_sheet(mrs):
 
 
 def test_lists_with_cells_on_their_faces_and_far_out(mrs):
-    """positions exactly on cell faces (multiples of the 2.25-m edge), pairs just inside / outside the list radius, unusable
-    positions (NaN, beyond the position limit), coordinates of 1e5 m"""
+    """positions exactly on cell faces (multiples of the 2.25-m edge), pairs at R +- 1e-9 with R = sqrt(3) + 0.5 (and half of that),
+    unusable positions (NaN, beyond the position limit), coordinates of 1e5 m.  Both kinds of pair are INSIDE the list radius: the
+    kernel lists up to LIST_R2 = R^2 (1 + 1e-9) + 1e-5, a radius some 2.2e-6 m beyond R, so R + 1e-9 is listed like R - 1e-9.  The
+    list radius itself — pairs at LIST_R2 exactly and an ulp below it — is the subject of
+    test_collision_thresholds_gpu.py::test_list_radius_with_cells_and_quantisation_against_it."""
     rng = np.random.default_rng(5)
     edge, R = 2.25, np.sqrt(3.0) + 0.5
     pts = []

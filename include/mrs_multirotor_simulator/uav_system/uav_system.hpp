@@ -779,6 +779,20 @@ public:
                      int index_stride, int32_t* dev_count, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_nearest_device(s_, first, count, k, radius, fields, dev_rows, dtype, stride, dev_index, index_stride, dev_count, stream));
   }
+  // collision worlds (mrs_swarm_set_worlds): UAVs interact through the collision pass, and appear in each other's nearest-neighbour rows,
+  // only if their 32-bit labels are equal (0 until set); the labels of UAVs [first, first + worlds.size())
+  void setWorlds(int first, const std::vector<int32_t>& worlds) {
+    mrs_throw_on_error(mrs_swarm_set_worlds(s_, first, (int32_t)worlds.size(), worlds.data()));
+  }
+  std::vector<int32_t> getWorlds(int first, int count) {
+    std::vector<int32_t> out((size_t)(count > 0 ? count : 0));
+    mrs_throw_on_error(mrs_swarm_get_worlds(s_, first, count, out.data()));
+    return out;
+  }
+  // ... from `count` labels in device memory of the swarm's device, fenced against `stream` like the other device-resident calls
+  void setWorldsDevice(int first, int count, const int32_t* dev_worlds, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_set_worlds_device(s_, first, count, dev_worlds, stream));
+  }
   // n_steps steps of the whole swarm; UAVs [first, first + count) take command row block t of dev_cmd before step t, and row block t of
   // dev_obs receives their MRS_OBS_* groups after it (dev_obs may be null when groups == 0): the set-input / step / gather loop in one call
   void rolloutDevice(int first, int count, int mode, double dt, int n_steps, const void* dev_cmd, int dtype, int cmd_stride, uint32_t groups,

@@ -538,6 +538,28 @@ int mrs_nearest_width(uint32_t fields, int32_t k, int32_t* width);
 int mrs_swarm_nearest_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t k, double radius, uint32_t fields, void* dev_rows, int32_t dtype,
                              int32_t stride, int32_t* dev_index, int32_t index_stride, int32_t* dev_count, void* ext_stream);
 
+/* ---- collision worlds: several scenes in one swarm that do not see each other (per-sample horizons of a sampling-based planner) ----
+ * A world is a 32-bit label per UAV, 0 for every UAV until a setter says otherwise.  Two UAVs interact through the collision pass
+ * (mrs_swarm_handle_collisions, mrs_swarm_tick_n, the tick rollouts), or appear in each other's rows of mrs_swarm_nearest_device, only
+ * if their labels are equal: the neighbour set of i is { j : world[j] == world[i], j != i, d2(i,j) < 3.0 }, forces are summed in
+ * ascending partner index, and the neighbour lists (and their capacity) hold same-world partners only.  A swarm whose UAVs carry W
+ * distinct labels behaves, world by world, as W separate swarms that each hold the UAVs of one label in ascending index order and
+ * receive the same calls — UAVs of different worlds may share coordinates (a forked scene: mrs_swarm_load_device with an index).
+ * Labels are compared for equality and nothing else: every int32_t value is legal, there is no order.  Nothing else about a UAV follows
+ * its label: its step, its commands, its ground plane and its slot index are what they were.
+ * The label belongs to the slot, like the hold flag: mrs_swarm_construct, mrs_swarm_set_state*, mrs_swarm_load_device,
+ * mrs_swarm_reset_device and mrs_swarm_copy_uavs (the destination's labels stay) leave it alone, a snapshot record does not hold it;
+ * mrs_swarm_clone and mrs_swarm_clone_resized copy it (UAVs past the original's: 0).
+ * Each call enters like a state call (a pending collision tick is evaluated first, under the old labels); a setter makes the next
+ * collision tick repeat the neighbour search.  set_worlds_device honours ext_stream and checks its pointer like the other
+ * device-resident calls.  Errors: ranges MRS_ERR_RANGE; a null pointer, for _device a pointer that is not memory of the swarm's device
+ * holding `count` labels, or a setter on a sharded swarm MRS_ERR_ARG; count == 0 is MRS_OK; a refused call changes nothing.  Sharded
+ * swarms have one world: mrs_swarm_comm_init* and mrs_swarm_handle_collisions_gathered return MRS_ERR_ARG on a swarm that holds a
+ * label other than 0.  get_worlds returns zeros when no label was ever set, on a sharded swarm (its own UAVs) too. */
+int mrs_swarm_set_worlds(mrs_swarm_t* s, int32_t first, int32_t count, const int32_t* worlds);
+int mrs_swarm_get_worlds(mrs_swarm_t* s, int32_t first, int32_t count, int32_t* out);
+int mrs_swarm_set_worlds_device(mrs_swarm_t* s, int32_t first, int32_t count, const int32_t* dev_worlds, void* ext_stream);
+
 /* ---- state snapshots: the whole per-UAV simulation state into caller-owned device records and back (rewind, recorded resets, forks) ----
  * One record holds everything a step reads of a UAV besides its command, feed-forwards and mode, bit for bit.  The 60 doubles are the
  * state columns in their order (MultirotorModel::State x, v, v_prev, R row-major, omega, motor_rpm — all MRS_MAX_MOTORS columns as

@@ -2,8 +2,9 @@
 // nanoflann kd-tree (src/multirotor_simulator.cpp:295-359 + include/nanoflann.hpp radius search).
 //
 // Semantics reproduced exactly:
-//   neighbour set of i  = { j : d2(i,j) < 3.0 }  with d2 = ((0 + dx^2) + dy^2) + dz^2, dx = x_i - x_j
-//                         (nanoflann L2_Adaptor::evalMetric, RadiusResultSet(3.0): SQUARED distance vs 3.0)
+//   neighbour set of i  = { j : world[j] == world[i], j != i, d2(i,j) < 3.0 }  with d2 = ((0 + dx^2) + dy^2) + dz^2, dx = x_i - x_j
+//                         (nanoflann L2_Adaptor::evalMetric, RadiusResultSet(3.0): SQUARED distance vs 3.0; world: the 32-bit label
+//                          of mrs_swarm_set_worlds, 0 for every UAV of a swarm that never set one — see "collision worlds" below)
 //   for j != i with d2 < crit(i,j) = ((arm_i + prop_i) + arm_j) + prop_j   (squared metres vs metres — kept)
 //     crash mode : j is crashed                       (:348)
 //     otherwise  : F_i += ((rebounce * normalized(x_i - x_j)) * m_i) * (m_j / (m_i + m_j))   (:350)
@@ -32,6 +33,14 @@
 // writes to positions or airframe constants force a rebuild, and a UAV with more than LIST_CAP listed neighbours keeps
 // the pass in rebuild mode.  Results are identical to searching every tick.
 //
+// Collision worlds (single-GPU swarms): once a label has been set, the searches run as world-aware instantiations (the same kernel
+// templates with the label column as a trailing argument; with the empty pack — a swarm without labels — a kernel has the arguments
+// and the code it always had).  A mixed image of
+// the label enters the bucket hash and the cell tag, so the copies of a forked scene — same cells, different labels — spread over the
+// table instead of chaining up in one bucket, and a lone head of another world is dropped from its head word; a pair COUNTS only after
+// its two labels have been compared exactly, next to the exact cell comparison.  The lists then hold same-world partners only, and
+// everything that evaluates lists (list ticks, fused launches, skin test, rollouts) is unchanged.
+//
 // The export-set exchange of sharded swarms lives in collide_export.hip (shared geometry and work object: collide_work.h); the
 // kernels of the stand-in collective and of the peer-window all-gather live with their transports (transport_local.hip, transport_peer.hip).
 #include <string.h>
@@ -55,8 +64,35 @@ __device__ __forceinline__ Cell cell_of(double x, double y, double z) {
 
 // the column (cx, cy) is hashed, cz is added: the three z-neighbours of a cell sit in consecutive buckets, so a UAV's 27
 // probes touch ~9 cache lines of the descriptor table instead of 27
+// world labels in the hashes: wm = world_mix(label) is folded into the column hash (bucket) and, through world_tag, into the cell tag.
+// Label 0 mixes to 0: the hashes of a swarm without labels (wm = 0 everywhere below) are the ones they always were.
+__device__ __forceinline__ uint32_t world_mix(uint32_t w) {
+#ifdef MRS_WORLDS_PLAIN_HASH  // measurement variant (tools/worlds_rate.py): labels only in the exact comparison — stacked worlds chain up
+  (void)w;
+  return 0u;
+#else
+  w *= 0x9E3779B1u;
+  w ^= w >> 16;
+  w *= 0x85EBCA6Bu;
+  w ^= w >> 13;
+  return w;
+#endif
+}
+// A world-aware kernel is the SAME kernel template with the label column as a trailing argument pack of one: the instantiation with
+// the empty pack has the arguments and the code it always had.
+__device__ __forceinline__ const uint32_t* world_labels() { return nullptr; }
+__device__ __forceinline__ const uint32_t* world_labels(const uint32_t* p) { return p; }
+__device__ __forceinline__ uint32_t world_tag(uint32_t wm) { return ((wm << 16) | (wm >> 16)) * 0x165667B1u; }
+
 __device__ __forceinline__ uint32_t bucket_of(int cx, int cy, int cz, uint32_t mask) {
   uint32_t h = ((uint32_t)cx * 73856093u) ^ ((uint32_t)cy * 19349663u);
+  h ^= h >> 15;
+  h *= 0x2c1b3c6du;
+  h ^= h >> 12;
+  return (h + (uint32_t)cz) & mask;
+}
+__device__ __forceinline__ uint32_t bucket_of(int cx, int cy, int cz, uint32_t mask, uint32_t wm) {  // (world-aware)
+  uint32_t h = ((uint32_t)cx * 73856093u) ^ ((uint32_t)cy * 19349663u) ^ wm;
   h ^= h >> 15;
   h *= 0x2c1b3c6du;
   h ^= h >> 12;
@@ -67,6 +103,18 @@ __device__ __forceinline__ uint32_t cell_tag(int cx, int cy, int cz) {
   uint32_t h = (uint32_t)cx * 0x9E3779B1u + (uint32_t)cy * 0x85EBCA77u + (uint32_t)cz * 0xC2B2AE3Du;
   h ^= h >> 16;
   return h * 0x27D4EB2Fu;
+}
+__device__ __forceinline__ uint32_t cell_tag(int cx, int cy, int cz, uint32_t wm) {  // (world-aware)
+  uint32_t h = (uint32_t)cx * 0x9E3779B1u + (uint32_t)cy * 0x85EBCA77u + (uint32_t)cz * 0xC2B2AE3Du + world_tag(wm);
+  h ^= h >> 16;
+  return h * 0x27D4EB2Fu;
+}
+// the hash of a kernel's flavour, picked at compile time: the kernels without labels call the functions they always called
+template <bool WORLDS> __device__ __forceinline__ uint32_t bucket_of_x(int cx, int cy, int cz, uint32_t mask, uint32_t wm) {
+  if constexpr (WORLDS) return bucket_of(cx, cy, cz, mask, wm); else return bucket_of(cx, cy, cz, mask);
+}
+template <bool WORLDS> __device__ __forceinline__ uint32_t cell_tag_x(int cx, int cy, int cz, uint32_t wm) {
+  if constexpr (WORLDS) return cell_tag(cx, cy, cz, wm); else return cell_tag(cx, cy, cz);
 }
 
 __global__ void k_flags_update(uint32_t* F, int first, int count, uint32_t and_mask, uint32_t or_mask) {
@@ -94,13 +142,14 @@ __global__ void k_pack_positions(SwarmDev sw, PosRecord* out) {
 // "more than one member": a single-member bucket is accepted or dropped from its head word alone.
 constexpr uint32_t CHAIN_BIT = 0x80000000u;
 
-__device__ __forceinline__ void insert_uav(long long j, const Cell& c, uint32_t mask, uint2* head, uint2* next) {
+template <bool WORLDS = false>
+__device__ __forceinline__ void insert_uav(long long j, const Cell& c, uint32_t mask, uint2* head, uint2* next, uint32_t wm = 0u) {
   if (!c.ok) {  // never inserted
     next[j] = make_uint2(0u, 0u);
     return;
   }
-  const uint32_t b = bucket_of(c.x, c.y, c.z, mask);
-  const unsigned long long me = (unsigned long long)((uint32_t)j + 1u) | ((unsigned long long)(cell_tag(c.x, c.y, c.z) & ~CHAIN_BIT) << 32);
+  const uint32_t b = bucket_of_x<WORLDS>(c.x, c.y, c.z, mask, wm);
+  const unsigned long long me = (unsigned long long)((uint32_t)j + 1u) | ((unsigned long long)(cell_tag_x<WORLDS>(c.x, c.y, c.z, wm) & ~CHAIN_BIT) << 32);
   unsigned long long* slot = reinterpret_cast<unsigned long long*>(head + b);
   const unsigned long long old = atomicExch(slot, me);
   next[j] = make_uint2((uint32_t)old, (uint32_t)(old >> 32) & ~CHAIN_BIT);
@@ -152,11 +201,26 @@ __device__ __forceinline__ uint32_t bucket_col(int cx, int cy) {  // bucket_of(c
   h ^= h >> 12;
   return h;
 }
+__device__ __forceinline__ uint32_t bucket_col(int cx, int cy, uint32_t wm) {  // (world-aware; the same identity with bucket_of(..., wm))
+  uint32_t h = ((uint32_t)cx * 73856093u) ^ ((uint32_t)cy * 19349663u) ^ wm;
+  h ^= h >> 15;
+  h *= 0x2c1b3c6du;
+  h ^= h >> 12;
+  return h;
+}
 __device__ __forceinline__ uint32_t tag_col(int cx, int cy) { return (uint32_t)cx * 0x9E3779B1u + (uint32_t)cy * 0x85EBCA77u; }
+__device__ __forceinline__ uint32_t tag_col(int cx, int cy, uint32_t wm) { return (uint32_t)cx * 0x9E3779B1u + (uint32_t)cy * 0x85EBCA77u + world_tag(wm); }
+template <bool WORLDS> __device__ __forceinline__ uint32_t bucket_col_x(int cx, int cy, uint32_t wm) {
+  if constexpr (WORLDS) return bucket_col(cx, cy, wm); else return bucket_col(cx, cy);
+}
+template <bool WORLDS> __device__ __forceinline__ uint32_t tag_col_x(int cx, int cy, uint32_t wm) {
+  if constexpr (WORLDS) return tag_col(cx, cy, wm); else return tag_col(cx, cy);
+}
 __device__ __forceinline__ uint32_t tag_fin(uint32_t tcol, int cz, int ib) {  // the top 32 - ib bits of a product: every lower bit of the sum reaches them
   return ((tcol + (uint32_t)cz * 0xC2B2AE3Du) * 0x27D4EB2Fu) >> ib;  // (one quarter-rate multiply costs less issue time than a shift-and-add mix of equal reach)
 }
 __device__ __forceinline__ uint32_t tag_bits(int cx, int cy, int cz, int ib) { return tag_fin(tag_col(cx, cy), cz, ib); }
+template <bool WORLDS> __device__ __forceinline__ uint32_t tag_bits_x(int cx, int cy, int cz, int ib, uint32_t wm) { return tag_fin(tag_col_x<WORLDS>(cx, cy, wm), cz, ib); }
 // the test described above, with the prober's part of the three differences precomputed (offset x 1024 - own coordinate); 24-bit multiplies
 template <int WIDE>
 __device__ __forceinline__ bool q_near(int dx, int dy, int dz, uint32_t qj) {
@@ -169,13 +233,14 @@ __device__ __forceinline__ bool q_near(int dx, int dy, int dz, uint32_t qj) {
   return __mul24(dx, dx) + __mul24(dy, dy) + __mul24(dz, dz) <= thr2;
 }
 
-__device__ __forceinline__ void insert_uav2(long long j, const Cell& c, uint32_t q, uint32_t mask, int ib, uint2* head, uint2* next) {
+template <bool WORLDS = false>
+__device__ __forceinline__ void insert_uav2(long long j, const Cell& c, uint32_t q, uint32_t mask, int ib, uint2* head, uint2* next, uint32_t wm = 0u) {
   if (!c.ok) {  // never inserted
     next[j] = make_uint2(0u, 0u);
     return;
   }
-  const uint32_t b = bucket_of(c.x, c.y, c.z, mask);
-  const unsigned long long me = (unsigned long long)(((uint32_t)j + 1u) | (tag_bits(c.x, c.y, c.z, ib) << ib)) | ((unsigned long long)(q & ~CHAIN_BIT) << 32);
+  const uint32_t b = bucket_of_x<WORLDS>(c.x, c.y, c.z, mask, wm);
+  const unsigned long long me = (unsigned long long)(((uint32_t)j + 1u) | (tag_bits_x<WORLDS>(c.x, c.y, c.z, ib, wm) << ib)) | ((unsigned long long)(q & ~CHAIN_BIT) << 32);
   unsigned long long* slot = reinterpret_cast<unsigned long long*>(head + b);
   const unsigned long long old = atomicExch(slot, me);
   next[j] = make_uint2((uint32_t)old, (uint32_t)(old >> 32) & ~CHAIN_BIT);
@@ -198,19 +263,22 @@ __global__ void k_insert(const PosRecord* rec, long long n_total, uint32_t mask,
 // reference path for one lane: repeated sweeps over the 27 bucket chains, each returning the smallest qualifying partner
 // index above the previous one (ascending-index accumulation without per-lane arrays).  Correct for any bucket
 // occupancy; used when the wave-cooperative path below overflows its LDS lists.
-template <int WIDE>
+// WORLDS: `wlab` holds the world labels, `myw` is this UAV's — only members that carry the same label count (compared exactly)
+template <int WIDE, bool WORLDS = false>
 __device__ void query_lane_sweeps(const PosRecord& me, const Cell& c, long long gi, const PosRecord* rec, long long n_total, uint32_t mask,
                                   const uint2* head, const uint2* next, int crash, double rebounce, double& fx, double& fy, double& fz,
-                                  bool& crashed) {
+                                  bool& crashed, const uint32_t* wlab = nullptr, uint32_t myw = 0u) {
+  const uint32_t wm = WORLDS ? world_mix(myw) : 0u;
   long long prev = -1;
   for (;;) {
     long long best = n_total;
     for (int q = 0; q < 27; q++) {
       const int      cx = c.x + q / 9 - 1, cy = c.y + (q / 3) % 3 - 1, cz = c.z + q % 3 - 1;
-      const uint32_t tg = cell_tag(cx, cy, cz) & ~CHAIN_BIT;
-      for (uint2 e = head[bucket_of(cx, cy, cz, mask)]; e.x != 0u; e = next[e.x - 1u]) {
+      const uint32_t tg = cell_tag_x<WORLDS>(cx, cy, cz, wm) & ~CHAIN_BIT;
+      for (uint2 e = head[bucket_of_x<WORLDS>(cx, cy, cz, mask, wm)]; e.x != 0u; e = next[e.x - 1u]) {
         const long long j = (long long)e.x - 1;
         if ((e.y & ~CHAIN_BIT) != tg || j <= prev || j >= best || j == gi) continue;
+        if (WORLDS && wlab[j] != myw) continue;  // another world (bucket and tag agreeing proves nothing)
         const PosRecord o  = rec[j];
         const Cell      oc = cell_of<WIDE>(o.x, o.y, o.z);
         if (oc.x != cx || oc.y != cy || oc.z != cz) continue;  // another cell sharing the bucket (and the tag)
@@ -297,10 +365,12 @@ __device__ __forceinline__ void list_tick(const SwarmDev& sw, const PosRecord* r
 // single-GPU tick: pack and insert in one pass over the state (the records are still written: the query reads them).
 // With LISTS the pass only happens on a rebuild tick (the records then double as the reference positions of the skin test);
 // on every other tick this light kernel evaluates the neighbour lists and the query kernel that follows returns at once.
-template <int LISTS>
+// W: empty, or the world labels (const uint32_t*) — read by the inserts only
+template <int LISTS, class... W>
 __global__ void k_pack_insert(SwarmDev sw, PosRecord* rec, uint32_t mask, uint2* head, uint2* next, uint32_t* ctl, int cur, int force,
                               int table_id, uint2* head_to_clear, uint32_t table_size, const uint32_t* nbr, const uint32_t* nbr_cnt, int crash,
-                              double rebounce, Pos4* pos_now, const uint32_t* stall_word, int ib) {
+                              double rebounce, Pos4* pos_now, const uint32_t* stall_word, int ib, W... labels) {
+  constexpr bool WORLDS = sizeof...(W) != 0;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   (void)stall_word;  // (the pass always runs in full: the two head tables are wiped alternately, a skipped pass would leave stale chains)
   if (LISTS) {
@@ -335,17 +405,18 @@ __global__ void k_pack_insert(SwarmDev sw, PosRecord* rec, uint32_t mask, uint2*
   r.arm_length  = P.arm_length;
   r.prop_radius = P.prop_radius;
   rec[i] = r;
+  uint32_t wm = 0u;
+  if constexpr (WORLDS) wm = world_mix(world_labels(labels...)[i]);
   if (LISTS) {
     const Pos4 pp = {r.x, r.y, r.z, (double)(sw.F[i] >> FLAG_TYPE_SHIFT)};
     pos_now[i]    = pp;
     uint32_t   q;
     const Cell c = cell_q<LISTS ? LISTS : 1>(r.x, r.y, r.z, q);
-    insert_uav2(i, c, q, mask, ib, head, next);
+    insert_uav2<WORLDS>(i, c, q, mask, ib, head, next, wm);
   } else {
-    insert_uav(i, cell_of<LISTS>(r.x, r.y, r.z), mask, head, next);
+    insert_uav<WORLDS>(i, cell_of<LISTS>(r.x, r.y, r.z), mask, head, next, wm);
   }
 }
-
 // ---- neighbour lists over GATHERED records (multi-GPU ticks): every rank holds the current records of all UAVs after the
 // all-gather, so the skin test, the rebuild decision and the list tick are local to the rank — ranks may rebuild on different ticks.
 __device__ __forceinline__ bool record_usable(const PosRecord& r) { return cell_of<true>(r.x, r.y, r.z).ok; }
@@ -488,13 +559,14 @@ __global__ void k_insert_gathered_lists(SwarmDev sw, const PosRecord* rec, PosRe
 // or any head of a chained bucket), .y = its tag with CHAIN_BIT kept for chained buckets.  Returns the number of entries.
 // Unconditional loads from always-valid addresses: a load under a divergent branch is waited for at the join, which would
 // serialise 27 memory round trips.
-__device__ __forceinline__ uint32_t load_heads(const Cell& c, uint32_t mask, const uint2* head, uint2 (&info)[27]) {
+template <bool WORLDS = false>
+__device__ __forceinline__ uint32_t load_heads(const Cell& c, uint32_t mask, const uint2* head, uint2 (&info)[27], uint32_t wm = 0u) {
   uint32_t tc = 0;
 #pragma unroll
-  for (int q = 0; q < 27; q++) info[q] = head[bucket_of(c.x + q / 9 - 1, c.y + (q / 3) % 3 - 1, c.z + q % 3 - 1, mask)];
+  for (int q = 0; q < 27; q++) info[q] = head[bucket_of_x<WORLDS>(c.x + q / 9 - 1, c.y + (q / 3) % 3 - 1, c.z + q % 3 - 1, mask, wm)];
 #pragma unroll
   for (int q = 0; q < 27; q++) {
-    const uint32_t tg    = cell_tag(c.x + q / 9 - 1, c.y + (q / 3) % 3 - 1, c.z + q % 3 - 1) & ~CHAIN_BIT;
+    const uint32_t tg    = cell_tag_x<WORLDS>(c.x + q / 9 - 1, c.y + (q / 3) % 3 - 1, c.z + q % 3 - 1, wm) & ~CHAIN_BIT;
     const bool     chain = (info[q].y & CHAIN_BIT) != 0u;
     const bool     take  = c.ok && info[q].x != 0u && (chain || info[q].y == tg);
     info[q].y = (info[q].y & ~CHAIN_BIT);
@@ -524,7 +596,8 @@ struct QueryLds {  // the LDS arrays of k_query, handed to the helper below
   uint2*      pair_e;
   uint32_t*   pair_m;
   PosRecord*  me_s;
-  int4*       me_cell;
+  int4*       me_cell;  // .w: the owner's world label (world-aware instantiation; 0 otherwise).  k_query2 has a me_cell of its own, whose
+                        // .w is the in-cell coordinate word: there the owner's label is read from the label column
   uint32_t*   hit_j;   // [64][HIT_CAP]
   uint32_t*   hit_n;
   uint32_t*   next_n;
@@ -536,8 +609,9 @@ struct QueryLds {  // the LDS arrays of k_query, handed to the helper below
 // COMPACTED to the front (slot k < the number of entries read so far, so no unread entry is overwritten) — and the shrunken
 // list is swept again until every chain has ended.  Never more entries than the sweep started with: nothing can overflow, and
 // the later levels of the walk (a few percent of the heads) cost one short pass each instead of a pass over every head.
+template <bool WORLDS = false>
 __device__ __forceinline__ void sweep_window(const QueryLds& L, uint32_t wn, int lane, const PosRecord* rec, const uint2* next, long long wave_first,
-                                             int crash) {
+                                             int crash, const uint32_t* wlab = nullptr) {
   // entries per lane and iteration.  Four looked right while the kernel waited on single round trips; since the record loads travel
   // with the chain links and the later levels are compacted, ONE is fastest (100 k UAVs: 26.9 us, U = 2: 27.8, 4: 29.0, 6: 31.1; at
   // 16 m^3 per UAV 63.9 vs 68.0): the work list of a wave is 4-5 entries per lane, and what limits it now is the rate of scattered accesses.
@@ -568,7 +642,7 @@ __device__ __forceinline__ void sweep_window(const QueryLds& L, uint32_t wn, int
         if (pe[u].x != 0u) {
           const int  ow = (int)(pm[u] & 0xFFu), q = (int)((pm[u] >> 8) & 0xFFu);
           const int4 mc = L.me_cell[ow];
-          live[u] = pe[u].y == (cell_tag(mc.x + q / 9 - 1, mc.y + (q / 3) % 3 - 1, mc.z + q % 3 - 1) & ~CHAIN_BIT) &&
+          live[u] = pe[u].y == (cell_tag_x<WORLDS>(mc.x + q / 9 - 1, mc.y + (q / 3) % 3 - 1, mc.z + q % 3 - 1, WORLDS ? world_mix((uint32_t)mc.w) : 0u) & ~CHAIN_BIT) &&
                     (long long)pe[u].x - 1 != wave_first + ow;  // idx == i, src/multirotor_simulator.cpp:335
         }
       }
@@ -577,6 +651,9 @@ __device__ __forceinline__ void sweep_window(const QueryLds& L, uint32_t wn, int
       PosRecord ob[U];
 #pragma unroll
       for (int u = 0; u < U; u++) ob[u] = rec[live[u] ? (long long)pe[u].x - 1 : wave_first];
+      uint32_t ol[U];  // the candidates' world labels, in the same round trip
+#pragma unroll
+      for (int u = 0; u < U; u++) ol[u] = WORLDS ? wlab[live[u] ? (long long)pe[u].x - 1 : wave_first] : 0u;
 #pragma unroll
       for (int u = 0; u < U; u++) {
         if (nx[u].x != 0u) {  // the chain goes on: its next member joins the next sweep
@@ -590,6 +667,7 @@ __device__ __forceinline__ void sweep_window(const QueryLds& L, uint32_t wn, int
         const PosRecord o  = ob[u];
         const Cell      oc = cell_of<0>(o.x, o.y, o.z);
         if (oc.x != mc.x + q / 9 - 1 || oc.y != mc.y + (q / 3) % 3 - 1 || oc.z != mc.z + q % 3 - 1) continue;  // tag collision
+        if (WORLDS && ol[u] != (uint32_t)mc.w) continue;  // another world
         const PosRecord m = L.me_s[ow];
         if (!qualifies(m, o, crash)) continue;
         const uint32_t k = atomicAdd(&L.hit_n[ow], 1u);
@@ -606,9 +684,12 @@ __device__ __forceinline__ void sweep_window(const QueryLds& L, uint32_t wn, int
 }
 
 // The search-every-tick query (neighbour lists switched off, or the caller-driven gathered form): one lane per UAV, see above.
+template <class... W>  // W: empty, or the world labels (const uint32_t*)
 __global__ void __launch_bounds__(64) k_query(SwarmDev sw, const PosRecord* rec, long long n_total, long long my_offset, uint32_t mask,
                                               const uint2* head, const uint2* next, uint2* head_to_clear, uint32_t table_size, int crash,
-                                              double rebounce) {
+                                              double rebounce, W... labels) {
+  constexpr bool  WORLDS = sizeof...(W) != 0;
+  const uint32_t* wlab   = world_labels(labels...);
   __shared__ PosRecord me_s[64];
   __shared__ int4      me_cell[64];
   __shared__ uint2     pair_e[PAIR_CAP];   // x: candidate index + 1, y: its tag
@@ -625,9 +706,11 @@ __global__ void __launch_bounds__(64) k_query(SwarmDev sw, const PosRecord* rec,
   me.x = me.y = me.z = __longlong_as_double(0x7ff8000000000000ll);
   me.mass = me.arm_length = me.prop_radius = 0.0;
   if (active) me = rec[gi];
+  uint32_t myw = 0u, wm = 0u;
+  if constexpr (WORLDS) myw = active ? wlab[gi] : 0u, wm = world_mix(myw);
   const Cell c = cell_of<0>(me.x, me.y, me.z);
   me_s[lane]   = me;
-  me_cell[lane] = make_int4(c.x, c.y, c.z, 0);
+  me_cell[lane] = make_int4(c.x, c.y, c.z, WORLDS ? (int)myw : 0);
   hit_n[lane]  = 0;
   if (lane == 0) hit_overflow = 0;
 
@@ -640,7 +723,7 @@ __global__ void __launch_bounds__(64) k_query(SwarmDev sw, const PosRecord* rec,
   uint32_t first_slot, n_heads;
   {
     uint2          info[27];
-    const uint32_t tc = load_heads(c, mask, head, info);
+    const uint32_t tc = load_heads<WORLDS>(c, mask, head, info, wm);
     // this tick's table has been read by this wave's probes: wipe the other one for the next tick (grid-strided, coalesced)
     {
       const uint32_t stride = gridDim.x * 64u;
@@ -673,16 +756,16 @@ __global__ void __launch_bounds__(64) k_query(SwarmDev sw, const PosRecord* rec,
   const long long wave_first = my_offset + (long long)blockIdx.x * 64;
   if (n_heads <= (uint32_t)PAIR_CAP) {
     __syncthreads();
-    sweep_window(lds, n_heads, lane, rec, next, wave_first, crash);
+    sweep_window<WORLDS>(lds, n_heads, lane, rec, next, wave_first, crash, wlab);
   } else {
     // dense neighbourhood: more heads than the list holds — windows of PAIR_CAP, the heads are probed again per window
     // (cheaper than keeping 27 head words per lane alive across the sweeps of the usual case)
     for (uint32_t wbase = 0; wbase < n_heads; wbase += PAIR_CAP) {
       uint2 info[27];
-      load_heads(c, mask, head, info);
+      load_heads<WORLDS>(c, mask, head, info, wm);
       fill_window(info, first_slot, wbase, lane, pair_e, pair_m);
       __syncthreads();
-      sweep_window(lds, n_heads - wbase < (uint32_t)PAIR_CAP ? n_heads - wbase : (uint32_t)PAIR_CAP, lane, rec, next, wave_first, crash);
+      sweep_window<WORLDS>(lds, n_heads - wbase < (uint32_t)PAIR_CAP ? n_heads - wbase : (uint32_t)PAIR_CAP, lane, rec, next, wave_first, crash, wlab);
     }
   }
   __syncthreads();
@@ -698,7 +781,7 @@ __global__ void __launch_bounds__(64) k_query(SwarmDev sw, const PosRecord* rec,
   bool   crashed = false;
   if (active && c.ok) {
     if (hit_overflow && hit_n[lane] > HIT_CAP) {  // more qualifying partners than the hit list holds: the reference path
-      query_lane_sweeps<0>(me, c, gi, rec, n_total, mask, head, next, crash, rebounce, fx, fy, fz, crashed);
+      query_lane_sweeps<0, WORLDS>(me, c, gi, rec, n_total, mask, head, next, crash, rebounce, fx, fy, fz, crashed, wlab, myw);
     } else {
       const uint32_t nh = hit_n[lane];
       uint32_t       prev = 0;
@@ -748,20 +831,22 @@ __global__ void __launch_bounds__(64) k_query(SwarmDev sw, const PosRecord* rec,
 constexpr uint32_t IT_VERIFY = 1u << 14, IT_WALK = 1u << 15;  // item meta (16 bits): owner | probe << 6 | flags
 
 // reference path for one UAV: see query_lane_sweeps (the same sweeps over entries of the list-building format)
-template <int WIDE>
+template <int WIDE, bool WORLDS = false>
 __device__ void query_lane_sweeps2(const PosRecord& me, const Cell& c, long long gi, const PosRecord* rec, long long n_total, uint32_t mask, int ib,
                                    const uint2* head, const uint2* next, int crash, double rebounce, double& fx, double& fy, double& fz,
-                                   bool& crashed) {
+                                   bool& crashed, const uint32_t* wlab = nullptr, uint32_t myw = 0u) {
+  const uint32_t wm  = WORLDS ? world_mix(myw) : 0u;
   const uint32_t ibm = (1u << ib) - 1u;
   long long      prev = -1;
   for (;;) {
     long long best = n_total;
     for (int q = 0; q < 27; q++) {
       const int      cx = c.x + q / 9 - 1, cy = c.y + (q / 3) % 3 - 1, cz = c.z + q % 3 - 1;
-      const uint32_t tg = tag_bits(cx, cy, cz, ib);
-      for (uint2 e = head[bucket_of(cx, cy, cz, mask)]; e.x != 0u; e = next[(e.x & ibm) - 1u]) {
+      const uint32_t tg = tag_bits_x<WORLDS>(cx, cy, cz, ib, wm);
+      for (uint2 e = head[bucket_of_x<WORLDS>(cx, cy, cz, mask, wm)]; e.x != 0u; e = next[(e.x & ibm) - 1u]) {
         const long long j = (long long)(e.x & ibm) - 1;
         if ((e.x >> ib) != tg || j <= prev || j >= best || j == gi) continue;
+        if (WORLDS && wlab[j] != myw) continue;  // another world
         const PosRecord o  = rec[j];
         const Cell      oc = cell_of<WIDE>(o.x, o.y, o.z);
         if (oc.x != cx || oc.y != cy || oc.z != cz) continue;  // another cell sharing the bucket (and the tag)
@@ -782,10 +867,16 @@ __device__ __forceinline__ unsigned long long clock_dep(uint32_t dep) {
   return t;
 }
 #endif
-template <int LISTS, int LPU>
+// W: empty, or the world labels (const uint32_t*), indexed like `rec` (single-GPU lists only: sharded swarms carry no labels).  The LDS
+// is the same in both forms — the owner's label of a verified pair comes from the label column like its position comes from rec, a
+// cache hit: one more array of UPW words would push the one-lane-per-UAV instantiation into the next 1280-byte step.
+template <int LISTS, int LPU, class... W>
 __global__ void __launch_bounds__(64) k_query2(SwarmDev sw, const PosRecord* rec, long long n_total, long long my_offset, uint32_t mask, int ib,
                                                const uint2* head, const uint2* next, int crash, double rebounce, uint32_t* ctl, int cur, int force,
-                                               uint32_t* nbr, uint32_t* nbr_cnt, uint32_t* stall_word, volatile uint32_t* hostw, uint32_t stall_tau) {
+                                               uint32_t* nbr, uint32_t* nbr_cnt, uint32_t* stall_word, volatile uint32_t* hostw, uint32_t stall_tau,
+                                               W... labels) {
+  constexpr bool  WORLDS = sizeof...(W) != 0;
+  const uint32_t* wlab   = world_labels(labels...);
   constexpr int UPW    = 64 / LPU;              // UAVs per wave
   constexpr int CPL    = (9 + LPU - 1) / LPU;   // columns (cx, cy) of three probes per lane
   constexpr int WL_CAP = UPW * 27;              // every probe of the wave an item: the list cannot overflow
@@ -825,6 +916,8 @@ __global__ void __launch_bounds__(64) k_query2(SwarmDev sw, const PosRecord* rec
     my = xy.y;
     mz = pm[2];
   }
+  uint32_t myw = 0u, wm = 0u;
+  if constexpr (WORLDS) myw = active ? wlab[gi] : 0u, wm = world_mix(myw);
   uint32_t   qme;
   const Cell c = cell_q<LISTS>(mx, my, mz, qme);
   MRS_Q2_STAMP(1, qme);
@@ -853,8 +946,8 @@ __global__ void __launch_bounds__(64) k_query2(SwarmDev sw, const PosRecord* rec
     for (int k = 0; k < CPL; k++) {
       const int      cq = (r + k * LPU) < 9 ? (r + k * LPU) : r;
       const int      cx = c.x + cq / 3 - 1, cy = c.y + cq % 3 - 1;
-      const uint32_t b0 = (bucket_col(cx, cy) + (uint32_t)(c.z - 1)) & mask;
-      tcol[k]           = tag_col(cx, cy);
+      const uint32_t b0 = (bucket_col_x<WORLDS>(cx, cy, wm) + (uint32_t)(c.z - 1)) & mask;
+      tcol[k]           = tag_col_x<WORLDS>(cx, cy, wm);
       const uint4    a  = *reinterpret_cast<const HeadPair*>(head + b0);
       e[k][0] = make_uint2(a.x, a.y);
       e[k][1] = make_uint2(a.z, a.w);
@@ -917,7 +1010,10 @@ __global__ void __launch_bounds__(64) k_query2(SwarmDev sw, const PosRecord* rec
         const double  mz_ = pm[2];
         const int     cq = q / 3, ox = cq / 3 - 1, oy = cq % 3 - 1, oz = q % 3 - 1;
         const int4    mc = me_cell[ow];
-        if (ver) {
+        // the two labels of the pair, in the same round trip as the positions (the owner's: a cache hit, like its position)
+        uint32_t lo = 0u, lm = 0u;
+        if constexpr (WORLDS) lo = wlab[ver ? (long long)it.x : wave_first], lm = wlab[wave_first + ow];
+        if (WORLDS ? (ver && lo == lm) : ver) {  // (same world — compared exactly: agreeing buckets and tag bits prove nothing)
           const Cell oc = cell_of<LISTS>(oxy.x, oxy.y, oz_);
           if (oc.ok && oc.x == mc.x + ox && oc.y == mc.y + oy && oc.z == mc.z + oz) {  // (else: another cell that shares bucket and tag bits)
             const double d0 = mxy.x - oxy.x, d1 = mxy.y - oxy.y, d2 = mz_ - oz_;
@@ -940,7 +1036,7 @@ __global__ void __launch_bounds__(64) k_query2(SwarmDev sw, const PosRecord* rec
         if (walk && nx.x != 0u) {  // the chain goes on: its next member joins the next sweep
           const uint32_t j     = (nx.x & ibm) - 1u;
           const uint32_t qo    = (uint32_t)mc.w;
-          const bool     match = (nx.x >> ib) == tag_fin(tag_col(mc.x + ox, mc.y + oy), mc.z + oz, ib) && (long long)j != wave_first + ow &&
+          const bool     match = (nx.x >> ib) == tag_fin(tag_col_x<WORLDS>(mc.x + ox, mc.y + oy, WORLDS ? world_mix(lm) : 0u), mc.z + oz, ib) && (long long)j != wave_first + ow &&
                                  q_near<LISTS>(ox * (int)QONE - (int)(qo & QMASK), oy * (int)QONE - (int)((qo >> QBITS) & QMASK),
                                                oz * (int)QONE - (int)((qo >> (2 * QBITS)) & QMASK), nx.y);
           const uint32_t k = atomicAdd(&next_n, 1u);
@@ -966,7 +1062,7 @@ __global__ void __launch_bounds__(64) k_query2(SwarmDev sw, const PosRecord* rec
     if (nh) {
       const PosRecord me = rec[gi];
       if (hit_overflow && nh > (uint32_t)HITS) {  // more qualifying partners than the hit list holds: the reference path
-        query_lane_sweeps2<LISTS>(me, c, gi, rec, n_total, mask, ib, head, next, crash, rebounce, fx, fy, fz, crashed);
+        query_lane_sweeps2<LISTS, WORLDS>(me, c, gi, rec, n_total, mask, ib, head, next, crash, rebounce, fx, fy, fz, crashed, wlab, myw);
       } else {
         uint32_t prev = 0;
         for (uint32_t h = 0; h < nh; h++) {  // selection by repeated minimum: nh <= 4, almost always 1
@@ -1025,7 +1121,22 @@ __global__ void __launch_bounds__(64) k_query2(SwarmDev sw, const PosRecord* rec
 template <int LISTS>
 static void launch_query2(int lpu, SwarmDev sw, const PosRecord* rec, long long n_total, long long my_offset, uint32_t mask, int ib, const uint2* head,
                           const uint2* next, int crash, double rebounce, uint32_t* ctl, int cur, int force, uint32_t* nbr, uint32_t* nbr_cnt,
-                          uint32_t* stall_word, volatile uint32_t* hostw, uint32_t stall_tau, hipStream_t st) {
+                          uint32_t* stall_word, volatile uint32_t* hostw, uint32_t stall_tau, hipStream_t st, const uint32_t* wlab = nullptr) {
+  if (LISTS == 1 && wlab) {  // world-aware instantiations: the label column is one more argument
+#define MRS_Q2W_LAUNCH(L)                                                                                                                         \
+  hipLaunchKernelGGL((k_query2<1, L, const uint32_t*>), dim3((sw.n + 64 / L - 1) / (64 / L)), dim3(64), 0, st, sw, rec, n_total, my_offset, mask, ib, head, next, crash, \
+                     rebounce, ctl, cur, force, nbr, nbr_cnt, stall_word, hostw, stall_tau, wlab)
+    if (lpu == 1)
+      MRS_Q2W_LAUNCH(1);
+    else if (lpu == 2)
+      MRS_Q2W_LAUNCH(2);
+    else if (lpu == 3)
+      MRS_Q2W_LAUNCH(3);
+    else
+      MRS_Q2W_LAUNCH(4);
+#undef MRS_Q2W_LAUNCH
+    return;
+  }
 #define MRS_Q2_LAUNCH(L)                                                                                                                        \
   hipLaunchKernelGGL((k_query2<LISTS, L>), dim3((sw.n + 64 / L - 1) / (64 / L)), dim3(64), 0, st, sw, rec, n_total, my_offset, mask, ib, head, next, crash, \
                      rebounce, ctl, cur, force, nbr, nbr_cnt, stall_word, hostw, stall_tau)
@@ -1144,8 +1255,10 @@ static hipError_t empty_tables(CollideWork* w, hipStream_t st) {
 
 // Plain search every tick over ready (gathered) records — the multi-GPU path, and single-GPU ticks with lists switched off
 // (rec_is_local_scratch: `rec` is this swarm's own, not yet packed, record buffer; pack and insert are then fused).
+// worlds: the swarm's world labels (null: a swarm that never set one — the kernels without them); local records only
 extern "C" hipError_t mrs_collide_run(SwarmDev sw, CollideWork** work, const PosRecord* rec, long long n_total, long long my_offset,
-                                      int crash, double rebounce, int rec_is_local_scratch, hipStream_t st) {
+                                      int crash, double rebounce, int rec_is_local_scratch, const uint32_t* worlds, hipStream_t st) {
+  if (worlds && !rec_is_local_scratch) return hipErrorInvalidValue;
   if (!*work) *work = new CollideWork();
   CollideWork* w = *work;
   crash = mode_word(sw, crash);
@@ -1157,12 +1270,19 @@ extern "C" hipError_t mrs_collide_run(SwarmDev sw, CollideWork** work, const Pos
   uint2*         head = w->head[w->cur];
   uint2*         other = w->head[w->cur ^ 1];
   w->cur ^= 1;
+  if (worlds) {
+    hipLaunchKernelGGL((k_pack_insert<false, const uint32_t*>), dim3(gN), dim3(256), 0, st, sw, const_cast<PosRecord*>(rec), mask, head, w->next, nullptr, 0, 1, 0,
+                       nullptr, 0u, nullptr, nullptr, 0, 0.0, nullptr, nullptr, 0, worlds);
+    hipLaunchKernelGGL((k_query<const uint32_t*>), dim3((sw.n + 63) / 64), dim3(64), 0, st, sw, rec, n_total, my_offset, mask, head, w->next, other, T, crash, rebounce,
+                       worlds);
+    return hipGetLastError();
+  }
   if (rec_is_local_scratch)
     hipLaunchKernelGGL(k_pack_insert<false>, dim3(gN), dim3(256), 0, st, sw, const_cast<PosRecord*>(rec), mask, head, w->next, nullptr, 0, 1, 0,
                        nullptr, 0u, nullptr, nullptr, 0, 0.0, nullptr, nullptr, 0);
   else
     hipLaunchKernelGGL(k_insert<false>, dim3(gN), dim3(256), 0, st, rec, n_total, mask, head, w->next);
-  hipLaunchKernelGGL(k_query, dim3((sw.n + 63) / 64), dim3(64), 0, st, sw, rec, n_total, my_offset, mask, head, w->next, other, T, crash, rebounce);
+  hipLaunchKernelGGL((k_query<>), dim3((sw.n + 63) / 64), dim3(64), 0, st, sw, rec, n_total, my_offset, mask, head, w->next, other, T, crash, rebounce);
   return hipGetLastError();
 }
 
@@ -1198,8 +1318,9 @@ extern "C" hipError_t mrs_collide_rebuilds(const CollideWork* w, hipStream_t st,
 // Single-GPU tick with neighbour lists.  force_rebuild: the host changed positions or airframe constants since the last call.
 // guard_tau != 0: the pass is queued in stream order behind fused step launches (tick index of the last one = guard_tau): it does
 // nothing if those have stalled, and stalls what follows if the new lists come out incomplete
+// worlds: the swarm's world labels (null: a swarm that never set one — the kernels without them)
 extern "C" hipError_t mrs_collide_run_lists(SwarmDev sw, CollideWork** work, int crash, double rebounce, int force_rebuild, unsigned guard_tau,
-                                            hipStream_t st) {
+                                            const uint32_t* worlds, hipStream_t st) {
   if (!*work) *work = new CollideWork();
   CollideWork*    w = *work;
   const long long n = sw.n;
@@ -1218,10 +1339,15 @@ extern "C" hipError_t mrs_collide_run_lists(SwarmDev sw, CollideWork** work, int
   uint2*         other = w->head[tid ^ 1];
   w->cur ^= 1;
   const int ib = index_bits(n);
-  hipLaunchKernelGGL(k_pack_insert<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sw, w->rec_build, mask, head, w->next, w->ctl,
-                     w->fcur, force, tid, other, T, w->nbr, w->nbr_cnt, crash, rebounce, w->P[w->pcur], guard_tau ? w->fctl + CTL_STALL : nullptr, ib);
+  if (worlds)
+    hipLaunchKernelGGL((k_pack_insert<true, const uint32_t*>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sw, w->rec_build, mask, head, w->next, w->ctl,
+                       w->fcur, force, tid, other, T, w->nbr, w->nbr_cnt, crash, rebounce, w->P[w->pcur], guard_tau ? w->fctl + CTL_STALL : nullptr, ib,
+                       worlds);
+  else
+    hipLaunchKernelGGL(k_pack_insert<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sw, w->rec_build, mask, head, w->next, w->ctl,
+                       w->fcur, force, tid, other, T, w->nbr, w->nbr_cnt, crash, rebounce, w->P[w->pcur], guard_tau ? w->fctl + CTL_STALL : nullptr, ib);
   launch_query2<1>(query_lpu(n), sw, w->rec_build, n, 0ll, mask, ib, head, w->next, crash, rebounce, w->ctl, w->fcur, force, w->nbr, w->nbr_cnt,
-                   guard_tau ? w->fctl + CTL_STALL : nullptr, w->hostw, guard_tau, st);
+                   guard_tau ? w->fctl + CTL_STALL : nullptr, w->hostw, guard_tau, st, worlds);
   w->fcur ^= 1;  // steps launched from now on report into the flag the next tick reads
   w->lists_live = true;
   w->g_lists_live = false;

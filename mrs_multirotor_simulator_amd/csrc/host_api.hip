@@ -316,6 +316,36 @@ int get_strided(mrs_swarm* s, int f, int first, int count, double* dst, int widt
   for (int k = 0; k < count; k++) dst[(size_t)k * width + j] = s->stage[(size_t)k];
   return MRS_OK;
 }
+// ---- collision worlds: the label column exists from the first setter call on (all zeros until then) ----
+int ensure_worlds(mrs_swarm* s) {
+  if (s->dWorld) return MRS_OK;
+  HIPCHK(s->dWorld.alloc((size_t)s->npad));
+  HIPCHK(hipMemsetAsync(s->dWorld, 0, sizeof(uint32_t) * (size_t)s->npad, s->stream));
+  s->worlds_nonzero = 0;
+  return MRS_OK;
+}
+// what every setter leaves behind: the lists were built under other labels, the next collision tick searches
+void worlds_written(mrs_swarm* s) {
+  s->worlds_nonzero = -1;
+  s->nbr_dirty      = true;
+}
+// does any UAV carry a label other than 0?  (asked by the calls that refuse such a swarm; the answer is kept until the next setter)
+int worlds_any_nonzero(mrs_swarm* s, bool* any) {
+  *any = false;
+  if (!s->dWorld) return MRS_OK;
+  if (s->worlds_nonzero < 0) {
+    HIPCHK(hipSetDevice(s->device));
+    s->stage_u.resize((size_t)s->n);
+    HIPCHK(hipMemcpyAsync(s->stage_u.data(), s->dWorld, sizeof(uint32_t) * (size_t)s->n, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    s->worlds_nonzero = 0;
+    for (uint32_t w : s->stage_u)
+      if (w != 0u) s->worlds_nonzero = 1;
+  }
+  *any = s->worlds_nonzero == 1;
+  return MRS_OK;
+}
+
 int flags_update(mrs_swarm* s, int first, int count, uint32_t and_mask, uint32_t or_mask) {
   if (count <= 0) return MRS_OK;
   HIPCHK(mrs_launch_flags_update(s->dF, first, count, and_mask, or_mask, s->stream));
@@ -884,8 +914,73 @@ int mrs_swarm_clone_resized(mrs_swarm_t* s, int32_t n_uavs, mrs_swarm_t** out) {
   c->types_dirty  = true;  // the copy uploads its own type / block tables before its first launch
   c->blocks_dirty = true;
   c->nbr_dirty    = true;
+  if (s->dWorld) {  // the labels travel with their UAVs; the copy's further UAVs are in world 0
+    if ((rc = ensure_worlds(c)) == MRS_OK) {
+      e = hipMemcpyAsync(c->dWorld, s->dWorld, sizeof(uint32_t) * (size_t)s->n, hipMemcpyDeviceToDevice, c->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+      if (e != hipSuccess) rc = fail(MRS_ERR_HIP, std::string("clone: ") + hipGetErrorString(e));
+    }
+    if (rc) {
+      mrs_swarm_destroy(c);
+      return rc;
+    }
+    c->worlds_nonzero = s->worlds_nonzero;
+  }
   *out = c;
   return MRS_OK;
+}
+
+/* ---- collision worlds (include/mrs_swarm.h) ---- */
+static int worlds_setter_entry(mrs_swarm* s, int32_t first, int32_t count, const char* what) {
+  int rc = check_range(s, first, count);
+  if (rc) return rc;
+  if (s->comm_world > 0) return fail(MRS_ERR_ARG, std::string(what) + ": not on a sharded swarm");
+  return MRS_OK;
+}
+
+int mrs_swarm_set_worlds(mrs_swarm_t* s, int32_t first, int32_t count, const int32_t* worlds) {
+  MRS_ENTER(s);  // (a pending collision tick is evaluated first, under the labels it was requested with)
+  int rc = worlds_setter_entry(s, first, count, "mrs_swarm_set_worlds");
+  if (rc) return rc;
+  if (count == 0) return MRS_OK;
+  if (!worlds) return fail(MRS_ERR_ARG, "null worlds");
+  HIPCHK(hipSetDevice(s->device));
+  if ((rc = ensure_worlds(s))) return rc;
+  HIPCHK(hipMemcpyAsync(s->dWorld + first, worlds, sizeof(uint32_t) * (size_t)count, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  worlds_written(s);
+  return MRS_OK;
+}
+
+int mrs_swarm_get_worlds(mrs_swarm_t* s, int32_t first, int32_t count, int32_t* out) {
+  MRS_ENTER(s);
+  int rc = check_range(s, first, count);  // (a sharded swarm answers too: it holds no label but 0)
+  if (rc) return rc;
+  if (count == 0) return MRS_OK;
+  if (!out) return fail(MRS_ERR_ARG, "null out");
+  if (!s->dWorld) {  // no label was ever set
+    memset(out, 0, sizeof(int32_t) * (size_t)count);
+    return MRS_OK;
+  }
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipMemcpyAsync(out, s->dWorld + first, sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  return MRS_OK;
+}
+
+int mrs_swarm_set_worlds_device(mrs_swarm_t* s, int32_t first, int32_t count, const int32_t* dev_worlds, void* ext_stream) {
+  MRS_ENTER(s);
+  int rc = worlds_setter_entry(s, first, count, "mrs_swarm_set_worlds_device");
+  if (rc) return rc;
+  if (count == 0) return MRS_OK;
+  if ((rc = check_device_ptr(s, dev_worlds, sizeof(int32_t) * (size_t)count, "dev_worlds"))) return rc;
+  HIPCHK(hipSetDevice(s->device));
+  hipStream_t ext = (hipStream_t)ext_stream;
+  if ((rc = fence_in(s, ext))) return rc;
+  if ((rc = ensure_worlds(s))) return rc;  // behind the fence: a call refused up to here leaves the swarm on the kernels it had
+  HIPCHK(hipMemcpyAsync(s->dWorld + first, dev_worlds, sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToDevice, s->stream));
+  worlds_written(s);
+  return fence_out(s, ext);
 }
 
 int mrs_swarm_clone(mrs_swarm_t* s, mrs_swarm_t** out) {

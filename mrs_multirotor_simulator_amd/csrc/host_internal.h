@@ -82,9 +82,9 @@ extern "C" hipError_t mrs_launch_flags_update(uint32_t* F, int first, int count,
 extern "C" hipError_t mrs_launch_pack_positions(SwarmDev sw, PosRecord* out, hipStream_t st);
 extern "C" void       mrs_collide_step_hook(const CollideWork* w, const PosRecord** rec, uint32_t** flag, double* lim2);
 extern "C" hipError_t mrs_collide_run(SwarmDev sw, CollideWork** work, const PosRecord* rec, long long n_total, long long my_offset,
-                                      int crash, double rebounce, int rec_is_local_scratch, hipStream_t st);
+                                      int crash, double rebounce, int rec_is_local_scratch, const uint32_t* worlds, hipStream_t st);
 extern "C" hipError_t mrs_collide_run_lists(SwarmDev sw, CollideWork** work, int crash, double rebounce, int force_rebuild, unsigned guard_tau,
-                                            hipStream_t st);
+                                            const uint32_t* worlds, hipStream_t st);
 extern "C" hipError_t mrs_collide_run_lists_gathered(SwarmDev sw, CollideWork** work, const PosRecord* rec, long long n_total, long long my_offset,
                                                      int crash, double rebounce, int force_rebuild, hipStream_t st);
 extern "C" void       mrs_collide_invalidate_gathered(CollideWork* w);
@@ -314,7 +314,12 @@ struct mrs_swarm {
   DevBuf<PosRecord> dRec;
   CollideWork* cwork = nullptr;
   bool         use_lists = true;   // single-GPU collision ticks reuse neighbour lists between rebuilds (tuning: MRS_NEIGHBOUR_LISTS=0)
-  bool         nbr_dirty = true;   // the host wrote positions or airframe constants since the last collision tick
+  bool         nbr_dirty = true;   // the host wrote positions, airframe constants or world labels since the last collision tick
+  // collision worlds (mrs_swarm_set_worlds): one 32-bit label per UAV, allocated by the first setter call — until then every UAV is in
+  // world 0 and the collision pass and the nearest-neighbour search launch the kernels without labels.  The labels belong to the slot
+  // (no state call touches them); clones copy them.  worlds_nonzero: does any UAV carry a label != 0 (-1: not known since the last setter)
+  DevBuf<uint32_t> dWorld;  // [npad]
+  int              worlds_nonzero = 0;
   int64_t      collision_ticks = 0;
   // Lazily evaluated collision ticks (single-GPU neighbour lists).  handleCollisions is not launched when it is called: it is
   // evaluated by the NEXT makeStep launch, whose prologue forms the forces from the neighbour lists (step_device.inc *_coll), or
@@ -436,6 +441,7 @@ int     fill_column(mrs_swarm* s, int f, int first, int count, double value);
 int     put_strided(mrs_swarm* s, int f, int first, int count, const double* src, int width, int j);
 int     get_strided(mrs_swarm* s, int f, int first, int count, double* dst, int width, int j);
 int     flags_update(mrs_swarm* s, int first, int count, uint32_t and_mask, uint32_t or_mask);
+int     worlds_any_nonzero(mrs_swarm* s, bool* any);  // (synchronises the stream when a setter ran since it was last asked)
 // ---- tick_single.hip ----
 int  launch_part(mrs_swarm* s, double dt, int substeps, int blk0, int nblk, int with_mixed, hipStream_t st, bool imu_dead = false);
 int  launch_step(mrs_swarm* s, double dt, int substeps, bool imu_dead = false);

@@ -13,6 +13,10 @@
 //   query   one lane per query UAV: the 27 cells around its own, their buckets deduplicated (two cells can hash to one bucket, which
 //           must not be read twice), every record of those ranges tested literally; a per-lane top-KC list in registers by (d2, j);
 //           then the k slots of the row, relative quantities from the state columns of i and the listed j.
+// Collision worlds (mrs_swarm_set_worlds): once a label has been set, the world-aware instantiations of bin, scatter and query run instead
+// (the same templates with the label column as one more argument).  A mixed image of the label enters the bucket hash on the bin side and the probe side alike (the
+// copies of a forked scene spread over the table instead of sharing every bucket), the sorted record carries the label in its spare
+// word, and a candidate enters the top-k list only after its label has been compared with the query UAV's exactly.
 // Lanes walk either the query range in index order or the sorted records (all n slots, those outside the range return at once): the
 // second reads neighbouring cells across a wave (MRS_NN_ORDER).  The result depends on neither: it is defined by (d2, j).
 #include <stdlib.h>
@@ -31,9 +35,9 @@ constexpr double CELL_LIMIT = 1073741824.0;           // 2^30: clamped cell coor
 constexpr double CELL_MARGIN = 1e-6;                  // edge = radius (1 + margin): covers the rounding of x * inv_edge up to |x * inv_edge| = 2^30
 constexpr int    kNnWidth[5] = {3, 3, 3, 3, 1};
 
-struct NnRec {  // one sorted record: position and global index (32 B)
+struct NnRec {  // one sorted record: position, global index and world label (32 B)
   double  x, y, z;
-  int32_t idx, pad;
+  int32_t idx, pad;  // pad: the world label (0 when the swarm has none)
 };
 
 struct NnArgs {
@@ -55,6 +59,18 @@ __device__ __forceinline__ int cell_coord(double x, double inv_edge) {
   return (int)fmin(fmax(c, -CELL_LIMIT), CELL_LIMIT);
 }
 
+// wm: a mixed image of the world label (0 for label 0 and for swarms without labels: the hash they always had)
+__device__ __forceinline__ uint32_t world_mix(uint32_t w) {
+  w *= 0x9E3779B1u;
+  w ^= w >> 16;
+  w *= 0x85EBCA6Bu;
+  w ^= w >> 13;
+  return w;
+}
+// A world-aware kernel is the same kernel template with the label column as a trailing argument pack of one: the instantiation with the
+// empty pack has the arguments and the code it always had.
+__device__ __forceinline__ const uint32_t* world_labels() { return nullptr; }
+__device__ __forceinline__ const uint32_t* world_labels(const uint32_t* p) { return p; }
 __device__ __forceinline__ uint32_t bucket_of(int cx, int cy, int cz, uint32_t tmask) {
   uint32_t h = ((uint32_t)cx * 73856093u) ^ ((uint32_t)cy * 19349663u) ^ ((uint32_t)cz * 83492791u);
   h ^= h >> 16;
@@ -62,21 +78,35 @@ __device__ __forceinline__ uint32_t bucket_of(int cx, int cy, int cz, uint32_t t
   h ^= h >> 13;
   return h & tmask;
 }
+__device__ __forceinline__ uint32_t bucket_of(int cx, int cy, int cz, uint32_t tmask, uint32_t wm) {  // (world-aware)
+  uint32_t h = ((uint32_t)cx * 73856093u) ^ ((uint32_t)cy * 19349663u) ^ ((uint32_t)cz * 83492791u) ^ wm;
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  return h & tmask;
+}
+template <bool WORLDS> __device__ __forceinline__ uint32_t bucket_of_x(int cx, int cy, int cz, uint32_t tmask, uint32_t wm) {
+  if constexpr (WORLDS) return bucket_of(cx, cy, cz, tmask, wm); else return bucket_of(cx, cy, cz, tmask);
+}
 
 __device__ __forceinline__ bool finite3(double x, double y, double z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
 // bucket and rank of every UAV (bucket tmask + 1: non-finite position)
+// (W: empty, or the label column, const uint32_t*)
+template <class... W>
 __global__ void __launch_bounds__(NN_BLOCK) k_nn_bin(const double* S, int n, int npad, double inv_edge, uint32_t tmask, int32_t* cnt, int32_t* rank,
-                                                     int32_t* bkt) {
+                                                     int32_t* bkt, W... labels) {
+  constexpr bool WORLDS = sizeof...(W) != 0;
   const int i = blockIdx.x * NN_BLOCK + threadIdx.x;
   if (i >= n) return;
   const size_t np = (size_t)npad;
   const double x = S[(size_t)F_X * np + i], y = S[(size_t)(F_X + 1) * np + i], z = S[(size_t)(F_X + 2) * np + i];
-  const uint32_t b = finite3(x, y, z) ? bucket_of(cell_coord(x, inv_edge), cell_coord(y, inv_edge), cell_coord(z, inv_edge), tmask) : tmask + 1;
+  uint32_t wm = 0u;
+  if constexpr (WORLDS) wm = world_mix(world_labels(labels...)[i]);
+  const uint32_t b = finite3(x, y, z) ? bucket_of_x<WORLDS>(cell_coord(x, inv_edge), cell_coord(y, inv_edge), cell_coord(z, inv_edge), tmask, wm) : tmask + 1;
   rank[i] = atomicAdd(&cnt[b], 1);
   bkt[i]  = (int32_t)b;
 }
-
 // exclusive scan of the 256 lane values of a block; returns the block total in every lane
 __device__ __forceinline__ int block_exclusive_scan(int v, int* excl) {
   __shared__ int wsum[NN_BLOCK / 64];
@@ -138,8 +168,10 @@ __global__ void __launch_bounds__(NN_BLOCK) k_nn_scan_top(int32_t* bsum, int nch
 
 __device__ __forceinline__ int bucket_begin(const int32_t* start, const int32_t* bsum, uint32_t b) { return start[b] + bsum[b >> SCAN_LOG]; }
 
+template <class... W>
 __global__ void __launch_bounds__(NN_BLOCK) k_nn_scatter(const double* S, int n, int npad, const int32_t* rank, const int32_t* bkt,
-                                                         const int32_t* start, const int32_t* bsum, NnRec* rec) {
+                                                         const int32_t* start, const int32_t* bsum, NnRec* rec, W... labels) {
+  constexpr bool WORLDS = sizeof...(W) != 0;
   const int i = blockIdx.x * NN_BLOCK + threadIdx.x;
   if (i >= n) return;
   const size_t np = (size_t)npad;
@@ -149,10 +181,10 @@ __global__ void __launch_bounds__(NN_BLOCK) k_nn_scatter(const double* S, int n,
   r.z   = S[(size_t)(F_X + 2) * np + i];
   r.idx = i;
   r.pad = 0;
+  if constexpr (WORLDS) r.pad = (int32_t)world_labels(labels...)[i];
   const int slot = bucket_begin(start, bsum, (uint32_t)bkt[i]) + rank[i];
   if ((unsigned)slot < (unsigned)n) rec[slot] = r;  // (always: the slots are a permutation of [0, n))
 }
-
 // (d2, j) orders before (e2, m)
 __device__ __forceinline__ bool nn_before(double d2, int j, double e2, int m) { return d2 < e2 || (d2 == e2 && j < m); }
 
@@ -201,13 +233,17 @@ __device__ __forceinline__ void write_slot(T* o, const NnArgs& a, bool valid, in
   if (f & MRS_NN_DIST) o[0] = (T)sqrt(d2);
 }
 
-// KC: list length (>= k); SORTED: lanes walk the sorted records instead of the query range
-template <int KC, typename T, bool SORTED>
-__global__ void __launch_bounds__(NN_BLOCK) k_nn_query(NnArgs a) {
+// KC: list length (>= k); SORTED: lanes walk the sorted records instead of the query range; WORLDS: only UAVs that carry the query
+// UAV's label are candidates (wlab = the label column; the records carry the labels too)
+template <int KC, typename T, bool SORTED, class... W>
+__global__ void __launch_bounds__(NN_BLOCK) k_nn_query(NnArgs a, W... labels) {
+  constexpr bool  WORLDS = sizeof...(W) != 0;
+  const uint32_t* wlab   = world_labels(labels...);
   const int    q  = blockIdx.x * NN_BLOCK + threadIdx.x;
   const size_t np = (size_t)a.npad;
   int          i;
   double       xi, yi, zi;
+  int32_t      myw = 0;  // (the query UAV's label; unused without labels)
   if (SORTED) {
     if (q >= a.n) return;
     const NnRec r = a.rec[q];
@@ -216,14 +252,18 @@ __global__ void __launch_bounds__(NN_BLOCK) k_nn_query(NnArgs a) {
     xi = r.x;
     yi = r.y;
     zi = r.z;
+    if constexpr (WORLDS) myw = r.pad;
   } else {
     if (q >= a.count) return;
     i  = a.first + q;
     xi = a.S[(size_t)F_X * np + i];
     yi = a.S[(size_t)(F_X + 1) * np + i];
     zi = a.S[(size_t)(F_X + 2) * np + i];
+    if constexpr (WORLDS) myw = (int32_t)wlab[i];
   }
   const int row = i - a.first;
+  uint32_t  wm  = 0u;
+  if constexpr (WORLDS) wm = world_mix((uint32_t)myw);
 
   double ld[KC];
   int    lj[KC];
@@ -238,7 +278,7 @@ __global__ void __launch_bounds__(NN_BLOCK) k_nn_query(NnArgs a) {
     // the 27 buckets; bit p of `dup`: probe p hits a bucket an earlier probe reads already
     uint32_t bk[27];
 #pragma unroll
-    for (int p = 0; p < 27; p++) bk[p] = bucket_of(cx + p % 3 - 1, cy + (p / 3) % 3 - 1, cz + p / 9 - 1, a.tmask);
+    for (int p = 0; p < 27; p++) bk[p] = bucket_of_x<WORLDS>(cx + p % 3 - 1, cy + (p / 3) % 3 - 1, cz + p / 9 - 1, a.tmask, wm);
     uint32_t dup = 0;
 #pragma unroll
     for (int p = 1; p < 27; p++) {
@@ -249,7 +289,7 @@ __global__ void __launch_bounds__(NN_BLOCK) k_nn_query(NnArgs a) {
     }
     for (int p = 0; p < 27; p++) {
       if (dup & (1u << p)) continue;
-      const uint32_t b   = bucket_of(cx + p % 3 - 1, cy + (p / 3) % 3 - 1, cz + p / 9 - 1, a.tmask);
+      const uint32_t b   = bucket_of_x<WORLDS>(cx + p % 3 - 1, cy + (p / 3) % 3 - 1, cz + p / 9 - 1, a.tmask, wm);
       const int      beg = bucket_begin(a.start, a.bsum, b), end = min(beg + a.cnt[b], a.n);
       for (int s = beg; s < end; s++) {
         const NnRec  r  = a.rec[s];
@@ -257,6 +297,7 @@ __global__ void __launch_bounds__(NN_BLOCK) k_nn_query(NnArgs a) {
         const double d2 = ((dx * dx) + dy * dy) + dz * dz;
         const int    j  = r.idx;
         if (!(d2 < a.rr) || j == i || (unsigned)j >= (unsigned)a.n) continue;
+        if (WORLDS && r.pad != myw) continue;  // another world: never a neighbour, however close
         found++;
         if (!nn_before(d2, j, ld[KC - 1], lj[KC - 1])) continue;
         // insertion into the sorted list, from the back (every slot decided from the old values of its own and the one before)
@@ -301,11 +342,17 @@ __global__ void __launch_bounds__(NN_BLOCK) k_nn_query(NnArgs a) {
   for (int m = 0; m < KC; m++)
     if (m < a.k) write_slot(o + (size_t)m * (size_t)a.width, a, m < nf, lj[m], ld[m], xs, vi, R);
 }
-
 inline dim3 grid_of(int count) { return dim3((unsigned)((count + NN_BLOCK - 1) / NN_BLOCK)); }
 
 template <int KC, typename T>
-void launch_query(const NnArgs& a, bool sorted, hipStream_t st) {
+void launch_query(const NnArgs& a, bool sorted, hipStream_t st, const uint32_t* wlab) {
+  if (wlab) {
+    if (sorted)
+      hipLaunchKernelGGL((k_nn_query<KC, T, true, const uint32_t*>), grid_of(a.n), dim3(NN_BLOCK), 0, st, a, wlab);
+    else
+      hipLaunchKernelGGL((k_nn_query<KC, T, false, const uint32_t*>), grid_of(a.count), dim3(NN_BLOCK), 0, st, a, wlab);
+    return;
+  }
   if (sorted)
     hipLaunchKernelGGL((k_nn_query<KC, T, true>), grid_of(a.n), dim3(NN_BLOCK), 0, st, a);
   else
@@ -313,13 +360,13 @@ void launch_query(const NnArgs& a, bool sorted, hipStream_t st) {
 }
 
 template <typename T>
-void launch_query_k(const NnArgs& a, bool sorted, hipStream_t st) {
+void launch_query_k(const NnArgs& a, bool sorted, hipStream_t st, const uint32_t* wlab) {
   if (a.k <= 8)
-    launch_query<8, T>(a, sorted, st);
+    launch_query<8, T>(a, sorted, st, wlab);
   else if (a.k <= 16)
-    launch_query<16, T>(a, sorted, st);
+    launch_query<16, T>(a, sorted, st, wlab);
   else
-    launch_query<32, T>(a, sorted, st);
+    launch_query<32, T>(a, sorted, st, wlab);
 }
 
 // lane order of the query: MRS_NN_ORDER=index / sorted; default (auto): sorted records when the query range covers at least a quarter
@@ -396,10 +443,17 @@ int mrs_swarm_nearest_device(mrs_swarm_t* s, int32_t first, int32_t count, int32
   if ((rc = fence_in(s, ext))) return rc;
   const double inv_edge = 1.0 / (radius * (1.0 + CELL_MARGIN));
   HIPCHK(hipMemsetAsync(cnt, 0, sizeof(int32_t) * ncnt, s->stream));
-  hipLaunchKernelGGL(k_nn_bin, grid_of(n), dim3(NN_BLOCK), 0, s->stream, s->dS, n, s->npad, inv_edge, T - 1, cnt, rank, bkt);
+  const uint32_t* wlab = s->dWorld;  // null: no label was ever set — the kernels without them
+  if (wlab)
+    hipLaunchKernelGGL((k_nn_bin<const uint32_t*>), grid_of(n), dim3(NN_BLOCK), 0, s->stream, s->dS, n, s->npad, inv_edge, T - 1, cnt, rank, bkt, wlab);
+  else
+    hipLaunchKernelGGL((k_nn_bin<>), grid_of(n), dim3(NN_BLOCK), 0, s->stream, s->dS, n, s->npad, inv_edge, T - 1, cnt, rank, bkt);
   hipLaunchKernelGGL(k_nn_scan_chunks, dim3((unsigned)nchunks), dim3(NN_BLOCK), 0, s->stream, cnt, start, bsum);
   hipLaunchKernelGGL(k_nn_scan_top, dim3(1), dim3(NN_BLOCK), 0, s->stream, bsum, nchunks);
-  hipLaunchKernelGGL(k_nn_scatter, grid_of(n), dim3(NN_BLOCK), 0, s->stream, s->dS, n, s->npad, rank, bkt, start, bsum, rec);
+  if (wlab)
+    hipLaunchKernelGGL((k_nn_scatter<const uint32_t*>), grid_of(n), dim3(NN_BLOCK), 0, s->stream, s->dS, n, s->npad, rank, bkt, start, bsum, rec, wlab);
+  else
+    hipLaunchKernelGGL((k_nn_scatter<>), grid_of(n), dim3(NN_BLOCK), 0, s->stream, s->dS, n, s->npad, rank, bkt, start, bsum, rec);
   NnArgs a;
   a.S = s->dS;
   a.n = n;
@@ -423,9 +477,9 @@ int mrs_swarm_nearest_device(mrs_swarm_t* s, int32_t first, int32_t count, int32
   a.counts = dev_count;
   const bool sorted = nn_order() >= 0 ? nn_order() == 1 : 4LL * count >= n;
   if (dtype == MRS_DTYPE_F32)
-    launch_query_k<float>(a, sorted, s->stream);
+    launch_query_k<float>(a, sorted, s->stream, wlab);
   else
-    launch_query_k<double>(a, sorted, s->stream);
+    launch_query_k<double>(a, sorted, s->stream, wlab);
   HIPCHK(hipGetLastError());
   return fence_out(s, ext);
 }

@@ -21,6 +21,9 @@ int comm_allgather(mrs_swarm* s, const void* send, void* recv, size_t bytes) {
 int comm_setup(mrs_swarm* s, int world, int rank, int64_t n_total) {
   if (world < 1 || rank < 0 || rank >= world || n_total < s->n) return fail(MRS_ERR_ARG, "bad communicator shape");
   if (s->comm_world > 0) return fail(MRS_ERR_ARG, "communicator already initialised");
+  bool labelled = false;
+  if (int rcw = worlds_any_nonzero(s, &labelled)) return rcw;
+  if (labelled) return fail(MRS_ERR_ARG, "this swarm holds collision-world labels other than 0: sharded swarms have one world");
   const int64_t base = n_total / world, rem = n_total % world;
   const int64_t mine = base + (rank < rem ? 1 : 0);  // equal-count shards, sizes differ by at most one
   if (mine != s->n) return fail(MRS_ERR_ARG, "this swarm does not hold the shard of its rank (n_total / world UAVs, the first n_total % world ranks one more)");
@@ -227,7 +230,7 @@ int full_gather_ticks(mrs_swarm* s, double dt, int n_ticks, const mrs_swarm::Col
     if (s->use_lists)
       HIPCHK(mrs_collide_run_lists_gathered(s->view(), &s->cwork, s->comm_recv, n_rec, (int64_t)s->comm_rank * s->comm_n_max, c.crash, c.rebounce, 0, s->stream));
     else
-      HIPCHK(mrs_collide_run(s->view(), &s->cwork, s->comm_recv, n_rec, (int64_t)s->comm_rank * s->comm_n_max, c.crash, c.rebounce, 0, s->stream));
+      HIPCHK(mrs_collide_run(s->view(), &s->cwork, s->comm_recv, n_rec, (int64_t)s->comm_rank * s->comm_n_max, c.crash, c.rebounce, 0, nullptr, s->stream));
   }
   return MRS_OK;
 }

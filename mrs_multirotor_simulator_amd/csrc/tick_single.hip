@@ -122,7 +122,7 @@ int finish_profile(mrs_swarm* s) {
 int collide_now(mrs_swarm* s, const mrs_swarm::Collide& c, bool force) {
   int rc = upload_types(s, s->table_dt > 0 ? s->table_dt : 0.001);
   if (rc) return rc;
-  HIPCHK(mrs_collide_run_lists(s->view(), &s->cwork, c.crash, c.rebounce, (force || s->nbr_dirty) ? 1 : 0, 0u, s->stream));
+  HIPCHK(mrs_collide_run_lists(s->view(), &s->cwork, c.crash, c.rebounce, (force || s->nbr_dirty) ? 1 : 0, 0u, s->dWorld, s->stream));
   s->nbr_dirty = false;
   s->f_lazy.on = false;  // the pass latched this tick's force
   s->p_valid = true;  // the pass refreshed the position records
@@ -414,7 +414,7 @@ int step_one(mrs_swarm* s, double dt, const RolloutTickDev* row, const RolloutTi
         // some UAV has used up most of its skin: repeat the search NOW, in stream order — it evaluates the pending collision tick
         // itself — instead of running into the stall a few ticks on (no synchronisation, nothing to replay)
         if ((rc = upload_types(s, dt))) return rc;
-        HIPCHK(mrs_collide_run_lists(s->view(), &s->cwork, s->pend.crash, s->pend.rebounce, 1, s->tau, s->stream));  // (tau >= 1: the warning came from a launch of this log)
+        HIPCHK(mrs_collide_run_lists(s->view(), &s->cwork, s->pend.crash, s->pend.rebounce, 1, s->tau, s->dWorld, s->stream));  // (tau >= 1: the warning came from a launch of this log)
         e.searched     = true;
         s->search_mark = s->tau;
         s->n_ahead_searches++;
@@ -562,6 +562,9 @@ int mrs_swarm_handle_collisions_gathered(mrs_swarm_t* s, const void* dev_records
   if (!s) return fail(MRS_ERR_ARG, "null swarm");
   if (!(crash || enabled)) return MRS_OK;  // src/multirotor_simulator.cpp:299-301
   if (!dev_records || n_total < s->n || my_offset < 0 || my_offset + s->n > n_total) return fail(MRS_ERR_ARG, "bad gathered-record arguments");
+  bool labelled = false;  // (gathered records carry no labels)
+  if (int rcw = worlds_any_nonzero(s, &labelled)) return rcw;
+  if (labelled) return fail(MRS_ERR_ARG, "this swarm holds collision-world labels other than 0: gathered records have one world");
   if (s->n == 0) return MRS_OK;
   HIPCHK(hipSetDevice(s->device));
   s->fext_active = true;
@@ -570,7 +573,7 @@ int mrs_swarm_handle_collisions_gathered(mrs_swarm_t* s, const void* dev_records
   if (s->use_lists)
     HIPCHK(mrs_collide_run_lists_gathered(s->view(), &s->cwork, (const PosRecord*)dev_records, n_total, my_offset, crash, rebounce, 0, s->stream));
   else
-    HIPCHK(mrs_collide_run(s->view(), &s->cwork, (const PosRecord*)dev_records, n_total, my_offset, crash, rebounce, 0, s->stream));
+    HIPCHK(mrs_collide_run(s->view(), &s->cwork, (const PosRecord*)dev_records, n_total, my_offset, crash, rebounce, 0, nullptr, s->stream));
   return MRS_OK;
 }
 
@@ -596,7 +599,7 @@ int mrs_swarm_handle_collisions(mrs_swarm_t* s, int32_t enabled, int32_t crash, 
   if ((rc = upload_types(s, s->table_dt > 0 ? s->table_dt : 0.001))) return rc;
   s->fext_active = true;
   HIPCHK(s->dRec.reserve((size_t)s->npad));
-  HIPCHK(mrs_collide_run(s->view(), &s->cwork, s->dRec, s->n, 0, crash, rebounce, /*rec_is_local_scratch=*/1, s->stream));
+  HIPCHK(mrs_collide_run(s->view(), &s->cwork, s->dRec, s->n, 0, crash, rebounce, /*rec_is_local_scratch=*/1, s->dWorld, s->stream));
   return MRS_OK;
 }
 
@@ -650,7 +653,7 @@ int mrs_swarm_debug_search_ms(mrs_swarm_t* s, int32_t reps, int32_t crash, doubl
   if ((rc = collide_now(s, c, /*force=*/true))) return rc;  // buffers exist, tables are in their steady state
   if ((rc = ensure_events(s, 2))) return rc;
   HIPCHK(hipEventRecord(s->ev[0], s->stream));
-  for (int k = 0; k < reps; k++) HIPCHK(mrs_collide_run_lists(s->view(), &s->cwork, crash, rebounce, 1, 0u, s->stream));
+  for (int k = 0; k < reps; k++) HIPCHK(mrs_collide_run_lists(s->view(), &s->cwork, crash, rebounce, 1, 0u, s->dWorld, s->stream));
   HIPCHK(hipEventRecord(s->ev[1], s->stream));
   HIPCHK(hipStreamSynchronize(s->stream));
   float ms = 0;

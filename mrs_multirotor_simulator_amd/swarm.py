@@ -121,6 +121,7 @@ ABI_SYMBOLS = [
     "mrs_swarm_rollout_tick_device",
     "mrs_swarm_rollout_tick_cost_device",
     "mrs_swarm_rollout_tick_feedback_device",
+    "mrs_swarm_set_worlds", "mrs_swarm_get_worlds", "mrs_swarm_set_worlds_device",
 ]
 
 # device-resident callers (mrs_swarm_*_device): row element types and the observation groups of mrs_swarm_gather_device, in bit order
@@ -356,6 +357,9 @@ def load_library():
         "mrs_swarm_gather_device": [vp, i32, i32, C.c_uint32, vp, i32, i32, vp],
         "mrs_swarm_get_crashed_device": [vp, i32, i32, vp, vp],
         "mrs_swarm_reset_device": [vp, i32, i32, vp, vp, vp, i32, i32, vp],
+        "mrs_swarm_set_worlds": [vp, i32, i32, ip],
+        "mrs_swarm_get_worlds": [vp, i32, i32, ip],
+        "mrs_swarm_set_worlds_device": [vp, i32, i32, vp, vp],
         "mrs_nearest_width": [C.c_uint32, i32, ip],
         "mrs_swarm_nearest_device": [vp, i32, i32, i32, C.c_double, C.c_uint32, vp, i32, i32, vp, i32, vp, vp],
         "mrs_swarm_save_device": [vp, i32, i32, vp, vp],
@@ -530,6 +534,22 @@ class Swarm:
     def set_hold(self, first, count, hold):
         """UAVs on hold are not iterated by step/tick (UavSystemRos without input and iterate_without_input == false)."""
         _check(_lib.mrs_swarm_set_hold(self._h, int(first), int(count), int(bool(hold))))
+
+    def set_worlds(self, worlds, first=0):
+        """Collision-world labels of UAVs [first, first + len(worlds)) (mrs_swarm_set_worlds): UAVs interact through the collision pass, and
+        appear in each other's nearest-neighbour rows, only if their labels are equal.  Any int32 value; 0 until set."""
+        w = np.ascontiguousarray(worlds, dtype=np.int32).reshape(-1)
+        _check(_lib.mrs_swarm_set_worlds(self._h, int(first), int(w.size), w.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    def get_worlds(self, first=0, count=None):
+        """the labels of UAVs [first, first + count) as an int32 array (mrs_swarm_get_worlds): zeros when none was ever set"""
+        count = self.n - first if count is None else int(count)
+        out = np.zeros(max(count, 0), dtype=np.int32)
+        _check(_lib.mrs_swarm_get_worlds(self._h, int(first), int(count), out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def set_worlds_device(self, first, count, dev_worlds, ext_stream):
+        _check(_lib.mrs_swarm_set_worlds_device(self._h, int(first), int(count), dev_worlds or None, ext_stream or None))
 
     def collision_stats(self):
         """(collision ticks, ticks that repeated the neighbour search)"""

@@ -643,6 +643,20 @@ def nearest(swarm, k, radius, fields=NN_REL_POS | NN_DIST, first=0, count=None, 
     return rows, (index[:, :k] if index.shape[1] > k else index), counts
 
 
+def set_worlds(swarm, worlds, first=0):
+    """Collision-world labels of UAVs [first, first + len(worlds)) from an int32 vector on the swarm's device
+    (mrs_swarm_set_worlds_device): UAVs interact through the collision pass, and appear in each other's rows of nearest(), only if
+    their labels are equal.  The fork of a planner: save the M-UAV scene, load(index=i % M) into S * M UAVs, set_worlds(i // M)."""
+    if not isinstance(worlds, torch.Tensor) or worlds.dim() != 1:
+        raise ValueError("worlds must be an int32 vector")
+    count = worlds.shape[0]
+    if first < 0 or first + count > swarm.n:
+        raise ValueError(f"{count} labels from UAV {first} on do not fit a swarm of {swarm.n} UAVs")
+    dev = swarm.device()
+    check_tensor(worlds, count, None, torch.int32, dev)
+    swarm.set_worlds_device(first, count, worlds.data_ptr(), _stream(dev))
+
+
 def _check_records(records, rows, dev):
     """records: a dense torch.uint8 [rows, SNAP_BYTES] tensor on the swarm's device, 16-B aligned"""
     check_tensor(records, rows, SNAP_BYTES, torch.uint8, dev)

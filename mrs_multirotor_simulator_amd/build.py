@@ -32,7 +32,7 @@ UNITS = [
     ("transport_local.hip", "off"),
     ("transport_peer.hip", "off"),
 ]
-DEPS = ["step_device.inc", "rollout_device.inc", "rollout_rate_device.inc", "rollout_cost_device.inc", "rollout_tick_feedback_device.inc", "rollout_tick_cost_device.inc", "rollout_tick_device.inc", "collide_device.inc", "collide_work.h", "swarm_layout.h", "pose_math.h", "obs_row.h", "hip_owned.h", "host_internal.h", "sharded_protocol.h", os.path.join("..", "..", "include", "mrs_swarm.h")]
+DEPS = ["step_device.inc", "rollout_device.inc", "rollout_rate_device.inc", "rollout_cost_device.inc", "rollout_tick_device.inc", "collide_device.inc", "collide_work.h", "swarm_layout.h", "pose_math.h", "obs_row.h", "hip_owned.h", "host_internal.h", "sharded_protocol.h", os.path.join("..", "..", "include", "mrs_swarm.h")]
 
 
 def _hipcc():

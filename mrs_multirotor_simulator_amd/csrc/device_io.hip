@@ -397,6 +397,7 @@ struct RolloutArgs {
   uint8_t*    dev_crashed;
   int32_t     crash;
   double      rebounce;
+  double      crash_cost;  // (the two costed tick rollouts)
 };
 // what the checks work out on their way
 struct RolloutWidths {
@@ -622,9 +623,120 @@ int mrs_swarm_rollout_feedback_device(mrs_swarm_t* s, int32_t first, int32_t cou
   return rollout_locked(s, a);
 }
 
-// timerMain over n_ticks ticks with caller rows: every tick is step_one (tick_single.hip) with the row blocks of that tick, then the
-// tick's handleCollisions stays pending as after mrs_swarm_tick_n.  The launches of the call carry their row descriptors through the
-// stall / replay log, and the call drains the log before it returns.
+// The tick rollouts are timerMain over n_ticks ticks with what each tick carries of the caller's memory (mrs_swarm::TickLoad): every
+// tick is step_one (tick_single.hip) with that tick's pointers, then the tick's handleCollisions stays pending as after
+// mrs_swarm_tick_n.  The launches of the call carry their descriptors through the stall / replay log, and the call drains the log
+// before it returns.
+
+// what every tick of the call carries alike: the descriptor of the call's kind without a pointer
+static mrs_swarm::TickLoad tick_load(const RolloutArgs& a, const RolloutWidths& w) {
+  mrs_swarm::TickLoad p;
+  const uint32_t cmd_word = (uint32_t)w.cmd | (a.dtype == MRS_DTYPE_F32 ? 32u : 0u), mode_bits = (uint32_t)a.mode << FLAG_MODE_SHIFT;
+  if (a.kind == ROLLOUT_TICK) {
+    p.kind = mrs_swarm::TickLoad::ROWS;
+    RolloutTickDev& r = p.row = RolloutTickDev{};
+    r.first = a.first, r.count = a.count;
+    r.cmd_stride = a.cmd_stride, r.obs_stride = a.obs_stride;
+    r.cmd_word = cmd_word, r.groups = a.groups, r.mode_bits = mode_bits;
+  } else if (a.kind == ROLLOUT_TICK_COST) {
+    p.kind = mrs_swarm::TickLoad::COST;
+    RolloutTickCostDev& c = p.cost = RolloutTickCostDev{};
+    c.first = a.first, c.count = a.count;
+    c.cmd_stride = a.cmd_stride;
+    c.tgt_row = a.target_stride, c.wt_row = a.weight_stride, c.width = w.obs;
+    c.cmd_word = cmd_word, c.groups = a.groups, c.mode_bits = mode_bits;
+    c.crash_cost = a.crash_cost;
+  } else {
+    p.kind = mrs_swarm::TickLoad::FEEDBACK;
+    RolloutTickFeedbackDev& f = p.fb = RolloutTickFeedbackDev{};
+    f.first = a.first, f.count = a.count;
+    f.cmd_stride = a.cmd_stride;
+    f.ref_row = a.ref_stride, f.tgt_row = a.target_stride;
+    f.gain_lane = a.gain_per_uav ? 1 : 0, f.gain_col = a.gain_per_uav ? (uint32_t)a.count : 1u;
+    f.fb_word  = a.fb_groups | (uint32_t)w.fb << 8;
+    f.cmd_word = cmd_word, f.groups = a.groups, f.mode_bits = mode_bits;
+    f.crash_cost = a.crash_cost;
+  }
+  return p;
+}
+
+// block `blk` of a call's blocks, which lie `per_blk` elements of `elem` bytes apart (none: null)
+static const void* tick_block(const void* base, long long blk, size_t per_blk, size_t elem) {
+  return blk >= 0 ? static_cast<const char*>(base) + (size_t)blk * per_blk * elem : nullptr;
+}
+// The pointers of tick t: the blocks that start at it (commands; gains and setpoints, of which one block may serve every command
+// block) and the blocks that end with it (observation and crash rows; the evaluation).  An empty range has none.
+static void tick_pointers(mrs_swarm::TickLoad& p, const RolloutArgs& a, const RolloutWidths& w, int t) {
+  const size_t    elem = dtype_bytes(a.dtype), count = (size_t)a.count;
+  const long long b    = a.count > 0 && w.cmd > 0 ? mrs_tick_block_start(t, a.cmd_every, a.n_steps / a.cmd_every) : -1;
+  const long long j    = a.count > 0 && (w.costed || a.kind == ROLLOUT_TICK) ? mrs_tick_block_end(t, a.obs_every, a.n_steps / a.obs_every) : -1;
+  const void*     cmd  = tick_block(a.dev_cmd, b, count * (size_t)a.cmd_stride, elem);
+  // the evaluation that ends with a tick of a costed tick rollout: the caller's vector, and with cost groups the evaluation's target
+  // rows (a row per UAV, or one dense row for all) and weight row
+  auto evaluation = [&](auto& d) {
+    const long long rows    = a.groups != 0u ? j : -1;
+    const size_t    tgt_blk = a.target_stride ? count * (size_t)a.target_stride : (size_t)w.obs;
+    d.cost   = j >= 0 ? a.cost : nullptr;
+    d.target = tick_block(a.target, rows, tgt_blk, elem);
+    d.weight = tick_block(a.weight, rows, (size_t)a.weight_stride, elem);
+  };
+  switch (p.kind) {
+    case mrs_swarm::TickLoad::ROWS:
+      p.row.cmd     = cmd;
+      p.row.obs     = a.groups != 0u ? const_cast<void*>(tick_block(a.dev_obs, j, count * (size_t)a.obs_stride, elem)) : nullptr;
+      p.row.crashed = a.dev_crashed && j >= 0 ? a.dev_crashed + (size_t)j * count : nullptr;
+      break;
+    case mrs_swarm::TickLoad::COST:
+      p.cost.cmd = cmd;
+      evaluation(p.cost);
+      break;
+    case mrs_swarm::TickLoad::FEEDBACK: {
+      const size_t per      = a.gain_per_uav ? count : (size_t)1;
+      const size_t gain_blk = a.gain_blocks == 1 ? 0u : (size_t)w.cmd * (size_t)w.fb * per;
+      const size_t ref_blk  = a.ref_blocks == 1 ? 0u : a.ref_stride ? count * (size_t)a.ref_stride : (size_t)w.fb;
+      p.fb.cmd  = cmd;
+      p.fb.gain = tick_block(a.gain, b, gain_blk, elem);
+      p.fb.ref  = tick_block(a.ref, b, ref_blk, elem);
+      evaluation(p.fb);
+      break;
+    }
+    case mrs_swarm::TickLoad::NONE: break;
+  }
+}
+
+// the three tick rollout entry points, under the caller's lock
+static int rollout_tick_locked(mrs_swarm_t* s, const RolloutArgs& a) {
+  RolloutWidths w;
+  int           rc = check_rollout_args(s, a, "n_ticks", a.kind == ROLLOUT_TICK ? "obs_every" : "cost_every", w);
+  if (rc) return rc;
+  if (s->n == 0) return MRS_OK;
+  HIPCHK(hipSetDevice(s->device));
+  // like a command call: launches queued by earlier calls must have run before the mode mirror (which picks the kernel variant of a
+  // replay) changes; a collision tick pending at entry stays pending — the first launch of this call evaluates it
+  if (!s->log.empty() && (rc = drain(s))) return rc;
+  if ((rc = upload_types(s, a.dt))) return rc;
+  rollout_track_mode(s, a);
+  hipStream_t ext = (hipStream_t)a.ext_stream;
+  if ((rc = fence_in(s, ext))) return rc;
+  if ((rc = begin_profile(s))) return rc;
+  // dev_cost is zeroed once on the swarm's stream, behind the entry fence and in front of the first launch, unless the call
+  // accumulates; the memset is not part of the launch log, so a replay after a stall does not repeat it, and the replayed launches add
+  // what their no-ops did not.  (A feedback tick rollout without a dev_cost evaluates nothing: a pure closed-loop run.)
+  if (w.costed && a.count > 0 && !a.accumulate) HIPCHK(hipMemsetAsync(a.cost, 0, (size_t)a.count * sizeof(double), s->stream));  // (+0.0)
+  mrs_swarm::TickLoad p = tick_load(a, w);
+  for (int t = 0; t < a.n_steps; t++) {
+    tick_pointers(p, a, w, t);
+    if ((rc = step_one(s, a.dt, &p))) return rc;
+    if ((rc = mrs_swarm_handle_collisions(s, 1, a.crash, a.rebounce))) return rc;
+  }
+  // nothing of this call stays in the log: a replay after a stall writes into the caller's rows, reads the caller's rows and gains and
+  // adds to the caller's vector, which are only guaranteed to live until the call returns (one host wait per call); the last tick's
+  // collision stays pending
+  if ((rc = drain(s))) return rc;
+  if ((rc = finish_profile(s))) return rc;
+  return fence_out(s, ext);
+}
+
 int mrs_swarm_rollout_tick_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_ticks, int32_t cmd_every,
                                   int32_t obs_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t groups, void* dev_obs,
                                   int32_t obs_stride, uint8_t* dev_crashed, int32_t crash, double rebounce, void* ext_stream) {
@@ -632,51 +744,10 @@ int mrs_swarm_rollout_tick_device(mrs_swarm_t* s, int32_t first, int32_t count, 
   RolloutArgs a{"mrs_swarm_rollout_tick_device", ROLLOUT_TICK, first, count, mode, dt, n_ticks, cmd_every, obs_every, dev_cmd, dtype, cmd_stride, groups,
                 dev_obs, obs_stride, ext_stream};
   a.dev_crashed = dev_crashed, a.crash = crash, a.rebounce = rebounce;
-  RolloutWidths w;
-  int           rc = check_rollout_args(s, a, "n_ticks", "obs_every", w);
-  if (rc) return rc;
-  const int    width = w.cmd;
-  const size_t elem  = dtype_bytes(dtype);
-  if (s->n == 0) return MRS_OK;
-  HIPCHK(hipSetDevice(s->device));
-  // like a command call: launches queued by earlier calls must have run before the mode mirror (which picks the kernel variant of a
-  // replay) changes; a collision tick pending at entry stays pending — the first launch of this call evaluates it
-  if (!s->log.empty() && (rc = drain(s))) return rc;
-  if ((rc = upload_types(s, dt))) return rc;
-  rollout_track_mode(s, a);
-  hipStream_t ext = (hipStream_t)ext_stream;
-  if ((rc = fence_in(s, ext))) return rc;
-  if ((rc = begin_profile(s))) return rc;
-  RolloutTickDev row{};
-  row.first = first, row.count = count;
-  row.cmd_stride = cmd_stride, row.obs_stride = obs_stride;
-  row.cmd_word  = (uint32_t)width | (dtype == MRS_DTYPE_F32 ? 32u : 0u);
-  row.groups    = groups;
-  row.mode_bits = (uint32_t)mode << FLAG_MODE_SHIFT;
-  for (int t = 0; t < n_ticks; t++) {
-    row.cmd = row.obs = nullptr;
-    row.crashed = nullptr;
-    if (count > 0 && width > 0 && t % cmd_every == 0)
-      row.cmd = static_cast<const char*>(dev_cmd) + (size_t)(t / cmd_every) * (size_t)count * (size_t)cmd_stride * elem;
-    if (count > 0 && (t + 1) % obs_every == 0) {
-      const size_t j = (size_t)((t + 1) / obs_every - 1);
-      if (groups != 0u) row.obs = static_cast<char*>(dev_obs) + j * (size_t)count * (size_t)obs_stride * elem;
-      if (dev_crashed) row.crashed = dev_crashed + j * (size_t)count;
-    }
-    if ((rc = step_one(s, dt, &row))) return rc;
-    if ((rc = mrs_swarm_handle_collisions(s, 1, crash, rebounce))) return rc;
-  }
-  // a replay after a stall writes into the caller's rows, which are only guaranteed to live until the call returns: nothing of this
-  // call stays in the log (one host wait per call); the last tick's collision stays pending
-  if ((rc = drain(s))) return rc;
-  if ((rc = finish_profile(s))) return rc;
-  return fence_out(s, ext);
+  return rollout_tick_locked(s, a);
 }
 
-// mrs_swarm_rollout_tick_device whose ticks carry an evaluation in place of row blocks: the same loop of step_one and pending
-// collision ticks, the same single drain.  dev_cost is zeroed once on the swarm's stream, behind the entry fence and in front of the
-// first launch, unless the call accumulates; the memset is not part of the launch log, so a replay after a stall does not repeat it,
-// and the replayed launches add what their no-ops did not.
+// mrs_swarm_rollout_tick_device whose ticks carry an evaluation in place of row blocks
 int mrs_swarm_rollout_tick_cost_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_ticks, int32_t cmd_every,
                                        int32_t cost_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t groups,
                                        const void* dev_target, int32_t target_stride, const void* dev_weight, int32_t weight_stride,
@@ -686,58 +757,12 @@ int mrs_swarm_rollout_tick_cost_device(mrs_swarm_t* s, int32_t first, int32_t co
                 groups, nullptr, 0, ext_stream};
   a.target = dev_target, a.target_stride = target_stride, a.weight = dev_weight, a.weight_stride = weight_stride;
   a.cost = dev_cost, a.accumulate = accumulate;
-  a.crash = crash, a.rebounce = rebounce;
-  RolloutWidths w;
-  int           rc = check_rollout_args(s, a, "n_ticks", "cost_every", w);
-  if (rc) return rc;
-  const int    width = w.cmd;
-  const size_t elem  = dtype_bytes(dtype);
-  if (s->n == 0) return MRS_OK;
-  HIPCHK(hipSetDevice(s->device));
-  if (!s->log.empty() && (rc = drain(s))) return rc;  // (as mrs_swarm_rollout_tick_device: a collision tick pending at entry stays pending)
-  if ((rc = upload_types(s, dt))) return rc;
-  rollout_track_mode(s, a);
-  hipStream_t ext = (hipStream_t)ext_stream;
-  if ((rc = fence_in(s, ext))) return rc;
-  if ((rc = begin_profile(s))) return rc;
-  if (count > 0 && !accumulate) HIPCHK(hipMemsetAsync(dev_cost, 0, (size_t)count * sizeof(double), s->stream));  // (+0.0)
-  RolloutTickCostDev c{};
-  c.first = first, c.count = count;
-  c.cmd_stride = cmd_stride;
-  c.tgt_row = target_stride, c.wt_row = weight_stride, c.width = w.obs;
-  c.cmd_word   = (uint32_t)width | (dtype == MRS_DTYPE_F32 ? 32u : 0u);
-  c.groups     = groups;
-  c.mode_bits  = (uint32_t)mode << FLAG_MODE_SHIFT;
-  c.crash_cost = crash_cost;
-  // elements between two target row blocks: a row per UAV, or one dense row for all
-  const size_t tgt_blk = target_stride ? (size_t)count * (size_t)target_stride : (size_t)w.obs;
-  for (int t = 0; t < n_ticks; t++) {
-    c.cmd = c.target = c.weight = nullptr;
-    c.cost = nullptr;
-    if (count > 0 && width > 0 && t % cmd_every == 0)
-      c.cmd = static_cast<const char*>(dev_cmd) + (size_t)(t / cmd_every) * (size_t)count * (size_t)cmd_stride * elem;
-    if (count > 0 && (t + 1) % cost_every == 0) {
-      const size_t j = (size_t)((t + 1) / cost_every - 1);
-      c.cost = dev_cost;
-      if (groups != 0u) {
-        c.target = static_cast<const char*>(dev_target) + j * tgt_blk * elem;
-        c.weight = static_cast<const char*>(dev_weight) + j * (size_t)weight_stride * elem;
-      }
-    }
-    if ((rc = step_one(s, dt, nullptr, &c))) return rc;
-    if ((rc = mrs_swarm_handle_collisions(s, 1, crash, rebounce))) return rc;
-  }
-  // nothing of this call stays in the log: a replay adds to the caller's vector and reads the caller's rows, which are only guaranteed
-  // to live until the call returns (one host wait per call); the last tick's collision stays pending
-  if ((rc = drain(s))) return rc;
-  if ((rc = finish_profile(s))) return rc;
-  return fence_out(s, ext);
+  a.crash = crash, a.rebounce = rebounce, a.crash_cost = crash_cost;
+  return rollout_tick_locked(s, a);
 }
 
 // mrs_swarm_rollout_tick_cost_device whose command rows are nominal commands: every tick at which a command block starts carries that
-// block's nominal commands, gains and setpoints, and the launch forms the command from the state before the step.  The same loop of
-// step_one and pending collision ticks, the same single drain, the same memset outside the launch log.  Without a dev_cost no tick
-// carries an evaluation: a pure closed-loop run.
+// block's nominal commands, gains and setpoints, and the launch forms the command from the state before the step
 int mrs_swarm_rollout_tick_feedback_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t mode, double dt, int32_t n_ticks, int32_t cmd_every,
                                            int32_t cost_every, const void* dev_cmd, int32_t dtype, int32_t cmd_stride, uint32_t fb_groups,
                                            const void* dev_gain, int32_t gain_per_uav, int32_t gain_blocks, const void* dev_ref, int32_t ref_stride,
@@ -751,62 +776,8 @@ int mrs_swarm_rollout_tick_feedback_device(mrs_swarm_t* s, int32_t first, int32_
   a.cost = dev_cost, a.accumulate = accumulate;
   a.fb_groups = fb_groups, a.gain = dev_gain, a.gain_per_uav = gain_per_uav, a.gain_blocks = gain_blocks;
   a.ref = dev_ref, a.ref_stride = ref_stride, a.ref_blocks = ref_blocks;
-  a.crash = crash, a.rebounce = rebounce;
-  RolloutWidths w;
-  int           rc = check_rollout_args(s, a, "n_ticks", "cost_every", w);
-  if (rc) return rc;
-  const int    width = w.cmd;  // (at least 1: checked)
-  const size_t elem  = dtype_bytes(dtype);
-  if (s->n == 0) return MRS_OK;
-  HIPCHK(hipSetDevice(s->device));
-  if (!s->log.empty() && (rc = drain(s))) return rc;  // (as mrs_swarm_rollout_tick_device: a collision tick pending at entry stays pending)
-  if ((rc = upload_types(s, dt))) return rc;
-  rollout_track_mode(s, a);
-  hipStream_t ext = (hipStream_t)ext_stream;
-  if ((rc = fence_in(s, ext))) return rc;
-  if ((rc = begin_profile(s))) return rc;
-  if (w.costed && count > 0 && !accumulate) HIPCHK(hipMemsetAsync(dev_cost, 0, (size_t)count * sizeof(double), s->stream));  // (+0.0)
-  RolloutTickFeedbackDev f{};
-  f.first = first, f.count = count;
-  f.cmd_stride = cmd_stride;
-  f.ref_row = ref_stride, f.tgt_row = target_stride;
-  f.gain_lane = gain_per_uav ? 1 : 0, f.gain_col = gain_per_uav ? (uint32_t)count : 1u;
-  f.fb_word    = fb_groups | (uint32_t)w.fb << 8;
-  f.cmd_word   = (uint32_t)width | (dtype == MRS_DTYPE_F32 ? 32u : 0u);
-  f.groups     = cost_groups;
-  f.mode_bits  = (uint32_t)mode << FLAG_MODE_SHIFT;
-  f.crash_cost = crash_cost;
-  // elements between two blocks: gains (a matrix, or a matrix per UAV), setpoint rows and target rows (a row per UAV, or one dense row
-  // for all); gain_blocks / ref_blocks 1: one block serves every command block
-  const size_t per      = gain_per_uav ? (size_t)count : (size_t)1;
-  const size_t gain_blk = gain_blocks == 1 ? 0u : (size_t)width * (size_t)w.fb * per;
-  const size_t ref_blk  = ref_blocks == 1 ? 0u : ref_stride ? (size_t)count * (size_t)ref_stride : (size_t)w.fb;
-  const size_t tgt_blk  = target_stride ? (size_t)count * (size_t)target_stride : (size_t)w.obs;
-  for (int t = 0; t < n_ticks; t++) {
-    f.cmd = f.gain = f.ref = f.target = f.weight = nullptr;
-    f.cost = nullptr;
-    if (count > 0 && t % cmd_every == 0) {
-      const size_t b = (size_t)(t / cmd_every);
-      f.cmd  = static_cast<const char*>(dev_cmd) + b * (size_t)count * (size_t)cmd_stride * elem;
-      f.gain = static_cast<const char*>(dev_gain) + b * gain_blk * elem;
-      f.ref  = static_cast<const char*>(dev_ref) + b * ref_blk * elem;
-    }
-    if (w.costed && count > 0 && (t + 1) % cost_every == 0) {
-      const size_t j = (size_t)((t + 1) / cost_every - 1);
-      f.cost = dev_cost;
-      if (cost_groups != 0u) {
-        f.target = static_cast<const char*>(dev_target) + j * tgt_blk * elem;
-        f.weight = static_cast<const char*>(dev_weight) + j * (size_t)weight_stride * elem;
-      }
-    }
-    if ((rc = step_one(s, dt, nullptr, nullptr, &f))) return rc;
-    if ((rc = mrs_swarm_handle_collisions(s, 1, crash, rebounce))) return rc;
-  }
-  // nothing of this call stays in the log: a replay reads the caller's rows and gains and adds to the caller's vector, which are only
-  // guaranteed to live until the call returns (one host wait per call); the last tick's collision stays pending
-  if ((rc = drain(s))) return rc;
-  if ((rc = finish_profile(s))) return rc;
-  return fence_out(s, ext);
+  a.crash = crash, a.rebounce = rebounce, a.crash_cost = crash_cost;
+  return rollout_tick_locked(s, a);
 }
 
 }  // extern "C"

@@ -330,13 +330,21 @@ struct mrs_swarm {
   // pin: which position buffer the launch read; packs: the pipelined downloads packed right behind this launch, in the order they were
   // issued (re-issued when the launch is replayed after a stall: what they packed then was the state of an earlier tick).  At most
   // two per kind can still hold their slot, so four entries are enough (the _async call drops those whose slot has been recycled).
-  // rows: the launch is one tick of mrs_swarm_rollout_tick_device and `row` names the caller's row blocks of that tick — a replay
-  // writes into them what the no-op launch did not (the call drains the log before it returns: the rows live that long).
-  // cost: the launch is one tick of mrs_swarm_rollout_tick_cost_device and `cost` names that tick's command block and evaluation — a
-  // replay adds to the caller's cost vector what the no-op launch did not (it never got as far as the vector).
-  // fed: the launch is one tick of mrs_swarm_rollout_tick_feedback_device and `fb` names that tick's nominal commands, gains, setpoints
-  // and evaluation — a replay forms the command from the state the no-op launch left alone, and adds what it did not.
+  // load: what the launch carries besides the tick.  A tick of mrs_swarm_rollout_tick_device names the caller's row blocks of that tick
+  // (ROWS), one of mrs_swarm_rollout_tick_cost_device that tick's command block and evaluation (COST), one of
+  // mrs_swarm_rollout_tick_feedback_device that tick's nominal commands, gains, setpoints and evaluation (FEEDBACK).  A replay does
+  // what the no-op launch did not: it writes the rows, adds to the caller's cost vector (the no-op never got as far as the vector), forms
+  // the command from the state the no-op left alone.  The call drains the log before it returns: the caller's memory lives that long.
   struct PackRef { int32_t kind, ticket; };
+  struct TickLoad {  // one kind, and the descriptor of that kind
+    enum Kind { NONE, ROWS, COST, FEEDBACK } kind = NONE;
+    union {
+      RolloutTickDev         row;
+      RolloutTickCostDev     cost;
+      RolloutTickFeedbackDev fb;
+    };
+    TickLoad() : fb{} {}
+  };
   struct TickRec {
     double  dt;
     Collide eval;
@@ -344,12 +352,7 @@ struct mrs_swarm {
     int     pin = 0;
     int     n_packs = 0;
     PackRef packs[2 * PAYLOAD_KINDS] = {};
-    bool           rows = false;
-    RolloutTickDev row{};
-    bool               costed = false;
-    RolloutTickCostDev cost{};
-    bool                   fed = false;
-    RolloutTickFeedbackDev fb{};
+    TickLoad load;
   };
   Collide              pend;                        // requested after the most recent step, not evaluated yet
   // A fused launch consumes the force it evaluates from registers and does not write the F_ext columns (24 B per UAV and tick).
@@ -449,10 +452,8 @@ int  begin_profile(mrs_swarm* s);
 int  finish_profile(mrs_swarm* s);
 int  collide_now(mrs_swarm* s, const mrs_swarm::Collide& c, bool force);
 int  wait_for_progress(mrs_swarm* s, const volatile unsigned* hw, unsigned index, int lead);
-// row: the tick's caller rows (mrs_swarm_rollout_tick_device); cost: the tick's evaluation (mrs_swarm_rollout_tick_cost_device); fb: the
-// tick's feedback law and evaluation (mrs_swarm_rollout_tick_feedback_device); at most one of them
-int  step_one(mrs_swarm* s, double dt, const RolloutTickDev* row = nullptr, const RolloutTickCostDev* cost = nullptr,
-              const RolloutTickFeedbackDev* fb = nullptr);
+// load: what the tick carries of a tick rollout (mrs_swarm::TickLoad); none: a plain tick
+int  step_one(mrs_swarm* s, double dt, const mrs_swarm::TickLoad* load = nullptr);
 int  drain(mrs_swarm* s);
 // the slot of `kind` that still holds the download `ticket` (nullptr: a ticket of the other kind, or its slot has been recycled)
 inline mrs_swarm::OutSlot* held_slot(mrs_swarm* s, int kind, int32_t ticket) {

@@ -37,6 +37,7 @@ struct LaneObs {
 // less and the same statements are scheduled differently), and DESIGN.md's register and spill tables are measured on this one.
 template <class Dev>
 struct RolloutHookBase {
+  static constexpr bool kOnCollKernels = false;  // a sub-step hook of the MULTI kernels (step_kernel_body's static_assert)
   Dev r;
 
   __device__ __forceinline__ bool mine(int i) const { return (unsigned)(i - r.first) < (unsigned)r.count; }

@@ -1157,13 +1157,11 @@ DEV bool coll_fold_and_decide(CDT& cd0, const int part, const uint32_t stall_own
 // HK: what a launch does around each fused sub-step besides stepping (MULTI only; rollout_device.inc).  enter() runs once per lane
 // after the wave-uniform exits and may finish the lane itself (true); cmd(s) runs at the top of sub-step s, before the controller
 // cascade, cmd_lane(s) behind it with the lane (the state BEFORE the sub-step: the feedback hook of rollout_cost_device.inc), and obs(s) after post_step.  The default does nothing: every kernel of this file compiles as it did without the hook.
-// One hook type, RolloutTickHook (rollout_tick_device.inc), rides on the single-GPU COLL kernels instead: one step per launch, and
-// held(), the last thing a held lane does — in COLL kernels a held lane takes part in the collisions and leaves inside
-// MRS_COLLIDE_THEN, so enter() cannot finish it.
-struct RolloutTickHook;
-struct RolloutTickCostHook;  // (rollout_tick_cost_device.inc: the same shape, a cost in place of the rows)
-struct RolloutTickFeedbackHook;  // (rollout_tick_feedback_device.inc: the cost tick hook whose command is formed from the state)
+// The tick hooks (rollout_tick_device.inc) ride on the single-GPU COLL kernels instead: one step per launch, and held(), the last
+// thing a held lane does — in COLL kernels a held lane takes part in the collisions and leaves inside MRS_COLLIDE_THEN, so enter()
+// cannot finish it.  A hook type says which it is: kOnCollKernels.
 struct NoStepHook {
+  static constexpr bool kOnCollKernels = false;
   template <class SW>
   __device__ __forceinline__ bool enter(const SW&, int, Lane&, int) const { return false; }
   template <class SW>
@@ -1180,7 +1178,7 @@ template <bool CASCADE, bool UNIFORM, int NU, bool MULTI, int SU, bool COLL, boo
 DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, const int substeps_arg, CDT& cd0, int& blk_out, bool& took_part,
                           const HK& hk = HK()) {
   static_assert(!COLL || (NU == 1 && !MULTI), "fused collision evaluation: one UAV per lane, one step per launch");
-  static_assert(__is_same(HK, NoStepHook) || (NU == 1 && MULTI && !COLL) || ((__is_same(HK, RolloutTickHook) || __is_same(HK, RolloutTickCostHook) || __is_same(HK, RolloutTickFeedbackHook)) && NU == 1 && !MULTI && COLL && !SHARD),
+  static_assert(__is_same(HK, NoStepHook) || (NU == 1 && MULTI && !COLL) || (HK::kOnCollKernels && NU == 1 && !MULTI && COLL && !SHARD),
                 "sub-step hooks: one UAV per lane, fused sub-steps, no collisions (the tick hooks: one step, single-GPU collisions)");
   // MULTI = false compiles the substep loop away: with the loop the state is loop-carried and the per-type constants are
   // hoisted in front of it, which costs the fused kernel ~120 registers (350 vs 227) and with them its second wave per SIMD

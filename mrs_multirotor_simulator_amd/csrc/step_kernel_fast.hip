@@ -4,6 +4,4 @@
 #include "rollout_device.inc"
 #include "rollout_rate_device.inc"
 #include "rollout_cost_device.inc"
-#include "rollout_tick_feedback_device.inc"
-#include "rollout_tick_cost_device.inc"
 #include "rollout_tick_device.inc"

@@ -164,6 +164,15 @@ inline mrs_ro_launch mrs_ro_launch_sched(uint32_t call_word, int t0, int sub, in
   if (s0 < sub) return {(call_word & 0xFF000000u) | mrs_ro_sched(s0, every), blk0};
   return {start ? call_word & (32u << 24) : 0u, blk0};
 }
+// The same two schedules where one launch is one tick and the host works out each tick's blocks (the tick rollouts): the block of
+// `n_blocks` blocks of `every` ticks each that STARTS at tick t (commands, gains, setpoints: block j at tick j * every), and the one
+// that ENDS with tick t (observation and crash rows, evaluations: block j at tick (j + 1) * every - 1).  -1: none does.
+inline long long mrs_tick_block_start(int t, int every, long long n_blocks) {
+  return t >= 0 && t % every == 0 && t / every < n_blocks ? t / every : -1;
+}
+inline long long mrs_tick_block_end(int t, int every, long long n_blocks) {
+  return t >= 0 && (t + 1) % every == 0 && (t + 1) / every <= n_blocks ? (t + 1) / every - 1 : -1;
+}
 
 // ---- one launch of a control-rate rollout under scheduled external forces (mrs_swarm_rollout_force_device, rollout_rate_device.inc) ----
 // RolloutRateDev and a third schedule: force row block j (applyForce, world frame, N) is latched in the F_FEXT columns from step
@@ -243,7 +252,7 @@ struct RolloutTickDev {
   int32_t     _pad;
 };
 
-// ---- ONE tick of a cost tick rollout (mrs_swarm_rollout_tick_cost_device, rollout_tick_cost_device.inc) ----
+// ---- ONE tick of a cost tick rollout (mrs_swarm_rollout_tick_cost_device, rollout_tick_device.inc) ----
 // RolloutTickDev's command side, and in place of row blocks the evaluation that ends with this tick: the observation row of UAV first + k
 // is compared with its target row under the weight row, the term is added to cost[k], and crash_cost is added behind it when the UAV's
 // crash flag is set.  The host works out the pointers of each tick: no schedule words.  The descriptor travels with the launch's record
@@ -265,7 +274,7 @@ struct RolloutTickCostDev {
   double      crash_cost;
 };
 
-// ---- ONE tick of a feedback tick rollout (mrs_swarm_rollout_tick_feedback_device, rollout_tick_feedback_device.inc) ----
+// ---- ONE tick of a feedback tick rollout (mrs_swarm_rollout_tick_feedback_device, rollout_tick_device.inc) ----
 // RolloutTickCostDev whose command side becomes the NOMINAL command, with the gains and setpoints of the command block that starts at
 // this tick: the F_CMD columns of UAV first + k take cmd row k + G(k) (ref row k - the observation row of fb_groups before the step).
 // G(k)[c][col] sits at element k * gain_lane + (c * row width + col) * gain_col of `gain`, as RolloutFeedbackDev's.  The host works out

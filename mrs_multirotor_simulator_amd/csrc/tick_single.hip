@@ -171,79 +171,101 @@ int wait_for_progress(mrs_swarm* s, const volatile unsigned* hw, unsigned index,
   return MRS_OK;
 }
 
-// One tick of mrs_swarm_rollout_tick_device without the fused form (no lists, lists incomplete, no collision tick since the previous
-// step): any collision tick has been evaluated on its own before; one step of the control-rate rollout kernels with this tick's row
-// blocks, then the crash bytes of a block that ends here.  The rows equal those of the fused launch.
-int launch_row_step(mrs_swarm* s, double dt, const RolloutTickDev& row) {
-  s->region_launches++;
-  RolloutRateDev r{};
-  r.cmd = row.cmd, r.obs = row.obs;
-  r.first = row.first, r.count = row.count;
-  r.cmd_stride = row.cmd_stride, r.obs_stride = row.obs_stride;
-  r.cmd_sched = (row.cmd ? row.cmd_word : (row.cmd_word & 32u)) << 24;  // (width 0: no command block starts at this tick)
-  r.obs_sched = row.obs ? row.groups << 24 : 0u;
-  r.mode_bits = row.mode_bits;
-  const int variant = s->n_cascade > 0 ? 0 : 1;
-  if (s->arith == MRS_ARITH_FAST)
-    HIPCHK(mrs_launch_rollout_rate_fast(s->view(), r, dt, 1, 1, 1, variant, s->stream));
-  else
-    HIPCHK(mrs_launch_rollout_rate_literal(s->view(), r, dt, 1, 1, 1, variant, s->stream));
-  if (row.crashed && row.count > 0) return launch_crashed_u8(s, row.first, row.count, row.crashed);
-  return MRS_OK;
+// ---- what a tick of a tick rollout carries (mrs_swarm::TickLoad) ----
+// the launchers of one step unit: the flavour is chosen once per dispatch
+struct StepUnit {
+  decltype(&mrs_launch_step_coll_literal)            step_coll;
+  decltype(&mrs_launch_rollout_tick_literal)          tick;
+  decltype(&mrs_launch_rollout_tick_cost_literal)     tick_cost;
+  decltype(&mrs_launch_rollout_tick_feedback_literal) tick_feedback;
+  decltype(&mrs_launch_rollout_rate_literal)          rate;
+  decltype(&mrs_launch_rollout_cost_literal)          cost;
+  decltype(&mrs_launch_rollout_feedback_literal)      feedback;
+};
+static const StepUnit& step_unit(const mrs_swarm* s) {
+  static const StepUnit units[2] = {
+      {mrs_launch_step_coll_literal, mrs_launch_rollout_tick_literal, mrs_launch_rollout_tick_cost_literal, mrs_launch_rollout_tick_feedback_literal,
+       mrs_launch_rollout_rate_literal, mrs_launch_rollout_cost_literal, mrs_launch_rollout_feedback_literal},
+      {mrs_launch_step_coll_fast, mrs_launch_rollout_tick_fast, mrs_launch_rollout_tick_cost_fast, mrs_launch_rollout_tick_feedback_fast,
+       mrs_launch_rollout_rate_fast, mrs_launch_rollout_cost_fast, mrs_launch_rollout_feedback_fast}};
+  return units[s->arith == MRS_ARITH_FAST ? 1 : 0];
 }
 
-// One tick of mrs_swarm_rollout_tick_cost_device without the fused form, as launch_row_step: one step of the cost rollout kernels with
-// this tick's command block and evaluation (the term), then the crash add of an evaluation that ends here.  The two adds round as the
-// fused launch's do, so the cost equals the fused launch's bit for bit.
-int launch_cost_step(mrs_swarm* s, double dt, const RolloutTickCostDev& c) {
-  s->region_launches++;
-  RolloutCostDev r{};
-  r.cmd = c.cmd;
-  r.first = c.first, r.count = c.count;
-  r.cmd_stride = c.cmd_stride;
-  r.cmd_sched  = (c.cmd ? c.cmd_word : (c.cmd_word & 32u)) << 24;  // (width 0: no command block starts at this tick)
-  r.cost_sched = (c.cost && c.groups != 0u) ? c.groups << 24 : 0u;  // (groups 0: no evaluation ends here, or the crash add alone)
-  r.mode_bits  = c.mode_bits;
-  if (r.cost_sched != 0u) {
-    r.target = c.target, r.weight = c.weight, r.cost = c.cost;
-    r.tgt_row = c.tgt_row, r.tgt_blk = 0, r.wt_row = 0;  // (one evaluation: the block and weight-row distances are never used)
+// The fused launch of a tick: mrs_launch_step_coll, or the same launch with what the tick carries.
+static hipError_t launch_fused_load(const StepUnit& u, const SwarmDev& v, const CollDev& cd, const mrs_swarm::TickLoad& p, double dt, int variant,
+                                    hipStream_t st) {
+  switch (p.kind) {
+    case mrs_swarm::TickLoad::ROWS: return u.tick(v, cd, p.row, dt, variant, st);                // the caller's rows of this tick
+    case mrs_swarm::TickLoad::COST: return u.tick_cost(v, cd, p.cost, dt, variant, st);          // this tick's evaluation
+    case mrs_swarm::TickLoad::FEEDBACK: return u.tick_feedback(v, cd, p.fb, dt, variant, st);    // this tick's feedback law and evaluation
+    case mrs_swarm::TickLoad::NONE: break;
   }
-  const int variant = s->n_cascade > 0 ? 0 : 1;
-  if (s->arith == MRS_ARITH_FAST)
-    HIPCHK(mrs_launch_rollout_cost_fast(s->view(), r, dt, 1, 1, 1, variant, s->stream));
-  else
-    HIPCHK(mrs_launch_rollout_cost_literal(s->view(), r, dt, 1, 1, 1, variant, s->stream));
-  if (c.cost && c.count > 0) return launch_crash_cost(s, c.first, c.count, c.cost, c.crash_cost);
-  return MRS_OK;
+  return u.step_coll(v, cd, dt, variant, 0, st);
 }
 
-// One tick of mrs_swarm_rollout_tick_feedback_device without the fused form, as launch_cost_step: one step of the feedback rollout kernels
-// with this tick's nominal commands, gains, setpoints and evaluation (the command from the state before the step, the term), then the
-// crash add of an evaluation that ends here.  The law and the two adds round as the fused launch's do: the same bits.
-int launch_feedback_step(mrs_swarm* s, double dt, const RolloutTickFeedbackDev& f) {
+// A tick of a tick rollout without the fused form (no lists, lists incomplete, no collision tick since the previous step): any collision
+// tick has been evaluated on its own before; one step of the rollout kernels that know the tick's descriptor as a launch of one due
+// sub-step, then what the fused hook does behind the step.  What the three translations share: the command side of the descriptor
+// (width 0: no command block starts at this tick) and the evaluation of the two costed ones (groups 0: no evaluation ends here, or the
+// crash add alone; one evaluation: the block and weight-row distances are never used).
+template <class R, class D>
+static void tick_command_side(R& r, const D& d) {
+  r.cmd = d.cmd;
+  r.first = d.first, r.count = d.count;
+  r.cmd_stride = d.cmd_stride;
+  r.cmd_sched  = (d.cmd ? d.cmd_word : (d.cmd_word & 32u)) << 24;
+  r.mode_bits  = d.mode_bits;
+}
+template <class R, class D>
+static void tick_evaluation(R& r, const D& d) {
+  r.cost_sched = (d.cost && d.groups != 0u) ? d.groups << 24 : 0u;
+  if (r.cost_sched == 0u) return;
+  r.target = d.target, r.weight = d.weight, r.cost = d.cost;
+  r.tgt_row = d.tgt_row, r.tgt_blk = 0, r.wt_row = 0;
+}
+static int launch_unfused_load(mrs_swarm* s, double dt, const mrs_swarm::TickLoad& p) {
   s->region_launches++;
-  RolloutFeedbackDev r{};
-  r.first = f.first, r.count = f.count;
-  r.cmd_stride = f.cmd_stride;
-  r.cmd_sched  = (f.cmd ? f.cmd_word : (f.cmd_word & 32u)) << 24;  // (width 0: no command block starts at this tick)
-  r.cost_sched = (f.cost && f.groups != 0u) ? f.groups << 24 : 0u;  // (groups 0: no evaluation ends here, or the crash add alone)
-  r.mode_bits  = f.mode_bits;
-  r.fb_word    = f.fb_word;
-  if (f.cmd) {  // (one command block: the block distances are never used)
-    r.cmd = f.cmd, r.gain = f.gain, r.ref = f.ref;
-    r.gain_col = f.gain_col, r.gain_lane = f.gain_lane, r.ref_row = f.ref_row;
+  const StepUnit& u       = step_unit(s);
+  const int       variant = s->n_cascade > 0 ? 0 : 1;
+  switch (p.kind) {
+    case mrs_swarm::TickLoad::ROWS: {  // the control-rate rollout kernels, then the crash bytes of a block that ends here: the fused launch's rows
+      const RolloutTickDev& row = p.row;
+      RolloutRateDev        r{};
+      tick_command_side(r, row);
+      r.obs = row.obs, r.obs_stride = row.obs_stride;
+      r.obs_sched = row.obs ? row.groups << 24 : 0u;
+      HIPCHK(u.rate(s->view(), r, dt, 1, 1, 1, variant, s->stream));
+      if (row.crashed && row.count > 0) return launch_crashed_u8(s, row.first, row.count, row.crashed);
+      return MRS_OK;
+    }
+    case mrs_swarm::TickLoad::COST: {  // the cost rollout kernels (the term), then the crash add of an evaluation that ends here.  The two
+                                       // adds round as the fused launch's do, so the cost equals the fused launch's bit for bit
+      const RolloutTickCostDev& c = p.cost;
+      RolloutCostDev            r{};
+      tick_command_side(r, c);
+      tick_evaluation(r, c);
+      HIPCHK(u.cost(s->view(), r, dt, 1, 1, 1, variant, s->stream));
+      if (c.cost && c.count > 0) return launch_crash_cost(s, c.first, c.count, c.cost, c.crash_cost);
+      return MRS_OK;
+    }
+    case mrs_swarm::TickLoad::FEEDBACK: {  // the feedback rollout kernels (the command from the state before the step, the term), then the
+                                           // crash add.  The law and the two adds round as the fused launch's do: the same bits
+      const RolloutTickFeedbackDev& f = p.fb;
+      RolloutFeedbackDev            r{};
+      tick_command_side(r, f);
+      tick_evaluation(r, f);
+      r.fb_word = f.fb_word;
+      if (f.cmd) {  // (one command block: the block distances are never used)
+        r.gain = f.gain, r.ref = f.ref;
+        r.gain_col = f.gain_col, r.gain_lane = f.gain_lane, r.ref_row = f.ref_row;
+      }
+      HIPCHK(u.feedback(s->view(), r, dt, 1, 1, 1, variant, s->stream));
+      if (f.cost && f.count > 0) return launch_crash_cost(s, f.first, f.count, f.cost, f.crash_cost);
+      return MRS_OK;
+    }
+    case mrs_swarm::TickLoad::NONE: break;
   }
-  if (r.cost_sched != 0u) {
-    r.target = f.target, r.weight = f.weight, r.cost = f.cost;
-    r.tgt_row = f.tgt_row, r.tgt_blk = 0, r.wt_row = 0;
-  }
-  const int variant = s->n_cascade > 0 ? 0 : 1;
-  if (s->arith == MRS_ARITH_FAST)
-    HIPCHK(mrs_launch_rollout_feedback_fast(s->view(), r, dt, 1, 1, 1, variant, s->stream));
-  else
-    HIPCHK(mrs_launch_rollout_feedback_literal(s->view(), r, dt, 1, 1, 1, variant, s->stream));
-  if (f.cost && f.count > 0) return launch_crash_cost(s, f.first, f.count, f.cost, f.crash_cost);
-  return MRS_OK;
+  return fail(MRS_ERR_ARG, "a tick without a load is a plain step");
 }
 
 // one fused launch: evaluate collision tick `e.eval` (if any) from the lists, then makeStep(e.dt)
@@ -268,25 +290,7 @@ int launch_fused(mrs_swarm* s, const mrs_swarm::TickRec& e) {
     s->ev_used += 2;
     HIPCHK(hipEventRecord(e0, s->stream));
   }
-  if (e.rows) {  // a tick of mrs_swarm_rollout_tick_device: the same launch with the caller's rows of this tick
-    if (s->arith == MRS_ARITH_FAST)
-      HIPCHK(mrs_launch_rollout_tick_fast(v, cd, e.row, e.dt, variant, s->stream));
-    else
-      HIPCHK(mrs_launch_rollout_tick_literal(v, cd, e.row, e.dt, variant, s->stream));
-  } else if (e.costed) {  // a tick of mrs_swarm_rollout_tick_cost_device: the same launch with this tick's evaluation
-    if (s->arith == MRS_ARITH_FAST)
-      HIPCHK(mrs_launch_rollout_tick_cost_fast(v, cd, e.cost, e.dt, variant, s->stream));
-    else
-      HIPCHK(mrs_launch_rollout_tick_cost_literal(v, cd, e.cost, e.dt, variant, s->stream));
-  } else if (e.fed) {  // a tick of mrs_swarm_rollout_tick_feedback_device: the same launch with this tick's feedback law and evaluation
-    if (s->arith == MRS_ARITH_FAST)
-      HIPCHK(mrs_launch_rollout_tick_feedback_fast(v, cd, e.fb, e.dt, variant, s->stream));
-    else
-      HIPCHK(mrs_launch_rollout_tick_feedback_literal(v, cd, e.fb, e.dt, variant, s->stream));
-  } else if (s->arith == MRS_ARITH_FAST)
-    HIPCHK(mrs_launch_step_coll_fast(v, cd, e.dt, variant, 0, s->stream));
-  else
-    HIPCHK(mrs_launch_step_coll_literal(v, cd, e.dt, variant, 0, s->stream));
+  HIPCHK(launch_fused_load(step_unit(s), v, cd, e.load, e.dt, variant, s->stream));
   if (s->profiling == 2) HIPCHK(hipEventRecord(e1, s->stream));
   mrs_swarm::TickRec rec = e;
   rec.pin = mrs_collide_fused_pin(s->cwork);
@@ -356,10 +360,9 @@ int drain(mrs_swarm* s) {
       } else {  // (lists incomplete: dense neighbourhoods) every tick on its own
         if (e.eval.on && (rc = collide_now(s, e.eval, false))) return rc;
         s->p_valid = false;
-        if (e.rows || e.costed || e.fed) {
+        if (e.load.kind != mrs_swarm::TickLoad::NONE) {
           if (e.dt != s->table_dt && (rc = upload_types(s, e.dt))) return rc;
-          if ((rc = e.rows ? launch_row_step(s, e.dt, e.row) : e.costed ? launch_cost_step(s, e.dt, e.cost) : launch_feedback_step(s, e.dt, e.fb)))
-            return rc;
+          if ((rc = launch_unfused_load(s, e.dt, e.load))) return rc;
         } else {
           s->region_launches++;
           if ((rc = launch_part(s, e.dt, 1, 0, (s->n + 63) / 64, 1, s->stream))) return rc;
@@ -397,7 +400,7 @@ int settle(mrs_swarm* s) {
 }
 
 // one makeStep of every UAV; the collision tick requested since the previous step (if any) is evaluated by the same launch
-int step_one(mrs_swarm* s, double dt, const RolloutTickDev* row, const RolloutTickCostDev* cost, const RolloutTickFeedbackDev* fb) {
+int step_one(mrs_swarm* s, double dt, const mrs_swarm::TickLoad* load) {
   int rc;
   if (s->collide_since_step && s->use_lists && s->use_fused) {
     const volatile unsigned* hw = mrs_collide_host_words(s->cwork);
@@ -407,9 +410,7 @@ int step_one(mrs_swarm* s, double dt, const RolloutTickDev* row, const RolloutTi
     if (s->pend.on && !fused_usable(s) && (rc = settle(s))) return rc;  // first tick / after host writes: the pass on its own
     if (fused_usable(s)) {
       mrs_swarm::TickRec e{dt, s->pend, false};
-      if (row) e.rows = true, e.row = *row;
-      if (cost) e.costed = true, e.cost = *cost;
-      if (fb) e.fed = true, e.fb = *fb;
+      if (load) e.load = *load;
       if (s->pend.on && hw && hw[CTL_WARN] > s->search_mark) {
         // some UAV has used up most of its skin: repeat the search NOW, in stream order — it evaluates the pending collision tick
         // itself — instead of running into the stall a few ticks on (no synchronisation, nothing to replay)
@@ -427,9 +428,7 @@ int step_one(mrs_swarm* s, double dt, const RolloutTickDev* row, const RolloutTi
   if ((rc = settle(s))) return rc;
   s->collide_since_step = false;
   s->p_valid            = false;  // a plain step kernel does not refresh the position records
-  if (row) return launch_row_step(s, dt, *row);
-  if (cost) return launch_cost_step(s, dt, *cost);
-  if (fb) return launch_feedback_step(s, dt, *fb);
+  if (load && load->kind != mrs_swarm::TickLoad::NONE) return launch_unfused_load(s, dt, *load);
   return launch_step(s, dt, 1);
 }
 

@@ -167,10 +167,12 @@ def macro_lines(text, macro):
 
 class RolloutKernels:
     """The rollout kernels both step units compile, from the sources: every MRS_ROLLOUT_FAMILY(infix, descriptor, hook) line of the
-    included rollout files times the MRS_ROLLOUT_SHAPE lines of that macro, and the MRS_ROLLOUT_TICK_KERNEL lines.
+    included rollout files times the MRS_ROLLOUT_SHAPE lines of that macro, and likewise every MRS_ROLLOUT_TICK_FAMILY line times the
+    MRS_ROLLOUT_TICK_SHAPE lines.
       families : {infix: {kernel: [bounds, CASCADE, UNIFORM, BUF]}}, infixes and kernels in definition order
       types    : {infix: (descriptor, hook)}
-      tick     : {kernel: [bounds, CASCADE, UNIFORM, ACC, SU]}
+      tick_families, tick_types : the same of the tick families, {kernel: [bounds, CASCADE, UNIFORM, ACC, SU]}
+      tick     : the kernels of the tick family without an infix (the tick rollout's own)
       order    : every kernel name in definition order
       files    : the rollout files in include order; texts : {file: text}"""
 
@@ -187,16 +189,21 @@ class RolloutKernels:
         self.texts = {f: open(os.path.join(CSRC, f)).read() for f in self.files}
         shapes = macro_lines(self.texts["rollout_device.inc"], "MRS_ROLLOUT_SHAPE")
         assert all(v[-2:] == ["DevType", "HookType"] for v in shapes.values()), shapes
-        self.families, self.types, self.tick, self.order = {}, {}, {}, []
+        tick_shapes = macro_lines(self.texts["rollout_tick_device.inc"], "MRS_ROLLOUT_TICK_SHAPE")
+        assert all(v[-2:] == ["DevType", "HookType"] for v in tick_shapes.values()), tick_shapes
+        self.families, self.types, self.tick_families, self.tick_types, self.order = {}, {}, {}, {}, []
         for f in self.files:
             for infix, dev, hook in re.findall(r"^MRS_ROLLOUT_FAMILY\((\w*), (\w+), (\w+)\)$", self.texts[f], flags=re.M):
                 assert infix not in self.families, infix
                 self.types[infix] = (dev, hook)
                 self.families[infix] = {k.replace("##infix##", infix).replace("##infix", infix): v[:-2] for k, v in shapes.items()}
                 self.order += list(self.families[infix])
-            tick = macro_lines(self.texts[f], "MRS_ROLLOUT_TICK_KERNEL")
-            self.tick.update(tick)
-            self.order += list(tick)
+            for infix, dev, hook in re.findall(r"^MRS_ROLLOUT_TICK_FAMILY\((\w*), (\w+), (\w+)\)$", self.texts[f], flags=re.M):
+                assert infix not in self.tick_families, infix
+                self.tick_types[infix] = (dev, hook)
+                self.tick_families[infix] = {k.replace("##infix##", infix).replace("##infix", infix): v[:-2] for k, v in tick_shapes.items()}
+                self.order += list(self.tick_families[infix])
+        self.tick = self.tick_families[""]
         step = open(os.path.join(CSRC, "step_device.inc")).read()
         self.step_kernels = re.findall(r"MRS_STEP_KERNEL\w*\(\s*(\w+)", step)
 

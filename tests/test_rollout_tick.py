@@ -166,6 +166,19 @@ def test_rollout_ticks_refuses_bad_tensors(monkeypatch):
         T.rollout_ticks(g, 10, cmd(), 0.001, False, 100.0, 0, crashed=cr())
 
 
+def test_block_helpers_against_their_statement(tmp_path):
+    """tests/cpp/rollout_tick_blocks_test.cpp: every rate 1..12 and every n_ticks up to 48 that the rate divides, the blocks that start at
+    and end with each tick (swarm_layout.h: mrs_tick_block_start, mrs_tick_block_end); the entry points use this text, not a copy"""
+    exe = str(tmp_path / "rollout_tick_blocks_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, os.path.join(ROOT, "tests", "cpp", "rollout_tick_blocks_test.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    n = sum(48 // every for every in range(1, 13))
+    assert out.returncode == 0 and f"{n} schedules ok" in out.stdout, out.stdout + out.stderr
+    io = open(os.path.join(CSRC, "device_io.hip")).read()
+    assert "mrs_tick_block_start(t, a.cmd_every" in io and "mrs_tick_block_end(t, a.obs_every" in io
+    assert "% cmd_every" not in io.replace("a.n_steps % a.cmd_every", "") and "% obs_every" not in io.replace("a.n_steps % a.obs_every", "")
+
+
 def test_rollout_tick_test_compiles(mrs, tmp_path):
     from mrs_multirotor_simulator_amd import swarm
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-DMRS_NO_EIGEN", "-D__HIP_PLATFORM_AMD__", "-I",

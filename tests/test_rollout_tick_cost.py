@@ -5,7 +5,7 @@ and tests/cpp/rollout_tick_cost_test.cpp compiles.  CPU tensors only: no pointer
 
 The call has kernels of its own: exactly four, each with a row in test_rollout_tick_cost_gpu.ROLLOUT_TICK_COST_KERNELS and the shape of
 the single-GPU MRS_STEP_KERNEL_COLL line it mirrors; they belong to no rollout family, are no tick-rollout kernel and no step-kernel line,
-and their file comes in front of rollout_tick_device.inc, so the tables of the earlier tests stay as they are."""
+and their tick family (_cost) is defined in front of the tick rollout's own, so the tables of the earlier tests stay as they are."""
 import ctypes as C
 import inspect
 import os
@@ -20,7 +20,7 @@ from helpers import CSRC, STEP_UNITS, macro_lines, rollout_kernels
 from test_rollout import CTYPE, ROOT
 from test_rollout_tick import _fakes
 
-FILE = "rollout_tick_cost_device.inc"
+FILE = "rollout_tick_device.inc"  # the tick families share one file; this one is MRS_ROLLOUT_TICK_FAMILY(_cost, ...)
 NAMES = ["s", "first", "count", "mode", "dt", "n_ticks", "cmd_every", "cost_every", "dev_cmd", "dtype", "cmd_stride", "groups", "dev_target",
          "target_stride", "dev_weight", "weight_stride", "crash_cost", "dev_cost", "accumulate", "crash", "rebounce", "ext_stream"]
 
@@ -65,7 +65,8 @@ def test_header_prototype_argtypes_and_method_agree(mrs):
 
 def test_every_kernel_has_a_row_and_the_shape_of_its_mirror():
     k = rollout_kernels()
-    mine = macro_lines(k.texts[FILE], "MRS_ROLLOUT_TICK_COST_KERNEL")
+    mine = k.tick_families["_cost"]
+    assert k.tick_types["_cost"] == ("RolloutTickCostDev", "RolloutTickCostHook")
     assert len(mine) == 4 and set(mine) == set(MIRRORS), sorted(mine)
     k.check_table(mine, RTC.ROLLOUT_TICK_COST_KERNELS, RTC, "cost tick")
     coll = macro_lines(open(os.path.join(CSRC, "step_device.inc")).read(), "MRS_STEP_KERNEL_COLL")
@@ -75,10 +76,12 @@ def test_every_kernel_has_a_row_and_the_shape_of_its_mirror():
         assert args == coll[MIRRORS[name]][:-1], (name, args, coll[MIRRORS[name]])
     # and of the tick kernel beside it
     assert {n.replace("_tick_cost", "_tick"): v for n, v in mine.items()} == k.tick
-    # compiled by both step units (rollout_kernels checks that the two include lists are one), behind LaneObs and in front of the tick file
-    assert k.files.index("rollout_cost_device.inc") < k.files.index(FILE) == len(k.files) - 2
+    # compiled by both step units (rollout_kernels checks that the two include lists are one), behind LaneObs and in front of the tick
+    # rollout's own family, which stays last
+    assert k.files.index("rollout_cost_device.inc") < k.files.index(FILE) == len(k.files) - 1
+    assert list(k.tick_families)[-2:] == ["_cost", ""] and k.order[-8:] == list(mine) + list(k.tick)
     # none of them is a kernel the earlier tables know
-    assert not set(mine) & set(k.order) and not set(mine) & set(k.step_kernels)
+    assert not set(mine) & ({n for fam in k.families.values() for n in fam} | set(k.tick)) and not set(mine) & set(k.step_kernels)
     for unit in STEP_UNITS:
         assert open(os.path.join(CSRC, unit)).read().count(f'#include "{FILE}"') == 1, unit
 
@@ -88,13 +91,16 @@ def test_no_other_kernel_lines_in_the_file():
     k = rollout_kernels()
     text = k.texts[FILE]
     assert "MRS_STEP_KERNEL" not in text
-    for macro in ("MRS_ROLLOUT_FAMILY", "MRS_ROLLOUT_SHAPE", "MRS_ROLLOUT_TICK_KERNEL"):
+    for macro in ("MRS_ROLLOUT_FAMILY", "MRS_ROLLOUT_SHAPE"):
         assert not re.search(rf"^\s*(#define\s+)?{macro}\(", text, flags=re.M), macro
-    assert not macro_lines(text, "MRS_ROLLOUT_TICK_KERNEL")
+    # one family line of its own, and the four shape lines of the family macro are every kernel line of the file
+    assert len(re.findall(r"^MRS_ROLLOUT_TICK_FAMILY\(_cost, ", text, flags=re.M)) == 1
+    assert len(macro_lines(text, "MRS_ROLLOUT_TICK_SHAPE")) == 4 and text.count("MRS_ROLLOUT_TICK_SHAPE(") == 5
     assert "mrs_ro_sched" not in text and "MRS_RO_" not in text and "mrs_ro_" not in text, "no schedule words"
-    assert text.count("__global__") == 1, "the macro is the only kernel definition"
-    # the descriptor is a kernel argument behind CollDev, whose offset is pinned, and the header states the replay argument
-    assert "static_assert(offsetof(RolloutTickCostKernArgs, cd) == offsetof(CollKernArgs, cd)" in text
+    assert text.count("__global__") == 1, "the shape macro is the only kernel definition"
+    # the descriptor is a kernel argument behind CollDev, whose offset is pinned for every family, and the header states the replay argument
+    family = text[text.index("#define MRS_ROLLOUT_TICK_FAMILY("):text.index("MRS_ROLLOUT_TICK_FAMILY(_feedback")]
+    assert "static_assert(offsetof(RolloutTickKernArgs<DevType>, cd) == offsetof(CollKernArgs, cd)" in family
     assert "no-op launch" in text.split("namespace {")[0]
     layout = open(os.path.join(CSRC, "swarm_layout.h")).read()
     body = layout[layout.index("struct RolloutTickCostDev {"):]

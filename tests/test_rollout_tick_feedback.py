@@ -5,8 +5,8 @@ tests/cpp/rollout_tick_feedback_test.cpp compiles.  CPU tensors only: no pointer
 
 The call has kernels of its own: exactly four, each with a row in test_rollout_tick_feedback_gpu.ROLLOUT_TICK_FEEDBACK_KERNELS and the
 shape of the single-GPU MRS_STEP_KERNEL_COLL line it mirrors; they belong to no rollout family, are no tick-rollout kernel and no
-step-kernel line, and their file comes behind rollout_cost_device.inc and in front of rollout_tick_cost_device.inc, so the tables and
-positions of the earlier tests stay as they are."""
+step-kernel line, and their tick family (_feedback) is defined behind rollout_cost_device.inc and in front of the cost tick family, so
+the tables and positions of the earlier tests stay as they are."""
 import ctypes as C
 import inspect
 import os
@@ -20,7 +20,7 @@ from helpers import CSRC, STEP_UNITS, macro_lines, rollout_kernels
 from test_rollout import CTYPE, ROOT
 from test_rollout_tick import _fakes
 
-FILE = "rollout_tick_feedback_device.inc"
+FILE = "rollout_tick_device.inc"  # the tick families share one file; this one is MRS_ROLLOUT_TICK_FAMILY(_feedback, ...)
 NAMES = ["s", "first", "count", "mode", "dt", "n_ticks", "cmd_every", "cost_every", "dev_cmd", "dtype", "cmd_stride",
          "fb_groups", "dev_gain", "gain_per_uav", "gain_blocks", "dev_ref", "ref_stride", "ref_blocks",
          "cost_groups", "dev_target", "target_stride", "dev_weight", "weight_stride", "crash_cost", "dev_cost", "accumulate",
@@ -73,7 +73,8 @@ def test_header_prototype_argtypes_and_method_agree(mrs):
 
 def test_every_kernel_has_a_row_and_the_shape_of_its_mirror():
     k = rollout_kernels()
-    mine = macro_lines(k.texts[FILE], "MRS_ROLLOUT_TICK_FEEDBACK_KERNEL")
+    mine = k.tick_families["_feedback"]
+    assert k.tick_types["_feedback"] == ("RolloutTickFeedbackDev", "RolloutTickFeedbackHook")
     assert len(mine) == 4 and set(mine) == set(MIRRORS), sorted(mine)
     k.check_table(mine, RTF.ROLLOUT_TICK_FEEDBACK_KERNELS, RTF, "feedback tick")
     coll = macro_lines(open(os.path.join(CSRC, "step_device.inc")).read(), "MRS_STEP_KERNEL_COLL")
@@ -83,13 +84,13 @@ def test_every_kernel_has_a_row_and_the_shape_of_its_mirror():
         assert args == coll[MIRRORS[name]][:-1], (name, args, coll[MIRRORS[name]])
     # and of the tick kernel and the cost tick kernel beside it
     assert {n.replace("_tick_feedback", "_tick"): v for n, v in mine.items()} == k.tick
-    cost = macro_lines(k.texts["rollout_tick_cost_device.inc"], "MRS_ROLLOUT_TICK_COST_KERNEL")
+    cost = k.tick_families["_cost"]
     assert {n.replace("_tick_feedback", "_tick_cost"): v for n, v in mine.items()} == cost
-    # compiled by both step units, behind LaneObs and the feedback arithmetic's family, in front of the cost tick file and the tick file
-    assert k.files.index("rollout_cost_device.inc") + 1 == k.files.index(FILE) == len(k.files) - 3
-    assert k.files[-2:] == ["rollout_tick_cost_device.inc", "rollout_tick_device.inc"]
+    # compiled by both step units, behind LaneObs and the feedback arithmetic's family, in front of the cost tick family and the tick family
+    assert k.files.index("rollout_cost_device.inc") + 1 == k.files.index(FILE) == len(k.files) - 1
+    assert list(k.tick_families) == ["_feedback", "_cost", ""] and k.order[-12:] == list(mine) + list(cost) + list(k.tick)
     # none of them is a kernel the earlier tables know
-    assert not set(mine) & set(k.order) and not set(mine) & set(k.step_kernels) and not set(mine) & set(cost)
+    assert not set(mine) & ({n for fam in k.families.values() for n in fam} | set(k.tick)) and not set(mine) & set(k.step_kernels) and not set(mine) & set(cost)
     for unit in STEP_UNITS:
         assert open(os.path.join(CSRC, unit)).read().count(f'#include "{FILE}"') == 1, unit
     build = open(os.path.join(os.path.dirname(CSRC), "build.py")).read()
@@ -101,14 +102,18 @@ def test_no_other_kernel_lines_in_the_file():
     k = rollout_kernels()
     text = k.texts[FILE]
     assert "MRS_STEP_KERNEL" not in text
-    for macro in ("MRS_ROLLOUT_FAMILY", "MRS_ROLLOUT_SHAPE", "MRS_ROLLOUT_TICK_KERNEL", "MRS_ROLLOUT_TICK_COST_KERNEL"):
+    for macro in ("MRS_ROLLOUT_FAMILY", "MRS_ROLLOUT_SHAPE"):
         assert not re.search(rf"^\s*(#define\s+)?{macro}\(", text, flags=re.M), macro
         assert not macro_lines(text, macro), macro
+    # one family line of its own, and the four shape lines of the family macro are every kernel line of the file
+    assert len(re.findall(r"^MRS_ROLLOUT_TICK_FAMILY\(_feedback, ", text, flags=re.M)) == 1
+    assert len(macro_lines(text, "MRS_ROLLOUT_TICK_SHAPE")) == 4 and text.count("MRS_ROLLOUT_TICK_SHAPE(") == 5
     assert "mrs_ro_sched" not in text and "MRS_RO_" not in text and "mrs_ro_" not in text, "no schedule words"
-    assert text.count("__global__") == 1, "the macro is the only kernel definition"
-    # the descriptor is a kernel argument behind CollDev, whose offset is pinned; the header states the replay argument and why the
-    # command may be formed ahead of the collision evaluation
-    assert "static_assert(offsetof(RolloutTickFeedbackKernArgs, cd) == offsetof(CollKernArgs, cd)" in text
+    assert text.count("__global__") == 1, "the shape macro is the only kernel definition"
+    # the descriptor is a kernel argument behind CollDev, whose offset is pinned for every family; the header states the replay argument
+    # and why the command may be formed ahead of the collision evaluation
+    family = text[text.index("#define MRS_ROLLOUT_TICK_FAMILY("):text.index("MRS_ROLLOUT_TICK_FAMILY(_feedback")]
+    assert "static_assert(offsetof(RolloutTickKernArgs<DevType>, cd) == offsetof(CollKernArgs, cd)" in family
     head = text.split("namespace {")[0]
     assert "no-op launch" in head and "MRS_COLLIDE_EVAL" in head and "F_FEXT" in head
     assert "mrs_obs_row_feedback(" in text and "mrs_obs_row_cost(" in text
@@ -116,10 +121,16 @@ def test_no_other_kernel_lines_in_the_file():
     body = layout[layout.index("struct RolloutTickFeedbackDev {"):]
     body = body[:body.index("};")]
     assert "sched" not in body and "_blk" not in body and "crash_cost" in body and "gain_col" in body
-    # step_device.inc admits the hook on the tick shape and forward-declares it; nothing else of it names the new type
+    # step_device.inc admits the hook on the tick shape by the trait its base declares, and names none of the tick hook types
     step = open(os.path.join(CSRC, "step_device.inc")).read()
-    assert step.count("RolloutTickFeedbackHook") == 2
-    assert "__is_same(HK, RolloutTickFeedbackHook)) && NU == 1 && !MULTI && COLL && !SHARD" in step
+    assert "RolloutTick" not in step
+    assert "(HK::kOnCollKernels && NU == 1 && !MULTI && COLL && !SHARD)" in step
+    base = text[text.index("struct RolloutTickHookBase {"):text.index("struct RolloutTickHook :")]
+    assert "static constexpr bool kOnCollKernels = true;" in base
+    assert "struct RolloutTickFeedbackHook : RolloutTickEvalHook<RolloutTickFeedbackDev>" in text
+    assert "struct RolloutTickEvalHook : RolloutTickHookBase<Dev>" in text
+    for other in ("step_device.inc", "rollout_device.inc"):  # every other hook says it does not: NoStepHook and the sub-step hooks' base
+        assert open(os.path.join(CSRC, other)).read().count("static constexpr bool kOnCollKernels = false;") == 1, other
 
 
 class _Swarm:

@@ -779,6 +779,13 @@ public:
                      int index_stride, int32_t* dev_count, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_nearest_device(s_, first, count, k, radius, fields, dev_rows, dtype, stride, dev_index, index_stride, dev_count, stream));
   }
+  // a separation penalty over the k nearest other UAVs within `radius`, one FP64 number per UAV (mrs_swarm_proximity_cost_device): kind
+  // MRS_PROX_HINGE2 / INVERSE / COUNT; written to dev_cost, or added to it (accumulate); dev_found (may be null): the neighbours within
+  // the radius, not capped by k
+  void proximityCostDevice(int first, int count, int k, double radius, int kind, double weight, double eps, double* dev_cost, bool accumulate,
+                           int32_t* dev_found = nullptr, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_proximity_cost_device(s_, first, count, k, radius, kind, weight, eps, dev_cost, accumulate ? 1 : 0, dev_found, stream));
+  }
   // collision worlds (mrs_swarm_set_worlds): UAVs interact through the collision pass, and appear in each other's nearest-neighbour rows,
   // only if their 32-bit labels are equal (0 until set); the labels of UAVs [first, first + worlds.size())
   void setWorlds(int first, const std::vector<int32_t>& worlds) {

@@ -538,6 +538,37 @@ int mrs_nearest_width(uint32_t fields, int32_t k, int32_t* width);
 int mrs_swarm_nearest_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t k, double radius, uint32_t fields, void* dev_rows, int32_t dtype,
                              int32_t stride, int32_t* dev_index, int32_t index_stride, int32_t* dev_count, void* ext_stream);
 
+/* ---- proximity cost: a per-UAV separation penalty over the k nearest UAVs, added into the cost vector of the cost rollouts ----
+ * The search of mrs_swarm_nearest_device followed by a reduction, so that no neighbour row is written and read back.  Neighbours are
+ * word for word those of mrs_swarm_nearest_device: query set [first, first+count); candidates every UAV with a finite position, crashed
+ * ones included; a UAV is never its own neighbour; equal world labels only, once a label was ever set; d2 = ((dx*dx) + dy*dy) + dz*dz
+ * < radius * radius in FP64 without contraction (radius * radius rounded once on the host); order ascending (d2, j).  Let `found` be the
+ * number of such neighbours and nf = min(found, k).  Evaluation of UAV first + r:
+ *     term = +0.0
+ *     for m in [0, nf):                    (nearest first: the slot order of mrs_swarm_nearest_device)
+ *       MRS_PROX_HINGE2 : d = sqrt(d2_m) (as MRS_NN_DIST forms it);  g = radius - d;  term = term + (weight * g) * g
+ *       MRS_PROX_INVERSE: term = term + weight / (d2_m + eps)
+ *       MRS_PROX_COUNT  : term = term + weight
+ *     c = accumulate ? dev_cost[r] : +0.0
+ *     c = c + term
+ *     dev_cost[r] = c
+ *     if (dev_found) dev_found[r] = found
+ * dev_found is NOT capped by k: a value above k says the term left neighbours out.  Everything is FP64, one rounding per operation, no
+ * fused multiply-add, and nothing is special-cased: a query UAV with a non-finite position adds +0.0, coincident UAVs under INVERSE with
+ * eps == 0 give what IEEE gives (weight / 0), any weight is legal.  With accumulate == 0 the result does not depend on what dev_cost
+ * held (it is not read); elements outside [0, count) are not touched.
+ * Entry, stream fence and host waits are those of mrs_swarm_nearest_device: no simulation state is written, the collision pass's
+ * tables are left alone, a pending collision tick stays pending; the scratch is that of mrs_swarm_nearest_device.  A horizon cut at its
+ * evaluation points reads rollout_tick_cost(accumulate) -> proximity_cost(accumulate) -> rollout_tick_cost(accumulate) -> ..., and the
+ * proximity calls between the pieces leave the simulation bit for bit as it was.
+ * Every argument is checked before any launch, and a refused call changes nothing: the range MRS_ERR_RANGE; MRS_ERR_ARG for k outside
+ * [1, MRS_NN_MAX_K], a radius that is not finite and > 0, an unknown kind, under INVERSE an eps that is NaN, infinite or negative (eps is
+ * ignored by the other kinds), a NULL dev_cost, a dev_cost or dev_found that is not device memory of the swarm's device holding `count`
+ * elements, and a sharded swarm.  count == 0 is MRS_OK. */
+enum { MRS_PROX_HINGE2 = 0, MRS_PROX_INVERSE = 1, MRS_PROX_COUNT = 2 };
+int mrs_swarm_proximity_cost_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t k, double radius, int32_t kind, double weight, double eps,
+                                    double* dev_cost, int32_t accumulate, int32_t* dev_found /* may be NULL */, void* ext_stream);
+
 /* ---- collision worlds: several scenes in one swarm that do not see each other (per-sample horizons of a sampling-based planner) ----
  * A world is a 32-bit label per UAV, 0 for every UAV until a setter says otherwise.  Two UAVs interact through the collision pass
  * (mrs_swarm_handle_collisions, mrs_swarm_tick_n, the tick rollouts), or appear in each other's rows of mrs_swarm_nearest_device, only

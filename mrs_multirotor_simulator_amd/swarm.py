@@ -122,6 +122,7 @@ ABI_SYMBOLS = [
     "mrs_swarm_rollout_tick_cost_device",
     "mrs_swarm_rollout_tick_feedback_device",
     "mrs_swarm_set_worlds", "mrs_swarm_get_worlds", "mrs_swarm_set_worlds_device",
+    "mrs_swarm_proximity_cost_device",
 ]
 
 # device-resident callers (mrs_swarm_*_device): row element types and the observation groups of mrs_swarm_gather_device, in bit order
@@ -132,6 +133,8 @@ OBS_ALL = 0xFF
 NN_REL_POS, NN_REL_POS_BODY, NN_REL_VEL, NN_REL_VEL_BODY, NN_DIST = (1 << b for b in range(5))
 NN_ALL = 0x1F
 NN_MAX_K = 32
+# kinds of mrs_swarm_proximity_cost_device: weight (radius - d)^2, weight / (d2 + eps), weight per listed neighbour
+PROX_HINGE2, PROX_INVERSE, PROX_COUNT = 0, 1, 2
 # state snapshots (mrs_swarm_save_device / mrs_swarm_load_device): one mrs_uav_snapshot_t record per UAV, 496 B
 SNAP_CRASHED, SNAP_TAKEOFF, SNAP_VPREV_SPLIT = 1, 2, 4
 SNAP_MAGIC = 0x50414E53
@@ -362,6 +365,7 @@ def load_library():
         "mrs_swarm_set_worlds_device": [vp, i32, i32, vp, vp],
         "mrs_nearest_width": [C.c_uint32, i32, ip],
         "mrs_swarm_nearest_device": [vp, i32, i32, i32, C.c_double, C.c_uint32, vp, i32, i32, vp, i32, vp, vp],
+        "mrs_swarm_proximity_cost_device": [vp, i32, i32, i32, C.c_double, i32, C.c_double, C.c_double, vp, i32, vp, vp],
         "mrs_swarm_save_device": [vp, i32, i32, vp, vp],
         "mrs_swarm_load_device": [vp, i32, i32, vp, C.c_int64, vp, vp, vp],
         "mrs_swarm_rollout_device": [vp, i32, i32, i32, C.c_double, i32, vp, i32, i32, C.c_uint32, vp, i32, vp],
@@ -861,6 +865,11 @@ class Swarm:
         _check(_lib.mrs_swarm_nearest_device(self._h, int(first), int(count), int(k), C.c_double(float(radius)), C.c_uint32(int(fields)),
                                              dev_rows or None, int(dtype), int(stride), dev_index or None, int(index_stride), dev_count or None,
                                              ext_stream or None))
+
+    def proximity_cost_device(self, first, count, k, radius, kind, weight, eps, dev_cost, accumulate, dev_found, ext_stream):
+        _check(_lib.mrs_swarm_proximity_cost_device(self._h, int(first), int(count), int(k), C.c_double(float(radius)), int(kind),
+                                                    C.c_double(float(weight)), C.c_double(float(eps)), dev_cost or None,
+                                                    int(bool(accumulate)), dev_found or None, ext_stream or None))
 
     def save_device(self, first, count, dev_records, ext_stream):
         _check(_lib.mrs_swarm_save_device(self._h, int(first), int(count), dev_records or None, ext_stream or None))

@@ -12,7 +12,7 @@ import torch
 
 from .swarm import (ACTUATOR_CMD, ATTITUDE_CMD, DTYPE_F32, DTYPE_F64, INPUT_UNKNOWN, MAX_MOTORS, NN_ALL, NN_DIST, NN_MAX_K,  # noqa: F401
                     NN_REL_POS, NN_REL_POS_BODY, NN_REL_VEL, NN_REL_VEL_BODY, OBS_ALL, OBS_IMU, OBS_OMEGA, OBS_POS, OBS_QUAT, OBS_ROT,
-                    OBS_RPM, OBS_VEL, OBS_VEL_BODY, SNAP_BAD_AIRFRAME, SNAP_BAD_INDEX, SNAP_BAD_MAGIC, SNAP_CRASHED, SNAP_LOADED,
+                    OBS_RPM, OBS_VEL, OBS_VEL_BODY, PROX_COUNT, PROX_HINGE2, PROX_INVERSE, SNAP_BAD_AIRFRAME, SNAP_BAD_INDEX, SNAP_BAD_MAGIC, SNAP_CRASHED, SNAP_LOADED,
                     SNAP_MAGIC, SNAP_SKIPPED, SNAP_TAKEOFF, SNAP_VPREV_SPLIT, SNAPSHOT_DTYPE, TILT_HDG_RATE_CMD, gather_width, nearest_width)
 
 _DTYPES = {torch.float64: DTYPE_F64, torch.float32: DTYPE_F32}
@@ -641,6 +641,35 @@ def nearest(swarm, k, radius, fields=NN_REL_POS | NN_DIST, first=0, count=None, 
     if fields:
         rows = out[:, :width] if out.shape[1] > width else out
     return rows, (index[:, :k] if index.shape[1] > k else index), counts
+
+
+def proximity_cost(swarm, radius, k=8, kind=PROX_HINGE2, weight=1.0, eps=0.0, first=0, count=None, out=None, accumulate=False, found=False):
+    """A separation penalty over the k nearest other UAVs within `radius` of each UAV of [first, first + count), one FP64 number per UAV
+    (mrs_swarm_proximity_cost_device): the neighbours of nearest(), nearest first, summed as weight * (radius - d)^2 (PROX_HINGE2),
+    weight / (d2 + eps) (PROX_INVERSE) or weight (PROX_COUNT) per listed neighbour.  `out` is a dense torch.float64 [count] vector on
+    the swarm's device (a new one when None); accumulate=True adds the term to what `out` holds (the vector of the cost rollouts) and
+    needs it.  found: False, True (a new int32 [count] vector) or an int32 [count] vector: the number of neighbours within the radius,
+    not capped by k.  Returns (out, found or None).  No simulation state is written; a pending collision tick stays pending."""
+    count = _count(swarm, first, count)
+    dev = swarm.device()
+    tdev = torch.device("cuda", dev)
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs the `out` vector it adds to")
+        out = torch.empty(count, dtype=torch.float64, device=tdev)
+    if isinstance(out, torch.Tensor) and out.dtype != torch.float64:
+        raise ValueError(f"out has dtype {out.dtype}: the cost vector is always torch.float64")
+    check_tensor(out, count, None, torch.float64, dev)
+    fptr = 0
+    if found is True:
+        found = torch.empty(count, dtype=torch.int32, device=tdev)
+    if found is False or found is None:
+        found = None
+    else:
+        check_tensor(found, count, None, torch.int32, dev)
+        fptr = found.data_ptr()
+    swarm.proximity_cost_device(first, count, k, radius, kind, weight, eps, out.data_ptr(), bool(accumulate), fptr, _stream(dev))
+    return out, found
 
 
 def set_worlds(swarm, worlds, first=0):

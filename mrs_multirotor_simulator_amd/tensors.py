@@ -8,6 +8,8 @@ wrong dtypes or shapes are refused with a ValueError.  Row k of every tensor bel
 
 Imports torch; the package itself does not.
 """
+import collections
+
 import torch
 
 from .swarm import (ACTUATOR_CMD, ATTITUDE_CMD, DTYPE_F32, DTYPE_F64, INPUT_UNKNOWN, MAX_MOTORS, NN_ALL, NN_DIST, NN_MAX_K,  # noqa: F401
@@ -19,19 +21,26 @@ _DTYPES = {torch.float64: DTYPE_F64, torch.float32: DTYPE_F32}
 SNAP_BYTES = SNAPSHOT_DTYPE.itemsize  # 496: one mrs_uav_snapshot_t
 
 
+def _check_device(t, name, dtypes, device_index):
+    """Refuse `t` unless it is a tensor on cuda:`device_index` whose dtype is one of `dtypes`.  The messages open with `name`; None:
+    an unnamed tensor, in check_tensor's wording."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name + ': ' if name else ''}expected a torch.Tensor, got {type(t).__name__}")
+    who = name or "tensor"
+    if t.device.type != "cuda":
+        raise ValueError(f"{who} is on {t.device}: device-resident calls need a tensor on cuda:{device_index}"
+                         + ("" if name else " (use the host calls of Swarm for CPU data)"))
+    if t.device.index != device_index:
+        raise ValueError(f"{who} is on {t.device}, the swarm lives on cuda:{device_index}")
+    if t.dtype not in dtypes:
+        raise ValueError(f"{who} has dtype {t.dtype}, expected {' or '.join(str(d) for d in dtypes)}")
+
+
 def check_tensor(t, rows, min_width, dtype, device_index):
     """Refuse `t` unless it is a tensor on cuda:`device_index` of `dtype` with `rows` rows whose last dimension is contiguous.
     min_width None: a vector of `rows` elements; else a [rows, >= min_width] matrix.  Returns the row stride in elements (the
     distance between two rows; the columns past min_width are padding the library does not touch).  Needs no GPU."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"expected a torch.Tensor, got {type(t).__name__}")
-    if t.device.type != "cuda":
-        raise ValueError(f"tensor is on {t.device}: device-resident calls need a tensor on cuda:{device_index} (use the host calls of Swarm "
-                         "for CPU data)")
-    if t.device.index != device_index:
-        raise ValueError(f"tensor is on {t.device}, the swarm lives on cuda:{device_index}")
-    if t.dtype != dtype:
-        raise ValueError(f"tensor has dtype {t.dtype}, expected {dtype}")
+    _check_device(t, None, (dtype,), device_index)
     if min_width is None:
         if t.dim() != 1 or t.shape[0] != rows:
             raise ValueError(f"expected a vector of {rows} elements, got shape {tuple(t.shape)}")
@@ -120,14 +129,7 @@ def apply_force(swarm, rows, first=0):
 def _check_steps(t, name, steps, rows, min_width, dtype, device_index):
     """Refuse `t` unless it is a [steps, rows, >= min_width] tensor on cuda:`device_index` of `dtype` (steps None: any number >= 1) whose
     rows are contiguous and whose row blocks follow each other densely: stride(0) == rows * stride(1).  Returns the row stride."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
-    if t.device.type != "cuda":
-        raise ValueError(f"{name} is on {t.device}: device-resident calls need a tensor on cuda:{device_index}")
-    if t.device.index != device_index:
-        raise ValueError(f"{name} is on {t.device}, the swarm lives on cuda:{device_index}")
-    if t.dtype != dtype:
-        raise ValueError(f"{name} has dtype {t.dtype}, expected {dtype}")
+    _check_device(t, name, (dtype,), device_index)
     if t.dim() != 3 or t.shape[0] < 1 or (steps is not None and t.shape[0] != steps) or t.shape[1] != rows or t.shape[2] < min_width:
         raise ValueError(f"{name}: expected a [{'T' if steps is None else steps}, {rows}, >= {min_width}] tensor, got shape {tuple(t.shape)}")
     if t.shape[2] > 1 and t.stride(2) != 1:
@@ -140,245 +142,9 @@ def _check_steps(t, name, steps, rows, min_width, dtype, device_index):
     return stride
 
 
-def rollout(swarm, mode, commands, dt, groups=OBS_POS | OBS_VEL | OBS_QUAT, first=0, out=None, hold=1, obs_every=None, forces=None,
-            force_hold=None):
-    """B * hold steps of the whole swarm in which UAVs [first, first + count) take command row block j before step j * hold, keep it for
-    `hold` steps (setInput latches), and report the OBS_* groups of `groups` after every `obs_every` steps (default: `hold`, a row block
-    per command; B * hold: the final state only).  With hold == 1 (mrs_swarm_rollout_device): `for t: set_input(swarm, mode,
-    commands[t], first); swarm.step_n(dt, 1); gather(swarm, groups, first, count, out=out[t])`, bit for bit in LITERAL, in one call;
-    with obs_every == hold (mrs_swarm_rollout_rate_device): `for j: set_input(commands[j]); swarm.step_n(dt, hold); gather(out=out[j])`.
-    commands: [B, count, >= width] FP32 / FP64 (the payload layouts of set_input; ACTUATOR rows are dense).  obs_every must be >= 1 and
-    divide B * hold.  out: [B * hold // obs_every, count, >= gather_width(groups)] of the same dtype, allocated when None; returned
-    (None when groups == 0).  UAVs outside the range are stepped with their own commands.
-    forces: [Bf, count, >= 3] of the commands' dtype: UAVs of the range take force row block j (applyForce: world frame, newtons) before
-    step j * force_hold and keep it for `force_hold` steps (default: B * hold // Bf; it must be >= 1 and Bf * force_hold == B * hold) —
-    the loop above with `apply_force(swarm, forces[j], first)` in it, in one call (mrs_swarm_rollout_force_device).  Afterwards the range
-    carries the last force block."""
-    dev = swarm.device()
-    if not isinstance(commands, torch.Tensor) or commands.dim() != 3:
-        raise ValueError("commands must be a [T, count, width] tensor")
-    hold = int(hold)
-    if hold < 1:
-        raise ValueError(f"hold must be at least 1, got {hold}")
-    code = _dtype_code(commands.dtype)
-    blocks, count = commands.shape[0], commands.shape[1]
-    steps = blocks * hold
-    every = hold if obs_every is None else int(obs_every)
-    if every < 1 or steps % every != 0:
-        raise ValueError(f"obs_every must be at least 1 and divide the {steps} steps of the call, got {every}")
-    width = command_width(mode, commands.shape[2])
-    cstride = _check_steps(commands, "commands", None, count, width, commands.dtype, dev)
-    if mode == ACTUATOR_CMD and count > 1 and cstride != commands.shape[2]:
-        raise ValueError("actuator rows must be dense (row stride == number of motors)")
-    if forces is not None:
-        fstride = _check_steps(forces, "forces", None, count, 3, commands.dtype, dev)
-        fhold = steps // forces.shape[0] if force_hold is None else int(force_hold)
-        if fhold < 1 or forces.shape[0] * fhold != steps:
-            raise ValueError(f"force_hold must be at least 1 and {forces.shape[0]} force blocks x force_hold must be the {steps} steps of the "
-                             f"call, got {fhold}")
-    owidth = gather_width(groups)
-    optr, ostride = 0, owidth
-    if groups:
-        if out is None:
-            out = torch.empty((steps // every, count, owidth), dtype=commands.dtype, device=torch.device("cuda", dev))
-        if isinstance(out, torch.Tensor) and out.dtype != commands.dtype:
-            raise ValueError(f"out has dtype {out.dtype}, the commands {commands.dtype}: one dtype serves both")
-        ostride = _check_steps(out, "out", steps // every, count, owidth, commands.dtype, dev)
-        optr = out.data_ptr()
-    cptr = commands.data_ptr() if width > 0 and count > 0 else 0
-    if forces is not None:
-        swarm.rollout_force_device(first, count, mode, dt, steps, hold, every, fhold, cptr, code, cstride, forces.data_ptr(), fstride, groups,
-                                   optr, ostride, _stream(dev))
-    elif hold == 1 and every == 1:
-        swarm.rollout_device(first, count, mode, dt, steps, cptr, code, cstride, groups, optr, ostride, _stream(dev))
-    else:
-        swarm.rollout_rate_device(first, count, mode, dt, steps, hold, every, cptr, code, cstride, groups, optr, ostride, _stream(dev))
-    if not groups:
-        return None
-    return out[:, :, :owidth] if out.shape[2] > owidth else out
-
-
-def rollout_cost(swarm, mode, commands, dt, groups, targets, weights, first=0, hold=1, cost_every=None, out=None, accumulate=False):
-    """rollout(hold=hold, obs_every=cost_every) that returns one FP64 number per UAV instead of row blocks: after every `cost_every` steps
-    (default: `hold`; B * hold: a terminal cost) the FP64 observation row of `groups` of UAV first + k is compared with its target row, and
-    `sum over columns of (weight * d) * d`, d = row - target, is added to the UAV's cost (mrs_swarm_rollout_cost_device; the arithmetic is
-    FP64, unfused, columns ascending, evaluations in order, in both flavours).  commands: as in rollout.  With E = B * hold // cost_every
-    evaluations and w = gather_width(groups): targets is [E, count, >= w] (a row per UAV) or [E, 1, w] (one dense row per evaluation for
-    all UAVs); weights is [E, >= w] (a row per evaluation: a heavier last row is a terminal cost) or [1, >= w]; both of the commands'
-    dtype.  out: a float64 [count] vector, allocated when None; accumulate=True adds to what `out` holds (two calls over the halves of a
-    horizon give the bits of one call), else it is overwritten.  Returns out.  No observation row is written."""
-    dev = swarm.device()
-    if not isinstance(commands, torch.Tensor) or commands.dim() != 3:
-        raise ValueError("commands must be a [T, count, width] tensor")
-    hold = int(hold)
-    if hold < 1:
-        raise ValueError(f"hold must be at least 1, got {hold}")
-    code = _dtype_code(commands.dtype)
-    blocks, count = commands.shape[0], commands.shape[1]
-    steps = blocks * hold
-    every = hold if cost_every is None else int(cost_every)
-    if every < 1 or steps % every != 0:
-        raise ValueError(f"cost_every must be at least 1 and divide the {steps} steps of the call, got {every}")
-    evals = steps // every
-    width = command_width(mode, commands.shape[2])
-    cstride = _check_steps(commands, "commands", None, count, width, commands.dtype, dev)
-    if mode == ACTUATOR_CMD and count > 1 and cstride != commands.shape[2]:
-        raise ValueError("actuator rows must be dense (row stride == number of motors)")
-    w = gather_width(groups)
-    if w == 0:
-        raise ValueError("groups must select at least one observation group: a cost needs columns")
-    for name, t in (("targets", targets), ("weights", weights)):
-        if isinstance(t, torch.Tensor) and t.dtype != commands.dtype:
-            raise ValueError(f"{name} has dtype {t.dtype}, the commands {commands.dtype}: one dtype serves commands, targets and weights")
-    if (not isinstance(targets, torch.Tensor) or targets.dim() != 3 or targets.shape[0] != evals or targets.shape[1] not in (1, count)
-            or targets.shape[2] < w):
-        raise ValueError(f"targets: expected a [{evals}, {count} or 1, >= {w}] tensor, got "
-                         f"{tuple(targets.shape) if isinstance(targets, torch.Tensor) else type(targets).__name__}")
-    if targets.shape[1] == 1:  # one row per evaluation: its stride is that of the first dimension
-        tstride = check_tensor(targets[:, 0, :], evals, w, commands.dtype, dev)
-        if count != 1:
-            if evals > 1 and tstride != w:
-                raise ValueError(f"targets: shared target rows must be dense, [{evals}, 1, {w}], got a row stride of {tstride}")
-            tstride = 0
-    else:
-        tstride = _check_steps(targets, "targets", evals, count, w, commands.dtype, dev)
-    if not isinstance(weights, torch.Tensor) or weights.dim() != 2 or weights.shape[0] not in (1, evals):
-        raise ValueError(f"weights: expected a [{evals} or 1, >= {w}] tensor, got "
-                         f"{tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights).__name__}")
-    wstride = check_tensor(weights, weights.shape[0], w, commands.dtype, dev)
-    if weights.shape[0] == 1:
-        wstride = 0
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate=True needs the `out` vector it adds to")
-        out = torch.empty(count, dtype=torch.float64, device=torch.device("cuda", dev))
-    if isinstance(out, torch.Tensor) and out.dtype != torch.float64:
-        raise ValueError(f"out has dtype {out.dtype}: the cost vector is always torch.float64")
-    check_tensor(out, count, None, torch.float64, dev)
-    cptr = commands.data_ptr() if width > 0 and count > 0 else 0
-    swarm.rollout_cost_device(first, count, mode, dt, steps, hold, every, cptr, code, cstride, groups, targets.data_ptr(), tstride,
-                              weights.data_ptr(), wstride, out.data_ptr(), bool(accumulate), _stream(dev))
-    return out
-
-
-def rollout_ticks(swarm, mode, commands, dt, crash, rebounce, groups=OBS_POS | OBS_VEL | OBS_QUAT, first=0, out=None, hold=1, obs_every=None,
-                  crashed=None):
-    """B * hold ticks of the whole swarm in one call (mrs_swarm_rollout_tick_device): each tick is a step of every UAV, then the
-    collision pass `swarm.handle_collisions(True, crash, rebounce)`.  UAVs [first, first + count) take command row block j before tick
-    j * hold and keep it for `hold` ticks; after every `obs_every` ticks (default: `hold`) the OBS_* groups of `groups` and the crash
-    flags of the range are reported, taken after the tick's step and before its collision pass.  It is the loop `for t: set_input(...);
-    swarm.tick_n(dt, 1, True, crash, rebounce); gather(...); crashed(...)` with the rows taken between the step and the collision pass,
-    bit for bit in LITERAL, with one host wait per call.
-    commands, out: as in rollout.  crashed: a dense torch.bool or torch.uint8 [B * hold // obs_every, count] tensor, allocated (bool) when
-    None; crashed=False asks for no crash rows.  Returns (rows or None when groups == 0, crashed or None).  The collision pass of the last
-    tick stays pending: the next step or tick evaluates it."""
-    dev = swarm.device()
-    if not isinstance(commands, torch.Tensor) or commands.dim() != 3:
-        raise ValueError("commands must be a [T, count, width] tensor")
-    hold = int(hold)
-    if hold < 1:
-        raise ValueError(f"hold must be at least 1, got {hold}")
-    code = _dtype_code(commands.dtype)
-    blocks, count = commands.shape[0], commands.shape[1]
-    ticks = blocks * hold
-    every = hold if obs_every is None else int(obs_every)
-    if every < 1 or ticks % every != 0:
-        raise ValueError(f"obs_every must be at least 1 and divide the {ticks} ticks of the call, got {every}")
-    width = command_width(mode, commands.shape[2])
-    cstride = _check_steps(commands, "commands", None, count, width, commands.dtype, dev)
-    if mode == ACTUATOR_CMD and count > 1 and cstride != commands.shape[2]:
-        raise ValueError("actuator rows must be dense (row stride == number of motors)")
-    owidth = gather_width(groups)
-    optr, ostride = 0, owidth
-    if groups:
-        if out is None:
-            out = torch.empty((ticks // every, count, owidth), dtype=commands.dtype, device=torch.device("cuda", dev))
-        if isinstance(out, torch.Tensor) and out.dtype != commands.dtype:
-            raise ValueError(f"out has dtype {out.dtype}, the commands {commands.dtype}: one dtype serves both")
-        ostride = _check_steps(out, "out", ticks // every, count, owidth, commands.dtype, dev)
-        optr = out.data_ptr()
-    kptr = 0
-    if crashed is False:
-        crashed = None
-    else:
-        if crashed is None:
-            crashed = torch.empty((ticks // every, count), dtype=torch.bool, device=torch.device("cuda", dev))
-        _check_crash_rows(crashed, ticks // every, count, dev)
-        kptr = crashed.data_ptr()
-    cptr = commands.data_ptr() if width > 0 and count > 0 else 0
-    swarm.rollout_tick_device(first, count, mode, dt, ticks, hold, every, cptr, code, cstride, groups, optr, ostride, kptr, bool(crash),
-                              float(rebounce), _stream(dev))
-    rows = None if not groups else (out[:, :, :owidth] if out.shape[2] > owidth else out)
-    return rows, crashed
-
-
-def rollout_tick_cost(swarm, mode, commands, dt, crash, rebounce, groups, targets, weights, crash_cost=0.0, first=0, hold=1, cost_every=None,
-                      out=None, accumulate=False):
-    """rollout_ticks(hold=hold, obs_every=cost_every) that returns one FP64 number per UAV instead of row blocks
-    (mrs_swarm_rollout_tick_cost_device): after every `cost_every` ticks (default: `hold`), between the tick's step and its collision
-    pass, the term of rollout_cost (the FP64 row of `groups` against its target row under the weight row) is added to the UAV's cost,
-    and then `crash_cost` if the UAV has crashed — two separately rounded FP64 additions, in that order.  The crash flag is a level: a
-    UAV that crashed early pays at every later evaluation; a crash caused by the last tick's collision pass stays pending with it and is
-    charged by the next horizon.  commands, targets, weights, out, accumulate: as in rollout_cost.  groups == 0 (then targets and
-    weights stay None) is the crash cost alone.  Returns out.  No observation row and no crash byte is written; the collision pass of
-    the last tick stays pending."""
-    dev = swarm.device()
-    if not isinstance(commands, torch.Tensor) or commands.dim() != 3:
-        raise ValueError("commands must be a [T, count, width] tensor")
-    hold = int(hold)
-    if hold < 1:
-        raise ValueError(f"hold must be at least 1, got {hold}")
-    code = _dtype_code(commands.dtype)
-    blocks, count = commands.shape[0], commands.shape[1]
-    ticks = blocks * hold
-    every = hold if cost_every is None else int(cost_every)
-    if every < 1 or ticks % every != 0:
-        raise ValueError(f"cost_every must be at least 1 and divide the {ticks} ticks of the call, got {every}")
-    evals = ticks // every
-    width = command_width(mode, commands.shape[2])
-    cstride = _check_steps(commands, "commands", None, count, width, commands.dtype, dev)
-    if mode == ACTUATOR_CMD and count > 1 and cstride != commands.shape[2]:
-        raise ValueError("actuator rows must be dense (row stride == number of motors)")
-    w = gather_width(groups)
-    tptr, tstride, wptr, wstride = 0, 0, 0, 0
-    if w == 0:
-        if targets is not None or weights is not None:
-            raise ValueError("groups == 0 is the crash cost alone: it takes no targets and no weights")
-    else:
-        for name, t in (("targets", targets), ("weights", weights)):
-            if isinstance(t, torch.Tensor) and t.dtype != commands.dtype:
-                raise ValueError(f"{name} has dtype {t.dtype}, the commands {commands.dtype}: one dtype serves commands, targets and weights")
-        tstride = _row_blocks(targets, "targets", evals, count, w, commands.dtype, dev)
-        if not isinstance(weights, torch.Tensor) or weights.dim() != 2 or weights.shape[0] not in (1, evals):
-            raise ValueError(f"weights: expected a [{evals} or 1, >= {w}] tensor, got "
-                             f"{tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights).__name__}")
-        wstride = check_tensor(weights, weights.shape[0], w, commands.dtype, dev)
-        if weights.shape[0] == 1:
-            wstride = 0
-        tptr, wptr = targets.data_ptr(), weights.data_ptr()
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate=True needs the `out` vector it adds to")
-        out = torch.empty(count, dtype=torch.float64, device=torch.device("cuda", dev))
-    if isinstance(out, torch.Tensor) and out.dtype != torch.float64:
-        raise ValueError(f"out has dtype {out.dtype}: the cost vector is always torch.float64")
-    check_tensor(out, count, None, torch.float64, dev)
-    cptr = commands.data_ptr() if width > 0 and count > 0 else 0
-    swarm.rollout_tick_cost_device(first, count, mode, dt, ticks, hold, every, cptr, code, cstride, groups, tptr, tstride, wptr, wstride,
-                                   float(crash_cost), out.data_ptr(), bool(accumulate), bool(crash), float(rebounce), _stream(dev))
-    return out
-
-
 def _check_crash_rows(t, blocks, rows, device_index):
     """Refuse `t` unless it is a dense [blocks, rows] torch.bool / torch.uint8 tensor on cuda:`device_index` (block j at byte j * rows)."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"crashed: expected a torch.Tensor, got {type(t).__name__}")
-    if t.device.type != "cuda":
-        raise ValueError(f"crashed is on {t.device}: device-resident calls need a tensor on cuda:{device_index}")
-    if t.device.index != device_index:
-        raise ValueError(f"crashed is on {t.device}, the swarm lives on cuda:{device_index}")
-    if t.dtype not in (torch.bool, torch.uint8):
-        raise ValueError(f"crashed has dtype {t.dtype}, expected torch.bool or torch.uint8")
+    _check_device(t, "crashed", (torch.bool, torch.uint8), device_index)
     if t.dim() != 2 or t.shape[0] != blocks or t.shape[1] != rows:
         raise ValueError(f"crashed: expected a [{blocks}, {rows}] tensor, got shape {tuple(t.shape)}")
     if (rows > 1 and t.stride(1) != 1) or (blocks > 1 and t.stride(0) != rows):
@@ -401,6 +167,227 @@ def _row_blocks(t, name, blocks, count, w, dtype, dev):
     return _check_steps(t, name, blocks, count, w, dtype, dev)
 
 
+# What the six rollout wrappers share.  Every wrapper is _rollout_head, then the blocks its kind takes (_obs_rows; _feedback;
+# _evaluation), then its library call; the blocks raise in the order the wrappers call them, and that order is part of the interface:
+# a call with several faults reports the first.
+_Head = collections.namedtuple("_Head", "dev dtype code blocks count steps hold every width cstride cptr")
+
+
+def _rollout_head(swarm, mode, commands, hold, every, every_name, noun, payload=False):
+    """The command side of a rollout: commands [B, count, >= width] on the swarm's device, held for `hold` steps each, a report or an
+    evaluation after every `every` (the argument `every_name`; default: hold) of the B * hold `noun` ("steps" or "ticks") of the call.
+    payload: the mode must have payload elements.  Returns the _Head the blocks and the library call read: the device, the commands'
+    dtype and its code, B, count, B * hold, hold and every as ints, the payload width, the command row stride and the command pointer
+    (0 when no element would be read)."""
+    dev = swarm.device()
+    if not isinstance(commands, torch.Tensor) or commands.dim() != 3:
+        raise ValueError("commands must be a [T, count, width] tensor")
+    hold = int(hold)
+    if hold < 1:
+        raise ValueError(f"hold must be at least 1, got {hold}")
+    code = _dtype_code(commands.dtype)
+    blocks, count = commands.shape[0], commands.shape[1]
+    steps = blocks * hold
+    every = hold if every is None else int(every)
+    if every < 1 or steps % every != 0:
+        raise ValueError(f"{every_name} must be at least 1 and divide the {steps} {noun} of the call, got {every}")
+    width = command_width(mode, commands.shape[2])
+    if payload and width < 1:
+        raise ValueError("a feedback rollout needs a mode with a payload")
+    cstride = _check_steps(commands, "commands", None, count, width, commands.dtype, dev)
+    if mode == ACTUATOR_CMD and count > 1 and cstride != commands.shape[2]:
+        raise ValueError("actuator rows must be dense (row stride == number of motors)")
+    cptr = commands.data_ptr() if width > 0 and count > 0 else 0
+    return _Head(dev, commands.dtype, code, blocks, count, steps, hold, every, width, cstride, cptr)
+
+
+def _obs_rows(h, groups, out):
+    """The observation rows of rollout and rollout_ticks: `out` is [steps // every, count, >= gather_width(groups)] of the commands' dtype,
+    allocated when None.  Returns (the rows the wrapper returns: `out` without its columns past the width, None when groups == 0; the
+    pointer; the row stride)."""
+    owidth = gather_width(groups)
+    if not groups:
+        return None, 0, owidth
+    if out is None:
+        out = torch.empty((h.steps // h.every, h.count, owidth), dtype=h.dtype, device=torch.device("cuda", h.dev))
+    if isinstance(out, torch.Tensor) and out.dtype != h.dtype:
+        raise ValueError(f"out has dtype {out.dtype}, the commands {h.dtype}: one dtype serves both")
+    ostride = _check_steps(out, "out", h.steps // h.every, h.count, owidth, h.dtype, h.dev)
+    return (out[:, :, :owidth] if out.shape[2] > owidth else out), out.data_ptr(), ostride
+
+
+def _one_dtype(h, **tensors):
+    """Refuse a tensor among `tensors` (by argument name; what is no tensor is left to the check of its shape) of another dtype than the
+    commands'."""
+    for name, t in tensors.items():
+        if isinstance(t, torch.Tensor) and t.dtype != h.dtype:
+            raise ValueError(f"{name} has dtype {t.dtype}, the commands {h.dtype}: one dtype serves commands, "
+                             f"{', '.join(list(tensors)[:-1])} and {list(tensors)[-1]}")
+
+
+def _cost_vector(out, count, accumulate, dev):
+    """The FP64 [count] cost vector of a costed call: `out`, or a new one when None, which accumulate=True refuses"""
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs the `out` vector it adds to")
+        out = torch.empty(count, dtype=torch.float64, device=torch.device("cuda", dev))
+    if isinstance(out, torch.Tensor) and out.dtype != torch.float64:
+        raise ValueError(f"out has dtype {out.dtype}: the cost vector is always torch.float64")
+    check_tensor(out, count, None, torch.float64, dev)
+    return out
+
+
+def _evaluation(h, groups, targets, weights, out, accumulate, alone, refusal):
+    """The cost side of the four costed wrappers.  With E = steps // every evaluations and w = gather_width(groups): targets is
+    [E, count or 1, >= w] (_row_blocks), weights [E or 1, >= w], both of the commands' dtype, and `out` the cost vector (_cost_vector).
+    Returns (out, (target pointer, target stride, weight pointer, weight stride), cost pointer).
+    groups == 0 leaves no column to compare and takes no targets and no weights.  What it means is the wrapper's, told by `alone`;
+    `refusal` is the message of a call that does not fit it:
+      None       nothing: refused (rollout_cost);
+      "crash"    the crash cost alone, with `out` as ever (rollout_tick_cost);
+      "nothing"  a run without a cost: `out` stays None and accumulate false, and None is returned (rollout_feedback);
+      "either"   the crash cost alone into a given `out`, a run without a cost without one: `out` is never allocated, and accumulate
+                 needs it (rollout_tick_feedback)."""
+    w, evals = gather_width(groups), h.steps // h.every
+    rows = (0, 0, 0, 0)
+    if w == 0:
+        if alone is None or targets is not None or weights is not None or (alone == "nothing" and (out is not None or accumulate)):
+            raise ValueError(refusal)
+        if alone != "crash" and out is None and not accumulate:
+            return None, rows, 0
+    else:
+        _one_dtype(h, targets=targets, weights=weights)  # (nothing left to refuse behind _feedback, which compares these two as well)
+        tstride = _row_blocks(targets, "targets", evals, h.count, w, h.dtype, h.dev)
+        if not isinstance(weights, torch.Tensor) or weights.dim() != 2 or weights.shape[0] not in (1, evals):
+            raise ValueError(f"weights: expected a [{evals} or 1, >= {w}] tensor, got "
+                             f"{tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights).__name__}")
+        wstride = check_tensor(weights, weights.shape[0], w, h.dtype, h.dev)
+        rows = (targets.data_ptr(), tstride, weights.data_ptr(), 0 if weights.shape[0] == 1 else wstride)
+    out = _cost_vector(out, h.count, accumulate, h.dev)
+    return out, rows, out.data_ptr()
+
+
+def _feedback(h, fb_groups, gains, refs, targets, weights):
+    """The feedback side of the two feedback wrappers: gains [Bg, W_c, W_o] or [Bg, W_c, W_o, count], dense, and refs
+    [Bg, count or 1, >= W_o] (_row_blocks), Bg in {1, B}, W_o = gather_width(fb_groups) >= 1; one dtype for them, the commands and the
+    cost side's tensors.  Returns (gain pointer, gain_per_uav, gain blocks, ref pointer, ref stride, ref blocks), as the library takes them."""
+    wo = gather_width(fb_groups)
+    if wo == 0:
+        raise ValueError("fb_groups must select at least one observation group: a feedback needs columns")
+    _one_dtype(h, gains=gains, refs=refs, targets=targets, weights=weights)
+    if not isinstance(gains, torch.Tensor) or gains.dim() not in (3, 4):
+        raise ValueError(f"gains: expected a [Bg, {h.width}, {wo}] (shared) or [Bg, {h.width}, {wo}, {h.count}] (per UAV, UAV-minor) tensor, got "
+                         f"{tuple(gains.shape) if isinstance(gains, torch.Tensor) else type(gains).__name__}")
+    per_uav = gains.dim() == 4
+    want = (h.width, wo, h.count) if per_uav else (h.width, wo)
+    if gains.shape[0] not in (1, h.blocks) or tuple(gains.shape[1:]) != want:
+        raise ValueError(f"gains: expected a [{h.blocks} or 1, {', '.join(str(x) for x in want)}] tensor, got {tuple(gains.shape)}")
+    if gains.device.type != "cuda" or gains.device.index != h.dev:
+        raise ValueError(f"gains is on {gains.device}, the swarm lives on cuda:{h.dev}")
+    if not gains.is_contiguous():
+        raise ValueError("gains must be dense" + (": [Bg, W_c, W_o, count] with the UAV index last (g.permute(0, 2, 3, 1).contiguous())"
+                                                  if per_uav else ": [Bg, W_c, W_o], row-major"))
+    if not isinstance(refs, torch.Tensor) or refs.dim() != 3 or refs.shape[0] not in (1, h.blocks):
+        raise ValueError(f"refs: expected a [{h.blocks} or 1, {h.count} or 1, >= {wo}] tensor, got "
+                         f"{tuple(refs.shape) if isinstance(refs, torch.Tensor) else type(refs).__name__}")
+    rstride = _row_blocks(refs, "refs", refs.shape[0], h.count, wo, h.dtype, h.dev)
+    return gains.data_ptr(), int(per_uav), gains.shape[0], refs.data_ptr(), rstride, refs.shape[0]
+
+
+def rollout(swarm, mode, commands, dt, groups=OBS_POS | OBS_VEL | OBS_QUAT, first=0, out=None, hold=1, obs_every=None, forces=None,
+            force_hold=None):
+    """B * hold steps of the whole swarm in which UAVs [first, first + count) take command row block j before step j * hold, keep it for
+    `hold` steps (setInput latches), and report the OBS_* groups of `groups` after every `obs_every` steps (default: `hold`, a row block
+    per command; B * hold: the final state only).  With hold == 1 (mrs_swarm_rollout_device): `for t: set_input(swarm, mode,
+    commands[t], first); swarm.step_n(dt, 1); gather(swarm, groups, first, count, out=out[t])`, bit for bit in LITERAL, in one call;
+    with obs_every == hold (mrs_swarm_rollout_rate_device): `for j: set_input(commands[j]); swarm.step_n(dt, hold); gather(out=out[j])`.
+    commands: [B, count, >= width] FP32 / FP64 (the payload layouts of set_input; ACTUATOR rows are dense).  obs_every must be >= 1 and
+    divide B * hold.  out: [B * hold // obs_every, count, >= gather_width(groups)] of the same dtype, allocated when None; returned
+    (None when groups == 0).  UAVs outside the range are stepped with their own commands.
+    forces: [Bf, count, >= 3] of the commands' dtype: UAVs of the range take force row block j (applyForce: world frame, newtons) before
+    step j * force_hold and keep it for `force_hold` steps (default: B * hold // Bf; it must be >= 1 and Bf * force_hold == B * hold) —
+    the loop above with `apply_force(swarm, forces[j], first)` in it, in one call (mrs_swarm_rollout_force_device).  Afterwards the range
+    carries the last force block."""
+    h = _rollout_head(swarm, mode, commands, hold, obs_every, "obs_every", "steps")
+    if forces is not None:
+        fstride = _check_steps(forces, "forces", None, h.count, 3, h.dtype, h.dev)
+        fhold = h.steps // forces.shape[0] if force_hold is None else int(force_hold)
+        if fhold < 1 or forces.shape[0] * fhold != h.steps:
+            raise ValueError(f"force_hold must be at least 1 and {forces.shape[0]} force blocks x force_hold must be the {h.steps} steps of "
+                             f"the call, got {fhold}")
+    rows, optr, ostride = _obs_rows(h, groups, out)
+    if forces is not None:
+        swarm.rollout_force_device(first, h.count, mode, dt, h.steps, h.hold, h.every, fhold, h.cptr, h.code, h.cstride, forces.data_ptr(),
+                                   fstride, groups, optr, ostride, _stream(h.dev))
+    elif h.hold == 1 and h.every == 1:
+        swarm.rollout_device(first, h.count, mode, dt, h.steps, h.cptr, h.code, h.cstride, groups, optr, ostride, _stream(h.dev))
+    else:
+        swarm.rollout_rate_device(first, h.count, mode, dt, h.steps, h.hold, h.every, h.cptr, h.code, h.cstride, groups, optr, ostride,
+                                  _stream(h.dev))
+    return rows
+
+
+def rollout_cost(swarm, mode, commands, dt, groups, targets, weights, first=0, hold=1, cost_every=None, out=None, accumulate=False):
+    """rollout(hold=hold, obs_every=cost_every) that returns one FP64 number per UAV instead of row blocks: after every `cost_every` steps
+    (default: `hold`; B * hold: a terminal cost) the FP64 observation row of `groups` of UAV first + k is compared with its target row, and
+    `sum over columns of (weight * d) * d`, d = row - target, is added to the UAV's cost (mrs_swarm_rollout_cost_device; the arithmetic is
+    FP64, unfused, columns ascending, evaluations in order, in both flavours).  commands: as in rollout.  With E = B * hold // cost_every
+    evaluations and w = gather_width(groups): targets is [E, count, >= w] (a row per UAV) or [E, 1, w] (one dense row per evaluation for
+    all UAVs); weights is [E, >= w] (a row per evaluation: a heavier last row is a terminal cost) or [1, >= w]; both of the commands'
+    dtype.  out: a float64 [count] vector, allocated when None; accumulate=True adds to what `out` holds (two calls over the halves of a
+    horizon give the bits of one call), else it is overwritten.  Returns out.  No observation row is written."""
+    h = _rollout_head(swarm, mode, commands, hold, cost_every, "cost_every", "steps")
+    out, rows, optr = _evaluation(h, groups, targets, weights, out, accumulate, None,
+                                  "groups must select at least one observation group: a cost needs columns")
+    swarm.rollout_cost_device(first, h.count, mode, dt, h.steps, h.hold, h.every, h.cptr, h.code, h.cstride, groups, *rows, optr,
+                              bool(accumulate), _stream(h.dev))
+    return out
+
+
+def rollout_ticks(swarm, mode, commands, dt, crash, rebounce, groups=OBS_POS | OBS_VEL | OBS_QUAT, first=0, out=None, hold=1, obs_every=None,
+                  crashed=None):
+    """B * hold ticks of the whole swarm in one call (mrs_swarm_rollout_tick_device): each tick is a step of every UAV, then the
+    collision pass `swarm.handle_collisions(True, crash, rebounce)`.  UAVs [first, first + count) take command row block j before tick
+    j * hold and keep it for `hold` ticks; after every `obs_every` ticks (default: `hold`) the OBS_* groups of `groups` and the crash
+    flags of the range are reported, taken after the tick's step and before its collision pass.  It is the loop `for t: set_input(...);
+    swarm.tick_n(dt, 1, True, crash, rebounce); gather(...); crashed(...)` with the rows taken between the step and the collision pass,
+    bit for bit in LITERAL, with one host wait per call.
+    commands, out: as in rollout.  crashed: a dense torch.bool or torch.uint8 [B * hold // obs_every, count] tensor, allocated (bool) when
+    None; crashed=False asks for no crash rows.  Returns (rows or None when groups == 0, crashed or None).  The collision pass of the last
+    tick stays pending: the next step or tick evaluates it."""
+    h = _rollout_head(swarm, mode, commands, hold, obs_every, "obs_every", "ticks")
+    rows, optr, ostride = _obs_rows(h, groups, out)
+    kptr = 0
+    if crashed is False:
+        crashed = None
+    else:
+        if crashed is None:
+            crashed = torch.empty((h.steps // h.every, h.count), dtype=torch.bool, device=torch.device("cuda", h.dev))
+        _check_crash_rows(crashed, h.steps // h.every, h.count, h.dev)
+        kptr = crashed.data_ptr()
+    swarm.rollout_tick_device(first, h.count, mode, dt, h.steps, h.hold, h.every, h.cptr, h.code, h.cstride, groups, optr, ostride, kptr,
+                              bool(crash), float(rebounce), _stream(h.dev))
+    return rows, crashed
+
+
+def rollout_tick_cost(swarm, mode, commands, dt, crash, rebounce, groups, targets, weights, crash_cost=0.0, first=0, hold=1, cost_every=None,
+                      out=None, accumulate=False):
+    """rollout_ticks(hold=hold, obs_every=cost_every) that returns one FP64 number per UAV instead of row blocks
+    (mrs_swarm_rollout_tick_cost_device): after every `cost_every` ticks (default: `hold`), between the tick's step and its collision
+    pass, the term of rollout_cost (the FP64 row of `groups` against its target row under the weight row) is added to the UAV's cost,
+    and then `crash_cost` if the UAV has crashed — two separately rounded FP64 additions, in that order.  The crash flag is a level: a
+    UAV that crashed early pays at every later evaluation; a crash caused by the last tick's collision pass stays pending with it and is
+    charged by the next horizon.  commands, targets, weights, out, accumulate: as in rollout_cost.  groups == 0 (then targets and
+    weights stay None) is the crash cost alone.  Returns out.  No observation row and no crash byte is written; the collision pass of
+    the last tick stays pending."""
+    h = _rollout_head(swarm, mode, commands, hold, cost_every, "cost_every", "ticks")
+    out, rows, optr = _evaluation(h, groups, targets, weights, out, accumulate, "crash",
+                                  "groups == 0 is the crash cost alone: it takes no targets and no weights")
+    swarm.rollout_tick_cost_device(first, h.count, mode, dt, h.steps, h.hold, h.every, h.cptr, h.code, h.cstride, groups, *rows,
+                                   float(crash_cost), optr, bool(accumulate), bool(crash), float(rebounce), _stream(h.dev))
+    return out
+
+
 def rollout_feedback(swarm, mode, commands, dt, fb_groups, gains, refs, cost_groups=0, targets=None, weights=None, first=0, hold=1,
                      cost_every=None, out=None, accumulate=False):
     """rollout_cost whose commands are NOMINAL commands: at the start of command block b (every `hold` steps) the command of UAV
@@ -420,72 +407,12 @@ def rollout_feedback(swarm, mode, commands, dt, fb_groups, gains, refs, cost_gro
              `g.permute(0, 2, 3, 1).contiguous()`.
     One dtype serves commands, gains, refs, targets and weights.  cost_groups, targets, weights, cost_every, out, accumulate: as in
     rollout_cost; cost_groups == 0 (then targets, weights and out stay None) is a pure closed-loop run and returns None."""
-    dev = swarm.device()
-    if not isinstance(commands, torch.Tensor) or commands.dim() != 3:
-        raise ValueError("commands must be a [T, count, width] tensor")
-    hold = int(hold)
-    if hold < 1:
-        raise ValueError(f"hold must be at least 1, got {hold}")
-    code = _dtype_code(commands.dtype)
-    blocks, count = commands.shape[0], commands.shape[1]
-    steps = blocks * hold
-    every = hold if cost_every is None else int(cost_every)
-    if every < 1 or steps % every != 0:
-        raise ValueError(f"cost_every must be at least 1 and divide the {steps} steps of the call, got {every}")
-    evals = steps // every
-    width = command_width(mode, commands.shape[2])
-    if width < 1:
-        raise ValueError("a feedback rollout needs a mode with a payload")
-    cstride = _check_steps(commands, "commands", None, count, width, commands.dtype, dev)
-    if mode == ACTUATOR_CMD and count > 1 and cstride != commands.shape[2]:
-        raise ValueError("actuator rows must be dense (row stride == number of motors)")
-    wo = gather_width(fb_groups)
-    if wo == 0:
-        raise ValueError("fb_groups must select at least one observation group: a feedback needs columns")
-    for name, t in (("gains", gains), ("refs", refs), ("targets", targets), ("weights", weights)):
-        if isinstance(t, torch.Tensor) and t.dtype != commands.dtype:
-            raise ValueError(f"{name} has dtype {t.dtype}, the commands {commands.dtype}: one dtype serves commands, gains, refs, targets "
-                             "and weights")
-    if not isinstance(gains, torch.Tensor) or gains.dim() not in (3, 4):
-        raise ValueError(f"gains: expected a [Bg, {width}, {wo}] (shared) or [Bg, {width}, {wo}, {count}] (per UAV, UAV-minor) tensor, got "
-                         f"{tuple(gains.shape) if isinstance(gains, torch.Tensor) else type(gains).__name__}")
-    per_uav = gains.dim() == 4
-    want = (width, wo, count) if per_uav else (width, wo)
-    if gains.shape[0] not in (1, blocks) or tuple(gains.shape[1:]) != want:
-        raise ValueError(f"gains: expected a [{blocks} or 1, {', '.join(str(x) for x in want)}] tensor, got {tuple(gains.shape)}")
-    if gains.device.type != "cuda" or gains.device.index != dev:
-        raise ValueError(f"gains is on {gains.device}, the swarm lives on cuda:{dev}")
-    if not gains.is_contiguous():
-        raise ValueError("gains must be dense" + (": [Bg, W_c, W_o, count] with the UAV index last (g.permute(0, 2, 3, 1).contiguous())"
-                                                  if per_uav else ": [Bg, W_c, W_o], row-major"))
-    if not isinstance(refs, torch.Tensor) or refs.dim() != 3 or refs.shape[0] not in (1, blocks):
-        raise ValueError(f"refs: expected a [{blocks} or 1, {count} or 1, >= {wo}] tensor, got "
-                         f"{tuple(refs.shape) if isinstance(refs, torch.Tensor) else type(refs).__name__}")
-    rstride = _row_blocks(refs, "refs", refs.shape[0], count, wo, commands.dtype, dev)
-    tptr = wptr = optr = tstride = wstride = 0
-    if cost_groups == 0:
-        if targets is not None or weights is not None or out is not None or accumulate:
-            raise ValueError("cost_groups == 0 is a run without a cost: targets, weights and out must stay None")
-    else:
-        w = gather_width(cost_groups)
-        tstride = _row_blocks(targets, "targets", evals, count, w, commands.dtype, dev)
-        if not isinstance(weights, torch.Tensor) or weights.dim() != 2 or weights.shape[0] not in (1, evals):
-            raise ValueError(f"weights: expected a [{evals} or 1, >= {w}] tensor, got "
-                             f"{tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights).__name__}")
-        wstride = check_tensor(weights, weights.shape[0], w, commands.dtype, dev)
-        if weights.shape[0] == 1:
-            wstride = 0
-        if out is None:
-            if accumulate:
-                raise ValueError("accumulate=True needs the `out` vector it adds to")
-            out = torch.empty(count, dtype=torch.float64, device=torch.device("cuda", dev))
-        if isinstance(out, torch.Tensor) and out.dtype != torch.float64:
-            raise ValueError(f"out has dtype {out.dtype}: the cost vector is always torch.float64")
-        check_tensor(out, count, None, torch.float64, dev)
-        tptr, wptr, optr = targets.data_ptr(), weights.data_ptr(), out.data_ptr()
-    swarm.rollout_feedback_device(first, count, mode, dt, steps, hold, every, commands.data_ptr() if count > 0 else 0, code, cstride, fb_groups,
-                                  gains.data_ptr(), int(per_uav), gains.shape[0], refs.data_ptr(), rstride, refs.shape[0], cost_groups, tptr,
-                                  tstride, wptr, wstride, optr, bool(accumulate), _stream(dev))
+    h = _rollout_head(swarm, mode, commands, hold, cost_every, "cost_every", "steps", payload=True)
+    fb = _feedback(h, fb_groups, gains, refs, targets, weights)
+    out, rows, optr = _evaluation(h, cost_groups, targets, weights, out, accumulate, "nothing",
+                                  "cost_groups == 0 is a run without a cost: targets, weights and out must stay None")
+    swarm.rollout_feedback_device(first, h.count, mode, dt, h.steps, h.hold, h.every, h.cptr, h.code, h.cstride, fb_groups, *fb, cost_groups,
+                                  *rows, optr, bool(accumulate), _stream(h.dev))
     return out
 
 
@@ -503,77 +430,14 @@ def rollout_tick_feedback(swarm, mode, commands, dt, crash, rebounce, fb_groups,
       cost_groups == 0 with an `out`   the crash cost alone (targets and weights stay None);
       cost_groups == 0, out None       a pure closed-loop run with no evaluation at all: returns None.
     Returns out.  The collision pass of the last tick stays pending."""
-    dev = swarm.device()
-    if not isinstance(commands, torch.Tensor) or commands.dim() != 3:
-        raise ValueError("commands must be a [T, count, width] tensor")
-    hold = int(hold)
-    if hold < 1:
-        raise ValueError(f"hold must be at least 1, got {hold}")
-    code = _dtype_code(commands.dtype)
-    blocks, count = commands.shape[0], commands.shape[1]
-    ticks = blocks * hold
-    every = hold if cost_every is None else int(cost_every)
-    if every < 1 or ticks % every != 0:
-        raise ValueError(f"cost_every must be at least 1 and divide the {ticks} ticks of the call, got {every}")
-    evals = ticks // every
-    width = command_width(mode, commands.shape[2])
-    if width < 1:
-        raise ValueError("a feedback rollout needs a mode with a payload")
-    cstride = _check_steps(commands, "commands", None, count, width, commands.dtype, dev)
-    if mode == ACTUATOR_CMD and count > 1 and cstride != commands.shape[2]:
-        raise ValueError("actuator rows must be dense (row stride == number of motors)")
-    wo = gather_width(fb_groups)
-    if wo == 0:
-        raise ValueError("fb_groups must select at least one observation group: a feedback needs columns")
-    for name, t in (("gains", gains), ("refs", refs), ("targets", targets), ("weights", weights)):
-        if isinstance(t, torch.Tensor) and t.dtype != commands.dtype:
-            raise ValueError(f"{name} has dtype {t.dtype}, the commands {commands.dtype}: one dtype serves commands, gains, refs, targets "
-                             "and weights")
-    if not isinstance(gains, torch.Tensor) or gains.dim() not in (3, 4):
-        raise ValueError(f"gains: expected a [Bg, {width}, {wo}] (shared) or [Bg, {width}, {wo}, {count}] (per UAV, UAV-minor) tensor, got "
-                         f"{tuple(gains.shape) if isinstance(gains, torch.Tensor) else type(gains).__name__}")
-    per_uav = gains.dim() == 4
-    want = (width, wo, count) if per_uav else (width, wo)
-    if gains.shape[0] not in (1, blocks) or tuple(gains.shape[1:]) != want:
-        raise ValueError(f"gains: expected a [{blocks} or 1, {', '.join(str(x) for x in want)}] tensor, got {tuple(gains.shape)}")
-    if gains.device.type != "cuda" or gains.device.index != dev:
-        raise ValueError(f"gains is on {gains.device}, the swarm lives on cuda:{dev}")
-    if not gains.is_contiguous():
-        raise ValueError("gains must be dense" + (": [Bg, W_c, W_o, count] with the UAV index last (g.permute(0, 2, 3, 1).contiguous())"
-                                                  if per_uav else ": [Bg, W_c, W_o], row-major"))
-    if not isinstance(refs, torch.Tensor) or refs.dim() != 3 or refs.shape[0] not in (1, blocks):
-        raise ValueError(f"refs: expected a [{blocks} or 1, {count} or 1, >= {wo}] tensor, got "
-                         f"{tuple(refs.shape) if isinstance(refs, torch.Tensor) else type(refs).__name__}")
-    rstride = _row_blocks(refs, "refs", refs.shape[0], count, wo, commands.dtype, dev)
-    tptr = wptr = optr = tstride = wstride = 0
-    if cost_groups == 0:
-        if targets is not None or weights is not None:
-            raise ValueError("cost_groups == 0 is the crash cost alone (with an `out`) or a run without a cost: it takes no targets and no weights")
-        if out is None and accumulate:
-            raise ValueError("accumulate=True needs the `out` vector it adds to")
-    else:
-        w = gather_width(cost_groups)
-        tstride = _row_blocks(targets, "targets", evals, count, w, commands.dtype, dev)
-        if not isinstance(weights, torch.Tensor) or weights.dim() != 2 or weights.shape[0] not in (1, evals):
-            raise ValueError(f"weights: expected a [{evals} or 1, >= {w}] tensor, got "
-                             f"{tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights).__name__}")
-        wstride = check_tensor(weights, weights.shape[0], w, commands.dtype, dev)
-        if weights.shape[0] == 1:
-            wstride = 0
-        if out is None:
-            if accumulate:
-                raise ValueError("accumulate=True needs the `out` vector it adds to")
-            out = torch.empty(count, dtype=torch.float64, device=torch.device("cuda", dev))
-        tptr, wptr = targets.data_ptr(), weights.data_ptr()
-    if out is not None:
-        if isinstance(out, torch.Tensor) and out.dtype != torch.float64:
-            raise ValueError(f"out has dtype {out.dtype}: the cost vector is always torch.float64")
-        check_tensor(out, count, None, torch.float64, dev)
-        optr = out.data_ptr()
-    swarm.rollout_tick_feedback_device(first, count, mode, dt, ticks, hold, every, commands.data_ptr() if count > 0 else 0, code, cstride,
-                                       fb_groups, gains.data_ptr(), int(per_uav), gains.shape[0], refs.data_ptr(), rstride, refs.shape[0],
-                                       cost_groups, tptr, tstride, wptr, wstride, float(crash_cost), optr, bool(accumulate), bool(crash),
-                                       float(rebounce), _stream(dev))
+    h = _rollout_head(swarm, mode, commands, hold, cost_every, "cost_every", "ticks", payload=True)
+    fb = _feedback(h, fb_groups, gains, refs, targets, weights)
+    out, rows, optr = _evaluation(h, cost_groups, targets, weights, out, accumulate, "either",
+                                  "cost_groups == 0 is the crash cost alone (with an `out`) or a run without a cost: it takes no targets and no "
+                                  "weights")
+    swarm.rollout_tick_feedback_device(first, h.count, mode, dt, h.steps, h.hold, h.every, h.cptr, h.code, h.cstride, fb_groups, *fb,
+                                       cost_groups, *rows, float(crash_cost), optr, bool(accumulate), bool(crash), float(rebounce),
+                                       _stream(h.dev))
     return out
 
 
@@ -652,17 +516,10 @@ def proximity_cost(swarm, radius, k=8, kind=PROX_HINGE2, weight=1.0, eps=0.0, fi
     not capped by k.  Returns (out, found or None).  No simulation state is written; a pending collision tick stays pending."""
     count = _count(swarm, first, count)
     dev = swarm.device()
-    tdev = torch.device("cuda", dev)
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate=True needs the `out` vector it adds to")
-        out = torch.empty(count, dtype=torch.float64, device=tdev)
-    if isinstance(out, torch.Tensor) and out.dtype != torch.float64:
-        raise ValueError(f"out has dtype {out.dtype}: the cost vector is always torch.float64")
-    check_tensor(out, count, None, torch.float64, dev)
+    out = _cost_vector(out, count, accumulate, dev)
     fptr = 0
     if found is True:
-        found = torch.empty(count, dtype=torch.int32, device=tdev)
+        found = torch.empty(count, dtype=torch.int32, device=torch.device("cuda", dev))
     if found is False or found is None:
         found = None
     else:

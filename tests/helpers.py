@@ -1,5 +1,8 @@
 """Shared scenario builders for the parity tests: the same calls are issued to the CPU oracle
-(oracle/oracle_swarm.py — test infrastructure) and to the product (mrs_multirotor_simulator_amd.Swarm)."""
+(oracle/oracle_swarm.py — test infrastructure) and to the product (mrs_multirotor_simulator_amd.Swarm).  Further down, what the
+CPU-side test files share: the prototypes of include/mrs_swarm.h (abi_prototype), CPU tensors dressed as cuda tensors (fake_cuda), a
+swarm whose library calls may not be reached (stand_in), and the rollout kernels as the sources define them (rollout_kernels)."""
+import ctypes as C
 import os
 import re
 
@@ -147,6 +150,64 @@ def assert_close(a, b, rtol, what=""):
     e = rel_linf(a, b)
     assert e <= rtol, f"{what}: relative L-inf error {e:.3e} > {rtol:.1e}"
     return e
+
+
+# the C ABI as include/mrs_swarm.h declares it ----------------------------------------------------------------------------------
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CTYPE = {"mrs_swarm_t*": C.c_void_p, "const void*": C.c_void_p, "void*": C.c_void_p, "int32_t": C.c_int32, "uint32_t": C.c_uint32,
+         "double": C.c_double}
+
+
+def abi_header():
+    """include/mrs_swarm.h without its comments"""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mrs_swarm.h")).read(), flags=re.S)
+
+
+def abi_prototype(name):
+    """(parameter names, C types) of the prototype `int name(...);` in include/mrs_swarm.h, a pointer's star written with its type"""
+    m = re.search(r"int\s+" + name + r"\(([^)]*)\);", abi_header())
+    assert m, f"prototype of {name}"
+    params = [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
+    types = [re.match(r"(.*?)\s*\b\w+$", p).group(1).replace(" *", "*") for p in params]
+    return [p.rsplit(" ", 1)[-1].lstrip("*") for p in params], types
+
+
+# the tensor layer without a GPU ------------------------------------------------------------------------------------------------
+class _Dev:
+    def __init__(self, index):
+        self.type, self.index = "cuda", index
+
+    def __str__(self):
+        return f"cuda:{self.index}"
+
+
+def fake_cuda(monkeypatch):
+    """on(t, index=0): the CPU tensor `t` dressed as a tensor on cuda:index.  Only .device is faked, so nothing can be launched; a
+    tensor made from a dressed one (a slice, a view) says cuda:0."""
+    import torch
+
+    class Fake(torch.Tensor):
+        pass
+
+    def on(t, index=0):
+        f = t.as_subclass(Fake)
+        f._fake_dev = _Dev(index)
+        return f
+
+    monkeypatch.setattr(Fake, "device", property(lambda self: getattr(self, "_fake_dev", _Dev(0))), raising=False)
+    return on
+
+
+def stand_in(*methods):
+    """A class that stands in for a Swarm of 100 UAVs on cuda:0 where no library call may be reached: each of the named methods raises
+    AssertionError("the call reached the library (<name>)"), and a method that is not named does not exist.  A subclass overrides
+    the calls it wants to take."""
+    def refuse(name):
+        def method(self, *a):
+            raise AssertionError(f"the call reached the library ({name})")
+        return method
+
+    return type("StandIn", (), dict({m: refuse(m) for m in methods}, n=100, device=lambda self: 0))
 
 
 # the rollout kernels, as the sources define them -------------------------------------------------------------------------------

@@ -12,9 +12,9 @@ import pytest
 import collision_thresholds as ct
 import collision_worlds as cw
 from collision_threshold_swarms import cluster_preconditions
+from helpers import ROOT, abi_header, fake_cuda
 from test_device_io_gpu import build_cpp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("mrs_swarm_set_worlds", "mrs_swarm_get_worlds", "mrs_swarm_set_worlds_device")
 
 
@@ -113,7 +113,7 @@ def test_restatement_per_world_against_the_reference_kdtree(oracle, name):
 def test_symbols_exported_mirrored_and_declared(mrs):
     from mrs_multirotor_simulator_amd import swarm
     L = C.CDLL(swarm.LIB_PATH)
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mrs_swarm.h")).read(), flags=re.S)
+    header = abi_header()
     for name in SYMBOLS:
         assert hasattr(L, name) and name in swarm.ABI_SYMBOLS, name
         assert len(getattr(mrs.load_library(), name).argtypes) == len(re.search(name + r"\s*\(([^)]*)\)", header).group(1).split(",")), name
@@ -143,40 +143,25 @@ def test_tensors_set_worlds_refuses_bad_tensors(mrs, monkeypatch):
     g = _FakeSwarm()
     with pytest.raises(ValueError, match="is on cpu"):
         T.set_worlds(g, torch.zeros(100, dtype=torch.int32))
-
-    class Dev:
-        def __init__(self, index):
-            self.type, self.index = "cuda", index
-
-        def __str__(self):
-            return f"cuda:{self.index}"
-
-    class Fake(torch.Tensor):
-        pass
-
-    class Other(torch.Tensor):
-        pass
-
-    monkeypatch.setattr(Fake, "device", property(lambda self: Dev(0)), raising=False)
-    monkeypatch.setattr(Other, "device", property(lambda self: Dev(1)), raising=False)
+    on = fake_cuda(monkeypatch)
     monkeypatch.setattr(T, "_stream", lambda dev: 0)
     i32 = torch.int32
     with pytest.raises(ValueError, match="dtype"):
-        T.set_worlds(g, torch.zeros(100, dtype=torch.int64).as_subclass(Fake))
+        T.set_worlds(g, on(torch.zeros(100, dtype=torch.int64)))
     with pytest.raises(ValueError, match="dtype"):
-        T.set_worlds(g, torch.zeros(100).as_subclass(Fake))
+        T.set_worlds(g, on(torch.zeros(100)))
     with pytest.raises(ValueError, match="lives on cuda:0"):
-        T.set_worlds(g, torch.zeros(100, dtype=i32).as_subclass(Other))
+        T.set_worlds(g, on(torch.zeros(100, dtype=i32), 1))
     with pytest.raises(ValueError, match="int32 vector"):
-        T.set_worlds(g, torch.zeros((100, 1), dtype=i32).as_subclass(Fake))
+        T.set_worlds(g, on(torch.zeros((100, 1), dtype=i32)))
     with pytest.raises(ValueError, match="do not fit"):
-        T.set_worlds(g, torch.zeros(101, dtype=i32).as_subclass(Fake))
+        T.set_worlds(g, on(torch.zeros(101, dtype=i32)))
     with pytest.raises(ValueError, match="do not fit"):  # a row too short for the range is a range too long for the row
-        T.set_worlds(g, torch.zeros(60, dtype=i32).as_subclass(Fake), first=41)
+        T.set_worlds(g, on(torch.zeros(60, dtype=i32)), first=41)
     with pytest.raises(ValueError, match="not contiguous"):
-        T.set_worlds(g, torch.zeros(200, dtype=i32)[::2].as_subclass(Fake))
+        T.set_worlds(g, on(torch.zeros(200, dtype=i32)[::2]))
     assert not g.calls
-    w = torch.zeros(60, dtype=i32).as_subclass(Fake)
+    w = on(torch.zeros(60, dtype=i32))
     T.set_worlds(g, w, first=40)
     assert g.calls == [(40, 60, w.data_ptr(), 0)]
 

@@ -7,17 +7,16 @@ import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from helpers import ROOT, abi_header, fake_cuda
+
 NEW_SYMBOLS = ["mrs_swarm_device", "mrs_swarm_gather_width", "mrs_swarm_set_input_device", "mrs_swarm_gather_device",
                "mrs_swarm_get_crashed_device", "mrs_swarm_reset_device"]
 WIDTHS = {"POS": 3, "VEL": 3, "VEL_BODY": 3, "ROT": 9, "QUAT": 4, "OMEGA": 3, "IMU": 3, "RPM": 8}
 
 
 def header_enums():
-    src = open(os.path.join(ROOT, "include", "mrs_swarm.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     vals = {}
-    for name, expr in re.findall(r"\b(MRS_(?:OBS|DTYPE)_[A-Z0-9_]+)\s*=\s*([^,}\n]+)", src):
+    for name, expr in re.findall(r"\b(MRS_(?:OBS|DTYPE)_[A-Z0-9_]+)\s*=\s*([^,}\n]+)", abi_header()):
         vals[name] = eval(expr.strip(), {})  # "1 << 3", "0xFF", "0"
     return vals
 
@@ -67,23 +66,7 @@ def test_check_tensor_rules_past_the_device_check(monkeypatch):
     """The checks behind the device test, on CPU tensors dressed as cuda:0 ones (only .device is faked; nothing is launched)."""
     import torch
     from mrs_multirotor_simulator_amd import tensors
-
-    class Dev:
-        def __init__(self, index):
-            self.type, self.index = "cuda", index
-
-        def __str__(self):
-            return f"cuda:{self.index}"
-
-    class Fake(torch.Tensor):
-        pass
-
-    def on(t, index=0):
-        f = t.as_subclass(Fake)
-        f._fake_dev = Dev(index)
-        return f
-
-    monkeypatch.setattr(Fake, "device", property(lambda self: self._fake_dev), raising=False)
+    on = fake_cuda(monkeypatch)
     f32, f64 = torch.float32, torch.float64
     ok = on(torch.zeros(10, 4))
     assert tensors.check_tensor(ok, 10, 4, f32, 0) == 4

@@ -9,7 +9,8 @@ import re
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from helpers import abi_header, fake_cuda, stand_in
+
 NN_WIDTHS = {"REL_POS": 3, "REL_POS_BODY": 3, "REL_VEL": 3, "REL_VEL_BODY": 3, "DIST": 1}
 
 
@@ -141,9 +142,7 @@ def brute_force(x, first, count, k, radius):
 
 
 def header_enums():
-    src = open(os.path.join(ROOT, "include", "mrs_swarm.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return {name: eval(expr.strip(), {}) for name, expr in re.findall(r"\b(MRS_NN_[A-Z0-9_]+)\s*=\s*([^,}\n]+)", src)}
+    return {name: eval(expr.strip(), {}) for name, expr in re.findall(r"\b(MRS_NN_[A-Z0-9_]+)\s*=\s*([^,}\n]+)", abi_header())}
 
 
 # ---- tests ----
@@ -217,15 +216,7 @@ def test_nearest_width(mrs):
             swarm.nearest_width(swarm.NN_DIST, k)
 
 
-class _FakeSwarm:
-    n = 100
-
-    @staticmethod
-    def device():
-        return 0
-
-    def nearest_device(self, *a):
-        raise AssertionError("the library must not be called")
+_FakeSwarm = stand_in("nearest_device")
 
 
 def test_tensors_nearest_refuses_bad_tensors(mrs, monkeypatch):
@@ -236,21 +227,7 @@ def test_tensors_nearest_refuses_bad_tensors(mrs, monkeypatch):
     with pytest.raises(ValueError, match="is on cpu"):
         T.nearest(g, 4, 5.0, out=torch.zeros(100, 16), index=torch.zeros((100, 4), dtype=torch.int32),
                   counts=torch.zeros(100, dtype=torch.int32))
-
-    class Dev:
-        type, index = "cuda", 0
-
-        def __str__(self):
-            return "cuda:0"
-
-    class Fake(torch.Tensor):
-        pass
-
-    monkeypatch.setattr(Fake, "device", property(lambda self: Dev()), raising=False)
-
-    def on(t):
-        return t.as_subclass(Fake)
-
+    on = fake_cuda(monkeypatch)
     i32 = torch.int32
     rows, idx, cnt = on(torch.zeros(100, 16)), on(torch.zeros((100, 4), dtype=i32)), on(torch.zeros(100, dtype=i32))
     bad = [

@@ -11,8 +11,8 @@ import re
 import numpy as np
 import pytest  # noqa: F401
 
+from helpers import CTYPE, abi_header, abi_prototype, fake_cuda, stand_in
 from test_nearest import nearest_ref
-from test_rollout import CTYPE, ROOT, _Dev
 
 HINGE2, INVERSE, COUNT = 0, 1, 2
 NAMES = ["s", "first", "count", "k", "radius", "kind", "weight", "eps", "dev_cost", "accumulate", "dev_found", "ext_stream"]
@@ -140,10 +140,6 @@ def lattice_set():
     return np.concatenate([lat, np.full((5, 3), 0.25), [[np.nan, 0, 0], [1e12, -3e11, 5.0], [-4.0, 7.0, 1.0]]])
 
 
-def header_text():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mrs_swarm.h")).read(), flags=re.S)
-
-
 # ---- tests ----
 
 def test_restatement_equals_the_definition():
@@ -199,49 +195,29 @@ def test_symbol_is_exported_and_listed(mrs):
 
 def test_header_prototype_equals_the_argtypes(mrs):
     from mrs_multirotor_simulator_amd import swarm
-    m = re.search(r"int\s+mrs_swarm_proximity_cost_device\(([^)]*)\);", header_text())
-    assert m, "prototype"
-    params = [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
-    types = [re.match(r"(.*?)\s*\b\w+$", p).group(1).replace(" *", "*") for p in params]
-    assert [p.rsplit(" ", 1)[-1].lstrip("*") for p in params] == NAMES
+    names, types = abi_prototype("mrs_swarm_proximity_cost_device")
+    assert names == NAMES
     got = swarm.load_library().mrs_swarm_proximity_cost_device.argtypes
     assert [TYPES[t] for t in types] == list(got), (types, got)
 
 
 def test_header_values_equal_the_python_ones(mrs):
     from mrs_multirotor_simulator_amd import swarm, tensors
-    vals = {name: int(v) for name, v in re.findall(r"\b(MRS_PROX_[A-Z0-9_]+)\s*=\s*(\d+)", header_text())}
+    vals = {name: int(v) for name, v in re.findall(r"\b(MRS_PROX_[A-Z0-9_]+)\s*=\s*(\d+)", abi_header())}
     assert vals == {"MRS_PROX_HINGE2": 0, "MRS_PROX_INVERSE": 1, "MRS_PROX_COUNT": 2}
     for name, v in vals.items():
         assert getattr(swarm, name[4:]) == getattr(tensors, name[4:]) == v, name
     assert (HINGE2, INVERSE, COUNT) == (tensors.PROX_HINGE2, tensors.PROX_INVERSE, tensors.PROX_COUNT)
 
 
-class _Swarm:
-    """stands in for a Swarm on cuda:0: the library call may not be reached"""
-    n = 100
-
-    def device(self):
-        return 0
-
-    def proximity_cost_device(self, *a):
-        raise AssertionError("a refused call reached the library (proximity_cost_device)")
+_Swarm = stand_in("proximity_cost_device")
 
 
 def test_proximity_cost_refuses_bad_tensors(monkeypatch):
     """CPU tensors dressed as cuda tensors (only .device is faked; nothing is launched)"""
     import torch
     from mrs_multirotor_simulator_amd import tensors as T
-
-    class Fake(torch.Tensor):
-        pass
-
-    def on(t, index=0):
-        f = t.as_subclass(Fake)
-        f._fake_dev = _Dev(index)
-        return f
-
-    monkeypatch.setattr(Fake, "device", property(lambda self: getattr(self, "_fake_dev", _Dev(0))), raising=False)
+    on = fake_cuda(monkeypatch)
     g, f64, i32 = _Swarm(), torch.float64, torch.int32
     cases = [
         (dict(out=torch.zeros(100, dtype=f64)), "is on cpu"),

@@ -4,16 +4,11 @@ rollout family (helpers.rollout_kernels) has a row in test_rollout_gpu.ROLLOUT_K
 pointer reaches the library."""
 import ctypes as C
 import os
-import re
 
 import pytest
 
 import test_rollout_gpu as R
-from helpers import rollout_kernels
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CTYPE = {"mrs_swarm_t*": C.c_void_p, "const void*": C.c_void_p, "void*": C.c_void_p, "int32_t": C.c_int32, "uint32_t": C.c_uint32,
-         "double": C.c_double}
+from helpers import CTYPE, ROOT, abi_prototype, fake_cuda, rollout_kernels, stand_in
 
 
 def test_symbol_is_exported_and_listed(mrs):
@@ -24,50 +19,21 @@ def test_symbol_is_exported_and_listed(mrs):
 
 def test_header_prototype_equals_the_argtypes(mrs):
     from mrs_multirotor_simulator_amd import swarm
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mrs_swarm.h")).read(), flags=re.S)
-    m = re.search(r"int\s+mrs_swarm_rollout_device\(([^)]*)\);", src)
-    assert m, "prototype"
-    params = [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
-    types = [re.match(r"(.*?)\s*\b\w+$", p).group(1).replace(" *", "*") for p in params]
-    assert [p.rsplit(" ", 1)[-1].lstrip("*") for p in params] == ["s", "first", "count", "mode", "dt", "n_steps", "dev_cmd", "dtype",
-                                                                  "cmd_stride", "groups", "dev_obs", "obs_stride", "ext_stream"]
+    names, types = abi_prototype("mrs_swarm_rollout_device")
+    assert names == ["s", "first", "count", "mode", "dt", "n_steps", "dev_cmd", "dtype", "cmd_stride", "groups", "dev_obs",
+                     "obs_stride", "ext_stream"]
     got = swarm.load_library().mrs_swarm_rollout_device.argtypes
     assert [CTYPE[t] for t in types] == list(got), (types, got)
 
 
-class _Dev:
-    def __init__(self, index):
-        self.type, self.index = "cuda", index
-
-    def __str__(self):
-        return f"cuda:{self.index}"
-
-
-class _Swarm:
-    """stands in for a Swarm on cuda:0: the library must never be reached"""
-    n = 100
-
-    def device(self):
-        return 0
-
-    def rollout_device(self, *a):
-        raise AssertionError("a refused tensor reached the library")
+_Swarm = stand_in("rollout_device")
 
 
 def test_rollout_refuses_bad_tensors(monkeypatch):
     """CPU tensors dressed as cuda tensors (only .device is faked; nothing is launched)"""
     import torch
     from mrs_multirotor_simulator_amd import tensors as T
-
-    class Fake(torch.Tensor):
-        pass
-
-    def on(t, index=0):
-        f = t.as_subclass(Fake)
-        f._fake_dev = _Dev(index)
-        return f
-
-    monkeypatch.setattr(Fake, "device", property(lambda self: getattr(self, "_fake_dev", _Dev(0))), raising=False)
+    on = fake_cuda(monkeypatch)
     g, f64, pos = _Swarm(), torch.float64, T.OBS_POS  # (mode 10: POSITION_CMD)
     out = on(torch.zeros(5, 10, 3, dtype=f64))
     cases = [

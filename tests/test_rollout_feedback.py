@@ -10,16 +10,13 @@ test_rollout_feedback_gpu.FEEDBACK_KERNELS, one per cost kernel, and none of the
 import ctypes as C
 import inspect
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 import test_rollout_feedback_gpu as RF
-from helpers import rollout_kernels
-from test_rollout import CTYPE, ROOT
-from test_rollout_rate import _fakes
+from helpers import CTYPE, ROOT, abi_prototype, fake_cuda, rollout_kernels, stand_in
 
 NAMES = ["s", "first", "count", "mode", "dt", "n_steps", "cmd_every", "cost_every", "dev_cmd", "dtype", "cmd_stride", "fb_groups", "dev_gain",
          "gain_per_uav", "gain_blocks", "dev_ref", "ref_stride", "ref_blocks", "cost_groups", "dev_target", "target_stride", "dev_weight",
@@ -102,12 +99,8 @@ def test_symbol_is_declared_exported_and_listed(mrs):
 
 def test_header_prototype_argtypes_and_method_agree(mrs):
     from mrs_multirotor_simulator_amd import swarm
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mrs_swarm.h")).read(), flags=re.S)
-    m = re.search(r"int\s+mrs_swarm_rollout_feedback_device\(([^)]*)\);", src)
-    assert m, "prototype"
-    params = [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
-    types = [re.match(r"(.*?)\s*\b\w+$", p).group(1).replace(" *", "*") for p in params]
-    assert [p.rsplit(" ", 1)[-1].lstrip("*") for p in params] == NAMES
+    names, types = abi_prototype("mrs_swarm_rollout_feedback_device")
+    assert names == NAMES
     ctype = dict(CTYPE, **{"double*": C.c_void_p})
     got = swarm.load_library().mrs_swarm_rollout_feedback_device.argtypes
     assert [ctype[t] for t in types] == list(got), (types, got)
@@ -127,25 +120,15 @@ def test_width_helpers_refuse_unknown_group_bits(mrs):
     assert [T.command_width(m, 8) for m in range(11)] == [0, 8, 4, 4, 10, 5, 4, 4, 4, 4, 4]
 
 
-class _Swarm:
-    """stands in for a Swarm on cuda:0: a refused call reaches no library call, a well-formed one reaches rollout_feedback_device only"""
-    n = 100
-
-    def device(self):
-        return 0
-
-    def rollout_cost_device(self, *a):
-        raise AssertionError("the call reached the library (rollout_cost_device)")
-
-    def rollout_feedback_device(self, *a):
-        raise AssertionError("the call reached the library (rollout_feedback_device)")
+# a refused call reaches no library call, a well-formed one reaches rollout_feedback_device only
+_Swarm = stand_in("rollout_cost_device", "rollout_feedback_device")
 
 
 def test_rollout_feedback_refuses_before_the_library(monkeypatch):
     """CPU tensors dressed as cuda tensors (only .device is faked; nothing is launched)"""
     import torch
     from mrs_multirotor_simulator_amd import tensors as T
-    on = _fakes(monkeypatch)
+    on = fake_cuda(monkeypatch)
     g, f64, f32 = _Swarm(), torch.float64, torch.float32
     fb, pos = T.OBS_POS | T.OBS_OMEGA, T.OBS_POS  # W_o = 6; cost columns: 3; mode 10 (POSITION_CMD): W_c = 4
 
@@ -206,7 +189,7 @@ def test_rollout_feedback_refuses_before_the_library(monkeypatch):
 def test_strides_handed_to_the_library(monkeypatch):
     import torch
     from mrs_multirotor_simulator_amd import tensors as T
-    on = _fakes(monkeypatch)
+    on = fake_cuda(monkeypatch)
     monkeypatch.setattr(T, "_stream", lambda dev: 0)
     seen = []
 

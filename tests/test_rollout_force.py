@@ -8,16 +8,13 @@ The forces have kernels of their own (the _force family of helpers.rollout_kerne
 test_rollout_force_gpu.ROLLOUT_FORCE_KERNELS and a rate counterpart, and the tables of the step, plain and rate kernels stay as they are."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import pytest
 
 import test_rollout_force_gpu as RF
-from helpers import rollout_kernels
-from test_rollout import CTYPE, ROOT
+from helpers import CTYPE, ROOT, abi_prototype, fake_cuda, rollout_kernels, stand_in
 from test_rollout_rate import NAMES as RATE_NAMES
-from test_rollout_rate import _fakes
 
 # the rate call with force_every behind obs_every and dev_force, force_stride behind cmd_stride
 NAMES = RATE_NAMES[:8] + ["force_every"] + RATE_NAMES[8:11] + ["dev_force", "force_stride"] + RATE_NAMES[11:]
@@ -25,12 +22,8 @@ APPLY_NAMES = ["s", "first", "count", "dev_force", "dtype", "stride", "ext_strea
 
 
 def _prototype(name):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mrs_swarm.h")).read(), flags=re.S)
-    m = re.search(r"int\s+" + name + r"\(([^)]*)\);", src)
-    assert m, f"prototype of {name}"
-    params = [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
-    types = [re.match(r"(.*?)\s*\b\w+$", p).group(1).replace(" *", "*") for p in params]
-    return [p.rsplit(" ", 1)[-1].lstrip("*") for p in params], [CTYPE[t] for t in types]
+    names, types = abi_prototype(name)
+    return names, [CTYPE[t] for t in types]
 
 
 def test_symbols_are_exported_and_listed(mrs):
@@ -60,31 +53,14 @@ def test_header_prototypes_equal_the_argtypes(mrs):
     assert list(inspect.signature(swarm.Swarm.apply_force_device).parameters)[1:] == APPLY_NAMES[1:]
 
 
-class _Swarm:
-    """stands in for a Swarm on cuda:0: no call of the library may be reached"""
-    n = 100
-
-    def device(self):
-        return 0
-
-    def rollout_device(self, *a):
-        raise AssertionError("a refused call reached the library (rollout_device)")
-
-    def rollout_rate_device(self, *a):
-        raise AssertionError("a refused call reached the library (rollout_rate_device)")
-
-    def rollout_force_device(self, *a):
-        raise AssertionError("a refused call reached the library (rollout_force_device)")
-
-    def apply_force_device(self, *a):
-        raise AssertionError("a refused call reached the library (apply_force_device)")
+_Swarm = stand_in("rollout_device", "rollout_rate_device", "rollout_force_device", "apply_force_device")
 
 
 def test_rollout_refuses_bad_forces(monkeypatch):
     """CPU tensors dressed as cuda tensors (only .device is faked; nothing is launched)"""
     import torch
     from mrs_multirotor_simulator_amd import tensors as T
-    on = _fakes(monkeypatch)
+    on = fake_cuda(monkeypatch)
     g, f64, pos = _Swarm(), torch.float64, T.OBS_POS  # (mode 10: POSITION_CMD)
     cmd = on(torch.zeros(5, 10, 4, dtype=f64))  # B = 5, hold = 2: 10 steps
     out = on(torch.zeros(5, 10, 3, dtype=f64))
@@ -132,7 +108,7 @@ def test_rollout_refuses_bad_forces(monkeypatch):
         with pytest.raises(AssertionError, match=r"\(rollout_force_device\)"):
             T.rollout(g, 10, cmd, 0.001, pos, out=on(torch.zeros(blocks, 10, 3, dtype=f64)), forces=forces, **kw)
     # without forces the function takes the paths it took: a stand-in without any force method is never asked for one
-    from test_rollout_rate import _Swarm as RateSwarm
+    RateSwarm = stand_in("rollout_device", "rollout_rate_device")
     with pytest.raises(AssertionError, match="rollout_rate_device"):
         T.rollout(RateSwarm(), 10, cmd, 0.001, pos, out=out, hold=2)
     with pytest.raises(AssertionError, match=r"\(rollout_device\)"):
@@ -142,7 +118,7 @@ def test_rollout_refuses_bad_forces(monkeypatch):
 def test_apply_force_refuses_bad_tensors(monkeypatch):
     import torch
     from mrs_multirotor_simulator_amd import tensors as T
-    on = _fakes(monkeypatch)
+    on = fake_cuda(monkeypatch)
     g, f64 = _Swarm(), torch.float64
     cases = [
         (torch.zeros(10, 3, dtype=f64), "is on cpu"),

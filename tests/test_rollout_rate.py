@@ -10,14 +10,12 @@ The per-launch schedule (swarm_layout.h: mrs_ro_launch_sched, mrs_ro_due, mrs_ro
 tests/cpp/rollout_sched_test.cpp, on the host."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import pytest
 
 import test_rollout_rate_gpu as RR
-from helpers import CSRC, rollout_kernels
-from test_rollout import CTYPE, ROOT, _Dev
+from helpers import CSRC, CTYPE, ROOT, abi_prototype, fake_cuda, rollout_kernels, stand_in
 
 NAMES = ["s", "first", "count", "mode", "dt", "n_steps", "cmd_every", "obs_every", "dev_cmd", "dtype", "cmd_stride", "groups", "dev_obs",
          "obs_stride", "ext_stream"]
@@ -32,12 +30,8 @@ def test_symbol_is_exported_and_listed(mrs):
 
 def test_header_prototype_equals_the_argtypes(mrs):
     from mrs_multirotor_simulator_amd import swarm
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mrs_swarm.h")).read(), flags=re.S)
-    m = re.search(r"int\s+mrs_swarm_rollout_rate_device\(([^)]*)\);", src)
-    assert m, "prototype"
-    params = [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
-    types = [re.match(r"(.*?)\s*\b\w+$", p).group(1).replace(" *", "*") for p in params]
-    assert [p.rsplit(" ", 1)[-1].lstrip("*") for p in params] == NAMES
+    names, types = abi_prototype("mrs_swarm_rollout_rate_device")
+    assert names == NAMES
     got = swarm.load_library().mrs_swarm_rollout_rate_device.argtypes
     assert [CTYPE[t] for t in types] == list(got), (types, got)
     # the plain call keeps its prototype: the new one is it with the two rates behind n_steps
@@ -45,40 +39,14 @@ def test_header_prototype_equals_the_argtypes(mrs):
     assert list(got[:6]) + list(got[8:]) == list(plain) and list(got[6:8]) == [C.c_int32, C.c_int32]
 
 
-class _Swarm:
-    """stands in for a Swarm on cuda:0: neither rollout call of the library may be reached"""
-    n = 100
-
-    def device(self):
-        return 0
-
-    def rollout_device(self, *a):
-        raise AssertionError("a refused call reached the library (rollout_device)")
-
-    def rollout_rate_device(self, *a):
-        raise AssertionError("a refused call reached the library (rollout_rate_device)")
-
-
-def _fakes(monkeypatch):
-    import torch
-
-    class Fake(torch.Tensor):
-        pass
-
-    def on(t, index=0):
-        f = t.as_subclass(Fake)
-        f._fake_dev = _Dev(index)
-        return f
-
-    monkeypatch.setattr(Fake, "device", property(lambda self: getattr(self, "_fake_dev", _Dev(0))), raising=False)
-    return on
+_Swarm = stand_in("rollout_device", "rollout_rate_device")  # neither rollout call of the library may be reached
 
 
 def test_rollout_refuses_bad_rates(monkeypatch):
     """CPU tensors dressed as cuda tensors (only .device is faked; nothing is launched)"""
     import torch
     from mrs_multirotor_simulator_amd import tensors as T
-    on = _fakes(monkeypatch)
+    on = fake_cuda(monkeypatch)
     g, f64, pos = _Swarm(), torch.float64, T.OBS_POS  # (mode 10: POSITION_CMD)
     cmd = on(torch.zeros(5, 10, 4, dtype=f64))  # B = 5
 
@@ -118,7 +86,7 @@ def test_rollout_refuses_bad_tensors_at_a_hold(monkeypatch):
     """the list of test_rollout.test_rollout_refuses_bad_tensors, at hold = 3 (obs_every = hold: `out` keeps its B row blocks)"""
     import torch
     from mrs_multirotor_simulator_amd import tensors as T
-    on = _fakes(monkeypatch)
+    on = fake_cuda(monkeypatch)
     g, f64, pos = _Swarm(), torch.float64, T.OBS_POS
     out = on(torch.zeros(5, 10, 3, dtype=f64))
     cases = [

@@ -14,8 +14,7 @@ import subprocess
 import pytest
 
 import test_rollout_tick_gpu as RT
-from helpers import CSRC, macro_lines, rollout_kernels
-from test_rollout import CTYPE, ROOT, _Dev
+from helpers import CSRC, CTYPE, ROOT, abi_prototype, fake_cuda, macro_lines, rollout_kernels, stand_in
 
 NAMES = ["s", "first", "count", "mode", "dt", "n_ticks", "cmd_every", "obs_every", "dev_cmd", "dtype", "cmd_stride", "groups", "dev_obs",
          "obs_stride", "dev_crashed", "crash", "rebounce", "ext_stream"]
@@ -39,12 +38,8 @@ def test_symbol_is_exported_and_listed(mrs):
 
 def test_header_prototype_equals_the_argtypes(mrs):
     from mrs_multirotor_simulator_amd import swarm
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mrs_swarm.h")).read(), flags=re.S)
-    m = re.search(r"int\s+mrs_swarm_rollout_tick_device\(([^)]*)\);", src)
-    assert m, "prototype"
-    params = [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
-    types = [re.match(r"(.*?)\s*\b\w+$", p).group(1).replace(" *", "*") for p in params]
-    assert [p.rsplit(" ", 1)[-1].lstrip("*") for p in params] == NAMES
+    names, types = abi_prototype("mrs_swarm_rollout_tick_device")
+    assert names == NAMES
     got = swarm.load_library().mrs_swarm_rollout_tick_device.argtypes
     assert [TYPES[t] for t in types] == list(got), (types, got)
     # the control-rate call with the crash rows and the collision arguments between obs_stride and the stream
@@ -79,37 +74,14 @@ def test_no_other_kernel_lines_in_the_file():
     assert "mrs_ro_sched" not in text and "MRS_RO_" not in text and "mrs_ro_" not in text, "one launch is one tick: no schedule words"
 
 
-class _Swarm:
-    """stands in for a Swarm on cuda:0: the library call may not be reached"""
-    n = 100
-
-    def device(self):
-        return 0
-
-    def rollout_tick_device(self, *a):
-        raise AssertionError("a refused call reached the library (rollout_tick_device)")
-
-
-def _fakes(monkeypatch):
-    import torch
-
-    class Fake(torch.Tensor):
-        pass
-
-    def on(t, index=0):
-        f = t.as_subclass(Fake)
-        f._fake_dev = _Dev(index)
-        return f
-
-    monkeypatch.setattr(Fake, "device", property(lambda self: getattr(self, "_fake_dev", _Dev(0))), raising=False)
-    return on
+_Swarm = stand_in("rollout_tick_device")
 
 
 def test_rollout_ticks_refuses_bad_tensors(monkeypatch):
     """CPU tensors dressed as cuda tensors (only .device is faked; nothing is launched)"""
     import torch
     from mrs_multirotor_simulator_amd import tensors as T
-    on = _fakes(monkeypatch)
+    on = fake_cuda(monkeypatch)
     g, f64, pos = _Swarm(), torch.float64, T.OBS_POS  # (mode 10: POSITION_CMD)
 
     def cmd(**kw):

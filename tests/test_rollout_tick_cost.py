@@ -16,9 +16,7 @@ import numpy as np
 import pytest
 
 import test_rollout_tick_cost_gpu as RTC
-from helpers import CSRC, STEP_UNITS, macro_lines, rollout_kernels
-from test_rollout import CTYPE, ROOT
-from test_rollout_tick import _fakes
+from helpers import CSRC, CTYPE, ROOT, STEP_UNITS, abi_prototype, fake_cuda, macro_lines, rollout_kernels, stand_in
 
 FILE = "rollout_tick_device.inc"  # the tick families share one file; this one is MRS_ROLLOUT_TICK_FAMILY(_cost, ...)
 NAMES = ["s", "first", "count", "mode", "dt", "n_ticks", "cmd_every", "cost_every", "dev_cmd", "dtype", "cmd_stride", "groups", "dev_target",
@@ -43,12 +41,8 @@ def test_symbol_is_exported_and_listed(mrs):
 def test_header_prototype_argtypes_and_method_agree(mrs):
     from mrs_multirotor_simulator_amd import swarm
     text = open(os.path.join(ROOT, "include", "mrs_swarm.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"int\s+mrs_swarm_rollout_tick_cost_device\(([^)]*)\);", src)
-    assert m, "prototype"
-    params = [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
-    types = [re.match(r"(.*?)\s*\b\w+$", p).group(1).replace(" *", "*") for p in params]
-    assert [p.rsplit(" ", 1)[-1].lstrip("*") for p in params] == NAMES
+    names, types = abi_prototype("mrs_swarm_rollout_tick_cost_device")
+    assert names == NAMES
     ctype = dict(CTYPE, **{"double*": C.c_void_p})
     got = swarm.load_library().mrs_swarm_rollout_tick_cost_device.argtypes
     assert [ctype[t] for t in types] == list(got), (types, got)
@@ -108,28 +102,14 @@ def test_no_other_kernel_lines_in_the_file():
     assert "sched" not in body and "crash_cost" in body
 
 
-class _Swarm:
-    """stands in for a Swarm on cuda:0: the library call may not be reached"""
-    n = 100
-
-    def device(self):
-        return 0
-
-    def rollout_tick_device(self, *a):
-        raise AssertionError("the call reached the library (rollout_tick_device)")
-
-    def rollout_cost_device(self, *a):
-        raise AssertionError("the call reached the library (rollout_cost_device)")
-
-    def rollout_tick_cost_device(self, *a):
-        raise AssertionError("the call reached the library (rollout_tick_cost_device)")
+_Swarm = stand_in("rollout_tick_device", "rollout_cost_device", "rollout_tick_cost_device")
 
 
 def test_rollout_tick_cost_refuses_bad_tensors(monkeypatch):
     """CPU tensors dressed as cuda tensors (only .device is faked; nothing is launched)"""
     import torch
     from mrs_multirotor_simulator_amd import tensors as T
-    on = _fakes(monkeypatch)
+    on = fake_cuda(monkeypatch)
     g, f64, f32, pos = _Swarm(), torch.float64, torch.float32, T.OBS_POS  # (mode 10: POSITION_CMD; OBS_POS: w = 3)
 
     def z(*shape, dtype=f64, dev=0):
@@ -204,7 +184,7 @@ def test_arguments_handed_to_the_library(monkeypatch):
     """shared targets travel as target_stride 0, a single weight row as weight_stride 0, the crash-only form as null pointers"""
     import torch
     from mrs_multirotor_simulator_amd import tensors as T
-    on = _fakes(monkeypatch)
+    on = fake_cuda(monkeypatch)
     monkeypatch.setattr(T, "_stream", lambda dev: 0)
     seen = []
 

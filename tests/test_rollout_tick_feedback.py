@@ -16,9 +16,7 @@ import subprocess
 import pytest
 
 import test_rollout_tick_feedback_gpu as RTF
-from helpers import CSRC, STEP_UNITS, macro_lines, rollout_kernels
-from test_rollout import CTYPE, ROOT
-from test_rollout_tick import _fakes
+from helpers import CSRC, CTYPE, ROOT, STEP_UNITS, abi_prototype, fake_cuda, macro_lines, rollout_kernels, stand_in
 
 FILE = "rollout_tick_device.inc"  # the tick families share one file; this one is MRS_ROLLOUT_TICK_FAMILY(_feedback, ...)
 NAMES = ["s", "first", "count", "mode", "dt", "n_ticks", "cmd_every", "cost_every", "dev_cmd", "dtype", "cmd_stride",
@@ -47,12 +45,8 @@ def test_symbol_is_exported_and_listed(mrs):
 def test_header_prototype_argtypes_and_method_agree(mrs):
     from mrs_multirotor_simulator_amd import swarm, tensors
     text = open(os.path.join(ROOT, "include", "mrs_swarm.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"int\s+mrs_swarm_rollout_tick_feedback_device\(([^)]*)\);", src)
-    assert m, "prototype"
-    params = [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
-    types = [re.match(r"(.*?)\s*\b\w+$", p).group(1).replace(" *", "*") for p in params]
-    assert [p.rsplit(" ", 1)[-1].lstrip("*") for p in params] == NAMES
+    names, types = abi_prototype("mrs_swarm_rollout_tick_feedback_device")
+    assert names == NAMES
     ctype = dict(CTYPE, **{"double*": C.c_void_p})
     lib = swarm.load_library()
     got = list(lib.mrs_swarm_rollout_tick_feedback_device.argtypes)
@@ -133,21 +127,7 @@ def test_no_other_kernel_lines_in_the_file():
         assert open(os.path.join(CSRC, other)).read().count("static constexpr bool kOnCollKernels = false;") == 1, other
 
 
-class _Swarm:
-    """stands in for a Swarm on cuda:0: the library call may not be reached"""
-    n = 100
-
-    def device(self):
-        return 0
-
-    def rollout_feedback_device(self, *a):
-        raise AssertionError("the call reached the library (rollout_feedback_device)")
-
-    def rollout_tick_cost_device(self, *a):
-        raise AssertionError("the call reached the library (rollout_tick_cost_device)")
-
-    def rollout_tick_feedback_device(self, *a):
-        raise AssertionError("the call reached the library (rollout_tick_feedback_device)")
+_Swarm = stand_in("rollout_feedback_device", "rollout_tick_cost_device", "rollout_tick_feedback_device")
 
 
 def test_rollout_tick_feedback_refuses_bad_tensors(monkeypatch):
@@ -155,7 +135,7 @@ def test_rollout_tick_feedback_refuses_bad_tensors(monkeypatch):
     rollout_tick_cost"""
     import torch
     from mrs_multirotor_simulator_amd import tensors as T
-    on = _fakes(monkeypatch)
+    on = fake_cuda(monkeypatch)
     g, f64, f32 = _Swarm(), torch.float64, torch.float32
     fb, pos = T.OBS_POS | T.OBS_OMEGA, T.OBS_POS  # W_o = 6; cost columns: 3; mode 10 (POSITION_CMD): W_c = 4
 
@@ -256,7 +236,7 @@ def test_arguments_handed_to_the_library(monkeypatch):
     pointers and the pure closed-loop run a null cost pointer too, and returns None"""
     import torch
     from mrs_multirotor_simulator_amd import tensors as T
-    on = _fakes(monkeypatch)
+    on = fake_cuda(monkeypatch)
     monkeypatch.setattr(T, "_stream", lambda dev: 0)
     seen = []
 

@@ -9,13 +9,13 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from helpers import ROOT, abi_header, fake_cuda, stand_in
+
 NEW_SYMBOLS = ["mrs_swarm_save_device", "mrs_swarm_load_device"]
 
 
 def header_values():
-    src = open(os.path.join(ROOT, "include", "mrs_swarm.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = abi_header()
     vals = {name: eval(expr.strip(), {}) for name, expr in re.findall(r"\b(MRS_SNAP_[A-Z_]+)\s*=\s*([^,}\n]+)", src)}
     m = re.search(r"#define\s+MRS_SNAP_MAGIC\s+(0x[0-9A-Fa-f]+)u", src)
     vals["MRS_SNAP_MAGIC"] = int(m.group(1), 16)
@@ -87,43 +87,13 @@ def test_snapshot_fields_share_memory():
         tensors.snapshot_fields(torch.zeros((5, 2 * tensors.SNAP_BYTES), dtype=torch.uint8)[:, :tensors.SNAP_BYTES])
 
 
-class _Dev:
-    def __init__(self, index):
-        self.type, self.index = "cuda", index
-
-    def __str__(self):
-        return f"cuda:{self.index}"
-
-
-class _NoSwarm:
-    """a stand-in that fails the test if any check lets a call through to the library"""
-    n = 100
-
-    def device(self):
-        return 0
-
-    def save_device(self, *a):
-        raise AssertionError("reached the library")
-
-    load_device = save_device
+_NoSwarm = stand_in("save_device", "load_device")  # fails the test if any check lets a call through to the library
 
 
 @pytest.fixture
 def on(monkeypatch):
     """CPU tensors dressed as cuda:<index> ones (only .device is faked; nothing is launched), as test_device_io does"""
-    import torch
-
-    class Fake(torch.Tensor):
-        pass
-
-    monkeypatch.setattr(Fake, "device", property(lambda self: self._fake_dev), raising=False)
-
-    def dress(t, index=0):
-        f = t.as_subclass(Fake)
-        f._fake_dev = _Dev(index)
-        return f
-
-    return dress
+    return fake_cuda(monkeypatch)
 
 
 def test_save_and_load_refuse_bad_tensors(on):

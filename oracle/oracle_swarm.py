@@ -113,6 +113,8 @@ def lib():
         L.orc_swarm_step.argtypes = [C.c_void_p, C.c_double]
         L.orc_swarm_step_n.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_int32]
         L.orc_swarm_handle_collisions.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_double]
+        L.orc_swarm_set_worlds.argtypes = [C.c_void_p, C.c_int32, C.c_int32, ip]
+        L.orc_swarm_get_worlds.argtypes = [C.c_void_p, C.c_int32, C.c_int32, ip]
         L.orc_swarm_apply_force.argtypes = [C.c_void_p, C.c_int32, C.c_int32, dp]
         L.orc_swarm_crash.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         L.orc_swarm_set_hold.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
@@ -222,6 +224,16 @@ class OracleSwarm:
 
     def handle_collisions(self, enabled, crash, rebounce):
         lib().orc_swarm_handle_collisions(self._h, int(enabled), int(crash), float(rebounce))
+
+    def set_worlds(self, worlds, first=0):
+        w = np.ascontiguousarray(worlds, dtype=np.int32).reshape(-1)
+        lib().orc_swarm_set_worlds(self._h, int(first), int(w.size), w.ctypes.data_as(C.POINTER(C.c_int32)))
+
+    def get_worlds(self, first=0, count=None):
+        count = self.n - first if count is None else int(count)
+        out = np.zeros(max(count, 0), dtype=np.int32)
+        lib().orc_swarm_get_worlds(self._h, int(first), int(count), out.ctypes.data_as(C.POINTER(C.c_int32)))
+        return out
 
     def apply_force(self, first, count, force):
         force = _arr(force, (count, 3))

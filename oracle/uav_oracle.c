@@ -252,6 +252,7 @@ struct orc_swarm {
   int32_t    n;
   uav_t*     u;
   orc_diag_t diag;
+  int32_t*   world; /* collision-world label per slot (include/mrs_swarm.h, "collision worlds"); NULL until a setter is called */
 };
 
 /* ------------------------------------------------------------------ */
@@ -1025,6 +1026,7 @@ orc_swarm_t* orc_swarm_create(int32_t n) {
 
 void orc_swarm_destroy(orc_swarm_t* s) {
   if (!s) return;
+  free(s->world);
   free(s->u);
   free(s);
 }
@@ -1239,6 +1241,14 @@ void orc_swarm_handle_collisions(orc_swarm_t* s, int32_t enabled, int32_t crash,
   }
   double* forces = (double*)calloc((size_t)n * 3, sizeof(double)); /* :315-319 */
   int*    cand   = (int*)malloc(sizeof(int) * (size_t)n);
+  /* collision worlds: a candidate of another label is skipped.  Decided once per call: a swarm that holds one label (every swarm
+   * whose labels were never set) runs the loop without the comparison */
+  const int32_t* world = s->world;
+  if (world) {
+    int one = 1;
+    for (int i = 1; i < n && one; i++) one = world[i] == world[0];
+    if (one) world = NULL;
+  }
 
   for (int i = 0; i < n; i++) { /* :321 */
     const uav_t* u1 = &s->u[i];
@@ -1262,6 +1272,12 @@ void orc_swarm_handle_collisions(orc_swarm_t* s, int32_t enabled, int32_t crash,
       qsort(cand, (size_t)nc, sizeof(int), int_cmp); /* deterministic accumulation order: ascending index */
     } else {
       for (int j = 0; j < n; j++) cand[nc++] = j;
+    }
+    if (world) { /* same-world candidates only, still in ascending index; the loop below is what it was */
+      int m = 0;
+      for (int c = 0; c < nc; c++)
+        if (world[cand[c]] == world[i]) cand[m++] = cand[c];
+      nc = m;
     }
     for (int c = 0; c < nc; c++) {
       const int    idx = cand[c];
@@ -1291,6 +1307,16 @@ void orc_swarm_handle_collisions(orc_swarm_t* s, int32_t enabled, int32_t crash,
   free(cand);
   free(forces);
   free(ent);
+}
+
+/* collision worlds: the label belongs to the slot (construct / set_state leave it alone); 0 until set */
+void orc_swarm_set_worlds(orc_swarm_t* s, int32_t first, int32_t count, const int32_t* worlds) {
+  if (count <= 0) return;
+  if (!s->world) s->world = (int32_t*)calloc((size_t)(s->n > 0 ? s->n : 1), sizeof(int32_t));
+  memcpy(s->world + first, worlds, sizeof(int32_t) * (size_t)count);
+}
+void orc_swarm_get_worlds(const orc_swarm_t* s, int32_t first, int32_t count, int32_t* out) {
+  for (int k = 0; k < count; k++) out[k] = s->world ? s->world[first + k] : 0;
 }
 
 /* ------------------------------------------------------------------ */

@@ -132,6 +132,11 @@ void orc_swarm_step_n(orc_swarm_t* s, double dt, int32_t n_steps, int32_t n_thre
 /* MultirotorSimulator::handleCollisions, src/multirotor_simulator.cpp:295-359.
  * Neighbour search restated as an exhaustive scan accelerated by a uniform grid; pair predicate literal. */
 void orc_swarm_handle_collisions(orc_swarm_t* s, int32_t enabled, int32_t crash, double rebounce);
+/* collision worlds (include/mrs_swarm.h): an int32 label per slot, 0 until set; handle_collisions skips a candidate whose label differs
+ * from the query UAV's, so that the result is that of one swarm per label holding the label's UAVs in ascending index.  The label
+ * belongs to the slot: construct and set_state leave it alone. */
+void orc_swarm_set_worlds(orc_swarm_t* s, int32_t first, int32_t count, const int32_t* worlds);
+void orc_swarm_get_worlds(const orc_swarm_t* s, int32_t first, int32_t count, int32_t* out);
 
 void orc_swarm_apply_force(orc_swarm_t* s, int32_t first, int32_t count, const double* force);  /* uav_system.hpp:295 */
 void orc_swarm_set_hold(orc_swarm_t* s, int32_t first, int32_t count, int32_t hold);              /* src/uav_system_ros.cpp:265 */

@@ -8,7 +8,17 @@ tuple against the header's rules and records it: the generator draws the same nu
 for the GPU test's sequences.
 
 Steps are budgeted: a sequence never takes more than `cap` steps (rollout steps included), because the tolerances of the compare were
-set for the step totals of test_random_sequences_gpu.py; a stepping call that no longer fits is drawn shorter or becomes a gather."""
+set for the step totals of test_random_sequences_gpu.py; a stepping call that no longer fits is drawn shorter or becomes a gather.
+
+Two surfaces.  SEEDS and VARIANTS draw from the 33 kinds above and draw what they always drew.  SEEDS_EXT and VARIANTS_EXT
+(run_sequence(surface="ext")) draw from 39: tensors.rollout_ticks, rollout_tick_cost, rollout_feedback, rollout_tick_feedback and
+proximity_cost, and, in the seeds that carry the `worlds` flag, collision-world labels set in the middle of the run (the whole swarm is
+labelled i % 3 before the first call, so that every collision pass, list tick, fused launch, nearest() and rollout of the sequence runs
+the world-aware kernels).  Ticks of a tick rollout count as steps.  SEEDS_EXT holds 20 seeds, 8 of them with worlds; the largest takes 76
+steps, and over all of them there are 27 rollout_ticks, 27 rollout_tick_cost, 25 rollout_feedback, 35 rollout_tick_feedback, 49
+proximity_cost and 13 set_worlds calls (counted by test_random_device_sequences.py).  Two conditions keep the comparison of these seeds honest, and the
+CPU dry run asserts both, so they are properties of the chosen seeds (contact_violations; near_quat_branch at the block starts of a
+feedback on the quaternion)."""
 import contextlib
 from collections import Counter
 
@@ -19,8 +29,11 @@ from helpers import FIELD_FLOOR, Pair
 from oracle import oracle_swarm as O
 from test_device_io_gpu import _runs
 from test_nearest_gpu import compare_with_numpy
+from test_proximity_cost import add_bits, proximity_ref, same_bits
 from test_random_sequences_gpu import DT, build_fleet, check, compare_outputs, host_op, payload, rng_range
 from test_rollout_cost_gpu import restate
+from test_rollout_feedback_gpu import restate_feedback
+from test_rollout_tick_cost_gpu import restate_ticks
 
 N_UAVS = 150
 N_ITER = 50        # calls of a sequence
@@ -46,8 +59,19 @@ OP_NAMES = {**{k: f"host{k}" for k in range(18)}, DEV_SET_INPUT: "dev_set_input"
             TICK_LONG: "tick_long", MODEL_ALL: "model_all"}
 ROLLOUTS = (ROLL_PLAIN, ROLL_RATE, ROLL_FORCE, ROLL_COST)
 STALL_FOLLOWERS = (ASYNC_OUTPUTS, ASYNC_POSES, GATHER, NEAREST, DEV_SET_INPUT)
+# the kinds of the extended surface (drawn by SEEDS_EXT and VARIANTS_EXT only; SET_WORLDS only in their seeds with the `worlds` flag)
+ROLL_TICK, ROLL_TICK_COST, ROLL_FEEDBACK, ROLL_TICK_FEEDBACK, PROXIMITY, SET_WORLDS = range(35, 41)
+EXT_KINDS = (ROLL_TICK, ROLL_TICK_COST, ROLL_FEEDBACK, ROLL_TICK_FEEDBACK, PROXIMITY, SET_WORLDS)
+OP_NAMES.update({ROLL_TICK: "rollout_ticks", ROLL_TICK_COST: "rollout_tick_cost", ROLL_FEEDBACK: "rollout_feedback",
+                 ROLL_TICK_FEEDBACK: "rollout_tick_feedback", PROXIMITY: "proximity_cost", SET_WORLDS: "set_worlds"})
+TICK_ROLLOUTS = (ROLL_TICK, ROLL_TICK_COST, ROLL_TICK_FEEDBACK)
+ROLLOUTS_EXT = ROLLOUTS + (ROLL_TICK, ROLL_TICK_COST, ROLL_FEEDBACK, ROLL_TICK_FEEDBACK)
+STALL_ROLLOUTS = (ROLL_TICK_COST, ROLL_TICK_FEEDBACK)  # what the FAST_UAVS recipe forces in place of TICK_LONG, half of the time
+STALL_HORIZONS = (5, 12)                               # ... of at least four ticks
+WORLD_LABELS = (0, 7, -2000000000, 1234567890)
+OBS_POS = 1
 # calls that enter through MRS_ENTER_COMMANDS (or do not enter at all): a collision tick that is pending stays pending across them
-KEEP_PENDING = (0, 1, 2, 3, 9, 15, DEV_SET_INPUT, GATHER, ASYNC_OUTPUTS, ASYNC_POSES)
+KEEP_PENDING = (0, 1, 2, 3, 9, 15, DEV_SET_INPUT, GATHER, ASYNC_OUTPUTS, ASYNC_POSES, PROXIMITY)
 
 
 def gather_width(groups):
@@ -120,6 +144,26 @@ def cost_bound(rows, targets, weights, groups, rtol):
         return (np.abs(wt) * (2.0 * d * delta + delta * delta)).sum(axis=(0, 2))
 
 
+def contact_violations(o, rtol):
+    """the same-world pairs of the oracle swarm `o` that a collision pass could decide the other way within the compare's tolerance.
+    Crash rows, crash costs and rebounce forces jump where a pair's squared distance d2 crosses its contact threshold crit.  Positions
+    that agree within delta = rtol * max(|x|_inf, FIELD_FLOOR["x"]) per UAV move d2 by at most 2 d (delta_i + delta_j) to first order;
+    a pair counts unless |d2 - crit| is at least twice that (the 2 is margin over the derived bound, not a measurement)."""
+    n = o.n
+    x, w = o.get_state()["x"], o.get_worlds()
+    par = [o.get_params(i) for i in range(n)]
+    r = np.array([q.arm_length + q.prop_radius for q in par])
+    fin = np.isfinite(x).all(axis=1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = x[:, None, :] - x[None, :, :]
+        d2 = (d * d).sum(axis=2)
+        delta = rtol * np.maximum(np.abs(x).max(axis=1), FIELD_FLOOR["x"])
+        moves = 2.0 * np.sqrt(d2) * (delta[:, None] + delta[None, :])
+        close = np.abs(d2 - (r[:, None] + r[None, :])) < 2.0 * moves
+    pair = (w[:, None] == w[None, :]) & fin[:, None] & fin[None, :]
+    return int(np.triu(close & pair, 1).sum())
+
+
 # ---- the product side --------------------------------------------------------------------------------------------------------------
 
 class RecordingSwarm:
@@ -157,6 +201,7 @@ class StubPair(Pair):
 class Stub:
     """the device-resident calls as argument checks: what include/mrs_swarm.h and tensors.py accept, asserted; every tuple is recorded"""
     real = False
+    tick_rollout_stats = (0, 0)
 
     def __init__(self, p):
         self.p, self.calls, self.open = p, [], {"outputs": [], "poses": []}
@@ -213,7 +258,7 @@ class Stub:
         assert not self.open["outputs"] and not self.open["poses"], "a ticket would outlive its swarm"
         self.calls.append(("clone",))
 
-    def nearest(self, k, radius, fields, first, count, f32):
+    def nearest(self, k, radius, fields, first, count, f32, worlds=None):
         self._range(first, count)
         assert 1 <= k <= 32 and radius > 0 and 0 <= fields <= 31
         self.calls.append(("nearest", k, radius, fields, first, count, f32))
@@ -240,6 +285,79 @@ class Stub:
         assert 1 <= groups <= 255 and targets.shape == (E, count, w) and weights.shape in ((E, w), (1, w)) and min(pads) >= 0
         assert start is None or start.shape == (count,)
         self.calls.append(("rollout_cost", mode, cmd.shape, first, groups, weights.shape[0], hold, every, start is not None, f32, pads))
+
+    def _head(self, mode, cmd, first, hold, every, pads):
+        """the command side of a rollout; returns (ticks, count, evaluations)"""
+        assert cmd.ndim == 3
+        self._commands(mode, cmd, first, pads[0])
+        steps = cmd.shape[0] * hold
+        self._rates(steps, hold, every, cmd.shape[0])
+        assert min(pads) >= 0
+        return steps, cmd.shape[1], steps // every
+
+    @staticmethod
+    def _evaluation(groups, targets, weights, E, count, start):
+        """targets, weights and the start vector of a costed call; groups == 0 takes no targets and no weights"""
+        w = gather_width(groups)
+        assert 0 <= groups <= 255 and (start is None or start.shape == (count,))
+        if groups:
+            assert targets.shape == (E, count, w) and weights.shape in ((E, w), (1, w))
+        else:
+            assert targets is None and weights is None
+
+    @staticmethod
+    def _collide(crash, rebounce, crash_cost=0.0):
+        assert isinstance(crash, bool) and np.isfinite(rebounce) and np.isfinite(crash_cost)
+
+    def rollout_ticks(self, mode, cmd, first, groups, hold, every, crash, rebounce, crashed, f32, pads, measure=False):
+        steps, count, E = self._head(mode, cmd, first, hold, every, pads)
+        self._collide(crash, rebounce)
+        assert 0 <= groups <= 255 and crashed in ("bool", "uint8", None)
+        self.calls.append(("rollout_ticks", mode, cmd.shape, first, groups, hold, every, crash, rebounce, crashed, f32, pads))
+
+    def rollout_tick_cost(self, mode, cmd, first, groups, targets, weights, crash_cost, hold, every, crash, rebounce, start, f32, pads, measure=False):
+        steps, count, E = self._head(mode, cmd, first, hold, every, pads)
+        self._collide(crash, rebounce, crash_cost)
+        self._evaluation(groups, targets, weights, E, count, start)
+        self.calls.append(("rollout_tick_cost", mode, cmd.shape, first, groups, None if weights is None else weights.shape[0], crash_cost, hold, every,
+                           crash, rebounce, start is not None, f32, pads))
+
+    def _feedback(self, name, tick, mode, cmd, first, fb_groups, gains, refs, cost_groups, targets, weights, hold, every, start, want_out, f32, pads):
+        steps, count, E = self._head(mode, cmd, first, hold, every, pads)
+        B, wo = cmd.shape[0], gather_width(fb_groups)
+        wc = cmd.shape[2] if mode == O.ACTUATOR_CMD else WIDTH[mode]
+        assert mode != 0, "a feedback rollout needs a mode with a payload: tensors.py refuses INPUT_UNKNOWN"
+        assert 1 <= fb_groups <= 255 and cmd.shape[2] == wc
+        assert gains.ndim in (3, 4) and gains.shape[0] in (1, B) and gains.shape[1:3] == (wc, wo) and (gains.ndim == 3 or gains.shape[3] == count)
+        assert refs.ndim == 3 and refs.shape[0] in (1, B) and refs.shape[1] in (1, count) and refs.shape[2] == wo
+        assert np.isfinite(gains).all() and np.isfinite(refs).all()
+        self._evaluation(cost_groups, targets, weights, E, count, start)
+        if cost_groups:
+            assert want_out
+        elif tick is None:
+            assert not want_out and start is None, "cost_groups == 0 is a run without a cost"
+        else:
+            self._collide(*tick)
+            assert want_out or start is None, "accumulate needs the vector it adds to"
+        self.calls.append((name, mode, cmd.shape, first, fb_groups, gains.shape, refs.shape, cost_groups, hold, every, tick, start is not None, want_out,
+                           f32, pads))
+
+    def rollout_feedback(self, *a):
+        self._feedback("rollout_feedback", None, *a)
+
+    def rollout_tick_feedback(self, tick, *a, measure=False):
+        self._feedback("rollout_tick_feedback", tick, *a)
+
+    def proximity_cost(self, k, radius, kind, weight, eps, first, count, start, found):
+        self._range(first, count)
+        assert 1 <= k <= 32 and np.isfinite(radius) and radius > 0 and kind in (0, 1, 2) and np.isfinite(weight) and np.isfinite(eps) and eps >= 0
+        assert (start is None or start.shape == (count,)) and isinstance(found, bool)
+        self.calls.append(("proximity_cost", k, radius, kind, weight, eps, first, count, start is not None, found))
+
+    def set_worlds(self, worlds, first):
+        assert worlds.dtype == np.int32 and worlds.ndim == 1
+        self._range(first, len(worlds))
+        self.calls.append(("set_worlds", first, len(worlds)))
 
     def async_issue(self, kind, first, count):
         self._range(first, count)
@@ -274,6 +392,7 @@ class Device:
         self.dev = torch.device("cuda", p.g.device())
         self.stream = torch.cuda.Stream(self.dev) if side else None
         self.totals = np.zeros(7, dtype=np.int64)  # fused_stats (4), download_stats (2), split_stats[0]
+        self.tick_rollout_stats = np.zeros(2, dtype=np.int64)  # stalls and replayed launches inside the measured tick-rollout calls
 
     def ctx(self):
         return self.torch.cuda.stream(self.stream) if self.stream is not None else contextlib.nullcontext()
@@ -345,12 +464,12 @@ class Device:
         self.p.g.close()
         self.p.g = new
 
-    def nearest(self, k, radius, fields, first, count, f32):
+    def nearest(self, k, radius, fields, first, count, f32, worlds=None):
         with self.ctx():
             rows, idx, cnt = self.T.nearest(self.p.g, k, radius, fields, first, count, dtype=self._dtype(f32))
             s = self.p.g.get_states()  # right after the call: the state it read
             compare_with_numpy(self.T, rows, idx, cnt, s["x"], s["v"], s["R"].reshape(self.p.n, 3, 3), k, radius, fields, self._dtype(f32), first, count,
-                               label=("nearest", k, radius, fields, first, count))
+                               label=("nearest", k, radius, fields, first, count), worlds=worlds)
 
     def rollout(self, mode, cmd, first, groups, hold, every, forces, fhold, f32, pads):
         steps, count, w = cmd.shape[0] * hold, cmd.shape[1], gather_width(groups)
@@ -370,6 +489,89 @@ class Device:
             out = None if start is None else torch.tensor(start, dtype=torch.float64, device=self.dev)
             got = self.T.rollout_cost(self.p.g, mode, c, DT, groups, tg, wt, first=first, hold=hold, cost_every=every, out=out, accumulate=start is not None)
             return got.cpu().numpy()
+
+    def _measured(self, measure, call):
+        """`call()`, and with `measure` the stalls and replayed launches it took: fused_stats() before and after.  Both reads enter like
+        state calls and evaluate a pending collision tick, so the generator asks for them only where it expects none before the call and
+        needs none behind it."""
+        if not measure:
+            return call()
+        before = self.p.g.fused_stats()
+        got = call()
+        after = self.p.g.fused_stats()
+        self.tick_rollout_stats += [after[1] - before[1], after[2] - before[2]]
+        return got
+
+    def rollout_ticks(self, mode, cmd, first, groups, hold, every, crash, rebounce, crashed, f32, pads, measure=False):
+        torch = self.torch
+        steps, count, w = cmd.shape[0] * hold, cmd.shape[1], gather_width(groups)
+        E = steps // every
+        with self.ctx():
+            _, c = self._up(cmd, pads[0], f32)
+            big, out = self._empty((E, count, w), pads[1], f32) if groups else (None, None)
+            cr = False
+            if crashed is not None:  # (3: a byte the call must overwrite with 0 or 1)
+                cr = torch.zeros((E, count), dtype=torch.bool, device=self.dev) if crashed == "bool" else torch.full((E, count), 3, dtype=torch.uint8,
+                                                                                                                     device=self.dev)
+            self._measured(measure, lambda: self.T.rollout_ticks(self.p.g, mode, c, DT, crash, rebounce, groups, first=first, out=out, hold=hold,
+                                                                 obs_every=every, crashed=cr))
+            return (self._down(big, w, "rollout_ticks") if groups else None), (None if crashed is None else cr.cpu().numpy())
+
+    def _evaluation(self, groups, targets, weights, start, want_out, count, f32, pads):
+        """(targets, weights, out) of a costed call as tensors: padded rows; `out` holds `start`, or PAD_VALUE where the call overwrites it"""
+        torch = self.torch
+        tg = wt = out = None
+        if groups:
+            tg, wt = self._up(targets, pads[1], f32)[1], self._up(weights, pads[2], f32)[1]
+        if start is not None:
+            out = torch.tensor(start, dtype=torch.float64, device=self.dev)
+        elif want_out:
+            out = torch.full((count,), PAD_VALUE, dtype=torch.float64, device=self.dev)
+        return tg, wt, out
+
+    def rollout_tick_cost(self, mode, cmd, first, groups, targets, weights, crash_cost, hold, every, crash, rebounce, start, f32, pads, measure=False):
+        with self.ctx():
+            _, c = self._up(cmd, pads[0], f32)
+            tg, wt, out = self._evaluation(groups, targets, weights, start, True, cmd.shape[1], f32, pads)
+            got = self._measured(measure, lambda: self.T.rollout_tick_cost(self.p.g, mode, c, DT, crash, rebounce, groups, tg, wt, crash_cost=crash_cost,
+                                                                           first=first, hold=hold, cost_every=every, out=out,
+                                                                           accumulate=start is not None))
+            return got.cpu().numpy()
+
+    def _feedback(self, tick, mode, cmd, first, fb_groups, gains, refs, cost_groups, targets, weights, hold, every, start, want_out, f32, pads, measure):
+        torch, count = self.torch, cmd.shape[1]
+        with self.ctx():
+            _, c = self._up(cmd, pads[0], f32)
+            gn = torch.tensor(np.ascontiguousarray(gains), dtype=self._dtype(f32), device=self.dev)  # (dense, UAV-minor when per UAV)
+            rf = self._up(refs, pads[3] if refs.shape[1] == count and count > 1 else 0, f32)[1]        # (shared setpoint rows are dense)
+            tg, wt, out = self._evaluation(cost_groups, targets, weights, start, want_out, count, f32, pads)
+            kw = dict(cost_groups=cost_groups, targets=tg, weights=wt, first=first, hold=hold, cost_every=every, out=out, accumulate=start is not None)
+            if tick is None:
+                got = self.T.rollout_feedback(self.p.g, mode, c, DT, fb_groups, gn, rf, **kw)
+            else:
+                crash, rebounce, crash_cost = tick
+                got = self._measured(measure, lambda: self.T.rollout_tick_feedback(self.p.g, mode, c, DT, crash, rebounce, fb_groups, gn, rf,
+                                                                                   crash_cost=crash_cost, **kw))
+            assert (got is None) == (out is None and not cost_groups), "a run without a cost returns None, a costed one its vector"
+            return None if got is None else got.cpu().numpy()
+
+    def rollout_feedback(self, *a):
+        return self._feedback(None, *a, False)
+
+    def rollout_tick_feedback(self, tick, *a, measure=False):
+        return self._feedback(tick, *a, measure)
+
+    def proximity_cost(self, k, radius, kind, weight, eps, first, count, start, found):
+        torch = self.torch
+        with self.ctx():
+            out = None if start is None else torch.tensor(start, dtype=torch.float64, device=self.dev)
+            cost, fnd = self.T.proximity_cost(self.p.g, radius, k=k, kind=kind, weight=weight, eps=eps, first=first, count=count, out=out,
+                                              accumulate=start is not None, found=found)
+            return cost.cpu().numpy(), None if fnd is None else fnd.cpu().numpy()
+
+    def set_worlds(self, worlds, first):
+        with self.ctx():
+            self.T.set_worlds(self.p.g, self.torch.tensor(worlds, dtype=self.torch.int32, device=self.dev), first)
 
     def async_issue(self, kind, first, count):
         return self.p.g.get_outputs_async(first, count) if kind == "outputs" else self.p.g.get_poses_async(first, count)
@@ -397,6 +599,22 @@ def seed_rtol(fast):
     return 1e-7 if fast else helpers.RTOL_LITERAL  # the tolerances of test_random_sequences_gpu.py, as they are
 
 
+# the seeds of the extended surface, with the flags of SEEDS by the same rules and two more: (seed, FAST, fleet, the long rollout — here a
+# tick rollout —, model-only phases, collision worlds).  The numbers are those of a run of candidates that keep the two conditions of the
+# module docstring and the limits of test_the_oracle_stays_usable (test_random_device_sequences.py asserts all of it).
+EXT_SEED_NUMBERS = (100, 101, 102, 103, 104, 105, 107, 108, 109, 110, 112, 113, 114, 116, 117, 118, 119, 121, 130, 131)
+EXT_LONG_SEED = 100
+
+
+def ext_flags(s):
+    return s, s % 3 == 2, "mixed" if (s // 2) % 2 else "x500", s == EXT_LONG_SEED, s % 5 == 4, s % 5 in (0, 2)
+
+
+SEEDS_EXT = [ext_flags(s) for s in EXT_SEED_NUMBERS]
+# two more seeds per child-process variant, one per fleet and one of them with worlds
+VARIANTS_EXT = {"split": (108, 107), "pointer": (121, 102), "split+pointer": (105, 126)}
+
+
 # ---- the generator -----------------------------------------------------------------------------------------------------------------
 
 def divisors(steps, extra=()):
@@ -411,22 +629,73 @@ def f32_round(a):
     return np.asarray(a).astype(np.float32).astype(np.float64)
 
 
-def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, long_rollout=False, model=False):
+def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, long_rollout=False, model=False, surface="base", worlds=False):
     """one random sequence on the Pair `p`, whose product side is reached through `dev` as well.
+    surface: "base" draws from the first N_OPS kinds, as ever; "ext" from EXT_KINDS as well (SET_WORLDS only with `worlds`), forces any of
+    ROLLOUTS_EXT where "base" forces one of ROLLOUTS, lets the FAST_UAVS recipe force a cost-carrying tick rollout in place of its run of
+    ticks half of the time and a proximity cost follow a pending tick, takes the long horizon through a tick rollout, and counts
+    contact_violations at every collision pass of the oracle.
+    worlds: the whole swarm is labelled i % 3 before the first call.
     split: host call 12 steps in runs of five to seven launches, so that the two-stream form of step_n is taken.
     long_rollout: a shorter sequence whose first rollout takes LONG_HORIZON steps.
     model: every fifth call gives the whole swarm actuator commands, through the host call, the device call or a one-step rollout in
     turn, so that the launches that follow use the model-only kernels until a call puts some UAVs under the controller cascade again;
     half of the time that call is made a rollout.
     Returns a dict: steps, the Counter of op kinds, the op log, quaternions compared up to sign, rollouts that followed a pending
-    collision tick, tickets waited for, the worst cost bound relative to its cost, and the product's counters (Device.finish)."""
+    collision tick, tickets waited for, the worst cost bound relative to its cost, and the product's counters (Device.finish); for
+    "ext" also the rollouts of the new kinds and the proximity costs behind a pending tick, the stalls and replayed launches inside the
+    measured tick rollouts, contact_violations summed over the collision passes, and the UAVs near a quaternion branch boundary at a
+    block start of a feedback on the quaternion."""
     n, n_iter = p.n, N_ITER_LONG if long_rollout else N_ITER
+    ext = surface == "ext"
+    assert surface in ("base", "ext") and (ext or not worlds)
+    n_ops, rollouts = N_OPS, ROLLOUTS
+    if ext:
+        n_ops, rollouts = N_OPS + len(EXT_KINDS) - (0 if worlds else 1), ROLLOUTS_EXT
     kinds, oplog = Counter(), []
-    res = dict(steps=0, kinds=kinds, log=oplog, quat_sign_cases=0, rollouts_behind_pending=0, worst_cost_ratio=0.0, tickets_waited=0)
+    res = dict(steps=0, kinds=kinds, log=oplog, quat_sign_cases=0, rollouts_behind_pending=0, worst_cost_ratio=0.0, tickets_waited=0,
+               ext_rollouts_behind_pending=0, proximity_behind_pending=0, contact_violations=0, feedback_near_quat_branch=0, world_sets=[0, 0],
+               measured_tick_rollouts=0)
     pos = build_fleet(p, rng, n, fleet, seed)
     p.both("set_input", 0, n, O.POSITION_CMD, payload(rng, 10, n, pos))
+    if worlds:
+        p.both("set_worlds", (np.arange(n) % 3).astype(np.int32), 0)
+    if ext:  # every collision pass of the oracle, whichever call makes it
+        passes = p.o.handle_collisions
+
+        def watched(enabled, crash, rebounce):
+            if enabled or crash:
+                res["contact_violations"] += contact_violations(p.o, rtol)
+            passes(enabled, crash, rebounce)
+        p.o.handle_collisions = watched
     tickets = {"outputs": [], "poses": []}  # per kind, oldest first: (ticket, iteration it is due, the oracle's outputs of its range)
     pending, forced, long_left, ticked, stepped, model_due = False, [], long_rollout, False, False, False
+    stall_at = -1  # the call at which the FAST_UAVS recipe forces a tick rollout
+
+    def labels():
+        return p.o.get_worlds() if worlds else None
+
+    def cost_inputs(want, groups, f32):
+        """targets within a few units (of each group's scale) of the rows, and weights, a row per evaluation or one for all"""
+        E, w = want.shape[0], want.shape[2]
+        off = rng.uniform(0.5, 3.0, want.shape) * rng.choice([-1.0, 1.0], want.shape) * group_floors(groups)
+        targets = np.where(np.isfinite(want), want, 0.0) + off
+        weights = rng.uniform(0.1, 2.0, (E if rng.integers(0, 2) else 1, w))
+        return (f32_round(targets), f32_round(weights)) if f32 else (targets, weights)
+
+    def cost_check(got, cost, bound, start, what):
+        """a cost vector of the product against its restatement on the oracle's rows, within the first-order bound of the rows' tolerance"""
+        own = cost - (0.0 if start is None else start)  # the cost of this call
+        ok = np.isfinite(cost)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ratio = np.where(own[ok] > 0, bound[ok] / own[ok], bound[ok])  # (a cost of 0 counts against the absolute bound)
+        res["worst_cost_ratio"] = max(res["worst_cost_ratio"], float(ratio.max(initial=0.0)))
+        if got is not None:
+            assert np.array_equal(np.isfinite(got), ok), f"{what}: non-finite costs differ"
+            err = np.abs(got[ok] - cost[ok])
+            i = int(np.argmax(err - bound[ok])) if ok.any() else 0
+            assert (err <= bound[ok]).all(), (f"{what}: cost of UAV {first + int(np.flatnonzero(ok)[i])} is off by {err[i]:.3e}, the bound is "
+                                             f"{bound[ok][i]:.3e} (cost {cost[ok][i]:.6e})")
 
     def wait_oldest(kind, what):
         ticket, _, want = tickets[kind].pop(0)
@@ -446,8 +715,10 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
                 wait_oldest(kind, what)
         room = cap - res["steps"] - 2 * sum(1 for j in range(it, n_iter) if j % 5 == 4)  # (the two steps before every compare are kept free)
         model_due = model_due or (model and it % 5 == 0)
-        was_forced = bool(forced)
-        op = forced.pop(0) if forced else int(rng.integers(0, N_OPS))
+        was_forced, measure = bool(forced), False
+        op = forced.pop(0) if forced else int(rng.integers(0, n_ops))
+        if op >= N_OPS and not was_forced:
+            op = EXT_KINDS[op - N_OPS]  # (33 and 34 are the two kinds that are never drawn)
         first, count = rng_range(rng, n)
         if model_due and not was_forced:  # (calls that belong together stay together)
             forced, op, first, count, model_due = [op], MODEL_ALL, 0, n, False  # (the call drawn for this turn comes next)
@@ -458,8 +729,12 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
         if split and not stepped and op != 12:
             free -= 14  # (... and, where the two-stream form of step_n is what the sequence is run for, fourteen for its first step run)
         need = {12: 14 if split else 10, 14: 7}
+        stall = ext and it == stall_at
         if (op in need and free < need[op]) or (op == TICK_LONG and room < 7) or (op in ROLLOUTS and room < (LONG_HORIZON if long_left else 1)):
             op = GATHER  # no room left for the steps of this call
+        elif ext and ((op in TICK_ROLLOUTS and room < (LONG_HORIZON if long_left else 7 if stall else 1))
+                      or (op == ROLL_FEEDBACK and room < 1) or (long_left and (op == TICK_LONG or op in rollouts and op not in TICK_ROLLOUTS))):
+            op = GATHER  # ... and the long horizon is kept for a tick rollout
         kinds[op] += 1
         oplog.append((it, OP_NAMES[op], first, count))
         if op == 12 and split:  # at least four launches behind the one that may carry a pending collision tick: the two-stream form is taken
@@ -483,7 +758,7 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
                 dev.rollout(O.ACTUATOR_CMD, pl[None], 0, 0, 1, 1, None, None, False, (0, 0, 0))
                 res["steps"] += 1
             if rng.integers(0, 2):
-                forced.insert(0, pick(rng, ROLLOUTS))
+                forced.insert(0, pick(rng, rollouts))
         elif op == TICK_LONG:
             k = int(rng.integers(4, 8))
             for _ in range(k):
@@ -555,7 +830,7 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
             dev.clone_swap()
         elif op == NEAREST:
             k, radius, fields, f32 = int(rng.integers(1, 9)), float(rng.uniform(0.5, 4.0)), int(rng.integers(0, 32)), bool(rng.integers(0, 2))
-            dev.nearest(k, radius, fields, first, count, f32)
+            dev.nearest(k, radius, fields, first, count, f32, worlds=labels())
         elif op in ROLLOUTS:
             mode, f32 = int(rng.integers(0, 11)), bool(rng.integers(0, 2))
             if long_left:
@@ -602,28 +877,143 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
                     rows_check(got, np.array(want), np.array(Rs), groups, f32, f"{what}: {OP_NAMES[op]} of {steps} steps, mode {mode}")
             else:
                 want = np.array(want)
-                E, w = want.shape[0], want.shape[2]
-                finite = np.isfinite(want)
-                off = rng.uniform(0.5, 3.0, want.shape) * rng.choice([-1.0, 1.0], want.shape) * group_floors(groups)
-                targets = np.where(finite, want, 0.0) + off  # within a few units (of each group's scale) of the rows
-                weights = rng.uniform(0.1, 2.0, (E if rng.integers(0, 2) else 1, w))
+                targets, weights = cost_inputs(want, groups, f32)
                 start = rng.uniform(0.0, 5.0, count) if rng.integers(0, 3) == 0 else None
-                if f32:
-                    targets, weights = f32_round(targets), f32_round(weights)
                 cost = restate(want, targets, weights, start)
                 bound = cost_bound(want, targets, weights, groups, rtol)
-                own = cost - (0.0 if start is None else start)  # the cost of this call
-                ok = np.isfinite(cost)
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    ratio = np.where(own[ok] > 0, bound[ok] / own[ok], bound[ok])  # (a cost of 0 counts against the absolute bound)
-                res["worst_cost_ratio"] = max(res["worst_cost_ratio"], float(ratio.max(initial=0.0)))
                 got = dev.rollout_cost(mode, cmd, first, groups, targets, weights, hold, every, start, f32, pads)
+                cost_check(got, cost, bound, start, what)
+        elif op in ROLLOUTS_EXT:  # the four entry points of the extended surface
+            tick, fb = op != ROLL_FEEDBACK, op in (ROLL_FEEDBACK, ROLL_TICK_FEEDBACK)
+            mode, f32 = int(rng.integers(1 if fb else 0, 11)), bool(rng.integers(0, 2))  # (a feedback needs a mode with a payload)
+            if long_left:
+                steps, long_left = LONG_HORIZON, False
+            elif stall:
+                steps = pick(rng, [h for h in STALL_HORIZONS if h <= max(STALL_HORIZONS[0], free // 2)])
+            else:
+                steps = pick(rng, [h for h in HORIZONS if h <= max(1, free // 2)])
+            ticked = ticked or stall
+            hold, every = pick(rng, divisors(steps)), pick(rng, divisors(steps, (steps,)))
+            blocks = steps // hold
+            crash, rebounce, crash_cost = bool(rng.integers(0, 4) == 0), pick(rng, (60.0, 100.0)), pick(rng, (0.0, 2.5))
+            crashed = pick(rng, ("bool", "uint8", None))
+            # what is evaluated: observation rows (ROLL_TICK), or a cost in one of three forms: 0 a term over `groups`; 1 no cost at all
+            # (ROLL_FEEDBACK, ROLL_TICK_FEEDBACK: no `out`); 2 the crash cost alone (`groups` 0: ROLL_TICK_COST; ROLL_TICK_FEEDBACK with `out`)
+            groups = int(rng.integers(1, 256))
+            form = 0
+            if op == ROLL_TICK_COST:
+                form = 2 if rng.integers(0, 5) == 0 else 0
+            elif fb:
+                form = int(rng.integers(0, 3 if tick else 2))
+            if form or (op == ROLL_TICK and rng.integers(0, 5) == 0):
+                groups = 0
+            pads = tuple(int(v) for v in rng.integers(0, 4, 4))  # commands, rows or targets, weights, setpoints
+            if mode == O.ACTUATOR_CMD:
+                pads = (0,) + pads[1:]
+            if count == 1:
+                pads = (0, 0, 0, 0)
+            cmd = np.zeros((blocks, count, 1)) if mode == 0 else np.stack([payload(rng, mode, count, x) for _ in range(blocks)])
+            cmd = f32_round(cmd) if f32 else cmd
+            if fb:
+                fb_groups, per_uav, wc = int(rng.integers(1, 256)), bool(rng.integers(0, 2)), cmd.shape[2]
+                wo = gather_width(fb_groups)
+                scale = np.full(wo, 1e-3)  # small enough that the closed loop stays finite (test_rollout_feedback_gpu.draw)
+                if fb_groups >> 7 & 1:
+                    scale[-O.MAX_MOTORS:] = 1e-7  # (the rpm columns are thousands)
+                Bg, Br = (blocks if rng.integers(0, 2) else 1), (blocks if rng.integers(0, 2) else 1)
+                gains = rng.normal(0.0, 1.0, (Bg, wc, wo, count) if per_uav else (Bg, wc, wo)) * (scale[:, None] if per_uav else scale)
+                refs = rng.normal(0.0, 2.0, (Br, 1 if rng.integers(0, 2) else count, wo))
+                if f32:
+                    gains, refs = f32_round(gains), f32_round(refs)
+            measure = tick and not pending and (stall or rng.integers(0, 2) == 0)  # (Device._measured)
+            res["measured_tick_rollouts"] += int(measure)
+            res["rollouts_behind_pending"] += int(pending)
+            res["ext_rollouts_behind_pending"] += int(pending)
+            if pending and not forced and rng.integers(0, 2):
+                forced.append(13)
+            # the oracle's side: the loops of the header comments, literally
+            want, Rs, crs = [], [], []
+            for t in range(steps):
+                if t % hold == 0:
+                    if fb:  # the command of the block: nominal + G (ref - obs), from the rows before the step
+                        obs, R = ref_rows(p.o, first, count, fb_groups)
+                        if fb_groups >> QUAT_BIT & 1:
+                            res["feedback_near_quat_branch"] += int(near_quat_branch(R).sum())
+                        p.o.set_input(first, count, mode, restate_feedback(obs, cmd, gains, refs, t // hold))
+                    else:
+                        p.o.set_input(first, count, mode, cmd[t // hold] if mode else None)
+                p.o.step(DT)
+                if (t + 1) % every == 0:  # between the tick's step and its collision pass
+                    if groups:
+                        rows, R = ref_rows(p.o, first, count, groups)
+                        want.append(rows)
+                        Rs.append(R)
+                    crs.append(p.o.has_crashed(first, count).astype(bool))
+                if tick:
+                    p.o.handle_collisions(True, crash, rebounce)
+            res["steps"] += steps
+            oplog[-1] += (mode, steps, hold, every, None, groups, f32)
+            want, crs = (np.array(want) if groups else None), np.array(crs)
+            label = f"{what}: {OP_NAMES[op]} of {steps} steps, mode {mode}"
+            if op == ROLL_TICK:
+                got = dev.rollout_ticks(mode, cmd, first, groups, hold, every, crash, rebounce, crashed, f32, pads[:3], measure=measure)
                 if got is not None:
-                    assert np.array_equal(np.isfinite(got), ok), f"{what}: non-finite costs differ"
-                    err = np.abs(got[ok] - cost[ok])
-                    i = int(np.argmax(err - bound[ok])) if ok.any() else 0
-                    assert (err <= bound[ok]).all(), (f"{what}: cost of UAV {first + int(np.flatnonzero(ok)[i])} is off by {err[i]:.3e}, the bound is "
-                                                     f"{bound[ok][i]:.3e} (cost {cost[ok][i]:.6e})")
+                    if groups:
+                        rows_check(got[0], want, np.array(Rs), groups, f32, label)
+                    assert got[1] is None or np.array_equal(got[1].astype(bool), crs), f"{label}: crash rows"
+                    assert (got[0] is None) == (groups == 0) and (got[1] is None) == (crashed is None)
+            else:
+                targets = weights = start = None
+                if groups:
+                    targets, weights = cost_inputs(want, groups, f32)
+                want_out = form != 1
+                if want_out and rng.integers(0, 3) == 0:
+                    start = rng.uniform(0.0, 5.0, count)
+                if form == 1:
+                    cost = None
+                elif tick:
+                    cost = restate_ticks(want, crs, targets, weights, crash_cost, start)
+                else:
+                    cost = restate(want, targets, weights, start)
+                bound = cost_bound(want, targets, weights, groups, rtol) if groups else np.zeros(count)  # (the crash cost alone: exact)
+                if op == ROLL_TICK_COST:
+                    got = dev.rollout_tick_cost(mode, cmd, first, groups, targets, weights, crash_cost, hold, every, crash, rebounce, start, f32, pads[:3],
+                                                measure=measure)
+                elif op == ROLL_FEEDBACK:
+                    got = dev.rollout_feedback(mode, cmd, first, fb_groups, gains, refs, groups, targets, weights, hold, every, start, want_out, f32, pads)
+                else:
+                    got = dev.rollout_tick_feedback((crash, rebounce, crash_cost), mode, cmd, first, fb_groups, gains, refs, groups, targets, weights,
+                                                    hold, every, start, want_out, f32, pads, measure=measure)
+                if cost is not None:
+                    cost_check(got, cost, bound, start, label)
+                else:
+                    assert got is None, f"{label}: a run without a cost returned one"
+        elif op == PROXIMITY:
+            k, radius, kind = int(rng.integers(1, 33)), float(rng.uniform(0.5, 4.0)), int(rng.integers(0, 3))
+            weight, eps, found = float(rng.uniform(0.1, 2.0)), pick(rng, (0.0, 0.01)), bool(rng.integers(0, 2))
+            start = rng.uniform(0.0, 5.0, count) if rng.integers(0, 2) else None
+            res["proximity_behind_pending"] += int(pending)
+            oplog[-1] += (k, kind)
+            # the reference reads what the call reads: the product's FP64 positions (a gather keeps a pending tick pending) and the labels
+            # (the oracle's: the product's own getter enters like a state call; the two are compared at every compare)
+            xs = dev.gather(OBS_POS, 0, n, False, 0)
+            got = dev.proximity_cost(k, radius, kind, weight, eps, first, count, start, found)
+            if got is not None:
+                term, nfound = proximity_ref(xs, first, count, k, radius, kind, weight, eps, worlds=labels())
+                assert same_bits(got[0], add_bits(start, term)), f"{what}: proximity cost, kind {kind}, k {k}, radius {radius}"
+                assert (got[1] is None) == (not found) and (got[1] is None or np.array_equal(got[1], nfound)), f"{what}: proximity cost: found"
+        elif op == SET_WORLDS:
+            whole = rng.integers(0, 6) == 0
+            if whole:
+                first, count = 0, n
+            w = np.full(count, pick(rng, WORLD_LABELS), dtype=np.int32) if whole else rng.choice(np.array(WORLD_LABELS, dtype=np.int32), count)
+            how = sum(res["world_sets"]) % 2  # the host call on both sides, or the device call on the product's, in turn
+            res["world_sets"][how] += 1
+            if how == 0:
+                p.both("set_worlds", w, first)
+            else:
+                p.o.set_worlds(w, first)
+                dev.set_worlds(w, first)
         elif op in (ASYNC_OUTPUTS, ASYNC_POSES):
             kind = "outputs" if op == ASYNC_OUTPUTS else "poses"
             if len(tickets[kind]) == 2:
@@ -636,10 +1026,17 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
             st["v"][:] = [0.0, 170.0, 0.0]
             p.both("set_state", first, cnt, st["x"], st["v"], st["R"], st["omega"], st["motor_rpm"])
             # ... then a run of ticks that stalls, and two of the calls that must replay it and leave its last tick pending
-            forced += [TICK_LONG] + [pick(rng, STALL_FOLLOWERS) for _ in range(2)]
+            # (the extended surface, half of the time: a cost-carrying tick rollout of at least four ticks stalls instead — a replayed launch
+            # adds to the caller's cost vector once)
+            ticks = TICK_LONG
+            if ext and rng.integers(0, 2):
+                ticks, stall_at = pick(rng, STALL_ROLLOUTS), it + 1
+            forced += [ticks] + [pick(rng, STALL_FOLLOWERS) for _ in range(2)]
         if op == 14 and not forced and rng.integers(0, 3) == 0:
-            forced.append(pick(rng, ROLLOUTS))  # a rollout right behind the pending tick of a run
-        if op in (13, 14, TICK_LONG):
+            forced.append(pick(rng, rollouts))  # a rollout right behind the pending tick of a run
+        if ext and op in (13, 14, ROLL_TICK) and not measure and not forced and rng.integers(0, 2):
+            forced.append(PROXIMITY)  # the call that promises to leave the pending tick alone, right behind one
+        if op in (13, 14, TICK_LONG) or (op in TICK_ROLLOUTS and not measure):
             pending = True
         elif op not in KEEP_PENDING and not (op == MODEL_ALL and how < 2):
             pending = False
@@ -649,10 +1046,15 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
             pending = False
             if dev.real:
                 check(p, rtol, f"{what} ({it + 1} calls)")
+                if ext:
+                    assert np.array_equal(p.g.get_worlds(), p.o.get_worlds()), f"{what} ({it + 1} calls): world labels"
     for kind in tickets:
         while tickets[kind]:
             wait_oldest(kind, f"seed {seed}, end")
     assert res["steps"] <= cap, (res["steps"], cap)
     assert not long_left, "the long rollout did not happen"
+    if ext:
+        del p.o.handle_collisions  # (the watched one)
     res["stats"] = dev.finish()
+    res["stalls_in_tick_rollouts"], res["replayed_in_tick_rollouts"] = (int(v) for v in dev.tick_rollout_stats)
     return res

@@ -24,10 +24,25 @@ def check_against_numpy(T, g, x, v, R, k, radius, fields, dtype, first=0, count=
     return compare_with_numpy(T, rows, idx, cnt, x, v, R, k, radius, fields, dtype, first, count, label)
 
 
-def compare_with_numpy(T, rows, idx, cnt, x, v, R, k, radius, fields, dtype, first, count, label=""):
-    """the (rows, index, counts) of a tensors.nearest call against nearest_ref / nearest_rows on the state (x, v, R) it read"""
+def nearest_ref_in_worlds(x, worlds, first, count, k, radius):
+    """nearest_ref among the UAVs that carry the query UAV's label: world by world, a swarm of its own that holds the UAVs of one label
+    in ascending index order (include/mrs_swarm.h, "collision worlds"); indices are the whole swarm's"""
+    x, worlds = np.asarray(x, np.float64), np.asarray(worlds)
+    idx, cnt, dd = np.full((count, k), -1, np.int64), np.zeros(count, np.int64), np.zeros((count, k))
+    for w in np.unique(worlds[first:first + count]):
+        m = np.flatnonzero(worlds == w)
+        i, c, d = nearest_ref(x[m], 0, len(m), k, radius)
+        sel = (m >= first) & (m < first + count)
+        rows = m[sel] - first
+        idx[rows], cnt[rows], dd[rows] = np.where(i >= 0, m[np.maximum(i, 0)], -1)[sel], c[sel], d[sel]
+    return idx, cnt, dd
+
+
+def compare_with_numpy(T, rows, idx, cnt, x, v, R, k, radius, fields, dtype, first, count, label="", worlds=None):
+    """the (rows, index, counts) of a tensors.nearest call against nearest_ref / nearest_rows on the state (x, v, R) it read; worlds: the
+    collision-world labels of the whole swarm, where some were set"""
     import torch
-    ridx, rcnt, rdd = nearest_ref(x, first, count, k, radius)
+    ridx, rcnt, rdd = nearest_ref(x, first, count, k, radius) if worlds is None else nearest_ref_in_worlds(x, worlds, first, count, k, radius)
     assert np.array_equal(cnt.cpu().numpy(), rcnt), label
     assert np.array_equal(idx.cpu().numpy(), ridx), label
     if not fields:

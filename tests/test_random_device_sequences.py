@@ -3,7 +3,15 @@ product that checks every argument tuple against the header's rules and records 
 observation rows with, against tests/independent_model.py and against Eigen's four quaternion branches.  No GPU.
 
 Step totals (counted here): the 24 sequences of test_random_sequences_gpu.py take 39 .. 76 steps; the sequences of device_sequences.SEEDS
-and VARIANTS take at most STEP_CAP = 76, rollout steps included."""
+and VARIANTS take at most STEP_CAP = 76, rollout steps included, and so do those of SEEDS_EXT and VARIANTS_EXT (ticks of a tick rollout
+count as steps; the largest takes 76).
+
+The extended surface (counted here, over the 20 seeds of SEEDS_EXT, 8 of them with collision worlds): 27 rollout_ticks, 27
+rollout_tick_cost, 25 rollout_feedback, 35 rollout_tick_feedback, 49 proximity_cost and 13 set_worlds calls; one seed takes the 66-tick
+horizon through a tick rollout.  The first surface draws what it drew before the second existed: the SHA-256 of every op log is
+recorded in tests/golden/device_sequence_logs.json.  The two conditions that keep the comparison of the extended seeds honest — no
+same-world pair near its contact threshold at a collision pass, no quaternion near a branch boundary where a feedback reads it — are
+asserted here, on the oracle alone, so they are properties of the chosen seeds."""
 import numpy as np
 import pytest
 
@@ -15,12 +23,12 @@ from oracle import oracle_swarm as O
 from test_rollout_cost_gpu import restate
 
 
-def dry_run(mrs, seed, split=False):
-    _, fast, fleet, long_rollout, model = D.SEEDS[seed]
+def dry_run(mrs, seed, split=False, ext=False):
+    _, fast, fleet, long_rollout, model, worlds = D.ext_flags(seed) if ext else D.SEEDS[seed] + (False,)
     p = D.StubPair(mrs, D.N_UAVS)
     dev = D.Stub(p)
     res = D.run_sequence(p, dev, mrs, np.random.default_rng(D.RNG_BASE + seed), seed, fast, fleet, D.seed_rtol(fast), D.STEP_CAP, split=split,
-                         long_rollout=long_rollout, model=model)
+                         long_rollout=long_rollout, model=model, surface="ext" if ext else "base", worlds=worlds)
     st = p.o.get_state()
     res["non_finite_uavs"] = int((~np.isfinite(np.concatenate([st[k].reshape(p.n, -1) for k in st], axis=1))).any(axis=1).sum())
     res["calls"], res["product_calls"] = dev.calls, p.g.calls
@@ -30,12 +38,31 @@ def dry_run(mrs, seed, split=False):
 
 @pytest.fixture(scope="module")
 def runs(mrs):
-    """every sequence the GPU module runs: {(variant or None, seed): result}"""
+    """every sequence the GPU module runs: {(variant or None, seed): result}; the seeds of the extended surface are those from
+    D.EXT_SEED_NUMBERS[0] on, in every variant"""
     out = {(None, seed): dry_run(mrs, seed) for seed, *_ in D.SEEDS}
+    out.update({(None, seed): dry_run(mrs, seed, ext=True) for seed, *_ in D.SEEDS_EXT})
     for name, (_, seeds, split) in D.VARIANTS.items():
         for seed in seeds:
             out[name, seed] = dry_run(mrs, seed, split=split)
+        for seed in D.VARIANTS_EXT[name]:
+            out[name, seed] = dry_run(mrs, seed, split=split, ext=True)
     return out
+
+
+def is_ext(key):
+    return key[1] >= D.EXT_SEED_NUMBERS[0]
+
+
+@pytest.fixture(scope="module")
+def base_runs(runs):
+    return {k: r for k, r in runs.items() if not is_ext(k)}
+
+
+@pytest.fixture(scope="module")
+def ext_runs(runs):
+    """the sequences of the extended surface that run in the parent process: D.SEEDS_EXT"""
+    return {k: r for k, r in runs.items() if is_ext(k) and k[0] is None}
 
 
 def test_step_cap_is_the_largest_total_of_the_existing_sequences(mrs):
@@ -56,12 +83,18 @@ def test_every_sequence_keeps_the_step_budget(runs):
     for seed, _, _, long_rollout, _ in D.SEEDS:  # the long rollout happened, and left room for nothing but the compares
         longs = [e for e in runs[None, seed]["log"] if len(e) > 4 and e[5] == D.LONG_HORIZON]
         assert len(longs) == int(long_rollout), (seed, longs)
+    for seed, _, _, long_rollout, _, _ in D.SEEDS_EXT:  # ... and on the extended surface it is a tick rollout that takes it
+        longs = [e[1] for e in runs[None, seed]["log"] if len(e) > 5 and e[5] == D.LONG_HORIZON]
+        assert len(longs) == int(long_rollout) and all(name in [D.OP_NAMES[op] for op in D.TICK_ROLLOUTS] for name in longs), (seed, longs)
+    assert sum(f[3] for f in D.SEEDS_EXT) == 1
 
 
-def test_every_op_kind_occurs(runs):
+def test_every_op_kind_occurs(base_runs):
+    runs = base_runs
     kinds = sum((r["kinds"] for (variant, _), r in runs.items() if variant is None), D.Counter())
     for op in range(D.N_OPS + 2):
         assert kinds[op] >= 5, f"{D.OP_NAMES[op]} occurs {kinds[op]} times over all seeds"
+    assert not any(kinds[op] for op in D.EXT_KINDS), "the first surface draws what it always drew"
     # all four entry points of the rollouts take the long horizon once, both dtypes occur, and so do the tensor calls of every kind
     names = [c[0] for r in runs.values() for c in r["calls"]]
     for name in ("set_input", "apply_force", "gather", "crashed", "reset", "save_load", "clone", "nearest", "rollout", "rollout_cost", "async_issue",
@@ -74,16 +107,112 @@ def test_every_op_kind_occurs(runs):
         assert {D.SEEDS[s][2] for s in seeds} == {"x500", "mixed"}, variant
 
 
+def test_the_first_surface_draws_what_it_always_drew(base_runs):
+    """the op logs of the 28 seeds and the three variants, as they were before the extended surface existed: SHA-256 of repr(log)"""
+    import hashlib
+    import json
+    import os
+    with open(os.path.join(helpers.ROOT, "tests", "golden", "device_sequence_logs.json")) as f:
+        want = json.load(f)
+    got = {f"{variant},{seed}": hashlib.sha256(repr(r["log"]).encode()).hexdigest() for (variant, seed), r in base_runs.items()}
+    assert got == want
+
+
+def test_every_kind_of_the_extended_surface_occurs(runs, ext_runs):
+    """the counts of the module docstrings, over D.SEEDS_EXT"""
+    assert len(ext_runs) == len(D.SEEDS_EXT) >= 15 and min(D.EXT_SEED_NUMBERS) > len(D.SEEDS)
+    assert 3 * sum(f[5] for f in D.SEEDS_EXT) >= len(D.SEEDS_EXT), "at least a third of the seeds carry world labels"
+    kinds = sum((r["kinds"] for r in ext_runs.values()), D.Counter())
+    print("extended surface, calls per kind:", {D.OP_NAMES[op]: kinds[op] for op in D.EXT_KINDS}, "steps:", [r["steps"] for r in ext_runs.values()])
+    for op in D.EXT_KINDS:
+        assert kinds[op] >= 5, f"{D.OP_NAMES[op]} occurs {kinds[op]} times over the seeds of the extended surface"
+    calls = [c for r in ext_runs.values() for c in r["calls"]]
+    by_name = {name: [c for c in calls if c[0] == name] for name in ("rollout_ticks", "rollout_tick_cost", "rollout_feedback", "rollout_tick_feedback",
+                                                                     "proximity_cost", "set_worlds")}
+    for name, cs in by_name.items():
+        assert len(cs) >= 5, (name, len(cs))
+    # crash mode and groups == 0 in the tick rollouts; both gain layouts, a gain block per command block, every cost form
+    assert any(c[7] for c in by_name["rollout_ticks"]) and any(c[4] == 0 for c in by_name["rollout_ticks"])
+    assert {c[9] for c in by_name["rollout_ticks"]} == {"bool", "uint8", None}
+    assert any(c[9] for c in by_name["rollout_tick_cost"]) and any(c[4] == 0 for c in by_name["rollout_tick_cost"])
+    fb = by_name["rollout_feedback"] + by_name["rollout_tick_feedback"]
+    assert {len(c[5]) for c in fb} == {3, 4}, "shared and per-UAV gains"
+    assert any(c[5][0] == c[2][0] > 1 for c in fb), "Bg = B"
+    assert any(c[6][1] == 1 for c in fb) and any(c[6][1] > 1 for c in fb), "shared and per-UAV setpoints"
+    assert {(c[7] != 0, c[12]) for c in by_name["rollout_feedback"]} == {(True, True), (False, False)}
+    assert {(c[7] != 0, c[12]) for c in by_name["rollout_tick_feedback"]} == {(True, True), (False, False), (False, True)}
+    assert any(c[10][0] for c in by_name["rollout_tick_feedback"]), "crash mode under feedback"
+    assert {c[3] for c in by_name["proximity_cost"]} == {0, 1, 2} and any(c[1] == 32 for c in by_name["proximity_cost"])
+    assert {c[8] for c in by_name["proximity_cost"]} == {False, True} == {c[9] for c in by_name["proximity_cost"]}
+    # both world-setting paths, and only where the seed says so
+    for (_, seed), r in ext_runs.items():
+        worlds = D.ext_flags(seed)[5]
+        assert (r["kinds"][D.SET_WORLDS] > 0) <= worlds and ("set_worlds" in r["product_calls"]) == worlds, seed
+    assert sum(r["world_sets"][0] for r in ext_runs.values()) >= 2 and sum(r["world_sets"][1] for r in ext_runs.values()) >= 2
+    assert sum("set_worlds" == c[0] for c in calls) == sum(r["world_sets"][1] for r in ext_runs.values())
+    # what the hooks are for
+    assert sum(r["ext_rollouts_behind_pending"] for r in ext_runs.values()) >= 3
+    assert sum(r["proximity_behind_pending"] for r in ext_runs.values()) >= 3
+    assert sum(r["measured_tick_rollouts"] for r in ext_runs.values()) >= 5
+    # the child-process variants: two seeds each, one per fleet and one of them with worlds; host call 12 where step_n is split
+    for variant, (_, _, split) in D.VARIANTS.items():
+        seeds = D.VARIANTS_EXT[variant]
+        assert len(seeds) == 2 and {D.ext_flags(s)[2] for s in seeds} == {"x500", "mixed"} and sum(D.ext_flags(s)[5] for s in seeds) == 1, variant
+        for s in seeds:
+            assert not split or runs[variant, s]["kinds"][12] >= 1, (variant, s)
+            assert sum(runs[variant, s]["kinds"][op] for op in D.ROLLOUTS_EXT[4:]) >= 2, (variant, s)
+
+
+def test_the_extended_seeds_keep_their_comparison_honest(runs):
+    """the two conditions of device_sequences' docstring, for every sequence of the extended surface: no same-world pair within twice the
+    compare's reach of its contact threshold at any collision pass, and no UAV near a branch boundary of the quaternion where a
+    feedback reads it.  A seed that breaks one is replaced by another (D.EXT_SEED_NUMBERS); no tolerance moves."""
+    passes = 0
+    for key, r in runs.items():
+        if is_ext(key):
+            assert r["contact_violations"] == 0, (key, r["contact_violations"])
+            assert r["feedback_near_quat_branch"] == 0, (key, r["feedback_near_quat_branch"])
+            passes += sum(r["kinds"][op] for op in (13, 14, D.TICK_LONG) + D.TICK_ROLLOUTS)
+    assert passes >= 100
+
+
+def test_contact_violations_counts_pairs_near_their_threshold(oracle):
+    o = oracle.OracleSwarm(4)
+    o.construct(0, 4, helpers.oracle_params("x500"))
+    par = o.get_params(0)
+    crit = 2.0 * (par.arm_length + par.prop_radius)
+    st = o.get_state()
+
+    def at(d2, far=50.0):
+        x = np.array([[0.0, 0.0, 5.0], [np.sqrt(d2), 0.0, 5.0], [far, 0.0, 5.0], [far, 3.0, 5.0]])
+        o.set_state(0, 4, x, st["v"], st["R"], st["omega"], st["motor_rpm"])
+    reach = 2.0 * np.sqrt(crit) * 2.0 * 1e-7 * 5.0  # 2 d (delta_i + delta_j), delta = rtol * |x|_inf
+    for off, want in ((0.0, 1), (1.5 * reach, 1), (-1.5 * reach, 1), (3.0 * reach, 0), (-3.0 * reach, 0)):
+        at(crit + off)
+        assert D.contact_violations(o, 1e-7) == want, off
+        assert D.contact_violations(o, 1e-11) == (1 if off == 0.0 else 0), off
+    at(crit)
+    o.set_worlds([0, 1, 0, 0])
+    assert D.contact_violations(o, 1e-7) == 0, "UAVs of two worlds do not meet"
+
+
 def test_fast_uavs_are_followed_by_ticks_and_calls_that_replay_them(runs):
     n, seen, followers = 0, set(), [D.OP_NAMES[op] for op in D.STALL_FOLLOWERS]
-    for r in runs.values():
+    stallers = D.Counter()
+    for key, r in runs.items():
         names = [e[1] for e in r["log"]]
+        ticks = ["tick_long"] + ([D.OP_NAMES[op] for op in D.STALL_ROLLOUTS] if is_ext(key) else [])
         for i, name in enumerate(names[:-3]):
-            if name == "fast_uavs" and names[i + 1] == "tick_long":
+            if name == "fast_uavs" and names[i + 1] in ticks:
                 assert names[i + 2] in followers and names[i + 3] in followers
-                n += 1
-                seen.update(names[i + 2:i + 4])
+                if names[i + 1] != "tick_long":
+                    assert r["log"][i + 1][5] >= 4, "a stall needs a run of ticks"
+                    stallers[names[i + 1]] += int(key[0] is None)  # (over D.SEEDS_EXT: the variants repeat some of them)
+                elif not is_ext(key):
+                    n += 1
+                    seen.update(names[i + 2:i + 4])
     assert n >= 10 and seen == set(followers), (n, seen)
+    assert all(stallers[D.OP_NAMES[op]] >= 3 for op in D.STALL_ROLLOUTS), stallers
 
 
 def test_the_oracle_stays_usable(runs):

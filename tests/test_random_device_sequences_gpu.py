@@ -18,7 +18,20 @@ test_random_device_sequences.py counts both on the CPU and checks the generator 
 After the seeds, the counters of the library summed over them must show what the sequences are there for: a stall that was replayed, a
 pipelined download re-issued by a replay and then waited for, a rollout behind a collision tick that was still pending.  Three variants
 run in child processes (two seeds each, one per fleet): the two-stream form of step_n (MRS_SPLIT_MIN_BLOCKS=1: three blocks), the
-pointer-addressed kernels (MRS_NO_BUFFER_ADDRESSING=1), and both."""
+pointer-addressed kernels (MRS_NO_BUFFER_ADDRESSING=1), and both.
+
+The extended surface (device_sequences.SEEDS_EXT: 20 more seeds under test ids of their own, 8 of them with collision worlds, and two
+more seeds per child-process variant, one per fleet and one of them with worlds) mixes in what came after: tensors.rollout_ticks,
+rollout_tick_cost, rollout_feedback, rollout_tick_feedback and proximity_cost, and world labels set in the middle of a run that goes on
+through list ticks, fused launches, nearest() and tick rollouts.  Over the 20 seeds (counted by test_random_device_sequences.py): 27
+rollout_ticks, 27 rollout_tick_cost, 25 rollout_feedback, 35 rollout_tick_feedback, 49 proximity_cost and 13 set_worlds calls; the largest
+sequence takes 76 steps, ticks of tick rollouts included, and one takes a tick rollout of 66 ticks.  The oracle runs the loops of the header
+comments literally (set_input at block starts — from the feedback law restated in numpy where there is one —, step, rows and crash
+flags at the evaluations, handle_collisions); rows are compared like gathered rows, crash rows exactly, the term of a cost within the
+first-order bound of its rows and the crash cost exactly, a proximity cost bit for bit against numpy on the positions the product
+holds.  Their counters must show a tick rollout that stalled and replayed a launch, a proximity cost and a rollout of the new kinds
+behind a collision tick that was still pending.  The stall and replay counters of a tick rollout are read around the call, and those
+reads evaluate a pending tick: the generator takes them where none is pending before the call, and treats none as pending behind it."""
 import json
 import os
 import subprocess
@@ -27,7 +40,7 @@ import sys
 import numpy as np
 import pytest
 
-from device_sequences import N_UAVS, RNG_BASE, SEEDS, STEP_CAP, VARIANTS, Device, run_sequence, seed_rtol
+from device_sequences import N_UAVS, RNG_BASE, SEEDS, SEEDS_EXT, STEP_CAP, VARIANTS, VARIANTS_EXT, Device, ext_flags, run_sequence, seed_rtol
 from helpers import Pair
 
 pytestmark = pytest.mark.gpu
@@ -35,17 +48,18 @@ TESTS = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(TESTS)
 CHILD_TIMEOUT = 300
 STAT_NAMES = ("fused", "stalls", "replayed", "ahead", "packs", "reissued", "split_steps")
+EXT_FIGURES = ("stalls_in_tick_rollouts", "replayed_in_tick_rollouts", "proximity_behind_pending", "ext_rollouts_behind_pending")
 
-_results = {}  # seed -> what run_sequence returned
+_results = {}  # seed -> what run_sequence returned (the seeds of the extended surface too: their numbers are their own)
 _dead = []     # the first child process that died by a signal or timed out: nothing more is started on the GPU
 
 
-def run_seed(mrs, seed, split=False):
-    _, fast, fleet, long_rollout, model = SEEDS[seed]
+def run_seed(mrs, seed, split=False, ext=False):
+    _, fast, fleet, long_rollout, model, worlds = ext_flags(seed) if ext else SEEDS[seed] + (False,)
     p = Pair(mrs, N_UAVS, arith=mrs.ARITH_FAST if fast else mrs.ARITH_LITERAL)
     dev = Device(p, side=bool(seed % 2))
     res = run_sequence(p, dev, mrs, np.random.default_rng(RNG_BASE + seed), seed, fast, fleet, seed_rtol(fast), STEP_CAP, split=split,
-                       long_rollout=long_rollout, model=model)
+                       long_rollout=long_rollout, model=model, surface="ext" if ext else "base", worlds=worlds)
     assert p.g.get_diag() == p.o.get_diag()
     return res
 
@@ -54,7 +68,7 @@ def figures(res):
     st = dict(zip(STAT_NAMES, (int(v) for v in res["stats"])))
     return dict(steps=res["steps"], stalls=st["stalls"], replayed=st["replayed"], reissued=st["reissued"], tickets_waited=res["tickets_waited"],
                 quat_sign_cases=res["quat_sign_cases"], rollouts_behind_pending=res["rollouts_behind_pending"], split_steps=st["split_steps"],
-                fused=st["fused"])
+                fused=st["fused"], **{k: res[k] for k in EXT_FIGURES})
 
 
 @pytest.mark.parametrize("seed,fast,fleet,long_rollout,model", SEEDS)
@@ -64,13 +78,28 @@ def test_random_device_sequences_match_oracle(mrs, seed, fast, fleet, long_rollo
     _results[seed] = res
 
 
+@pytest.mark.parametrize("seed,fast,fleet,long_rollout,model,worlds", SEEDS_EXT)
+def test_random_sequences_of_the_extended_surface_match_oracle(mrs, seed, fast, fleet, long_rollout, model, worlds):
+    res = run_seed(mrs, seed, ext=True)
+    print(f"seed {seed} ({'FAST' if fast else 'LITERAL'}, {fleet}{', worlds' if worlds else ''}): {figures(res)}")
+    _results[seed] = res
+
+
 def test_the_sequences_met_what_they_are_for():
-    assert len(_results) == len(SEEDS), f"only {len(_results)} of the {len(SEEDS)} seeds ran to their end: this check speaks for all of them"
-    total = {k: sum(figures(r)[k] for r in _results.values()) for k in figures(next(iter(_results.values())))}
+    assert len(_results) == len(SEEDS) + len(SEEDS_EXT), (f"only {len(_results)} of the {len(SEEDS) + len(SEEDS_EXT)} seeds ran to their end: this "
+                                                          "check speaks for all of them")
+    first = [r for s, r in _results.items() if s < len(SEEDS)]
+    total = {k: sum(figures(r)[k] for r in first) for k in figures(first[0])}
     print(f"all seeds: {total}")
     assert total["stalls"] >= 1 and total["replayed"] >= 1, f"no stall of the lazy collision ticks was replayed: {total}"
     assert total["reissued"] >= 1 and total["tickets_waited"] >= 1, f"no pipelined download was re-issued by a replay and waited for: {total}"
     assert total["rollouts_behind_pending"] >= 1, f"no rollout followed a collision tick that was still pending: {total}"
+    ext = [r for s, r in _results.items() if s >= len(SEEDS)]
+    total = {k: sum(figures(r)[k] for r in ext) for k in figures(ext[0])}
+    print(f"the seeds of the extended surface: {total}")
+    assert total["stalls_in_tick_rollouts"] >= 1 and total["replayed_in_tick_rollouts"] >= 1, f"no tick rollout stalled and replayed a launch: {total}"
+    assert total["proximity_behind_pending"] >= 1, f"no proximity cost followed a collision tick that was still pending: {total}"
+    assert total["ext_rollouts_behind_pending"] >= 1, f"no tick or feedback rollout followed a collision tick that was still pending: {total}"
 
 
 def child_main(out_path, variant):
@@ -78,8 +107,8 @@ def child_main(out_path, variant):
     M.load_library()
     _, seeds, split = VARIANTS[variant]
     out = {}
-    for seed in seeds:
-        out[str(seed)] = figures(run_seed(M, seed, split=split))
+    for seed, ext in [(s, False) for s in seeds] + [(s, True) for s in VARIANTS_EXT[variant]]:
+        out[str(seed)] = figures(run_seed(M, seed, split=split, ext=ext))
         print(f"{variant}: seed {seed}: {out[str(seed)]}", flush=True)
     with open(out_path, "w") as f:
         json.dump(out, f)
@@ -106,7 +135,7 @@ def test_variant_in_a_child_process(mrs, tmp_path, variant):
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     with open(out) as f:
         got = json.load(f)
-    assert sorted(got) == sorted(str(s) for s in seeds)
+    assert sorted(got) == sorted(str(s) for s in seeds + VARIANTS_EXT[variant])
     for seed, fig in got.items():
         if split:  # the two-stream form was taken: steps launched as two half-swarm launches
             assert fig["split_steps"] >= 4, f"{variant}, seed {seed}: step_n never took the two-stream form: {fig}"

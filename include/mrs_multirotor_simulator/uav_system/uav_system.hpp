@@ -786,6 +786,37 @@ public:
                            int32_t* dev_found = nullptr, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_proximity_cost_device(s_, first, count, k, radius, kind, weight, eps, dev_cost, accumulate ? 1 : 0, dev_found, stream));
   }
+  // static obstacles (mrs_swarm_set_obstacles): replaces the swarm's set of spheres, axis-aligned boxes and vertical cylinders (an empty
+  // vector clears it).  Obstacles are seen by nearestObstaclesDevice and obstacleCostDevice only: UAVs fly through them.
+  void setObstacles(const std::vector<mrs_obstacle_t>& obstacles) {
+    mrs_throw_on_error(mrs_swarm_set_obstacles(s_, (int32_t)obstacles.size(), obstacles.data()));
+  }
+  std::vector<mrs_obstacle_t> getObstacles() const {
+    int32_t n = 0;
+    mrs_throw_on_error(mrs_swarm_get_obstacles(s_, 0, nullptr, &n));
+    std::vector<mrs_obstacle_t> out((size_t)n);
+    if (n > 0) mrs_throw_on_error(mrs_swarm_get_obstacles(s_, n, out.data(), &n));
+    return out;
+  }
+  mrs_obstacle_stats_t obstacleStats() {
+    mrs_obstacle_stats_t st;
+    mrs_throw_on_error(mrs_swarm_obstacle_stats(s_, &st));
+    return st;
+  }
+  // the k nearest obstacles within `radius` (signed distance) of UAVs [first, first + count), nearest first, ties to the lower obstacle
+  // index: row r of dev_rows holds k slots of the MRS_ON_* fields of `fields` (mrs_obstacle_width(fields, k) elements; empty slots 0),
+  // dev_index (may be null) the obstacle indices (-1: empty), dev_count (may be null) the number listed
+  void nearestObstaclesDevice(int first, int count, int k, double radius, uint32_t fields, void* dev_rows, int dtype, int stride,
+                              int32_t* dev_index, int index_stride, int32_t* dev_count, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_nearest_obstacles_device(s_, first, count, k, radius, fields, dev_rows, dtype, stride, dev_index, index_stride,
+                                                          dev_count, stream));
+  }
+  // a penalty over those obstacles, one FP64 number per UAV (mrs_swarm_obstacle_cost_device): kind MRS_PROX_HINGE2 / COUNT; written to
+  // dev_cost, or added to it (accumulate); dev_found (may be null): the obstacles within the radius, not capped by k
+  void obstacleCostDevice(int first, int count, int k, double radius, int kind, double weight, double* dev_cost, bool accumulate,
+                          int32_t* dev_found = nullptr, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_obstacle_cost_device(s_, first, count, k, radius, kind, weight, dev_cost, accumulate ? 1 : 0, dev_found, stream));
+  }
   // collision worlds (mrs_swarm_set_worlds): UAVs interact through the collision pass, and appear in each other's nearest-neighbour rows,
   // only if their 32-bit labels are equal (0 until set); the labels of UAVs [first, first + worlds.size())
   void setWorlds(int first, const std::vector<int32_t>& worlds) {

@@ -569,6 +569,91 @@ enum { MRS_PROX_HINGE2 = 0, MRS_PROX_INVERSE = 1, MRS_PROX_COUNT = 2 };
 int mrs_swarm_proximity_cost_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t k, double radius, int32_t kind, double weight, double eps,
                                     double* dev_cost, int32_t accumulate, int32_t* dev_found /* may be NULL */, void* ext_stream);
 
+/* ---- static obstacles: a set of solids owned by the swarm, observed (nearest_obstacles) and penalised (obstacle_cost), never hit ----
+ * Obstacles affect nothing but the two queries below: UAVs fly through them, and the step, the collision pass and every other call
+ * behave exactly as without a set.  (Counting penetrations and masking a reset is the caller's business: MRS_PROX_COUNT with the body
+ * radius.)
+ * Kinds: MRS_OBST_SPHERE centre c, radius h[0]; MRS_OBST_BOX axis-aligned, centre c, half-extents h; MRS_OBST_CYLINDER vertical, centre c,
+ * radius h[0], half-height h[2] (+inf: a pillar without ends; h[1] is not used, nor are a sphere's h[1], h[2]).
+ * mrs_swarm_set_obstacles replaces the set (count 0 clears it) after validating all of it on the host: c finite; the used h entries
+ * finite and >= 0, except a cylinder's h[2], which may be +inf; a known kind; no unknown flag bits; reserved == 0; count in
+ * [0, MRS_OBST_MAX]; a non-NULL array when count > 0.  Anything else is MRS_ERR_ARG and changes nothing.  The setter is ordered behind
+ * earlier work on the swarm's stream, writes no simulation state, and leaves a pending collision tick pending; it is legal on a sharded
+ * swarm (the queries are not).  The set belongs to the swarm: mrs_swarm_clone and mrs_swarm_clone_resized copy it, mrs_swarm_destroy
+ * frees it, snapshots and mrs_swarm_copy_uavs do not touch it.
+ * mrs_swarm_get_obstacles: *count (may not be NULL) receives the size of the set; the set is copied to `out` when out != NULL, which then
+ * needs capacity >= the size (MRS_ERR_ARG otherwise, *count still written).
+ * An obstacle applies to UAV i if it carries MRS_OBST_ALL_WORLDS or its `world` equals the UAV's label (mrs_swarm_set_worlds; every label
+ * is 0 until a setter says otherwise).
+ *
+ * Signed distance sd and offset rel (from the UAV to the closest point of the solid; zero inside) of a UAV at p, d = p - c per component.
+ * Everything is FP64, one rounding per operation, no fused multiply-add; max(a,b) := a < b ? b : a and min(a,b) := b < a ? b : a,
+ * literally (signed zeros follow the comparisons):
+ *   SPHERE   rho = sqrt(((dx*dx) + dy*dy) + dz*dz);  sd = rho - r;  t = rho > r ? (r / rho - 1.0) : 0.0;  rel = (t*dx, t*dy, t*dz)
+ *   BOX      a_c = |d_c| - h_c;  m_c = max(a_c, 0.0);  sd = sqrt(((m0*m0) + m1*m1) + m2*m2) + min(max(a0, max(a1, a2)), 0.0);
+ *            u_c = min(max(d_c, -h_c), h_c);  rel_c = u_c - d_c
+ *   CYLINDER rho = sqrt((dx*dx) + dy*dy);  a_r = rho - r;  a_z = |dz| - hz;
+ *            sd = sqrt((max(a_r,0.0)*max(a_r,0.0)) + max(a_z,0.0)*max(a_z,0.0)) + min(max(a_r, a_z), 0.0);
+ *            t = rho > r ? (r / rho - 1.0) : 0.0;  rel = (t*dx, t*dy, min(max(dz, -hz), hz) - dz)
+ * The obstacles of UAV i are those that apply to it with sd < radius; the first k by ascending (sd, obstacle index) are listed, so the
+ * result depends on neither traversal order nor grid layout.  A UAV with a non-finite position has no obstacles.
+ *
+ * mrs_swarm_nearest_obstacles_device: rows, slots (the MRS_ON_* fields concatenated in bit order, k slots of mrs_obstacle_width(fields, 1)
+ * elements), empty slots (zeros, index -1), untouched slack ([k*width, stride) of a row, [k, index_stride) of an index row), NULL rules
+ * (dev_index and dev_count may be NULL, dev_rows when fields == 0, at least one output), dtype handling (FP32 is the round-to-nearest
+ * cast of the FP64 value), stream fence and entry are those of mrs_swarm_nearest_device; dev_index holds obstacle indices, dev_count
+ * min(found, k).
+ * mrs_swarm_obstacle_cost_device: the evaluation of mrs_swarm_proximity_cost_device with sd_m in place of sqrt(d2_m), nearest first:
+ *     term = +0.0;  for m in [0, min(found, k)):
+ *       MRS_PROX_HINGE2: g = radius - sd_m;  term = term + (weight * g) * g        (grows the deeper the UAV is inside)
+ *       MRS_PROX_COUNT : term = term + weight                                      (MRS_PROX_INVERSE is refused)
+ *     c = accumulate ? dev_cost[r] : +0.0;  c = c + term;  dev_cost[r] = c;  if (dev_found) dev_found[r] = found   (NOT capped by k)
+ * A horizon cut at its evaluation points reads rollout_tick_cost(accumulate) -> obstacle_cost(accumulate) -> ..., bit for bit.
+ * Both calls: a pending collision tick stays pending and the simulation is left bit for bit as it was; an empty set is legal (empty
+ * rows, +0.0, found 0); every argument is checked before any launch and a refused call changes nothing: ranges MRS_ERR_RANGE;
+ * MRS_ERR_ARG for k outside [1, MRS_OBST_MAX_K], a radius that is not finite and > 0, unknown fields or kind, pointers and strides as in
+ * mrs_swarm_nearest_device / mrs_swarm_proximity_cost_device, and a sharded swarm; count == 0 is MRS_OK.
+ * The search structure is a uniform grid built on the host when a query first needs it for its radius, cached (one entry) until the
+ * radius changes or the set is replaced, and uploaded on the swarm's stream: a cell lists every obstacle whose bounding box, grown by
+ * the radius, overlaps it, so a query reads the one cell that contains p and tests every listed obstacle literally.
+ * mrs_swarm_obstacle_stats describes the set and the cached grid (zeros where no grid is cached); grid_builds counts builds so far. */
+enum { MRS_OBST_SPHERE = 0, MRS_OBST_BOX = 1, MRS_OBST_CYLINDER = 2 };
+enum { MRS_OBST_ALL_WORLDS = 1u }; /* flags: seen by UAVs of every world label */
+enum { MRS_OBST_MAX = 1 << 20, MRS_OBST_MAX_K = 32 };
+typedef struct {
+  int32_t  kind, world;
+  uint32_t flags, reserved;
+  double   c[3], h[3];
+} mrs_obstacle_t; /* 64 B */
+typedef struct {
+  int32_t count;        /* obstacles in the set */
+  int32_t dims[3];      /* cells per axis of the cached grid */
+  int64_t cells;        /* dims[0] * dims[1] * dims[2] */
+  int64_t list_items;   /* entries of all cell lists together */
+  int32_t longest_list; /* entries of the longest cell list */
+  int32_t reserved;
+  int64_t grid_builds;  /* grids built for this swarm so far */
+  double  grid_radius;  /* the query radius the cached grid serves (0: none cached) */
+  double  cell_edge;    /* edge of a cell of the cached grid */
+} mrs_obstacle_stats_t; /* 64 B */
+int mrs_swarm_set_obstacles(mrs_swarm_t* s, int32_t count, const mrs_obstacle_t* obstacles);
+int mrs_swarm_get_obstacles(const mrs_swarm_t* s, int32_t capacity, mrs_obstacle_t* out, int32_t* count);
+int mrs_swarm_obstacle_stats(mrs_swarm_t* s, mrs_obstacle_stats_t* stats);
+/* fields of one obstacle slot of mrs_swarm_nearest_obstacles_device, concatenated in bit order */
+enum {
+  MRS_ON_REL      = 1 << 0, /* 3: rel, world frame */
+  MRS_ON_REL_BODY = 1 << 1, /* 3: R_i^T rel, as MRS_NN_REL_POS_BODY forms it */
+  MRS_ON_DIST     = 1 << 2, /* 1: sd */
+  MRS_ON_ALL      = 7
+};
+/* elements per row of mrs_swarm_nearest_obstacles_device: k * (width of one slot of `fields`) (fields 0 -> 0; unknown bits or k outside
+ * [1, MRS_OBST_MAX_K] -> MRS_ERR_ARG); host only, no GPU */
+int mrs_obstacle_width(uint32_t fields, int32_t k, int32_t* width);
+int mrs_swarm_nearest_obstacles_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t k, double radius, uint32_t fields, void* dev_rows,
+                                       int32_t dtype, int32_t stride, int32_t* dev_index, int32_t index_stride, int32_t* dev_count, void* ext_stream);
+int mrs_swarm_obstacle_cost_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t k, double radius, int32_t kind, double weight,
+                                   double* dev_cost, int32_t accumulate, int32_t* dev_found /* may be NULL, NOT capped by k */, void* ext_stream);
+
 /* ---- collision worlds: several scenes in one swarm that do not see each other (per-sample horizons of a sampling-based planner) ----
  * A world is a 32-bit label per UAV, 0 for every UAV until a setter says otherwise.  Two UAVs interact through the collision pass
  * (mrs_swarm_handle_collisions, mrs_swarm_tick_n, the tick rollouts), or appear in each other's rows of mrs_swarm_nearest_device, only

@@ -561,6 +561,7 @@ int mrs_swarm_destroy(mrs_swarm_t* s) {
   if (s->rccl_comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(s->rccl_comm);
   peer_release(s);  // closes the peers' windows mapped here
   mrs_collide_free(s->cwork);
+  mrs_obstacles_free(s->obst);
   delete s;
   return MRS_OK;
 }
@@ -925,6 +926,10 @@ int mrs_swarm_clone_resized(mrs_swarm_t* s, int32_t n_uavs, mrs_swarm_t** out) {
       return rc;
     }
     c->worlds_nonzero = s->worlds_nonzero;
+  }
+  if ((rc = obstacles_copy(c, s))) {  // the obstacle set belongs to the swarm: the copy gets its own
+    mrs_swarm_destroy(c);
+    return rc;
   }
   *out = c;
   return MRS_OK;

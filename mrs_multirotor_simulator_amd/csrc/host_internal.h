@@ -5,6 +5,8 @@
 //   tick_sharded.hip      the sharded tick: communicator bookkeeping, search path, serial and split segments of the export-set exchange
 //   device_io.hip         C ABI + kernels for device-resident callers: commands, observations, resets, crash flags in device rows
 //   nearest.hip           C ABI + kernels of the k-nearest-neighbour observations for device-resident callers
+//   obstacles.hip         C ABI + kernels of the static obstacles (the set, nearest-obstacle rows, the obstacle cost); obstacle_grid.h
+//                         holds its pure host functions (tested without a GPU: tests/cpp/obstacle_grid_test.cpp)
 //   snapshot.hip          C ABI + kernels of the state snapshots (save / indexed load of whole per-UAV records) for device-resident callers
 //   transport_rccl.hip    RCCL bound at run time (dlopen)
 //   transport_local.hip   in-process loopback group, caller-supplied all-gather, measurement stand-in (with its kernels)
@@ -126,6 +128,9 @@ extern "C" hipError_t mrs_collide_handoff_init(CollideWork* w, int n, unsigned t
 extern "C" hipError_t mrs_collide_export_eval(SwarmDev sw, CollDev cd, hipStream_t st);
 extern "C" hipError_t mrs_collide_export_fold_stall(CollideWork* w, unsigned progress_tau, hipStream_t st);
 extern "C" hipError_t mrs_collide_latch_force(SwarmDev sw, CollideWork* w, int pin, int crash, double rebounce, hipStream_t st);
+// ---- obstacles.hip: the obstacle set of a swarm (host copy, device copy, cached grid) ----
+struct ObstacleSet;
+extern "C" void       mrs_obstacles_free(ObstacleSet* o);
 // ---- outputs.hip ----
 extern "C" hipError_t mrs_launch_timeout_input(SwarmDev sw, int first, int count, hipStream_t st);
 extern "C" hipError_t mrs_launch_unpack_rows(SwarmDev sw, const double* rows, int stride, int width, int base, int first, int count, hipStream_t st);
@@ -310,6 +315,8 @@ struct mrs_swarm {
   // nearest-neighbour observations (nearest.hip): one device block carved into bucket counts, starts, sorted records; grown on demand,
   // never shared with the collision pass, not copied by clone
   DevBuf<void> nn_buf;  // (counts bytes)
+  // static obstacles (obstacles.hip): allocated by the first setter or query; copied by clone, freed by mrs_swarm_destroy
+  ObstacleSet* obst = nullptr;
   // collision scratch
   DevBuf<PosRecord> dRec;
   CollideWork* cwork = nullptr;
@@ -474,6 +481,8 @@ int    fence_in(mrs_swarm* s, hipStream_t ext);
 int    fence_out(mrs_swarm* s, hipStream_t ext);
 int    launch_crashed_u8(mrs_swarm* s, int first, int count, uint8_t* dev_out);  // hasCrashed of a range as bytes, on the swarm's stream
 int    launch_crash_cost(mrs_swarm* s, int first, int count, double* dev_cost, double crash_cost);  // cost[k] += crash_cost where crashed
+// ---- obstacles.hip ----
+int    obstacles_copy(mrs_swarm* dst, const mrs_swarm* src);  // the set of src into dst (clone)
 // ---- transports (transport_*.hip) and the communicator bookkeeping (tick_sharded.hip) ----
 int  rccl_load(const char* path);
 int  rccl_check(int rc, const char* what);

@@ -85,6 +85,18 @@ COMP_WIDTHS = {1: (9, 9), 2: (18, 18), 3: (4, 8), 4: (3, 3), 5: (3, 3), 6: (4, 1
 EXCHANGE_NAMES = {0: "none", 1: "full all-gather of 48-B records per tick", 2: "export-set all-gather (boundary UAVs), full gather on search ticks"}
 
 
+class Obstacle(C.Structure):
+    """mrs_obstacle_t: one static obstacle (sphere: radius h[0]; box: half-extents h; vertical cylinder: radius h[0], half-height h[2])."""
+    _fields_ = [("kind", C.c_int32), ("world", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32), ("c", C.c_double * 3),
+                ("h", C.c_double * 3)]
+
+
+class ObstacleStats(C.Structure):
+    """mrs_obstacle_stats_t: the obstacle set and its cached search grid"""
+    _fields_ = [("count", C.c_int32), ("dims", C.c_int32 * 3), ("cells", C.c_int64), ("list_items", C.c_int64), ("longest_list", C.c_int32),
+                ("reserved", C.c_int32), ("grid_builds", C.c_int64), ("grid_radius", C.c_double), ("cell_edge", C.c_double)]
+
+
 class Diag(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("hdg_rate_denom_small", "projected_norm_small", "yaw_rate_not_finite",
                                           "nan_rollback")]
@@ -123,6 +135,8 @@ ABI_SYMBOLS = [
     "mrs_swarm_rollout_tick_feedback_device",
     "mrs_swarm_set_worlds", "mrs_swarm_get_worlds", "mrs_swarm_set_worlds_device",
     "mrs_swarm_proximity_cost_device",
+    "mrs_swarm_set_obstacles", "mrs_swarm_get_obstacles", "mrs_swarm_obstacle_stats", "mrs_obstacle_width",
+    "mrs_swarm_nearest_obstacles_device", "mrs_swarm_obstacle_cost_device",
 ]
 
 # device-resident callers (mrs_swarm_*_device): row element types and the observation groups of mrs_swarm_gather_device, in bit order
@@ -135,6 +149,14 @@ NN_ALL = 0x1F
 NN_MAX_K = 32
 # kinds of mrs_swarm_proximity_cost_device: weight (radius - d)^2, weight / (d2 + eps), weight per listed neighbour
 PROX_HINGE2, PROX_INVERSE, PROX_COUNT = 0, 1, 2
+# static obstacles (mrs_swarm_set_obstacles): kinds, flags, limits, and the fields of one slot of mrs_swarm_nearest_obstacles_device in bit
+# order (widths 3, 3, 1)
+OBST_SPHERE, OBST_BOX, OBST_CYLINDER = 0, 1, 2
+OBST_ALL_WORLDS = 1
+OBST_MAX, OBST_MAX_K = 1 << 20, 32
+ON_REL, ON_REL_BODY, ON_DIST = (1 << b for b in range(3))
+ON_ALL = 7
+OBSTACLE_DTYPE = np.dtype([("kind", "i4"), ("world", "i4"), ("flags", "u4"), ("reserved", "u4"), ("c", "f8", 3), ("h", "f8", 3)])  # mrs_obstacle_t, 64 B
 # state snapshots (mrs_swarm_save_device / mrs_swarm_load_device): one mrs_uav_snapshot_t record per UAV, 496 B
 SNAP_CRASHED, SNAP_TAKEOFF, SNAP_VPREV_SPLIT = 1, 2, 4
 SNAP_MAGIC = 0x50414E53
@@ -366,6 +388,12 @@ def load_library():
         "mrs_nearest_width": [C.c_uint32, i32, ip],
         "mrs_swarm_nearest_device": [vp, i32, i32, i32, C.c_double, C.c_uint32, vp, i32, i32, vp, i32, vp, vp],
         "mrs_swarm_proximity_cost_device": [vp, i32, i32, i32, C.c_double, i32, C.c_double, C.c_double, vp, i32, vp, vp],
+        "mrs_swarm_set_obstacles": [vp, i32, vp],
+        "mrs_swarm_get_obstacles": [vp, i32, vp, ip],
+        "mrs_swarm_obstacle_stats": [vp, vp],
+        "mrs_obstacle_width": [C.c_uint32, i32, ip],
+        "mrs_swarm_nearest_obstacles_device": [vp, i32, i32, i32, C.c_double, C.c_uint32, vp, i32, i32, vp, i32, vp, vp],
+        "mrs_swarm_obstacle_cost_device": [vp, i32, i32, i32, C.c_double, i32, C.c_double, vp, i32, vp, vp],
         "mrs_swarm_save_device": [vp, i32, i32, vp, vp],
         "mrs_swarm_load_device": [vp, i32, i32, vp, C.c_int64, vp, vp, vp],
         "mrs_swarm_rollout_device": [vp, i32, i32, i32, C.c_double, i32, vp, i32, i32, C.c_uint32, vp, i32, vp],
@@ -422,6 +450,13 @@ def nearest_width(fields, k):
     """elements per row of Swarm.nearest_device: k slots of the NN_* fields in `fields` (host only, no GPU)"""
     w = C.c_int32()
     _check(load_library().mrs_nearest_width(C.c_uint32(int(fields)), int(k), C.byref(w)))
+    return int(w.value)
+
+
+def obstacle_width(fields, k):
+    """elements per row of Swarm.nearest_obstacles_device: k slots of the ON_* fields in `fields` (host only, no GPU)"""
+    w = C.c_int32()
+    _check(load_library().mrs_obstacle_width(C.c_uint32(int(fields)), int(k), C.byref(w)))
     return int(w.value)
 
 
@@ -870,6 +905,37 @@ class Swarm:
         _check(_lib.mrs_swarm_proximity_cost_device(self._h, int(first), int(count), int(k), C.c_double(float(radius)), int(kind),
                                                     C.c_double(float(weight)), C.c_double(float(eps)), dev_cost or None,
                                                     int(bool(accumulate)), dev_found or None, ext_stream or None))
+
+    def set_obstacles(self, obstacles):
+        """Replaces the swarm's static obstacle set (mrs_swarm_set_obstacles): an OBSTACLE_DTYPE array (or None / an empty one: no
+        obstacles).  Obstacles are seen by nearest_obstacles_device and obstacle_cost_device only; UAVs fly through them."""
+        a = np.zeros(0, OBSTACLE_DTYPE) if obstacles is None else np.ascontiguousarray(obstacles, dtype=OBSTACLE_DTYPE).reshape(-1)
+        _check(_lib.mrs_swarm_set_obstacles(self._h, int(a.size), a.ctypes.data_as(C.c_void_p) if a.size else None))
+
+    def get_obstacles(self):
+        n = C.c_int32()
+        _check(_lib.mrs_swarm_get_obstacles(self._h, 0, None, C.byref(n)))
+        out = np.zeros(n.value, OBSTACLE_DTYPE)
+        if n.value:
+            _check(_lib.mrs_swarm_get_obstacles(self._h, n.value, out.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return out
+
+    def obstacle_stats(self):
+        """dict of mrs_obstacle_stats_t: count, dims, cells, list_items, longest_list, grid_builds, grid_radius, cell_edge"""
+        st = ObstacleStats()
+        _check(_lib.mrs_swarm_obstacle_stats(self._h, C.byref(st)))
+        return dict(count=st.count, dims=tuple(st.dims), cells=st.cells, list_items=st.list_items, longest_list=st.longest_list,
+                    grid_builds=st.grid_builds, grid_radius=st.grid_radius, cell_edge=st.cell_edge)
+
+    def nearest_obstacles_device(self, first, count, k, radius, fields, dev_rows, dtype, stride, dev_index, index_stride, dev_count, ext_stream):
+        _check(_lib.mrs_swarm_nearest_obstacles_device(self._h, int(first), int(count), int(k), C.c_double(float(radius)),
+                                                       C.c_uint32(int(fields)), dev_rows or None, int(dtype), int(stride), dev_index or None,
+                                                       int(index_stride), dev_count or None, ext_stream or None))
+
+    def obstacle_cost_device(self, first, count, k, radius, kind, weight, dev_cost, accumulate, dev_found, ext_stream):
+        _check(_lib.mrs_swarm_obstacle_cost_device(self._h, int(first), int(count), int(k), C.c_double(float(radius)), int(kind),
+                                                   C.c_double(float(weight)), dev_cost or None, int(bool(accumulate)), dev_found or None,
+                                                   ext_stream or None))
 
     def save_device(self, first, count, dev_records, ext_stream):
         _check(_lib.mrs_swarm_save_device(self._h, int(first), int(count), dev_records or None, ext_stream or None))

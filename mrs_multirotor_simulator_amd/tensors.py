@@ -15,7 +15,9 @@ import torch
 from .swarm import (ACTUATOR_CMD, ATTITUDE_CMD, DTYPE_F32, DTYPE_F64, INPUT_UNKNOWN, MAX_MOTORS, NN_ALL, NN_DIST, NN_MAX_K,  # noqa: F401
                     NN_REL_POS, NN_REL_POS_BODY, NN_REL_VEL, NN_REL_VEL_BODY, OBS_ALL, OBS_IMU, OBS_OMEGA, OBS_POS, OBS_QUAT, OBS_ROT,
                     OBS_RPM, OBS_VEL, OBS_VEL_BODY, PROX_COUNT, PROX_HINGE2, PROX_INVERSE, SNAP_BAD_AIRFRAME, SNAP_BAD_INDEX, SNAP_BAD_MAGIC, SNAP_CRASHED, SNAP_LOADED,
-                    SNAP_MAGIC, SNAP_SKIPPED, SNAP_TAKEOFF, SNAP_VPREV_SPLIT, SNAPSHOT_DTYPE, TILT_HDG_RATE_CMD, gather_width, nearest_width)
+                    SNAP_MAGIC, SNAP_SKIPPED, SNAP_TAKEOFF, SNAP_VPREV_SPLIT, SNAPSHOT_DTYPE, TILT_HDG_RATE_CMD, gather_width, nearest_width,
+                    OBST_ALL_WORLDS, OBST_BOX, OBST_CYLINDER, OBST_MAX, OBST_MAX_K, OBST_SPHERE, OBSTACLE_DTYPE, ON_ALL, ON_DIST, ON_REL, ON_REL_BODY,
+                    obstacle_width)
 
 _DTYPES = {torch.float64: DTYPE_F64, torch.float32: DTYPE_F32}
 SNAP_BYTES = SNAPSHOT_DTYPE.itemsize  # 496: one mrs_uav_snapshot_t
@@ -526,6 +528,105 @@ def proximity_cost(swarm, radius, k=8, kind=PROX_HINGE2, weight=1.0, eps=0.0, fi
         check_tensor(found, count, None, torch.int32, dev)
         fptr = found.data_ptr()
     swarm.proximity_cost_device(first, count, k, radius, kind, weight, eps, out.data_ptr(), bool(accumulate), fptr, _stream(dev))
+    return out, found
+
+
+def _host_array(a, name, dtype, shape):
+    """`a` (a tensor of any device, or anything numpy takes) as a host array of `dtype` and `shape` (-1: the obstacle count)"""
+    import numpy as np
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    if a.ndim != len(shape) or any(s != -1 and a.shape[d] != s for d, s in enumerate(shape)):
+        raise ValueError(f"{name} must have shape [{', '.join('M' if s == -1 else str(s) for s in shape)}], got {tuple(a.shape)}")
+    if a.dtype.kind not in "biuf":
+        raise ValueError(f"{name} has dtype {a.dtype}, expected numbers")
+    return a.astype(dtype)
+
+
+def set_obstacles(swarm, kinds, centres, sizes, worlds=None, all_worlds=None):
+    """Replaces the swarm's static obstacle set (mrs_swarm_set_obstacles): M obstacles of kinds [M] (OBST_SPHERE: radius sizes[:, 0];
+    OBST_BOX: axis-aligned, half-extents sizes; OBST_CYLINDER: vertical, radius sizes[:, 0], half-height sizes[:, 2], inf: a pillar
+    without ends) at centres [M, 3]; sizes is [M, 3].  worlds [M] (default 0): the world label whose UAVs see the obstacle; all_worlds
+    [M] bool (default False): seen by the UAVs of every label.  Tensors (of any device) or arrays: the set is static and travels through
+    the host.  M = 0 clears the set.  Obstacles are seen by nearest_obstacles() and obstacle_cost() only: UAVs fly through them."""
+    import numpy as np
+    kinds = _host_array(kinds, "kinds", np.int32, (-1,))
+    m = len(kinds)
+    rec = np.zeros(m, OBSTACLE_DTYPE)
+    rec["kind"] = kinds
+    rec["c"] = _host_array(centres, "centres", np.float64, (m, 3))
+    rec["h"] = _host_array(sizes, "sizes", np.float64, (m, 3))
+    if worlds is not None:
+        rec["world"] = _host_array(worlds, "worlds", np.int32, (m,))
+    if all_worlds is not None:
+        rec["flags"] = np.where(_host_array(all_worlds, "all_worlds", np.bool_, (m,)), OBST_ALL_WORLDS, 0)
+    if m > OBST_MAX:
+        raise ValueError(f"{m} obstacles: at most {OBST_MAX}")
+    if not np.isin(rec["kind"], (OBST_SPHERE, OBST_BOX, OBST_CYLINDER)).all():
+        raise ValueError("kinds must be OBST_SPHERE, OBST_BOX or OBST_CYLINDER")
+    if not np.isfinite(rec["c"]).all():
+        raise ValueError("centres must be finite")
+    used = np.stack([np.ones(m, bool), rec["kind"] == OBST_BOX, rec["kind"] != OBST_SPHERE], axis=1)
+    pillar = np.zeros((m, 3), bool)
+    pillar[:, 2] = (rec["kind"] == OBST_CYLINDER) & (rec["h"][:, 2] == np.inf)
+    with np.errstate(invalid="ignore"):
+        if (used & ~pillar & ~(np.isfinite(rec["h"]) & (rec["h"] >= 0))).any():
+            raise ValueError("sizes must be finite and >= 0 (a cylinder's half-height may be inf)")
+    swarm.set_obstacles(rec)
+
+
+def nearest_obstacles(swarm, k, radius, fields=ON_REL | ON_DIST, first=0, count=None, dtype=torch.float32, out=None, index=None, counts=None):
+    """The k nearest static obstacles within `radius` (signed distance to the solid) of each UAV of [first, first + count), nearest first,
+    ties to the lower obstacle index (mrs_swarm_nearest_obstacles_device).  Returns (rows, index, counts) shaped like nearest()'s: rows
+    [count, k * w] of `dtype` holding k slots of the ON_* fields of `fields` in bit order (w = obstacle_width(fields, 1); None when
+    fields == 0), index int32 [count, k] (obstacle indices; -1: empty slot, whose fields are 0) and counts int32 [count].  `out`, `index`
+    and `counts` are used instead of new tensors when given; columns past the widths are left alone."""
+    count = _count(swarm, first, count)
+    width = obstacle_width(fields, k)
+    dev = swarm.device()
+    tdev = torch.device("cuda", dev)
+    code, stride, rows_ptr = DTYPE_F32, 0, 0
+    if fields:
+        if out is None:
+            out = torch.empty((count, width), dtype=dtype, device=tdev)
+        code = _dtype_code(out.dtype)
+        stride = check_tensor(out, count, width, out.dtype, dev)
+        rows_ptr = out.data_ptr()
+    if index is None:
+        index = torch.empty((count, k), dtype=torch.int32, device=tdev)
+    istride = check_tensor(index, count, k, torch.int32, dev)
+    if counts is None:
+        counts = torch.empty(count, dtype=torch.int32, device=tdev)
+    check_tensor(counts, count, None, torch.int32, dev)
+    swarm.nearest_obstacles_device(first, count, k, radius, fields, rows_ptr, code, stride, index.data_ptr(), istride, counts.data_ptr(),
+                                   _stream(dev))
+    rows = None
+    if fields:
+        rows = out[:, :width] if out.shape[1] > width else out
+    return rows, (index[:, :k] if index.shape[1] > k else index), counts
+
+
+def obstacle_cost(swarm, radius, k=8, kind=PROX_HINGE2, weight=1.0, first=0, count=None, out=None, accumulate=False, found=False):
+    """A penalty over the k nearest static obstacles within `radius` of each UAV of [first, first + count), one FP64 number per UAV
+    (mrs_swarm_obstacle_cost_device): the obstacles of nearest_obstacles(), nearest first, summed as weight * (radius - sd)^2
+    (PROX_HINGE2, growing the deeper the UAV is inside) or weight (PROX_COUNT) per listed obstacle; PROX_INVERSE is refused.  out,
+    accumulate and found are those of proximity_cost().  Returns (out, found or None).  No simulation state is written; a pending
+    collision tick stays pending."""
+    if kind == PROX_INVERSE:
+        raise ValueError("PROX_INVERSE is not an obstacle cost kind (PROX_HINGE2 or PROX_COUNT)")
+    count = _count(swarm, first, count)
+    dev = swarm.device()
+    out = _cost_vector(out, count, accumulate, dev)
+    fptr = 0
+    if found is True:
+        found = torch.empty(count, dtype=torch.int32, device=torch.device("cuda", dev))
+    if found is False or found is None:
+        found = None
+    else:
+        check_tensor(found, count, None, torch.int32, dev)
+        fptr = found.data_ptr()
+    swarm.obstacle_cost_device(first, count, k, radius, kind, weight, out.data_ptr(), bool(accumulate), fptr, _stream(dev))
     return out, found
 
 

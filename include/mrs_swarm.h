@@ -198,7 +198,10 @@ int mrs_swarm_step_range(mrs_swarm_t* s, int32_t first, int32_t count, double dt
 /* n_steps consecutive makeStep(dt) rounds; substeps_per_launch > 1 keeps the state in registers across that many
  * steps inside one launch (legal while commands are constant and collisions are off; results identical).  After the call every
  * getter returns what n_steps single mrs_swarm_step calls leave behind; the IMU value (an output no step reads) is stored by the
- * last launch of the call only. */
+ * last launch of the call only.  substeps_per_launch is the caller's minimum: with the value 1 the library may still keep the state
+ * in registers across steps of the call (no UAV in a cascade mode, no mixed-airframe blocks: launches of up to four steps), and the
+ * results are those of single steps, bit for bit; MRS_RUN_FUSION=0 in the environment at mrs_swarm_create restores one launch per step.
+ * mrs_swarm_last_step_kernel_ms counts the launches really issued. */
 int mrs_swarm_step_n(mrs_swarm_t* s, double dt, int32_t n_steps, int32_t substeps_per_launch);
 /* MultirotorSimulator::handleCollisions — src/multirotor_simulator.cpp:295-359 (kd-tree replaced by a spatial hash) */
 int mrs_swarm_handle_collisions(mrs_swarm_t* s, int32_t enabled, int32_t crash, double rebounce);

@@ -530,6 +530,10 @@ int mrs_swarm_create(int32_t n_uavs, int32_t device_id, mrs_swarm_t** out) {
     if (ncu > 0) s->resident_waves = ncu * 4 * 2;
   }
   if (const char* e = getenv("MRS_SPLIT_STREAMS")) s->split_steps = atoi(e) != 0;
+  if (const char* e = getenv("MRS_RUN_FUSION")) {  // 0 (or 1): one launch per step; 2 .. MRS_FUSE_MAX: that many steps per launch
+    const int d   = atoi(e);
+    s->run_fusion = d < 2 ? 0 : (d > MRS_FUSE_MAX ? MRS_FUSE_MAX : d);
+  }
   if (const char* e = getenv("MRS_FUSED_COLLISIONS")) s->use_fused = atoi(e) != 0;
   if (const char* e = getenv("MRS_FUSED_LEAD")) s->fused_lead = atoi(e) > 0 ? atoi(e) : 1;
   if (const char* e = getenv("MRS_SHARD_SPLIT")) s->shard_split = atoi(e) != 0;

@@ -45,6 +45,10 @@
 // ---- step_kernel_literal.hip / step_kernel_fast.hip ----
 extern "C" hipError_t mrs_launch_step_literal(SwarmDev sw, double dt, int substeps, int cascade, int blk0, int nblk, int with_mixed, hipStream_t st);
 extern "C" hipError_t mrs_launch_step_fast(SwarmDev sw, double dt, int substeps, int cascade, int blk0, int nblk, int with_mixed, hipStream_t st);
+extern "C" hipError_t mrs_launch_step_fused_literal(SwarmDev sw, double dt, int depth, int blk0, int nblk, hipStream_t st);
+extern "C" hipError_t mrs_launch_step_fused_fast(SwarmDev sw, double dt, int depth, int blk0, int nblk, hipStream_t st);
+extern "C" int        mrs_step_fusable_literal(SwarmDev sw);
+extern "C" int        mrs_step_fusable_fast(SwarmDev sw);
 extern "C" hipError_t mrs_launch_rollout_literal(SwarmDev sw, RolloutDev r, double dt, int n_steps, int variant, hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_fast(SwarmDev sw, RolloutDev r, double dt, int n_steps, int variant, hipStream_t st);
 extern "C" hipError_t mrs_launch_rollout_rate_literal(SwarmDev sw, RolloutRateDev r, double dt, int n_steps, int cmd_every, int obs_every, int variant,
@@ -207,6 +211,7 @@ struct mrs_swarm {
   uint64_t    op_seq = 0, quiet_seq = ~0ull;
   mutable bool stream_exported = false;  // mrs_swarm_stream has handed the stream to the caller, who may enqueue work behind the library's back
   bool        split_steps = true;  // tuning: MRS_SPLIT_STREAMS=0
+  int         run_fusion  = MRS_FUSE_MAX;  // steps per launch of a plain step run (mrs_swarm_step_n); MRS_RUN_FUSION=0: one launch per step
   // native multi-GPU collision exchange (mrs_swarm_comm_init): RCCL all-gather issued on `stream`
   void*      rccl_comm = nullptr;
   int        comm_world = 0, comm_rank = 0;   // comm_world > 0: a communicator of some kind is bound
@@ -453,8 +458,8 @@ int     get_strided(mrs_swarm* s, int f, int first, int count, double* dst, int 
 int     flags_update(mrs_swarm* s, int first, int count, uint32_t and_mask, uint32_t or_mask);
 int     worlds_any_nonzero(mrs_swarm* s, bool* any);  // (synchronises the stream when a setter ran since it was last asked)
 // ---- tick_single.hip ----
-int  launch_part(mrs_swarm* s, double dt, int substeps, int blk0, int nblk, int with_mixed, hipStream_t st, bool imu_dead = false);
-int  launch_step(mrs_swarm* s, double dt, int substeps, bool imu_dead = false);
+int  launch_part(mrs_swarm* s, double dt, int substeps, int blk0, int nblk, int with_mixed, hipStream_t st, bool imu_dead = false, int fuse = 0);
+int  launch_step(mrs_swarm* s, double dt, int substeps, bool imu_dead = false, int fuse = 0);
 int  begin_profile(mrs_swarm* s);
 int  finish_profile(mrs_swarm* s);
 int  collide_now(mrs_swarm* s, const mrs_swarm::Collide& c, bool force);

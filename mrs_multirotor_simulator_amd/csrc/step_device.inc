@@ -506,8 +506,10 @@ struct Lane {
 // The part of control_and_motors that depends on the motor count: ACTUATOR_CMD payload or mixer -> throttles ->
 // MultirotorModel::setInput -> motor low-pass, allocation*rpm^2, F_ext/m.  NM > 0 fixes the count at compile time (no
 // predicated work on absent motors, and only the used columns of the allocation table are fetched).
-template <int NM, bool PRE, class SW, class PT>
-DEV void motors_stage(const SW& sw, PT& P0, const int i, const Lane& L, const int src, const double (&cg)[4], StepConst& sc, double& mean_in) {
+// CARRY (the fused plain step kernels): the new rpm of the first four motors stays in L.pre_rpm for the next step of the launch
+// instead of going to HBM; the launch's epilogue stores it.
+template <int NM, bool PRE, bool CARRY, class SW, class PT>
+DEV void motors_stage(const SW& sw, PT& P0, const int i, Lane& L, const int src, const double (&cg)[4], StepConst& sc, double& mean_in) {
   PT&       P    = fresh(P0);
   const int n    = NM ? NM : P.n_motors;
   const unsigned off8 = (unsigned)i * 8u;
@@ -548,7 +550,10 @@ DEV void motors_stage(const SW& sw, PT& P0, const int i, const Lane& L, const in
       if (m < n) {
         const double rpm = (PRE && m < 4) ? L.pre_rpm[m < 4 ? m : 0] : LD(F_RPM + m);
         rsq[m]           = rpm * rpm;                                  // :332
-        ST(F_RPM + m, P.filt_c * rpm + P.filt_1mc * input[m]);         // :246
+        if (CARRY && PRE && m < 4)
+          L.pre_rpm[m < 4 ? m : 0] = P.filt_c * rpm + P.filt_1mc * input[m];
+        else
+          ST(F_RPM + m, P.filt_c * rpm + P.filt_1mc * input[m]);       // :246
       }
     }
     mean_in = dyn_sum(input, n) / (double)n;
@@ -880,22 +885,22 @@ DEV void control_cascade(const SW& sw, PT& P, const int i, const Lane& L, const 
   (void)x; (void)v; (void)R; (void)w; (void)dt; (void)inv_dt;
 }
 
-template <bool UNIFORM, bool PRE, class SW, class PT>
-DEV void motors_dispatch(const SW& sw, PT& P, const int i, const Lane& L, const int src, const double (&cg)[4], StepConst& sc, double& mean_in,
+template <bool UNIFORM, bool PRE, bool CARRY = false, class SW, class PT>
+DEV void motors_dispatch(const SW& sw, PT& P, const int i, Lane& L, const int src, const double (&cg)[4], StepConst& sc, double& mean_in,
                          const int n_block) {
   // the motor count is wave-uniform in single-type blocks: branch once into the code specialised for it
   if (UNIFORM) {
     const int n = n_block;  // from the block-type word the prologue already holds: no extra scalar load before the branch
     if (n == 4)
-      motors_stage<4, PRE>(sw, P, i, L, src, cg, sc, mean_in);
+      motors_stage<4, PRE, CARRY>(sw, P, i, L, src, cg, sc, mean_in);
     else if (n == 6)
-      motors_stage<6, PRE>(sw, P, i, L, src, cg, sc, mean_in);
+      motors_stage<6, PRE, CARRY>(sw, P, i, L, src, cg, sc, mean_in);
     else if (n == 8)
-      motors_stage<8, PRE>(sw, P, i, L, src, cg, sc, mean_in);
+      motors_stage<8, PRE, CARRY>(sw, P, i, L, src, cg, sc, mean_in);
     else
-      motors_stage<0, PRE>(sw, P, i, L, src, cg, sc, mean_in);
+      motors_stage<0, PRE, CARRY>(sw, P, i, L, src, cg, sc, mean_in);
   } else {
-    motors_stage<0, PRE>(sw, P, i, L, src, cg, sc, mean_in);
+    motors_stage<0, PRE, CARRY>(sw, P, i, L, src, cg, sc, mean_in);
   }
 }
 
@@ -1173,16 +1178,50 @@ struct NoStepHook {
   template <class SW>
   __device__ __forceinline__ void held(const SW&, int, const Lane&, uint32_t) const {}
 };
-template <bool CASCADE, bool UNIFORM, int NU, bool MULTI, int SU, bool COLL, bool PIDPRE = false, bool SHARD = false, class HK = NoStepHook, class SW,
-          class CDT>
+// The joints between the steps of a fused launch (FUSE > 0 in step_kernel_body).  At the top of every step the carried values pass
+// an empty asm in the form a buffer load hands them out (two dwords, bit-cast to a double): the step's code then sees its inputs as
+// the single-step kernel sees the state it has loaded - opaque values of the same kind -, so that the compiler orders and contracts
+// the step's arithmetic as it does there, and nothing is contracted or reassociated across a step boundary.  At the end of every step
+// the IMU goes out under the branch the single-step kernel has around its IMU stores: the IMU arithmetic of every step has the uses
+// it has there.  A launch that is not the run's last leaves the columns alone; the run's last launch writes them FUSE times, the
+// last step's stores last in program order - 24 B per UAV and earlier step beyond what the result needs, once per run.
+DEV void fused_opaque(double& v) {
+  mrs_v2u t = __builtin_bit_cast(mrs_v2u, v);
+  asm volatile("" : "+v"(t));
+  v = __builtin_bit_cast(double, t);
+}
+DEV void fused_step_entry(Lane& L) {
+#pragma unroll
+  for (int c = 0; c < 18; c++) fused_opaque(L.y[c]);
+#pragma unroll
+  for (int c = 0; c < 3; c++) fused_opaque(L.vp[c]);
+#pragma unroll
+  for (int m = 0; m < 4; m++) fused_opaque(L.pre_rpm[m]);
+}
+template <class SW>
+DEV void fused_step_exit(const SW& sw, const int i, const Lane& L) {
+  if (!(sw.opts & MRS_OPT_IMU_DEAD)) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) sw.st(F_IMU + c, (unsigned)i * 8u, L.imu[c]);
+  }
+}
+// FUSE = D > 0 (the *_fuseD kernels of a plain run of steps): D consecutive single steps of the block in one launch.  The per-step code
+// is the single-step kernel's (commands, rpm and force fetched in the prologue), the loop is kept rolled, and x, v, R, w, v_prev and the
+// rpm of the first four motors are carried in registers from one step to the next (fused_step_entry); the rpm of further motors goes
+// through its columns every step, as in the MULTI kernels.
+template <bool CASCADE, bool UNIFORM, int NU, bool MULTI, int SU, bool COLL, bool PIDPRE = false, bool SHARD = false, class HK = NoStepHook,
+          int FUSE = 0, class SW, class CDT>
 DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, const int substeps_arg, CDT& cd0, int& blk_out, bool& took_part,
                           const HK& hk = HK()) {
   static_assert(!COLL || (NU == 1 && !MULTI), "fused collision evaluation: one UAV per lane, one step per launch");
+  static_assert(FUSE == 0 || (FUSE >= 2 && NU == 1 && !MULTI && !COLL && !CASCADE && UNIFORM && __is_same(HK, NoStepHook)),
+                "fixed-depth fused steps: the plain model-step family, single-type blocks");
+  constexpr bool LOOPED = MULTI || FUSE > 0;  // more than one step per launch: start-of-step backup in LDS for the NaN rollback
   static_assert(__is_same(HK, NoStepHook) || (NU == 1 && MULTI && !COLL) || (HK::kOnCollKernels && NU == 1 && !MULTI && COLL && !SHARD),
                 "sub-step hooks: one UAV per lane, fused sub-steps, no collisions (the tick hooks: one step, single-GPU collisions)");
   // MULTI = false compiles the substep loop away: with the loop the state is loop-carried and the per-type constants are
   // hoisted in front of it, which costs the fused kernel ~120 registers (350 vs 227) and with them its second wave per SIMD
-  const int substeps = MULTI ? substeps_arg : 1;
+  const int substeps = MULTI ? substeps_arg : (FUSE > 0 ? FUSE : 1);
   // the launches of a plain run of steps may be told to leave the IMU columns alone (epilogue).  The collision / sharded ticks never
   // are (a stall and its replay change after the fact which launch was the last one), nor the rollouts (hooked kernels)
   constexpr bool IMU_OPT = !COLL && __is_same(HK, NoStepHook);
@@ -1394,7 +1433,7 @@ DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, co
       L[u].flags &= ~FLAG_VPREV_SPLIT;  // v_prev == v again once this launch has stepped
     }
   }
-  __shared__ double y_backup[MULTI ? 18 * 64 : 1];  // fused sub-steps: the state at the start of the current one, for the NaN rollback
+  __shared__ double y_backup[LOOPED ? 18 * 64 : 1];  // fused sub-steps: the state at the start of the current one, for the NaN rollback
 // COLL: handleCollisions of the previous tick from the neighbour list -> applyForce (the F_ext columns stay authoritative:
 // getExternalForce, later plain steps) and crash().  The first partner is fetched up front; the evaluation itself runs between the
 // controller cascade and the motor stage, where the force is first needed — except in crash mode (the cascade must see the crash
@@ -1437,7 +1476,8 @@ DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, co
   for (int s = 0; s < substeps; s++) {                                                                                \
     StepConst sc[NU];                                                                                                 \
     double    mean_in[NU];                                                                                            \
-    if (MULTI) _Pragma("unroll") for (int c = 0; c < 18; c++) y_backup[c * 64 + threadIdx.x] = L[0].y[c];             \
+    if (FUSE > 0) fused_step_entry(L[0]);                                                                             \
+    if (LOOPED) _Pragma("unroll") for (int c = 0; c < 18; c++) y_backup[c * 64 + threadIdx.x] = L[0].y[c];            \
     _Pragma("unroll") for (int u = 0; u < NU; u++) if (u == 0 || idx[u] >= 0) {                                       \
       int    src_;                                                                                                    \
       double cg_[4];                                                                                                  \
@@ -1451,7 +1491,7 @@ DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, co
         if (cdm.eval && !cdm.crash && !(MRS_ABL & 2)) MRS_COLLIDE_EVAL(P)                                             \
       }                                                                                                               \
       if (L[u].pre_fe[0] != L[u].pre_fe[0] + 1e300) { MRS_STAMP(5) }                                                  \
-      motors_dispatch<UNIFORM, !MULTI>(sw, P, idx[u], L[u], src_, cg_, sc[u], mean_in[u], (int)(bt_word >> 16));      \
+      motors_dispatch<UNIFORM, !MULTI, (FUSE > 0)>(sw, P, idx[u], L[u], src_, cg_, sc[u], mean_in[u], (int)(bt_word >> 16)); \
       if (COLL && SHARD) thrust_now = sc[0].thrust; /* displacement bound of the epilogue */                         \
       if (sc[u].thrust != sc[u].thrust + 1e300) { MRS_STAMP(6) }                                                      \
     }                                                                                                                 \
@@ -1459,10 +1499,11 @@ DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, co
       sc[NU - 1]      = sc[0];                                                                                        \
       mean_in[NU - 1] = mean_in[0];                                                                                   \
     }                                                                                                                 \
-    rk4_integrate<NU, SU>(sw, P, sc, L, idx, dt, MULTI ? y_backup : nullptr);                                                                     \
+    rk4_integrate<NU, SU>(sw, P, sc, L, idx, dt, LOOPED ? y_backup : nullptr);                                        \
     _Pragma("unroll") for (int u = 0; u < NU; u++)                                                                    \
         post_step(sw, P, idx[u] < 0 ? idx[0] : idx[u], L[u], mean_in[u], dt, inv_dt);                                 \
     hk.obs(sw, P, idx[0], L[0], s);                                                                                   \
+    if (FUSE > 0) fused_step_exit(sw, idx[0], L[0]);                                                                  \
   }
   double thrust_now = 0.0;  // SHARD kernels: allocation * rpm^2 of this step (after the motor low-pass), kept for the displacement bound
   if (UNIFORM) {
@@ -1490,7 +1531,11 @@ DEV void step_kernel_body(const SW& sw, const double dt, const double inv_dt, co
       }
 #pragma unroll
       for (int c = 0; c < 9; c++) sw.st(F_R + c, (unsigned)i * 8u, L[u].y[6 + c]);
-      if (!(sw.opts & MRS_OPT_IMU_DEAD)) {
+      if (FUSE > 0) {  // (the IMU left with each step; the carried rpm of the motors the block has)
+#pragma unroll
+        for (int m = 0; m < 4; m++)
+          if (m < (int)(bt_word >> 16)) sw.st(F_RPM + m, (unsigned)i * 8u, L[u].pre_rpm[m]);
+      } else if (!(sw.opts & MRS_OPT_IMU_DEAD)) {
 #pragma unroll
         for (int c = 0; c < 3; c++) sw.st(F_IMU + c, (unsigned)i * 8u, L[u].imu[c]);
       }
@@ -1640,6 +1685,15 @@ __device__ unsigned           mrs_ts_step_cnt;
     bool took_;                                                                                                     \
     step_kernel_body<CASCADE, UNIFORM, 1, true, SU, false>(SwarmAcc<BUF>(sw), dt, inv_dt, substeps, none, blk_, took_); \
   }
+#define MRS_FUSED_RUN_KERNEL(name, bounds, ACC, SU, D)                                                            \
+  extern "C" __global__ void __launch_bounds__ bounds KNAME(name)(SwarmDev sw, double dt, double inv_dt) {       \
+    const CollDev none{};                                                                                        \
+    int  blk_;                                                                                                   \
+    bool took_;                                                                                                  \
+    MRS_TS_STEP_IN                                                                                               \
+    step_kernel_body<false, true, 1, false, SU, false, false, false, NoStepHook, D>(ACC(sw), dt, inv_dt, 1, none, blk_, took_); \
+    MRS_TS_STEP_OUT                                                                                              \
+  }
 #define MRS_STEP_KERNEL_BND(name, bounds, CASCADE, ACC, SU)                                                       \
   extern "C" __global__ void __launch_bounds__ bounds KNAME(name)(SwarmDev sw, double dt, double inv_dt, CollDev /*read in place*/) { \
     typedef const __attribute__((address_space(4))) char CChar;                                                  \
@@ -1665,10 +1719,22 @@ MRS_STEP_KERNEL(mrs_uav_model_step_buf_w3, (64, 3), false, true, true, 1)
 typedef SwarmAcc<true, true> SwarmAccNt;
 MRS_STEP_KERNEL_ACC(mrs_uav_model_step_buf_nt, (64, MRS_WAVES_PER_SIMD), false, true, SwarmAccNt, MRS_SU)
 MRS_STEP_KERNEL_ACC(mrs_uav_step_buf_nt, (64, MRS_WAVES_PER_SIMD), true, true, SwarmAccNt, MRS_SU)
+// *_fuseD: D single model steps per launch with the state in registers (plain runs of steps: mrs_launch_step_fused).
+// They are instantiated through a macro of another name than MRS_STEP_KERNEL* ON PURPOSE: tests/test_step_kernel_table.py reads every
+// MRS_STEP_KERNEL* line of this file and wants a row for it in the variant matrix of tests/test_step_variants_gpu.py, which forces a
+// kernel through the single-step / tick forms these kernels do not have.  So that completeness check does not see them; their own
+// table - which case forces which of them - is FUSED_KERNELS in tests/test_run_fusion_gpu.py, and tests/test_run_fusion_table.py
+// holds it against the MRS_FUSED_RUN_KERNEL lines below in the same way.
+typedef SwarmAcc<true, false> SwarmAccBuf;
+MRS_FUSED_RUN_KERNEL(mrs_uav_model_step_buf_fuse2, (64, MRS_WAVES_PER_SIMD), SwarmAccBuf, MRS_SU, 2)
+MRS_FUSED_RUN_KERNEL(mrs_uav_model_step_buf_fuse3, (64, MRS_WAVES_PER_SIMD), SwarmAccBuf, MRS_SU, 3)
+MRS_FUSED_RUN_KERNEL(mrs_uav_model_step_buf_fuse4, (64, MRS_WAVES_PER_SIMD), SwarmAccBuf, MRS_SU, 4)
+MRS_FUSED_RUN_KERNEL(mrs_uav_model_step_buf_nt_fuse2, (64, MRS_WAVES_PER_SIMD), SwarmAccNt, MRS_SU, 2)
+MRS_FUSED_RUN_KERNEL(mrs_uav_model_step_buf_nt_fuse3, (64, MRS_WAVES_PER_SIMD), SwarmAccNt, MRS_SU, 3)
+MRS_FUSED_RUN_KERNEL(mrs_uav_model_step_buf_nt_fuse4, (64, MRS_WAVES_PER_SIMD), SwarmAccNt, MRS_SU, 4)
 MRS_STEP_KERNEL_MULTI(mrs_uav_model_step_multi, (64, MRS_WAVES_PER_SIMD), false, true, false, MRS_SU)
 MRS_STEP_KERNEL_MULTI(mrs_uav_model_step_multi_buf, (64, MRS_WAVES_PER_SIMD), false, true, true, MRS_SU)
 // *_coll: the collision tick of the previous step is evaluated in the prologue (neighbour lists), the step follows
-typedef SwarmAcc<true, false> SwarmAccBuf;
 typedef SwarmAcc<false, false> SwarmAccPtr;
 MRS_STEP_KERNEL_COLL(mrs_uav_step_coll_buf, (64, MRS_WAVES_PER_SIMD), true, true, SwarmAccBuf, MRS_SU, false)
 MRS_STEP_KERNEL_COLL(mrs_uav_model_step_coll_buf, (64, MRS_WAVES_PER_SIMD), false, true, SwarmAccBuf, MRS_SU, false)
@@ -1737,17 +1803,18 @@ extern "C" hipError_t KNAME(mrs_launch_pid_probe)(const double* params, const do
   return hipGetLastError();
 }
 
-// variant: 0 = every input mode, 1 = model only (no UAV in a cascade mode).  The launch covers the 64-UAV blocks
-// [blk0, blk0 + nblk) — the host splits a step over two streams — and, if asked to, the (normally empty) list of mixed blocks.
-extern "C" hipError_t KNAME(mrs_launch_step)(SwarmDev sw, double dt, int substeps, int variant, int blk0, int nblk, int with_mixed, hipStream_t st) {
-  const int nb = (sw.n + 63) / 64;  // kernel choice follows the whole swarm, not the part launched here
-  if (nb <= 0 || substeps <= 0) return hipSuccess;
-  sw.blk0 = blk0;
-  const dim3   g(nblk > 0 ? nblk : 1), b(64);
-  const double inv_dt = 1.0 / dt;  // the same IEEE division the kernels used to repeat per launch
+// Which member of a step-kernel family a launch takes: ONE rule for the single-step launches and the fused ones (kernel choice follows
+// the whole swarm, not the part launched).
+struct StepKernelChoice {
+  bool force_multi, buf, w3, w3_forced, nt, nt_cascade;
+};
+static StepKernelChoice step_kernel_choice(const SwarmDev& sw, const int variant) {
+  StepKernelChoice k;
+  const int nb = (sw.n + 63) / 64;
   static const bool force_multi = getenv("MRS_FORCE_MULTI") != nullptr;  // tuning aids: A/B the looped kernels at substeps == 1,
   static const bool no_buf      = getenv("MRS_NO_BUFFER_ADDRESSING") != nullptr;  // and the pointer-addressed ones
-  const bool buf = !no_buf && (unsigned long long)F_COUNT * (unsigned long long)sw.npad * 8ull < (1ull << 32);
+  k.force_multi = force_multi;
+  k.buf = !no_buf && (unsigned long long)F_COUNT * (unsigned long long)sw.npad * 8ull < (1ull << 32);
   // more than two waves per SIMD to place (256 CUs x 4 SIMDs): the 160-register kernels keep three resident
   static const int w3_pref = getenv("MRS_THREE_WAVES") ? atoi(getenv("MRS_THREE_WAVES")) : -1;  // tuning aid: force on/off
   // (LITERAL's three-wave build spills a few registers since it carries both RK4 passes: measured slower at 1 M, 116 vs 108.5 us)
@@ -1756,11 +1823,31 @@ extern "C" hipError_t KNAME(mrs_launch_step)(SwarmDev sw, double dt, int substep
   // nothing is read twice: the two-wave kernel with non-temporal accesses streams 5-7 % faster than the three-wave one there
   // (4 M UAVs: 301 vs 319 us; 2 M cascade: 299 vs 319 us), while from 0.3 M to 2.5 M, where the cache still holds part of the
   // state, it is up to 15 % slower (tools/gpu_size_knobs.sh).
-  const bool hbm_stream = buf && MRS_FAST != 0 && w3_pref < 0 && nt_pref < 0 && (double)sw.npad * (variant == 1 ? 412.0 : 796.0) >= 1.4e9;
-  const bool w3 = buf && !hbm_stream && (w3_pref < 0 ? (MRS_FAST != 0 && nb > 2 * 1024) : w3_pref != 0);
+  const bool hbm_stream = k.buf && MRS_FAST != 0 && w3_pref < 0 && nt_pref < 0 && (double)sw.npad * (variant == 1 ? 412.0 : 796.0) >= 1.4e9;
+  k.w3 = k.buf && !hbm_stream && (w3_pref < 0 ? (MRS_FAST != 0 && nb > 2 * 1024) : w3_pref != 0);
   // small swarm, short launch: non-temporal state accesses too (LITERAL measured neutral: 11.5 us either way)
-  const bool nt = buf && !w3 && (nt_pref < 0 ? (MRS_FAST != 0 && (nb <= 1900 || hbm_stream)) : nt_pref != 0);  // 120 k UAVs: -0.5 us, 131 k: +0.8 us
-  const bool nt_cascade = buf && !w3 && (nt_pref < 0 ? (MRS_FAST != 0 && (nb <= 900 || hbm_stream)) : nt_pref != 0);  // 56 k UAVs: -0.4 us, 62 k: +0.25 us
+  k.nt = k.buf && !k.w3 && (nt_pref < 0 ? (MRS_FAST != 0 && (nb <= 1900 || hbm_stream)) : nt_pref != 0);  // 120 k UAVs: -0.5 us, 131 k: +0.8 us
+  k.nt_cascade = k.buf && !k.w3 && (nt_pref < 0 ? (MRS_FAST != 0 && (nb <= 900 || hbm_stream)) : nt_pref != 0);  // 56 k UAVs: -0.4 us, 62 k: +0.25 us
+  k.w3_forced = w3_pref > 0;
+  return k;
+}
+// A plain run of this swarm may be issued as fused launches (mrs_launch_step_fused): buffer-addressed state, no mixed blocks, and none
+// of the tuning aids set that ask for another kernel (MRS_FORCE_MULTI, MRS_THREE_WAVES=1: there is no three-wave fused kernel).
+extern "C" int KNAME(mrs_step_fusable)(SwarmDev sw) {
+  const StepKernelChoice k = step_kernel_choice(sw, 1);
+  return k.buf && !k.force_multi && !k.w3_forced && sw.n_mixed == 0;
+}
+
+// variant: 0 = every input mode, 1 = model only (no UAV in a cascade mode).  The launch covers the 64-UAV blocks
+// [blk0, blk0 + nblk) — the host splits a step over two streams — and, if asked to, the (normally empty) list of mixed blocks.
+extern "C" hipError_t KNAME(mrs_launch_step)(SwarmDev sw, double dt, int substeps, int variant, int blk0, int nblk, int with_mixed, hipStream_t st) {
+  const int nb = (sw.n + 63) / 64;  // kernel choice follows the whole swarm, not the part launched here
+  if (nb <= 0 || substeps <= 0) return hipSuccess;
+  sw.blk0 = blk0;
+  const dim3   g(nblk > 0 ? nblk : 1), b(64);
+  const double inv_dt = 1.0 / dt;  // the same IEEE division the kernels used to repeat per launch
+  const StepKernelChoice k = step_kernel_choice(sw, variant);
+  const bool force_multi = k.force_multi, buf = k.buf, w3 = k.w3, nt = k.nt, nt_cascade = k.nt_cascade;
   if (nblk > 0) {
     if (substeps == 1 && !force_multi) {
       if (variant == 1) {
@@ -1803,6 +1890,36 @@ extern "C" hipError_t KNAME(mrs_launch_step)(SwarmDev sw, double dt, int substep
     else
       hipLaunchKernelGGL(KNAME(mrs_uav_step_mixed_multi), dim3(sw.n_mixed), b, 0, st, sw, dt, inv_dt, substeps);
   }
+  return hipGetLastError();
+}
+
+// `depth` (2 .. MRS_FUSE_MAX) single model steps of the blocks [blk0, blk0 + nblk) in ONE launch, the state in registers in between:
+// the plain model-step family only (no UAV in a cascade mode, no mixed blocks, buffer-addressed state) - the caller has checked.
+extern "C" hipError_t KNAME(mrs_launch_step_fused)(SwarmDev sw, double dt, int depth, int blk0, int nblk, hipStream_t st) {
+  const int nb = (sw.n + 63) / 64;
+  if (nb <= 0 || nblk <= 0) return hipSuccess;
+  const StepKernelChoice k = step_kernel_choice(sw, 1);
+  if (depth < 2 || depth > MRS_FUSE_MAX || sw.n_mixed > 0 || !k.buf) return hipErrorInvalidValue;
+  sw.blk0 = blk0;
+  const dim3   g(nblk), b(64);
+  const double inv_dt = 1.0 / dt;
+  // non-temporal accesses where the single-step launch has them: small swarms, and far beyond the Infinity Cache.  Where that launch
+  // takes the three-wave kernel (FAST, more than 2048 blocks) this one takes the two-wave *_fuseD: a quarter of the bytes outweighs
+  // the third resident wave (MEASUREMENTS section 11, 1 M UAVs).
+  const bool nt = k.nt;
+#define MRS_FUSE_LAUNCH(D)                                                                             \
+  case D:                                                                                              \
+    if (nt)                                                                                            \
+      hipLaunchKernelGGL(KNAME(mrs_uav_model_step_buf_nt_fuse##D), g, b, 0, st, sw, dt, inv_dt);       \
+    else                                                                                               \
+      hipLaunchKernelGGL(KNAME(mrs_uav_model_step_buf_fuse##D), g, b, 0, st, sw, dt, inv_dt);          \
+    break;
+  switch (depth) {
+    MRS_FUSE_LAUNCH(2)
+    MRS_FUSE_LAUNCH(3)
+    MRS_FUSE_LAUNCH(4)
+  }
+#undef MRS_FUSE_LAUNCH
   return hipGetLastError();
 }
 

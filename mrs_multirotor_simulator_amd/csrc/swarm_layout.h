@@ -74,6 +74,7 @@ struct TypeParams {
 // the F_IMU columns, so this launch does not store them (the IMU value is an output only: no step reads it).  Plain step kernels
 // only; the *_coll / sharded kernels and the rollout kernels never see the bit and do not test it.
 #define MRS_OPT_IMU_DEAD 2u
+#define MRS_FUSE_MAX 4  // deepest fused plain step launch (step_device.inc *_fuseD)
 struct PosRecord;
 struct SwarmDev {
   double*             S;      // F_COUNT x npad

@@ -9,10 +9,19 @@ namespace mrs_host {
 // imu_dead: another launch of the same mrs_swarm_step_n call follows on this stream and steps the same UAVs again before anybody can
 // read the IMU columns — this one (and the mixed-block launch that rides with it) does not store them (MRS_OPT_IMU_DEAD).  Only
 // mrs_swarm_step_n passes true; every other caller's launch may be the last one somebody looks at.
-int launch_part(mrs_swarm* s, double dt, int substeps, int blk0, int nblk, int with_mixed, hipStream_t st, bool imu_dead) {
+// fuse > 0: the launch runs `fuse` single steps with the state in registers (the *_fuseD kernels; mrs_swarm_step_n has checked that the
+// swarm qualifies), substeps is 1 then.
+int launch_part(mrs_swarm* s, double dt, int substeps, int blk0, int nblk, int with_mixed, hipStream_t st, bool imu_dead, int fuse) {
   const int variant = s->n_cascade > 0 ? 0 : 1;  // 0 all input modes | 1 model only
   SwarmDev  v       = s->view();
   if (imu_dead) v.opts |= MRS_OPT_IMU_DEAD;
+  if (fuse > 0) {
+    if (s->arith == MRS_ARITH_FAST)
+      HIPCHK(mrs_launch_step_fused_fast(v, dt, fuse, blk0, nblk, st));
+    else
+      HIPCHK(mrs_launch_step_fused_literal(v, dt, fuse, blk0, nblk, st));
+    return MRS_OK;
+  }
   if (s->arith == MRS_ARITH_FAST)
     HIPCHK(mrs_launch_step_fast(v, dt, substeps, variant, blk0, nblk, with_mixed, st));
   else
@@ -30,7 +39,7 @@ static int ensure_events(mrs_swarm* s, size_t count) {
   return MRS_OK;
 }
 
-int launch_step(mrs_swarm* s, double dt, int substeps, bool imu_dead) {
+int launch_step(mrs_swarm* s, double dt, int substeps, bool imu_dead, int fuse) {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   s->region_launches++;
   if (s->profiling == 2) {
@@ -41,20 +50,21 @@ int launch_step(mrs_swarm* s, double dt, int substeps, bool imu_dead) {
     HIPCHK(hipEventRecord(e0, s->stream));
   }
   // (per-launch events: somebody times single launches — they all do the same work)
-  int rc = launch_part(s, dt, substeps, 0, (s->n + 63) / 64, 1, s->stream, imu_dead && s->profiling != 2);
+  int rc = launch_part(s, dt, substeps, 0, (s->n + 63) / 64, 1, s->stream, imu_dead && s->profiling != 2, fuse);
   if (rc) return rc;
   if (s->profiling == 2) HIPCHK(hipEventRecord(e1, s->stream));
   return MRS_OK;
 }
 
 // one step as two independent half-swarm launches, one per stream (between fork_streams and join_streams)
-int launch_step_split(mrs_swarm* s, double dt, int substeps, bool imu_dead) {
+int launch_step_split(mrs_swarm* s, double dt, int substeps, bool imu_dead, int fuse) {
   s->region_launches++;
-  s->x_split_ticks++;  // (mrs_swarm_get_split_stats: a sharded swarm never comes here, its own split ticks count there)
+  // (mrs_swarm_get_split_stats: a sharded swarm never comes here, its own split ticks count there.  A fused launch is that many ticks.)
+  s->x_split_ticks += fuse > 0 ? fuse : 1;
   const int nb = (s->n + 63) / 64, half = nb / 2;
-  int rc = launch_part(s, dt, substeps, 0, half, 1, s->stream, imu_dead);
+  int rc = launch_part(s, dt, substeps, 0, half, 1, s->stream, imu_dead, fuse);
   if (rc) return rc;
-  return launch_part(s, dt, substeps, half, nb - half, 0, s->stream2, imu_dead);
+  return launch_part(s, dt, substeps, half, nb - half, 0, s->stream2, imu_dead, fuse);
 }
 int fork_streams(mrs_swarm* s) {
   HIPCHK(hipEventRecord(s->ev_fork, s->stream));
@@ -461,7 +471,19 @@ int mrs_swarm_step_n(mrs_swarm_t* s, double dt, int32_t n_steps, int32_t substep
     s->p_valid = false;
     // enough launches to overlap, enough blocks for two useful halves, and no per-launch events to keep in order
     static const int split_min_blocks = getenv("MRS_SPLIT_MIN_BLOCKS") ? atoi(getenv("MRS_SPLIT_MIN_BLOCKS")) : 1024;  // tuning aid
-    const bool split = s->split_steps && s->profiling != 2 && (s->n + 63) / 64 >= split_min_blocks && (n_steps + substeps_per_launch - 1) / substeps_per_launch >= 4;
+    // Fused runs.  With one step per launch asked for, nobody can look at the state between two steps of this call: commands are
+    // constant, collisions are off, every getter runs after the call has returned.  The plain model-step family then runs up to
+    // `run_fusion` steps per launch with the state in registers - the results are those of single steps, bit for bit - as full
+    // launches and one launch of the remainder (a remainder of one step: the single-step kernel).  Everything else takes the launches
+    // it always took: a UAV in a cascade mode, mixed-airframe blocks, per-launch events, a state array the buffer-addressed kernels
+    // cannot reach.
+    // (the launcher's own rule says whether the fused kernels can serve the swarm: mrs_step_fusable in step_device.inc)
+    const int  depth = (substeps_per_launch == 1 && s->run_fusion >= 2 && s->n_cascade == 0 && s->mixed_blocks.empty() && s->profiling != 2 &&
+                        (s->arith == MRS_ARITH_FAST ? mrs_step_fusable_fast(s->view()) : mrs_step_fusable_literal(s->view())))
+                           ? s->run_fusion
+                           : 0;
+    const int  per_launch = depth > 0 ? depth : substeps_per_launch;
+    const bool split = s->split_steps && s->profiling != 2 && (s->n + 63) / 64 >= split_min_blocks && (n_steps + per_launch - 1) / per_launch >= 4;
     // (the call right before this one was mrs_swarm_synchronize and nothing has been enqueued since — not even by the lines above:
     //  both streams are idle (upload_types synchronises when it copies), the second one needs no event to wait for)
     const bool quiet = idle_at_entry && !enqueued;
@@ -473,9 +495,10 @@ int mrs_swarm_step_n(mrs_swarm_t* s, double dt, int32_t n_steps, int32_t substep
     // collision launches always write: their stall / replay logs can change after the fact which launch was the last one.
     int left = n_steps;
     while (left > 0 && rc == MRS_OK) {
-      const int  sub  = left < substeps_per_launch ? left : substeps_per_launch;
+      const int  sub  = left < per_launch ? left : per_launch;
       const bool last = left == sub;
-      rc = split ? launch_step_split(s, dt, sub, !last) : launch_step(s, dt, sub, !last);
+      const int  fuse = depth > 0 && sub >= 2 ? sub : 0;
+      rc = split ? launch_step_split(s, dt, fuse ? 1 : sub, !last, fuse) : launch_step(s, dt, fuse ? 1 : sub, !last, fuse);
       left -= sub;
     }
     if (split) {  // also on a failed launch: nothing else may touch the state before the second stream has been joined

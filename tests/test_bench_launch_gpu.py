@@ -43,9 +43,14 @@ def _gpu_sample(g, pick):
 @pytest.mark.parametrize("workload,n,steps", [("actuator", 100_000, 120), ("position", 100_000, 120), ("actuator", 1_000_000, 40),
                                               ("position", 50_000, 120), ("actuator", 4_000_000, 24), ("position", 2_000_000, 24)])
 def test_bench_launch_against_oracle(mrs, oracle, workload, n, steps):
-    """100 k actuator: *_model_step_buf_nt_fast x 2 streams; 100 k position: mrs_uav_step_buf_fast x 2 streams; 1 M actuator:
-    *_model_step_buf_w3_fast x 2 streams; 50 k position: mrs_uav_step_buf_nt_fast on one stream (< 1024 blocks); 4 M actuator and
-    2 M position (>= 1.4 GB moved per step, the HBM-streaming sizes of profiles/): the non-temporal two-wave kernels again."""
+    """The actuator runs are fused launches of four steps ("State in registers inside a run"), on two streams: 100 k
+    *_model_step_buf_nt_fuse4_fast; 1 M *_model_step_buf_fuse4_fast (the two-wave fused kernel, where a single step() is the
+    three-wave *_model_step_buf_w3_fast); 4 M (>= 1.4 GB moved per step, the HBM-streaming sizes of profiles/)
+    *_model_step_buf_nt_fuse4_fast again.  The position runs never fuse: 100 k mrs_uav_step_buf_fast x 2 streams; 50 k
+    mrs_uav_step_buf_nt_fast on one stream (< 1024 blocks); 2 M (HBM streaming) mrs_uav_step_buf_nt_fast x 2 streams.
+    The model-only three-wave kernel in the two-stream run form, which the 1 M case ran before runs were fused, is kept covered by
+    test_run_imu_elision_gpu.py::test_run_equals_single_steps_in_the_two_wave_and_three_wave_regimes[model-131073-*] (a run with
+    MRS_RUN_FUSION=0 at 2049 blocks) and by the single steps of test_run_fusion_gpu.py's [131073-fast] cases."""
     M = mrs
     rng = np.random.default_rng(11)
     st, cmd = _bench_inputs(n, workload, seed=3)

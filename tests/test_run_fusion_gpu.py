@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from helpers import random_state
+from step_regimes import N_BUF_LAST, N_W3_FIRST  # 131 072 UAVs (2048 full blocks) and 131 073 (2049 blocks, a one-lane tail block)
 
 pytestmark = pytest.mark.gpu
 DT = 0.001
@@ -17,14 +18,19 @@ ARITHS = ["literal", "fast"]
 N_BUF = 122_000  # 1907 blocks: above the size up to which FAST launches the non-temporal (*_nt) kernels
 # The fused kernels step_device.inc compiles and the cases of this file that force them (the launcher takes the *_nt ones for FAST swarms of
 # up to 1900 blocks, the others for LITERAL and for larger FAST swarms; depth D for full launches, 2 .. D-1 for remainders).
+# The single-step kernel they are held against changes once more on the way: the two-wave *_buf up to 2048 blocks ([122000-fast],
+# [131072-fast]), the three-wave *_buf_w3 above ([131073-fast]: the pairing of the 1 M benchmark leg; the same pair on three blocks
+# in test_step_regimes_gpu.py).  The sizes come from step_regimes.py, which test_step_regimes.py holds against the launcher's rule.
 # tests/test_run_fusion_table.py holds this table against the source.
+_BUF_CASES = ["test_fused_runs_equal_single_steps[1000-literal]", "test_fused_runs_equal_single_steps[122000-fast]",
+              "test_fused_runs_equal_single_steps[131072-fast]", "test_fused_runs_equal_single_steps[131073-fast]"]
 FUSED_KERNELS = {
     "mrs_uav_model_step_buf_nt_fuse2": ["test_fused_runs_equal_single_steps[1000-fast]"],
     "mrs_uav_model_step_buf_nt_fuse3": ["test_fused_runs_equal_single_steps[1000-fast]"],
     "mrs_uav_model_step_buf_nt_fuse4": ["test_fused_runs_equal_single_steps[1000-fast]"],
-    "mrs_uav_model_step_buf_fuse2": ["test_fused_runs_equal_single_steps[1000-literal]", "test_fused_runs_equal_single_steps[122000-fast]"],
-    "mrs_uav_model_step_buf_fuse3": ["test_fused_runs_equal_single_steps[1000-literal]", "test_fused_runs_equal_single_steps[122000-fast]"],
-    "mrs_uav_model_step_buf_fuse4": ["test_fused_runs_equal_single_steps[1000-literal]", "test_fused_runs_equal_single_steps[122000-fast]"],
+    "mrs_uav_model_step_buf_fuse2": list(_BUF_CASES),
+    "mrs_uav_model_step_buf_fuse3": list(_BUF_CASES),
+    "mrs_uav_model_step_buf_fuse4": list(_BUF_CASES),
 }
 
 
@@ -146,9 +152,11 @@ def test_fused_runs_equal_single_steps_with_six_and_eight_motors(M, monkeypatch,
 
 
 @pytest.mark.parametrize("arith", ARITHS)
-@pytest.mark.parametrize("n", [37, 64, 1000, N_SPLIT, N_BUF])
+@pytest.mark.parametrize("n", [37, 64, 1000, N_SPLIT, N_BUF, N_BUF_LAST, N_W3_FIRST])
 def test_fused_runs_equal_single_steps(M, monkeypatch, arith, n):
-    """tail lanes and one stream (n = 37, 64, 1000), two streams (1032 blocks; 1907 blocks, where FAST leaves the *_nt kernels);
+    """tail lanes and one stream (n = 37, 64, 1000), two streams (1032 blocks; 1907 blocks, where FAST leaves the *_nt kernels; 2048
+    full blocks, the last size at which a FAST step() is the two-wave *_buf kernel; 2049 blocks with a one-lane tail block, where it
+    is the three-wave *_buf_w3 and the fused launch stays the two-wave *_buf_fuseD);
     K = 1, 2, 3, D, D+1, 2D+1, 4D+3 one after the other on the same three swarms: every remainder depth, the single-step remainder, and
     from 1024 blocks on the switch to the two-stream form"""
     a, b, c = swarms(M, monkeypatch, n, arith_of(M, arith), 11 + n)
@@ -166,7 +174,7 @@ def test_fused_runs_equal_single_steps(M, monkeypatch, arith, n):
 
 
 @pytest.mark.parametrize("arith", ARITHS)
-@pytest.mark.parametrize("n", [1000, N_SPLIT])
+@pytest.mark.parametrize("n", [1000, N_SPLIT, N_BUF_LAST, N_W3_FIRST])
 def test_hold_vprev_takeoff_ground_force_and_crash(M, monkeypatch, arith, n):
     """UAVs on hold keep state and IMU; set_state right before the run (v_prev split); the take-off patch and the ground clamp UAVs
     first in the SECOND step of the fused launch; an external force; crashed UAVs"""
@@ -277,7 +285,7 @@ def test_nan_first_in_a_later_step_of_a_fused_launch(M, monkeypatch, arith):
 
 
 @pytest.mark.parametrize("arith", ARITHS)
-@pytest.mark.parametrize("n", [1000, N_SPLIT])
+@pytest.mark.parametrize("n", [1000, N_SPLIT, N_BUF_LAST, N_W3_FIRST])
 def test_run_directly_after_a_collision_tick(M, monkeypatch, arith, n):
     """the first step of the run carries the collision tick and stays a launch of its own, the rest fuse"""
     a, b, c = swarms(M, monkeypatch, n, arith_of(M, arith), 41)
@@ -294,7 +302,7 @@ def test_run_directly_after_a_collision_tick(M, monkeypatch, arith, n):
 
 
 @pytest.mark.parametrize("arith", ARITHS)
-@pytest.mark.parametrize("n", [900, N_SPLIT])
+@pytest.mark.parametrize("n", [900, N_SPLIT, N_BUF_LAST, N_W3_FIRST])
 def test_two_runs_back_to_back_then_a_single_step(M, monkeypatch, arith, n):
     a, b, c = swarms(M, monkeypatch, n, arith_of(M, arith), 51)
     seen = []

@@ -9,6 +9,7 @@ import pytest
 
 import helpers
 from helpers import RTOL_FAST, RTOL_LITERAL, RTOL_NORTH_STAR, Pair, random_state
+from step_regimes import N_BUF_LAST, N_CASCADE_BUF_FIRST, N_W3_FIRST, two_streams
 
 pytestmark = pytest.mark.gpu
 DT = 0.001
@@ -163,6 +164,39 @@ def test_run_equals_single_steps_position_cascade(M, arith, n):
     a, b = twin_swarms(M, n, arith_of(M, arith), 5, workload="position")
     run_both(a, b, 6)
     assert_same(a, b, f"position cascade, n={n}, {arith}")
+
+
+@pytest.mark.parametrize("arith", ARITHS)
+@pytest.mark.parametrize("workload,n", [("model", N_BUF_LAST), ("model", N_W3_FIRST), ("position", N_CASCADE_BUF_FIRST), ("position", N_W3_FIRST)])
+def test_run_equals_single_steps_in_the_two_wave_and_three_wave_regimes(M, monkeypatch, arith, workload, n):
+    """The kernels the cases above never run with MRS_OPT_IMU_DEAD set (sizes and regimes: step_regimes.py).  Model-only, 2048 full
+    blocks and 2049 blocks with a one-lane tail, MRS_RUN_FUSION=0 at creation so that the run's launches are the single-step kernels:
+    in FAST the two-wave *_model_step_buf and the three-wave *_model_step_buf_w3.  Position cascade (never fused), 901 blocks: FAST
+    has left mrs_uav_step_buf_nt for mrs_uav_step_buf, on one stream; 2049 blocks: mrs_uav_step_buf_w3, on two.  K = 7: from 1024 blocks
+    on the two-stream form.  Both sides of the comparison run the SAME instantiation, the run with the IMU stores of its first six
+    launches switched off: bit identity is owed in both flavours.  One block of UAVs on hold keeps the IMU it had."""
+    k = 7
+    if workload == "model":
+        monkeypatch.setenv("MRS_RUN_FUSION", "0")  # read when the swarm is created
+    a, b = twin_swarms(M, n, arith_of(M, arith), 10, workload="actuator" if workload == "model" else "position")
+    monkeypatch.delenv("MRS_RUN_FUSION", raising=False)
+    hold = slice(4 * 64 - 3, 5 * 64 + 3)  # block 4 entirely, and three lanes of each neighbour
+    for g in (a, b):
+        g.step_n(DT, 3)  # every UAV has an IMU value now
+        g.set_hold(hold.start, hold.stop - hold.start, True)
+    imu_before, st_before = a.get_imu(), a.get_state()
+    assert same(imu_before, b.get_imu()) and np.abs(imu_before[hold]).min(axis=1).max() > 0
+    a.set_profiling(1)
+    run_both(a, b, k)
+    v = assert_same(a, b, f"{workload}, n={n}, K={k}, {arith}")
+    assert a.last_step_kernel_ms()[1] == k, ("one launch per step", a.last_step_kernel_ms())
+    assert a.split_stats()[0] == (k if two_streams(n, k) else 0), a.split_stats()
+    assert same(v["imu"][hold], imu_before[hold]) and same(b.get_imu()[hold], imu_before[hold]), "a UAV on hold must keep its IMU over a run"
+    for f in ("x", "v", "R", "omega", "motor_rpm"):
+        assert same(v[f][hold], st_before[f][hold]), f"a UAV on hold must keep {f}"
+    moved = np.ones(n, bool)
+    moved[hold] = False
+    assert np.all(np.isfinite(v["imu"])) and (v["imu"][moved] != imu_before[moved]).any(axis=1).mean() > 0.9  # (scenario sanity: the others are stepped)
 
 
 @pytest.mark.parametrize("arith", ARITHS)

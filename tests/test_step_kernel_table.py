@@ -1,8 +1,10 @@
 """The step-kernel matrix stays complete: every entry point step_device.inc compiles has a row in
 test_step_variants_gpu.STEP_KERNELS naming the test that forces it, and no row names a kernel that no longer exists."""
+import importlib
 import os
 import re
 
+import step_regimes as R
 import test_step_variants_gpu as V
 
 SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mrs_multirotor_simulator_amd", "csrc",
@@ -42,6 +44,13 @@ def test_every_row_names_a_test_and_form_that_exist():
     for kernel, where in V.STEP_KERNELS.items():
         assert where, kernel
         for w in where:
+            if "::" in w:  # a case of another module: the module has that test, and the case names a size step_regimes.py names
+                m = re.fullmatch(r"(\w+)::(\w+)\[(?:(?:model|position)-)?(?:(\d+)-)?(literal|fast)\]", w)
+                assert m and callable(getattr(importlib.import_module(m.group(1)), m.group(2), None)), f"{kernel}: {w} names no test"
+                if m.group(3):
+                    cascade = "[position-" in w
+                    assert R.regime(int(m.group(3)), m.group(4) == "fast", cascade) == ("w3" if kernel.endswith("_w3") else "buf"), f"{kernel}: {w}"
+                continue
             m = re.match(r"(\w+)\[(\w+)\]", w)
             assert m and callable(getattr(V, m.group(1), None)), f"{kernel}: {w} is no test of test_step_variants_gpu"
             assert m.group(2) in forms[m.group(1)], f"{kernel}: {m.group(1)} has no form {m.group(2)}"

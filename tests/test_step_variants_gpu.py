@@ -36,16 +36,23 @@ REBOUNCE = 100.0
 TESTS = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(TESTS)
 
-# which test forces each entry point ("test[form]"; LITERAL / FAST noted where the launcher's choice differs between them)
+# which test forces each entry point ("test[form]"; LITERAL / FAST noted where the launcher's choice differs between them); a case of
+# another module is written "module::test[case]" - the three-wave kernels are also run at the sizes at which the launcher takes them
+# by itself (step_regimes.py), as the launches of a run on two streams with the IMU stores switched off, and against fused runs
+W3_IMU_CASE = "test_run_imu_elision_gpu::test_run_equals_single_steps_in_the_two_wave_and_three_wave_regimes"
 STEP_KERNELS = {
     "mrs_uav_step": ("test_single_gpu_variant[pointer]",),
-    "mrs_uav_step_buf": ("test_single_gpu_variant[default]  (LITERAL)", "test_single_gpu_variant[nt_off]  (FAST)"),
-    "mrs_uav_step_buf_w3": ("test_single_gpu_variant[three_waves]",),
+    "mrs_uav_step_buf": ("test_single_gpu_variant[default]  (LITERAL)", "test_single_gpu_variant[nt_off]  (FAST)",
+                         W3_IMU_CASE + "[position-57601-fast]"),
+    "mrs_uav_step_buf_w3": ("test_single_gpu_variant[three_waves]", W3_IMU_CASE + "[position-131073-fast]"),
     "mrs_uav_step_multi": ("test_single_gpu_variant[pointer]",),
     "mrs_uav_step_multi_buf": ("test_single_gpu_variant[default]",),
     "mrs_uav_model_step": ("test_single_gpu_variant[pointer]",),
-    "mrs_uav_model_step_buf": ("test_single_gpu_variant[default]  (LITERAL)", "test_single_gpu_variant[nt_off]  (FAST)"),
-    "mrs_uav_model_step_buf_w3": ("test_single_gpu_variant[three_waves]",),
+    "mrs_uav_model_step_buf": ("test_single_gpu_variant[default]  (LITERAL)", "test_single_gpu_variant[nt_off]  (FAST)",
+                               W3_IMU_CASE + "[model-131072-fast]"),
+    "mrs_uav_model_step_buf_w3": ("test_single_gpu_variant[three_waves]", W3_IMU_CASE + "[model-131073-fast]",
+                                  "test_run_fusion_gpu::test_fused_runs_equal_single_steps[131073-fast]",
+                                  "test_step_regimes_gpu::test_three_wave_single_steps_equal_the_fused_run[fast]"),
     "mrs_uav_model_step_buf_nt": ("test_single_gpu_variant[nt_on]  (LITERAL)", "test_single_gpu_variant[default]  (FAST)"),
     "mrs_uav_step_buf_nt": ("test_single_gpu_variant[nt_on]  (LITERAL)", "test_single_gpu_variant[default]  (FAST)"),
     "mrs_uav_model_step_multi": ("test_single_gpu_variant[pointer]",),
@@ -75,7 +82,7 @@ SINGLE_FORMS = {
 SHARDED_FORMS = ("split", "serial", "mixed", "model")
 POINTER_FORMS = ("pointer",)
 SWITCHES = ("MRS_THREE_WAVES", "MRS_NT_ACCESSES", "MRS_NO_BUFFER_ADDRESSING", "MRS_FORCE_MULTI", "MRS_SHARD_SPLIT",
-            "MRS_SHARD_SPLIT_MIN_BLOCKS", "MRS_SHARD_SPLIT_MAX_FRACTION", "MRS_NO_BOUNDARY_KERNEL", "MRS_INTERIOR_NT")
+            "MRS_SHARD_SPLIT_MIN_BLOCKS", "MRS_SHARD_SPLIT_MAX_FRACTION", "MRS_NO_BOUNDARY_KERNEL", "MRS_INTERIOR_NT", "MRS_RUN_FUSION")
 ARITHS = {"literal": 0, "fast": 1}  # mrs_multirotor_simulator_amd.ARITH_*
 AIRFRAMES3 = ("x500", "f550", "naki")
 N_MOTORS = {"x500": 4, "f550": 6, "naki": 8}
@@ -98,13 +105,15 @@ def _alive():
         pytest.fail(f"an earlier child process of this module died ({_dead[0]}): no further GPU process is started")
 
 
-def run_child(kind, form, env_extra, tmp_dir):
-    """child_main(kind, form) in a fresh process under the given launcher switches; its results as {key: array}"""
+def run_child(kind, form, env_extra, tmp_dir, module="test_step_variants_gpu"):
+    """child_main(kind, form) of `module` (a test module with an entry point of that name) in a fresh process under the given launcher
+    switches; its results as {key: array}.  One rule for every module that starts children through here: after a child that died
+    by a signal or timed out, nothing more is started on the GPU."""
     _alive()
     out = os.path.join(str(tmp_dir), f"{kind}_{form}.npz")
     env = {k: v for k, v in os.environ.items() if k not in SWITCHES}
     env.update(env_extra)
-    code = (f"import sys; sys.path[:0] = [{ROOT!r}, {TESTS!r}]; import test_step_variants_gpu as T; "
+    code = (f"import sys; sys.path[:0] = [{ROOT!r}, {TESTS!r}]; import {module} as T; "
             f"T.child_main({kind!r}, {form!r}, {out!r})")
     try:
         p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=CHILD_TIMEOUT)

@@ -817,6 +817,25 @@ public:
                           int32_t* dev_found = nullptr, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_obstacle_cost_device(s_, first, count, k, radius, kind, weight, dev_cost, accumulate ? 1 : 0, dev_found, stream));
   }
+  // range scans (mrs_swarm_set_scan_beams): the swarm's beam pattern, unit vectors (x, y, z) one after the other (an empty vector clears it)
+  void setScanBeams(const std::vector<double>& dirs) {
+    if (dirs.size() % 3 != 0) throw std::invalid_argument("setScanBeams: dirs holds whole (x, y, z) rows");
+    mrs_throw_on_error(mrs_swarm_set_scan_beams(s_, (int32_t)(dirs.size() / 3), dirs.data()));
+  }
+  std::vector<double> getScanBeams() const {
+    int32_t n = 0;
+    mrs_throw_on_error(mrs_swarm_get_scan_beams(s_, 0, nullptr, &n));
+    std::vector<double> out((size_t)n * 3);
+    if (n > 0) mrs_throw_on_error(mrs_swarm_get_scan_beams(s_, n, out.data(), &n));
+    return out;
+  }
+  // one range per beam of the pattern for UAVs [first, first + count), cast from the UAV's position against the static obstacles and,
+  // under MRS_SCAN_GROUND, the ground plane: row r of dev_ranges holds the ranges of UAV first + r (max_range: nothing closer), dev_hit
+  // (may be null) the obstacle index, MRS_SCAN_HIT_NONE or MRS_SCAN_HIT_GROUND; flags: MRS_SCAN_BODY_FRAME | MRS_SCAN_GROUND
+  void rangeScanDevice(int first, int count, double max_range, uint32_t flags, void* dev_ranges, int dtype, int stride, int32_t* dev_hit = nullptr,
+                       int hit_stride = 0, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_range_scan_device(s_, first, count, max_range, flags, dev_ranges, dtype, stride, dev_hit, hit_stride, stream));
+  }
   // collision worlds (mrs_swarm_set_worlds): UAVs interact through the collision pass, and appear in each other's nearest-neighbour rows,
   // only if their 32-bit labels are equal (0 until set); the labels of UAVs [first, first + worlds.size())
   void setWorlds(int first, const std::vector<int32_t>& worlds) {

@@ -657,6 +657,69 @@ int mrs_swarm_nearest_obstacles_device(mrs_swarm_t* s, int32_t first, int32_t co
 int mrs_swarm_obstacle_cost_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t k, double radius, int32_t kind, double weight,
                                    double* dev_cost, int32_t accumulate, int32_t* dev_found /* may be NULL, NOT capped by k */, void* ext_stream);
 
+/* ---- range scans: a pattern of beams per UAV cast against the static obstacles and the ground plane, one range per beam ----
+ * The observation of a perception-driven policy: a fixed angular layout with occlusion, which the k-nearest list above is not.  Beams see
+ * the obstacle set and the ground plane and nothing else (not other UAVs); they start at the UAV's position.
+ * The pattern belongs to the swarm, one for all its UAVs.  mrs_swarm_set_scan_beams replaces it by n_beams rows (bx, by, bz) after
+ * validating all of it on the host: n_beams in [0, MRS_SCAN_MAX_BEAMS] (0 clears the pattern); a non-NULL array when n_beams > 0; every
+ * row finite with |((bx*bx + by*by) + bz*bz) - 1.0| <= 1e-9 — beams are unit vectors, the kernel never normalises.  Anything else is
+ * MRS_ERR_ARG and changes nothing.  Ordering and ownership are those of mrs_swarm_set_obstacles: ordered behind earlier work on the
+ * swarm's stream, no simulation state written, a pending collision tick stays pending, legal on a sharded swarm (the scan is not);
+ * mrs_swarm_clone and mrs_swarm_clone_resized copy the pattern, mrs_swarm_destroy frees it, snapshots and mrs_swarm_copy_uavs do not
+ * touch it.  mrs_swarm_get_scan_beams: *n_beams (may not be NULL) receives the size of the pattern; the rows are copied to `out` when
+ * out != NULL, which then needs capacity >= that size in rows (MRS_ERR_ARG otherwise, *n_beams still written).
+ *
+ * mrs_swarm_range_scan_device: row r of dev_ranges holds the n_beams ranges of UAV first + r, FP64, or FP32 as the round-to-nearest cast
+ * of the FP64 value; stride >= n_beams elements, the slack [n_beams, stride) of a row is not touched.  dev_hit (may be NULL; int32 rows of
+ * hit_stride >= n_beams, slack untouched) holds per beam the index of the obstacle hit, MRS_SCAN_HIT_NONE (the range is then max_range)
+ * or MRS_SCAN_HIT_GROUND.
+ * Beam b of a UAV at p with attitude R (row-major) is p + t u, t >= 0, with u = b in the world frame, or under MRS_SCAN_BODY_FRAME
+ *     u_c = (R[c][0]*bx + R[c][1]*by) + R[c][2]*bz.
+ * Everything is FP64, one rounding per operation, no fused multiply-add; max and min are the comparisons of the static obstacles
+ * (max(a,b) := a < b ? b : a, min(a,b) := b < a ? b : a); every comparison below is written so that a NaN misses.
+ * Candidates of UAV i, stated without reference to any search structure: obstacle m is a candidate if it applies to i (the world rule of
+ * the static obstacles) and, with d = p - c, on every axis a:  |d_a| - hb_a < max_range, where hb is the half-extent of m's bounding box
+ * (sphere (r, r, r); box h; cylinder (r, r, hz)).  The gate only cuts hits that could not lie within max_range anyway; it is what makes
+ * the result independent of the grid (below).
+ * Range t_m of a candidate: the closed solid is entered at t_m >= 0, 0 when p lies in it or on its surface; otherwise a miss.
+ *   slab(d, u, h; enter, exit) — one axis of |d + t u| <= h:
+ *            u == 0.0:  miss if |d| > h, else no bound (no division, and no 0 * inf ever forms);
+ *            else t1 = (-h - d) / u;  t2 = (h - d) / u;  enter = max(enter, min(t1, t2));  exit = min(exit, max(t1, t2))
+ *   SPHERE   cc = (((dx*dx) + dy*dy) + dz*dz) - r*r;  cc <= 0.0 -> t = 0.0;
+ *            b = ((dx*ux) + dy*uy) + dz*uz;  not b < 0.0 -> miss;  disc = b*b - cc;  not disc >= 0.0 -> miss;
+ *            t = cc / (-b + sqrt(disc))                                               (the form without cancellation)
+ *   BOX      enter = 0.0, exit = +inf;  slab(dx, ux, h0), slab(dy, uy, h1), slab(dz, uz, h2) in this order;
+ *            enter <= exit -> t = enter, else miss
+ *   CYLINDER enter = 0.0, exit = +inf;  slab(dz, uz, hz)  (hz = +inf, uz == 0.0 tested first: the pillar);
+ *            a = (ux*ux) + uy*uy;  cc = ((dx*dx) + dy*dy) - r*r;
+ *            a == 0.0 (a vertical beam):  not cc <= 0.0 -> miss, else no bound;
+ *            else b = (dx*ux) + dy*uy;  disc = b*b - a*cc;  not disc >= 0.0 -> miss;  q = -b + sqrt(disc);
+ *                 cc <= 0.0:  exit = min(exit, q / a);
+ *                 else  not b < 0.0 -> miss;  enter = max(enter, cc / q);  exit = min(exit, q / a);
+ *            enter <= exit -> t = enter, else miss
+ * Selection: best = max_range, hit = MRS_SCAN_HIT_NONE; for the candidates in ascending obstacle index: t_m < best -> best = t_m,
+ * hit = m.  So a candidate hits only with t_m < max_range, strictly; the smallest range wins and among equal ranges the lowest index.
+ * Under MRS_SCAN_GROUND the plane z = ground_z of the UAV's airframe type (the value the rangefinder of mrs_swarm_get_outputs reads,
+ * whatever ground_enabled says) is considered last:  p_z <= ground_z -> t = 0.0;  else u_z < 0.0 -> t = (p_z - ground_z) / (-u_z);  else
+ * miss;  t < best -> best = t, hit = MRS_SCAN_HIT_GROUND (an obstacle at the same range keeps the beam).  A UAV with a non-finite
+ * position gets max_range and MRS_SCAN_HIT_NONE on every beam.
+ * The search structure is the grid of the static obstacles built for radius = max_range, in a cache entry of the scans' own (one
+ * entry, kept until max_range changes or the set is replaced; a loop that alternates obstacle_cost(radius) with range_scan(max_range)
+ * builds two grids, not one per call).  The cell that contains p lists every candidate: the gate is the per-axis inequality the grid's
+ * coverage proof passes through.  mrs_swarm_obstacle_stats keeps describing the queries' grid; grid_builds counts both.
+ * Entry, stream fence and NULL rules are those of mrs_swarm_nearest_obstacles_device: a pending collision tick stays pending and the
+ * simulation is left bit for bit as it was; an empty obstacle set is legal.  Every argument is checked before any launch and a refused
+ * call changes nothing: the range MRS_ERR_RANGE; MRS_ERR_ARG for no pattern set, a max_range that is not finite and > 0, unknown flag
+ * bits, a bad dtype, strides below n_beams, a NULL dev_ranges, a dev_ranges or dev_hit that is not device memory of the swarm's device
+ * holding the rows, count * n_beams above 2^39 (one launch), and a sharded swarm; count == 0 is MRS_OK. */
+enum { MRS_SCAN_MAX_BEAMS = 4096 };
+enum { MRS_SCAN_BODY_FRAME = 1u << 0, MRS_SCAN_GROUND = 1u << 1 }; /* flags of mrs_swarm_range_scan_device */
+enum { MRS_SCAN_HIT_NONE = -1, MRS_SCAN_HIT_GROUND = -2 };         /* values of dev_hit besides obstacle indices */
+int mrs_swarm_set_scan_beams(mrs_swarm_t* s, int32_t n_beams, const double* dirs /* n_beams x 3 */);
+int mrs_swarm_get_scan_beams(const mrs_swarm_t* s, int32_t capacity, double* out, int32_t* n_beams);
+int mrs_swarm_range_scan_device(mrs_swarm_t* s, int32_t first, int32_t count, double max_range, uint32_t flags, void* dev_ranges, int32_t dtype,
+                                int32_t stride, int32_t* dev_hit /* may be NULL */, int32_t hit_stride, void* ext_stream);
+
 /* ---- collision worlds: several scenes in one swarm that do not see each other (per-sample horizons of a sampling-based planner) ----
  * A world is a 32-bit label per UAV, 0 for every UAV until a setter says otherwise.  Two UAVs interact through the collision pass
  * (mrs_swarm_handle_collisions, mrs_swarm_tick_n, the tick rollouts), or appear in each other's rows of mrs_swarm_nearest_device, only

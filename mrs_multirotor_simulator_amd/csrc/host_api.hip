@@ -566,6 +566,7 @@ int mrs_swarm_destroy(mrs_swarm_t* s) {
   peer_release(s);  // closes the peers' windows mapped here
   mrs_collide_free(s->cwork);
   mrs_obstacles_free(s->obst);
+  mrs_scan_beams_free(s->scan);
   delete s;
   return MRS_OK;
 }
@@ -932,6 +933,10 @@ int mrs_swarm_clone_resized(mrs_swarm_t* s, int32_t n_uavs, mrs_swarm_t** out) {
     c->worlds_nonzero = s->worlds_nonzero;
   }
   if ((rc = obstacles_copy(c, s))) {  // the obstacle set belongs to the swarm: the copy gets its own
+    mrs_swarm_destroy(c);
+    return rc;
+  }
+  if ((rc = scan_beams_copy(c, s))) {  // ... and so does the beam pattern of the range scans
     mrs_swarm_destroy(c);
     return rc;
   }

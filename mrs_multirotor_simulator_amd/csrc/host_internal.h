@@ -6,7 +6,9 @@
 //   device_io.hip         C ABI + kernels for device-resident callers: commands, observations, resets, crash flags in device rows
 //   nearest.hip           C ABI + kernels of the k-nearest-neighbour observations for device-resident callers
 //   obstacles.hip         C ABI + kernels of the static obstacles (the set, nearest-obstacle rows, the obstacle cost); obstacle_grid.h
-//                         holds its pure host functions (tested without a GPU: tests/cpp/obstacle_grid_test.cpp)
+//                         holds its pure host functions (tested without a GPU: tests/cpp/obstacle_grid_test.cpp); obstacle_set.h the set
+//   range_scan.hip        C ABI + kernel of the range scans (the beam pattern, the scan); range_scan_math.h holds its pure functions
+//                         (tested without a GPU: tests/cpp/range_scan_math_test.cpp)
 //   snapshot.hip          C ABI + kernels of the state snapshots (save / indexed load of whole per-UAV records) for device-resident callers
 //   transport_rccl.hip    RCCL bound at run time (dlopen)
 //   transport_local.hip   in-process loopback group, caller-supplied all-gather, measurement stand-in (with its kernels)
@@ -135,6 +137,9 @@ extern "C" hipError_t mrs_collide_latch_force(SwarmDev sw, CollideWork* w, int p
 // ---- obstacles.hip: the obstacle set of a swarm (host copy, device copy, cached grid) ----
 struct ObstacleSet;
 extern "C" void       mrs_obstacles_free(ObstacleSet* o);
+// ---- range_scan.hip: the beam pattern of a swarm (host copy, device copy) ----
+struct ScanBeams;
+extern "C" void       mrs_scan_beams_free(ScanBeams* b);
 // ---- outputs.hip ----
 extern "C" hipError_t mrs_launch_timeout_input(SwarmDev sw, int first, int count, hipStream_t st);
 extern "C" hipError_t mrs_launch_unpack_rows(SwarmDev sw, const double* rows, int stride, int width, int base, int first, int count, hipStream_t st);
@@ -322,6 +327,8 @@ struct mrs_swarm {
   DevBuf<void> nn_buf;  // (counts bytes)
   // static obstacles (obstacles.hip): allocated by the first setter or query; copied by clone, freed by mrs_swarm_destroy
   ObstacleSet* obst = nullptr;
+  // beam pattern of the range scans (range_scan.hip): allocated by the first setter; copied by clone, freed by mrs_swarm_destroy
+  ScanBeams* scan = nullptr;
   // collision scratch
   DevBuf<PosRecord> dRec;
   CollideWork* cwork = nullptr;
@@ -488,6 +495,8 @@ int    launch_crashed_u8(mrs_swarm* s, int first, int count, uint8_t* dev_out); 
 int    launch_crash_cost(mrs_swarm* s, int first, int count, double* dev_cost, double crash_cost);  // cost[k] += crash_cost where crashed
 // ---- obstacles.hip ----
 int    obstacles_copy(mrs_swarm* dst, const mrs_swarm* src);  // the set of src into dst (clone)
+// ---- range_scan.hip ----
+int    scan_beams_copy(mrs_swarm* dst, const mrs_swarm* src);  // the beam pattern of src into dst (clone)
 // ---- transports (transport_*.hip) and the communicator bookkeeping (tick_sharded.hip) ----
 int  rccl_load(const char* path);
 int  rccl_check(int rc, const char* what);

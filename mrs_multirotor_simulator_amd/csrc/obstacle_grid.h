@@ -102,7 +102,7 @@ MRS_OBST_HD double eval(const mrs_obstacle_t& o, const double p[3], double rel[3
 }
 
 // half-extents of the bounding box of o
-inline void half_extents(const mrs_obstacle_t& o, double h[3]) {
+MRS_OBST_HD void half_extents(const mrs_obstacle_t& o, double h[3]) {
   if (o.kind == MRS_OBST_BOX)
     h[0] = o.h[0], h[1] = o.h[1], h[2] = o.h[2];
   else if (o.kind == MRS_OBST_SPHERE)

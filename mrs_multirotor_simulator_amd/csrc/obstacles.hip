@@ -8,16 +8,8 @@
 // Nothing here writes simulation state; the calls enter like mrs_swarm_nearest_device (a pending collision tick stays pending).
 #include "host_internal.h"
 #include "obstacle_grid.h"
+#include "obstacle_set.h"
 #include "pose_math.h"
-
-struct ObstacleSet {
-  std::vector<mrs_obstacle_t> host;  // the set as given (get_obstacles, clone, the grid builder)
-  DevBuf<mrs_obstacle_t>      dev;
-  mrs_obst::Built             grid;  // the cached grid: its vectors are the source of the upload and live until the next build
-  bool                        grid_ok = false;
-  DevBuf<int32_t>             d_start, d_items;
-  int64_t                     builds = 0;
-};
 
 namespace {
 
@@ -229,6 +221,7 @@ int adopt(mrs_swarm* s, const mrs_obstacle_t* obstacles, int32_t count) {
   }
   o->host.swap(fresh);
   o->grid_ok = false;
+  o->scan.ok = false;  // (the range scans' grid served the old set too)
   return MRS_OK;
 }
 

@@ -137,6 +137,7 @@ ABI_SYMBOLS = [
     "mrs_swarm_proximity_cost_device",
     "mrs_swarm_set_obstacles", "mrs_swarm_get_obstacles", "mrs_swarm_obstacle_stats", "mrs_obstacle_width",
     "mrs_swarm_nearest_obstacles_device", "mrs_swarm_obstacle_cost_device",
+    "mrs_swarm_set_scan_beams", "mrs_swarm_get_scan_beams", "mrs_swarm_range_scan_device",
 ]
 
 # device-resident callers (mrs_swarm_*_device): row element types and the observation groups of mrs_swarm_gather_device, in bit order
@@ -157,6 +158,10 @@ OBST_MAX, OBST_MAX_K = 1 << 20, 32
 ON_REL, ON_REL_BODY, ON_DIST = (1 << b for b in range(3))
 ON_ALL = 7
 OBSTACLE_DTYPE = np.dtype([("kind", "i4"), ("world", "i4"), ("flags", "u4"), ("reserved", "u4"), ("c", "f8", 3), ("h", "f8", 3)])  # mrs_obstacle_t, 64 B
+# range scans (mrs_swarm_range_scan_device): the pattern's limit, the flags, and the values of a hit row besides obstacle indices
+SCAN_MAX_BEAMS = 4096
+SCAN_BODY_FRAME, SCAN_GROUND = 1, 2
+SCAN_HIT_NONE, SCAN_HIT_GROUND = -1, -2
 # state snapshots (mrs_swarm_save_device / mrs_swarm_load_device): one mrs_uav_snapshot_t record per UAV, 496 B
 SNAP_CRASHED, SNAP_TAKEOFF, SNAP_VPREV_SPLIT = 1, 2, 4
 SNAP_MAGIC = 0x50414E53
@@ -394,6 +399,9 @@ def load_library():
         "mrs_obstacle_width": [C.c_uint32, i32, ip],
         "mrs_swarm_nearest_obstacles_device": [vp, i32, i32, i32, C.c_double, C.c_uint32, vp, i32, i32, vp, i32, vp, vp],
         "mrs_swarm_obstacle_cost_device": [vp, i32, i32, i32, C.c_double, i32, C.c_double, vp, i32, vp, vp],
+        "mrs_swarm_set_scan_beams": [vp, i32, vp],
+        "mrs_swarm_get_scan_beams": [vp, i32, vp, ip],
+        "mrs_swarm_range_scan_device": [vp, i32, i32, C.c_double, C.c_uint32, vp, i32, i32, vp, i32, vp],
         "mrs_swarm_save_device": [vp, i32, i32, vp, vp],
         "mrs_swarm_load_device": [vp, i32, i32, vp, C.c_int64, vp, vp, vp],
         "mrs_swarm_rollout_device": [vp, i32, i32, i32, C.c_double, i32, vp, i32, i32, C.c_uint32, vp, i32, vp],
@@ -936,6 +944,30 @@ class Swarm:
         _check(_lib.mrs_swarm_obstacle_cost_device(self._h, int(first), int(count), int(k), C.c_double(float(radius)), int(kind),
                                                    C.c_double(float(weight)), dev_cost or None, int(bool(accumulate)), dev_found or None,
                                                    ext_stream or None))
+
+    def set_scan_beams(self, dirs):
+        """Replaces the swarm's beam pattern of the range scans (mrs_swarm_set_scan_beams): an [n_beams, 3] array of unit vectors (or
+        None / an empty one: no pattern).  One pattern for all UAVs; range_scan_device casts it."""
+        a = np.zeros((0, 3)) if dirs is None else np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        _check(_lib.mrs_swarm_set_scan_beams(self._h, int(len(a)), a.ctypes.data_as(C.c_void_p) if len(a) else None))
+
+    def scan_beam_count(self):
+        """beams of the pattern (0: none set): one call, nothing copied"""
+        n = C.c_int32()
+        _check(_lib.mrs_swarm_get_scan_beams(self._h, 0, None, C.byref(n)))
+        return n.value
+
+    def get_scan_beams(self):
+        n = self.scan_beam_count()
+        out = np.zeros((n, 3))
+        if n:
+            _check(_lib.mrs_swarm_get_scan_beams(self._h, n, out.ctypes.data_as(C.c_void_p), C.byref(C.c_int32())))
+        return out
+
+    def range_scan_device(self, first, count, max_range, flags, dev_ranges, dtype, stride, dev_hit, hit_stride, ext_stream):
+        _check(_lib.mrs_swarm_range_scan_device(self._h, int(first), int(count), C.c_double(float(max_range)), C.c_uint32(int(flags)),
+                                                dev_ranges or None, int(dtype), int(stride), dev_hit or None, int(hit_stride),
+                                                ext_stream or None))
 
     def save_device(self, first, count, dev_records, ext_stream):
         _check(_lib.mrs_swarm_save_device(self._h, int(first), int(count), dev_records or None, ext_stream or None))

@@ -17,7 +17,7 @@ from .swarm import (ACTUATOR_CMD, ATTITUDE_CMD, DTYPE_F32, DTYPE_F64, INPUT_UNKN
                     OBS_RPM, OBS_VEL, OBS_VEL_BODY, PROX_COUNT, PROX_HINGE2, PROX_INVERSE, SNAP_BAD_AIRFRAME, SNAP_BAD_INDEX, SNAP_BAD_MAGIC, SNAP_CRASHED, SNAP_LOADED,
                     SNAP_MAGIC, SNAP_SKIPPED, SNAP_TAKEOFF, SNAP_VPREV_SPLIT, SNAPSHOT_DTYPE, TILT_HDG_RATE_CMD, gather_width, nearest_width,
                     OBST_ALL_WORLDS, OBST_BOX, OBST_CYLINDER, OBST_MAX, OBST_MAX_K, OBST_SPHERE, OBSTACLE_DTYPE, ON_ALL, ON_DIST, ON_REL, ON_REL_BODY,
-                    obstacle_width)
+                    SCAN_BODY_FRAME, SCAN_GROUND, SCAN_HIT_GROUND, SCAN_HIT_NONE, SCAN_MAX_BEAMS, obstacle_width)
 
 _DTYPES = {torch.float64: DTYPE_F64, torch.float32: DTYPE_F32}
 SNAP_BYTES = SNAPSHOT_DTYPE.itemsize  # 496: one mrs_uav_snapshot_t
@@ -628,6 +628,88 @@ def obstacle_cost(swarm, radius, k=8, kind=PROX_HINGE2, weight=1.0, first=0, cou
         fptr = found.data_ptr()
     swarm.obstacle_cost_device(first, count, k, radius, kind, weight, out.data_ptr(), bool(accumulate), fptr, _stream(dev))
     return out, found
+
+
+def scan_ring(n, elevation=0.0):
+    """n unit vectors [n, 3] (numpy, FP64) evenly spaced in azimuth, beam 0 along +x, counter-clockwise seen from above, all at
+    `elevation` radians above the xy plane: a planar lidar's pattern for set_scan_beams()."""
+    import numpy as np
+    if n < 1:
+        raise ValueError(f"scan_ring needs n >= 1, got {n}")
+    az = 2.0 * np.pi * np.arange(n) / n
+    return _unit(np.stack([np.cos(az) * np.cos(elevation), np.sin(az) * np.cos(elevation), np.full(n, np.sin(elevation))], axis=1))
+
+
+def scan_grid(n_h, n_v, fov_h, fov_v):
+    """n_v rows of n_h unit vectors [n_v * n_h, 3] (numpy, FP64) around +x: azimuths evenly spaced over [-fov_h / 2, fov_h / 2] (left
+    to right: descending azimuth), elevations over [fov_v / 2, -fov_v / 2] (top row first), radians; a single column or row looks
+    straight ahead.  A depth camera's pattern for set_scan_beams(), row-major like an image."""
+    import numpy as np
+    if n_h < 1 or n_v < 1:
+        raise ValueError(f"scan_grid needs n_h >= 1 and n_v >= 1, got {n_h} x {n_v}")
+    az = np.linspace(fov_h / 2.0, -fov_h / 2.0, n_h) if n_h > 1 else np.zeros(1)
+    el = np.linspace(fov_v / 2.0, -fov_v / 2.0, n_v) if n_v > 1 else np.zeros(1)
+    el, az = (a.reshape(-1) for a in np.meshgrid(el, az, indexing="ij"))
+    return _unit(np.stack([np.cos(az) * np.cos(el), np.sin(az) * np.cos(el), np.sin(el)], axis=1))
+
+
+def _unit(v):
+    """rows of v over their norms (what cos and sin leave is a few ulps from 1: far inside the setter's 1e-9)"""
+    import numpy as np
+    return v / np.sqrt((v * v).sum(axis=1, keepdims=True))
+
+
+def set_scan_beams(swarm, dirs):
+    """Replaces the swarm's beam pattern of the range scans (mrs_swarm_set_scan_beams): dirs [B, 3], unit vectors (a tensor of any
+    device, or an array; scan_ring() and scan_grid() make some).  One pattern for every UAV, B <= SCAN_MAX_BEAMS; B = 0 clears it.
+    Rows that are not finite or whose squared norm differs from 1 by more than 1e-9 are refused: range_scan() never normalises."""
+    import numpy as np
+    d = _host_array(dirs, "dirs", np.float64, (-1, 3))
+    if len(d) > SCAN_MAX_BEAMS:
+        raise ValueError(f"{len(d)} beams: at most {SCAN_MAX_BEAMS}")
+    if not np.isfinite(d).all():
+        raise ValueError("dirs must be finite")
+    with np.errstate(over="ignore"):
+        if (np.abs(((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]) - 1.0) > 1e-9).any():
+            raise ValueError("dirs must be unit vectors (squared norm within 1e-9 of 1)")
+    swarm.set_scan_beams(d)
+
+
+def range_scan(swarm, max_range, body_frame=True, ground=False, first=0, count=None, dtype=torch.float32, out=None, hits=None):
+    """One range per beam of the swarm's pattern (set_scan_beams) for each UAV of [first, first + count), cast from the UAV's position
+    against the static obstacles that apply to it and, with ground=True, the ground plane of its airframe
+    (mrs_swarm_range_scan_device).  body_frame: the beams turn with the UAV's attitude (else they are world directions).  Returns
+    (ranges, hits): ranges [count, B] of `dtype` (max_range where nothing is hit closer than that), hits int32 [count, B] (the obstacle
+    index, SCAN_HIT_NONE or SCAN_HIT_GROUND) when hits=True or a tensor is given, else None.  `out` and `hits` are used instead of new
+    tensors when given; columns past B are left alone.  No simulation state is written; a pending collision tick stays pending."""
+    import math
+    count = _count(swarm, first, count)
+    dev = swarm.device()
+    tdev = torch.device("cuda", dev)
+    try:
+        max_range = float(max_range)  # (numpy scalars and one-element tensors too)
+    except (TypeError, ValueError):
+        raise ValueError(f"max_range must be a finite number > 0, got {max_range!r}") from None
+    if not (math.isfinite(max_range) and max_range > 0):
+        raise ValueError(f"max_range must be a finite number > 0, got {max_range!r}")
+    nb = swarm.scan_beam_count()
+    if nb == 0:
+        raise ValueError("no beam pattern set: call set_scan_beams() first")
+    if out is None:
+        out = torch.empty((count, nb), dtype=dtype, device=tdev)
+    code = _dtype_code(out.dtype)
+    stride = check_tensor(out, count, nb, out.dtype, dev)
+    hptr, hstride = 0, 0
+    if hits is True:
+        hits = torch.empty((count, nb), dtype=torch.int32, device=tdev)
+    if hits is False or hits is None:
+        hits = None
+    else:
+        hstride = check_tensor(hits, count, nb, torch.int32, dev)
+        hptr = hits.data_ptr()
+    flags = (SCAN_BODY_FRAME if body_frame else 0) | (SCAN_GROUND if ground else 0)
+    swarm.range_scan_device(first, count, max_range, flags, out.data_ptr(), code, stride, hptr, hstride, _stream(dev))
+    return (out[:, :nb] if out.shape[1] > nb else out), (None if hits is None else hits[:, :nb] if hits.shape[1] > nb else hits)
 
 
 def set_worlds(swarm, worlds, first=0):

@@ -836,6 +836,13 @@ public:
                        int hit_stride = 0, void* stream = nullptr) {
     mrs_throw_on_error(mrs_swarm_range_scan_device(s_, first, count, max_range, flags, dev_ranges, dtype, stride, dev_hit, hit_stride, stream));
   }
+  // the same scan that also sees the other UAVs of each observer's world as closed spheres of radius arm_length + prop_radius: dev_hit
+  // holds MRS_UAVSCAN_HIT_UAV where a UAV took the beam, dev_uav (may be null; int32 rows of uav_stride) that UAV's index, -1 elsewhere
+  void rangeScanUavsDevice(int first, int count, double max_range, uint32_t flags, void* dev_ranges, int dtype, int stride, int32_t* dev_hit = nullptr,
+                           int hit_stride = 0, int32_t* dev_uav = nullptr, int uav_stride = 0, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_range_scan_uavs_device(s_, first, count, max_range, flags, dev_ranges, dtype, stride, dev_hit, hit_stride, dev_uav,
+                                                        uav_stride, stream));
+  }
   // collision worlds (mrs_swarm_set_worlds): UAVs interact through the collision pass, and appear in each other's nearest-neighbour rows,
   // only if their 32-bit labels are equal (0 until set); the labels of UAVs [first, first + worlds.size())
   void setWorlds(int first, const std::vector<int32_t>& worlds) {

@@ -720,6 +720,41 @@ int mrs_swarm_get_scan_beams(const mrs_swarm_t* s, int32_t capacity, double* out
 int mrs_swarm_range_scan_device(mrs_swarm_t* s, int32_t first, int32_t count, double max_range, uint32_t flags, void* dev_ranges, int32_t dtype,
                                 int32_t stride, int32_t* dev_hit /* may be NULL */, int32_t hit_stride, void* ext_stream);
 
+/* ---- range scans that see other UAVs: the scan above, and every other UAV of the observer's world as a closed sphere ----
+ * In a swarm, what most often fills a UAV's lidar is another UAV.  mrs_swarm_range_scan_uavs_device is mrs_swarm_range_scan_device (same
+ * pattern, same beams, same obstacles, same ground, same rows) with the UAVs considered between the obstacles and the ground; the old call
+ * stays what it is.  Arguments, checks, their order and their messages are those of mrs_swarm_range_scan_device (the function name
+ * aside): the range, not on a sharded swarm, a pattern set, max_range finite and > 0, flags within MRS_SCAN_BODY_FRAME | MRS_SCAN_GROUND,
+ * dtype, stride, dev_hit / hit_stride; then dev_uav (may be NULL, also where dev_hit is given, and given where dev_hit is NULL): int32
+ * rows of uav_stride >= n_beams, slack untouched, per beam the index of the UAV hit or -1; one launch holds count * ceil(n_beams / 64)
+ * < 2^31 blocks; count == 0 is MRS_OK after the checks; dev_ranges, dev_hit and dev_uav must be device memory of the swarm's device
+ * holding their rows.  A refused call changes nothing.
+ * What a UAV is to a beam: UAV j is the closed sphere centred at its position p_j with radius rad_j = arm_length + prop_radius of its
+ * airframe type (one rounded FP64 addition: the prefix (marm + mprop) of the collision criterion), read from the airframe table, which is
+ * brought up to date before the launch.
+ * Candidates of observer i, stated without reference to any search structure: every UAV j of the swarm (all n of them, not only those of
+ * [first, first + count)) with j != i, world[j] == world[i] (all 0 when no label was ever set) and, on every axis a,
+ *     |p_i[a] - p_j[a]| - rad_j < max_range
+ * — the gate of the range scans applied to the sphere record {MRS_OBST_SPHERE, c = p_j, h[0] = rad_j}.  A non-finite p_j fails it by
+ * itself (every comparison is written so that a NaN misses).  Crashed UAVs are seen like any other.
+ * Range t_j of a candidate: the SPHERE lines of the range scans for that record, from p_i along the beam direction u formed as above;
+ * 0.0 when p_i lies in or on the sphere, otherwise possibly a miss.
+ * Selection per beam: (1) the obstacles exactly as above: best = max_range, hit = MRS_SCAN_HIT_NONE, ascending index, strict <.
+ * (2) Among the candidate UAVs the lexicographic minimum of (t_j, j) (a NaN t_j never taken); it takes the beam only if t_j < best,
+ * strictly — an obstacle at the same range keeps the beam: best = t_j, hit = MRS_UAVSCAN_HIT_UAV, uav = j.  (3) Under MRS_SCAN_GROUND the
+ * plane as above: t < best -> best = t, hit = MRS_SCAN_HIT_GROUND, uav = -1.  dev_uav is -1 wherever hit != MRS_UAVSCAN_HIT_UAV.  An
+ * observer with a non-finite position gets max_range, MRS_SCAN_HIT_NONE and -1 on every beam.  The range is FP64, or its
+ * round-to-nearest FP32 cast.
+ * The search structures are the scans' cached obstacle grid and the hash of mrs_swarm_nearest_device built for radius = max_range +
+ * the largest rad of the swarm's airframe table, in the scratch that call uses; the kernel applies j != i, world equality and the gate
+ * literally to what the 27 buckets around the observer's cell list, so the result depends on neither.
+ * Effect on the simulation: none.  Entry and stream fence are those of mrs_swarm_range_scan_device: a pending collision tick stays
+ * pending, the caller's stream is fenced in and out, and a horizon cut at this call is the uncut horizon bit for bit. */
+enum { MRS_UAVSCAN_HIT_UAV = -3 }; /* value of dev_hit besides those of the range scans */
+int mrs_swarm_range_scan_uavs_device(mrs_swarm_t* s, int32_t first, int32_t count, double max_range, uint32_t flags, void* dev_ranges,
+                                     int32_t dtype, int32_t stride, int32_t* dev_hit /* may be NULL */, int32_t hit_stride,
+                                     int32_t* dev_uav /* may be NULL */, int32_t uav_stride, void* ext_stream);
+
 /* ---- collision worlds: several scenes in one swarm that do not see each other (per-sample horizons of a sampling-based planner) ----
  * A world is a 32-bit label per UAV, 0 for every UAV until a setter says otherwise.  Two UAVs interact through the collision pass
  * (mrs_swarm_handle_collisions, mrs_swarm_tick_n, the tick rollouts), or appear in each other's rows of mrs_swarm_nearest_device, only

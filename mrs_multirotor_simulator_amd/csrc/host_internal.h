@@ -9,6 +9,8 @@
 //                         holds its pure host functions (tested without a GPU: tests/cpp/obstacle_grid_test.cpp); obstacle_set.h the set
 //   range_scan.hip        C ABI + kernel of the range scans (the beam pattern, the scan); range_scan_math.h holds its pure functions
 //                         (tested without a GPU: tests/cpp/range_scan_math_test.cpp)
+//   range_scan_uavs.hip   C ABI + kernel of the range scans that also see the other UAVs of the observer's world (the hash of nearest.hip,
+//                         read through nn_hash.h, joined with the ray tests of range_scan_math.h)
 //   snapshot.hip          C ABI + kernels of the state snapshots (save / indexed load of whole per-UAV records) for device-resident callers
 //   transport_rccl.hip    RCCL bound at run time (dlopen)
 //   transport_local.hip   in-process loopback group, caller-supplied all-gather, measurement stand-in (with its kernels)
@@ -140,6 +142,10 @@ extern "C" void       mrs_obstacles_free(ObstacleSet* o);
 // ---- range_scan.hip: the beam pattern of a swarm (host copy, device copy) ----
 struct ScanBeams;
 extern "C" void       mrs_scan_beams_free(ScanBeams* b);
+// ---- nn_hash.h: what a kernel reads of the hash nearest.hip builds ----
+namespace mrs_nn {
+struct NnHash;
+}
 // ---- outputs.hip ----
 extern "C" hipError_t mrs_launch_timeout_input(SwarmDev sw, int first, int count, hipStream_t st);
 extern "C" hipError_t mrs_launch_unpack_rows(SwarmDev sw, const double* rows, int stride, int width, int base, int first, int count, hipStream_t st);
@@ -497,6 +503,11 @@ int    launch_crash_cost(mrs_swarm* s, int first, int count, double* dev_cost, d
 int    obstacles_copy(mrs_swarm* dst, const mrs_swarm* src);  // the set of src into dst (clone)
 // ---- range_scan.hip ----
 int    scan_beams_copy(mrs_swarm* dst, const mrs_swarm* src);  // the beam pattern of src into dst (clone)
+int32_t       scan_beam_count(const mrs_swarm* s);             // beams of the pattern (0: none set)
+const double* scan_beams_dev(const mrs_swarm* s);              // its device copy, n_beams x 3
+int    scan_grid(mrs_swarm* s, double max_range);              // the scans' cached obstacle grid (s->obst->scan) made current for max_range
+// ---- nearest.hip: the per-call hash of the UAV positions for another unit's kernel (nn_hash.h) ----
+int    nn_hash(mrs_swarm* s, double radius, hipStream_t ext, mrs_nn::NnHash* out);  // fences ext in, builds in nn_buf on the swarm's stream
 // ---- transports (transport_*.hip) and the communicator bookkeeping (tick_sharded.hip) ----
 int  rccl_load(const char* path);
 int  rccl_check(int rc, const char* what);

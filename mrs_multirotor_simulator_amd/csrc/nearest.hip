@@ -24,22 +24,19 @@
 #include <string.h>
 
 #include "host_internal.h"
+#include "nn_hash.h"
 #include "pose_math.h"
 
 namespace {
 
+// the record, the cell coordinate, the bucket hash and the bucket starts: nn_hash.h (range_scan_uavs.hip probes the same hash)
+using namespace mrs_nn;
+
 constexpr int    NN_BLOCK   = 256;
 constexpr int    SCAN_PER   = 8;                      // counts per lane of the chunk scan
-constexpr int    SCAN_CH    = NN_BLOCK * SCAN_PER;    // 2048 counts per chunk
-constexpr int    SCAN_LOG   = 11;
-constexpr double CELL_LIMIT = 1073741824.0;           // 2^30: clamped cell coordinates, +-1 stays inside int32
-constexpr double CELL_MARGIN = 1e-6;                  // edge = radius (1 + margin): covers the rounding of x * inv_edge up to |x * inv_edge| = 2^30
+constexpr int    SCAN_CH    = NN_BLOCK * SCAN_PER;    // 2048 counts per chunk (1 << SCAN_LOG)
+static_assert(SCAN_CH == 1 << SCAN_LOG, "bucket_begin adds the chunk total of bucket b >> SCAN_LOG");
 constexpr int    kNnWidth[5] = {3, 3, 3, 3, 1};
-
-struct NnRec {  // one sorted record: position, global index and world label (32 B)
-  double  x, y, z;
-  int32_t idx, pad;  // pad: the world label (0 when the swarm has none)
-};
 
 struct NnArgs {
   const double* S;
@@ -54,41 +51,6 @@ struct NnArgs {
   int32_t       index_stride;
   int32_t*      counts;
 };
-
-__device__ __forceinline__ int cell_coord(double x, double inv_edge) {
-  const double c = floor(x * inv_edge);  // (+-inf for an overflowing product: clamped like any far cell)
-  return (int)fmin(fmax(c, -CELL_LIMIT), CELL_LIMIT);
-}
-
-// wm: a mixed image of the world label (0 for label 0 and for swarms without labels: the hash they always had)
-__device__ __forceinline__ uint32_t world_mix(uint32_t w) {
-  w *= 0x9E3779B1u;
-  w ^= w >> 16;
-  w *= 0x85EBCA6Bu;
-  w ^= w >> 13;
-  return w;
-}
-// A world-aware kernel is the same kernel template with the label column as a trailing argument pack of one: the instantiation with the
-// empty pack has the arguments and the code it always had.
-__device__ __forceinline__ const uint32_t* world_labels() { return nullptr; }
-__device__ __forceinline__ const uint32_t* world_labels(const uint32_t* p) { return p; }
-__device__ __forceinline__ uint32_t bucket_of(int cx, int cy, int cz, uint32_t tmask) {
-  uint32_t h = ((uint32_t)cx * 73856093u) ^ ((uint32_t)cy * 19349663u) ^ ((uint32_t)cz * 83492791u);
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  return h & tmask;
-}
-__device__ __forceinline__ uint32_t bucket_of(int cx, int cy, int cz, uint32_t tmask, uint32_t wm) {  // (world-aware)
-  uint32_t h = ((uint32_t)cx * 73856093u) ^ ((uint32_t)cy * 19349663u) ^ ((uint32_t)cz * 83492791u) ^ wm;
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  return h & tmask;
-}
-template <bool WORLDS> __device__ __forceinline__ uint32_t bucket_of_x(int cx, int cy, int cz, uint32_t tmask, uint32_t wm) {
-  if constexpr (WORLDS) return bucket_of(cx, cy, cz, tmask, wm); else return bucket_of(cx, cy, cz, tmask);
-}
 
 __device__ __forceinline__ bool finite3(double x, double y, double z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
@@ -166,8 +128,6 @@ __global__ void __launch_bounds__(NN_BLOCK) k_nn_scan_top(int32_t* bsum, int nch
     carry += total;
   }
 }
-
-__device__ __forceinline__ int bucket_begin(const int32_t* start, const int32_t* bsum, uint32_t b) { return start[b] + bsum[b >> SCAN_LOG]; }
 
 template <class... W>
 __global__ void __launch_bounds__(NN_BLOCK) k_nn_scatter(const double* S, int n, int npad, const int32_t* rank, const int32_t* bkt,
@@ -599,6 +559,24 @@ int nn_build_hash(mrs_swarm* s, int32_t first, int32_t count, int32_t k, double 
 bool nn_sorted(const mrs_swarm* s, int32_t count) { return nn_order() >= 0 ? nn_order() == 1 : 4LL * count >= s->n; }
 
 }  // namespace
+
+namespace mrs_host {
+// the hash of the swarm's positions for `radius`, for a kernel of another unit (range_scan_uavs.hip): nn_build_hash as it is — the entry
+// fence, the scratch in nn_buf, the four launches on the swarm's stream — and what a probe needs of it
+int nn_hash(mrs_swarm* s, double radius, hipStream_t ext, mrs_nn::NnHash* out) {
+  NnArgs a;
+  int    rc = nn_build_hash(s, 0, s->n, 1, radius, ext, &a);
+  if (rc) return rc;
+  out->rec      = a.rec;
+  out->cnt      = a.cnt;
+  out->start    = a.start;
+  out->bsum     = a.bsum;
+  out->inv_edge = a.inv_edge;
+  out->tmask    = a.tmask;
+  out->n        = a.n;
+  return MRS_OK;
+}
+}  // namespace mrs_host
 
 extern "C" {
 

@@ -145,6 +145,10 @@ int scan_beams_copy(mrs_swarm* dst, const mrs_swarm* src) {
   if (!src->scan || src->scan->host.empty()) return MRS_OK;
   return adopt_beams(dst, src->scan->host.data(), (int32_t)(src->scan->host.size() / 3));
 }
+// for the scans that see other UAVs (range_scan_uavs.hip): the pattern's size and device copy, and the scans' cached obstacle grid
+int32_t       scan_beam_count(const mrs_swarm* s) { return s->scan ? (int32_t)(s->scan->host.size() / 3) : 0; }
+const double* scan_beams_dev(const mrs_swarm* s) { return s->scan ? s->scan->dev.get() : nullptr; }
+int           scan_grid(mrs_swarm* s, double max_range) { return ensure_scan_grid(s, max_range); }
 }  // namespace mrs_host
 
 extern "C" {

@@ -96,4 +96,28 @@ MRS_OBST_HD double ground(double pz, double uz, double gz) {
   return miss();
 }
 
+// ---- scans that see other UAVs (include/mrs_swarm.h, "range scans that see other UAVs"; range_scan_uavs.hip) ----
+
+// UAV j as a beam sees it: the closed sphere of radius rad = fl(arm_length + prop_radius) around its position q, as the sphere record that
+// gate() and ray() above take (so a UAV and a spherical obstacle of equal centre and radius give equal bits)
+MRS_OBST_HD mrs_obstacle_t uav_target(const double q[3], double rad) {
+  mrs_obstacle_t o;
+  o.kind     = MRS_OBST_SPHERE;
+  o.world    = 0;
+  o.flags    = 0u;
+  o.reserved = 0u;
+  o.c[0] = q[0], o.c[1] = q[1], o.c[2] = q[2];
+  o.h[0] = rad, o.h[1] = 0.0, o.h[2] = 0.0;
+  return o;
+}
+
+// the running lexicographic minimum of (t, j): (t, j) replaces (*best_t, *best_j) when it orders before it.  A NaN t is never taken
+// (both comparisons are false).  Idempotent and associative: the order and the number of times the candidates arrive do not matter.
+MRS_OBST_HD void take_uav(double t, int32_t j, double* best_t, int32_t* best_j) {
+  if (t < *best_t || (t == *best_t && j < *best_j)) {
+    *best_t = t;
+    *best_j = j;
+  }
+}
+
 }  // namespace mrs_scan

@@ -17,7 +17,7 @@ from .swarm import (ACTUATOR_CMD, ATTITUDE_CMD, DTYPE_F32, DTYPE_F64, INPUT_UNKN
                     OBS_RPM, OBS_VEL, OBS_VEL_BODY, PROX_COUNT, PROX_HINGE2, PROX_INVERSE, SNAP_BAD_AIRFRAME, SNAP_BAD_INDEX, SNAP_BAD_MAGIC, SNAP_CRASHED, SNAP_LOADED,
                     SNAP_MAGIC, SNAP_SKIPPED, SNAP_TAKEOFF, SNAP_VPREV_SPLIT, SNAPSHOT_DTYPE, TILT_HDG_RATE_CMD, gather_width, nearest_width,
                     OBST_ALL_WORLDS, OBST_BOX, OBST_CYLINDER, OBST_MAX, OBST_MAX_K, OBST_SPHERE, OBSTACLE_DTYPE, ON_ALL, ON_DIST, ON_REL, ON_REL_BODY,
-                    SCAN_BODY_FRAME, SCAN_GROUND, SCAN_HIT_GROUND, SCAN_HIT_NONE, SCAN_MAX_BEAMS, obstacle_width)
+                    SCAN_BODY_FRAME, SCAN_GROUND, SCAN_HIT_GROUND, SCAN_HIT_NONE, SCAN_MAX_BEAMS, UAVSCAN_HIT_UAV, obstacle_width)
 
 _DTYPES = {torch.float64: DTYPE_F64, torch.float32: DTYPE_F32}
 SNAP_BYTES = SNAPSHOT_DTYPE.itemsize  # 496: one mrs_uav_snapshot_t
@@ -682,10 +682,20 @@ def range_scan(swarm, max_range, body_frame=True, ground=False, first=0, count=N
     (ranges, hits): ranges [count, B] of `dtype` (max_range where nothing is hit closer than that), hits int32 [count, B] (the obstacle
     index, SCAN_HIT_NONE or SCAN_HIT_GROUND) when hits=True or a tensor is given, else None.  `out` and `hits` are used instead of new
     tensors when given; columns past B are left alone.  No simulation state is written; a pending collision tick stays pending."""
-    import math
     count = _count(swarm, first, count)
     dev = swarm.device()
-    tdev = torch.device("cuda", dev)
+    max_range, nb = _scan_args(swarm, max_range)
+    out, code, stride = _scan_ranges(out, count, nb, dtype, dev)
+    hits, hptr, hstride = _scan_int_rows(hits, count, nb, dev)
+    flags = (SCAN_BODY_FRAME if body_frame else 0) | (SCAN_GROUND if ground else 0)
+    swarm.range_scan_device(first, count, max_range, flags, out.data_ptr(), code, stride, hptr, hstride, _stream(dev))
+    return _first_columns(out, nb), _first_columns(hits, nb)
+
+
+def _scan_args(swarm, max_range):
+    """(max_range as a float, beams of the swarm's pattern) of a scan, or the ValueError of a max_range that is no finite number > 0 or
+    of a swarm without a pattern"""
+    import math
     try:
         max_range = float(max_range)  # (numpy scalars and one-element tensors too)
     except (TypeError, ValueError):
@@ -695,21 +705,47 @@ def range_scan(swarm, max_range, body_frame=True, ground=False, first=0, count=N
     nb = swarm.scan_beam_count()
     if nb == 0:
         raise ValueError("no beam pattern set: call set_scan_beams() first")
+    return max_range, nb
+
+
+def _scan_ranges(out, count, nb, dtype, dev):
+    """the range rows of a scan: (tensor, dtype code, stride) of `out`, or of a new [count, nb] tensor of `dtype`"""
     if out is None:
-        out = torch.empty((count, nb), dtype=dtype, device=tdev)
-    code = _dtype_code(out.dtype)
-    stride = check_tensor(out, count, nb, out.dtype, dev)
-    hptr, hstride = 0, 0
-    if hits is True:
-        hits = torch.empty((count, nb), dtype=torch.int32, device=tdev)
-    if hits is False or hits is None:
-        hits = None
-    else:
-        hstride = check_tensor(hits, count, nb, torch.int32, dev)
-        hptr = hits.data_ptr()
+        out = torch.empty((count, nb), dtype=dtype, device=torch.device("cuda", dev))
+    return out, _dtype_code(out.dtype), check_tensor(out, count, nb, out.dtype, dev)
+
+
+def _scan_int_rows(rows, count, nb, dev):
+    """an optional int32 output of a scan (hit or UAV indices): (tensor or None, pointer, stride) — True: a new [count, nb] tensor; a
+    tensor: checked and filled; None or False: none"""
+    if rows is True:
+        rows = torch.empty((count, nb), dtype=torch.int32, device=torch.device("cuda", dev))
+    if rows is False or rows is None:
+        return None, 0, 0
+    stride = check_tensor(rows, count, nb, torch.int32, dev)
+    return rows, rows.data_ptr(), stride
+
+
+def _first_columns(t, nb):
+    return None if t is None else t[:, :nb] if t.shape[1] > nb else t
+
+
+def range_scan_uavs(swarm, max_range, body_frame=True, ground=False, first=0, count=None, dtype=torch.float32, out=None, hits=None, uavs=None):
+    """range_scan() that also sees the other UAVs of each observer's world (mrs_swarm_range_scan_uavs_device): UAV j is the closed sphere
+    of radius arm_length + prop_radius of its airframe around its position.  Per beam the obstacles are considered first, then the UAVs
+    (the nearest, ties to the lower index; it takes the beam only when strictly nearer than the obstacle), then the ground.  Returns
+    (ranges, hit, uav): ranges as range_scan(); hit int32 [count, B] with UAVSCAN_HIT_UAV where a UAV took the beam; uav int32 [count, B]
+    with that UAV's index, -1 elsewhere.  hits / uavs: True for new tensors, a tensor to fill, None for none (returned as None).  No
+    simulation state is written; a pending collision tick stays pending."""
+    count = _count(swarm, first, count)
+    dev = swarm.device()
+    max_range, nb = _scan_args(swarm, max_range)
+    out, code, stride = _scan_ranges(out, count, nb, dtype, dev)
+    hits, hptr, hstride = _scan_int_rows(hits, count, nb, dev)
+    uavs, uptr, ustride = _scan_int_rows(uavs, count, nb, dev)
     flags = (SCAN_BODY_FRAME if body_frame else 0) | (SCAN_GROUND if ground else 0)
-    swarm.range_scan_device(first, count, max_range, flags, out.data_ptr(), code, stride, hptr, hstride, _stream(dev))
-    return (out[:, :nb] if out.shape[1] > nb else out), (None if hits is None else hits[:, :nb] if hits.shape[1] > nb else hits)
+    swarm.range_scan_uavs_device(first, count, max_range, flags, out.data_ptr(), code, stride, hptr, hstride, uptr, ustride, _stream(dev))
+    return _first_columns(out, nb), _first_columns(hits, nb), _first_columns(uavs, nb)
 
 
 def set_worlds(swarm, worlds, first=0):

@@ -35,7 +35,7 @@ UNITS = [
     ("transport_local.hip", "off"),
     ("transport_peer.hip", "off"),
 ]
-DEPS = ["step_device.inc", "rollout_device.inc", "rollout_rate_device.inc", "rollout_cost_device.inc", "rollout_tick_device.inc", "collide_device.inc", "collide_work.h", "swarm_layout.h", "pose_math.h", "obs_row.h", "hip_owned.h", "host_internal.h", "sharded_protocol.h", "obstacle_grid.h", "obstacle_set.h", "range_scan_math.h", "nn_hash.h", os.path.join("..", "..", "include", "mrs_swarm.h")]
+DEPS = ["step_device.inc", "rollout_device.inc", "rollout_rate_device.inc", "rollout_cost_device.inc", "rollout_tick_device.inc", "collide_device.inc", "collide_work.h", "swarm_layout.h", "pose_math.h", "obs_row.h", "hip_owned.h", "host_internal.h", "sharded_protocol.h", "obstacle_grid.h", "obstacle_set.h", "range_scan_math.h", "range_scan_common.h", "nn_hash.h", os.path.join("..", "..", "include", "mrs_swarm.h")]
 
 
 def _hipcc():

@@ -188,6 +188,8 @@ int check_device_ptr(const mrs_swarm* s, const void* p, size_t bytes, const char
 size_t rows_bytes(int count, int stride, int width, int dtype) {
   return ((size_t)(count - 1) * (size_t)stride + (size_t)width) * dtype_bytes(dtype);
 }
+// ... and by such rows of int32 indices or counts (one per row: stride = width = 1)
+size_t index_rows_bytes(int count, int stride, int width) { return ((size_t)(count - 1) * (size_t)stride + (size_t)width) * sizeof(int32_t); }
 
 // the stream fence of every call: the swarm's stream waits for what the caller queued on `ext` so far ...
 int fence_in(mrs_swarm* s, hipStream_t ext) {

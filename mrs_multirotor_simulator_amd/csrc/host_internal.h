@@ -5,12 +5,15 @@
 //   tick_sharded.hip      the sharded tick: communicator bookkeeping, search path, serial and split segments of the export-set exchange
 //   device_io.hip         C ABI + kernels for device-resident callers: commands, observations, resets, crash flags in device rows
 //   nearest.hip           C ABI + kernels of the k-nearest-neighbour observations for device-resident callers
-//   obstacles.hip         C ABI + kernels of the static obstacles (the set, nearest-obstacle rows, the obstacle cost); obstacle_grid.h
-//                         holds its pure host functions (tested without a GPU: tests/cpp/obstacle_grid_test.cpp); obstacle_set.h the set
+//   obstacles.hip         C ABI + kernels of the static obstacles (the set, the one routine that makes a cached grid current,
+//                         nearest-obstacle rows, the obstacle cost); obstacle_grid.h holds its pure functions, the kernels' view of a
+//                         grid and the cell walk (walk_cell) that both scans call (tested without a GPU: tests/cpp/obstacle_grid_test.cpp,
+//                         tests/cpp/obstacle_walk_test.cpp); obstacle_set.h the set, its two cache entries and the fill of that view
 //   range_scan.hip        C ABI + kernel of the range scans (the beam pattern, the scan); range_scan_math.h holds its pure functions
-//                         (tested without a GPU: tests/cpp/range_scan_math_test.cpp)
+//                         (tested without a GPU: tests/cpp/range_scan_math_test.cpp); range_scan_common.h what it shares with the next
+//                         unit, once: argument block, beam set-up, obstacle pass, ground pass, stores, argument checks and fill
 //   range_scan_uavs.hip   C ABI + kernel of the range scans that also see the other UAVs of the observer's world (the hash of nearest.hip,
-//                         read through nn_hash.h, joined with the ray tests of range_scan_math.h)
+//                         read through nn_hash.h, joined with the shared scan code of range_scan_common.h)
 //   snapshot.hip          C ABI + kernels of the state snapshots (save / indexed load of whole per-UAV records) for device-resident callers
 //   transport_rccl.hip    RCCL bound at run time (dlopen)
 //   transport_local.hip   in-process loopback group, caller-supplied all-gather, measurement stand-in (with its kernels)
@@ -495,17 +498,18 @@ size_t dtype_bytes(int dtype);
 int    check_dtype(int dtype);
 int    check_device_ptr(const mrs_swarm* s, const void* p, size_t bytes, const char* what);
 size_t rows_bytes(int count, int stride, int width, int dtype);
+size_t index_rows_bytes(int count, int stride, int width);  // the same for rows of int32 indices or counts
 int    fence_in(mrs_swarm* s, hipStream_t ext);
 int    fence_out(mrs_swarm* s, hipStream_t ext);
 int    launch_crashed_u8(mrs_swarm* s, int first, int count, uint8_t* dev_out);  // hasCrashed of a range as bytes, on the swarm's stream
 int    launch_crash_cost(mrs_swarm* s, int first, int count, double* dev_cost, double crash_cost);  // cost[k] += crash_cost where crashed
 // ---- obstacles.hip ----
 int    obstacles_copy(mrs_swarm* dst, const mrs_swarm* src);  // the set of src into dst (clone)
+int    scan_grid(mrs_swarm* s, double max_range);              // the scans' cached obstacle grid (s->obst->scan) made current for max_range
 // ---- range_scan.hip ----
 int    scan_beams_copy(mrs_swarm* dst, const mrs_swarm* src);  // the beam pattern of src into dst (clone)
 int32_t       scan_beam_count(const mrs_swarm* s);             // beams of the pattern (0: none set)
 const double* scan_beams_dev(const mrs_swarm* s);              // its device copy, n_beams x 3
-int    scan_grid(mrs_swarm* s, double max_range);              // the scans' cached obstacle grid (s->obst->scan) made current for max_range
 // ---- nearest.hip: the per-call hash of the UAV positions for another unit's kernel (nn_hash.h) ----
 int    nn_hash(mrs_swarm* s, double radius, hipStream_t ext, mrs_nn::NnHash* out);  // fences ext in, builds in nn_buf on the swarm's stream
 // ---- transports (transport_*.hip) and the communicator bookkeeping (tick_sharded.hip) ----

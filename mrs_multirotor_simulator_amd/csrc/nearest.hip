@@ -608,9 +608,9 @@ int mrs_swarm_nearest_device(mrs_swarm_t* s, int32_t first, int32_t count, int32
   if (dev_index && index_stride < k) return fail(MRS_ERR_ARG, "index_stride smaller than k");
   if (count == 0) return MRS_OK;
   if (fields && (rc = check_device_ptr(s, dev_rows, rows_bytes(count, stride, width, dtype), "dev_rows"))) return rc;
-  if (dev_index && (rc = check_device_ptr(s, dev_index, ((size_t)(count - 1) * (size_t)index_stride + (size_t)k) * sizeof(int32_t), "dev_index")))
+  if (dev_index && (rc = check_device_ptr(s, dev_index, index_rows_bytes(count, index_stride, k), "dev_index")))
     return rc;
-  if (dev_count && (rc = check_device_ptr(s, dev_count, (size_t)count * sizeof(int32_t), "dev_count"))) return rc;
+  if (dev_count && (rc = check_device_ptr(s, dev_count, index_rows_bytes(count, 1, 1), "dev_count"))) return rc;
   HIPCHK(hipSetDevice(s->device));
   hipStream_t ext = (hipStream_t)ext_stream;
   NnArgs      a;
@@ -645,7 +645,7 @@ int mrs_swarm_proximity_cost_device(mrs_swarm_t* s, int32_t first, int32_t count
   if (!dev_cost) return fail(MRS_ERR_ARG, "dev_cost: null pointer");
   if (count == 0) return MRS_OK;
   if ((rc = check_device_ptr(s, dev_cost, (size_t)count * sizeof(double), "dev_cost"))) return rc;
-  if (dev_found && (rc = check_device_ptr(s, dev_found, (size_t)count * sizeof(int32_t), "dev_found"))) return rc;
+  if (dev_found && (rc = check_device_ptr(s, dev_found, index_rows_bytes(count, 1, 1), "dev_found"))) return rc;
   HIPCHK(hipSetDevice(s->device));
   hipStream_t ext = (hipStream_t)ext_stream;
   NnArgs      a;

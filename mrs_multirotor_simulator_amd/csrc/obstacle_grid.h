@@ -1,7 +1,9 @@
 // obstacle_grid.h — the pure functions of the static obstacles (include/mrs_swarm.h, "static obstacles"; obstacles.hip): validation of a
 // set, the signed distance and offset of one obstacle as the contract states them, the cell coordinate of a value, and the host-side
-// builder of the search grid.  No GPU call, so that all of it is exercised without one (tests/cpp/obstacle_grid_test.cpp); eval() and
-// cell_coord() are the very functions the kernels of obstacles.hip call.
+// builder of the search grid, and the definition of how a kernel reads that grid: GridView, which every kernel's arguments embed, and
+// walk_cell(), the cell walk of both range scans (range_scan_common.h; obst_search of obstacles.hip keeps the same steps as a loop of
+// its own and says why).  No GPU call, so that all of it is exercised without one (tests/cpp/obstacle_grid_test.cpp,
+// tests/cpp/obstacle_walk_test.cpp); eval(), cell_coord() and walk_cell() are the very functions the kernels call.
 //
 // The grid: cubic cells of one edge over the bounding box of the solids.  A cell lists every obstacle whose axis-aligned bounding
 // box, grown by `grow` on every side, overlaps the cell, so a query reads ONE cell, the one that contains p — no 27 probes, no
@@ -70,6 +72,32 @@ MRS_OBST_HD int64_t cell_of(const Grid& g, double x, double y, double z) {
   const int cx = cell_coord(x, g.org[0], g.inv_edge, g.dim[0]), cy = cell_coord(y, g.org[1], g.inv_edge, g.dim[1]),
             cz = cell_coord(z, g.org[2], g.inv_edge, g.dim[2]);
   return ((int64_t)cz * g.dim[1] + cy) * g.dim[0] + cx;
+}
+
+// what a kernel needs to read a grid and the set it indexes (handed to the kernels by value; obstacle_set.h fills it)
+struct GridView {
+  Grid                  g;
+  const int32_t *       start, *items;  // [cells + 1], [n_items]
+  const mrs_obstacle_t* obst;           // [m]
+  int32_t               m, n_items;
+};
+
+// The cell walk: visit(j, record) for every obstacle listed in the one cell that contains p, in list order
+// (indices ascend), that an observer with world label myw sees.  Reads nothing outside the arrays whatever they hold: the cell lies
+// inside the grid by the clamp of cell_coord (NaN -> 0), the list bounds are clamped to [0, n_items], an item that is no index of the
+// set is skipped.  Whether to walk at all (m > 0, p finite) is the caller's decision.
+template <class Visit>
+MRS_OBST_HD void walk_cell(const GridView& v, const double p[3], uint32_t myw, Visit&& visit) {
+  const int64_t q  = cell_of(v.g, p[0], p[1], p[2]);
+  const int     s0 = v.start[q], s1 = v.start[q + 1];
+  const int     beg = s0 > 0 ? s0 : 0, end = s1 < v.n_items ? s1 : v.n_items;
+  for (int s = beg; s < end; s++) {
+    const int j = v.items[s];
+    if ((unsigned)j >= (unsigned)v.m) continue;
+    const mrs_obstacle_t o = v.obst[j];
+    if (!(o.flags & (uint32_t)MRS_OBST_ALL_WORLDS) && (uint32_t)o.world != myw) continue;  // another world's obstacle
+    visit(j, o);
+  }
 }
 
 // signed distance of the point p to obstacle o, and the offset rel from p to the closest point of the solid (zero inside), as

@@ -1,5 +1,7 @@
-// obstacle_set.h — the obstacle set a swarm owns (include/mrs_swarm.h, "static obstacles"), shared by the units that query it:
-// obstacles.hip (ownership, the setter, the query grid and the two queries) and range_scan.hip (the scan grid and the range scan).
+// obstacle_set.h — the obstacle set a swarm owns (include/mrs_swarm.h, "static obstacles"), shared by the units that read it:
+// obstacles.hip (ownership, the setter, the one routine that makes a cached grid current, the two queries) and the two scan units
+// (range_scan.hip, range_scan_uavs.hip, through range_scan_common.h).  Every kernel reads it through the GridView that grid_view() fills
+// (obstacle_grid.h, where the scans' cell walk lives too).
 #pragma once
 #include "host_internal.h"
 #include "obstacle_grid.h"
@@ -14,11 +16,13 @@ struct ObstacleGridCache {
 struct ObstacleSet {
   std::vector<mrs_obstacle_t> host;  // the set as given (get_obstacles, clone, the grid builder)
   DevBuf<mrs_obstacle_t>      dev;
-  mrs_obst::Built             grid;  // the cached grid: its vectors are the source of the upload and live until the next build
-  bool                        grid_ok = false;
-  DevBuf<int32_t>             d_start, d_items;
+  // two independent entries, the queries' keyed by radius and the scans' by max_range: a loop that alternates a query of one radius with
+  // a scan of another range rebuilds neither.  Both are dropped when the set is replaced.
+  ObstacleGridCache           query, scan;
   int64_t                     builds = 0;  // grids built so far, for the queries and for the scans
-  // the range scans' own entry (range_scan.hip), keyed by max_range: a loop that alternates a query of one radius with a scan of another
-  // range rebuilds neither.  Dropped with the query grid when the set is replaced.
-  ObstacleGridCache           scan;
 };
+
+// what a kernel reads of the set through the (current) cache entry c
+inline mrs_obst::GridView grid_view(const ObstacleSet& o, const ObstacleGridCache& c) {
+  return {c.grid.g, c.d_start, c.d_items, o.dev, (int32_t)o.host.size(), (int32_t)c.grid.items.size()};
+}

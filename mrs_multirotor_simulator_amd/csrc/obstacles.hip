@@ -4,8 +4,16 @@
 // position (obstacle_grid.h: inflated binning, built on the host, cached per radius), tests every obstacle listed there literally
 // (world rule, sd < radius) and keeps the first KC by (sd, obstacle index) in a register list.  A wave's lanes sit in unrelated cells, so
 // the walk diverges; the lists are short (a cell's neighbourhood) and the 64-B obstacle records stay in cache.
-// The sorted insertion is that of nearest.hip's nn_probe with a text of its own: that unit and its measured schedule stay as they are.
+// The steps of the walk are those of mrs_obst::walk_cell (obstacle_grid.h), which both range scans call, over the same GridView;
+// obst_search keeps them as a loop of its own because the callable form measured slower here ("One cell walk ...").
+// This unit also owns the set and ensure(), the one routine that makes a cached grid current, for the queries' entry and, through
+// mrs_host::scan_grid, for the scans'.
+// The sorted insertion stays here, a text of its own beside nearest.hip's nn_probe: it orders by (sd, obstacle index) over a list this
+// kernel keeps, nn_probe by (d2, UAV index) inside a probe loop whose measured schedule a shared template would disturb — that unit
+// stays as it is.
 // Nothing here writes simulation state; the calls enter like mrs_swarm_nearest_device (a pending collision tick stays pending).
+#include <type_traits>
+
 #include "host_internal.h"
 #include "obstacle_grid.h"
 #include "obstacle_set.h"
@@ -21,10 +29,7 @@ struct ObstArgs {
   const uint32_t*       wlab;  // null: every UAV is in world 0
   int32_t               n, npad, first, count, k;
   double                radius;
-  mrs_obst::Grid        g;
-  const int32_t *       start, *items;
-  const mrs_obstacle_t* obst;
-  int32_t               m, n_items;
+  mrs_obst::GridView    v;
   // rows of k_obst_rows
   void*    rows;
   int32_t  stride, width;  // width: elements of one slot
@@ -53,13 +58,14 @@ __device__ __forceinline__ int obst_search(const ObstArgs& a, const double p[3],
     lj[m] = 0x7FFFFFFF;
   }
   int found = 0;
-  if (a.m > 0 && isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2])) {
-    const int64_t q   = mrs_obst::cell_of(a.g, p[0], p[1], p[2]);  // (inside the grid by the clamp of cell_coord)
-    const int     beg = max(a.start[q], 0), end = min(a.start[q + 1], a.n_items);
-    for (int s = beg; s < end; s++) {
-      const int j = a.items[s];
-      if ((unsigned)j >= (unsigned)a.m) continue;
-      const mrs_obstacle_t o = a.obst[j];
+  if (a.v.m > 0 && isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2])) {
+    const mrs_obst::GridView& v   = a.v;
+    const int64_t             q   = mrs_obst::cell_of(v.g, p[0], p[1], p[2]);  // (inside the grid by the clamp of cell_coord)
+    const int                 beg = max(v.start[q], 0), end = min(v.start[q + 1], v.n_items);
+    for (int s = beg; s < end; s++) {  // (the steps of mrs_obst::walk_cell, see the head of the file)
+      const int j = v.items[s];
+      if ((unsigned)j >= (unsigned)v.m) continue;
+      const mrs_obstacle_t o = v.obst[j];
       if (!(o.flags & (uint32_t)MRS_OBST_ALL_WORLDS) && (uint32_t)o.world != myw) continue;  // another world's obstacle
       double       rel[3];
       const double sd = mrs_obst::eval(o, p, rel);
@@ -110,7 +116,7 @@ __device__ __forceinline__ void write_slot(T* o, const ObstArgs& a, bool valid, 
   }
   const uint32_t f = a.fields;
   double         rel[3];
-  if (f & (MRS_ON_REL | MRS_ON_REL_BODY)) (void)mrs_obst::eval(a.obst[j], p, rel);
+  if (f & (MRS_ON_REL | MRS_ON_REL_BODY)) (void)mrs_obst::eval(a.v.obst[j], p, rel);
   if (f & MRS_ON_REL) {
     put3(o, rel[0], rel[1], rel[2]);
     o += 3;
@@ -186,22 +192,22 @@ __global__ void __launch_bounds__(OB_BLOCK) k_obst_cost(ObstArgs a, ObstCost c) 
 
 inline dim3 grid_of(int count) { return dim3((unsigned)((count + OB_BLOCK - 1) / OB_BLOCK)); }
 
+// the list length of the kernels that serve k: launch(integral_constant<int, 8 / 16 / 32>)
+template <class Launch>
+void for_list_length(int k, Launch&& launch) {
+  if (k <= 8)
+    launch(std::integral_constant<int, 8>{});
+  else if (k <= 16)
+    launch(std::integral_constant<int, 16>{});
+  else
+    launch(std::integral_constant<int, 32>{});
+}
 template <typename T>
 void launch_rows(const ObstArgs& a, hipStream_t st) {
-  if (a.k <= 8)
-    hipLaunchKernelGGL((k_obst_rows<8, T>), grid_of(a.count), dim3(OB_BLOCK), 0, st, a);
-  else if (a.k <= 16)
-    hipLaunchKernelGGL((k_obst_rows<16, T>), grid_of(a.count), dim3(OB_BLOCK), 0, st, a);
-  else
-    hipLaunchKernelGGL((k_obst_rows<32, T>), grid_of(a.count), dim3(OB_BLOCK), 0, st, a);
+  for_list_length(a.k, [&](auto kc) { hipLaunchKernelGGL((k_obst_rows<decltype(kc)::value, T>), grid_of(a.count), dim3(OB_BLOCK), 0, st, a); });
 }
 void launch_cost(const ObstArgs& a, const ObstCost& c, hipStream_t st) {
-  if (a.k <= 8)
-    hipLaunchKernelGGL((k_obst_cost<8>), grid_of(a.count), dim3(OB_BLOCK), 0, st, a, c);
-  else if (a.k <= 16)
-    hipLaunchKernelGGL((k_obst_cost<16>), grid_of(a.count), dim3(OB_BLOCK), 0, st, a, c);
-  else
-    hipLaunchKernelGGL((k_obst_cost<32>), grid_of(a.count), dim3(OB_BLOCK), 0, st, a, c);
+  for_list_length(a.k, [&](auto kc) { hipLaunchKernelGGL((k_obst_cost<decltype(kc)::value>), grid_of(a.count), dim3(OB_BLOCK), 0, st, a, c); });
 }
 
 ObstacleSet* set_of(mrs_swarm* s) {
@@ -220,45 +226,46 @@ int adopt(mrs_swarm* s, const mrs_obstacle_t* obstacles, int32_t count) {
     HIPCHK(hipStreamSynchronize(s->stream));
   }
   o->host.swap(fresh);
-  o->grid_ok = false;
-  o->scan.ok = false;  // (the range scans' grid served the old set too)
+  o->query.ok = o->scan.ok = false;  // (both grids served the old set)
   return MRS_OK;
 }
 
-// The grid for `radius`: built and uploaded on the swarm's stream when the cached one serves another radius or another set.  Fills the
-// search part of `a`.  Called after every argument check and before the entry fence (the upload reads nothing of the caller's).
-int ensure_grid(mrs_swarm* s, int32_t first, int32_t count, int32_t k, double radius, ObstArgs* out) {
-  ObstacleSet* o = set_of(s);
-  if (!o->grid_ok || o->grid.radius != radius) {
-    mrs_obst::Built b = mrs_obst::build(o->host.data(), (int32_t)o->host.size(), radius);
-    HIPCHK(hipStreamSynchronize(s->stream));  // (a query may still read the cached grid, and its host vectors may still be uploading)
-    o->grid_ok = false;
-    HIPCHK(o->d_start.reserve(b.start.size()));
-    HIPCHK(o->d_items.reserve(std::max<size_t>(b.items.size(), 1)));
-    o->grid = std::move(b);
-    HIPCHK(hipMemcpyAsync(o->d_start, o->grid.start.data(), sizeof(int32_t) * o->grid.start.size(), hipMemcpyHostToDevice, s->stream));
-    if (!o->grid.items.empty())
-      HIPCHK(hipMemcpyAsync(o->d_items, o->grid.items.data(), sizeof(int32_t) * o->grid.items.size(), hipMemcpyHostToDevice, s->stream));
-    o->grid_ok = true;
-    o->builds++;
-  }
+// Makes the cache entry c of s's set current for `radius`: built and uploaded on the swarm's stream when the cached grid serves another
+// radius or another set.  Called after every argument check and before the entry fence (the upload reads nothing of the caller's).
+int ensure(mrs_swarm* s, ObstacleGridCache& c, double radius) {
+  ObstacleSet* o = s->obst;
+  if (c.ok && c.grid.radius == radius) return MRS_OK;
+  mrs_obst::Built b = mrs_obst::build(o->host.data(), (int32_t)o->host.size(), radius);
+  HIPCHK(hipStreamSynchronize(s->stream));  // (a kernel may still read the cached grid, and its host vectors may still be uploading)
+  c.ok = false;
+  HIPCHK(c.d_start.reserve(b.start.size()));
+  HIPCHK(c.d_items.reserve(std::max<size_t>(b.items.size(), 1)));
+  c.grid = std::move(b);
+  HIPCHK(hipMemcpyAsync(c.d_start, c.grid.start.data(), sizeof(int32_t) * c.grid.start.size(), hipMemcpyHostToDevice, s->stream));
+  if (!c.grid.items.empty())
+    HIPCHK(hipMemcpyAsync(c.d_items, c.grid.items.data(), sizeof(int32_t) * c.grid.items.size(), hipMemcpyHostToDevice, s->stream));
+  c.ok = true;
+  o->builds++;
+  return MRS_OK;
+}
+
+// the queries' grid made current for `radius`, and the search part of `a`
+int query_args(mrs_swarm* s, int32_t first, int32_t count, int32_t k, double radius, ObstArgs* out) {
+  ObstacleSet* o  = set_of(s);
+  int          rc = ensure(s, o->query, radius);
+  if (rc) return rc;
   ObstArgs a;
   memset(&a, 0, sizeof a);
-  a.S       = s->dS;
-  a.wlab    = s->dWorld;
-  a.n       = s->n;
-  a.npad    = s->npad;
-  a.first   = first;
-  a.count   = count;
-  a.k       = k;
-  a.radius  = radius;
-  a.g       = o->grid.g;
-  a.start   = o->d_start;
-  a.items   = o->d_items;
-  a.obst    = o->dev;
-  a.m       = (int32_t)o->host.size();
-  a.n_items = (int32_t)o->grid.items.size();
-  *out      = a;
+  a.S      = s->dS;
+  a.wlab   = s->dWorld;
+  a.n      = s->n;
+  a.npad   = s->npad;
+  a.first  = first;
+  a.count  = count;
+  a.k      = k;
+  a.radius = radius;
+  a.v      = grid_view(*o, o->query);
+  *out     = a;
   return MRS_OK;
 }
 
@@ -281,6 +288,8 @@ int obstacles_copy(mrs_swarm* dst, const mrs_swarm* src) {
   if (!src->obst || src->obst->host.empty()) return MRS_OK;
   return adopt(dst, src->obst->host.data(), (int32_t)src->obst->host.size());
 }
+// the scans' entry (s->obst->scan) made current for max_range, for the kernels of the two scan units
+int scan_grid(mrs_swarm* s, double max_range) { return ensure(s, set_of(s)->scan, max_range); }
 }  // namespace mrs_host
 
 extern "C" {
@@ -315,13 +324,14 @@ int mrs_swarm_obstacle_stats(mrs_swarm_t* s, mrs_obstacle_stats_t* st) {
   if (!o) return MRS_OK;
   st->count       = (int32_t)o->host.size();
   st->grid_builds = o->builds;
-  if (!o->grid_ok) return MRS_OK;
-  for (int a = 0; a < 3; a++) st->dims[a] = o->grid.g.dim[a];
-  st->cells        = o->grid.cells();
-  st->list_items   = (int64_t)o->grid.items.size();
-  st->longest_list = o->grid.longest;
-  st->grid_radius  = o->grid.radius;
-  st->cell_edge    = o->grid.edge;
+  if (!o->query.ok) return MRS_OK;
+  const mrs_obst::Built& b = o->query.grid;  // (the queries' entry: the scans' is not reported)
+  for (int a = 0; a < 3; a++) st->dims[a] = b.g.dim[a];
+  st->cells        = b.cells();
+  st->list_items   = (int64_t)b.items.size();
+  st->longest_list = b.longest;
+  st->grid_radius  = b.radius;
+  st->cell_edge    = b.edge;
   return MRS_OK;
 }
 
@@ -351,13 +361,13 @@ int mrs_swarm_nearest_obstacles_device(mrs_swarm_t* s, int32_t first, int32_t co
   if (dev_index && index_stride < k) return fail(MRS_ERR_ARG, "index_stride smaller than k");
   if (count == 0) return MRS_OK;
   if (fields && (rc = check_device_ptr(s, dev_rows, rows_bytes(count, stride, width, dtype), "dev_rows"))) return rc;
-  if (dev_index && (rc = check_device_ptr(s, dev_index, ((size_t)(count - 1) * (size_t)index_stride + (size_t)k) * sizeof(int32_t), "dev_index")))
+  if (dev_index && (rc = check_device_ptr(s, dev_index, index_rows_bytes(count, index_stride, k), "dev_index")))
     return rc;
-  if (dev_count && (rc = check_device_ptr(s, dev_count, (size_t)count * sizeof(int32_t), "dev_count"))) return rc;
+  if (dev_count && (rc = check_device_ptr(s, dev_count, index_rows_bytes(count, 1, 1), "dev_count"))) return rc;
   HIPCHK(hipSetDevice(s->device));
   hipStream_t ext = (hipStream_t)ext_stream;
   ObstArgs    a;
-  if ((rc = ensure_grid(s, first, count, k, radius, &a))) return rc;
+  if ((rc = query_args(s, first, count, k, radius, &a))) return rc;
   if ((rc = fence_in(s, ext))) return rc;
   a.fields       = dev_rows ? fields : 0u;
   a.rows         = dev_rows;
@@ -384,11 +394,11 @@ int mrs_swarm_obstacle_cost_device(mrs_swarm_t* s, int32_t first, int32_t count,
   if (!dev_cost) return fail(MRS_ERR_ARG, "dev_cost: null pointer");
   if (count == 0) return MRS_OK;
   if ((rc = check_device_ptr(s, dev_cost, (size_t)count * sizeof(double), "dev_cost"))) return rc;
-  if (dev_found && (rc = check_device_ptr(s, dev_found, (size_t)count * sizeof(int32_t), "dev_found"))) return rc;
+  if (dev_found && (rc = check_device_ptr(s, dev_found, index_rows_bytes(count, 1, 1), "dev_found"))) return rc;
   HIPCHK(hipSetDevice(s->device));
   hipStream_t ext = (hipStream_t)ext_stream;
   ObstArgs    a;
-  if ((rc = ensure_grid(s, first, count, k, radius, &a))) return rc;
+  if ((rc = query_args(s, first, count, k, radius, &a))) return rc;
   if ((rc = fence_in(s, ext))) return rc;
   ObstCost c;
   c.weight     = weight;

@@ -7,12 +7,11 @@
 // over 27 buckets, each with a dependent load for its airframe radius: the block gathers them once, 64 records at a time across its
 // lanes, into a chunk in LDS, and every lane then runs ray + take_uav over the chunk for its own beam (all lanes read the same entry: a
 // broadcast, no bank conflict).  Gather and sweep repeat until the buckets are exhausted: the running (t, j) minimum is associative.
+// Beam set-up, obstacle pass, ground pass, range / hit stores, argument checks and fill are range_scan_common.h's, the very functions
+// k_range_scan calls; what is this unit's own: the block shape, the live lanes, gather and sweep, the UAV / ground merge, the uav rows.
 // Nothing here writes simulation state; entry, fence and scratch are those of the scans and of nearest (the swarm's nn_buf).
-#include "host_internal.h"
 #include "nn_hash.h"
-#include "obstacle_set.h"
-#include "pose_math.h"
-#include "range_scan_math.h"
+#include "range_scan_common.h"
 
 namespace {
 
@@ -20,23 +19,10 @@ constexpr int RU_WAVE = 64;   // lanes of a block: one wave, so every barrier be
 constexpr int RU_CAP  = 256;  // entries of the candidate chunk in LDS (tests/test_range_scan_uavs_gpu.py names this value): 9 KiB per block
 
 struct UavScanArgs {
-  const double*         S;
-  const uint32_t*       F;
-  const TypeParams*     T;
-  int32_t               npad, first, n_beams, groups;
-  uint32_t              flags;
-  const double*         beams;
-  double                max_range;
-  // the obstacles, as in range_scan.hip
-  mrs_obst::Grid        g;
-  const int32_t *       start, *items;
-  const mrs_obstacle_t* obst;
-  int32_t               m, n_items;
-  // the hash of the UAV positions
-  mrs_nn::NnHash        h;
-  void*                 ranges;
-  int32_t *             hit, *uav;
-  int32_t               stride, hit_stride, uav_stride;
+  ScanCommon     c;
+  mrs_nn::NnHash h;  // the hash of the UAV positions
+  int32_t*       uav;
+  int32_t        uav_stride, groups;
 };
 
 // every lane runs ray + take_uav over the `fill` chunk entries for its own beam (fill is the same in every lane)
@@ -56,51 +42,20 @@ __global__ void __launch_bounds__(RU_WAVE) k_range_scan_uavs(UavScanArgs a, W...
   constexpr bool WORLDS = sizeof...(W) != 0;
   __shared__ double  cx[RU_CAP], cy[RU_CAP], cz[RU_CAP], crad[RU_CAP];
   __shared__ int32_t cj[RU_CAP];
-  const int    lane = (int)threadIdx.x;
-  const int    r    = (int)(blockIdx.x / (unsigned)a.groups), grp = (int)(blockIdx.x - (unsigned)r * (unsigned)a.groups);
-  const int    i    = a.first + r;  // the observer: the same in every lane
-  const int    b    = RU_WAVE * grp + lane;
-  const bool   live = b < a.n_beams;  // lanes past the pattern stay in the block, take part in every barrier and store nothing
-  const int    bb   = live ? b : a.n_beams - 1;
-  const size_t np   = (size_t)a.npad;
-  double       p[3], u[3];
-  p[0] = a.S[(size_t)F_X * np + i];
-  p[1] = a.S[(size_t)(F_X + 1) * np + i];
-  p[2] = a.S[(size_t)(F_X + 2) * np + i];
-  // ---- beam setup: u, then the one obstacle cell, exactly as k_range_scan ----
-  const double bm[3] = {a.beams[3 * bb], a.beams[3 * bb + 1], a.beams[3 * bb + 2]};
-  if (a.flags & MRS_SCAN_BODY_FRAME) {  // u = R b: row c of R times b, as body_velocity forms a column of its argument times a vector
-    double Rt[9];
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-#pragma unroll
-      for (int k = 0; k < 3; k++) Rt[3 * k + c] = a.S[(size_t)(F_R + 3 * c + k) * np + i];
-    u[0] = body_velocity(Rt, bm, 0), u[1] = body_velocity(Rt, bm, 1), u[2] = body_velocity(Rt, bm, 2);
-  } else {
-    u[0] = bm[0], u[1] = bm[1], u[2] = bm[2];
-  }
-  double     best = a.max_range;
+  const int  lane = (int)threadIdx.x;
+  const int  r    = (int)(blockIdx.x / (unsigned)a.groups), grp = (int)(blockIdx.x - (unsigned)r * (unsigned)a.groups);
+  const int  i    = a.c.first + r;  // the observer: the same in every lane
+  const int  b    = RU_WAVE * grp + lane;
+  const bool live = b < a.c.n_beams;  // lanes past the pattern stay in the block, take part in every barrier and store nothing
+  double     p[3], u[3];
+  scan_beam(a.c, i, live ? b : a.c.n_beams - 1, p, u);
+  double     best = a.c.max_range;
   int        idx  = MRS_SCAN_HIT_NONE, who = -1;
   const bool seen = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);  // (the same in every lane)
   if (seen) {
     uint32_t myw = 0u;
     if constexpr (WORLDS) myw = world_labels(labels...)[i];
-    if (a.m > 0) {
-      const int64_t q   = mrs_obst::cell_of(a.g, p[0], p[1], p[2]);  // (inside the grid by the clamp of cell_coord)
-      const int     beg = max(a.start[q], 0), end = min(a.start[q + 1], a.n_items);
-      for (int s = beg; s < end; s++) {  // obstacle indices ascend within a cell: a strict < keeps the lowest index among equal ranges
-        const int j = a.items[s];
-        if ((unsigned)j >= (unsigned)a.m) continue;
-        const mrs_obstacle_t o = a.obst[j];
-        if (!(o.flags & (uint32_t)MRS_OBST_ALL_WORLDS) && (uint32_t)o.world != myw) continue;  // another world's obstacle
-        if (!mrs_scan::gate(o, p, a.max_range)) continue;
-        const double t = mrs_scan::ray(o, p, u);
-        if (t < best) {
-          best = t;
-          idx  = j;
-        }
-      }
-    }
+    if (a.c.v.m > 0) scan_obstacles(a.c, p, u, myw, &best, &idx);
     // ---- the UAVs: gather the candidates of the 27 buckets into the chunk, sweep it whenever it cannot take 64 more ----
     // Two probed cells may hash to one bucket, whose records are then gathered twice.  k_nn_query must not count a neighbour twice and
     // removes such probes; here a second arrival of (t, j) changes nothing — take_uav is a minimum, and a minimum is idempotent — so the
@@ -130,9 +85,9 @@ __global__ void __launch_bounds__(RU_WAVE) k_range_scan_uavs(UavScanArgs a, W...
           pass = j != i && (unsigned)j < (unsigned)a.h.n;
           if constexpr (WORLDS) pass = pass && (uint32_t)rec.pad == myw;  // another world: invisible, however close
           if (pass) {
-            const TypeParams& tp = a.T[a.F[j] >> FLAG_TYPE_SHIFT];
+            const TypeParams& tp = a.c.T[a.c.F[j] >> FLAG_TYPE_SHIFT];
             rad  = tp.arm_length + tp.prop_radius;
-            pass = mrs_scan::gate(mrs_scan::uav_target(q, rad), p, a.max_range);
+            pass = mrs_scan::gate(mrs_scan::uav_target(q, rad), p, a.c.max_range);
           }
         }
         const unsigned long long mask = __ballot(pass);
@@ -152,24 +107,16 @@ __global__ void __launch_bounds__(RU_WAVE) k_range_scan_uavs(UavScanArgs a, W...
     }
     __syncthreads();
     sweep(fill, cx, cy, cz, crad, cj, p, u, &bt, &bj);
-    // ---- finish: an obstacle at the same range keeps the beam; then the ground, as in k_range_scan ----
+    // ---- finish: an obstacle at the same range keeps the beam; then the ground ----
     if (bt < best) {
       best = bt;
       idx  = MRS_UAVSCAN_HIT_UAV;
       who  = bj;
     }
-    if (a.flags & MRS_SCAN_GROUND) {
-      const double t = mrs_scan::ground(p[2], u[2], a.T[a.F[i] >> FLAG_TYPE_SHIFT].ground_z);
-      if (t < best) {
-        best = t;
-        idx  = MRS_SCAN_HIT_GROUND;
-        who  = -1;
-      }
-    }
+    if (scan_ground(a.c, i, p, u, &best, &idx)) who = -1;
   }
   if (!live) return;
-  static_cast<T*>(a.ranges)[(size_t)r * (size_t)a.stride + (size_t)b] = (T)best;
-  if (a.hit) a.hit[(size_t)r * (size_t)a.hit_stride + (size_t)b] = idx;
+  scan_store<T>(a.c, r, b, best, idx);
   if (a.uav) a.uav[(size_t)r * (size_t)a.uav_stride + (size_t)b] = who;
 }
 
@@ -189,24 +136,11 @@ extern "C" {
 int mrs_swarm_range_scan_uavs_device(mrs_swarm_t* s, int32_t first, int32_t count, double max_range, uint32_t flags, void* dev_ranges, int32_t dtype,
                                      int32_t stride, int32_t* dev_hit, int32_t hit_stride, int32_t* dev_uav, int32_t uav_stride, void* ext_stream) {
   MRS_ENTER_COMMANDS(s);
-  int rc = check_range(s, first, count);
-  if (rc) return rc;
-  if (s->comm_world > 0) return fail(MRS_ERR_ARG, "mrs_swarm_range_scan_uavs_device: not on a sharded swarm");
-  const int32_t nb = scan_beam_count(s);
-  if (nb == 0) return fail(MRS_ERR_ARG, "no beam pattern set (mrs_swarm_set_scan_beams)");
-  if (!(max_range > 0.0) || !std::isfinite(max_range)) return fail(MRS_ERR_ARG, "max_range must be finite and > 0");
-  if (flags & ~(uint32_t)(MRS_SCAN_BODY_FRAME | MRS_SCAN_GROUND)) return fail(MRS_ERR_ARG, "unknown scan flag bits");
-  if ((rc = check_dtype(dtype))) return rc;
-  if (stride < nb) return fail(MRS_ERR_ARG, "stride smaller than n_beams");
-  if (dev_hit && hit_stride < nb) return fail(MRS_ERR_ARG, "hit_stride smaller than n_beams");
-  if (dev_uav && uav_stride < nb) return fail(MRS_ERR_ARG, "uav_stride smaller than n_beams");
-  if (!dev_ranges) return fail(MRS_ERR_ARG, "dev_ranges: null pointer");
-  const int32_t groups = (nb + RU_WAVE - 1) / RU_WAVE;
-  if ((int64_t)count * groups > 0x7FFFFFFFll) return fail(MRS_ERR_ARG, "count * ceil(n_beams / 64) exceeds one launch (2^31 blocks)");
-  if (count == 0) return MRS_OK;
-  if ((rc = check_device_ptr(s, dev_ranges, rows_bytes(count, stride, nb, dtype), "dev_ranges"))) return rc;
-  if (dev_hit && (rc = check_device_ptr(s, dev_hit, ((size_t)(count - 1) * (size_t)hit_stride + (size_t)nb) * sizeof(int32_t), "dev_hit"))) return rc;
-  if (dev_uav && (rc = check_device_ptr(s, dev_uav, ((size_t)(count - 1) * (size_t)uav_stride + (size_t)nb) * sizeof(int32_t), "dev_uav"))) return rc;
+  const int32_t  nb = scan_beam_count(s), groups = (nb + RU_WAVE - 1) / RU_WAVE;
+  const ScanRows rows{dev_ranges, dtype, stride, dev_hit, hit_stride, dev_uav, uav_stride};
+  int            rc = check_scan(s, "mrs_swarm_range_scan_uavs_device", nb, first, count, max_range, flags, rows, (int64_t)count * groups,
+                                 "count * ceil(n_beams / 64) exceeds one launch (2^31 blocks)");
+  if (rc || count == 0) return rc;
   HIPCHK(hipSetDevice(s->device));
   hipStream_t ext = (hipStream_t)ext_stream;
   // the airframe radii (and the ground plane) are read from the airframe table: current before the launch
@@ -222,29 +156,10 @@ int mrs_swarm_range_scan_uavs_device(mrs_swarm_t* s, int32_t first, int32_t coun
   UavScanArgs a;
   memset(&a, 0, sizeof a);
   if ((rc = nn_hash(s, max_range + rmax, ext, &a.h))) return rc;  // (fences the caller's stream in)
-  const ObstacleSet* o = s->obst;
-  a.S          = s->dS;
-  a.F          = s->dF;
-  a.T          = s->dT;
-  a.npad       = s->npad;
-  a.first      = first;
-  a.n_beams    = nb;
-  a.groups     = groups;
-  a.flags      = flags;
-  a.beams      = scan_beams_dev(s);
-  a.max_range  = max_range;
-  a.g          = o->scan.grid.g;
-  a.start      = o->scan.d_start;
-  a.items      = o->scan.d_items;
-  a.obst       = o->dev;
-  a.m          = (int32_t)o->host.size();
-  a.n_items    = (int32_t)o->scan.grid.items.size();
-  a.ranges     = dev_ranges;
-  a.hit        = dev_hit;
+  a.c          = scan_common(s, first, nb, max_range, flags, rows);
   a.uav        = dev_uav;
-  a.stride     = stride;
-  a.hit_stride = hit_stride;
   a.uav_stride = uav_stride;
+  a.groups     = groups;
   if (dtype == MRS_DTYPE_F32)
     launch<float>(a, count, s->dWorld, s->stream);
   else

@@ -593,6 +593,17 @@ def test_grid_builder_under_sanitizers():
     assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr
 
 
+def test_cell_walk_under_sanitizers():
+    """tests/cpp/obstacle_walk_test.cpp: mrs_obst::walk_cell, the cell walk of the range scans, on the host compiler without
+    contraction under the address and undefined-behaviour sanitizers — intact arrays, damaged arrays, m == 0"""
+    exe = os.path.join(ROOT, "tests", "cpp", "obstacle_walk_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", os.path.join(ROOT, "tests", "cpp", "obstacle_walk_test.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "ok obstacle_walk" in out.stdout, out.stdout + out.stderr
+    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr
+
+
 def test_obstacles_test_compiles(mrs):
     """tests/cpp/obstacles_test.cpp builds against the facade and the HIP runtime (run on the GPU by test_obstacles_gpu.py)"""
     from test_device_io_gpu import build_cpp

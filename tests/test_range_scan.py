@@ -420,7 +420,7 @@ def test_symbols_are_declared_exported_and_listed(mrs):
         assert callable(getattr(swarm.Swarm, method, None)), method
     for fn in ("set_scan_beams", "range_scan", "scan_ring", "scan_grid"):
         assert callable(getattr(tensors, fn, None)), fn
-    assert ("range_scan.hip", "off") in build.UNITS and {"range_scan_math.h", "obstacle_set.h"} <= set(build.DEPS)
+    assert ("range_scan.hip", "off") in build.UNITS and {"range_scan_math.h", "range_scan_common.h", "obstacle_set.h"} <= set(build.DEPS)
     facade = open(os.path.join(ROOT, "include", "mrs_multirotor_simulator", "uav_system", "uav_system.hpp")).read()
     for method in ("setScanBeams", "getScanBeams", "rangeScanDevice"):
         assert re.search(r"\b" + method + r"\(", facade), method

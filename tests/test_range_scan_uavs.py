@@ -325,7 +325,7 @@ def test_symbol_is_declared_exported_and_listed(mrs):
     assert re.search(r"\bint\s+" + NAME + r"\(", abi_header())
     assert hasattr(L, NAME) and NAME in swarm.ABI_SYMBOLS
     assert callable(getattr(swarm.Swarm, "range_scan_uavs_device", None)) and callable(getattr(tensors, "range_scan_uavs", None))
-    assert ("range_scan_uavs.hip", "off") in build.UNITS and {"range_scan_math.h", "nn_hash.h"} <= set(build.DEPS)
+    assert ("range_scan_uavs.hip", "off") in build.UNITS and {"range_scan_math.h", "range_scan_common.h", "nn_hash.h"} <= set(build.DEPS)
     facade = open(os.path.join(ROOT, "include", "mrs_multirotor_simulator", "uav_system", "uav_system.hpp")).read()
     assert re.search(r"\brangeScanUavsDevice\(", facade)
 

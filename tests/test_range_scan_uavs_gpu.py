@@ -315,6 +315,70 @@ def test_alternating_with_nearest_and_proximity_cost(mrs, scene):
             assert x.dtype == y.dtype and torch.equal(torch.nan_to_num(x.double(), nan=7.0), torch.nan_to_num(y.double(), nan=7.0)), (rep, k)
 
 
+def test_queries_and_scans_interleaved_on_two_cache_entries(mrs):
+    """nearest_obstacles, range_scan, range_scan_uavs and obstacle_cost interleaved on one swarm (600 UAVs of the fixture scene, 16 beams):
+    every result is its restatement's bit for bit, and the grid builds are those of two independent cache entries — the two scan calls
+    share the scans' entry, the two queries the queries'"""
+    import torch
+    from mrs_multirotor_simulator_amd import tensors as T
+    from test_obstacles import HINGE2, ON_DIST, ON_REL, add_bits, restate_cost, restate_obstacles, restate_rows
+    pos, worlds, ob = fixture_scene()
+    n, k, r1, r2, r3 = 600, 8, 3.0, MAX_RANGE, 2.5
+    pos, worlds = pos[:n], worlds[:n]
+    R = scene_state()["R"].reshape(-1, 3, 3)[:n]
+    beams, gz = mixed_beams(16), np.zeros(n)
+    g = plain_swarm(mrs, pos, R)
+    g.set_worlds(worlds)
+    g.set_obstacles(ob)
+    T.set_scan_beams(g, beams)
+    near = restate_obstacles(pos, R, worlds, ob, k, r1)
+    rows_want = restate_rows(near, ON_REL | ON_DIST)
+    cost_want = add_bits(None, restate_cost(near, k, r1, HINGE2, 1.5))
+    scan_want = {r: restate_scan(pos, R, worlds, ob, beams, r, ground_z=gz) for r in (r2, r3)}
+    uavs_want = {r: restate_scan_uavs(pos, R, worlds, X500, ob, beams, r, ground_z=gz) for r in (r2, r3)}
+    assert (near["found"] > 0).sum() > 100 and (scan_want[r3][1] >= 0).sum() > 100 and (uavs_want[r3][1] == HIT_UAV).sum() >= 10
+
+    def nearest():
+        rows, index, counts = T.nearest_obstacles(g, k, r1, ON_REL | ON_DIST, dtype=torch.float64)
+        assert same_bits(rows.cpu().numpy(), rows_want) and np.array_equal(index.cpu().numpy(), near["index"])
+        assert np.array_equal(counts.cpu().numpy(), near["count"])
+
+    def scan(r):
+        ranges, hit = T.range_scan(g, r, ground=True, hits=True, dtype=torch.float64)
+        assert same_bits(ranges.cpu().numpy(), scan_want[r][0]) and np.array_equal(hit.cpu().numpy(), scan_want[r][1]), r
+
+    def scan_uavs(r):
+        ranges, hit, uav = T.range_scan_uavs(g, r, ground=True, hits=True, uavs=True, dtype=torch.float64)
+        assert same_bits(ranges.cpu().numpy(), uavs_want[r][0]) and np.array_equal(hit.cpu().numpy(), uavs_want[r][1]), r
+        assert np.array_equal(uav.cpu().numpy(), uavs_want[r][2]), r
+
+    def cost():
+        c, found = T.obstacle_cost(g, r1, k, HINGE2, 1.5, found=True)
+        assert same_bits(c.cpu().numpy(), cost_want) and np.array_equal(found.cpu().numpy(), near["found"])
+
+    def builds():
+        return g.obstacle_stats()["grid_builds"]
+
+    assert builds() == 0
+    for call, want in ((nearest, 1), (lambda: scan(r2), 2), (lambda: scan_uavs(r2), 2), (cost, 2), (lambda: scan_uavs(r3), 3), (lambda: scan(r3), 3)):
+        call()
+        assert builds() == want, want
+    for call in (nearest, lambda: scan(r3), lambda: scan_uavs(r3), cost, lambda: scan_uavs(r3), lambda: scan(r3)):  # r1 and r3 only: no build
+        call()
+        assert builds() == 3
+    assert g.obstacle_stats()["grid_radius"] == r1  # (the stats describe the queries' entry)
+    g.set_obstacles(ob)  # the same set again: both entries are dropped
+    assert builds() == 3 and g.obstacle_stats()["cells"] == 0
+    cost()
+    assert builds() == 4
+    scan_uavs(r3)
+    assert builds() == 5
+    scan(r3)
+    nearest()
+    assert builds() == 5
+    g.close()
+
+
 def test_clones(mrs):
     from mrs_multirotor_simulator_amd import tensors as T
     pos, worlds, ob = fixture_scene()

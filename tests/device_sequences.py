@@ -18,7 +18,33 @@ the world-aware kernels).  Ticks of a tick rollout count as steps.  SEEDS_EXT ho
 steps, and over all of them there are 27 rollout_ticks, 27 rollout_tick_cost, 25 rollout_feedback, 35 rollout_tick_feedback, 49
 proximity_cost and 13 set_worlds calls (counted by test_random_device_sequences.py).  Two conditions keep the comparison of these seeds honest, and the
 CPU dry run asserts both, so they are properties of the chosen seeds (contact_violations; near_quat_branch at the block starts of a
-feedback on the quaternion)."""
+feedback on the quaternion).
+
+A third surface.  SEEDS_SCENE and VARIANTS_SCENE (run_sequence(surface="scene"), seed numbers from 200 up, the flags of ext_flags) draw
+from everything the extended surface draws plus six kinds: set_obstacles, nearest_obstacles, obstacle_cost, set_scan_beams, range_scan
+and range_scan_uavs.  The oracle has neither obstacles nor beams: the generator keeps its own copies (draw_obstacles, draw_beams), sets
+both before the first call, replaces them in the middle of the run (the host call and the tensor call in turn) and compares
+get_obstacles() and get_scan_beams() with them, bit for bit, at every compare.  Each query and each scan is checked bit for bit
+against the restatements of test_obstacles.py, test_range_scan.py and test_range_scan_uavs.py on what the call reads: the FP64
+positions and attitudes of the whole swarm gathered right before it under the same stream context (a gather keeps a pending tick
+pending; the dry run takes the oracle's), the oracle's labels, and ground_z and arm_length + prop_radius of the oracle's parameters.
+Radius and max_range come from PALETTE.  All six kinds keep a pending collision tick pending; half of the time one of them is forced
+where a proximity cost is forced on the extended surface.  Behind a call that re-interns airframe types (TABLE_CALLS) the generator
+forces, half of the time, a range_scan without the ground flag and then a scan that reads the airframe table (the stale-table shape:
+only the second uploads it); behind a clone swap, set_worlds and set_obstacles, a scan.
+The grid cache is modelled as csrc/obstacle_set.h states it — two entries, the queries' keyed by radius and the scans' by max_range,
+both dropped by set_obstacles — and obstacle_stats()["grid_builds"] (which takes the lock only) is asserted against the model after
+every scene call.  What the header leaves open was read from csrc/obstacles.hip: set_obstacles itself builds nothing (it only marks
+both entries); an empty set is built and cached like any other (ensure() does not look at the size, and both scans call it); a clone
+adopts the set into an ObstacleSet of its own, so it starts with grid_builds == 0 and both entries empty (the clone of a swarm with an
+empty set has no set at all until a call needs one); mrs_swarm_obstacle_stats describes the queries' entry only.  Code and header
+agree.
+Over the 12 seeds of SEEDS_SCENE, 8 of them with worlds (SCENE_COUNTS, asserted exactly by test_random_device_sequences.py): 16
+set_obstacles, 16 nearest_obstacles, 17 obstacle_cost, 18 set_scan_beams, 41 range_scan and 21 range_scan_uavs calls, 16 of them behind
+a pending tick; scans that follow a call with no other scan in between: 9 set_ground_z, 8 set_params, 7 resets, 8 clone swaps, 7
+set_worlds, 12 set_obstacles; 10 stale-table shapes; beams taken by spheres 448, boxes 614, cylinders 4862, UAVs 2594, the ground 2725,
+nothing 64699; 2398 beams of range 0; 66 beams a UAV takes from an obstacle and 63 an obstacle keeps from a UAV; 65 query UAVs with
+found > k; grids built 29 (queries) and 53 (scans), cache hits 4 and 9."""
 import contextlib
 from collections import Counter
 
@@ -29,8 +55,13 @@ from helpers import FIELD_FLOOR, Pair
 from oracle import oracle_swarm as O
 from test_device_io_gpu import _runs
 from test_nearest_gpu import compare_with_numpy
+from test_obstacles import ALL_WORLDS, CYLINDER, OBSTACLE, restate_cost, restate_obstacles, restate_rows
+from test_obstacles import add_bits as obstacle_add_bits
+from test_obstacles import same_bits as same_typed_bits
 from test_proximity_cost import add_bits, proximity_ref, same_bits
 from test_random_sequences_gpu import DT, build_fleet, check, compare_outputs, host_op, payload, rng_range
+from test_range_scan import BODY_FRAME, GROUND, HIT_GROUND, HIT_NONE, MAX_BEAMS, mixed_beams, restate_scan
+from test_range_scan_uavs import HIT_UAV, NO_OBSTACLES, restate_scan_uavs
 from test_rollout_cost_gpu import restate
 from test_rollout_feedback_gpu import restate_feedback
 from test_rollout_tick_cost_gpu import restate_ticks
@@ -69,9 +100,27 @@ ROLLOUTS_EXT = ROLLOUTS + (ROLL_TICK, ROLL_TICK_COST, ROLL_FEEDBACK, ROLL_TICK_F
 STALL_ROLLOUTS = (ROLL_TICK_COST, ROLL_TICK_FEEDBACK)  # what the FAST_UAVS recipe forces in place of TICK_LONG, half of the time
 STALL_HORIZONS = (5, 12)                               # ... of at least four ticks
 WORLD_LABELS = (0, 7, -2000000000, 1234567890)
-OBS_POS = 1
+OBS_POS, OBS_R = 1, 8
+# the kinds of the scene surface (drawn by SEEDS_SCENE and VARIANTS_SCENE only, on top of everything the extended surface draws)
+SCENE_KINDS = (SET_OBSTACLES, NEAREST_OBSTACLES, OBSTACLE_COST, SET_BEAMS, RANGE_SCAN, RANGE_SCAN_UAVS) = tuple(range(41, 47))
+SCAN_BLIND, SCAN_TABLE = 47, 48  # never drawn, forced behind a table-changing call: a range_scan without the ground; a scan that reads the table
+SCANS = (RANGE_SCAN, RANGE_SCAN_UAVS)
+OP_NAMES.update({SET_OBSTACLES: "set_obstacles", NEAREST_OBSTACLES: "nearest_obstacles", OBSTACLE_COST: "obstacle_cost", SET_BEAMS: "set_scan_beams",
+                 RANGE_SCAN: "range_scan", RANGE_SCAN_UAVS: "range_scan_uavs"})
+PALETTE = (1.5, 3.0, 6.0)                       # radius and max_range: few enough values that cache hits and rebuilds both happen
+OBSTACLE_COUNTS = (0, 1, 5, 5, 24, 24, 48, 48)  # M of a drawn set: 0 one time in eight
+BEAM_COUNTS = (1, 7, 16, 64, 65)                # mixed_beams(nb); 65: a second beam group of the UAV scan with one live lane
+OBST_MAX = 512
+PAD_INT = -77  # what the slack columns of a padded int32 tensor hold, and a vector the call must overwrite
+ON_WIDTHS = (3, 3, 1)
+# host calls and device calls that re-intern airframe types: the device table is stale until some call uploads it
+TABLE_CALLS = {7: "set_mass", 8: "set_ground_z", 17: "set_params", RESET: "reset"}
+# what a scan is counted as following when none of the scans came in between
+SCAN_MARKS = {8: "set_ground_z", 17: "set_params", RESET: "reset", CLONE: "clone", SET_WORLDS: "set_worlds", SET_OBSTACLES: "set_obstacles"}
 # calls that enter through MRS_ENTER_COMMANDS (or do not enter at all): a collision tick that is pending stays pending across them
-KEEP_PENDING = (0, 1, 2, 3, 9, 15, DEV_SET_INPUT, GATHER, ASYNC_OUTPUTS, ASYNC_POSES, PROXIMITY)
+KEEP_PENDING = (0, 1, 2, 3, 9, 15, DEV_SET_INPUT, GATHER, ASYNC_OUTPUTS, ASYNC_POSES, PROXIMITY) + SCENE_KINDS
+# scene calls that upload no airframe table (a range_scan does under MRS_SCAN_GROUND, a UAV scan always)
+NO_TABLE_UPLOAD = (SET_OBSTACLES, NEAREST_OBSTACLES, OBSTACLE_COST, SET_BEAMS)
 
 
 def gather_width(groups):
@@ -359,6 +408,52 @@ class Stub:
         self._range(first, len(worlds))
         self.calls.append(("set_worlds", first, len(worlds)))
 
+    # ---- the scene calls: include/mrs_swarm.h, "static obstacles", "range scans", "range scans that see other UAVs" ----
+
+    def set_obstacles(self, ob, host):
+        assert ob.dtype == OBSTACLE and ob.ndim == 1 and len(ob) <= OBST_MAX
+        assert np.isin(ob["kind"], (0, 1, 2)).all() and not (ob["flags"] & ~np.uint32(ALL_WORLDS)).any() and not ob["reserved"].any()
+        assert np.isfinite(ob["c"]).all()
+        used = np.stack([np.ones(len(ob), bool), ob["kind"] == 1, ob["kind"] != 0], axis=1)
+        pillar = np.zeros((len(ob), 3), bool)
+        pillar[:, 2] = (ob["kind"] == CYLINDER) & (ob["h"][:, 2] == np.inf)
+        assert not (used & ~pillar & ~(np.isfinite(ob["h"]) & (ob["h"] >= 0))).any(), "sizes: finite and >= 0 (a cylinder's half-height may be +inf)"
+        self.calls.append(("set_obstacles", len(ob), host))
+
+    def set_beams(self, beams, host):
+        assert beams.ndim == 2 and beams.shape[1] == 3 and 1 <= len(beams) <= MAX_BEAMS, "the pattern is never cleared"
+        assert np.isfinite(beams).all() and (np.abs((beams * beams).sum(axis=1) - 1.0) <= 1e-9).all()
+        self.calls.append(("set_scan_beams", len(beams), host))
+
+    def _query(self, k, radius, first, count):
+        self._range(first, count)
+        assert 1 <= k <= 32 and np.isfinite(radius) and radius > 0
+
+    def nearest_obstacles(self, k, radius, fields, first, count, f32, pads):
+        self._query(k, radius, first, count)
+        assert 0 <= fields <= 7 and min(pads) >= 0, "unknown field bits, or a stride below k * the width of the fields / below k"
+        outputs = (fields != 0, True, True)  # rows, index, counts: tensors.py always passes the last two
+        assert any(outputs)
+        self.calls.append(("nearest_obstacles", k, radius, fields, first, count, f32, pads))
+
+    def obstacle_cost(self, k, radius, kind, weight, first, count, start, found):
+        self._query(k, radius, first, count)
+        assert kind in (0, 2) and np.isfinite(weight) and (start is None or start.shape == (count,)) and isinstance(found, bool)
+        self.calls.append(("obstacle_cost", k, radius, kind, weight, first, count, start is not None, found))
+
+    def range_scan(self, see_uavs, max_range, flags, first, count, f32, nb, pads, hits, uavs=False):
+        self._range(first, count)
+        assert np.isfinite(max_range) and max_range > 0 and not flags & ~(BODY_FRAME | GROUND) and 1 <= nb <= MAX_BEAMS
+        assert min(pads) >= 0, "a stride below n_beams"
+        assert isinstance(hits, bool) and isinstance(uavs, bool) and (see_uavs or not uavs)  # (the ranges are the output that is always there)
+        self.calls.append(("range_scan_uavs" if see_uavs else "range_scan", max_range, flags, first, count, f32, nb, pads, hits, uavs))
+
+    def scene_state(self):
+        return None
+
+    def grid_builds(self):
+        return None
+
     def async_issue(self, kind, first, count):
         self._range(first, count)
         self.open[kind].append(self.next_ticket)
@@ -573,6 +668,77 @@ class Device:
         with self.ctx():
             self.T.set_worlds(self.p.g, self.torch.tensor(worlds, dtype=self.torch.int32, device=self.dev), first)
 
+    # ---- the scene calls: padded int32 rows hold PAD_INT where float rows hold PAD_VALUE ----
+
+    def _ints(self, shape, pad):
+        big = self.torch.full(tuple(shape[:-1]) + (shape[-1] + pad,), PAD_INT, dtype=self.torch.int32, device=self.dev)
+        return big, big[..., :shape[-1]]
+
+    @staticmethod
+    def _down_ints(big, width, what):
+        host = big.cpu().numpy()
+        assert (host[..., width:] == PAD_INT).all(), f"{what}: the slack columns were written"
+        return host[..., :width]
+
+    def set_obstacles(self, ob, host):
+        torch = self.torch
+        with self.ctx():
+            if host:
+                self.p.g.set_obstacles(ob)
+            else:  # (the set travels through the host: tensors of the device and arrays both serve)
+                self.T.set_obstacles(self.p.g, ob["kind"], torch.tensor(ob["c"], dtype=torch.float64, device=self.dev),
+                                     torch.tensor(ob["h"], dtype=torch.float64, device=self.dev), worlds=ob["world"],
+                                     all_worlds=(ob["flags"] & ALL_WORLDS) != 0)
+
+    def set_beams(self, beams, host):
+        with self.ctx():
+            if host:
+                self.p.g.set_scan_beams(beams)
+            else:
+                self.T.set_scan_beams(self.p.g, self.torch.tensor(beams, dtype=self.torch.float64, device=self.dev))
+
+    def nearest_obstacles(self, k, radius, fields, first, count, f32, pads):
+        torch = self.torch
+        w = k * sum(ON_WIDTHS[b] for b in range(3) if fields >> b & 1)
+        with self.ctx():
+            big, out = self._empty((count, w), pads[0], f32) if fields else (None, None)
+            ibig, index = self._ints((count, k), pads[1])
+            counts = torch.full((count,), PAD_INT, dtype=torch.int32, device=self.dev)
+            rows, _, _ = self.T.nearest_obstacles(self.p.g, k, radius, fields, first, count, out=out, index=index, counts=counts)
+            assert (rows is None) == (fields == 0)
+            return (self._down(big, w, "nearest_obstacles") if fields else None), self._down_ints(ibig, k, "nearest_obstacles: index"), counts.cpu().numpy()
+
+    def obstacle_cost(self, k, radius, kind, weight, first, count, start, found):
+        torch = self.torch
+        with self.ctx():
+            out = None if start is None else torch.tensor(start, dtype=torch.float64, device=self.dev)
+            fnd = torch.full((count,), PAD_INT, dtype=torch.int32, device=self.dev) if found else False
+            cost, fnd = self.T.obstacle_cost(self.p.g, radius, k=k, kind=kind, weight=weight, first=first, count=count, out=out,
+                                             accumulate=start is not None, found=fnd)
+            return cost.cpu().numpy(), None if fnd is None else fnd.cpu().numpy()
+
+    def range_scan(self, see_uavs, max_range, flags, first, count, f32, nb, pads, hits, uavs=False):
+        name = "range_scan_uavs" if see_uavs else "range_scan"
+        body, ground = bool(flags & BODY_FRAME), bool(flags & GROUND)
+        with self.ctx():
+            big, out = self._empty((count, nb), pads[0], f32)
+            hbig, hview = self._ints((count, nb), pads[1]) if hits else (None, None)
+            ubig, uview = self._ints((count, nb), pads[2]) if uavs else (None, None)
+            if see_uavs:
+                got = self.T.range_scan_uavs(self.p.g, max_range, body, ground, first, count, out=out, hits=hview, uavs=uview)
+            else:
+                got = self.T.range_scan(self.p.g, max_range, body, ground, first, count, out=out, hits=hview) + (None,)
+            assert (got[1] is None) == (not hits) and (got[2] is None) == (not uavs), f"{name}: an output that was not asked for"
+            return (self._down(big, nb, name), self._down_ints(hbig, nb, name + ": hit") if hits else None,
+                    self._down_ints(ubig, nb, name + ": uav") if uavs else None)
+
+    def scene_state(self):
+        """(the obstacle set, the beam pattern) as the product returns them: both getters take the lock only"""
+        return self.p.g.get_obstacles(), self.p.g.get_scan_beams()
+
+    def grid_builds(self):
+        return self.p.g.obstacle_stats()["grid_builds"]  # (mrs_swarm_obstacle_stats takes the lock only: a pending tick stays pending)
+
     def async_issue(self, kind, first, count):
         return self.p.g.get_outputs_async(first, count) if kind == "outputs" else self.p.g.get_poses_async(first, count)
 
@@ -614,6 +780,90 @@ SEEDS_EXT = [ext_flags(s) for s in EXT_SEED_NUMBERS]
 # two more seeds per child-process variant, one per fleet and one of them with worlds
 VARIANTS_EXT = {"split": (108, 107), "pointer": (121, 102), "split+pointer": (105, 126)}
 
+# the seeds of the scene surface, from 200 up, with the flags of ext_flags (none takes the long horizon); chosen like EXT_SEED_NUMBERS
+SCENE_SEED_NUMBERS = (200, 201, 202, 203, 204, 205, 206, 222, 230, 242, 260, 280)
+SEEDS_SCENE = [ext_flags(s) for s in SCENE_SEED_NUMBERS]
+# one more seed per child-process variant
+VARIANTS_SCENE = {"split": 317, "pointer": 221, "split+pointer": 310}
+
+
+# what the 12 dry runs of SEEDS_SCENE add up to (scene_totals): test_random_device_sequences.py asserts these figures exactly, the GPU
+# module about half of each, there counted from the restatement of the product's own state
+SCENE_COUNTS = {"set_obstacles": 16, "nearest_obstacles": 16, "obstacle_cost": 17, "set_scan_beams": 18, "range_scan": 41, "range_scan_uavs": 21,
+                "scene_behind_pending": 16,
+                # scans that follow the call, no other scan in between; table-changing call, blind range_scan, scan that reads the table
+                "scan_after_set_ground_z": 9, "scan_after_set_params": 8, "scan_after_reset": 7, "scan_after_clone": 8, "scan_after_set_worlds": 7,
+                "scan_after_set_obstacles": 12, "stale_table_shapes": 10,
+                # beams by what took them, beams of range 0, beams a UAV takes from an obstacle and beams an obstacle keeps from a UAV
+                "hit_sphere": 448, "hit_box": 614, "hit_cylinder": 4862, "hit_uav": 2594, "hit_ground": 2725, "hit_none": 64699, "range_zero": 2398,
+                "uav_takes_from_obstacle": 66, "obstacle_keeps_from_uav": 63,
+                # query UAVs with more obstacles within the radius than slots, and with none; builds and hits of the two cache entries
+                "found_over_k": 65, "found_none": 958, "query_grid_builds": 29, "query_cache_hits": 4, "scan_grid_builds": 53, "scan_cache_hits": 9}
+
+
+def scene_totals(results):
+    """the figures of SCENE_COUNTS over the results of run_sequence: calls per scene kind, scene calls behind a pending collision tick,
+    and what the restatements and the cache model met"""
+    results = list(results)
+    total = {OP_NAMES[op]: sum(r["kinds"][op] for r in results) for op in SCENE_KINDS}
+    total["scene_behind_pending"] = sum(r["scene_behind_pending"] for r in results)
+    tally = sum((r["scene"] for r in results), Counter())
+    total.update({name: int(tally[name]) for name in SCENE_TALLIES})
+    return total
+
+
+SCENE_TALLIES = ("scan_after_set_ground_z", "scan_after_set_params", "scan_after_reset", "scan_after_clone", "scan_after_set_worlds",
+                 "scan_after_set_obstacles", "stale_table_shapes", "hit_sphere", "hit_box", "hit_cylinder", "hit_uav", "hit_ground", "hit_none",
+                 "range_zero", "uav_takes_from_obstacle", "obstacle_keeps_from_uav", "found_over_k", "found_none", "query_grid_builds",
+                 "query_cache_hits", "scan_grid_builds", "scan_cache_hits")
+
+
+def surface_of(seed):
+    """the surface a seed number belongs to"""
+    return "base" if seed < EXT_SEED_NUMBERS[0] else "ext" if seed < 200 else "scene"
+
+
+def draw_obstacles(rng):
+    """an obstacle set of the scene surface: M of OBSTACLE_COUNTS records, all three kinds, every other cylinder a pillar without ends,
+    centres in [-2, 11]^3 (the fleet lives in [0, 9]^3 + (0, 0, 0.5)), sizes 0.15 .. 1.0 m; from five obstacles on the last one sits about
+    1e3 m away, so that the grid's outlier clamp is walked; by threes, obstacles are in world 0, carry one of the labels UAVs carry, or
+    are ALL_WORLDS with a junk label"""
+    M = pick(rng, OBSTACLE_COUNTS)
+    idx = np.arange(M)
+    ob = np.zeros(M, OBSTACLE)
+    ob["kind"] = (idx + int(rng.integers(0, 3))) % 3
+    ob["c"] = rng.uniform(-2.0, 11.0, (M, 3))
+    ob["h"] = rng.uniform(0.15, 1.0, (M, 3))
+    ob["h"][np.flatnonzero(ob["kind"] == CYLINDER)[::2], 2] = np.inf
+    if M >= 5:
+        ob["c"][M - 1] = rng.uniform(0.9e3, 1.1e3, 3) * rng.choice([-1.0, 1.0], 3)
+    group = (idx // 3 + int(rng.integers(0, 3))) % 3
+    carried = rng.choice(np.array((0, 1, 2) + WORLD_LABELS, dtype=np.int32), M)
+    junk = rng.integers(-2 ** 31, 2 ** 31, M).astype(np.int32)
+    ob["world"] = np.where(group == 1, carried, np.where(group == 2, junk, 0))
+    ob["flags"] = np.where(group == 2, ALL_WORLDS, 0)
+    return ob
+
+
+def draw_beams(rng):
+    """a beam pattern of the scene surface: mixed_beams(nb) with nb of BEAM_COUNTS, or a ring of eight with the straight-down beam"""
+    which = int(rng.integers(0, len(BEAM_COUNTS) + 1))
+    if which < len(BEAM_COUNTS):
+        return mixed_beams(BEAM_COUNTS[which])
+    from mrs_multirotor_simulator_amd.tensors import scan_ring
+    return np.ascontiguousarray(np.concatenate([scan_ring(8), [[0.0, 0.0, -1.0]]]))
+
+
+def first_difference(got, want):
+    """where two arrays of one shape first differ in their bits, as text"""
+    got, want = np.asarray(got), np.asarray(want)
+    if got.shape != want.shape or got.dtype != want.dtype:
+        return f"shape / dtype {got.shape} {got.dtype} != {want.shape} {want.dtype}"
+    raw = np.dtype(f"u{got.dtype.itemsize}")
+    bad = np.argwhere(np.ascontiguousarray(got).view(raw) != np.ascontiguousarray(want).view(raw))
+    at = tuple(int(v) for v in bad[0])
+    return f"{len(bad)} of {got.size} values differ, the first at {at}: got {got[at]!r}, the restatement gives {want[at]!r}"
+
 
 # ---- the generator -----------------------------------------------------------------------------------------------------------------
 
@@ -634,7 +884,8 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
     surface: "base" draws from the first N_OPS kinds, as ever; "ext" from EXT_KINDS as well (SET_WORLDS only with `worlds`), forces any of
     ROLLOUTS_EXT where "base" forces one of ROLLOUTS, lets the FAST_UAVS recipe force a cost-carrying tick rollout in place of its run of
     ticks half of the time and a proximity cost follow a pending tick, takes the long horizon through a tick rollout, and counts
-    contact_violations at every collision pass of the oracle.
+    contact_violations at every collision pass of the oracle; "scene" is "ext" plus SCENE_KINDS (see the module docstring): its result
+    also holds scene_behind_pending and, under "scene", the Counter of what the restatements and the cache model met (SCENE_TALLIES).
     worlds: the whole swarm is labelled i % 3 before the first call.
     split: host call 12 steps in runs of five to seven launches, so that the two-stream form of step_n is taken.
     long_rollout: a shorter sequence whose first rollout takes LONG_HORIZON steps.
@@ -647,19 +898,30 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
     measured tick rollouts, contact_violations summed over the collision passes, and the UAVs near a quaternion branch boundary at a
     block start of a feedback on the quaternion."""
     n, n_iter = p.n, N_ITER_LONG if long_rollout else N_ITER
-    ext = surface == "ext"
-    assert surface in ("base", "ext") and (ext or not worlds)
-    n_ops, rollouts = N_OPS, ROLLOUTS
+    scene = surface == "scene"
+    ext = surface == "ext" or scene  # (the scene surface draws everything the extended one draws)
+    assert surface in ("base", "ext", "scene") and (ext or not worlds)
+    n_ops, rollouts, drawn = N_OPS, ROLLOUTS, ()
     if ext:
-        n_ops, rollouts = N_OPS + len(EXT_KINDS) - (0 if worlds else 1), ROLLOUTS_EXT
+        drawn = EXT_KINDS[:len(EXT_KINDS) - (0 if worlds else 1)] + (SCENE_KINDS if scene else ())  # (SET_WORLDS is the last of EXT_KINDS)
+        n_ops, rollouts = N_OPS + len(drawn), ROLLOUTS_EXT
     kinds, oplog = Counter(), []
+    tally = Counter()  # what the scene calls met, counted from the restatements
     res = dict(steps=0, kinds=kinds, log=oplog, quat_sign_cases=0, rollouts_behind_pending=0, worst_cost_ratio=0.0, tickets_waited=0,
                ext_rollouts_behind_pending=0, proximity_behind_pending=0, contact_violations=0, feedback_near_quat_branch=0, world_sets=[0, 0],
-               measured_tick_rollouts=0)
+               measured_tick_rollouts=0, scene_behind_pending=0, scene=tally)
     pos = build_fleet(p, rng, n, fleet, seed)
     p.both("set_input", 0, n, O.POSITION_CMD, payload(rng, 10, n, pos))
     if worlds:
         p.both("set_worlds", (np.arange(n) % 3).astype(np.int32), 0)
+    if scene:  # what the oracle does not have: the generator's own copies are part of the reference
+        ob, beams = draw_obstacles(rng), draw_beams(rng)
+        dev.set_obstacles(ob, True)
+        dev.set_beams(beams, True)
+        sets = [1, 1]                            # set_obstacles and set_scan_beams calls so far: the host call and the tensor call in turn
+        cache = {"query": None, "scan": None}    # the model of obstacle_set.h: what each entry is current for (None: dropped)
+        builds = 0                               # ... and grid_builds of the handle
+        since_scan, stale = set(), 0             # SCAN_MARKS since the last scan; 1: the device table is stale, 2: ... and a blind scan ran
     if ext:  # every collision pass of the oracle, whichever call makes it
         passes = p.o.handle_collisions
 
@@ -708,6 +970,34 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
         if got is not None:
             res["quat_sign_cases"] += compare_rows(got, want, R, groups, rtol, f32, what)
 
+    def touch(entry, key):
+        """the rule of obstacle_set.h for a cache entry: current for `key`, or built anew"""
+        nonlocal builds
+        if cache[entry] == key:
+            tally[entry + "_cache_hits"] += 1
+        else:
+            cache[entry], builds = key, builds + 1
+            tally[entry + "_grid_builds"] += 1
+
+    def scene_inputs():
+        """what a scene call reads, fetched right before it under the call's stream context: the FP64 positions and attitudes of the whole
+        swarm as the product holds them (a gather keeps a pending tick pending; the stub: the oracle's), and the oracle's labels"""
+        rows = dev.gather(OBS_POS | OBS_R, 0, n, False, 0)
+        if rows is None:
+            rows = ref_rows(p.o, 0, n, OBS_POS | OBS_R)[0]
+        return rows[:, :3], rows[:, 3:].reshape(n, 3, 3), labels()
+
+    def airframes():
+        """(ground_z, arm_length + prop_radius) per UAV, from the oracle's parameters as contact_violations takes them"""
+        par = [p.o.get_params(i) for i in range(n)]
+        return np.array([q.ground_z for q in par]), np.array([q.arm_length + q.prop_radius for q in par])
+
+    def exact(got, want, label):
+        assert np.array_equal(got, want), f"{label}: {first_difference(np.asarray(got, np.int64), np.asarray(want, np.int64))}"
+
+    def bits(got, want, label):
+        assert same_typed_bits(got, want), f"{label}: {first_difference(got, want)}"
+
     for it in range(n_iter):
         what = f"seed {seed}, call {it}"
         for kind in tickets:
@@ -718,7 +1008,11 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
         was_forced, measure = bool(forced), False
         op = forced.pop(0) if forced else int(rng.integers(0, n_ops))
         if op >= N_OPS and not was_forced:
-            op = EXT_KINDS[op - N_OPS]  # (33 and 34 are the two kinds that are never drawn)
+            op = drawn[op - N_OPS]  # (33 and 34 are the two kinds that are never drawn)
+        blind = table = False
+        if op in (SCAN_BLIND, SCAN_TABLE):  # the two scans of the stale-table shape
+            blind, table = op == SCAN_BLIND, op == SCAN_TABLE
+            op = RANGE_SCAN if blind or rng.integers(0, 2) else RANGE_SCAN_UAVS
         first, count = rng_range(rng, n)
         if model_due and not was_forced:  # (calls that belong together stay together)
             forced, op, first, count, model_due = [op], MODEL_ALL, 0, n, False  # (the call drawn for this turn comes next)
@@ -828,6 +1122,9 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
                 while tickets[kind]:
                     wait_oldest(kind, what)
             dev.clone_swap()
+            if scene:  # the clone owns a set of its own: no grid built yet, both entries empty (obstacles.hip: obstacles_copy adopts the set)
+                cache["query"] = cache["scan"] = None
+                builds = 0
         elif op == NEAREST:
             k, radius, fields, f32 = int(rng.integers(1, 9)), float(rng.uniform(0.5, 4.0)), int(rng.integers(0, 32)), bool(rng.integers(0, 2))
             dev.nearest(k, radius, fields, first, count, f32, worlds=labels())
@@ -1014,6 +1311,86 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
             else:
                 p.o.set_worlds(w, first)
                 dev.set_worlds(w, first)
+        elif op == SET_OBSTACLES:
+            ob = draw_obstacles(rng)
+            dev.set_obstacles(ob, sets[0] % 2 == 0)
+            sets[0] += 1
+            cache["query"] = cache["scan"] = None  # both entries served the old set; the setter itself builds nothing
+            oplog[-1] += (len(ob),)
+        elif op == SET_BEAMS:
+            beams = draw_beams(rng)
+            dev.set_beams(beams, sets[1] % 2 == 0)
+            sets[1] += 1
+            oplog[-1] += (len(beams),)
+        elif op in (NEAREST_OBSTACLES, OBSTACLE_COST):
+            # k: the largest one time in six, a small one (more obstacles within the radius than slots) two times, else any
+            k = (32, 0, 0, 33, 33, 33)[int(rng.integers(0, 6))]
+            k = k if k == 32 else int(rng.integers(1, 5)) if k == 0 else int(rng.integers(1, 33))
+            radius = pick(rng, PALETTE)
+            fields, f32, pads = int(rng.integers(0, 8)), bool(rng.integers(0, 2)), tuple(int(v) for v in rng.integers(0, 4, 2))
+            kind, weight, found = pick(rng, (0, 2)), float(rng.uniform(0.1, 2.0)), bool(rng.integers(0, 2))  # PROX_HINGE2, PROX_COUNT
+            start = rng.uniform(0.0, 5.0, count) if rng.integers(0, 2) else None
+            oplog[-1] += (k, radius)
+            sl = slice(first, first + count)
+            xs, Rs, lab = scene_inputs()
+            ref = restate_obstacles(xs, Rs, lab, ob, k, radius)
+            tally["found_over_k"] += int((ref["found"][sl] > k).sum())
+            tally["found_none"] += int((ref["found"][sl] == 0).sum())
+            touch("query", radius)
+            if op == NEAREST_OBSTACLES:
+                label = f"{what}: nearest_obstacles of {first}+{count}, k {k}, radius {radius}, fields {fields}, {'FP32' if f32 else 'FP64'}"
+                got = dev.nearest_obstacles(k, radius, fields, first, count, f32, pads)
+                if got is not None:
+                    exact(got[2], ref["count"][sl], label + ": counts")
+                    exact(got[1], ref["index"][sl], label + ": index")
+                    if fields:
+                        bits(got[0], restate_rows({key: v[sl] for key, v in ref.items()}, fields, np.float32 if f32 else np.float64), label + ": rows")
+            else:
+                label = f"{what}: obstacle_cost of {first}+{count}, k {k}, radius {radius}, kind {kind}"
+                got = dev.obstacle_cost(k, radius, kind, weight, first, count, start, found)
+                if got is not None:
+                    bits(got[0], obstacle_add_bits(start, restate_cost(ref, k, radius, kind, weight)[sl]), label + ": cost")
+                    assert (got[1] is None) == (not found), label
+                    if found:
+                        exact(got[1], ref["found"][sl], label + ": found")
+        elif op in SCANS:
+            see = op == RANGE_SCAN_UAVS
+            max_range, pads = pick(rng, PALETTE), tuple(int(v) for v in rng.integers(0, 4, 3))
+            body, ground, f32, hits, uavs = (bool(v) for v in rng.integers(0, 2, 5))
+            ground = (ground or (table and not see)) and not blind  # (the stale-table shape: a scan that reads no table, then one that does)
+            uavs = uavs and see
+            flags = (BODY_FRAME if body else 0) | (GROUND if ground else 0)
+            oplog[-1] += (max_range, flags, len(beams))
+            sl = slice(first, first + count)
+            xs, Rs, lab = scene_inputs()
+            gz, rad = airframes()
+            base = restate_scan(xs, Rs, lab, ob, beams, max_range, body)
+            if see:
+                want = restate_scan_uavs(xs, Rs, lab, rad, ob, beams, max_range, body, ground_z=gz if ground else None, base=base)
+                alone = restate_scan_uavs(xs, Rs, lab, rad, NO_OBSTACLES, beams, max_range, body)  # (what the UAVs alone would take)
+                tally["uav_takes_from_obstacle"] += int(((want[1][sl] == HIT_UAV) & (base[1][sl] >= 0)).sum())
+                tally["obstacle_keeps_from_uav"] += int(((want[1][sl] >= 0) & (alone[1][sl] == HIT_UAV)).sum())
+            else:
+                want = (restate_scan(xs, Rs, lab, ob, beams, max_range, body, ground_z=gz, base=base) if ground else base) + (None,)
+            h = want[1][sl]
+            for kind, name in enumerate(("hit_sphere", "hit_box", "hit_cylinder")):
+                tally[name] += int((ob["kind"][h[h >= 0]] == kind).sum())
+            for value, name in ((HIT_UAV, "hit_uav"), (HIT_GROUND, "hit_ground"), (HIT_NONE, "hit_none")):
+                tally[name] += int((h == value).sum())
+            tally["range_zero"] += int((want[0][sl] == 0.0).sum())
+            for mark in since_scan:
+                tally["scan_after_" + mark] += 1
+            since_scan.clear()
+            touch("scan", max_range)
+            label = (f"{what}: {OP_NAMES[op]} of {first}+{count}, {len(beams)} beams, max_range {max_range}, flags {flags}, "
+                     f"{'FP32' if f32 else 'FP64'}")
+            got = dev.range_scan(see, max_range, flags, first, count, f32, len(beams), pads, hits, uavs)
+            if got is not None:
+                bits(got[0], want[0][sl].astype(np.float32 if f32 else np.float64), label + ": ranges")
+                if hits:
+                    exact(got[1], want[1][sl], label + ": hit")
+                if uavs:
+                    exact(got[2], want[2][sl], label + ": uav")
         elif op in (ASYNC_OUTPUTS, ASYNC_POSES):
             kind = "outputs" if op == ASYNC_OUTPUTS else "poses"
             if len(tickets[kind]) == 2:
@@ -1034,8 +1411,30 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
             forced += [ticks] + [pick(rng, STALL_FOLLOWERS) for _ in range(2)]
         if op == 14 and not forced and rng.integers(0, 3) == 0:
             forced.append(pick(rng, rollouts))  # a rollout right behind the pending tick of a run
+        if scene and op in SCENE_KINDS:
+            res["scene_behind_pending"] += int(pending)
+            got = dev.grid_builds()
+            assert got is None or got == builds, (f"{what}: {OP_NAMES[op]}: grid_builds is {got}, the cache rule of obstacle_set.h gives {builds} "
+                                                  f"(entries current for {cache})")
         if ext and op in (13, 14, ROLL_TICK) and not measure and not forced and rng.integers(0, 2):
-            forced.append(PROXIMITY)  # the call that promises to leave the pending tick alone, right behind one
+            # a call that promises to leave the pending tick alone, right behind one
+            forced.append(pick(rng, SCENE_KINDS) if scene and rng.integers(0, 2) else PROXIMITY)
+        if scene:
+            if op in SCAN_MARKS:
+                since_scan.add(SCAN_MARKS[op])
+            # the stale-table shape: a call that re-interns airframe types, a range_scan that reads no table, a scan that reads it, and
+            # between them nothing that uploads the table (every stepping call does)
+            if op in TABLE_CALLS:
+                stale = 1
+            elif op == RANGE_SCAN and not ground:
+                stale = 2 if stale else 0
+            elif op in SCANS:
+                tally["stale_table_shapes"] += int(stale == 2)
+                stale = 0
+            elif op not in NO_TABLE_UPLOAD:
+                stale = 0
+            if (op in TABLE_CALLS or op in SCAN_MARKS) and not forced and it % 5 <= 2 and rng.integers(0, 2):
+                forced += [SCAN_BLIND, SCAN_TABLE] if op in TABLE_CALLS else [pick(rng, SCANS)]  # (the compare's steps do not come between)
         if op in (13, 14, TICK_LONG) or (op in TICK_ROLLOUTS and not measure):
             pending = True
         elif op not in KEEP_PENDING and not (op == MODEL_ALL and how < 2):
@@ -1044,10 +1443,16 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
             p.step(DT, 2)
             res["steps"] += 2
             pending = False
+            if scene:
+                stale = 0
             if dev.real:
                 check(p, rtol, f"{what} ({it + 1} calls)")
                 if ext:
                     assert np.array_equal(p.g.get_worlds(), p.o.get_worlds()), f"{what} ({it + 1} calls): world labels"
+                if scene:
+                    got_ob, got_beams = dev.scene_state()
+                    assert got_ob.tobytes() == ob.tobytes(), f"{what} ({it + 1} calls): get_obstacles() is not the set that was given"
+                    assert got_beams.tobytes() == beams.tobytes(), f"{what} ({it + 1} calls): get_scan_beams() is not the pattern that was given"
     for kind in tickets:
         while tickets[kind]:
             wait_oldest(kind, f"seed {seed}, end")

@@ -11,7 +11,17 @@ rollout_tick_cost, 25 rollout_feedback, 35 rollout_tick_feedback, 49 proximity_c
 horizon through a tick rollout.  The first surface draws what it drew before the second existed: the SHA-256 of every op log is
 recorded in tests/golden/device_sequence_logs.json.  The two conditions that keep the comparison of the extended seeds honest — no
 same-world pair near its contact threshold at a collision pass, no quaternion near a branch boundary where a feedback reads it — are
-asserted here, on the oracle alone, so they are properties of the chosen seeds."""
+asserted here, on the oracle alone, so they are properties of the chosen seeds.
+
+The scene surface (counted here, over the 12 seeds of SEEDS_SCENE, 8 of them with collision worlds, and asserted exactly against
+device_sequences.SCENE_COUNTS): 16 set_obstacles, 16 nearest_obstacles, 17 obstacle_cost, 18 set_scan_beams, 41 range_scan and 21
+range_scan_uavs calls, 16 of them behind a pending collision tick; scans that follow a call with no other scan in between: 9
+set_ground_z, 8 set_params, 7 resets, 8 clone swaps, 7 set_worlds, 12 set_obstacles; 10 stale-table shapes (a table-changing call, a
+range_scan without the ground, a scan that reads the table); from the restatements on the oracle's state: beams taken by spheres 448,
+boxes 614, cylinders 4862, UAVs 2594, the ground 2725, nothing 64699; 2398 beams of range 0; 66 beams a UAV takes from an obstacle, 63
+an obstacle keeps from a UAV; 65 query UAVs with found > k; from the cache model: 29 and 53 grids built for the queries and the scans,
+4 and 9 cache hits.  Their sequences keep the step budget and the two honesty conditions, and both earlier surfaces draw what they
+drew: the op logs of the extended surface, hashed before the scene surface existed, are in tests/golden/device_sequence_logs_ext.json."""
 import numpy as np
 import pytest
 
@@ -23,12 +33,13 @@ from oracle import oracle_swarm as O
 from test_rollout_cost_gpu import restate
 
 
-def dry_run(mrs, seed, split=False, ext=False):
-    _, fast, fleet, long_rollout, model, worlds = D.ext_flags(seed) if ext else D.SEEDS[seed] + (False,)
+def dry_run(mrs, seed, split=False):
+    surface = D.surface_of(seed)
+    _, fast, fleet, long_rollout, model, worlds = D.SEEDS[seed] + (False,) if surface == "base" else D.ext_flags(seed)
     p = D.StubPair(mrs, D.N_UAVS)
     dev = D.Stub(p)
     res = D.run_sequence(p, dev, mrs, np.random.default_rng(D.RNG_BASE + seed), seed, fast, fleet, D.seed_rtol(fast), D.STEP_CAP, split=split,
-                         long_rollout=long_rollout, model=model, surface="ext" if ext else "base", worlds=worlds)
+                         long_rollout=long_rollout, model=model, surface=surface, worlds=worlds)
     st = p.o.get_state()
     res["non_finite_uavs"] = int((~np.isfinite(np.concatenate([st[k].reshape(p.n, -1) for k in st], axis=1))).any(axis=1).sum())
     res["calls"], res["product_calls"] = dev.calls, p.g.calls
@@ -38,20 +49,34 @@ def dry_run(mrs, seed, split=False, ext=False):
 
 @pytest.fixture(scope="module")
 def runs(mrs):
-    """every sequence the GPU module runs: {(variant or None, seed): result}; the seeds of the extended surface are those from
-    D.EXT_SEED_NUMBERS[0] on, in every variant"""
-    out = {(None, seed): dry_run(mrs, seed) for seed, *_ in D.SEEDS}
-    out.update({(None, seed): dry_run(mrs, seed, ext=True) for seed, *_ in D.SEEDS_EXT})
+    """every sequence the GPU module runs: {(variant or None, seed): result}; a seed's number says which surface it draws from
+    (D.surface_of), in every variant"""
+    out = {(None, seed): dry_run(mrs, seed) for seed, *_ in D.SEEDS + D.SEEDS_EXT + D.SEEDS_SCENE}
     for name, (_, seeds, split) in D.VARIANTS.items():
-        for seed in seeds:
+        for seed in seeds + D.VARIANTS_EXT[name] + (D.VARIANTS_SCENE[name],):
             out[name, seed] = dry_run(mrs, seed, split=split)
-        for seed in D.VARIANTS_EXT[name]:
-            out[name, seed] = dry_run(mrs, seed, split=split, ext=True)
     return out
 
 
 def is_ext(key):
-    return key[1] >= D.EXT_SEED_NUMBERS[0]
+    """the sequences that draw the kinds of the extended surface: its own, and those of the scene surface"""
+    return D.surface_of(key[1]) != "base"
+
+
+def is_scene(key):
+    return D.surface_of(key[1]) == "scene"
+
+
+def log_hashes(runs):
+    import hashlib
+    return {f"{variant},{seed}": hashlib.sha256(repr(r["log"]).encode()).hexdigest() for (variant, seed), r in runs.items()}
+
+
+def golden(name):
+    import json
+    import os
+    with open(os.path.join(helpers.ROOT, "tests", "golden", name)) as f:
+        return json.load(f)
 
 
 @pytest.fixture(scope="module")
@@ -62,7 +87,13 @@ def base_runs(runs):
 @pytest.fixture(scope="module")
 def ext_runs(runs):
     """the sequences of the extended surface that run in the parent process: D.SEEDS_EXT"""
-    return {k: r for k, r in runs.items() if is_ext(k) and k[0] is None}
+    return {k: r for k, r in runs.items() if is_ext(k) and not is_scene(k) and k[0] is None}
+
+
+@pytest.fixture(scope="module")
+def scene_runs(runs):
+    """the sequences of the scene surface that run in the parent process: D.SEEDS_SCENE"""
+    return {k: r for k, r in runs.items() if is_scene(k) and k[0] is None}
 
 
 def test_step_cap_is_the_largest_total_of_the_existing_sequences(mrs):
@@ -109,13 +140,14 @@ def test_every_op_kind_occurs(base_runs):
 
 def test_the_first_surface_draws_what_it_always_drew(base_runs):
     """the op logs of the 28 seeds and the three variants, as they were before the extended surface existed: SHA-256 of repr(log)"""
-    import hashlib
-    import json
-    import os
-    with open(os.path.join(helpers.ROOT, "tests", "golden", "device_sequence_logs.json")) as f:
-        want = json.load(f)
-    got = {f"{variant},{seed}": hashlib.sha256(repr(r["log"]).encode()).hexdigest() for (variant, seed), r in base_runs.items()}
-    assert got == want
+    assert log_hashes(base_runs) == golden("device_sequence_logs.json")
+
+
+def test_the_extended_surface_draws_what_it_drew_before_the_scene_surface(runs):
+    """the op logs of the 20 extended seeds and their six variant runs, as they were before the scene surface existed"""
+    ext = {k: r for k, r in runs.items() if is_ext(k) and not is_scene(k)}
+    assert len(ext) == len(D.SEEDS_EXT) + sum(len(v) for v in D.VARIANTS_EXT.values())
+    assert log_hashes(ext) == golden("device_sequence_logs_ext.json")
 
 
 def test_every_kind_of_the_extended_surface_occurs(runs, ext_runs):
@@ -161,6 +193,51 @@ def test_every_kind_of_the_extended_surface_occurs(runs, ext_runs):
         for s in seeds:
             assert not split or runs[variant, s]["kinds"][12] >= 1, (variant, s)
             assert sum(runs[variant, s]["kinds"][op] for op in D.ROLLOUTS_EXT[4:]) >= 2, (variant, s)
+
+
+def test_every_kind_of_the_scene_surface_occurs(runs, scene_runs):
+    """the counts of the module docstrings, over D.SEEDS_SCENE: D.SCENE_COUNTS exactly, and what the seeds were chosen to show"""
+    flags = D.SEEDS_SCENE
+    assert len(scene_runs) == len(flags) == 12 and min(D.SCENE_SEED_NUMBERS) >= 200
+    assert 3 * sum(f[5] for f in flags) >= len(flags), "at least a third of the seeds carry world labels"
+    assert {f[1] for f in flags} == {False, True} and {f[2] for f in flags} == {"x500", "mixed"} and {f[0] % 2 for f in flags} == {0, 1}
+    total = D.scene_totals(scene_runs.values())
+    print("scene surface:", total)
+    assert total == D.SCENE_COUNTS
+    for op in D.SCENE_KINDS:
+        assert total[D.OP_NAMES[op]] >= 8, f"{D.OP_NAMES[op]} occurs {total[D.OP_NAMES[op]]} times over the seeds of the scene surface"
+    assert total["scene_behind_pending"] >= 3
+    for mark in D.SCAN_MARKS.values():
+        assert total["scan_after_" + mark] >= 5, mark
+    assert total["stale_table_shapes"] >= 3
+    for name in ("hit_sphere", "hit_box", "hit_cylinder", "hit_uav", "hit_ground", "hit_none", "range_zero", "uav_takes_from_obstacle",
+                 "obstacle_keeps_from_uav", "found_over_k", "query_grid_builds", "query_cache_hits", "scan_grid_builds", "scan_cache_hits"):
+        assert total[name] >= 1, name
+    calls = [c for r in scene_runs.values() for c in r["calls"]]
+    by_name = {name: [c for c in calls if c[0] == name] for name in ("set_obstacles", "set_scan_beams", "nearest_obstacles", "obstacle_cost",
+                                                                     "range_scan", "range_scan_uavs")}
+    # each set through the host call and through the tensor call; every size of a set and of a pattern
+    assert {c[2] for c in by_name["set_obstacles"]} == {False, True} == {c[2] for c in by_name["set_scan_beams"]}
+    assert {c[1] for c in by_name["set_obstacles"]} == set(D.OBSTACLE_COUNTS) and {c[1] for c in by_name["set_scan_beams"]} == set(D.BEAM_COUNTS) | {9}
+    # queries: both dtypes, k = 32, rows present and absent, every radius; costs: both kinds, a start vector or none, found or not
+    q = by_name["nearest_obstacles"]
+    assert {c[6] for c in q} == {False, True} and {c[3] != 0 for c in q} == {False, True} and any(c[1] == 32 for c in q)
+    assert {c[2] for c in q + by_name["obstacle_cost"]} == set(D.PALETTE) and any(max(c[7]) > 0 for c in q)
+    c = by_name["obstacle_cost"]
+    assert {v[3] for v in c} == {0, 2} and {v[7] for v in c} == {False, True} == {v[8] for v in c} and any(v[1] == 32 for v in c)
+    # scans: both dtypes, both frames, the ground on and off, every range, hits and UAV indices present and absent
+    for name in ("range_scan", "range_scan_uavs"):
+        s = by_name[name]
+        assert {v[5] for v in s} == {False, True} and {v[2] for v in s} == {0, 1, 2, 3} and {v[1] for v in s} == set(D.PALETTE), name
+        assert {v[8] for v in s} == {False, True} and any(max(v[7]) > 0 for v in s), name
+    assert {v[9] for v in by_name["range_scan_uavs"]} == {False, True} and not any(v[9] for v in by_name["range_scan"])
+    assert any(v[6] == 65 for v in by_name["range_scan_uavs"]), "a second beam group with one live lane"
+    # the child-process variants: one seed each; host call 12 where step_n is split
+    assert sorted(D.VARIANTS_SCENE) == sorted(D.VARIANTS)
+    for variant, (_, _, split) in D.VARIANTS.items():
+        r = runs[variant, D.VARIANTS_SCENE[variant]]
+        assert not split or r["kinds"][12] >= 1, variant
+        assert sum(r["kinds"][op] for op in D.SCANS) >= 2 and sum(r["kinds"][op] for op in D.SCENE_KINDS) >= 6, variant
 
 
 def test_the_extended_seeds_keep_their_comparison_honest(runs):

@@ -31,7 +31,20 @@ flags at the evaluations, handle_collisions); rows are compared like gathered ro
 first-order bound of its rows and the crash cost exactly, a proximity cost bit for bit against numpy on the positions the product
 holds.  Their counters must show a tick rollout that stalled and replayed a launch, a proximity cost and a rollout of the new kinds
 behind a collision tick that was still pending.  The stall and replay counters of a tick rollout are read around the call, and those
-reads evaluate a pending tick: the generator takes them where none is pending before the call, and treats none as pending behind it."""
+reads evaluate a pending tick: the generator takes them where none is pending before the call, and treats none as pending behind it.
+
+The scene surface (device_sequences.SEEDS_SCENE: 12 more seeds under test ids of their own, 8 of them with collision worlds, and one
+more seed per child-process variant) mixes in the static obstacles and the range scans: set_obstacles, nearest_obstacles, obstacle_cost,
+set_scan_beams, range_scan and range_scan_uavs, between calls that change what they read under them — set_ground_z, set_params,
+set_mass and masked resets (the airframe table), set_obstacles (both grid cache entries), set_worlds (the kernel instantiation), clone
+swaps (set, pattern and labels must travel).  Every query and scan is compared bit for bit with the numpy restatements on the
+positions and attitudes gathered right before the call; grid_builds is asserted against a model of the two-entry cache after every
+scene call; get_obstacles() and get_scan_beams() against the generator's copies at every compare.  Over the 12 dry runs (counted by
+test_random_device_sequences.py on the oracle's state): 16 set_obstacles, 16 nearest_obstacles, 17 obstacle_cost, 18 set_scan_beams, 41
+range_scan, 21 range_scan_uavs, 16 of them behind a pending tick; 10 stale-table shapes; beams taken by spheres 448, boxes 614,
+cylinders 4862, UAVs 2594, the ground 2725, nothing 64699, 2398 of range 0; 66 a UAV takes from an obstacle, 63 an obstacle keeps from
+a UAV; 65 query UAVs with found > k; 29 + 53 grids built, 4 + 9 cache hits.  This module counts the same figures from the restatement
+of the product's own state and asserts each at about half (scene_floor).  A scene seed takes 0.1 to 0.2 s on an MI355X."""
 import json
 import os
 import subprocess
@@ -40,7 +53,8 @@ import sys
 import numpy as np
 import pytest
 
-from device_sequences import N_UAVS, RNG_BASE, SEEDS, SEEDS_EXT, STEP_CAP, VARIANTS, VARIANTS_EXT, Device, ext_flags, run_sequence, seed_rtol
+from device_sequences import (N_UAVS, RNG_BASE, SCENE_COUNTS, SEEDS, SEEDS_EXT, SEEDS_SCENE, STEP_CAP, VARIANTS, VARIANTS_EXT, VARIANTS_SCENE, Device,
+                              ext_flags, run_sequence, scene_totals, seed_rtol, surface_of)
 from helpers import Pair
 
 pytestmark = pytest.mark.gpu
@@ -54,12 +68,13 @@ _results = {}  # seed -> what run_sequence returned (the seeds of the extended s
 _dead = []     # the first child process that died by a signal or timed out: nothing more is started on the GPU
 
 
-def run_seed(mrs, seed, split=False, ext=False):
-    _, fast, fleet, long_rollout, model, worlds = ext_flags(seed) if ext else SEEDS[seed] + (False,)
+def run_seed(mrs, seed, split=False):
+    surface = surface_of(seed)
+    _, fast, fleet, long_rollout, model, worlds = SEEDS[seed] + (False,) if surface == "base" else ext_flags(seed)
     p = Pair(mrs, N_UAVS, arith=mrs.ARITH_FAST if fast else mrs.ARITH_LITERAL)
     dev = Device(p, side=bool(seed % 2))
     res = run_sequence(p, dev, mrs, np.random.default_rng(RNG_BASE + seed), seed, fast, fleet, seed_rtol(fast), STEP_CAP, split=split,
-                       long_rollout=long_rollout, model=model, surface="ext" if ext else "base", worlds=worlds)
+                       long_rollout=long_rollout, model=model, surface=surface, worlds=worlds)
     assert p.g.get_diag() == p.o.get_diag()
     return res
 
@@ -80,26 +95,48 @@ def test_random_device_sequences_match_oracle(mrs, seed, fast, fleet, long_rollo
 
 @pytest.mark.parametrize("seed,fast,fleet,long_rollout,model,worlds", SEEDS_EXT)
 def test_random_sequences_of_the_extended_surface_match_oracle(mrs, seed, fast, fleet, long_rollout, model, worlds):
-    res = run_seed(mrs, seed, ext=True)
+    res = run_seed(mrs, seed)
     print(f"seed {seed} ({'FAST' if fast else 'LITERAL'}, {fleet}{', worlds' if worlds else ''}): {figures(res)}")
     _results[seed] = res
 
 
+@pytest.mark.parametrize("seed,fast,fleet,long_rollout,model,worlds", SEEDS_SCENE)
+def test_random_sequences_of_the_scene_surface_match_oracle_and_numpy(mrs, seed, fast, fleet, long_rollout, model, worlds):
+    import time
+    t0 = time.perf_counter()
+    res = run_seed(mrs, seed)
+    print(f"seed {seed} ({'FAST' if fast else 'LITERAL'}, {fleet}{', worlds' if worlds else ''}), {time.perf_counter() - t0:.1f} s: {figures(res)}\n"
+          f"scene: {scene_totals([res])}")
+    _results[seed] = res
+
+
+def scene_floor(count):
+    """what the GPU module asks of a figure that the CPU dry runs measured as `count`: about half (the restatement runs on the product's
+    own state here, which differs from the oracle's within the compare's tolerance)"""
+    return (count + 1) // 2
+
+
 def test_the_sequences_met_what_they_are_for():
-    assert len(_results) == len(SEEDS) + len(SEEDS_EXT), (f"only {len(_results)} of the {len(SEEDS) + len(SEEDS_EXT)} seeds ran to their end: this "
-                                                          "check speaks for all of them")
-    first = [r for s, r in _results.items() if s < len(SEEDS)]
+    n_seeds = len(SEEDS) + len(SEEDS_EXT) + len(SEEDS_SCENE)
+    assert len(_results) == n_seeds, f"only {len(_results)} of the {n_seeds} seeds ran to their end: this check speaks for all of them"
+    first = [r for s, r in _results.items() if surface_of(s) == "base"]
     total = {k: sum(figures(r)[k] for r in first) for k in figures(first[0])}
     print(f"all seeds: {total}")
     assert total["stalls"] >= 1 and total["replayed"] >= 1, f"no stall of the lazy collision ticks was replayed: {total}"
     assert total["reissued"] >= 1 and total["tickets_waited"] >= 1, f"no pipelined download was re-issued by a replay and waited for: {total}"
     assert total["rollouts_behind_pending"] >= 1, f"no rollout followed a collision tick that was still pending: {total}"
-    ext = [r for s, r in _results.items() if s >= len(SEEDS)]
+    ext = [r for s, r in _results.items() if surface_of(s) == "ext"]
     total = {k: sum(figures(r)[k] for r in ext) for k in figures(ext[0])}
     print(f"the seeds of the extended surface: {total}")
     assert total["stalls_in_tick_rollouts"] >= 1 and total["replayed_in_tick_rollouts"] >= 1, f"no tick rollout stalled and replayed a launch: {total}"
     assert total["proximity_behind_pending"] >= 1, f"no proximity cost followed a collision tick that was still pending: {total}"
     assert total["ext_rollouts_behind_pending"] >= 1, f"no tick or feedback rollout followed a collision tick that was still pending: {total}"
+    # the scene surface: every figure the CPU dry runs pinned (device_sequences.SCENE_COUNTS), here from the restatement of the product's state
+    total = scene_totals(r for s, r in _results.items() if surface_of(s) == "scene")
+    print(f"the seeds of the scene surface: {total}")
+    assert sorted(total) == sorted(SCENE_COUNTS)
+    for name, count in SCENE_COUNTS.items():
+        assert total[name] >= scene_floor(count), f"{name}: {total[name]} over the scene seeds, the dry runs on the oracle counted {count}"
 
 
 def child_main(out_path, variant):
@@ -107,8 +144,8 @@ def child_main(out_path, variant):
     M.load_library()
     _, seeds, split = VARIANTS[variant]
     out = {}
-    for seed, ext in [(s, False) for s in seeds] + [(s, True) for s in VARIANTS_EXT[variant]]:
-        out[str(seed)] = figures(run_seed(M, seed, split=split, ext=ext))
+    for seed in seeds + VARIANTS_EXT[variant] + (VARIANTS_SCENE[variant],):
+        out[str(seed)] = figures(run_seed(M, seed, split=split))
         print(f"{variant}: seed {seed}: {out[str(seed)]}", flush=True)
     with open(out_path, "w") as f:
         json.dump(out, f)
@@ -135,7 +172,7 @@ def test_variant_in_a_child_process(mrs, tmp_path, variant):
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     with open(out) as f:
         got = json.load(f)
-    assert sorted(got) == sorted(str(s) for s in seeds + VARIANTS_EXT[variant])
+    assert sorted(got) == sorted(str(s) for s in seeds + VARIANTS_EXT[variant] + (VARIANTS_SCENE[variant],))
     for seed, fig in got.items():
         if split:  # the two-stream form was taken: steps launched as two half-swarm launches
             assert fig["split_steps"] >= 4, f"{variant}, seed {seed}: step_n never took the two-stream form: {fig}"

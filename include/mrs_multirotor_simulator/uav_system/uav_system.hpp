@@ -843,6 +843,16 @@ public:
     mrs_throw_on_error(mrs_swarm_range_scan_uavs_device(s_, first, count, max_range, flags, dev_ranges, dtype, stride, dev_hit, hit_stride, dev_uav,
                                                         uav_stride, stream));
   }
+  // obstacle contacts (mrs_swarm_obstacle_contacts_device): UAVs [first, first + count) whose body sphere (arm_length + prop_radius, plus
+  // `margin`) touches a static obstacle, as dense device vectors of `count` elements, each may be null: dev_hit (1: touching), dev_index
+  // (the touching obstacle of smallest (sd, index), -1: none), dev_sd (its signed distance, +inf: none), dev_count (touching obstacles),
+  // dev_cost (+= hit_cost where touching).  flags MRS_CONTACT_CRASH: the touching UAVs are crashed as crash() does
+  void obstacleContactsDevice(int first, int count, double margin, uint32_t flags, uint8_t* dev_hit, int32_t* dev_index = nullptr,
+                              double* dev_sd = nullptr, int32_t* dev_count = nullptr, double* dev_cost = nullptr, double hit_cost = 0.0,
+                              void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_obstacle_contacts_device(s_, first, count, margin, flags, dev_hit, dev_index, dev_sd, dev_count, dev_cost,
+                                                          hit_cost, stream));
+  }
   // collision worlds (mrs_swarm_set_worlds): UAVs interact through the collision pass, and appear in each other's nearest-neighbour rows,
   // only if their 32-bit labels are equal (0 until set); the labels of UAVs [first, first + worlds.size())
   void setWorlds(int first, const std::vector<int32_t>& worlds) {

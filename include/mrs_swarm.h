@@ -575,7 +575,7 @@ int mrs_swarm_proximity_cost_device(mrs_swarm_t* s, int32_t first, int32_t count
 /* ---- static obstacles: a set of solids owned by the swarm, observed (nearest_obstacles) and penalised (obstacle_cost), never hit ----
  * Obstacles affect nothing but the two queries below: UAVs fly through them, and the step, the collision pass and every other call
  * behave exactly as without a set.  (Counting penetrations and masking a reset is the caller's business: MRS_PROX_COUNT with the body
- * radius.)
+ * radius.  A caller who wants UAVs to crash into obstacles asks for it: mrs_swarm_obstacle_contacts_device, "obstacle contacts" below.)
  * Kinds: MRS_OBST_SPHERE centre c, radius h[0]; MRS_OBST_BOX axis-aligned, centre c, half-extents h; MRS_OBST_CYLINDER vertical, centre c,
  * radius h[0], half-height h[2] (+inf: a pillar without ends; h[1] is not used, nor are a sphere's h[1], h[2]).
  * mrs_swarm_set_obstacles replaces the set (count 0 clears it) after validating all of it on the host: c finite; the used h entries
@@ -754,6 +754,46 @@ enum { MRS_UAVSCAN_HIT_UAV = -3 }; /* value of dev_hit besides those of the rang
 int mrs_swarm_range_scan_uavs_device(mrs_swarm_t* s, int32_t first, int32_t count, double max_range, uint32_t flags, void* dev_ranges,
                                      int32_t dtype, int32_t stride, int32_t* dev_hit /* may be NULL */, int32_t hit_stride,
                                      int32_t* dev_uav /* may be NULL */, int32_t uav_stride, void* ext_stream);
+
+/* ---- obstacle contacts: which UAVs touch a static obstacle, reported on the device and, on request, marked crashed ----
+ * The queries and scans above observe the obstacles; this call is the one that lets a UAV hit them.  It reports, per UAV, whether its
+ * body sphere touches an obstacle, and under MRS_CONTACT_CRASH marks the touching UAVs crashed exactly as UavSystem::crash() /
+ * mrs_swarm_crash does (uav_system.hpp:278): the next makeStep zeroes their motors and they fall.  Nothing else about the simulation
+ * changes: no rebound force, and without the call (or without the flag) UAVs keep flying through obstacles as before.
+ * For UAV i = first + k, everything FP64, one rounding per operation:
+ *     rad_i = arm_length + prop_radius   of its airframe type (the sphere of mrs_swarm_range_scan_uavs_device, the prefix of the collision
+ *                                        criterion), read from the airframe table, which is brought up to date before the launch
+ *     thr_i = rad_i + margin
+ *     C_i   = { j : obstacle j applies to i (its world label, or MRS_OBST_ALL_WORLDS) and sd_ij < thr_i }     (strictly)
+ * with sd_ij the signed distance of the static obstacles.  C_i is empty when a coordinate of p_i is not finite, and when thr_i is NaN
+ * (the comparison misses).  The outputs are dense vectors of `count` elements, each pointer may be NULL:
+ *     dev_hit[k]   = |C_i| > 0 ? 1 : 0
+ *     dev_count[k] = |C_i|                                        (not capped)
+ *     dev_index[k] = the j of the lexicographic minimum of (sd_ij, j) over C_i, or -1     (-0.0 == +0.0: such a tie goes to the lower index)
+ *     dev_sd[k]    = that sd_ij, or +inf
+ *     dev_cost[k]  = dev_cost[k] + hit_cost   where |C_i| > 0 (one addition); the element is not written elsewhere
+ * and under MRS_CONTACT_CRASH the flag word of UAV i gets the crashed bit OR-ed in where |C_i| > 0; the state of a UAV that touches
+ * nothing is not written.  The report is geometric: a crashed or held UAV is reported like any other, and marking twice is marking once.
+ * Entry.  Without MRS_CONTACT_CRASH no simulation state is written and the call enters like mrs_swarm_obstacle_cost_device: a pending
+ * collision tick stays pending, and a horizon cut at the call is the uncut horizon bit for bit.  With it the call enters like
+ * mrs_swarm_crash and mrs_swarm_reset_device: a pending collision tick is evaluated first.  Both forms fence the caller's stream in and
+ * out like the sibling calls.
+ * Refused with MRS_ERR_ARG (MRS_ERR_RANGE for the range), nothing written: unknown flag bits; a margin that is not finite or < 0; a
+ * hit_cost that is not finite when dev_cost is given; no output pointer and no MRS_CONTACT_CRASH; an output that is not device memory
+ * of the swarm's device holding `count` elements; a sharded swarm; R = fl(rmax + margin) not finite or not > 0, rmax being the largest
+ * finite rad of the swarm's airframe table.  count == 0 is MRS_OK after the checks.  An empty obstacle set is legal: nobody touches.
+ * The search structure is the grid of the static obstacles built for R, in a cache entry of the contacts' own beside the queries' and
+ * the scans' (a loop that alternates obstacle_cost, range_scan and obstacle_contacts builds three grids, not one per call;
+ * mrs_swarm_obstacle_stats keeps describing the queries' grid, grid_builds counts all three).  thr_i <= R for every UAV (rounding is
+ * monotone), so the one cell that contains p_i lists all of C_i; the kernel tests the world rule and sd < thr_i literally on what the
+ * cell lists, so the result depends on neither R, nor unused airframe types, nor the grid.  (An airframe whose rad is not
+ * finite is outside that argument.)
+ * Tunnelling is the caller's business: the test is a snapshot, not a sweep.  A contact with an obstacle of thickness w is missed only if
+ * the UAV travels more than w + 2 thr_i between two calls — at 10 m/s and the default airframe (thr = 0.4 m, margin 0) a call at least
+ * every 80 ms sees a wall of zero thickness. */
+enum { MRS_CONTACT_CRASH = 1 << 0 }; /* touching UAVs get crashed_, as UavSystem::crash() */
+int mrs_swarm_obstacle_contacts_device(mrs_swarm_t* s, int32_t first, int32_t count, double margin, uint32_t flags, uint8_t* dev_hit,
+                                       int32_t* dev_index, double* dev_sd, int32_t* dev_count, double* dev_cost, double hit_cost, void* ext_stream);
 
 /* ---- collision worlds: several scenes in one swarm that do not see each other (per-sample horizons of a sampling-based planner) ----
  * A world is a 32-bit label per UAV, 0 for every UAV until a setter says otherwise.  Two UAVs interact through the collision pass

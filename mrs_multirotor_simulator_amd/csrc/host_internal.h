@@ -8,7 +8,9 @@
 //   obstacles.hip         C ABI + kernels of the static obstacles (the set, the one routine that makes a cached grid current,
 //                         nearest-obstacle rows, the obstacle cost); obstacle_grid.h holds its pure functions, the kernels' view of a
 //                         grid and the cell walk (walk_cell) that both scans call (tested without a GPU: tests/cpp/obstacle_grid_test.cpp,
-//                         tests/cpp/obstacle_walk_test.cpp); obstacle_set.h the set, its two cache entries and the fill of that view
+//                         tests/cpp/obstacle_walk_test.cpp); obstacle_set.h the set, its three cache entries and the fill of that view
+//   obstacle_contact.hip  C ABI + kernel of the obstacle contacts (which UAVs touch an obstacle; the crash mark); obstacle_contact.h holds
+//                         its pure functions (tested without a GPU: tests/cpp/obstacle_contact_math_test.cpp)
 //   range_scan.hip        C ABI + kernel of the range scans (the beam pattern, the scan); range_scan_math.h holds its pure functions
 //                         (tested without a GPU: tests/cpp/range_scan_math_test.cpp); range_scan_common.h what it shares with the next
 //                         unit, once: argument block, beam set-up, obstacle pass, ground pass, stores, argument checks and fill
@@ -506,6 +508,7 @@ int    launch_crash_cost(mrs_swarm* s, int first, int count, double* dev_cost, d
 // ---- obstacles.hip ----
 int    obstacles_copy(mrs_swarm* dst, const mrs_swarm* src);  // the set of src into dst (clone)
 int    scan_grid(mrs_swarm* s, double max_range);              // the scans' cached obstacle grid (s->obst->scan) made current for max_range
+int    contact_grid(mrs_swarm* s, double R);                   // the contacts' cached obstacle grid (s->obst->contact) made current for R
 // ---- range_scan.hip ----
 int    scan_beams_copy(mrs_swarm* dst, const mrs_swarm* src);  // the beam pattern of src into dst (clone)
 int32_t       scan_beam_count(const mrs_swarm* s);             // beams of the pattern (0: none set)

@@ -139,6 +139,7 @@ ABI_SYMBOLS = [
     "mrs_swarm_nearest_obstacles_device", "mrs_swarm_obstacle_cost_device",
     "mrs_swarm_set_scan_beams", "mrs_swarm_get_scan_beams", "mrs_swarm_range_scan_device",
     "mrs_swarm_range_scan_uavs_device",
+    "mrs_swarm_obstacle_contacts_device",
 ]
 
 # device-resident callers (mrs_swarm_*_device): row element types and the observation groups of mrs_swarm_gather_device, in bit order
@@ -165,6 +166,8 @@ SCAN_BODY_FRAME, SCAN_GROUND = 1, 2
 SCAN_HIT_NONE, SCAN_HIT_GROUND = -1, -2
 # range scans that see other UAVs (mrs_swarm_range_scan_uavs_device): the value of a hit row where a UAV took the beam
 UAVSCAN_HIT_UAV = -3
+# obstacle contacts (mrs_swarm_obstacle_contacts_device): the flag that marks touching UAVs crashed
+CONTACT_CRASH = 1
 # state snapshots (mrs_swarm_save_device / mrs_swarm_load_device): one mrs_uav_snapshot_t record per UAV, 496 B
 SNAP_CRASHED, SNAP_TAKEOFF, SNAP_VPREV_SPLIT = 1, 2, 4
 SNAP_MAGIC = 0x50414E53
@@ -406,6 +409,7 @@ def load_library():
         "mrs_swarm_get_scan_beams": [vp, i32, vp, ip],
         "mrs_swarm_range_scan_device": [vp, i32, i32, C.c_double, C.c_uint32, vp, i32, i32, vp, i32, vp],
         "mrs_swarm_range_scan_uavs_device": [vp, i32, i32, C.c_double, C.c_uint32, vp, i32, i32, vp, i32, vp, i32, vp],
+        "mrs_swarm_obstacle_contacts_device": [vp, i32, i32, C.c_double, C.c_uint32, vp, vp, vp, vp, vp, C.c_double, vp],
         "mrs_swarm_save_device": [vp, i32, i32, vp, vp],
         "mrs_swarm_load_device": [vp, i32, i32, vp, C.c_int64, vp, vp, vp],
         "mrs_swarm_rollout_device": [vp, i32, i32, i32, C.c_double, i32, vp, i32, i32, C.c_uint32, vp, i32, vp],
@@ -978,6 +982,11 @@ class Swarm:
         _check(_lib.mrs_swarm_range_scan_uavs_device(self._h, int(first), int(count), C.c_double(float(max_range)), C.c_uint32(int(flags)),
                                                      dev_ranges or None, int(dtype), int(stride), dev_hit or None, int(hit_stride),
                                                      dev_uav or None, int(uav_stride), ext_stream or None))
+
+    def obstacle_contacts_device(self, first, count, margin, flags, dev_hit, dev_index, dev_sd, dev_count, dev_cost, hit_cost, ext_stream):
+        _check(_lib.mrs_swarm_obstacle_contacts_device(self._h, int(first), int(count), C.c_double(float(margin)), C.c_uint32(int(flags)),
+                                                       dev_hit or None, dev_index or None, dev_sd or None, dev_count or None, dev_cost or None,
+                                                       C.c_double(float(hit_cost)), ext_stream or None))
 
     def save_device(self, first, count, dev_records, ext_stream):
         _check(_lib.mrs_swarm_save_device(self._h, int(first), int(count), dev_records or None, ext_stream or None))

@@ -17,7 +17,7 @@ from .swarm import (ACTUATOR_CMD, ATTITUDE_CMD, DTYPE_F32, DTYPE_F64, INPUT_UNKN
                     OBS_RPM, OBS_VEL, OBS_VEL_BODY, PROX_COUNT, PROX_HINGE2, PROX_INVERSE, SNAP_BAD_AIRFRAME, SNAP_BAD_INDEX, SNAP_BAD_MAGIC, SNAP_CRASHED, SNAP_LOADED,
                     SNAP_MAGIC, SNAP_SKIPPED, SNAP_TAKEOFF, SNAP_VPREV_SPLIT, SNAPSHOT_DTYPE, TILT_HDG_RATE_CMD, gather_width, nearest_width,
                     OBST_ALL_WORLDS, OBST_BOX, OBST_CYLINDER, OBST_MAX, OBST_MAX_K, OBST_SPHERE, OBSTACLE_DTYPE, ON_ALL, ON_DIST, ON_REL, ON_REL_BODY,
-                    SCAN_BODY_FRAME, SCAN_GROUND, SCAN_HIT_GROUND, SCAN_HIT_NONE, SCAN_MAX_BEAMS, UAVSCAN_HIT_UAV, obstacle_width)
+                    SCAN_BODY_FRAME, SCAN_GROUND, SCAN_HIT_GROUND, SCAN_HIT_NONE, SCAN_MAX_BEAMS, UAVSCAN_HIT_UAV, CONTACT_CRASH, obstacle_width)
 
 _DTYPES = {torch.float64: DTYPE_F64, torch.float32: DTYPE_F32}
 SNAP_BYTES = SNAPSHOT_DTYPE.itemsize  # 496: one mrs_uav_snapshot_t
@@ -549,7 +549,7 @@ def set_obstacles(swarm, kinds, centres, sizes, worlds=None, all_worlds=None):
     OBST_BOX: axis-aligned, half-extents sizes; OBST_CYLINDER: vertical, radius sizes[:, 0], half-height sizes[:, 2], inf: a pillar
     without ends) at centres [M, 3]; sizes is [M, 3].  worlds [M] (default 0): the world label whose UAVs see the obstacle; all_worlds
     [M] bool (default False): seen by the UAVs of every label.  Tensors (of any device) or arrays: the set is static and travels through
-    the host.  M = 0 clears the set.  Obstacles are seen by nearest_obstacles() and obstacle_cost() only: UAVs fly through them."""
+    the host.  M = 0 clears the set.  Obstacles are seen by the queries and scans only: UAVs fly through them unless obstacle_contacts(crash=True) marks them."""
     import numpy as np
     kinds = _host_array(kinds, "kinds", np.int32, (-1,))
     m = len(kinds)
@@ -628,6 +628,66 @@ def obstacle_cost(swarm, radius, k=8, kind=PROX_HINGE2, weight=1.0, first=0, cou
         fptr = found.data_ptr()
     swarm.obstacle_cost_device(first, count, k, radius, kind, weight, out.data_ptr(), bool(accumulate), fptr, _stream(dev))
     return out, found
+
+
+def _contact_vector(t, name, count, dtype, dev):
+    """an optional [count] output of obstacle_contacts(): (tensor or None, pointer) — True: a new vector of `dtype`; a tensor: checked and
+    filled; None or False: none"""
+    if t is True:
+        t = torch.empty(count, dtype=dtype, device=torch.device("cuda", dev))
+    if t is False or t is None:
+        return None, 0
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be True, None or a {dtype} [{count}] tensor on the swarm's device, got {type(t).__name__}")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} has dtype {t.dtype}, expected {dtype}")
+    check_tensor(t, count, None, dtype, dev)
+    return t, t.data_ptr()
+
+
+def obstacle_contacts(swarm, margin=0.0, crash=False, first=0, count=None, hit=None, index=None, sd=None, counts=None, cost=None, hit_cost=0.0):
+    """Which UAVs of [first, first + count) touch a static obstacle (mrs_swarm_obstacle_contacts_device): UAV i touches obstacle j when j
+    applies to its world and the signed distance sd_ij < (arm_length + prop_radius) + margin of its airframe, strictly.  Returns
+    (hit, index, sd, counts), each a [count] vector on the swarm's device or None: hit uint8 (1: touching), index int32 (the touching
+    obstacle of smallest (sd, index), -1: none), sd float64 (that signed distance, inf: none), counts int32 (touching obstacles, not
+    capped).  Each takes True (a new vector), a tensor to fill, or None (not computed).  cost: a dense torch.float64 [count] vector,
+    cost[k] += hit_cost where UAV first + k touches (the vector of the cost rollouts; other elements are not written).  crash=True marks
+    the touching UAVs crashed as Swarm.crash() does — their motors stop at the next step and they fall — after evaluating a pending
+    collision tick; with crash=False no simulation state is written and a pending collision tick stays pending.  The test is a snapshot of
+    the positions, not a sweep: call it often enough for the speeds and walls at hand."""
+    import math
+    try:
+        margin = float(margin)
+    except (TypeError, ValueError):
+        raise ValueError(f"margin must be a finite number >= 0, got {margin!r}") from None
+    if not (math.isfinite(margin) and margin >= 0):
+        raise ValueError(f"margin must be a finite number >= 0, got {margin!r}")
+    count = _count(swarm, first, count)
+    if first < 0 or count < 0 or first + count > swarm.n:
+        raise ValueError(f"UAVs [{first}, {first + count}) do not fit a swarm of {swarm.n} UAVs")
+    dev = swarm.device()
+    hit, hit_ptr = _contact_vector(hit, "hit", count, torch.uint8, dev)
+    index, index_ptr = _contact_vector(index, "index", count, torch.int32, dev)
+    sd, sd_ptr = _contact_vector(sd, "sd", count, torch.float64, dev)
+    counts, counts_ptr = _contact_vector(counts, "counts", count, torch.int32, dev)
+    cost_ptr = 0
+    if cost is not None:
+        if not isinstance(cost, torch.Tensor):
+            raise ValueError(f"cost must be a torch.float64 [{count}] tensor on the swarm's device, got {type(cost).__name__}")
+        if cost.dtype != torch.float64:
+            raise ValueError(f"cost has dtype {cost.dtype}: the cost vector is always torch.float64")
+        check_tensor(cost, count, None, torch.float64, dev)
+        hit_cost = float(hit_cost)
+        if not math.isfinite(hit_cost):
+            raise ValueError(f"hit_cost must be finite, got {hit_cost!r}")
+        cost_ptr = cost.data_ptr()
+    if not crash and all(t is None for t in (hit, index, sd, counts, cost)):
+        raise ValueError("nothing to do: ask for an output (hit, index, sd, counts, cost) or crash=True")
+    if count == 0:  # (an empty vector has no address to hand over)
+        return hit, index, sd, counts
+    swarm.obstacle_contacts_device(first, count, margin, CONTACT_CRASH if crash else 0, hit_ptr, index_ptr, sd_ptr, counts_ptr, cost_ptr,
+                                   float(hit_cost) if cost_ptr else 0.0, _stream(dev))
+    return hit, index, sd, counts
 
 
 def scan_ring(n, elevation=0.0):

@@ -44,7 +44,43 @@ set_obstacles, 16 nearest_obstacles, 17 obstacle_cost, 18 set_scan_beams, 41 ran
 a pending tick; scans that follow a call with no other scan in between: 9 set_ground_z, 8 set_params, 7 resets, 8 clone swaps, 7
 set_worlds, 12 set_obstacles; 10 stale-table shapes; beams taken by spheres 448, boxes 614, cylinders 4862, UAVs 2594, the ground 2725,
 nothing 64699; 2398 beams of range 0; 66 beams a UAV takes from an obstacle and 63 an obstacle keeps from a UAV; 65 query UAVs with
-found > k; grids built 29 (queries) and 53 (scans), cache hits 4 and 9."""
+found > k; grids built 29 (queries) and 53 (scans), cache hits 4 and 9.
+
+A fourth surface.  SEEDS_CONTACT and VARIANTS_CONTACT (run_sequence(surface="contact"), seed numbers from 400 up — everything in
+[200, 400) stays a scene seed —, the flags of ext_flags) draw from everything the scene surface draws plus two kinds, both
+tensors.obstacle_contacts: OBSTACLE_CONTACTS, the read-only form, and CONTACT_MARK, the call with crash=True, the one scenery call that
+writes simulation state.  Range as every call draws it; margin from test_obstacle_contacts.MARGINS, for the marking form from
+MARK_MARGINS only (a margin of 1.0 would crash up to two thirds of the fleet); a random subset of hit / index / sd / counts, vectors to
+fill and True in turn, never empty for the read-only form, and one mark in four asks for nothing at all; half of the time a cost
+vector with a random hit_cost.  Every requested vector is compared bit for bit with restate_contacts and cost_after of
+test_obstacle_contacts.py on the FP64 positions gathered right before the call (scene_inputs), the oracle's labels and arm_length +
+prop_radius of the oracle's parameters.  Evaluating the pending tick moves no position: settle() drains — the same replay the gather
+has already made — and runs collide_now, which reads positions and writes forces and flag words (tick_single.hip), so the gather
+before a marking call sees what its kernel reads.  Behind the stall recipe the gather is made after the call instead (the mark writes
+flag words only), so that the marking call itself is the one that meets the stalled log.
+The oracle has no obstacles: the marking form crashes, on the oracle, the touching set of the restatement on the oracle's own
+positions (o.crash() on its runs), and the product's set — the restatement on the product's positions — must be that set.  A third
+honesty condition makes this a fair demand: signed distance is 1-Lipschitz in the position, positions that agree within delta_i = rtol
+* max(|x_i|_inf, FIELD_FLOOR["x"]) per component move sd by at most sqrt(3) delta_i, and obstacle_contact_violations counts the
+applicable pairs of a marking call's range with |sd - thr| < 2 sqrt(3) delta_i; the dry runs assert 0 for every contact seed.  After a
+mark no tick is pending (the kind is not in KEEP_PENDING; the read-only kind is), and the next crashed() call, crash rows, crash costs
+and the five-call compare see the marks.
+Forced, each half of the time where it applies: a mark as one of the two followers of the FAST_UAVS recipe behind a run of ticks (the
+stall is replayed before the mark, and no replayed launch may lose the marks); either form right behind a pending tick (13, 14,
+ROLL_TICK); behind a mark that newly crashed somebody a ROLL_TICK or ROLL_TICK_COST whose range covers one of them, with the crash
+rows asked for and a crash cost charged; a contact call behind TABLE_CALLS, a clone swap, set_worlds and set_obstacles (where the
+scene surface forces a scan, in turn with it); a mark right behind an async download that is still open two calls later.
+The cache model has a third entry, cache["contact"], keyed by fl(rmax + margin).  rmax is the maximum of arm_length + prop_radius over
+the airframe table, which never forgets: intern_type only appends, index 0 is the default parameter set, upload_types sends the whole
+table, and mrs_swarm_clone_resized copies keys and tparams whole while the clone's set starts with three empty entries and
+grid_builds == 0.  The generator keeps the running maximum over the default set and the oracle's parameters after every call (a call
+gives a UAV at most one new set); it never reads rmax back from the product.
+Over the 12 seeds of SEEDS_CONTACT, 7 of them with worlds, 2 with model-only phases (CONTACT_COUNTS, asserted exactly by
+test_random_device_sequences.py): 34 read-only and 59 marking calls, 12 and 13 of them behind a pending tick; 7 marks among the
+followers of a stall recipe, 25 while a download was open; 302 UAVs touching, 44 of them more than one obstacle, 94 newly marked, 53
+of those shown by the first crash row of a later tick rollout; 27 marks of nobody; contact calls that follow a call with no other
+contact call in between: 8 set_ground_z, 10 set_params, 8 resets, 10 clone swaps, 5 set_worlds, 12 set_obstacles; 66 grids built for
+the third entry, 27 cache hits.  No seed ends with more than half of its UAVs crashed."""
 import contextlib
 from collections import Counter
 
@@ -55,7 +91,8 @@ from helpers import FIELD_FLOOR, Pair
 from oracle import oracle_swarm as O
 from test_device_io_gpu import _runs
 from test_nearest_gpu import compare_with_numpy
-from test_obstacles import ALL_WORLDS, CYLINDER, OBSTACLE, restate_cost, restate_obstacles, restate_rows
+from test_obstacle_contacts import MARGINS, cost_after, restate_contacts
+from test_obstacles import ALL_WORLDS, CYLINDER, OBSTACLE, restate_cost, restate_obstacles, restate_rows, signed_distances
 from test_obstacles import add_bits as obstacle_add_bits
 from test_obstacles import same_bits as same_typed_bits
 from test_proximity_cost import add_bits, proximity_ref, same_bits
@@ -119,8 +156,20 @@ TABLE_CALLS = {7: "set_mass", 8: "set_ground_z", 17: "set_params", RESET: "reset
 SCAN_MARKS = {8: "set_ground_z", 17: "set_params", RESET: "reset", CLONE: "clone", SET_WORLDS: "set_worlds", SET_OBSTACLES: "set_obstacles"}
 # calls that enter through MRS_ENTER_COMMANDS (or do not enter at all): a collision tick that is pending stays pending across them
 KEEP_PENDING = (0, 1, 2, 3, 9, 15, DEV_SET_INPUT, GATHER, ASYNC_OUTPUTS, ASYNC_POSES, PROXIMITY) + SCENE_KINDS
-# scene calls that upload no airframe table (a range_scan does under MRS_SCAN_GROUND, a UAV scan always)
+# scene calls that upload no airframe table (a range_scan does under MRS_SCAN_GROUND, a UAV scan always; so do both contact calls)
 NO_TABLE_UPLOAD = (SET_OBSTACLES, NEAREST_OBSTACLES, OBSTACLE_COST, SET_BEAMS)
+# the kinds of the contact surface (drawn by SEEDS_CONTACT and VARIANTS_CONTACT only, on top of everything the scene surface draws):
+# tensors.obstacle_contacts without the mark (enters like obstacle_cost: a pending tick stays pending) and with crash=True (enters
+# through settle(): the pending tick is evaluated first, so the kind is not in KEEP_PENDING)
+CONTACT_KINDS = (OBSTACLE_CONTACTS, CONTACT_MARK) = (49, 50)
+MARK_BEHIND_STALL = 51  # never drawn, forced in place of a follower of the FAST_UAVS recipe: a CONTACT_MARK that must replay the stall
+OP_NAMES.update({OBSTACLE_CONTACTS: "obstacle_contacts", CONTACT_MARK: "contact_mark"})
+KEEP_PENDING += (OBSTACLE_CONTACTS,)
+# margins of the marking form: on the sequence fleets with the 48-obstacle sets of draw_obstacles a margin of 1.0 touches up to 99 of the
+# 150 UAVs, 0.25 at most 52, 0.0 at most 31 (counted on the CPU over 48 fleet / set draws): the sequence must stay one of flying UAVs
+MARK_MARGINS = (0.0, 0.25)
+CONTACT_OUTPUTS = ("hit", "index", "sd", "counts")
+CONTACT_SENTINEL = {"hit": 3, "index": PAD_INT, "sd": 7.25, "counts": PAD_INT}  # what a vector to fill holds before the call
 
 
 def gather_width(groups):
@@ -211,6 +260,31 @@ def contact_violations(o, rtol):
         close = np.abs(d2 - (r[:, None] + r[None, :])) < 2.0 * moves
     pair = (w[:, None] == w[None, :]) & fin[:, None] & fin[None, :]
     return int(np.triu(close & pair, 1).sum())
+
+
+def airframes_of(o):
+    """(ground_z [n], arm_length + prop_radius [n]) of the oracle swarm's parameters, the radius as contact_violations forms it"""
+    par = [o.get_params(i) for i in range(o.n)]
+    return np.array([q.ground_z for q in par]), np.array([q.arm_length + q.prop_radius for q in par])
+
+
+def obstacle_contact_violations(o, ob, rad, margin, first, count, rtol):
+    """the (UAV, obstacle) pairs of the range that a marking contact call could decide the other way within the compare's tolerance.
+    The signed distance of every obstacle kind is 1-Lipschitz in the position, so positions that agree within delta_i = rtol *
+    max(|x_i|_inf, FIELD_FLOOR["x"]) per component move sd by at most sqrt(3) delta_i; an applicable pair (the obstacle is ALL_WORLDS or
+    carries the UAV's label; the position is finite) counts unless |sd - thr_i| is at least twice that, thr_i = rad_i + margin (the 2
+    is margin over the derived bound, as in contact_violations, not a measurement)."""
+    if len(ob) == 0 or count == 0:
+        return 0
+    sl = slice(first, first + count)
+    x, w = o.get_state()["x"][sl], o.get_worlds()[sl]
+    thr = np.broadcast_to(np.asarray(rad, np.float64), (o.n,))[sl] + np.float64(margin)
+    with np.errstate(invalid="ignore", over="ignore"):
+        sd, _ = signed_distances(x, ob)
+        delta = rtol * np.maximum(np.abs(x).max(axis=1), FIELD_FLOOR["x"])
+        close = np.abs(sd - thr[:, None]) < 2.0 * np.sqrt(3.0) * delta[:, None]
+    applies = ((ob["flags"] & ALL_WORLDS) != 0)[None, :] | (ob["world"][None, :] == w[:, None].astype(np.int32))
+    return int((close & applies & np.isfinite(x).all(axis=1)[:, None]).sum())
 
 
 # ---- the product side --------------------------------------------------------------------------------------------------------------
@@ -447,6 +521,16 @@ class Stub:
         assert min(pads) >= 0, "a stride below n_beams"
         assert isinstance(hits, bool) and isinstance(uavs, bool) and (see_uavs or not uavs)  # (the ranges are the output that is always there)
         self.calls.append(("range_scan_uavs" if see_uavs else "range_scan", max_range, flags, first, count, f32, nb, pads, hits, uavs))
+
+    def obstacle_contacts(self, margin, crash, first, count, outs, fill, start, hit_cost):
+        """include/mrs_swarm.h, "obstacle contacts": the range; a finite margin >= 0; a finite hit_cost when a cost vector is given; no
+        output and no mark is refused ("nothing to do")"""
+        self._range(first, count)
+        assert isinstance(crash, bool) and isinstance(fill, bool) and np.isfinite(margin) and margin >= 0
+        assert set(outs) <= set(CONTACT_OUTPUTS) and len(set(outs)) == len(outs)
+        assert start is None or (start.shape == (count,) and np.isfinite(hit_cost))
+        assert crash or outs or start is not None, "nothing to do"
+        self.calls.append(("obstacle_contacts", margin, crash, first, count, tuple(outs), fill, start is not None, hit_cost))
 
     def scene_state(self):
         return None
@@ -732,6 +816,26 @@ class Device:
             return (self._down(big, nb, name), self._down_ints(hbig, nb, name + ": hit") if hits else None,
                     self._down_ints(ubig, nb, name + ": uav") if uavs else None)
 
+    def obstacle_contacts(self, margin, crash, first, count, outs, fill, start, hit_cost):
+        """the outputs named in `outs` (fill: vectors holding CONTACT_SENTINEL that the call must overwrite and hand back; else True: new
+        vectors) and, with `start`, the cost vector after the call: {name: numpy}"""
+        torch = self.torch
+        dtypes = {"hit": torch.uint8, "index": torch.int32, "sd": torch.float64, "counts": torch.int32}
+        with self.ctx():
+            kw = {name: torch.full((count,), CONTACT_SENTINEL[name], dtype=dtypes[name], device=self.dev) if fill else True for name in outs}
+            cost = None if start is None else torch.tensor(start, dtype=torch.float64, device=self.dev)
+            got = self.T.obstacle_contacts(self.p.g, margin, crash, first, count, cost=cost, hit_cost=hit_cost, **kw)
+            res = {}
+            for name, t in zip(CONTACT_OUTPUTS, got):
+                assert (t is None) == (name not in outs), f"obstacle_contacts: {name}: an output that was not asked for, or none that was"
+                if t is not None:
+                    assert not fill or t is kw[name], f"obstacle_contacts: {name}: not the vector that was given"
+                    assert t.shape == (count,) and t.dtype == dtypes[name]
+                    res[name] = t.cpu().numpy()
+            if cost is not None:
+                res["cost"] = cost.cpu().numpy()
+            return res
+
     def scene_state(self):
         """(the obstacle set, the beam pattern) as the product returns them: both getters take the lock only"""
         return self.p.g.get_obstacles(), self.p.g.get_scan_beams()
@@ -818,9 +922,49 @@ SCENE_TALLIES = ("scan_after_set_ground_z", "scan_after_set_params", "scan_after
                  "query_cache_hits", "scan_grid_builds", "scan_cache_hits")
 
 
+# the seeds of the contact surface, from 400 up (VARIANTS_SCENE took numbers above 300), with the flags of ext_flags; chosen like
+# EXT_SEED_NUMBERS: candidates that keep the three honesty conditions, the limits of test_the_oracle_stays_usable and the conditions
+# test_random_device_sequences.py states for them
+CONTACT_SEED_NUMBERS = (415, 422, 428, 437, 446, 450, 470, 471, 472, 474, 484, 500)
+SEEDS_CONTACT = [ext_flags(s) for s in CONTACT_SEED_NUMBERS]
+# one more seed per child-process variant
+VARIANTS_CONTACT = {"split": 565, "pointer": 411, "split+pointer": 545}
+
+# what the 12 dry runs of SEEDS_CONTACT add up to (contact_totals): asserted exactly by test_random_device_sequences.py, at scene_floor
+# by the GPU module, there counted from the restatement on the product's state
+CONTACT_COUNTS = {"obstacle_contacts": 34, "contact_mark": 59, "contacts_behind_pending": 12, "marks_behind_pending": 13,
+                  # marks among the followers of the stall recipe; marks while a pipelined download is open
+                  "marks_behind_stall": 7, "marks_with_open_ticket": 25,
+                  # UAVs of the ranges that touch, that touch more than one obstacle, that a mark crashed first, and of those the ones
+                  # a later tick rollout showed in its first crash row; marking calls over an empty touching set
+                  "uavs_touching": 302, "uavs_touching_several": 44, "uavs_newly_marked": 94, "marked_seen_in_crash_row": 53,
+                  "marks_of_nobody": 27,
+                  # contact calls that follow the call, no other contact call in between
+                  "contact_after_set_ground_z": 8, "contact_after_set_params": 10, "contact_after_reset": 8, "contact_after_clone": 10,
+                  "contact_after_set_worlds": 5, "contact_after_set_obstacles": 12,
+                  # builds and hits of the third cache entry
+                  "contact_grid_builds": 66, "contact_cache_hits": 27}
+CONTACT_TALLIES = ("marks_behind_stall", "marks_with_open_ticket", "uavs_touching", "uavs_touching_several", "uavs_newly_marked",
+                   "marked_seen_in_crash_row", "marks_of_nobody", "contact_after_set_ground_z", "contact_after_set_params",
+                   "contact_after_reset", "contact_after_clone", "contact_after_set_worlds", "contact_after_set_obstacles",
+                   "contact_grid_builds", "contact_cache_hits")
+
+
+def contact_totals(results):
+    """the figures of CONTACT_COUNTS over the results of run_sequence: calls per contact kind, those behind a pending collision tick by
+    form, and what the restatement and the cache model met"""
+    results = list(results)
+    total = {OP_NAMES[op]: sum(r["kinds"][op] for r in results) for op in CONTACT_KINDS}
+    total["contacts_behind_pending"] = sum(r["contacts_behind_pending"] for r in results)
+    total["marks_behind_pending"] = sum(r["marks_behind_pending"] for r in results)
+    tally = sum((r["scene"] for r in results), Counter())
+    total.update({name: int(tally[name]) for name in CONTACT_TALLIES})
+    return total
+
+
 def surface_of(seed):
     """the surface a seed number belongs to"""
-    return "base" if seed < EXT_SEED_NUMBERS[0] else "ext" if seed < 200 else "scene"
+    return "base" if seed < EXT_SEED_NUMBERS[0] else "ext" if seed < 200 else "scene" if seed < 400 else "contact"
 
 
 def draw_obstacles(rng):
@@ -885,7 +1029,9 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
     ROLLOUTS_EXT where "base" forces one of ROLLOUTS, lets the FAST_UAVS recipe force a cost-carrying tick rollout in place of its run of
     ticks half of the time and a proximity cost follow a pending tick, takes the long horizon through a tick rollout, and counts
     contact_violations at every collision pass of the oracle; "scene" is "ext" plus SCENE_KINDS (see the module docstring): its result
-    also holds scene_behind_pending and, under "scene", the Counter of what the restatements and the cache model met (SCENE_TALLIES).
+    also holds scene_behind_pending and, under "scene", the Counter of what the restatements and the cache model met (SCENE_TALLIES);
+    "contact" is "scene" plus CONTACT_KINDS: its result also holds contacts_behind_pending, marks_behind_pending,
+    obstacle_contact_violations summed over the marking calls, crashed_at_end, and CONTACT_TALLIES in the same Counter.
     worlds: the whole swarm is labelled i % 3 before the first call.
     split: host call 12 steps in runs of five to seven launches, so that the two-stream form of step_n is taken.
     long_rollout: a shorter sequence whose first rollout takes LONG_HORIZON steps.
@@ -898,18 +1044,21 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
     measured tick rollouts, contact_violations summed over the collision passes, and the UAVs near a quaternion branch boundary at a
     block start of a feedback on the quaternion."""
     n, n_iter = p.n, N_ITER_LONG if long_rollout else N_ITER
-    scene = surface == "scene"
-    ext = surface == "ext" or scene  # (the scene surface draws everything the extended one draws)
-    assert surface in ("base", "ext", "scene") and (ext or not worlds)
+    contact = surface == "contact"
+    scene = surface == "scene" or contact  # (the contact surface draws everything the scene surface draws)
+    ext = surface == "ext" or scene        # (... and the scene surface everything the extended one draws)
+    assert surface in ("base", "ext", "scene", "contact") and (ext or not worlds)
     n_ops, rollouts, drawn = N_OPS, ROLLOUTS, ()
     if ext:
         drawn = EXT_KINDS[:len(EXT_KINDS) - (0 if worlds else 1)] + (SCENE_KINDS if scene else ())  # (SET_WORLDS is the last of EXT_KINDS)
+        drawn += CONTACT_KINDS if contact else ()
         n_ops, rollouts = N_OPS + len(drawn), ROLLOUTS_EXT
     kinds, oplog = Counter(), []
     tally = Counter()  # what the scene calls met, counted from the restatements
     res = dict(steps=0, kinds=kinds, log=oplog, quat_sign_cases=0, rollouts_behind_pending=0, worst_cost_ratio=0.0, tickets_waited=0,
                ext_rollouts_behind_pending=0, proximity_behind_pending=0, contact_violations=0, feedback_near_quat_branch=0, world_sets=[0, 0],
-               measured_tick_rollouts=0, scene_behind_pending=0, scene=tally)
+               measured_tick_rollouts=0, scene_behind_pending=0, scene=tally, contacts_behind_pending=0, marks_behind_pending=0,
+               obstacle_contact_violations=0)
     pos = build_fleet(p, rng, n, fleet, seed)
     p.both("set_input", 0, n, O.POSITION_CMD, payload(rng, 10, n, pos))
     if worlds:
@@ -922,6 +1071,17 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
         cache = {"query": None, "scan": None}    # the model of obstacle_set.h: what each entry is current for (None: dropped)
         builds = 0                               # ... and grid_builds of the handle
         since_scan, stale = set(), 0             # SCAN_MARKS since the last scan; 1: the device table is stale, 2: ... and a blind scan ran
+    if contact:
+        cache["contact"] = None  # the third entry, current for fl(rmax + margin)
+        # rmax: the largest arm_length + prop_radius of the airframe table, which never forgets an entry (host_api.hip: intern_type only
+        # appends; mrs_swarm_clone_resized copies keys and tparams whole).  Index 0 is the default parameter set; every other entry is
+        # a set some UAV held, and a call gives a UAV at most one new set, so the running maximum over the oracle's parameters after
+        # every call is the table's maximum.  Never read back from the product.
+        dflt = O.default_params()
+        rmax = max(float(np.float64(dflt.arm_length) + np.float64(dflt.prop_radius)), float(airframes_of(p.o)[1].max()))
+        since_contact = set()                    # SCAN_MARKS since the last contact call
+        marked = set()                           # UAVs a CONTACT_MARK newly marked and no tick rollout's crash row has shown yet
+        contact_calls, cover = 0, None                # calls so far; the UAV the range of a forced tick rollout is to cover
     if ext:  # every collision pass of the oracle, whichever call makes it
         passes = p.o.handle_collisions
 
@@ -989,8 +1149,7 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
 
     def airframes():
         """(ground_z, arm_length + prop_radius) per UAV, from the oracle's parameters as contact_violations takes them"""
-        par = [p.o.get_params(i) for i in range(n)]
-        return np.array([q.ground_z for q in par]), np.array([q.arm_length + q.prop_radius for q in par])
+        return airframes_of(p.o)
 
     def exact(got, want, label):
         assert np.array_equal(got, want), f"{label}: {first_difference(np.asarray(got, np.int64), np.asarray(want, np.int64))}"
@@ -1013,7 +1172,16 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
         if op in (SCAN_BLIND, SCAN_TABLE):  # the two scans of the stale-table shape
             blind, table = op == SCAN_BLIND, op == SCAN_TABLE
             op = RANGE_SCAN if blind or rng.integers(0, 2) else RANGE_SCAN_UAVS
+        behind_stall = op == MARK_BEHIND_STALL  # the mark among the followers of the stall recipe
+        if behind_stall:
+            op = CONTACT_MARK
         first, count = rng_range(rng, n)
+        show = False
+        if contact and cover is not None:  # a tick rollout forced behind a mark: its range covers a UAV that was marked, its crash row
+            if was_forced and op in (ROLL_TICK, ROLL_TICK_COST):  # is asked for and its crash cost charged
+                lo, hi = min(first, cover), max(first + count, cover + 1)
+                first, count, show = lo, hi - lo, True
+            cover = None
         if model_due and not was_forced:  # (calls that belong together stay together)
             forced, op, first, count, model_due = [op], MODEL_ALL, 0, n, False  # (the call drawn for this turn comes next)
         x = p.o.get_state(first, count)["x"]
@@ -1098,6 +1266,8 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
                 po.takeoff_patch_enabled = int(takeoff)  # the flag of the call replaces the UAV's own
                 p.o.construct(first + int(i), 1, po, newpos[i:i + 1], hd[i:i + 1] if heading else None)
             dev.reset(mask, newpos, hd if heading else None, takeoff, first, f32, u8)
+            if contact:  # (a reset UAV flies again)
+                marked.difference_update(first + int(i) for i in np.flatnonzero(mask))
             # the oracle's construct forgets what the product's reset keeps: both sides are told all of it anew
             for lo, hi in _runs(mask):
                 a, c = first + int(lo), int(hi - lo)
@@ -1122,8 +1292,8 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
                 while tickets[kind]:
                     wait_oldest(kind, what)
             dev.clone_swap()
-            if scene:  # the clone owns a set of its own: no grid built yet, both entries empty (obstacles.hip: obstacles_copy adopts the set)
-                cache["query"] = cache["scan"] = None
+            if scene:  # the clone owns a set of its own: no grid built yet, every entry empty (obstacles.hip: obstacles_copy adopts the set);
+                cache.update(dict.fromkeys(cache))  # it inherits the airframe table whole (mrs_swarm_clone_resized), so rmax stays
                 builds = 0
         elif op == NEAREST:
             k, radius, fields, f32 = int(rng.integers(1, 9)), float(rng.uniform(0.5, 4.0)), int(rng.integers(0, 32)), bool(rng.integers(0, 2))
@@ -1194,6 +1364,8 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
             blocks = steps // hold
             crash, rebounce, crash_cost = bool(rng.integers(0, 4) == 0), pick(rng, (60.0, 100.0)), pick(rng, (0.0, 2.5))
             crashed = pick(rng, ("bool", "uint8", None))
+            if show:  # (the contact surface: the marked UAV must show in the crash rows, or in the cost at crash_cost a level)
+                crashed, crash_cost = crashed or "uint8", crash_cost or 2.5
             # what is evaluated: observation rows (ROLL_TICK), or a cost in one of three forms: 0 a term over `groups`; 1 no cost at all
             # (ROLL_FEEDBACK, ROLL_TICK_FEEDBACK: no `out`); 2 the crash cost alone (`groups` 0: ROLL_TICK_COST; ROLL_TICK_FEEDBACK with `out`)
             groups = int(rng.integers(1, 256))
@@ -1285,6 +1457,11 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
                     cost_check(got, cost, bound, start, label)
                 else:
                     assert got is None, f"{label}: a run without a cost returned one"
+            if contact and tick and marked and (crashed is not None if op == ROLL_TICK else cost is not None and crash_cost != 0.0):
+                # UAVs a contact mark crashed, in the first crash row of a rollout that hands the rows out or charges for them
+                seen = {u for u in marked if first <= u < first + count and crs[0][u - first]}
+                tally["marked_seen_in_crash_row"] += len(seen)
+                marked.difference_update(seen)
         elif op == PROXIMITY:
             k, radius, kind = int(rng.integers(1, 33)), float(rng.uniform(0.5, 4.0)), int(rng.integers(0, 3))
             weight, eps, found = float(rng.uniform(0.1, 2.0)), pick(rng, (0.0, 0.01)), bool(rng.integers(0, 2))
@@ -1315,7 +1492,7 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
             ob = draw_obstacles(rng)
             dev.set_obstacles(ob, sets[0] % 2 == 0)
             sets[0] += 1
-            cache["query"] = cache["scan"] = None  # both entries served the old set; the setter itself builds nothing
+            cache.update(dict.fromkeys(cache))  # every entry served the old set; the setter itself builds nothing
             oplog[-1] += (len(ob),)
         elif op == SET_BEAMS:
             beams = draw_beams(rng)
@@ -1391,12 +1568,78 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
                     exact(got[1], want[1][sl], label + ": hit")
                 if uavs:
                     exact(got[2], want[2][sl], label + ": uav")
+        elif op in CONTACT_KINDS:
+            mark = op == CONTACT_MARK
+            margin = pick(rng, MARK_MARGINS if mark else MARGINS)
+            outs = tuple(name for name, on in zip(CONTACT_OUTPUTS, rng.integers(0, 2, 4)) if on)
+            start = rng.uniform(0.0, 5.0, count) if rng.integers(0, 2) else None
+            hit_cost = float(rng.uniform(0.5, 5.0))
+            if mark and rng.integers(0, 4) == 0:
+                outs, start = (), None  # the mark alone, one time in four
+            elif not mark and not outs and start is None:
+                outs = (pick(rng, CONTACT_OUTPUTS),)  # ("nothing to do" is refused: the read-only form asks for something)
+            fill, contact_calls = contact_calls % 2 == 0, contact_calls + 1  # vectors to fill and True in turn
+            oplog[-1] += (margin, outs, start is not None)
+            res["marks_behind_pending" if mark else "contacts_behind_pending"] += int(pending)
+            sl = slice(first, first + count)
+            rad = airframes()[1]
+            # What the kernel reads: the positions behind the launches queued so far.  A gather before the call sees them (it drains
+            # like the read-only form; and the marking form's settle() evaluates the pending tick through collide_now, which reads
+            # positions and writes forces and flag words, never a position: tick_single.hip).  Behind the stall recipe the gather comes
+            # after the call instead, so that the mark itself is what has to replay the stall: the mark writes flag words only, so
+            # the positions it read are still there.
+            if not behind_stall:
+                xs, _, lab = scene_inputs()
+            touch("contact", float(np.float64(rmax) + np.float64(margin)))
+            label = f"{what}: {OP_NAMES[op]} of {first}+{count}, margin {margin}, outputs {outs}, {'vectors to fill' if fill else 'new vectors'}"
+            got = dev.obstacle_contacts(margin, mark, first, count, outs, fill, start, hit_cost)
+            if behind_stall:
+                xs, _, lab = scene_inputs()
+            ref = restate_contacts(xs, lab, ob, rad, margin)
+            hit = ref["hit"][sl] != 0
+            tally["uavs_touching"] += int(hit.sum())
+            tally["uavs_touching_several"] += int((ref["count"][sl] > 1).sum())
+            for name in since_contact:
+                tally["contact_after_" + name] += 1
+            since_contact.clear()
+            if got is not None:
+                assert sorted(got) == sorted(outs + (("cost",) if start is not None else ())), label
+                for name in outs:
+                    if name == "sd":
+                        bits(got["sd"], ref["sd"][sl], label + ": sd")
+                    else:
+                        exact(got[name], ref["count" if name == "counts" else name][sl], f"{label}: {name}")
+                if start is not None:  # (bit for bit: the elements of UAVs that touch nothing keep theirs)
+                    bits(got["cost"], cost_after(start, {"hit": ref["hit"][sl]}, hit_cost), label + ": cost")
+            if mark:
+                # the oracle has no obstacles: the touching set of the restatement on its own positions is crashed as Swarm.crash() does
+                res["obstacle_contact_violations"] += obstacle_contact_violations(p.o, ob, rad, margin, first, count, rtol)
+                own = restate_contacts(p.o.get_state()["x"], lab, ob, rad, margin)["hit"][sl] != 0 if dev.real else hit
+                assert np.array_equal(hit, own), (
+                    f"{label}: the product's positions touch UAVs {first + np.flatnonzero(hit & ~own)} that the oracle's do not, and not "
+                    f"{first + np.flatnonzero(own & ~hit)} that the oracle's do, although no pair of the range is within 2 sqrt(3) delta of "
+                    f"its threshold (obstacle_contact_violations is {res['obstacle_contact_violations']} so far)")
+                new = own & ~p.o.has_crashed(first, count).astype(bool)
+                for lo, hi in _runs(own):
+                    p.o.crash(first + int(lo), int(hi - lo))
+                tally["uavs_newly_marked"] += int(new.sum())
+                tally["marks_of_nobody"] += int(not own.any())
+                tally["marks_behind_stall"] += int(behind_stall)
+                tally["marks_with_open_ticket"] += int(any(tickets.values()))
+                marked.update(first + int(i) for i in np.flatnonzero(new))
+                if new.any() and not forced and rng.integers(0, 2):  # the crash row and the level crash cost of the next tick rollout
+                    forced.append(pick(rng, (ROLL_TICK, ROLL_TICK_COST)))
+                    cover = first + int(pick(rng, np.flatnonzero(new)))
         elif op in (ASYNC_OUTPUTS, ASYNC_POSES):
             kind = "outputs" if op == ASYNC_OUTPUTS else "poses"
             if len(tickets[kind]) == 2:
                 wait_oldest(kind, what)
             want = p.o.get_outputs(first, count).copy()
-            tickets[kind].append((dev.async_issue(kind, first, count), it + int(rng.integers(1, 7)), want))
+            ticket, due = dev.async_issue(kind, first, count), it + int(rng.integers(1, 7))
+            if contact and not forced and rng.integers(0, 2):  # a mark while the ticket is open: its payload stays the state at issue
+                forced.append(CONTACT_MARK)
+                due = max(due, it + 2)
+            tickets[kind].append((ticket, due, want))
         elif op == FAST_UAVS:  # the stall recipe: a handful of UAVs fast enough to leave their skin within two steps
             cnt = min(count, 6)
             st = p.o.get_state(first, cnt)
@@ -1409,16 +1652,26 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
             if ext and rng.integers(0, 2):
                 ticks, stall_at = pick(rng, STALL_ROLLOUTS), it + 1
             forced += [ticks] + [pick(rng, STALL_FOLLOWERS) for _ in range(2)]
+            # (the contact surface, half of the time behind a run of ticks: one of the two is a marking contact call, which has to replay
+            # the stall before it marks, and whose marks no replayed launch may lose)
+            if contact and ticks == TICK_LONG and rng.integers(0, 2):
+                forced[-1 - int(rng.integers(0, 2))] = MARK_BEHIND_STALL
         if op == 14 and not forced and rng.integers(0, 3) == 0:
             forced.append(pick(rng, rollouts))  # a rollout right behind the pending tick of a run
-        if scene and op in SCENE_KINDS:
-            res["scene_behind_pending"] += int(pending)
+        if scene and op in SCENE_KINDS + CONTACT_KINDS:
+            res["scene_behind_pending"] += int(pending and op in SCENE_KINDS)
             got = dev.grid_builds()
             assert got is None or got == builds, (f"{what}: {OP_NAMES[op]}: grid_builds is {got}, the cache rule of obstacle_set.h gives {builds} "
                                                   f"(entries current for {cache})")
         if ext and op in (13, 14, ROLL_TICK) and not measure and not forced and rng.integers(0, 2):
             # a call that promises to leave the pending tick alone, right behind one
             forced.append(pick(rng, SCENE_KINDS) if scene and rng.integers(0, 2) else PROXIMITY)
+            if contact and rng.integers(0, 2):  # either contact form: the read-only one keeps the tick pending, the mark evaluates it
+                forced[-1] = pick(rng, CONTACT_KINDS)
+        if contact:
+            rmax = max(rmax, float(airframes()[1].max()))  # (what the call has interned is in the table for good)
+            if op in SCAN_MARKS:
+                since_contact.add(SCAN_MARKS[op])
         if scene:
             if op in SCAN_MARKS:
                 since_scan.add(SCAN_MARKS[op])
@@ -1433,8 +1686,11 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
                 stale = 0
             elif op not in NO_TABLE_UPLOAD:
                 stale = 0
-            if (op in TABLE_CALLS or op in SCAN_MARKS) and not forced and it % 5 <= 2 and rng.integers(0, 2):
-                forced += [SCAN_BLIND, SCAN_TABLE] if op in TABLE_CALLS else [pick(rng, SCANS)]  # (the compare's steps do not come between)
+            if (op in TABLE_CALLS or op in SCAN_MARKS) and not forced and it % 5 <= 2:
+                if rng.integers(0, 2):
+                    forced += [SCAN_BLIND, SCAN_TABLE] if op in TABLE_CALLS else [pick(rng, SCANS)]  # (the compare's steps do not come between)
+                elif contact:  # the other half: a contact call, which reads the table, the set, the labels and its own cache entry
+                    forced.append(pick(rng, CONTACT_KINDS))
         if op in (13, 14, TICK_LONG) or (op in TICK_ROLLOUTS and not measure):
             pending = True
         elif op not in KEEP_PENDING and not (op == MODEL_ALL and how < 2):
@@ -1461,5 +1717,6 @@ def run_sequence(p, dev, mrs, rng, seed, fast, fleet, rtol, cap, split=False, lo
     if ext:
         del p.o.handle_collisions  # (the watched one)
     res["stats"] = dev.finish()
+    res["crashed_at_end"] = int(p.o.has_crashed().astype(bool).sum())
     res["stalls_in_tick_rollouts"], res["replayed_in_tick_rollouts"] = (int(v) for v in dev.tick_rollout_stats)
     return res

@@ -21,7 +21,20 @@ range_scan without the ground, a scan that reads the table); from the restatemen
 boxes 614, cylinders 4862, UAVs 2594, the ground 2725, nothing 64699; 2398 beams of range 0; 66 beams a UAV takes from an obstacle, 63
 an obstacle keeps from a UAV; 65 query UAVs with found > k; from the cache model: 29 and 53 grids built for the queries and the scans,
 4 and 9 cache hits.  Their sequences keep the step budget and the two honesty conditions, and both earlier surfaces draw what they
-drew: the op logs of the extended surface, hashed before the scene surface existed, are in tests/golden/device_sequence_logs_ext.json."""
+drew: the op logs of the extended surface, hashed before the scene surface existed, are in tests/golden/device_sequence_logs_ext.json.
+
+The contact surface (counted here, over the 12 seeds of SEEDS_CONTACT, 7 of them with collision worlds and 2 with model-only phases,
+and asserted exactly against device_sequences.CONTACT_COUNTS): 34 obstacle_contacts calls without the mark and 59 with it, 12 and 13
+of them behind a pending collision tick; 7 marks among the followers of a stall recipe, 25 while a pipelined download was open; from
+the restatement on the oracle's state: 302 UAVs touching, 44 of them more than one obstacle, 94 newly marked, 53 of those shown by the
+first crash row of a later tick rollout, 27 marks of nobody; contact calls that follow a call with no other contact call in between: 8
+set_ground_z, 10 set_params, 8 resets, 10 clone swaps, 5 set_worlds, 12 set_obstacles; from the cache model: 66 grids built for the
+third entry, 27 cache hits.  The conditions the seeds were chosen to keep are asserted beside the counts (at least 20 calls of each
+form, 5 of each behind a pending tick, 2 marks behind a stall recipe, 40 UAVs newly marked, 5 seen in a crash row, a mark of nobody, a
+contact call after each of the six SCAN_MARKS, 3 cache hits and 10 builds, no seed with more than half of its UAVs crashed at its
+end), and so are the step cap, the limits of test_the_oracle_stays_usable and all three honesty conditions: the two above and
+obstacle_contact_violations == 0 at every marking call.  The op logs of the scene surface, hashed before the contact surface existed,
+are in tests/golden/device_sequence_logs_scene.json (the three variant seeds included), and the two older golden files pass unchanged."""
 import numpy as np
 import pytest
 
@@ -51,16 +64,20 @@ def dry_run(mrs, seed, split=False):
 def runs(mrs):
     """every sequence the GPU module runs: {(variant or None, seed): result}; a seed's number says which surface it draws from
     (D.surface_of), in every variant"""
-    out = {(None, seed): dry_run(mrs, seed) for seed, *_ in D.SEEDS + D.SEEDS_EXT + D.SEEDS_SCENE}
+    out = {(None, seed): dry_run(mrs, seed) for seed, *_ in D.SEEDS + D.SEEDS_EXT + D.SEEDS_SCENE + D.SEEDS_CONTACT}
     for name, (_, seeds, split) in D.VARIANTS.items():
-        for seed in seeds + D.VARIANTS_EXT[name] + (D.VARIANTS_SCENE[name],):
+        for seed in seeds + D.VARIANTS_EXT[name] + (D.VARIANTS_SCENE[name], D.VARIANTS_CONTACT[name]):
             out[name, seed] = dry_run(mrs, seed, split=split)
     return out
 
 
 def is_ext(key):
-    """the sequences that draw the kinds of the extended surface: its own, and those of the scene surface"""
+    """the sequences that draw the kinds of the extended surface: its own, and those of the scene and the contact surface"""
     return D.surface_of(key[1]) != "base"
+
+
+def is_contact(key):
+    return D.surface_of(key[1]) == "contact"
 
 
 def is_scene(key):
@@ -87,13 +104,19 @@ def base_runs(runs):
 @pytest.fixture(scope="module")
 def ext_runs(runs):
     """the sequences of the extended surface that run in the parent process: D.SEEDS_EXT"""
-    return {k: r for k, r in runs.items() if is_ext(k) and not is_scene(k) and k[0] is None}
+    return {k: r for k, r in runs.items() if D.surface_of(k[1]) == "ext" and k[0] is None}
 
 
 @pytest.fixture(scope="module")
 def scene_runs(runs):
     """the sequences of the scene surface that run in the parent process: D.SEEDS_SCENE"""
     return {k: r for k, r in runs.items() if is_scene(k) and k[0] is None}
+
+
+@pytest.fixture(scope="module")
+def contact_runs(runs):
+    """the sequences of the contact surface that run in the parent process: D.SEEDS_CONTACT"""
+    return {k: r for k, r in runs.items() if is_contact(k) and k[0] is None}
 
 
 def test_step_cap_is_the_largest_total_of_the_existing_sequences(mrs):
@@ -145,9 +168,17 @@ def test_the_first_surface_draws_what_it_always_drew(base_runs):
 
 def test_the_extended_surface_draws_what_it_drew_before_the_scene_surface(runs):
     """the op logs of the 20 extended seeds and their six variant runs, as they were before the scene surface existed"""
-    ext = {k: r for k, r in runs.items() if is_ext(k) and not is_scene(k)}
+    ext = {k: r for k, r in runs.items() if D.surface_of(k[1]) == "ext"}
     assert len(ext) == len(D.SEEDS_EXT) + sum(len(v) for v in D.VARIANTS_EXT.values())
     assert log_hashes(ext) == golden("device_sequence_logs_ext.json")
+
+
+def test_the_scene_surface_draws_what_it_drew_before_the_contact_surface(runs):
+    """the op logs of the 12 scene seeds and their three variant runs, as they were before the contact surface existed"""
+    scene = {k: r for k, r in runs.items() if is_scene(k)}
+    assert len(scene) == len(D.SEEDS_SCENE) + len(D.VARIANTS_SCENE)
+    assert all(D.surface_of(s) == "scene" for s in range(200, 400)), "the variant seeds 310 and 317 stay scene seeds"
+    assert log_hashes(scene) == golden("device_sequence_logs_scene.json")
 
 
 def test_every_kind_of_the_extended_surface_occurs(runs, ext_runs):
@@ -240,6 +271,57 @@ def test_every_kind_of_the_scene_surface_occurs(runs, scene_runs):
         assert sum(r["kinds"][op] for op in D.SCANS) >= 2 and sum(r["kinds"][op] for op in D.SCENE_KINDS) >= 6, variant
 
 
+def test_every_kind_of_the_contact_surface_occurs(runs, contact_runs):
+    """the counts of the module docstrings, over D.SEEDS_CONTACT: D.CONTACT_COUNTS exactly, and the conditions the seeds were chosen to
+    keep (conditions, not measurements: a seed that breaks one is replaced by another candidate)"""
+    flags = D.SEEDS_CONTACT
+    assert len(contact_runs) == len(flags) == 12 and min(D.CONTACT_SEED_NUMBERS) >= 400
+    assert sum(f[5] for f in flags) >= 6 and sum(f[4] for f in flags) >= 2, "at least six seeds with worlds, two with model-only phases"
+    assert {f[1] for f in flags} == {False, True} and {f[2] for f in flags} == {"x500", "mixed"} and {f[0] % 2 for f in flags} == {0, 1}
+    assert not any(f[3] for f in flags), "none takes the long horizon"
+    total = D.contact_totals(contact_runs.values())
+    print("contact surface:", total)
+    print("contact surface, the scene kinds along the way:", D.scene_totals(contact_runs.values()))
+    assert total == D.CONTACT_COUNTS
+    assert total["obstacle_contacts"] >= 20 and total["contact_mark"] >= 20
+    assert total["contacts_behind_pending"] >= 5 and total["marks_behind_pending"] >= 5
+    assert total["marks_behind_stall"] >= 2 and total["marks_with_open_ticket"] >= 2
+    assert total["uavs_newly_marked"] >= 40 and total["marked_seen_in_crash_row"] >= 5 and total["marks_of_nobody"] >= 1
+    assert total["uavs_touching"] >= total["uavs_newly_marked"] and total["uavs_touching_several"] >= 1
+    for mark in D.SCAN_MARKS.values():
+        assert total["contact_after_" + mark] >= 1, mark
+    assert total["contact_cache_hits"] >= 3 and total["contact_grid_builds"] >= 10
+    for (_, seed), r in contact_runs.items():  # the sequence stays a test of flying UAVs
+        assert 2 * r["crashed_at_end"] <= D.N_UAVS, (seed, r["crashed_at_end"])
+    # the calls as drawn: every margin of each form, every output alone or with others, vectors to fill and new ones, a cost or none,
+    # a mark with no output at all, and the scene kinds still drawn beside them
+    calls = [c for r in contact_runs.values() for c in r["calls"] if c[0] == "obstacle_contacts"]
+    assert len(calls) == total["obstacle_contacts"] + total["contact_mark"]
+    plain, marks = [c for c in calls if not c[2]], [c for c in calls if c[2]]
+    assert {c[1] for c in plain} == set(D.MARGINS) and {c[1] for c in marks} == set(D.MARK_MARGINS) == {0.0, 0.25}
+    assert all(c[5] or c[7] for c in plain), "the read-only form always asks for something"
+    assert any(not c[5] and not c[7] for c in marks), "the mark alone"
+    for form in (plain, marks):
+        assert {name for c in form for name in c[5]} == set(D.CONTACT_OUTPUTS)
+        assert {c[6] for c in form} == {False, True} == {c[7] for c in form}
+    kinds = sum((r["kinds"] for r in contact_runs.values()), D.Counter())
+    for op in D.SCENE_KINDS + D.EXT_KINDS[:5]:
+        assert kinds[op] >= 5, f"{D.OP_NAMES[op]} occurs {kinds[op]} times over the seeds of the contact surface"
+    # the forced shapes, read from the op logs: a tick rollout right behind a mark, a contact call right behind a table-changing call
+    names = [[e[1] for e in r["log"]] for r in contact_runs.values()]
+    pairs = D.Counter((a, b) for seq in names for a, b in zip(seq, seq[1:]))
+    assert sum(pairs["contact_mark", b] for b in ("rollout_ticks", "rollout_tick_cost")) >= 3
+    assert sum(pairs[a, b] for a in D.TABLE_CALLS.values() for b in ("obstacle_contacts", "contact_mark")) >= 3
+    assert sum(pairs[a, "contact_mark"] for a in ("async_outputs", "async_poses")) >= 2
+    # the child-process variants: one seed each; host call 12 where step_n is split; both forms, and somebody marked
+    assert sorted(D.VARIANTS_CONTACT) == sorted(D.VARIANTS)
+    for variant, (_, _, split) in D.VARIANTS.items():
+        r = runs[variant, D.VARIANTS_CONTACT[variant]]
+        assert not split or r["kinds"][12] >= 1, variant
+        assert r["kinds"][D.OBSTACLE_CONTACTS] >= 1 and r["kinds"][D.CONTACT_MARK] >= 4 and r["scene"]["uavs_newly_marked"] >= 5, variant
+        assert 2 * r["crashed_at_end"] <= D.N_UAVS, variant
+
+
 def test_the_extended_seeds_keep_their_comparison_honest(runs):
     """the two conditions of device_sequences' docstring, for every sequence of the extended surface: no same-world pair within twice the
     compare's reach of its contact threshold at any collision pass, and no UAV near a branch boundary of the quaternion where a
@@ -251,6 +333,48 @@ def test_the_extended_seeds_keep_their_comparison_honest(runs):
             assert r["feedback_near_quat_branch"] == 0, (key, r["feedback_near_quat_branch"])
             passes += sum(r["kinds"][op] for op in (13, 14, D.TICK_LONG) + D.TICK_ROLLOUTS)
     assert passes >= 100
+
+
+def test_the_contact_seeds_keep_their_marks_honest(runs):
+    """the third condition, for every sequence of the contact surface: at no marking call is an applicable (UAV, obstacle) pair of the
+    range within 2 sqrt(3) delta of its threshold (D.obstacle_contact_violations), so the product's touching set is the oracle's"""
+    marks = 0
+    for key, r in runs.items():
+        assert r["obstacle_contact_violations"] == 0, (key, r["obstacle_contact_violations"])
+        marks += r["kinds"][D.CONTACT_MARK] if is_contact(key) else 0
+        assert is_contact(key) or not (r["kinds"][D.CONTACT_MARK] or r["kinds"][D.OBSTACLE_CONTACTS]), "the earlier surfaces draw no contact call"
+    assert marks >= 30
+
+
+def test_obstacle_contact_violations_counts_pairs_near_their_threshold(oracle):
+    from test_obstacles import ALL_WORLDS, BOX, SPHERE, obstacles
+    o = oracle.OracleSwarm(4)
+    o.construct(0, 4, helpers.oracle_params("x500"))
+    par = o.get_params(0)
+    rad = par.arm_length + par.prop_radius
+    st = o.get_state()
+    ob = obstacles([(SPHERE, (0.0, 0.0, 5.0), (1.0, 0, 0), 0), (BOX, (40.0, 0.0, 5.0), (1.0, 1.0, 1.0), 7)])
+
+    def at(sd, world=0):  # UAV 0 at signed distance sd from the sphere, along x; UAV 1 as far from the box of world 7; the others far away
+        x = np.array([[1.0 + sd, 0.0, 5.0], [41.0 + sd, 0.0, 5.0], [0.0, 80.0, 5.0], [0.0, 90.0, 5.0]])
+        o.set_state(0, 4, x, st["v"], st["R"], st["omega"], st["motor_rpm"])
+        o.set_worlds([0, world, 0, 0])
+    margin = 0.25
+    thr = rad + margin
+    reach = np.sqrt(3.0) * 1e-7 * 5.0  # sqrt(3) delta, delta = rtol * |x|_inf of UAV 0
+    for off, want in ((0.0, 1), (1.5 * reach, 1), (-1.5 * reach, 1), (3.0 * reach, 0), (-3.0 * reach, 0)):
+        at(thr + off)
+        assert D.obstacle_contact_violations(o, ob, rad, margin, 0, 4, 1e-7) == want, off
+        assert D.obstacle_contact_violations(o, ob, rad, margin, 0, 4, 1e-11) == (1 if off == 0.0 else 0), off
+        assert D.obstacle_contact_violations(o, ob, rad, margin, 1, 3, 1e-7) == 0, "UAV 0 is outside the range"
+        assert D.obstacle_contact_violations(o, ob, rad, 0.0, 0, 4, 1e-7) == 0, "another margin, another threshold"
+    at(thr, world=7)  # the box applies to UAV 1 now; its |x|_inf is 41, so its reach is larger
+    assert D.obstacle_contact_violations(o, ob, rad, margin, 0, 4, 1e-7) == 2
+    assert D.obstacle_contact_violations(o, ob, np.full(4, rad), margin, 1, 1, 1e-7) == 1, "per-UAV radii"
+    ob["flags"][1] = ALL_WORLDS
+    at(thr)
+    assert D.obstacle_contact_violations(o, ob, rad, margin, 0, 4, 1e-7) == 2, "an ALL_WORLDS obstacle applies whatever the label"
+    assert D.obstacle_contact_violations(o, ob[:0], rad, margin, 0, 4, 1e-7) == 0
 
 
 def test_contact_violations_counts_pairs_near_their_threshold(oracle):
@@ -281,7 +405,8 @@ def test_fast_uavs_are_followed_by_ticks_and_calls_that_replay_them(runs):
         ticks = ["tick_long"] + ([D.OP_NAMES[op] for op in D.STALL_ROLLOUTS] if is_ext(key) else [])
         for i, name in enumerate(names[:-3]):
             if name == "fast_uavs" and names[i + 1] in ticks:
-                assert names[i + 2] in followers and names[i + 3] in followers
+                allowed = followers + (["contact_mark"] if is_contact(key) else [])  # (the mark that has to replay the stall)
+                assert names[i + 2] in allowed and names[i + 3] in allowed
                 if names[i + 1] != "tick_long":
                     assert r["log"][i + 1][5] >= 4, "a stall needs a run of ticks"
                     stallers[names[i + 1]] += int(key[0] is None)  # (over D.SEEDS_EXT: the variants repeat some of them)

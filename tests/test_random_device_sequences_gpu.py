@@ -44,7 +44,23 @@ test_random_device_sequences.py on the oracle's state): 16 set_obstacles, 16 nea
 range_scan, 21 range_scan_uavs, 16 of them behind a pending tick; 10 stale-table shapes; beams taken by spheres 448, boxes 614,
 cylinders 4862, UAVs 2594, the ground 2725, nothing 64699, 2398 of range 0; 66 a UAV takes from an obstacle, 63 an obstacle keeps from
 a UAV; 65 query UAVs with found > k; 29 + 53 grids built, 4 + 9 cache hits.  This module counts the same figures from the restatement
-of the product's own state and asserts each at about half (scene_floor).  A scene seed takes 0.1 to 0.2 s on an MI355X."""
+of the product's own state and asserts each at about half (scene_floor).  A scene seed takes 0.1 to 0.2 s on an MI355X.
+
+The contact surface (device_sequences.SEEDS_CONTACT: 12 more seeds under test ids of their own, 7 of them with collision worlds, and
+one more seed per child-process variant) mixes in tensors.obstacle_contacts in both forms: the read-only one, which must leave a
+pending collision tick pending, and the marking one (crash=True), the only scenery call that writes simulation state — it evaluates the
+pending tick, ORs the crashed bit into the flag words, reads the airframe table it has just uploaded and makes a third grid cache
+entry current.  Every requested vector (hit, index, sd, counts, the cost vector) is compared bit for bit with the numpy restatement on
+the positions gathered around the call; the UAVs the product's positions touch must be the UAVs the oracle's positions touch (the
+third honesty condition, asserted by the dry runs, makes that a fair demand), and those are crashed on the oracle, so that the next
+crashed() call, the crash rows and crash costs of the tick rollouts forced behind a mark and the five-call compare see every mark.
+Marks stand among the calls that have to replay a stalled run of ticks, behind pending ticks, behind table-changing calls, clone
+swaps, set_worlds and set_obstacles, and between the issue and the wait of a pipelined download; grid_builds is asserted against the
+three-entry cache model after every scene and contact call.  Over the 12 dry runs (device_sequences.CONTACT_COUNTS): 34 read-only and
+59 marking calls, 12 and 13 of them behind a pending tick, 7 marks behind a stall recipe, 302 UAVs touching, 94 newly marked, 53 of
+them seen in a later crash row, 27 marks of nobody, 66 grids built and 27 cache hits; this module asserts each at scene_floor, and
+that a stall was replayed in these sequences (measured: every figure equals the dry runs'; 91 stalls, 135 replayed launches).  A
+contact seed takes 0.1 to 0.3 s on an MI355X."""
 import json
 import os
 import subprocess
@@ -53,8 +69,9 @@ import sys
 import numpy as np
 import pytest
 
-from device_sequences import (N_UAVS, RNG_BASE, SCENE_COUNTS, SEEDS, SEEDS_EXT, SEEDS_SCENE, STEP_CAP, VARIANTS, VARIANTS_EXT, VARIANTS_SCENE, Device,
-                              ext_flags, run_sequence, scene_totals, seed_rtol, surface_of)
+from device_sequences import (CONTACT_COUNTS, N_UAVS, RNG_BASE, SCENE_COUNTS, SEEDS, SEEDS_CONTACT, SEEDS_EXT, SEEDS_SCENE, STEP_CAP, VARIANTS,
+                              VARIANTS_CONTACT, VARIANTS_EXT, VARIANTS_SCENE, Device, contact_totals, ext_flags, run_sequence, scene_totals, seed_rtol,
+                              surface_of)
 from helpers import Pair
 
 pytestmark = pytest.mark.gpu
@@ -110,6 +127,17 @@ def test_random_sequences_of_the_scene_surface_match_oracle_and_numpy(mrs, seed,
     _results[seed] = res
 
 
+@pytest.mark.parametrize("seed,fast,fleet,long_rollout,model,worlds", SEEDS_CONTACT)
+def test_random_sequences_of_the_contact_surface_match_oracle_and_numpy(mrs, seed, fast, fleet, long_rollout, model, worlds):
+    import time
+    t0 = time.perf_counter()
+    res = run_seed(mrs, seed)
+    print(f"seed {seed} ({'FAST' if fast else 'LITERAL'}, {fleet}{', worlds' if worlds else ''}), {time.perf_counter() - t0:.1f} s: {figures(res)}\n"
+          f"contact: {contact_totals([res])}")
+    assert res["obstacle_contact_violations"] == 0, "no pair of a marking call is near its threshold on the oracle's positions"
+    _results[seed] = res
+
+
 def scene_floor(count):
     """what the GPU module asks of a figure that the CPU dry runs measured as `count`: about half (the restatement runs on the product's
     own state here, which differs from the oracle's within the compare's tolerance)"""
@@ -117,7 +145,7 @@ def scene_floor(count):
 
 
 def test_the_sequences_met_what_they_are_for():
-    n_seeds = len(SEEDS) + len(SEEDS_EXT) + len(SEEDS_SCENE)
+    n_seeds = len(SEEDS) + len(SEEDS_EXT) + len(SEEDS_SCENE) + len(SEEDS_CONTACT)
     assert len(_results) == n_seeds, f"only {len(_results)} of the {n_seeds} seeds ran to their end: this check speaks for all of them"
     first = [r for s, r in _results.items() if surface_of(s) == "base"]
     total = {k: sum(figures(r)[k] for r in first) for k in figures(first[0])}
@@ -137,6 +165,15 @@ def test_the_sequences_met_what_they_are_for():
     assert sorted(total) == sorted(SCENE_COUNTS)
     for name, count in SCENE_COUNTS.items():
         assert total[name] >= scene_floor(count), f"{name}: {total[name]} over the scene seeds, the dry runs on the oracle counted {count}"
+    # the contact surface: device_sequences.CONTACT_COUNTS likewise; and a stall of the lazy ticks was replayed in its sequences, where
+    # marking calls stand among the calls that have to replay it
+    contact = [r for s, r in _results.items() if surface_of(s) == "contact"]
+    total = contact_totals(contact)
+    print(f"the seeds of the contact surface: {total}; {({k: sum(figures(r)[k] for r in contact) for k in ('stalls', 'replayed')})}")
+    assert sorted(total) == sorted(CONTACT_COUNTS)
+    for name, count in CONTACT_COUNTS.items():
+        assert total[name] >= scene_floor(count), f"{name}: {total[name]} over the contact seeds, the dry runs on the oracle counted {count}"
+    assert sum(figures(r)["stalls"] for r in contact) >= 1 and sum(figures(r)["replayed"] for r in contact) >= 1, "no stall was replayed"
 
 
 def child_main(out_path, variant):
@@ -144,7 +181,7 @@ def child_main(out_path, variant):
     M.load_library()
     _, seeds, split = VARIANTS[variant]
     out = {}
-    for seed in seeds + VARIANTS_EXT[variant] + (VARIANTS_SCENE[variant],):
+    for seed in seeds + VARIANTS_EXT[variant] + (VARIANTS_SCENE[variant], VARIANTS_CONTACT[variant]):
         out[str(seed)] = figures(run_seed(M, seed, split=split))
         print(f"{variant}: seed {seed}: {out[str(seed)]}", flush=True)
     with open(out_path, "w") as f:
@@ -172,7 +209,7 @@ def test_variant_in_a_child_process(mrs, tmp_path, variant):
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     with open(out) as f:
         got = json.load(f)
-    assert sorted(got) == sorted(str(s) for s in seeds + VARIANTS_EXT[variant] + (VARIANTS_SCENE[variant],))
+    assert sorted(got) == sorted(str(s) for s in seeds + VARIANTS_EXT[variant] + (VARIANTS_SCENE[variant], VARIANTS_CONTACT[variant]))
     for seed, fig in got.items():
         if split:  # the two-stream form was taken: steps launched as two half-swarm launches
             assert fig["split_steps"] >= 4, f"{variant}, seed {seed}: step_n never took the two-stream form: {fig}"

@@ -436,6 +436,7 @@ int step_one(mrs_swarm* s, double dt, const mrs_swarm::TickLoad* load) {
     }
   }
   if ((rc = settle(s))) return rc;
+  if ((rc = upload_types(s, dt))) return rc;  // (settle may have replayed ticks of another dt: the table is theirs then)
   s->collide_since_step = false;
   s->p_valid            = false;  // a plain step kernel does not refresh the position records
   if (load && load->kind != mrs_swarm::TickLoad::NONE) return launch_unfused_load(s, dt, *load);
@@ -468,6 +469,10 @@ int mrs_swarm_step_n(mrs_swarm_t* s, double dt, int32_t n_steps, int32_t substep
   if (n_steps > 0) {
     enqueued = enqueued || !s->log.empty() || s->pend.on || s->f_lazy.on;  // (what settle is about to issue)
     if ((rc = settle(s))) return rc;
+    // settle may have replayed stalled collision ticks of an earlier call, each with its own dt (launch_fused, drain): the type table
+    // then holds THEIR motor-filter constants.  The plain launches below never look at table_dt, so it is brought back to this call's
+    // (no copy and no synchronisation when nothing was replayed)
+    if ((rc = upload_types(s, dt))) return rc;
     s->p_valid = false;
     // enough launches to overlap, enough blocks for two useful halves, and no per-launch events to keep in order
     static const int split_min_blocks = getenv("MRS_SPLIT_MIN_BLOCKS") ? atoi(getenv("MRS_SPLIT_MIN_BLOCKS")) : 1024;  // tuning aid

@@ -853,6 +853,16 @@ public:
     mrs_throw_on_error(mrs_swarm_obstacle_contacts_device(s_, first, count, margin, flags, dev_hit, dev_index, dev_sd, dev_count, dev_cost,
                                                           hit_cost, stream));
   }
+  // line-of-sight neighbours (mrs_swarm_nearest_visible_device): nearestDevice for observers that need a line of sight — of the UAVs
+  // within `radius` of each UAV of [first, first + count), the first k by (d2, j) that no static obstacle hides; rows, slots, fields,
+  // dev_index and dev_count (= min(visible, k)) as nearestDevice writes them; dev_visible / dev_hidden (int32[count], each may be null):
+  // the numbers of visible and of hidden candidates, not capped by k
+  void nearestVisibleDevice(int first, int count, int k, double radius, uint32_t fields, void* dev_rows, int32_t dtype, int stride,
+                            int32_t* dev_index = nullptr, int index_stride = 0, int32_t* dev_count = nullptr, int32_t* dev_visible = nullptr,
+                            int32_t* dev_hidden = nullptr, void* stream = nullptr) {
+    mrs_throw_on_error(mrs_swarm_nearest_visible_device(s_, first, count, k, radius, fields, dev_rows, dtype, stride, dev_index, index_stride,
+                                                        dev_count, dev_visible, dev_hidden, stream));
+  }
   // collision worlds (mrs_swarm_set_worlds): UAVs interact through the collision pass, and appear in each other's nearest-neighbour rows,
   // only if their 32-bit labels are equal (0 until set); the labels of UAVs [first, first + worlds.size())
   void setWorlds(int first, const std::vector<int32_t>& worlds) {

@@ -795,6 +795,51 @@ enum { MRS_CONTACT_CRASH = 1 << 0 }; /* touching UAVs get crashed_, as UavSystem
 int mrs_swarm_obstacle_contacts_device(mrs_swarm_t* s, int32_t first, int32_t count, double margin, uint32_t flags, uint8_t* dev_hit,
                                        int32_t* dev_index, double* dev_sd, int32_t* dev_count, double* dev_cost, double hit_cost, void* ext_stream);
 
+/* ---- line-of-sight neighbours: the k nearest UAVs that no static obstacle hides from the observer ----
+ * mrs_swarm_nearest_device lists the UAV behind a wall exactly like the one in the open.  This call is the neighbour observation of a
+ * camera- or UVDAR-based relative localisation: a neighbour is a neighbour only while there is a line of sight to it.  Arguments, rows,
+ * slots and fields are those of mrs_swarm_nearest_device, which stays what it is; two more optional outputs count what is seen and what
+ * is hidden.
+ * Candidates of observer i = first + r, word for word those of mrs_swarm_nearest_device: every UAV j != i of the swarm with a finite
+ * position (crashed ones included) and, once a label has been set, world_j == world_i, with
+ *     dx = x_j - x_i (per axis);  d2 = ((dx*dx) + dy*dy) + dz*dz;  d2 < radius * radius
+ * all in FP64 without FMA contraction, radius * radius rounded once on the host.
+ * Sight line of candidate j:
+ *     if d2 == 0:  visible, with no test (coincident UAVs see each other, inside a solid too)
+ *     else         d = sqrt(d2);  u = (dx / d, dy / d, dz / d)       (three separately rounded divisions)
+ *                  hidden  <=>  there is an obstacle o of the set that
+ *                                 applies to i        (MRS_OBST_ALL_WORLDS, or o.world == world_i; world_i = 0 without labels),
+ *                                 passes the gate     |p_a - c_a| - hb_a < radius on every axis a (hb: the half-extents of o's bounding
+ *                                                     box; the gate of the range scans with max_range = radius), and
+ *                                 t(o, p_i, u) < d    strictly, t the range at which the beam p_i + t u enters the closed solid o, as
+ *                                                     the range scans define it (0 when p_i lies in or on o, +inf when it misses).
+ * A NaN never hides (every comparison with it is false).  A target exactly on a surface (t == d) is visible.  An observer inside a solid
+ * (t == 0 < d) sees only coincident UAVs.  The target is a point, UAV bodies hide nothing, and the observer's own body is ignored.
+ * An obstacle that fails the gate cannot hide anything within the radius up to the rounding of the gate itself; it is part of the
+ * contract so that the result does not depend on which obstacles a search structure happens to list.
+ * Symmetry is NOT promised bit for bit: "i sees j" uses p_i and u, "j sees i" uses p_j and -u' with u' rounded from the opposite
+ * offsets; a sight line that grazes a surface within rounding may be judged differently from its two ends.
+ * Selection: the first k VISIBLE candidates by ascending (d2, j) — not the k nearest filtered afterwards: a hidden candidate takes no slot.
+ * Outputs.  Row r, its k slots, the MRS_NN_* fields, empty slots (zeros, index -1), the untouched slack of rows and index rows and the
+ * FP32 rows (the cast of the FP64 value) are exactly those of mrs_swarm_nearest_device.  dev_count[r] = min(visible, k);
+ * dev_visible[r] = the number of visible candidates and dev_hidden[r] = the number of hidden ones, neither capped by k (int32[count],
+ * each may be NULL).  An observer with a non-finite position gets an empty row and zeros.  dev_rows may be NULL when fields == 0; at
+ * least one of dev_rows (with fields), dev_index, dev_count, dev_visible, dev_hidden must be given.
+ * Obstacle sets.  An empty set, or none ever given, is legal: rows, index and count are then bit for bit those of
+ * mrs_swarm_nearest_device, and hidden is 0.
+ * Entry.  The call enters like mrs_swarm_nearest_device (a pending collision tick stays pending), fences the caller's stream in and out
+ * and writes no simulation state.  Its scratch is that of mrs_swarm_nearest_device plus a cached obstacle grid of its own, keyed by
+ * radius (counted in mrs_obstacle_stats_t::grid_builds, dropped by mrs_swarm_set_obstacles, not copied by clone); neither the grid nor
+ * the hash can change a result bit.
+ * Refusals, in this order, before anything is launched — a refused call changes no output byte and no state: the range (MRS_ERR_RANGE);
+ * then MRS_ERR_ARG for a sharded swarm; unknown field bits; k outside [1, MRS_NN_MAX_K]; a radius that is not finite and > 0; no output
+ * at all; with fields: an unknown dtype, stride < k * width; with dev_index: index_stride < k; then (count == 0 is MRS_OK here) dev_rows,
+ * dev_index, dev_count, dev_visible, dev_hidden, in this order, that is not device memory of the swarm's device large enough for its
+ * rows. */
+int mrs_swarm_nearest_visible_device(mrs_swarm_t* s, int32_t first, int32_t count, int32_t k, double radius, uint32_t fields, void* dev_rows,
+                                     int32_t dtype, int32_t stride, int32_t* dev_index, int32_t index_stride, int32_t* dev_count,
+                                     int32_t* dev_visible, int32_t* dev_hidden, void* ext_stream);
+
 /* ---- collision worlds: several scenes in one swarm that do not see each other (per-sample horizons of a sampling-based planner) ----
  * A world is a 32-bit label per UAV, 0 for every UAV until a setter says otherwise.  Two UAVs interact through the collision pass
  * (mrs_swarm_handle_collisions, mrs_swarm_tick_n, the tick rollouts), or appear in each other's rows of mrs_swarm_nearest_device, only

@@ -26,6 +26,7 @@ UNITS = [
     ("obstacle_contact.hip", "off"),  # off: thr = (arm_length + prop_radius) + margin and the same signed distances, bit for bit against numpy
     ("range_scan.hip", "off"),  # off: the ray tests of include/mrs_swarm.h literally, which a numpy restatement reproduces bit for bit
     ("range_scan_uavs.hip", "off"),  # off: the same ray tests for UAV spheres, bit for bit against the numpy restatement
+    ("nearest_visible.hip", "off"),  # off: d2, the sight line's direction and the same ray tests, bit for bit against the numpy restatement
     ("snapshot.hip", "off"),  # no arithmetic (records are copied bit for bit); off like every other unit
     # host side: C ABI, single-GPU tick, sharded tick, the three transports (transport_local and transport_peer hold the kernels of
     # their collectives, the others none)
@@ -36,7 +37,7 @@ UNITS = [
     ("transport_local.hip", "off"),
     ("transport_peer.hip", "off"),
 ]
-DEPS = ["step_device.inc", "rollout_device.inc", "rollout_rate_device.inc", "rollout_cost_device.inc", "rollout_tick_device.inc", "collide_device.inc", "collide_work.h", "swarm_layout.h", "pose_math.h", "obs_row.h", "hip_owned.h", "host_internal.h", "sharded_protocol.h", "obstacle_grid.h", "obstacle_set.h", "obstacle_contact.h", "range_scan_math.h", "range_scan_common.h", "nn_hash.h", os.path.join("..", "..", "include", "mrs_swarm.h")]
+DEPS = ["step_device.inc", "rollout_device.inc", "rollout_rate_device.inc", "rollout_cost_device.inc", "rollout_tick_device.inc", "collide_device.inc", "collide_work.h", "swarm_layout.h", "pose_math.h", "obs_row.h", "hip_owned.h", "host_internal.h", "sharded_protocol.h", "obstacle_grid.h", "obstacle_set.h", "obstacle_contact.h", "range_scan_math.h", "range_scan_common.h", "nn_hash.h", "nn_slot.h", "sight_math.h", os.path.join("..", "..", "include", "mrs_swarm.h")]
 
 
 def _hipcc():

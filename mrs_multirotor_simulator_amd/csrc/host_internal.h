@@ -8,7 +8,7 @@
 //   obstacles.hip         C ABI + kernels of the static obstacles (the set, the one routine that makes a cached grid current,
 //                         nearest-obstacle rows, the obstacle cost); obstacle_grid.h holds its pure functions, the kernels' view of a
 //                         grid and the cell walk (walk_cell) that both scans call (tested without a GPU: tests/cpp/obstacle_grid_test.cpp,
-//                         tests/cpp/obstacle_walk_test.cpp); obstacle_set.h the set, its three cache entries and the fill of that view
+//                         tests/cpp/obstacle_walk_test.cpp); obstacle_set.h the set, its four cache entries and the fill of that view
 //   obstacle_contact.hip  C ABI + kernel of the obstacle contacts (which UAVs touch an obstacle; the crash mark); obstacle_contact.h holds
 //                         its pure functions (tested without a GPU: tests/cpp/obstacle_contact_math_test.cpp)
 //   range_scan.hip        C ABI + kernel of the range scans (the beam pattern, the scan); range_scan_math.h holds its pure functions
@@ -16,6 +16,9 @@
 //                         unit, once: argument block, beam set-up, obstacle pass, ground pass, stores, argument checks and fill
 //   range_scan_uavs.hip   C ABI + kernel of the range scans that also see the other UAVs of the observer's world (the hash of nearest.hip,
 //                         read through nn_hash.h, joined with the shared scan code of range_scan_common.h)
+//   nearest_visible.hip   C ABI + kernel of the line-of-sight neighbours (the hash of nearest.hip, the obstacle cell walk and the ray tests
+//                         of the scans; sight_math.h holds its pure functions, tested without a GPU: tests/cpp/sight_math_test.cpp;
+//                         nn_slot.h the slot text it shares with nearest.hip)
 //   snapshot.hip          C ABI + kernels of the state snapshots (save / indexed load of whole per-UAV records) for device-resident callers
 //   transport_rccl.hip    RCCL bound at run time (dlopen)
 //   transport_local.hip   in-process loopback group, caller-supplied all-gather, measurement stand-in (with its kernels)
@@ -509,6 +512,7 @@ int    launch_crash_cost(mrs_swarm* s, int first, int count, double* dev_cost, d
 int    obstacles_copy(mrs_swarm* dst, const mrs_swarm* src);  // the set of src into dst (clone)
 int    scan_grid(mrs_swarm* s, double max_range);              // the scans' cached obstacle grid (s->obst->scan) made current for max_range
 int    contact_grid(mrs_swarm* s, double R);                   // the contacts' cached obstacle grid (s->obst->contact) made current for R
+int    sight_grid(mrs_swarm* s, double radius);                // the sight lines' cached obstacle grid (s->obst->sight) made current for radius
 // ---- range_scan.hip ----
 int    scan_beams_copy(mrs_swarm* dst, const mrs_swarm* src);  // the beam pattern of src into dst (clone)
 int32_t       scan_beam_count(const mrs_swarm* s);             // beams of the pattern (0: none set)

@@ -25,11 +25,13 @@
 
 #include "host_internal.h"
 #include "nn_hash.h"
+#include "nn_slot.h"
 #include "pose_math.h"
 
 namespace {
 
-// the record, the cell coordinate, the bucket hash and the bucket starts: nn_hash.h (range_scan_uavs.hip probes the same hash)
+// the record, the cell coordinate, the bucket hash and the bucket starts: nn_hash.h (range_scan_uavs.hip probes the same hash);
+// the argument block NnArgs and the slot text put3 / write_slot: nn_slot.h (nearest_visible.hip writes the same rows)
 using namespace mrs_nn;
 
 constexpr int    NN_BLOCK   = 256;
@@ -37,20 +39,6 @@ constexpr int    SCAN_PER   = 8;                      // counts per lane of the 
 constexpr int    SCAN_CH    = NN_BLOCK * SCAN_PER;    // 2048 counts per chunk (1 << SCAN_LOG)
 static_assert(SCAN_CH == 1 << SCAN_LOG, "bucket_begin adds the chunk total of bucket b >> SCAN_LOG");
 constexpr int    kNnWidth[5] = {3, 3, 3, 3, 1};
-
-struct NnArgs {
-  const double* S;
-  int32_t       n, npad, first, count, k;
-  double        inv_edge, rr;
-  uint32_t      tmask, fields;
-  const int32_t *cnt, *start, *bsum;
-  const NnRec*  rec;
-  void*         rows;
-  int32_t       stride, width;  // width: elements of one slot
-  int32_t*      index;
-  int32_t       index_stride;
-  int32_t*      counts;
-};
 
 __device__ __forceinline__ bool finite3(double x, double y, double z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
@@ -148,51 +136,6 @@ __global__ void __launch_bounds__(NN_BLOCK) k_nn_scatter(const double* S, int n,
 }
 // (d2, j) orders before (e2, m)
 __device__ __forceinline__ bool nn_before(double d2, int j, double e2, int m) { return d2 < e2 || (d2 == e2 && j < m); }
-
-template <typename T>
-__device__ __forceinline__ void put3(T* o, double a, double b, double c) {
-  o[0] = (T)a;
-  o[1] = (T)b;
-  o[2] = (T)c;
-}
-
-// slot of neighbour j (d2 apart) of a UAV at xs with velocity vi and attitude R, or an empty slot (zeros)
-template <typename T>
-__device__ __forceinline__ void write_slot(T* o, const NnArgs& a, bool valid, int j, double d2, const double xs[3], const double vi[3],
-                                           const double R[9]) {
-  if (!valid) {
-    for (int e = 0; e < a.width; e++) o[e] = (T)0;
-    return;
-  }
-  const uint32_t f  = a.fields;
-  const size_t   np = (size_t)a.npad;
-  double         d[3], w[3];
-  if (f & (MRS_NN_REL_POS | MRS_NN_REL_POS_BODY)) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) d[c] = a.S[(size_t)(F_X + c) * np + j] - xs[c];
-  }
-  if (f & (MRS_NN_REL_VEL | MRS_NN_REL_VEL_BODY)) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) w[c] = a.S[(size_t)(F_V + c) * np + j] - vi[c];
-  }
-  if (f & MRS_NN_REL_POS) {
-    put3(o, d[0], d[1], d[2]);
-    o += 3;
-  }
-  if (f & MRS_NN_REL_POS_BODY) {
-    put3(o, body_velocity(R, d, 0), body_velocity(R, d, 1), body_velocity(R, d, 2));
-    o += 3;
-  }
-  if (f & MRS_NN_REL_VEL) {
-    put3(o, w[0], w[1], w[2]);
-    o += 3;
-  }
-  if (f & MRS_NN_REL_VEL_BODY) {
-    put3(o, body_velocity(R, w, 0), body_velocity(R, w, 1), body_velocity(R, w, 2));
-    o += 3;
-  }
-  if (f & MRS_NN_DIST) o[0] = (T)sqrt(d2);
-}
 
 // The search of k_nn_query once more, for k_nn_proximity.  k_nn_query keeps its own text: with this function inlined into it, hipcc
 // schedules it differently and nearest(NN_DIST, FP64) at 100 000 UAVs measured about 1 % slower than the parent's build, so the loop has

@@ -7,7 +7,7 @@
 // The steps of the walk are those of mrs_obst::walk_cell (obstacle_grid.h), which both range scans call, over the same GridView;
 // obst_search keeps them as a loop of its own because the callable form measured slower here ("One cell walk ...").
 // This unit also owns the set and ensure(), the one routine that makes a cached grid current, for the queries' entry and, through
-// mrs_host::scan_grid and mrs_host::contact_grid, for the scans' and the contacts'.
+// mrs_host::scan_grid, mrs_host::contact_grid and mrs_host::sight_grid, for the scans', the contacts' and the sight lines'.
 // The sorted insertion stays here, a text of its own beside nearest.hip's nn_probe: it orders by (sd, obstacle index) over a list this
 // kernel keeps, nn_probe by (d2, UAV index) inside a probe loop whose measured schedule a shared template would disturb — that unit
 // stays as it is.
@@ -226,7 +226,7 @@ int adopt(mrs_swarm* s, const mrs_obstacle_t* obstacles, int32_t count) {
     HIPCHK(hipStreamSynchronize(s->stream));
   }
   o->host.swap(fresh);
-  o->query.ok = o->scan.ok = o->contact.ok = false;  // (every cached grid served the old set)
+  o->query.ok = o->scan.ok = o->contact.ok = o->sight.ok = false;  // (every cached grid served the old set)
   return MRS_OK;
 }
 
@@ -292,6 +292,8 @@ int obstacles_copy(mrs_swarm* dst, const mrs_swarm* src) {
 int scan_grid(mrs_swarm* s, double max_range) { return ensure(s, set_of(s)->scan, max_range); }
 // the contacts' entry (s->obst->contact) made current for R, for the kernel of obstacle_contact.hip
 int contact_grid(mrs_swarm* s, double R) { return ensure(s, set_of(s)->contact, R); }
+// the sight lines' entry (s->obst->sight) made current for radius, for the kernel of nearest_visible.hip
+int sight_grid(mrs_swarm* s, double radius) { return ensure(s, set_of(s)->sight, radius); }
 }  // namespace mrs_host
 
 extern "C" {

@@ -140,6 +140,7 @@ ABI_SYMBOLS = [
     "mrs_swarm_set_scan_beams", "mrs_swarm_get_scan_beams", "mrs_swarm_range_scan_device",
     "mrs_swarm_range_scan_uavs_device",
     "mrs_swarm_obstacle_contacts_device",
+    "mrs_swarm_nearest_visible_device",
 ]
 
 # device-resident callers (mrs_swarm_*_device): row element types and the observation groups of mrs_swarm_gather_device, in bit order
@@ -410,6 +411,7 @@ def load_library():
         "mrs_swarm_range_scan_device": [vp, i32, i32, C.c_double, C.c_uint32, vp, i32, i32, vp, i32, vp],
         "mrs_swarm_range_scan_uavs_device": [vp, i32, i32, C.c_double, C.c_uint32, vp, i32, i32, vp, i32, vp, i32, vp],
         "mrs_swarm_obstacle_contacts_device": [vp, i32, i32, C.c_double, C.c_uint32, vp, vp, vp, vp, vp, C.c_double, vp],
+        "mrs_swarm_nearest_visible_device": [vp, i32, i32, i32, C.c_double, C.c_uint32, vp, i32, i32, vp, i32, vp, vp, vp, vp],
         "mrs_swarm_save_device": [vp, i32, i32, vp, vp],
         "mrs_swarm_load_device": [vp, i32, i32, vp, C.c_int64, vp, vp, vp],
         "mrs_swarm_rollout_device": [vp, i32, i32, i32, C.c_double, i32, vp, i32, i32, C.c_uint32, vp, i32, vp],
@@ -916,6 +918,12 @@ class Swarm:
         _check(_lib.mrs_swarm_nearest_device(self._h, int(first), int(count), int(k), C.c_double(float(radius)), C.c_uint32(int(fields)),
                                              dev_rows or None, int(dtype), int(stride), dev_index or None, int(index_stride), dev_count or None,
                                              ext_stream or None))
+
+    def nearest_visible_device(self, first, count, k, radius, fields, dev_rows, dtype, stride, dev_index, index_stride, dev_count, dev_visible,
+                               dev_hidden, ext_stream):
+        _check(_lib.mrs_swarm_nearest_visible_device(self._h, int(first), int(count), int(k), C.c_double(float(radius)), C.c_uint32(int(fields)),
+                                                     dev_rows or None, int(dtype), int(stride), dev_index or None, int(index_stride),
+                                                     dev_count or None, dev_visible or None, dev_hidden or None, ext_stream or None))
 
     def proximity_cost_device(self, first, count, k, radius, kind, weight, eps, dev_cost, accumulate, dev_found, ext_stream):
         _check(_lib.mrs_swarm_proximity_cost_device(self._h, int(first), int(count), int(k), C.c_double(float(radius)), int(kind),

@@ -690,6 +690,61 @@ def obstacle_contacts(swarm, margin=0.0, crash=False, first=0, count=None, hit=N
     return hit, index, sd, counts
 
 
+def nearest_visible(swarm, k, radius, fields=NN_REL_POS | NN_DIST, first=0, count=None, dtype=torch.float32, out=None, index=None, counts=None,
+                    visible=True, hidden=True):
+    """nearest() for observers that need a line of sight (mrs_swarm_nearest_visible_device): of the other UAVs within `radius` of each UAV
+    of [first, first + count), the k nearest that no static obstacle hides (set_obstacles), nearest first, ties to the lower index.  A
+    candidate at distance d > 0 in direction u is hidden when an obstacle that applies to the observer's world, within `radius` of the
+    observer on every axis, is entered by the beam from the observer along u strictly before d; coincident UAVs always see each other.
+    Hidden candidates take no slot: these are the first k visible ones, not the k nearest filtered afterwards.  Returns
+    (rows, index, counts, visible, hidden): rows, index and counts as nearest() returns them (counts = min(visible, k)); visible and
+    hidden int32 [count], the numbers of visible and of hidden candidates, not capped by k — each takes True (a new vector), a tensor to
+    fill, or None (not computed).  `out`, `index`, `counts`: used instead of new tensors when given (index=False / counts=False: not
+    computed); columns past the widths are left alone.  Without obstacles the first three are bit for bit those of nearest()."""
+    import math
+    try:
+        radius = float(radius)
+    except (TypeError, ValueError):
+        raise ValueError(f"radius must be a finite number > 0, got {radius!r}") from None
+    if not (math.isfinite(radius) and radius > 0):
+        raise ValueError(f"radius must be a finite number > 0, got {radius!r}")
+    count = _count(swarm, first, count)
+    if first < 0 or count < 0 or first + count > swarm.n:
+        raise ValueError(f"UAVs [{first}, {first + count}) do not fit a swarm of {swarm.n} UAVs")
+    width = nearest_width(fields, k)
+    dev = swarm.device()
+    tdev = torch.device("cuda", dev)
+    code, stride, rows_ptr = DTYPE_F32, 0, 0
+    if fields:
+        if out is None:
+            out = torch.empty((count, width), dtype=dtype, device=tdev)
+        code = _dtype_code(out.dtype)
+        stride = check_tensor(out, count, width, out.dtype, dev)
+        rows_ptr = out.data_ptr()
+    istride, index_ptr = 0, 0
+    if index is None:
+        index = torch.empty((count, k), dtype=torch.int32, device=tdev)
+    if index is False:
+        index = None
+    else:
+        istride = check_tensor(index, count, k, torch.int32, dev)
+        index_ptr = index.data_ptr()
+    counts, counts_ptr = _contact_vector(True if counts is None else counts, "counts", count, torch.int32, dev)
+    visible, visible_ptr = _contact_vector(visible, "visible", count, torch.int32, dev)
+    hidden, hidden_ptr = _contact_vector(hidden, "hidden", count, torch.int32, dev)
+    if not fields and all(t is None for t in (index, counts, visible, hidden)):
+        raise ValueError("nothing to do: ask for an output (fields, index, counts, visible or hidden)")
+    if count > 0:  # (an empty tensor has no address to hand over)
+        swarm.nearest_visible_device(first, count, k, radius, fields, rows_ptr, code, stride, index_ptr, istride, counts_ptr, visible_ptr,
+                                     hidden_ptr, _stream(dev))
+    rows = None
+    if fields:
+        rows = out[:, :width] if out.shape[1] > width else out
+    if index is not None and index.shape[1] > k:
+        index = index[:, :k]
+    return rows, index, counts, visible, hidden
+
+
 def scan_ring(n, elevation=0.0):
     """n unit vectors [n, 3] (numpy, FP64) evenly spaced in azimuth, beam 0 along +x, counter-clockwise seen from above, all at
     `elevation` radians above the xy plane: a planar lidar's pattern for set_scan_beams()."""
